@@ -14,6 +14,12 @@ before anything in it has touched a GPU, relays rank 0's JSON line and exits wit
 `--config {2,3,4,5}` picks one of BASELINE.json's configurations (numbered as in SURVEY.md 8(d): 2 = configs[1], the
 headline, and the default); `config.workload` names what was really run.
 
+A plain run sets up, warms up, times `--steps` steps and prints the line: `value`, `ms_per_step`, and the per-stage times and
+roofline of the timed steps themselves.  `--full` adds what takes runs of its own, after the timed region: the fused sink
+beside the default (stages.fused_sink), the drop-in stage, the host / file / gzip stages and the CPU baseline.
+`--dump-outputs DIR` writes what the last timed step computed (the kept records and the context index a caller of the path
+receives, rank 0's sample; with N > 1 also the merged histogram) as float64 .npy files, at most 64 MB in all.
+
 Prints ONE JSON line on rank 0.  The CPU oracle is used only for the cpu_baseline leg (never in the timed GPU path).
 """
 import argparse
@@ -143,6 +149,41 @@ def exchange_report(per_rank):
                     "before the driver's 8-GPU node (the pool's boxes have one)"}
 
 
+DUMP_BYTES = 63_000_000       # --dump-outputs: the record arrays' budget (the files stay under 64 MB with their headers)
+
+
+def u64_columns(words):
+    """uint64 words -> their low and high 32-bit halves as float64 columns: exact whatever k is"""
+    w = np.asarray(words, dtype=np.uint64)
+    return [(w & np.uint64(0xFFFFFFFF)).astype(np.float64), (w >> np.uint64(32)).astype(np.float64)]
+
+
+def dump_outputs(path, records, summary):
+    """Write `records` (name -> float64 array, one row per record) and `summary` (name -> small float64 array) as
+    path/<name>.npy.  Records beyond DUMP_BYTES are cut to a seeded sample of rows, in order, the same fraction of each
+    array: the same outputs give the same files from run to run."""
+    os.makedirs(path, exist_ok=True)
+    total = sum(a.nbytes for a in records.values())
+    for name, a in records.items():
+        if total > DUMP_BYTES:
+            n = int(a.shape[0] * (DUMP_BYTES / total))
+            a = a[np.sort(np.random.default_rng(0x7A7A).choice(a.shape[0], n, replace=False))]
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(a, dtype=np.float64))
+    for name, a in summary.items():
+        np.save(os.path.join(path, name + ".npy"), np.asarray(a, dtype=np.float64))
+
+
+def kept_outputs(cnt):
+    """what the drop-in API hands a caller after a counter's finalise: the kept records (40-byte hopo_elements) and the
+    index of their contexts, as float64 arrays"""
+    e = cnt.download_kept()
+    gi, gf = cnt.download_idx()
+    rec = np.stack(u64_columns(e["ctx0"]) + u64_columns(e["ctx1"]) + u64_columns(e["meta"])
+                   + [e[f].astype(np.float64) for f in ("read_offset", "loc_ref_id", "loc_pos", "loc_last")], axis=1)
+    return ({"kept_records": rec.reshape(len(e), 10), "context_index": np.stack([gi, gf], axis=1).astype(np.float64).reshape(len(gi), 2)},
+            {"summary": [len(e), len(gi), cnt.coverage]})
+
+
 def workload_label(args):
     """names what the arguments really are: a BASELINE.json configuration, or 'custom'"""
     for n, c in CONFIGS.items():
@@ -258,16 +299,22 @@ def main():
     ap.add_argument("--kmer", type=int, default=10)
     ap.add_argument("--min-tract", type=int, default=3)
     ap.add_argument("--min-coverage", type=int, default=5)
-    ap.add_argument("--cpu-reads", type=int, default=2_000_000, help="reads of the same sample timed on the CPU oracle")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region, also measure what takes runs of its own: stages.fused_sink, stages.dropin, the I/O stages, cpu_baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy (float64, at most 64 MB in all)")
+    ap.add_argument("--cpu-reads", type=int, default=2_000_000, help="reads of the same sample timed on the CPU oracle (--full)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without cpu_baseline")
     ap.add_argument("--config", type=int, choices=sorted(CONFIGS), default=None,
                     help="a BASELINE.json configuration (SURVEY 8d numbering; 2 = configs[1] = the headline = the default sizes)")
     ap.add_argument("--order-stream", action="store_true", help="the ordering step of a sample's finalise on a stream of its own (tjamd_counter_set_order_stream) instead of the scan's; measured: 0.832 against 0.824 ms per step, so not the default")
-    ap.add_argument("--no-io-stages", action="store_true", help="skip the stages measured after the timed region other than the drop-in's (stages.fused_sink, from_host, from_file, from_gzip, from_bgzf)")
+    ap.add_argument("--no-io-stages", action="store_true", help="--full without the stages measured after the timed region other than the drop-in's (stages.fused_sink, from_host, from_file, from_gzip, from_bgzf)")
     ap.add_argument("--io-reads", type=int, default=2_000_000, help="reads of the sample used for stages.from_host / from_file")
     ap.add_argument("--gz-reads", type=int, default=500_000, help="reads of the sample used for stages.from_gzip / from_bgzf")
     ap.add_argument("--rehearse", action="store_true", help="launch plumbing only, no GPU work (CPU tests)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
     if args.config is not None:
         for kk, vv in CONFIGS[args.config].items():
             if kk != "label":
@@ -463,6 +510,14 @@ def main():
         tmax = torch.tensor([dt], dtype=torch.float64)
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
         dt = float(tmax.item())
+    if args.dump_outputs and rank == 0:
+        # the last timed step's outcome (c: the counter of the last sample; gathered: the union of its exchange)
+        recs, summ = kept_outputs(c)
+        if gathered is not None:
+            keys = gathered[0].cpu().numpy().view(np.uint64).reshape(-1, 3)
+            recs["union_records"] = np.stack(u64_columns(keys[:, 0]) + u64_columns(keys[:, 1]) + u64_columns(keys[:, 2]), axis=1).reshape(len(keys), 6)
+            recs["union_counts"] = gathered[1].cpu().numpy().astype(np.float64)
+        dump_outputs(args.dump_outputs, recs, summ)
 
     kept = c.n_kept
     scan_avg = float(np.mean(scan_ms))
@@ -542,7 +597,7 @@ def main():
                                       "note": "record log -> hash buckets, between the scan and the finalise; TATAJUBA_AMD_SINK=fused makes the scan kernel partition "
                                               "by itself instead (rounds 1-3: a shorter step, the scan kernel at a third of the HBM peak)"}
 
-    if rank == 0 and world == 1 and uses_log and "TATAJUBA_AMD_SINK" not in os.environ and not args.no_io_stages:
+    if args.full and rank == 0 and world == 1 and uses_log and "TATAJUBA_AMD_SINK" not in os.environ and not args.no_io_stages:
         # The other design, on the same box in the same process, outside the timed region: the scan kernel partitions its
         # records by itself (rounds 1-3) -- a shorter step, a scan kernel at a third of the HBM peak.  Same loop as the timed
         # one (two counters in turn on the stream), a few steps.
@@ -587,7 +642,7 @@ def main():
                                                "between the two designs (DESIGN.md 3.1c); `value` and `roofline` are the default's"}
         for cc in alt:
             cc.close()
-    if rank == 0 and world == 1:
+    if args.full and rank == 0 and world == 1:
         # what a C caller of the drop-in API gets per sample once its reads are in HBM: the scan, the whole of
         # finalise_hopo_counter's device work AND the copy of the histogram into hc->elem (24-byte records widened to the
         # 40-byte hopo_element on the host) + the index arrays -- the part of finalise_hopo_counter (csrc/hopo_host.c) that a
@@ -607,9 +662,9 @@ def main():
                                    "note": "HBM-resident stream -> scan + finalise + histogram copied into 40-byte hopo_elements on the host "
                                            "+ index arrays (what finalise_hopo_counter hands a C caller), synchronous, one counter"}
         cd.close()
-    if rank == 0 and world == 1 and not args.no_io_stages:
+    if args.full and rank == 0 and world == 1 and not args.no_io_stages:
         out["stages"].update(io_stages(tj, host, args, k, m, L))
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         from oracle import orc                             # checker / baseline only
         n_cpu = min(args.cpu_reads, args.reads)
         sample = host[: n_cpu * (L + 1)] if args.read_len_max <= L else host

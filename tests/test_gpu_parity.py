@@ -1380,13 +1380,13 @@ def test_scan_windows_batch_matches_single_calls_and_is_fast():
 
 @pytest.mark.gpu
 def test_bench_line_keeps_its_contract_on_a_small_sample():
-    """bench.py as the driver runs it (one GPU, a child process), on a sample small enough for a test: the one JSON line
-    carries the contract's keys, the roofline and the CPU baseline objects, the partition stage of the default sink and the
-    fused sink measured beside it -- on the same histogram"""
+    """bench.py --full as the driver runs it (one GPU, a child process), on a sample small enough for a test: the one JSON
+    line carries the contract's keys, the roofline and the CPU baseline objects, the partition stage of the default sink and
+    the fused sink measured beside it -- on the same histogram"""
     import json, subprocess, sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {kk: vv for kk, vv in os.environ.items() if kk not in ("TATAJUBA_AMD_SINK", "TATAJUBA_AMD_FAST")}
-    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--reads", "400000", "--steps", "3", "--warmup", "1", "--cpu-reads", "50000",
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--full", "--reads", "400000", "--steps", "3", "--warmup", "1", "--cpu-reads", "50000",
                         "--io-reads", "50000", "--gz-reads", "20000"], capture_output=True, text=True, cwd=root, env=env, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
@@ -1412,3 +1412,40 @@ def test_bench_line_keeps_its_contract_on_a_small_sample():
     assert st["dropin"]["kept_records"] == d["config"]["kept_records"]
     for io in ("from_host", "from_file", "from_gzip", "from_bgzf"):
         assert st[io]["reads_per_s"] > 0, io
+
+
+@pytest.mark.gpu
+def test_plain_bench_run_times_its_steps_and_dumps_what_the_last_one_computed(tmp_path):
+    """bench.py without --full: the timed steps and the line, none of the stages that take runs of their own; --steps is
+    the number of timed steps, and --dump-outputs writes the last step's histogram -- the oracle's on the same sample"""
+    import json, subprocess, sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = {kk: vv for kk, vv in os.environ.items() if kk not in ("TATAJUBA_AMD_SINK", "TATAJUBA_AMD_FAST")}
+    n, genome, k, m = 200000, 5_000_000, 10, 3
+    out = tmp_path / "out"
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--reads", str(n), "--steps", "4", "--warmup", "1",
+                        "--dump-outputs", str(out)], capture_output=True, text=True, cwd=root, env=env, timeout=300)
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
+    assert len(lines) == 1
+    d = json.loads(lines[0])
+    assert d["steps"] == 4 and d["warmup"] == 1 and d["unit"] == "reads/s" and d["higher_is_better"] is True and d["dtype"] == "u8/u64"
+    assert d["ms_per_step"] > 0 and abs(d["value"] - n * 4 / (d["ms_per_step"] * 4e-3)) < 1e-6 * d["value"]
+    assert "cpu_baseline" not in d and not {"fused_sink", "dropin", "from_host", "from_file", "from_gzip", "from_bgzf"} & set(d["stages"])
+    assert sorted(os.listdir(out)) == ["context_index.npy", "kept_records.npy", "summary.npy"]
+    rec, idx, summ = (np.load(out / f) for f in ("kept_records.npy", "context_index.npy", "summary.npy"))
+    assert rec.dtype == idx.dtype == summ.dtype == np.float64
+    assert rec.shape == (d["config"]["kept_records"], 10) and len(rec) > 0
+    e = np.zeros(len(rec), dtype=tj.ELEM_DTYPE)
+    for j, f in enumerate(("ctx0", "ctx1", "meta")):
+        e[f] = rec[:, 2 * j].astype(np.uint64) | (rec[:, 2 * j + 1].astype(np.uint64) << np.uint64(32))
+    for j, f in enumerate(("read_offset", "loc_ref_id", "loc_pos", "loc_last"), 6):
+        e[f] = rec[:, j].astype(np.int32)
+    o = orc.Oracle(k)
+    o.scan_stream(tj.synth_stream(n, 150, genome), m)         # bench.py's sample on one GPU (its seeds are the defaults)
+    o.finalise(1, 5)
+    assert e.tobytes() == o.elems().tobytes()
+    ei, ef = o.idx()
+    assert idx.shape == (len(ei), 2) and (idx[:, 0] == ei).all() and (idx[:, 1] == ef).all()
+    assert summ.tolist() == [len(e), len(ei), o.c.coverage]
+    o.close()
