@@ -178,6 +178,51 @@ long tjamd_allgather_histograms (tjamd_counter *c, tjamd_comm *comm, const void 
  * d_tract_id (device, may be NULL) and / or h_tract_id (host, may be NULL) receive int32[n].  Returns the number of ids. */
 long tjamd_tract_ids (tjamd_counter *c, const void *d_keys, long n, int *d_tract_id, int *h_tract_id);
 
+/* Per-tract statistics across the samples of a merged union, and the tracts that vary between them (reference:
+ * describe_statistics_for_genome_set, src/genome_set.c:619-678, with descriptive_stats_of_histogram :738-766,
+ * relative_difference_of_vector :768-779 and update_descriptive_stats_for_this_trait :692-710).
+ * A tract is a run of union rows with one tract id; a sample's histogram in it is the tract's rows as (signed 10-bit length,
+ * the sample's count), one bar per row; the sample is present if any of them has a non-zero count.  Per (tract, present
+ * sample), in this order (absent samples: 0 in all five):
+ *   avg length = sum count * length / integral       modal freq = max count / integral      prop coverage = integral / coverage
+ *   coverage per context = integral / n_context      entropy = -sum p ln p, p = count / integral
+ * integral = the sample's summed count; n_context = distinct contexts (base, ctx0, ctx1) among its non-zero rows (1 for the
+ * ids of tjamd_tract_ids), counted as changes of context from one non-zero row to the next: the rows of one context must be
+ * contiguous within a tract, as they are in the sorted union of tjamd_merge_samples; modal length = the length of the
+ * highest count, the larger length on a tie. */
+#define TJAMD_N_TRACT_STATS 5
+enum { TJAMD_STAT_AVG_LENGTH, TJAMD_STAT_MODAL_FREQ, TJAMD_STAT_PROP_COVERAGE, TJAMD_STAT_COVERAGE_PER_CONTEXT, TJAMD_STAT_ENTROPY };
+/* one tract: its rows [first, first + n_rows) of the union, present samples, the variable flag, and per statistic the
+ * max - min over the present samples (0 if that max <= DBL_MIN).  56 bytes. */
+typedef struct { int first, n_rows, n_present, variable; double reldiff[TJAMD_N_TRACT_STATS]; } tjamd_tract_summary;
+
+/* Summaries of all tracts and the ascending ids of the variable ones.  A tract is variable if n_present < n_samples, or if
+ * reldiff[avg length] + reldiff[modal freq] + reldiff[entropy] > 1e-5, or if a reference length > 0 was given for it and a
+ * present sample's modal length differs from it.
+ *   d_keys        device tjamd_record[n_union], d_counts device int32[n_union * n_samples] (as tjamd_merge_samples writes them)
+ *   n_samples     1 ... 4096
+ *   d_tract_id    device int32[n_union]: caller's tract ids (0 on the first row, up by 0 or 1 per row; refused otherwise);
+ *                 NULL = the context-keyed ids of tjamd_tract_ids, computed here
+ *   coverage      host int32[n_samples]: each sample's coverage (tjamd_coverage of its counter)
+ *   d_ref_length  device int32[n_tracts]: a reference tract length per tract (<= 0: none), or NULL (no such test)
+ *   d_summary     device tjamd_tract_summary[capacity]; d_var device int32[capacity] (may be NULL): variable tract ids
+ *   n_var         host (may be NULL): number of variable tracts
+ * Runs on the counter's stream, synchronises at the end.  Returns n_tracts, or a negative TJAMD_ERR_* (tjamd_last_error). */
+long tjamd_tract_stats (tjamd_counter *c, const void *d_keys, const void *d_counts, long n_union, int n_samples,
+                        const int *d_tract_id, const int *coverage, const int *d_ref_length,
+                        tjamd_tract_summary *d_summary, int *d_var, long capacity, long *n_var);
+/* The per-sample values of a list of tracts (typically d_var), in the reference's samples_per_trait layout
+ * (src/genome_set.c:696-698), recomputed from the union without a table of all tracts:
+ *   d_summary     device tjamd_tract_summary[n_tracts] from tjamd_tract_stats (first and n_rows are read)
+ *   d_list        device int32[n_list]: tract ids, each in [0, n_tracts) (refused otherwise)
+ *   d_values      device double[n_list][TJAMD_N_TRACT_STATS][n_samples]
+ *   d_modal_len   device int32[n_list][n_samples] (may be NULL): modal length, 0 if absent
+ *   d_n_context   device int32[n_list][n_samples] (may be NULL): n_context, 0 if absent
+ * Other arguments as for tjamd_tract_stats.  Synchronises at the end.  Returns n_list, or a negative TJAMD_ERR_*. */
+long tjamd_tract_sample_stats (tjamd_counter *c, const void *d_keys, const void *d_counts, long n_union, int n_samples,
+                               const int *coverage, const tjamd_tract_summary *d_summary, long n_tracts, const int *d_list, long n_list,
+                               double *d_values, int *d_modal_len, int *d_n_context);
+
 /* within-sample grouping of near-identical contexts on a finalised counter (reference: new_genomic_context_list,
  * src/context_histogram.c:245-270 with the Hamming distance of :25-48, on the finalised array's own order; no
  * Levenshtein retry).  group_of: int32[kept_count] (host, may be NULL); groups: one entry per group (host, may be NULL):
@@ -212,6 +257,7 @@ int    tjamd_counter_uses_log (const tjamd_counter *c);  /* 1: k <= 12 and the s
 double tjamd_last_partition_ms (tjamd_counter *c);  /* partition_log_kernel behind the last scan launch (k <= 12); 0 if the scan kernel partitioned by itself */
 double tjamd_last_finalise_ms (tjamd_counter *c);
 double tjamd_last_merge_ms (tjamd_counter *c);      /* kernels of the last tjamd_merge_samples on this counter */   /* whole device finalise of the last tjamd_finalise call */
+double tjamd_last_tract_stats_ms (tjamd_counter *c); /* the last tjamd_tract_stats on this counter, first launch to last (host waits included) */
 long   tjamd_last_scan_launches (tjamd_counter *c);
 /* finalises of this counter whose device-side sizing of the ordering step had read a stale kept count (checked against the
  * count at the next kernel boundary and repaired; expected to stay 0) */

@@ -23,6 +23,11 @@ CONTEXT_GROUP_DTYPE = np.dtype([("first", "<i4"), ("n_elem", "<i4"), ("n_context
                                 ("modal_len", "<i4"), ("modal_freq", "<i4"), ("integral", "<i8")])
 LENGTH_FREQ_DTYPE = np.dtype([("length", "<i4"), ("freq", "<i4")])
 LOCATED_DTYPE = np.dtype([("ctx0", "<u8"), ("ctx1", "<u8"), ("meta", "<u8"), ("pos", "<u8")])
+# tjamd_tract_summary (include/tatajuba_amd.h): reldiff in the order of TJAMD_STAT_* (avg length, modal freq, prop coverage,
+# coverage per context, entropy)
+N_TRACT_STATS = 5
+TRACT_SUMMARY_DTYPE = np.dtype([("first", "<i4"), ("n_rows", "<i4"), ("n_present", "<i4"), ("variable", "<i4"), ("reldiff", "<f8", (N_TRACT_STATS,))])
+assert TRACT_SUMMARY_DTYPE.itemsize == 56
 
 
 class TatajubaAmdError(RuntimeError):
@@ -90,7 +95,7 @@ EXPORTS = [
     "tjamd_download_raw", "tjamd_undefined_runs", "tjamd_upload_raw", "tjamd_finalise", "tjamd_finalise_begin", "tjamd_finalise_end", "tjamd_kept_count",
     "tjamd_n_idx", "tjamd_coverage", "tjamd_download_kept", "tjamd_download_idx", "tjamd_kept_device_ptr",
     "tjamd_merge_samples", "tjamd_gather_histograms", "tjamd_peer_access_report", "tjamd_comm_unique_id", "tjamd_comm_create", "tjamd_comm_destroy",
-    "tjamd_comm_set_stream", "tjamd_comm_rank", "tjamd_comm_world", "tjamd_comm_collectives", "tjamd_comm_count", "tjamd_comm_last_exchange", "tjamd_last_merge_ms", "tjamd_allgather_histograms", "tjamd_tract_ids", "tjamd_group_contexts", "tjamd_context_histograms", "tjamd_scan_windows", "tjamd_thread_cleanup", "tjamd_last_scan_ms", "tjamd_last_partition_ms", "tjamd_counter_uses_log", "tjamd_last_finalise_ms", "tjamd_last_scan_launches", "tjamd_plan_mismatches",
+    "tjamd_comm_set_stream", "tjamd_comm_rank", "tjamd_comm_world", "tjamd_comm_collectives", "tjamd_comm_count", "tjamd_comm_last_exchange", "tjamd_last_merge_ms", "tjamd_allgather_histograms", "tjamd_tract_ids", "tjamd_tract_stats", "tjamd_tract_sample_stats", "tjamd_last_tract_stats_ms", "tjamd_group_contexts", "tjamd_context_histograms", "tjamd_scan_windows", "tjamd_thread_cleanup", "tjamd_last_scan_ms", "tjamd_last_partition_ms", "tjamd_counter_uses_log", "tjamd_last_finalise_ms", "tjamd_last_scan_launches", "tjamd_plan_mismatches",
     "tjamd_synth_stream", "tjamd_read_file_stream",
     # include/tatajuba_context.h
     "new_genomic_context_list", "del_genomic_context_list", "del_context_histogram",
@@ -183,6 +188,13 @@ def lib():
     L.tjamd_gather_histograms.restype = C.c_long
     L.tjamd_gather_histograms.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_long)]
     L.tjamd_tract_ids.restype = C.c_long; L.tjamd_tract_ids.argtypes = [C.c_void_p, C.c_void_p, C.c_long, C.c_void_p, C.c_void_p]
+    L.tjamd_tract_stats.restype = C.c_long
+    L.tjamd_tract_stats.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_long, C.c_int, C.c_void_p, C.POINTER(C.c_int), C.c_void_p,
+                                    C.c_void_p, C.c_void_p, C.c_long, C.POINTER(C.c_long)]
+    L.tjamd_tract_sample_stats.restype = C.c_long
+    L.tjamd_tract_sample_stats.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_long, C.c_int, C.POINTER(C.c_int), C.c_void_p, C.c_long,
+                                           C.c_void_p, C.c_long, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.tjamd_last_tract_stats_ms.restype = C.c_double; L.tjamd_last_tract_stats_ms.argtypes = [C.c_void_p]
     L.tjamd_group_contexts.restype = C.c_long
     L.tjamd_group_contexts.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_long]
     L.new_genomic_context_list.restype = C.POINTER(GenomicContextListStruct); L.new_genomic_context_list.argtypes = [P]
@@ -520,6 +532,9 @@ class Counter:
         lib().tjamd_last_merge_ms.restype = C.c_double
         lib().tjamd_last_merge_ms.argtypes = [C.c_void_p]
         return lib().tjamd_last_merge_ms(self._h)
+
+    def last_tract_stats_ms(self):
+        return lib().tjamd_last_tract_stats_ms(self._h)
 
     def uses_log(self):
         lib().tjamd_counter_uses_log.restype = C.c_int

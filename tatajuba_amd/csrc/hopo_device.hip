@@ -30,6 +30,7 @@
 #include <string.h>
 #include <stdarg.h>
 #include <limits.h>
+#include <float.h>
 #include <algorithm>
 #include <vector>
 
@@ -4105,6 +4106,8 @@ struct tjamd_counter
   hipEvent_t ev_pa[TJ_PIECE_EVENTS] = {}, ev_pb[TJ_PIECE_EVENTS] = {};
   int n_piece_ev = 0;
   hipEvent_t ev_m0 = nullptr, ev_m1 = nullptr; bool merge_timed = false;   // around the kernels of the last tjamd_merge_samples
+  hipEvent_t ev_t0 = nullptr, ev_t1 = nullptr; bool tract_timed = false;   // around the last tjamd_tract_stats
+  DevBuf ts_cov, ts_aux;      // tjamd_tract_stats / tjamd_tract_sample_stats: the samples' coverages, error flag + last tract id
   bool part_timed = false;
   int fast_mode = 1;          // 1: scan_fast_kernel + the generic kernel on what it leaves; 0: generic kernel only; 2: fast kernel leaves everything (tests)
   u32 pool_chunks = 0, maxj = 0;
@@ -4200,6 +4203,7 @@ extern "C" tjamd_counter *tjamd_counter_create (int device, int kmer_size)
   HIPCHK_NULL (hipEventCreate (&c->ev_f0)); HIPCHK_NULL (hipEventCreate (&c->ev_f1));
   HIPCHK_NULL (hipEventCreate (&c->ev_p1));
   HIPCHK_NULL (hipEventCreate (&c->ev_m0)); HIPCHK_NULL (hipEventCreate (&c->ev_m1));
+  HIPCHK_NULL (hipEventCreate (&c->ev_t0)); HIPCHK_NULL (hipEventCreate (&c->ev_t1));
   HIPCHK_NULL (hipEventCreateWithFlags (&c->ev_done, hipEventDisableTiming));
   HIPCHK_NULL (hipEventCreateWithFlags (&c->ev_agg, hipEventDisableTiming));
   HIPCHK_NULL (hipStreamSynchronize (c->stream));
@@ -4212,7 +4216,8 @@ extern "C" void tjamd_counter_destroy (tjamd_counter *c)
   (void) hipSetDevice (c->device);
   (void) hipStreamSynchronize (c->stream);
   DevBuf *all[] = {&c->log, &c->logmeta, &c->pool, &c->table, &c->stage, &c->fix, &c->loc, &c->prefix, &c->rawlist, &c->slow, &c->alt, &c->hist, &c->flags, &c->segid, &c->headpos,
-                   &c->keep, &c->outpos, &c->scan_tmp, &c->kept, &c->idx_i, &c->idx_f, &c->cov, &c->bins, &c->binstart, &c->binctx, &c->ovf, &c->grp_jt, &c->grp_hist, &c->fine};
+                   &c->keep, &c->outpos, &c->scan_tmp, &c->kept, &c->idx_i, &c->idx_f, &c->cov, &c->bins, &c->binstart, &c->binctx, &c->ovf, &c->grp_jt, &c->grp_hist, &c->fine,
+                   &c->ts_cov, &c->ts_aux};
   for (DevBuf *b : all) release (*b);
   for (hipEvent_t ev : c->marks) if (ev) (void) hipEventDestroy (ev);
   if (c->d_state) (void) hipFree (c->d_state);
@@ -4226,6 +4231,8 @@ extern "C" void tjamd_counter_destroy (tjamd_counter *c)
   for (int i = 0; i < TJ_PIECE_EVENTS; i++) { if (c->ev_pa[i]) (void) hipEventDestroy (c->ev_pa[i]); if (c->ev_pb[i]) (void) hipEventDestroy (c->ev_pb[i]); }
   if (c->ev_m0) (void) hipEventDestroy (c->ev_m0);
   if (c->ev_m1) (void) hipEventDestroy (c->ev_m1);
+  if (c->ev_t0) (void) hipEventDestroy (c->ev_t0);
+  if (c->ev_t1) (void) hipEventDestroy (c->ev_t1);
   if (c->ev_f0) (void) hipEventDestroy (c->ev_f0);
   if (c->ev_f1) (void) hipEventDestroy (c->ev_f1);
   if (c->ev_done) (void) hipEventDestroy (c->ev_done);
@@ -5525,28 +5532,294 @@ __global__ void tract_id_kernel (const u32 *__restrict__ excl, const u32 *__rest
   for (long i = blockIdx.x * (long) blockDim.x + threadIdx.x; i < n; i += (long) gridDim.x * blockDim.x) id[i] = (int) (excl[i] + head[i]);
 }
 
+static int ensure_tract_id_scratch (tjamd_counter *c, long n)
+{
+  int rc = ensure (c->flags, (size_t) n * 4, c->stream);
+  if (!rc) rc = ensure (c->outpos, (size_t) n * 4, c->stream);
+  if (!rc) rc = ensure (c->segid, (size_t) n * 4, c->stream);
+  if (!rc) rc = ensure (c->scan_tmp, scan_tmp_words (n) * 4 + 64, c->stream);
+  return rc;
+}
+
+// queues the id pass on the counter's stream (scratch from ensure_tract_id_scratch); the number of heads lands in *total
+static int queue_tract_ids (tjamd_counter *c, const void *d_keys, long n, int *ids, u32 *total)
+{
+  hipLaunchKernelGGL (tract_head_kernel, dim3 (grid_for (n)), dim3 (256), 0, c->stream, (const u64 *) d_keys, n, (u32 *) c->flags.p);
+  int rc = exclusive_scan (c, (const u32 *) c->flags.p, (u32 *) c->outpos.p, n, total, (u32 *) c->scan_tmp.p, scan_tmp_words (n));
+  if (rc) return rc;
+  hipLaunchKernelGGL (tract_id_kernel, dim3 (grid_for (n)), dim3 (256), 0, c->stream, (const u32 *) c->outpos.p, (const u32 *) c->flags.p, n, ids);
+  if (hipGetLastError () != hipSuccess) return set_err (TJAMD_ERR_HIP, "tract id launch failed");
+  return TJAMD_OK;
+}
+
 extern "C" long tjamd_tract_ids (tjamd_counter *c, const void *d_keys, long n, int *d_tract_id, int *h_tract_id)
 {
   if (!c || n < 0 || (n && !d_keys)) return -set_err (TJAMD_ERR_ARG, "bad arguments");
   if (hipSetDevice (c->device) != hipSuccess) return -set_err (TJAMD_ERR_HIP, "hipSetDevice failed");
   if (n == 0) return 0;
-  int rc = ensure (c->flags, (size_t) n * 4, c->stream);
-  if (!rc) rc = ensure (c->outpos, (size_t) n * 4, c->stream);
-  if (!rc) rc = ensure (c->segid, (size_t) n * 4, c->stream);
-  if (!rc) rc = ensure (c->scan_tmp, scan_tmp_words (n) * 4 + 64, c->stream);
+  int rc = ensure_tract_id_scratch (c, n);
   if (rc) return -rc;
   u32 *total = (u32 *) c->scan_tmp.p + scan_tmp_words (n);
   int *ids = d_tract_id ? d_tract_id : (int *) c->segid.p;
-  hipLaunchKernelGGL (tract_head_kernel, dim3 (grid_for (n)), dim3 (256), 0, c->stream, (const u64 *) d_keys, n, (u32 *) c->flags.p);
-  rc = exclusive_scan (c, (const u32 *) c->flags.p, (u32 *) c->outpos.p, n, total, (u32 *) c->scan_tmp.p, scan_tmp_words (n));
+  rc = queue_tract_ids (c, d_keys, n, ids, total);
   if (rc) return -rc;
-  hipLaunchKernelGGL (tract_id_kernel, dim3 (grid_for (n)), dim3 (256), 0, c->stream, (const u32 *) c->outpos.p, (const u32 *) c->flags.p, n, ids);
-  if (hipGetLastError () != hipSuccess) return -set_err (TJAMD_ERR_HIP, "tract id launch failed");
   u32 nh = 0;
   if (hipMemcpyAsync (&nh, total, 4, hipMemcpyDeviceToHost, c->stream) != hipSuccess || hipStreamSynchronize (c->stream) != hipSuccess)
     return -set_err (TJAMD_ERR_HIP, "tract ids failed: %s", hipGetErrorString (hipGetLastError ()));
   if (h_tract_id && hipMemcpy (h_tract_id, ids, (size_t) n * 4, hipMemcpyDeviceToHost) != hipSuccess) return -set_err (TJAMD_ERR_HIP, "copy failed");
   return (long) nh + 1;
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// Per-tract statistics across samples and the variable tracts (reference: describe_statistics_for_genome_set,
+// src/genome_set.c:619-678; descriptive_stats_of_histogram :738-766; relative_difference_of_vector :768-779;
+// update_descriptive_stats_for_this_trait :692-710).  One segment of S = min (64, next_pow2 (n_samples)) lanes per tract,
+// 64 / S tracts per wavefront: a lane takes samples lane, lane + S, ..., so a count row is read as S contiguous words;
+// the min / max / presence over the samples are reduced across the segment with shuffles.  No atomics on values.
+
+struct TractSummary { int first, n_rows, n_present, variable; double reldiff[TJAMD_N_TRACT_STATS]; };
+static_assert (sizeof (TractSummary) == 56 && sizeof (TractSummary) == sizeof (tjamd_tract_summary), "tract summary layout");
+
+// tract starts from the ids: first row at the head, one past the last row (n_rows is made of it by tract_stats_kernel) at
+// the tail; err[0] |= 1 where the ids do not start at 0 or go up by something other than 0 or 1 (nothing is written then
+// outside [0, cap)); err[1] = the last row's id
+__global__ void tract_starts_kernel (const int *__restrict__ id, long n, long cap, TractSummary *__restrict__ sum, int *__restrict__ err)
+{
+  for (long i = blockIdx.x * (long) blockDim.x + threadIdx.x; i < n; i += (long) gridDim.x * blockDim.x) {
+    const int a = id[i];
+    const long step = i ? (long) a - (long) id[i - 1] : (a == 0 ? 1l : -1l);   // (row 0: id 0 and nothing else)
+    if (step != 0 && step != 1) { atomicOr (err, 1); continue; }
+    if (i == n - 1) err[1] = a;
+    if (a < 0 || a >= cap) continue;                    // (after a bad step elsewhere; or more tracts than the caller has room for)
+    if (step == 1) sum[a].first = (int) i;
+    if (i == n - 1 || id[i + 1] != a) sum[a].n_rows = (int) (i + 1);
+  }
+}
+
+// the five values of one (tract, sample) (descriptive_stats_of_histogram), its modal length and n_context; false if absent
+__device__ bool tract_sample_values (const u64 *__restrict__ keys, const int *__restrict__ counts, int ns, long first, long end, int s, int cov,
+                                     double *v, int &modal_len, int &n_ctx)
+{
+  long long integral = 0;
+  int maxc = 0, modal = 0, nctx = 0;
+  long prev = -1;
+  for (long r = first; r < end; r++) {
+    const int cnt = counts[r * ns + s];
+    if (cnt == 0) continue;
+    const u64 m = keys[3 * r + 2];
+    int len = (int) ((m >> TJ_META_LEN_SHIFT) & 0x3FFull);
+    if (len & 0x200) len -= 0x400;                      // signed 10-bit field, as group_histogram_kernel reads it
+    if (prev < 0 || keys[3 * r] != keys[3 * prev] || keys[3 * r + 1] != keys[3 * prev + 1] || ((m ^ keys[3 * prev + 2]) & 3ull)) nctx++;
+    if (prev < 0 || cnt > maxc || (cnt == maxc && len > modal)) { maxc = cnt; modal = len; }
+    integral += cnt;
+    prev = r;
+  }
+  modal_len = 0; n_ctx = 0;
+  for (int j = 0; j < TJAMD_N_TRACT_STATS; j++) v[j] = 0.0;
+  if (prev < 0) return false;
+  const double I = (double) integral;
+  double avg = 0.0, ent = 0.0;
+  for (long r = first; r <= prev; r++) {                // the reference's sums, bar by bar (:746-747, :758-761)
+    const int cnt = counts[r * ns + s];
+    if (cnt == 0) continue;
+    int len = (int) ((keys[3 * r + 2] >> TJ_META_LEN_SHIFT) & 0x3FFull);
+    if (len & 0x200) len -= 0x400;
+    avg += (double) ((long long) cnt * len) / I;
+    const double x = (double) cnt / I;
+    ent += x * log (x);
+  }
+  v[TJAMD_STAT_AVG_LENGTH] = avg;
+  v[TJAMD_STAT_MODAL_FREQ] = (double) maxc / I;
+  v[TJAMD_STAT_PROP_COVERAGE] = I / (double) cov;
+  v[TJAMD_STAT_COVERAGE_PER_CONTEXT] = I / (double) nctx;
+  v[TJAMD_STAT_ENTROPY] = -ent;
+  modal_len = modal; n_ctx = nctx;
+  return true;
+}
+
+__device__ __forceinline__ double dmax_ref (double a, double b) { return (a < b) ? b : a; }   // relative_difference_of_vector's comparisons
+__device__ __forceinline__ double dmin_ref (double a, double b) { return (a > b) ? b : a; }
+
+__global__ __launch_bounds__ (256)
+void tract_stats_kernel (const u64 *__restrict__ keys, const int *__restrict__ counts, long n_union, int ns, int S, const int *__restrict__ cov,
+                         const int *__restrict__ ref_len, TractSummary *__restrict__ sum, long n_bound, int *__restrict__ err, u32 *__restrict__ varflag)
+{ // n_bound: the tracts the caller has room for; the tracts there are (err[1] + 1) and whether the ids were good (err[0] == 0)
+  // come from tract_starts_kernel.  Every flag below n_bound is written (0 outside the tracts), so the scan behind is sound.
+  // err[2]: set here if a tract's rows lie outside the union.
+  const int lane = threadIdx.x & (S - 1);
+  const long segs_per_grid = (long) gridDim.x * (blockDim.x / S);
+  const long n_tracts = err[0] ? 0 : min ((long) err[1] + 1, n_bound);
+  for (long t = (blockIdx.x * (long) blockDim.x + threadIdx.x) / S; t < n_bound; t += segs_per_grid) {   // (uniform across a segment)
+    long first = 0, end = 0;                            // (tract_starts_kernel left one past the last row in n_rows)
+    if (t < n_tracts) { first = sum[t].first; end = sum[t].n_rows; }
+    if (t >= n_tracts || first < 0 || first >= end || end > n_union) {
+      if (lane == 0) { varflag[t] = 0u; if (t < n_tracts) atomicOr (err + 2, 1); }   // (rows outside the union: cannot happen after good ids)
+      continue;
+    }
+    const int ref = ref_len ? ref_len[t] : 0;
+    double mx[TJAMD_N_TRACT_STATS], mn[TJAMD_N_TRACT_STATS], v[TJAMD_N_TRACT_STATS];
+    for (int j = 0; j < TJAMD_N_TRACT_STATS; j++) { mx[j] = -FLT_MAX; mn[j] = FLT_MAX; }
+    int present = 0, off_ref = 0;
+    for (int s = lane; s < ns; s += S) {
+      int ml, nc;
+      if (!tract_sample_values (keys, counts, ns, first, end, s, cov[s], v, ml, nc)) continue;
+      present++;
+      if (ref > 0 && ml != ref) off_ref = 1;
+      for (int j = 0; j < TJAMD_N_TRACT_STATS; j++) { mx[j] = dmax_ref (mx[j], v[j]); mn[j] = dmin_ref (mn[j], v[j]); }
+    }
+    for (int o = 1; o < S; o <<= 1) {
+      present += __shfl_xor (present, o, S);
+      off_ref |= __shfl_xor (off_ref, o, S);
+      for (int j = 0; j < TJAMD_N_TRACT_STATS; j++) {
+        mx[j] = dmax_ref (mx[j], __shfl_xor (mx[j], o, S));
+        mn[j] = dmin_ref (mn[j], __shfl_xor (mn[j], o, S));
+      }
+    }
+    if (lane == 0) {
+      TractSummary o;
+      o.first = (int) first; o.n_rows = (int) (end - first); o.n_present = present;
+      for (int j = 0; j < TJAMD_N_TRACT_STATS; j++) o.reldiff[j] = (mx[j] > DBL_MIN) ? mx[j] - mn[j] : 0.0;
+      const double difference = o.reldiff[TJAMD_STAT_AVG_LENGTH] + o.reldiff[TJAMD_STAT_MODAL_FREQ] + o.reldiff[TJAMD_STAT_ENTROPY];
+      o.variable = (present < ns || difference > 1.e-5 || off_ref) ? 1 : 0;
+      sum[t] = o;
+      varflag[t] = (u32) o.variable;
+    }
+  }
+}
+
+__global__ void tract_var_scatter_kernel (const u32 *__restrict__ flag, const u32 *__restrict__ pos, long n, int *__restrict__ var)
+{
+  for (long i = blockIdx.x * (long) blockDim.x + threadIdx.x; i < n; i += (long) gridDim.x * blockDim.x)
+    if (flag[i]) var[pos[i]] = (int) i;
+}
+
+__global__ __launch_bounds__ (256)
+void tract_sample_stats_kernel (const u64 *__restrict__ keys, const int *__restrict__ counts, long n_union, int ns, int S, const int *__restrict__ cov,
+                                const TractSummary *__restrict__ sum, long n_tracts, const int *__restrict__ list, long n_list,
+                                double *__restrict__ values, int *__restrict__ modal_len, int *__restrict__ n_context, int *__restrict__ err)
+{
+  const int lane = threadIdx.x & (S - 1);
+  const long segs_per_grid = (long) gridDim.x * (blockDim.x / S);
+  for (long i = (blockIdx.x * (long) blockDim.x + threadIdx.x) / S; i < n_list; i += segs_per_grid) {
+    const int t = list[i];
+    long first = 0, end = 0;
+    if (t >= 0 && t < n_tracts) { first = sum[t].first; end = first + sum[t].n_rows; }
+    const bool ok = t >= 0 && t < n_tracts && first >= 0 && first <= end && end <= n_union;
+    if (!ok) { if (lane == 0) atomicOr (err, 1); first = end = 0; }
+    for (int s = lane; s < ns; s += S) {
+      double v[TJAMD_N_TRACT_STATS];
+      int ml, nc;
+      tract_sample_values (keys, counts, ns, first, end, s, cov[s], v, ml, nc);
+      for (int j = 0; j < TJAMD_N_TRACT_STATS; j++) values[(i * TJAMD_N_TRACT_STATS + j) * ns + s] = v[j];
+      if (modal_len) modal_len[i * ns + s] = ml;
+      if (n_context) n_context[i * ns + s] = nc;
+    }
+  }
+}
+
+static int tract_segment (int n_samples) { int S = 1; while (S < n_samples && S < 64) S <<= 1; return S; }
+static unsigned tract_grid (long n, int S) { return (unsigned) std::max<long> (1, std::min<long> ((n * S + 255) / 256, 65536)); }
+
+static int tract_args (const char *fn, const void *d_keys, const void *d_counts, long n_union, int n_samples, const int *coverage)
+{ // the checks both entries share, before any device call
+  if (n_union < 0) return set_err (TJAMD_ERR_ARG, "%s: n_union %ld < 0", fn, n_union);
+  if (n_union >= (1l << 31)) return set_err (TJAMD_ERR_CAPACITY, "%s: %ld union rows", fn, n_union);
+  if (n_samples < 1 || n_samples > 4096) return set_err (TJAMD_ERR_ARG, "%s: n_samples %d outside 1..4096", fn, n_samples);
+  if (n_union > 0 && (!d_keys || !d_counts)) return set_err (TJAMD_ERR_ARG, "%s: null union buffers", fn);
+  if (!coverage) return set_err (TJAMD_ERR_ARG, "%s: null coverage", fn);
+  return TJAMD_OK;
+}
+
+static int upload_coverage (tjamd_counter *c, const int *coverage, int n_samples)
+{
+  int rc = ensure (c->ts_cov, (size_t) n_samples * 4, c->stream);
+  if (!rc) rc = ensure (c->ts_aux, 64, c->stream);
+  if (rc) return rc;
+  HIPCHK (hipMemcpyAsync (c->ts_cov.p, coverage, (size_t) n_samples * 4, hipMemcpyHostToDevice, c->stream));
+  HIPCHK (hipMemsetAsync (c->ts_aux.p, 0, 64, c->stream));
+  return TJAMD_OK;
+}
+
+extern "C" long tjamd_tract_stats (tjamd_counter *c, const void *d_keys, const void *d_counts, long n_union, int n_samples,
+                                   const int *d_tract_id, const int *coverage, const int *d_ref_length,
+                                   tjamd_tract_summary *d_summary, int *d_var, long capacity, long *n_var)
+{
+  if (n_union > 0 && !d_summary) return -set_err (TJAMD_ERR_ARG, "tjamd_tract_stats: null summary buffer");
+  if (capacity < (n_union > 0 ? 1 : 0)) return -set_err (TJAMD_ERR_CAPACITY, "tjamd_tract_stats: capacity %ld for a union of %ld rows", capacity, n_union);
+  int rc = tract_args ("tjamd_tract_stats", d_keys, d_counts, n_union, n_samples, coverage);
+  if (rc) return -rc;
+  if (!c) return -set_err (TJAMD_ERR_ARG, "tjamd_tract_stats: null counter");
+  if (n_var) *n_var = 0;
+  if (hipSetDevice (c->device) != hipSuccess) return -set_err (TJAMD_ERR_HIP, "hipSetDevice failed");
+  if (n_union == 0) return 0;
+  // (no host round trip before the end: the kernels read the tract count and the id check from the device, and work on
+  // n_bound tracts at most; a count above the caller's capacity is reported at the end, nothing having been written past it)
+  const long n_bound = std::min (n_union, capacity);
+  rc = ensure_tract_id_scratch (c, n_union);
+  if (!rc) rc = upload_coverage (c, coverage, n_samples);
+  if (rc) return -rc;
+  c->tract_timed = false;                               // (a failed call leaves no timing behind)
+  (void) hipEventRecord (c->ev_t0, c->stream);
+  u32 *total = (u32 *) c->scan_tmp.p + scan_tmp_words (n_union);
+  const int *ids = d_tract_id;
+  if (!ids) {                                           // the context-keyed ids of tjamd_tract_ids, in c->segid
+    rc = queue_tract_ids (c, d_keys, n_union, (int *) c->segid.p, total);
+    if (rc) return -rc;
+    ids = (const int *) c->segid.p;
+  }
+  int *err = (int *) c->ts_aux.p;
+  hipLaunchKernelGGL (tract_starts_kernel, dim3 (grid_for (n_union)), dim3 (256), 0, c->stream, ids, n_union, n_bound, (TractSummary *) d_summary, err);
+  const int S = tract_segment (n_samples);
+  hipLaunchKernelGGL (tract_stats_kernel, dim3 (tract_grid (n_bound, S)), dim3 (256), 0, c->stream, (const u64 *) d_keys, (const int *) d_counts, n_union,
+                      n_samples, S, (const int *) c->ts_cov.p, d_ref_length, (TractSummary *) d_summary, n_bound, err, (u32 *) c->flags.p);
+  if (hipGetLastError () != hipSuccess) return -set_err (TJAMD_ERR_HIP, "tract stats launch failed");
+  rc = exclusive_scan (c, (const u32 *) c->flags.p, (u32 *) c->outpos.p, n_bound, total, (u32 *) c->scan_tmp.p, scan_tmp_words (n_bound));
+  if (rc) return -rc;
+  if (d_var) hipLaunchKernelGGL (tract_var_scatter_kernel, dim3 (grid_for (n_bound)), dim3 (256), 0, c->stream, (const u32 *) c->flags.p, (const u32 *) c->outpos.p,
+                                 n_bound, d_var);
+  if (hipGetLastError () != hipSuccess) return -set_err (TJAMD_ERR_HIP, "tract list launch failed");
+  (void) hipEventRecord (c->ev_t1, c->stream);
+  int h_err[3] = {0, 0, 0};
+  u32 nv = 0;
+  if (hipMemcpyAsync (h_err, err, 12, hipMemcpyDeviceToHost, c->stream) != hipSuccess || hipMemcpyAsync (&nv, total, 4, hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
+      hipStreamSynchronize (c->stream) != hipSuccess) return -set_err (TJAMD_ERR_HIP, "tract stats failed: %s", hipGetErrorString (hipGetLastError ()));
+  const long n_tracts = (long) h_err[1] + 1;
+  if (h_err[0] || h_err[2] || n_tracts < 1) return -set_err (TJAMD_ERR_ARG, "tjamd_tract_stats: tract ids must start at 0 and go up by 0 or 1 per row");
+  if (n_tracts > capacity) return -set_err (TJAMD_ERR_CAPACITY, "tjamd_tract_stats: %ld tracts, caller capacity %ld", n_tracts, capacity);
+  c->tract_timed = true;
+  if (n_var) *n_var = (long) nv;
+  return n_tracts;
+}
+
+extern "C" long tjamd_tract_sample_stats (tjamd_counter *c, const void *d_keys, const void *d_counts, long n_union, int n_samples,
+                                          const int *coverage, const tjamd_tract_summary *d_summary, long n_tracts, const int *d_list, long n_list,
+                                          double *d_values, int *d_modal_len, int *d_n_context)
+{
+  int rc = tract_args ("tjamd_tract_sample_stats", d_keys, d_counts, n_union, n_samples, coverage);
+  if (rc) return -rc;
+  if (n_list < 0 || n_tracts < 0 || n_tracts > n_union) return -set_err (TJAMD_ERR_ARG, "tjamd_tract_sample_stats: n_list %ld, n_tracts %ld (union of %ld rows)", n_list, n_tracts, n_union);
+  if (n_list > 0 && (!d_summary || !d_list || !d_values)) return -set_err (TJAMD_ERR_ARG, "tjamd_tract_sample_stats: null summary, list or values buffer");
+  if (!c) return -set_err (TJAMD_ERR_ARG, "tjamd_tract_sample_stats: null counter");
+  if (hipSetDevice (c->device) != hipSuccess) return -set_err (TJAMD_ERR_HIP, "hipSetDevice failed");
+  if (n_list == 0) return 0;
+  rc = upload_coverage (c, coverage, n_samples);
+  if (rc) return -rc;
+  const int S = tract_segment (n_samples);
+  int *err = (int *) c->ts_aux.p, h_err = 0;
+  hipLaunchKernelGGL (tract_sample_stats_kernel, dim3 (tract_grid (n_list, S)), dim3 (256), 0, c->stream, (const u64 *) d_keys, (const int *) d_counts, n_union,
+                      n_samples, S, (const int *) c->ts_cov.p, (const TractSummary *) d_summary, n_tracts, d_list, n_list, d_values, d_modal_len, d_n_context, err);
+  if (hipGetLastError () != hipSuccess || hipMemcpyAsync (&h_err, err, 4, hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
+      hipStreamSynchronize (c->stream) != hipSuccess) return -set_err (TJAMD_ERR_HIP, "tract sample stats failed: %s", hipGetErrorString (hipGetLastError ()));
+  if (h_err) return -set_err (TJAMD_ERR_ARG, "tjamd_tract_sample_stats: a listed tract id is outside [0, %ld) or its rows outside the union", n_tracts);
+  return n_list;
+}
+
+extern "C" double tjamd_last_tract_stats_ms (tjamd_counter *c)
+{
+  if (!c || !c->tract_timed) return -1.0;
+  float ms = 0.f;
+  if (hipSetDevice (c->device) != hipSuccess || hipEventSynchronize (c->ev_t1) != hipSuccess || hipEventElapsedTime (&ms, c->ev_t0, c->ev_t1) != hipSuccess) return -1.0;
+  return (double) ms;
 }
 
 // Peer access between two devices of this process, asked for once per ordered pair: with it hipMemcpyPeerAsync moves the

@@ -65,3 +65,39 @@ def merge_histograms_device(counter, records_u8, counts):
     if got < 0:
         raise TatajubaAmdError(_err())
     return keys[: got * RECORD_BYTES], mat[:got]
+
+
+def tract_stats_device(counter, keys_u8, mat, coverage, tract_ids=None, ref_length=None, per_sample=True):
+    """Per-tract statistics of a union on the GPU (tjamd_tract_stats, then tjamd_tract_sample_stats on the variable tracts):
+    keys_u8 / mat as merge_histograms_device returns them, coverage = each sample's coverage, tract_ids / ref_length = CUDA
+    int32 tensors (one id per union row / one length per tract) or None.  Returns a dict of numpy arrays: summary
+    (TRACT_SUMMARY_DTYPE[n_tracts]), variable (int32 ids, ascending) and, with per_sample, values (float64 [n_var, 5,
+    n_samples]), modal_len and n_context (int32 [n_var, n_samples])."""
+    import ctypes as C
+    import numpy as np
+    from .capi import lib, TatajubaAmdError, _err, TRACT_SUMMARY_DTYPE, N_TRACT_STATS
+    dev = mat.device
+    nu, ns = int(mat.shape[0]), int(mat.shape[1])
+    cov = (C.c_int * ns)(*[int(x) for x in coverage])
+    ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
+    summ = torch.empty(max(nu, 1) * TRACT_SUMMARY_DTYPE.itemsize, dtype=torch.uint8, device=dev)
+    var = torch.empty(max(nu, 1), dtype=torch.int32, device=dev)
+    nv = C.c_long()
+    torch.cuda.current_stream().synchronize()
+    nt = lib().tjamd_tract_stats(counter._h, ptr(keys_u8), ptr(mat), nu, ns, ptr(tract_ids), cov, ptr(ref_length), ptr(summ), ptr(var),
+                                 max(nu, 1), C.byref(nv))
+    if nt < 0:
+        raise TatajubaAmdError(_err())
+    out = {"summary": np.frombuffer(summ[: nt * TRACT_SUMMARY_DTYPE.itemsize].cpu().numpy().tobytes(), dtype=TRACT_SUMMARY_DTYPE),
+           "variable": var[: nv.value].cpu().numpy()}
+    if per_sample:
+        n = nv.value
+        vals = torch.zeros((max(n, 1), N_TRACT_STATS, ns), dtype=torch.float64, device=dev)
+        ml = torch.zeros((max(n, 1), ns), dtype=torch.int32, device=dev)
+        nc = torch.zeros((max(n, 1), ns), dtype=torch.int32, device=dev)
+        got = lib().tjamd_tract_sample_stats(counter._h, ptr(keys_u8), ptr(mat), nu, ns, cov, ptr(summ), nt, ptr(var), n,
+                                             ptr(vals), ptr(ml), ptr(nc))
+        if got < 0:
+            raise TatajubaAmdError(_err())
+        out.update(values=vals[:n].cpu().numpy(), modal_len=ml[:n].cpu().numpy(), n_context=nc[:n].cpu().numpy())
+    return out
