@@ -189,7 +189,8 @@ long tjamd_tract_ids (tjamd_counter *c, const void *d_keys, long n, int *d_tract
  * integral = the sample's summed count; n_context = distinct contexts (base, ctx0, ctx1) among its non-zero rows (1 for the
  * ids of tjamd_tract_ids), counted as changes of context from one non-zero row to the next: the rows of one context must be
  * contiguous within a tract, as they are in the sorted union of tjamd_merge_samples; modal length = the length of the
- * highest count, the larger length on a tie. */
+ * highest count, the larger length on a tie.  For tracts of several contexts (the grouped ids of tjamd_union_tracts),
+ * tjamd_union_tract_stats gives the reference's histogram h instead: one bar per length, summed over the contexts. */
 #define TJAMD_N_TRACT_STATS 5
 enum { TJAMD_STAT_AVG_LENGTH, TJAMD_STAT_MODAL_FREQ, TJAMD_STAT_PROP_COVERAGE, TJAMD_STAT_COVERAGE_PER_CONTEXT, TJAMD_STAT_ENTROPY };
 /* one tract: its rows [first, first + n_rows) of the union, present samples, the variable flag, and per statistic the
@@ -222,6 +223,60 @@ long tjamd_tract_stats (tjamd_counter *c, const void *d_keys, const void *d_coun
 long tjamd_tract_sample_stats (tjamd_counter *c, const void *d_keys, const void *d_counts, long n_union, int n_samples,
                                const int *coverage, const tjamd_tract_summary *d_summary, long n_tracts, const int *d_list, long n_list,
                                double *d_values, int *d_modal_len, int *d_n_context);
+
+/* Tracts across samples by grouping near-identical contexts of the union (N6; reference: the context histograms of
+ * new_genomic_context_list, src/context_histogram.c:245-286, as the tracts of new_g_tract_vector_from_genomic_context_list,
+ * src/genome_set.c:195-229, summarised by update_g_tract_summary_from_context_histogram / fill_g_tract_summary_tables
+ * :291-378 and selected by print_selected_g_tract_vector :380-434).
+ *   Grouping: the tracts are the context histograms that new_genomic_context_list's grouping forms on the union rows taken
+ *     in union order as one sample's finalised array: the max_distance_per_flank / levenshtein_distance rule of
+ *     tjamd_context_histograms, with the same edit-distance readings (TATAJUBA_AMD_EDIT_DISTANCE, read per call).
+ *   Row counts: a row's count is its exact total over the samples (the int64 sum of its d_counts row; the union key's
+ *     20-bit count field wraps and is not read).  The modal row (highest total, the first on a tie) carries the tract's
+ *     name in the indel retry.
+ *   Contiguity: a tract is a run of rows, so the ids start at 0 and go up by 0 or 1 per row (tjamd_tract_stats accepts them).
+ *   lev_distance: the largest edit distance that admitted a row through the retry (join type 2), measured between the row's
+ *     name and the modal name at that moment; 0 if no row joined that way (the reference's lev_distance).
+ *   A sample's histogram in a tract: its non-zero rows summed per length into bars, ordered by count (highest first), then
+ *     length (larger first): the reference's h.  The five values are descriptive_stats_of_histogram's (:738-766), its sums
+ *     taken bar by bar in h order; n_context = distinct contexts among the sample's non-zero rows; modal length = h's first.
+ *     reldiff is relative_difference_of_vector (:768-779) over the present samples.
+ *   variable: the rule of tjamd_tract_stats (d_ref_length included).  selected: the rule of print_selected_g_tract_vector:
+ *     n_present < n_samples, or lev_distance > 0, or reldiff of modal freq, avg length or entropy > 1e-6.
+ *   Known limitation: only rows that are neighbours in the sort order can join, as within a sample.  That covers variants in
+ *     the right flank and variants of the left flank far from the tract; a left-flank SNP next to the tract usually has
+ *     unrelated rows between its two alleles, and its two tracts stay apart.
+ * Names use the counter's k.  Every entry runs on the counter's stream, changes neither d_keys nor d_counts nor the
+ * counter's finalised state, and returns a count or a negative TJAMD_ERR_* (tjamd_last_error starts with its name). */
+typedef struct { int first, n_rows, n_context, mode, indel, lev_distance; long long integral; } tjamd_union_tract;   /* 32 bytes */
+/* one tract: rows [first, first + n_rows), present samples, both flags, lev_distance, and per statistic (TJAMD_STAT_*
+ * order) the max - min over the present samples (0 if that max <= DBL_MIN).  64 bytes. */
+typedef struct { int first, n_rows, n_present, variable, selected, lev_distance; double reldiff[TJAMD_N_TRACT_STATS]; } tjamd_union_tract_summary;
+
+/* Groups the union (d_keys / d_counts as tjamd_merge_samples writes them, n_samples 1 ... 4096):
+ *   d_tract_id   device int32[n_union]: each row's tract
+ *   d_join_type  device int32[n_union] (may be NULL): 0 opened its tract, 1 joined within the flank distance, 2 through the retry
+ *   d_tracts     device tjamd_union_tract[capacity]: first and n_rows, n_context (as tjamd_context_histograms counts them), mode
+ *                (the modal row, by totals), indel (a row joined through the retry), lev_distance, integral (summed totals)
+ * Distances must be >= 0; a capacity below the tracts found is refused (TJAMD_ERR_CAPACITY).  Waits twice: for the retry
+ * candidates and for the tract count, as tjamd_context_histograms does.  Returns n_tracts. */
+long tjamd_union_tracts (tjamd_counter *c, const void *d_keys, const void *d_counts, long n_union, int n_samples,
+                         int max_distance_per_flank, int levenshtein_distance,
+                         int *d_tract_id, int *d_join_type, tjamd_union_tract *d_tracts, long capacity);
+/* Summaries of the tracts of tjamd_union_tracts, the ascending ids of the variable ones (d_var, may be NULL; their number in
+ * *n_var) and of the selected ones (d_sel, may be NULL; *n_sel).  d_tracts must tile the union (first 0, each tract starting
+ * where the one before ends, the last ending at n_union): refused otherwise, from an error flag raised on the device.
+ * coverage and d_ref_length as for tjamd_tract_stats; d_summary, d_var, d_sel hold n_tracts entries.  Waits once, at the
+ * end.  Returns n_tracts. */
+long tjamd_union_tract_stats (tjamd_counter *c, const void *d_keys, const void *d_counts, long n_union, int n_samples,
+                              const tjamd_union_tract *d_tracts, long n_tracts, const int *coverage, const int *d_ref_length,
+                              tjamd_union_tract_summary *d_summary, int *d_var, long *n_var, int *d_sel, long *n_sel);
+/* The per-sample values of a list of tracts, as tjamd_tract_sample_stats lays them out ([n_list][TJAMD_N_TRACT_STATS]
+ * [n_samples]); d_modal_len, d_n_context and d_n_len (bars of h, 0 if absent) are int32[n_list][n_samples] and may be NULL.
+ * Waits once, at the end.  Returns n_list. */
+long tjamd_union_tract_sample_stats (tjamd_counter *c, const void *d_keys, const void *d_counts, long n_union, int n_samples,
+                                     const int *coverage, const tjamd_union_tract_summary *d_summary, long n_tracts,
+                                     const int *d_list, long n_list, double *d_values, int *d_modal_len, int *d_n_context, int *d_n_len);
 
 /* within-sample grouping of near-identical contexts on a finalised counter (reference: new_genomic_context_list,
  * src/context_histogram.c:245-270 with the Hamming distance of :25-48, on the finalised array's own order; no
@@ -258,6 +313,9 @@ double tjamd_last_partition_ms (tjamd_counter *c);  /* partition_log_kernel behi
 double tjamd_last_finalise_ms (tjamd_counter *c);
 double tjamd_last_merge_ms (tjamd_counter *c);      /* kernels of the last tjamd_merge_samples on this counter */   /* whole device finalise of the last tjamd_finalise call */
 double tjamd_last_tract_stats_ms (tjamd_counter *c); /* the last tjamd_tract_stats on this counter, first launch to last (host waits included) */
+double tjamd_last_union_tracts_ms (tjamd_counter *c);      /* the last tjamd_union_tracts, first launch to last (host waits included) */
+double tjamd_last_union_tract_stats_ms (tjamd_counter *c); /* the last tjamd_union_tract_stats, first launch to last */
+long   tjamd_last_union_tract_candidates (tjamd_counter *c); /* rows of the last tjamd_union_tracts that the indel retry was tried on first (-1: none yet) */
 long   tjamd_last_scan_launches (tjamd_counter *c);
 /* finalises of this counter whose device-side sizing of the ordering step had read a stale kept count (checked against the
  * count at the next kernel boundary and repaired; expected to stay 0) */

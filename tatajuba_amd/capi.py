@@ -28,6 +28,13 @@ LOCATED_DTYPE = np.dtype([("ctx0", "<u8"), ("ctx1", "<u8"), ("meta", "<u8"), ("p
 N_TRACT_STATS = 5
 TRACT_SUMMARY_DTYPE = np.dtype([("first", "<i4"), ("n_rows", "<i4"), ("n_present", "<i4"), ("variable", "<i4"), ("reldiff", "<f8", (N_TRACT_STATS,))])
 assert TRACT_SUMMARY_DTYPE.itemsize == 56
+# tjamd_union_tract / tjamd_union_tract_summary (include/tatajuba_amd.h): reldiff in TJAMD_STAT_* order, as above
+UNION_TRACT_DTYPE = np.dtype([("first", "<i4"), ("n_rows", "<i4"), ("n_context", "<i4"), ("mode", "<i4"), ("indel", "<i4"),
+                              ("lev_distance", "<i4"), ("integral", "<i8")])
+assert UNION_TRACT_DTYPE.itemsize == 32
+UNION_TRACT_SUMMARY_DTYPE = np.dtype([("first", "<i4"), ("n_rows", "<i4"), ("n_present", "<i4"), ("variable", "<i4"), ("selected", "<i4"),
+                                      ("lev_distance", "<i4"), ("reldiff", "<f8", (N_TRACT_STATS,))])
+assert UNION_TRACT_SUMMARY_DTYPE.itemsize == 64
 
 
 class TatajubaAmdError(RuntimeError):
@@ -95,7 +102,7 @@ EXPORTS = [
     "tjamd_download_raw", "tjamd_undefined_runs", "tjamd_upload_raw", "tjamd_finalise", "tjamd_finalise_begin", "tjamd_finalise_end", "tjamd_kept_count",
     "tjamd_n_idx", "tjamd_coverage", "tjamd_download_kept", "tjamd_download_idx", "tjamd_kept_device_ptr",
     "tjamd_merge_samples", "tjamd_gather_histograms", "tjamd_peer_access_report", "tjamd_comm_unique_id", "tjamd_comm_create", "tjamd_comm_destroy",
-    "tjamd_comm_set_stream", "tjamd_comm_rank", "tjamd_comm_world", "tjamd_comm_collectives", "tjamd_comm_count", "tjamd_comm_last_exchange", "tjamd_last_merge_ms", "tjamd_allgather_histograms", "tjamd_tract_ids", "tjamd_tract_stats", "tjamd_tract_sample_stats", "tjamd_last_tract_stats_ms", "tjamd_group_contexts", "tjamd_context_histograms", "tjamd_scan_windows", "tjamd_thread_cleanup", "tjamd_last_scan_ms", "tjamd_last_partition_ms", "tjamd_counter_uses_log", "tjamd_last_finalise_ms", "tjamd_last_scan_launches", "tjamd_plan_mismatches",
+    "tjamd_comm_set_stream", "tjamd_comm_rank", "tjamd_comm_world", "tjamd_comm_collectives", "tjamd_comm_count", "tjamd_comm_last_exchange", "tjamd_last_merge_ms", "tjamd_allgather_histograms", "tjamd_tract_ids", "tjamd_tract_stats", "tjamd_tract_sample_stats", "tjamd_last_tract_stats_ms", "tjamd_union_tracts", "tjamd_union_tract_stats", "tjamd_union_tract_sample_stats", "tjamd_last_union_tracts_ms", "tjamd_last_union_tract_stats_ms", "tjamd_last_union_tract_candidates", "tjamd_group_contexts", "tjamd_context_histograms", "tjamd_scan_windows", "tjamd_thread_cleanup", "tjamd_last_scan_ms", "tjamd_last_partition_ms", "tjamd_counter_uses_log", "tjamd_last_finalise_ms", "tjamd_last_scan_launches", "tjamd_plan_mismatches",
     "tjamd_synth_stream", "tjamd_read_file_stream",
     # include/tatajuba_context.h
     "new_genomic_context_list", "del_genomic_context_list", "del_context_histogram",
@@ -195,6 +202,17 @@ def lib():
     L.tjamd_tract_sample_stats.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_long, C.c_int, C.POINTER(C.c_int), C.c_void_p, C.c_long,
                                            C.c_void_p, C.c_long, C.c_void_p, C.c_void_p, C.c_void_p]
     L.tjamd_last_tract_stats_ms.restype = C.c_double; L.tjamd_last_tract_stats_ms.argtypes = [C.c_void_p]
+    L.tjamd_union_tracts.restype = C.c_long
+    L.tjamd_union_tracts.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_long, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_long]
+    L.tjamd_union_tract_stats.restype = C.c_long
+    L.tjamd_union_tract_stats.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_long, C.c_int, C.c_void_p, C.c_long, C.POINTER(C.c_int), C.c_void_p,
+                                          C.c_void_p, C.c_void_p, C.POINTER(C.c_long), C.c_void_p, C.POINTER(C.c_long)]
+    L.tjamd_union_tract_sample_stats.restype = C.c_long
+    L.tjamd_union_tract_sample_stats.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_long, C.c_int, C.POINTER(C.c_int), C.c_void_p, C.c_long,
+                                                 C.c_void_p, C.c_long, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.tjamd_last_union_tracts_ms.restype = C.c_double; L.tjamd_last_union_tracts_ms.argtypes = [C.c_void_p]
+    L.tjamd_last_union_tract_stats_ms.restype = C.c_double; L.tjamd_last_union_tract_stats_ms.argtypes = [C.c_void_p]
+    L.tjamd_last_union_tract_candidates.restype = C.c_long; L.tjamd_last_union_tract_candidates.argtypes = [C.c_void_p]
     L.tjamd_group_contexts.restype = C.c_long
     L.tjamd_group_contexts.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_long]
     L.new_genomic_context_list.restype = C.POINTER(GenomicContextListStruct); L.new_genomic_context_list.argtypes = [P]
@@ -535,6 +553,15 @@ class Counter:
 
     def last_tract_stats_ms(self):
         return lib().tjamd_last_tract_stats_ms(self._h)
+
+    def last_union_tracts_ms(self):
+        return lib().tjamd_last_union_tracts_ms(self._h)
+
+    def last_union_tract_stats_ms(self):
+        return lib().tjamd_last_union_tract_stats_ms(self._h)
+
+    def last_union_tract_candidates(self):
+        return int(lib().tjamd_last_union_tract_candidates(self._h))
 
     def uses_log(self):
         lib().tjamd_counter_uses_log.restype = C.c_int

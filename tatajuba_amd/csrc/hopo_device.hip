@@ -4108,6 +4108,10 @@ struct tjamd_counter
   hipEvent_t ev_m0 = nullptr, ev_m1 = nullptr; bool merge_timed = false;   // around the kernels of the last tjamd_merge_samples
   hipEvent_t ev_t0 = nullptr, ev_t1 = nullptr; bool tract_timed = false;   // around the last tjamd_tract_stats
   DevBuf ts_cov, ts_aux;      // tjamd_tract_stats / tjamd_tract_sample_stats: the samples' coverages, error flag + last tract id
+  hipEvent_t ev_u0 = nullptr, ev_u1 = nullptr, ev_v0 = nullptr, ev_v1 = nullptr;   // around the last tjamd_union_tracts / tjamd_union_tract_stats
+  bool union_timed = false, union_stats_timed = false;
+  long union_cand = -1;       // retry candidates of the last tjamd_union_tracts
+  DevBuf ut_tot, ut_lev, ut_fb, ut_slots;   // union tracts: exact row totals, admitted edit distances, fallback flags, global bars
   bool part_timed = false;
   int fast_mode = 1;          // 1: scan_fast_kernel + the generic kernel on what it leaves; 0: generic kernel only; 2: fast kernel leaves everything (tests)
   u32 pool_chunks = 0, maxj = 0;
@@ -4204,6 +4208,8 @@ extern "C" tjamd_counter *tjamd_counter_create (int device, int kmer_size)
   HIPCHK_NULL (hipEventCreate (&c->ev_p1));
   HIPCHK_NULL (hipEventCreate (&c->ev_m0)); HIPCHK_NULL (hipEventCreate (&c->ev_m1));
   HIPCHK_NULL (hipEventCreate (&c->ev_t0)); HIPCHK_NULL (hipEventCreate (&c->ev_t1));
+  HIPCHK_NULL (hipEventCreate (&c->ev_u0)); HIPCHK_NULL (hipEventCreate (&c->ev_u1));
+  HIPCHK_NULL (hipEventCreate (&c->ev_v0)); HIPCHK_NULL (hipEventCreate (&c->ev_v1));
   HIPCHK_NULL (hipEventCreateWithFlags (&c->ev_done, hipEventDisableTiming));
   HIPCHK_NULL (hipEventCreateWithFlags (&c->ev_agg, hipEventDisableTiming));
   HIPCHK_NULL (hipStreamSynchronize (c->stream));
@@ -4217,7 +4223,7 @@ extern "C" void tjamd_counter_destroy (tjamd_counter *c)
   (void) hipStreamSynchronize (c->stream);
   DevBuf *all[] = {&c->log, &c->logmeta, &c->pool, &c->table, &c->stage, &c->fix, &c->loc, &c->prefix, &c->rawlist, &c->slow, &c->alt, &c->hist, &c->flags, &c->segid, &c->headpos,
                    &c->keep, &c->outpos, &c->scan_tmp, &c->kept, &c->idx_i, &c->idx_f, &c->cov, &c->bins, &c->binstart, &c->binctx, &c->ovf, &c->grp_jt, &c->grp_hist, &c->fine,
-                   &c->ts_cov, &c->ts_aux};
+                   &c->ts_cov, &c->ts_aux, &c->ut_tot, &c->ut_lev, &c->ut_fb, &c->ut_slots};
   for (DevBuf *b : all) release (*b);
   for (hipEvent_t ev : c->marks) if (ev) (void) hipEventDestroy (ev);
   if (c->d_state) (void) hipFree (c->d_state);
@@ -4233,6 +4239,7 @@ extern "C" void tjamd_counter_destroy (tjamd_counter *c)
   if (c->ev_m1) (void) hipEventDestroy (c->ev_m1);
   if (c->ev_t0) (void) hipEventDestroy (c->ev_t0);
   if (c->ev_t1) (void) hipEventDestroy (c->ev_t1);
+  for (hipEvent_t ev : {c->ev_u0, c->ev_u1, c->ev_v0, c->ev_v1}) if (ev) (void) hipEventDestroy (ev);
   if (c->ev_f0) (void) hipEventDestroy (c->ev_f0);
   if (c->ev_f1) (void) hipEventDestroy (c->ev_f1);
   if (c->ev_done) (void) hipEventDestroy (c->ev_done);
@@ -5337,9 +5344,20 @@ __device__ int name_edit_distance (const u64 *__restrict__ kept, long a, long b,
 // sees type & 3
 #define GJ_ADDS_CONTEXT(t) ((t) != 1)
 
+// Where an element's count comes from, for the histogram's name (its element with the highest count, the first on a tie):
+// the 20-bit field of the record within a sample; the exact total over the samples for the rows of a union
+// (tjamd_union_tracts: the union key's field wraps).
+struct MetaCount { __device__ __forceinline__ int operator() (const u64 *__restrict__ kept, long i) const { return meta_count (kept[3 * i + 2]); } };
+struct TotalCount
+{
+  const long long *__restrict__ total;
+  __device__ __forceinline__ long long operator() (const u64 *__restrict__, long i) const { return total[i]; }
+};
+
 // (2): elements that open a group in the grouping without the retry, tested against the name of the group before them
+template <class CountOf>
 __global__ void group_speculate_kernel (const u64 *__restrict__ kept, long n, int k, int lev, int free_end, const u32 *__restrict__ head,
-                                        u32 *__restrict__ cand, int *__restrict__ jt, u32 *__restrict__ n_cand)
+                                        u32 *__restrict__ cand, int *__restrict__ jt, u32 *__restrict__ n_cand, CountOf count_of)
 {
   for (long i = blockIdx.x * (long) blockDim.x + threadIdx.x; i < n; i += (long) gridDim.x * blockDim.x) {
     u32 c = 0;
@@ -5350,8 +5368,8 @@ __global__ void group_speculate_kernel (const u64 *__restrict__ kept, long n, in
       long ph = i - 1;
       while (!head[ph]) ph--;
       long mode = ph;
-      int mc = meta_count (kept[3 * ph + 2]);
-      for (long j = ph + 1; j < i; j++) { const int cj = meta_count (kept[3 * j + 2]); if (cj > mc) { mc = cj; mode = j; } }
+      auto mc = count_of (kept, ph);
+      for (long j = ph + 1; j < i; j++) { const auto cj = count_of (kept, j); if (cj > mc) { mc = cj; mode = j; } }
       if (name_edit_distance (kept, mode, i, k, free_end) < lev) { c = 1u; atomicAdd (n_cand, 1u); }
     }
     cand[i] = c;
@@ -5363,10 +5381,12 @@ __global__ void group_speculate_kernel (const u64 *__restrict__ kept, long n, in
 // are no longer all close to one another, and the reference's distance loop (src/context_histogram.c:36-46) matters as
 // written: contexts in the order they were added, give up at the first one 2 * max_distance or more away, stop with
 // distance 0 at an identical one (whatever comes after it), otherwise the largest distance met.
+// lev_of (may be null): the edit distance that admitted each element taken in by the retry (type 2); other entries untouched.
 #define GR_CHUNK 4096
+template <class CountOf>
 __global__ __launch_bounds__ (256)
 void group_repair_kernel (const u64 *__restrict__ kept, long n, int k, int maxd, int lev, int free_end,
-                          u32 *__restrict__ head, const u32 *__restrict__ cand, int *__restrict__ jt)
+                          u32 *__restrict__ head, const u32 *__restrict__ cand, int *__restrict__ jt, CountOf count_of, int *__restrict__ lev_of)
 {
   __shared__ long s_pos, s_min;
   if (threadIdx.x == 0) s_pos = 0;
@@ -5387,8 +5407,8 @@ void group_repair_kernel (const u64 *__restrict__ kept, long n, int k, int maxd,
         long hd = h - 1;
         while (!head[hd]) hd--;                           // (flags before h are final: h lies past every earlier replay)
         long mode = hd;
-        int mc = meta_count (kept[3 * hd + 2]);
-        for (long j = hd + 1; j < h; j++) { const int cj = meta_count (kept[3 * j + 2]); if (cj > mc) { mc = cj; mode = j; } }
+        auto mc = count_of (kept, hd);
+        for (long j = hd + 1; j < h; j++) { const auto cj = count_of (kept, j); if (cj > mc) { mc = cj; mode = j; } }
         long i = h;
         while (i < n) {
           if ((kept[3 * i + 2] ^ kept[3 * hd + 2]) & 3ull) break;          // another base: opens a group in both passes, untouched
@@ -5406,16 +5426,19 @@ void group_repair_kernel (const u64 *__restrict__ kept, long n, int k, int maxd,
           }
           int type = 0;
           if (!fail && (matched ? 0 : this_max) < maxd) type = matched ? 1 : 5;
-          else if (name_edit_distance (kept, mode, i, k, free_end) < lev) type = 2;  // the indel retry
+          else {
+            const int d = name_edit_distance (kept, mode, i, k, free_end);
+            if (d < lev) { type = 2; if (lev_of) lev_of[i] = d; }       // the indel retry
+          }
           if (type) {
             head[i] = 0u; jt[i] = type;
-            const int ci = meta_count (kept[3 * i + 2]);
+            const auto ci = count_of (kept, i);
             if (ci > mc) { mc = ci; mode = i; }
             i++;
           }
           else {
             const bool was_head = head[i] != 0u;
-            head[i] = 1u; jt[i] = 0; hd = i; mode = i; mc = meta_count (kept[3 * i + 2]);
+            head[i] = 1u; jt[i] = 0; hd = i; mode = i; mc = count_of (kept, i);
             i++;
             if (was_head) break;                          // both passes open a group here: the same state from now on
           }
@@ -5496,13 +5519,13 @@ extern "C" long tjamd_context_histograms (tjamd_counter *c, int max_distance_per
   // (which reading of the absent edit distance's last argument: looked up per call -- tests switch it)
   const char *ed = getenv ("TATAJUBA_AMD_EDIT_DISTANCE");
   const int free_end = (ed && !strcmp (ed, "free_end")) ? 1 : 0;
-  hipLaunchKernelGGL (group_speculate_kernel, dim3 (grid_for (n)), dim3 (256), 0, c->stream, kept, n, c->k, levenshtein_distance, free_end,
-                      (const u32 *) c->flags.p, (u32 *) c->keep.p, (int *) c->grp_jt.p, n_cand);
+  hipLaunchKernelGGL (group_speculate_kernel<MetaCount>, dim3 (grid_for (n)), dim3 (256), 0, c->stream, kept, n, c->k, levenshtein_distance, free_end,
+                      (const u32 *) c->flags.p, (u32 *) c->keep.p, (int *) c->grp_jt.p, n_cand, MetaCount ());
   u32 nc = 0;
   if (hipMemcpyAsync (&nc, n_cand, 4, hipMemcpyDeviceToHost, c->stream) != hipSuccess || hipStreamSynchronize (c->stream) != hipSuccess)
     return -set_err (TJAMD_ERR_HIP, "grouping failed: %s", hipGetErrorString (hipGetLastError ()));
-  if (nc) hipLaunchKernelGGL (group_repair_kernel, dim3 (1), dim3 (256), 0, c->stream, kept, n, c->k, max_distance_per_flank, levenshtein_distance, free_end,
-                              (u32 *) c->flags.p, (const u32 *) c->keep.p, (int *) c->grp_jt.p);
+  if (nc) hipLaunchKernelGGL (group_repair_kernel<MetaCount>, dim3 (1), dim3 (256), 0, c->stream, kept, n, c->k, max_distance_per_flank, levenshtein_distance,
+                              free_end, (u32 *) c->flags.p, (const u32 *) c->keep.p, (int *) c->grp_jt.p, MetaCount (), (int *) nullptr);
   rc = exclusive_scan (c, (const u32 *) c->flags.p, (u32 *) c->outpos.p, n, total, (u32 *) c->scan_tmp.p, scan_tmp_words (n));
   if (rc) return -rc;
   hipLaunchKernelGGL (group_histogram_kernel, dim3 (grid_for (n)), dim3 (256), 0, c->stream, kept, n, (const u32 *) c->flags.p, (const u32 *) c->outpos.p,
@@ -5819,6 +5842,432 @@ extern "C" double tjamd_last_tract_stats_ms (tjamd_counter *c)
   if (!c || !c->tract_timed) return -1.0;
   float ms = 0.f;
   if (hipSetDevice (c->device) != hipSuccess || hipEventSynchronize (c->ev_t1) != hipSuccess || hipEventElapsedTime (&ms, c->ev_t0, c->ev_t1) != hipSuccess) return -1.0;
+  return (double) ms;
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// N6: tracts across samples by grouping (reference: new_genomic_context_list's grouping, src/context_histogram.c:245-270,
+// taken as the cross-sample tract of new_g_tract_vector_from_genomic_context_list, src/genome_set.c:195-229; statistics
+// of update_g_tract_summary_from_context_histogram / fill_g_tract_summary_tables :291-378; selection of
+// print_selected_g_tract_vector :380-434).  The union rows are grouped as one pooled sample's finalised array would be
+// (the N3 kernels above), a row's count being its exact total over the samples; a sample's histogram in a tract is then its
+// non-zero rows summed per length, bars ordered by count (highest first), then length (larger first): the reference's h.
+
+struct UnionTract { int first, n_rows, n_context, mode, indel, lev_distance; long long integral; };
+static_assert (sizeof (UnionTract) == 32 && sizeof (UnionTract) == sizeof (tjamd_union_tract), "union tract layout");
+struct UnionSummary { int first, n_rows, n_present, variable, selected, lev_distance; double reldiff[TJAMD_N_TRACT_STATS]; };
+static_assert (sizeof (UnionSummary) == 64 && sizeof (UnionSummary) == sizeof (tjamd_union_tract_summary), "union summary layout");
+
+// exact row totals: one segment of S lanes per row, a lane summing samples lane, lane + S, ... (S contiguous words per step)
+__global__ __launch_bounds__ (256)
+void union_totals_kernel (const int *__restrict__ counts, long n, int ns, int S, long long *__restrict__ total)
+{
+  const int lane = threadIdx.x & (S - 1);
+  const long segs_per_grid = (long) gridDim.x * (blockDim.x / S);
+  for (long r = (blockIdx.x * (long) blockDim.x + threadIdx.x) / S; r < n; r += segs_per_grid) {   // (uniform across a segment)
+    long long t = 0;
+    for (int s = lane; s < ns; s += S) t += counts[r * ns + s];
+    for (int o = 1; o < S; o <<= 1) t += __shfl_xor (t, o, S);
+    if (lane == 0) total[r] = t;
+  }
+}
+
+// one thread per tract (at its head): the fields of tjamd_union_tract, the ids of its rows, their join types (type & 3)
+__global__ void union_tract_kernel (long n, const long long *__restrict__ total, const u32 *__restrict__ head, const u32 *__restrict__ gid_excl,
+                                    const int *__restrict__ jt, const int *__restrict__ lev_of, long cap, int *__restrict__ tract_id,
+                                    int *__restrict__ join_type, UnionTract *__restrict__ tracts)
+{
+  for (long i = blockIdx.x * (long) blockDim.x + threadIdx.x; i < n; i += (long) gridDim.x * blockDim.x) {
+    if (!head[i]) continue;
+    const int g = (int) gid_excl[i];
+    UnionTract o = {(int) i, 0, 0, (int) i, 0, 0, 0};
+    long long mode_count = 0;
+    for (long j = i; j < n && (j == i || !head[j]); j++) {
+      const int t = jt[j];
+      if (j == i || GJ_ADDS_CONTEXT (t)) o.n_context++;   // (the rule of group_histogram_kernel)
+      if (t == 2) { o.indel = 1; o.lev_distance = max (o.lev_distance, lev_of[j]); }   // (lev_of: written by the repair for every type 2)
+      const long long cj = total[j];
+      if (j == i || mode_count < cj) { mode_count = cj; o.mode = (int) j; }
+      o.integral += cj; o.n_rows++;
+      tract_id[j] = g;
+      if (join_type) join_type[j] = t & 3;
+    }
+    if (g < cap) tracts[g] = o;
+  }
+}
+
+extern "C" long tjamd_union_tracts (tjamd_counter *c, const void *d_keys, const void *d_counts, long n_union, int n_samples,
+                                    int max_distance_per_flank, int levenshtein_distance,
+                                    int *d_tract_id, int *d_join_type, tjamd_union_tract *d_tracts, long capacity)
+{
+  static const char *fn = "tjamd_union_tracts";
+  if (n_union < 0) return -set_err (TJAMD_ERR_ARG, "%s: n_union %ld < 0", fn, n_union);
+  if (n_union >= (1l << 31)) return -set_err (TJAMD_ERR_CAPACITY, "%s: %ld union rows", fn, n_union);
+  if (n_samples < 1 || n_samples > 4096) return -set_err (TJAMD_ERR_ARG, "%s: n_samples %d outside 1..4096", fn, n_samples);
+  if (n_union > 0 && (!d_keys || !d_counts)) return -set_err (TJAMD_ERR_ARG, "%s: null union buffers", fn);
+  if (n_union > 0 && (!d_tract_id || !d_tracts)) return -set_err (TJAMD_ERR_ARG, "%s: null tract id or tract buffer", fn);
+  if (max_distance_per_flank < 0 || levenshtein_distance < 0)
+    return -set_err (TJAMD_ERR_ARG, "%s: negative distance (max_distance_per_flank %d, levenshtein_distance %d)", fn, max_distance_per_flank, levenshtein_distance);
+  if (capacity < (n_union > 0 ? 1 : 0)) return -set_err (TJAMD_ERR_CAPACITY, "%s: capacity %ld for a union of %ld rows", fn, capacity, n_union);
+  if (!c) return -set_err (TJAMD_ERR_ARG, "%s: null counter", fn);
+  if (hipSetDevice (c->device) != hipSuccess) return -set_err (TJAMD_ERR_HIP, "hipSetDevice failed");
+  c->union_timed = false; c->union_cand = -1;           // (a failed call leaves no timing behind)
+  const long n = n_union;
+  if (n == 0) return 0;
+  int rc = ensure (c->headpos, (size_t) n * 4, c->stream);          // back[]
+  if (!rc) rc = ensure (c->flags, (size_t) n * 4, c->stream);      // head flags
+  if (!rc) rc = ensure (c->outpos, (size_t) n * 4, c->stream);     // tracts before each row
+  if (!rc) rc = ensure (c->keep, (size_t) n * 4, c->stream);       // candidates of the retry
+  if (!rc) rc = ensure (c->grp_jt, (size_t) n * 4, c->stream);
+  if (!rc) rc = ensure (c->ut_tot, (size_t) n * 8, c->stream);
+  if (!rc) rc = ensure (c->ut_lev, (size_t) n * 4, c->stream);
+  if (!rc) rc = ensure (c->scan_tmp, scan_tmp_words (n) * 4 + 64, c->stream);
+  if (rc) return -rc;
+  const u64 *keys = (const u64 *) d_keys;
+  long long *tot = (long long *) c->ut_tot.p;
+  u32 *total = (u32 *) c->scan_tmp.p + scan_tmp_words (n), *n_cand = total + 1;
+  (void) hipEventRecord (c->ev_u0, c->stream);
+  const int S = tract_segment (n_samples);
+  hipLaunchKernelGGL (union_totals_kernel, dim3 (tract_grid (n, S)), dim3 (256), 0, c->stream, (const int *) d_counts, n, n_samples, S, tot);
+  hipLaunchKernelGGL (group_back_kernel, dim3 (grid_for (n)), dim3 (256), 0, c->stream, keys, n, max_distance_per_flank, (int *) c->headpos.p);
+  hipLaunchKernelGGL (group_resolve_kernel, dim3 (grid_for (n)), dim3 (256), 0, c->stream, (const int *) c->headpos.p, n, (u32 *) c->flags.p);
+  if (hipMemsetAsync (n_cand, 0, 4, c->stream) != hipSuccess) return -set_err (TJAMD_ERR_HIP, "memset failed");
+  // (the reading of the absent edit distance's last argument: looked up per call, as tjamd_context_histograms does)
+  const char *ed = getenv ("TATAJUBA_AMD_EDIT_DISTANCE");
+  const int free_end = (ed && !strcmp (ed, "free_end")) ? 1 : 0;
+  const TotalCount count_of = {tot};
+  hipLaunchKernelGGL (group_speculate_kernel<TotalCount>, dim3 (grid_for (n)), dim3 (256), 0, c->stream, keys, n, c->k, levenshtein_distance, free_end,
+                      (const u32 *) c->flags.p, (u32 *) c->keep.p, (int *) c->grp_jt.p, n_cand, count_of);
+  if (hipGetLastError () != hipSuccess) return -set_err (TJAMD_ERR_HIP, "%s: grouping launch failed", fn);
+  u32 nc = 0;
+  if (hipMemcpyAsync (&nc, n_cand, 4, hipMemcpyDeviceToHost, c->stream) != hipSuccess || hipStreamSynchronize (c->stream) != hipSuccess)
+    return -set_err (TJAMD_ERR_HIP, "%s: grouping failed: %s", fn, hipGetErrorString (hipGetLastError ()));
+  if (nc) hipLaunchKernelGGL (group_repair_kernel<TotalCount>, dim3 (1), dim3 (256), 0, c->stream, keys, n, c->k, max_distance_per_flank, levenshtein_distance,
+                              free_end, (u32 *) c->flags.p, (const u32 *) c->keep.p, (int *) c->grp_jt.p, count_of, (int *) c->ut_lev.p);
+  rc = exclusive_scan (c, (const u32 *) c->flags.p, (u32 *) c->outpos.p, n, total, (u32 *) c->scan_tmp.p, scan_tmp_words (n));
+  if (rc) return -rc;
+  hipLaunchKernelGGL (union_tract_kernel, dim3 (grid_for (n)), dim3 (256), 0, c->stream, n, (const long long *) tot, (const u32 *) c->flags.p,
+                      (const u32 *) c->outpos.p, (const int *) c->grp_jt.p, (const int *) c->ut_lev.p, capacity, d_tract_id, d_join_type, (UnionTract *) d_tracts);
+  if (hipGetLastError () != hipSuccess) return -set_err (TJAMD_ERR_HIP, "%s: tract launch failed", fn);
+  (void) hipEventRecord (c->ev_u1, c->stream);
+  u32 ng = 0;
+  if (hipMemcpyAsync (&ng, total, 4, hipMemcpyDeviceToHost, c->stream) != hipSuccess || hipStreamSynchronize (c->stream) != hipSuccess)
+    return -set_err (TJAMD_ERR_HIP, "%s: grouping failed: %s", fn, hipGetErrorString (hipGetLastError ()));
+  if ((long) ng > capacity) return -set_err (TJAMD_ERR_CAPACITY, "%s: %u tracts, caller capacity %ld", fn, ng, capacity);
+  c->union_timed = true; c->union_cand = (long) nc;
+  return (long) ng;
+}
+
+// A sample's bars in a tract: its non-zero rows summed per signed 10-bit length, then the lengths with a non-zero sum in
+// the order of the reference's h (count descending, the larger length first on a tie).  Slot q of a lane lives at
+// cnt[q * stride], len[q * stride].  FULL: every possible length has a slot (1024, global memory); otherwise the lengths
+// are looked up among UT_SLOTS slots (LDS) and -1 says that the sample has more.  Returns the number of bars; integral and
+// n_ctx (changes of context between non-zero rows: a tract's rows of one context are contiguous) are the sample's.
+#define UT_SLOTS 16
+#define UT_LENGTHS 1024
+#define UT_FULL_BLOCKS 4
+
+template <bool FULL>
+__device__ int union_sample_bars (const u64 *__restrict__ keys, const int *__restrict__ counts, int ns, long first, long end, int s,
+                                  long long *cnt, int *len, long stride, long long &integral, int &n_ctx)
+{
+  int nb = 0;
+  long prev = -1;
+  integral = 0; n_ctx = 0;
+  if (FULL) for (int q = 0; q < UT_LENGTHS; q++) cnt[q * stride] = 0;
+  for (long r = first; r < end; r++) {
+    const int x = counts[r * ns + s];
+    if (x == 0) continue;
+    const u64 m = keys[3 * r + 2];
+    int l = (int) ((m >> TJ_META_LEN_SHIFT) & 0x3FFull);
+    if (l & 0x200) l -= 0x400;                          // signed 10-bit field
+    if (prev < 0 || keys[3 * r] != keys[3 * prev] || keys[3 * r + 1] != keys[3 * prev + 1] || ((m ^ keys[3 * prev + 2]) & 3ull)) n_ctx++;
+    prev = r;
+    integral += x;
+    if (FULL) cnt[(l + UT_LENGTHS / 2) * stride] += x;
+    else {
+      int q = 0;
+      while (q < nb && len[q * stride] != l) q++;
+      if (q == nb) {
+        if (nb == UT_SLOTS) return -1;
+        len[q * stride] = l; cnt[q * stride] = 0; nb++;
+      }
+      cnt[q * stride] += x;
+    }
+  }
+  const int n_slots = FULL ? UT_LENGTHS : nb;
+  int b = 0;
+  for (int q = 0; q < n_slots; q++) {                   // keep the non-zero sums (b <= q: in place)
+    const long long x = cnt[q * stride];
+    if (x == 0) continue;
+    const int l = FULL ? q - UT_LENGTHS / 2 : len[q * stride];
+    cnt[b * stride] = x; len[b * stride] = l; b++;
+  }
+  for (int a = 1; a < b; a++) {                         // count descending, then length descending (insertion sort)
+    const long long x = cnt[a * stride];
+    const int l = len[a * stride];
+    int q = a - 1;
+    while (q >= 0 && (cnt[q * stride] < x || (cnt[q * stride] == x && len[q * stride] < l))) {
+      cnt[(q + 1) * stride] = cnt[q * stride]; len[(q + 1) * stride] = len[q * stride]; q--;
+    }
+    cnt[(q + 1) * stride] = x; len[(q + 1) * stride] = l;
+  }
+  return b;
+}
+
+// descriptive_stats_of_histogram (src/genome_set.c:738-766) on the ordered bars, its sums bar by bar; false if no bar
+__device__ bool union_sample_values (const long long *cnt, const int *len, long stride, int nb, long long integral, int n_ctx, int cov,
+                                     double *v, int &modal_len)
+{
+  for (int j = 0; j < TJAMD_N_TRACT_STATS; j++) v[j] = 0.0;
+  modal_len = 0;
+  if (nb <= 0) return false;
+  const double I = (double) integral;
+  double avg = 0.0, ent = 0.0;
+  for (int q = 0; q < nb; q++) {
+    const long long x = cnt[q * stride];
+    avg += (double) (x * (long long) len[q * stride]) / I;
+    const double p = (double) x / I;
+    ent += p * log (p);
+  }
+  v[TJAMD_STAT_AVG_LENGTH] = avg;
+  v[TJAMD_STAT_MODAL_FREQ] = (double) cnt[0] / I;
+  v[TJAMD_STAT_PROP_COVERAGE] = I / (double) cov;
+  v[TJAMD_STAT_COVERAGE_PER_CONTEXT] = I / (double) n_ctx;
+  v[TJAMD_STAT_ENTROPY] = -ent;
+  modal_len = len[0];
+  return true;
+}
+
+// a lane's slots: LDS [UT_SLOTS][256] (the block's threads side by side), or global [UT_LENGTHS][threads of the grid]
+#define UT_LANE_SLOTS(FULL, g_cnt, g_len)                                                                            \
+  __shared__ long long s_cnt[FULL ? 1 : UT_SLOTS * 256];                                                             \
+  __shared__ int s_len[FULL ? 1 : UT_SLOTS * 256];                                                                   \
+  const long gthread = blockIdx.x * (long) blockDim.x + threadIdx.x;                                                 \
+  long long *cnt = FULL ? g_cnt + gthread : s_cnt + threadIdx.x;                                                     \
+  int *len = FULL ? g_len + gthread : s_len + threadIdx.x;                                                           \
+  const long stride = FULL ? (long) gridDim.x * blockDim.x : 256l;
+
+// One segment of S lanes per tract, as tract_stats_kernel.  !FULL: every tract; a tract where a sample has more than UT_SLOTS
+// lengths is only flagged (fallback[t] = 1).  FULL (UT_FULL_BLOCKS blocks): the flagged tracts.  err[0] |= 1 where the
+// tracts do not tile the union (then nothing is read outside it).  Every flag below n_tracts is written.
+template <bool FULL>
+__global__ __launch_bounds__ (256)
+void union_tract_stats_kernel (const u64 *__restrict__ keys, const int *__restrict__ counts, long n_union, int ns, int S, const int *__restrict__ cov,
+                               const int *__restrict__ ref_len, const UnionTract *__restrict__ tracts, long n_tracts, UnionSummary *__restrict__ sum,
+                               u32 *__restrict__ varflag, u32 *__restrict__ selflag, u32 *__restrict__ fallback,
+                               long long *__restrict__ g_cnt, int *__restrict__ g_len, int *__restrict__ err)
+{
+  UT_LANE_SLOTS (FULL, g_cnt, g_len)
+  const int lane = threadIdx.x & (S - 1);
+  const long segs_per_grid = (long) gridDim.x * (blockDim.x / S);
+  for (long t = gthread / S; t < n_tracts; t += segs_per_grid) {   // (uniform across a segment)
+    if (FULL && !fallback[t]) continue;
+    const UnionTract u = tracts[t];
+    const long first = u.first, end = first + (long) u.n_rows;
+    const long prev_end = t ? (long) tracts[t - 1].first + (long) tracts[t - 1].n_rows : 0l;
+    if (first < 0 || u.n_rows < 1 || first != prev_end || end > n_union || (t == n_tracts - 1 && end != n_union)) {
+      if (lane == 0) { atomicOr (err, 1); varflag[t] = 0u; selflag[t] = 0u; if (!FULL) fallback[t] = 0u; }
+      continue;
+    }
+    const int ref = ref_len ? ref_len[t] : 0;
+    double mx[TJAMD_N_TRACT_STATS], mn[TJAMD_N_TRACT_STATS], v[TJAMD_N_TRACT_STATS];
+    for (int j = 0; j < TJAMD_N_TRACT_STATS; j++) { mx[j] = -FLT_MAX; mn[j] = FLT_MAX; }
+    int present = 0, off_ref = 0, over = 0;
+    for (int s = lane; s < ns; s += S) {
+      long long integral;
+      int n_ctx, ml;
+      const int nb = union_sample_bars<FULL> (keys, counts, ns, first, end, s, cnt, len, stride, integral, n_ctx);
+      if (nb < 0) { over = 1; break; }
+      if (!union_sample_values (cnt, len, stride, nb, integral, n_ctx, cov[s], v, ml)) continue;
+      present++;
+      if (ref > 0 && ml != ref) off_ref = 1;
+      for (int j = 0; j < TJAMD_N_TRACT_STATS; j++) { mx[j] = dmax_ref (mx[j], v[j]); mn[j] = dmin_ref (mn[j], v[j]); }
+    }
+    for (int o = 1; o < S; o <<= 1) {
+      present += __shfl_xor (present, o, S);
+      off_ref |= __shfl_xor (off_ref, o, S);
+      over |= __shfl_xor (over, o, S);
+      for (int j = 0; j < TJAMD_N_TRACT_STATS; j++) {
+        mx[j] = dmax_ref (mx[j], __shfl_xor (mx[j], o, S));
+        mn[j] = dmin_ref (mn[j], __shfl_xor (mn[j], o, S));
+      }
+    }
+    if (lane != 0) continue;
+    if (!FULL) fallback[t] = (u32) over;
+    if (over) { varflag[t] = 0u; selflag[t] = 0u; continue; }   // (FULL never overflows: the fallback kernel writes this tract)
+    UnionSummary o;
+    o.first = (int) first; o.n_rows = u.n_rows; o.n_present = present; o.lev_distance = u.lev_distance;
+    for (int j = 0; j < TJAMD_N_TRACT_STATS; j++) o.reldiff[j] = (mx[j] > DBL_MIN) ? mx[j] - mn[j] : 0.0;
+    const double difference = o.reldiff[TJAMD_STAT_AVG_LENGTH] + o.reldiff[TJAMD_STAT_MODAL_FREQ] + o.reldiff[TJAMD_STAT_ENTROPY];
+    o.variable = (present < ns || difference > 1.e-5 || off_ref) ? 1 : 0;                 // the rule of tjamd_tract_stats
+    o.selected = (present < ns || u.lev_distance > 0 || o.reldiff[TJAMD_STAT_MODAL_FREQ] > 1e-6 ||  // print_selected_g_tract_vector
+                  o.reldiff[TJAMD_STAT_AVG_LENGTH] > 1e-6 || o.reldiff[TJAMD_STAT_ENTROPY] > 1e-6) ? 1 : 0;
+    sum[t] = o;
+    varflag[t] = (u32) o.variable; selflag[t] = (u32) o.selected;
+  }
+}
+
+// the per-sample values of listed tracts; !FULL flags (fallback[i] = 1) an entry where a sample has more than UT_SLOTS
+// lengths, FULL (UT_FULL_BLOCKS blocks) writes the flagged entries again
+template <bool FULL>
+__global__ __launch_bounds__ (256)
+void union_tract_sample_stats_kernel (const u64 *__restrict__ keys, const int *__restrict__ counts, long n_union, int ns, int S, const int *__restrict__ cov,
+                                      const UnionSummary *__restrict__ sum, long n_tracts, const int *__restrict__ list, long n_list,
+                                      double *__restrict__ values, int *__restrict__ modal_len, int *__restrict__ n_context, int *__restrict__ n_len,
+                                      u32 *__restrict__ fallback, long long *__restrict__ g_cnt, int *__restrict__ g_len, int *__restrict__ err)
+{
+  UT_LANE_SLOTS (FULL, g_cnt, g_len)
+  const int lane = threadIdx.x & (S - 1);
+  const long segs_per_grid = (long) gridDim.x * (blockDim.x / S);
+  for (long i = gthread / S; i < n_list; i += segs_per_grid) {
+    if (FULL && !fallback[i]) continue;
+    const int t = list[i];
+    long first = 0, end = 0;
+    if (t >= 0 && t < n_tracts) { first = sum[t].first; end = first + (long) sum[t].n_rows; }
+    const bool ok = t >= 0 && t < n_tracts && first >= 0 && first <= end && end <= n_union;
+    if (!ok) { if (lane == 0) atomicOr (err, 1); first = end = 0; }
+    int over = 0;
+    for (int s = lane; s < ns; s += S) {
+      double v[TJAMD_N_TRACT_STATS];
+      long long integral;
+      int n_ctx, ml;
+      const int nb = union_sample_bars<FULL> (keys, counts, ns, first, end, s, cnt, len, stride, integral, n_ctx);
+      if (nb < 0) { over = 1; break; }
+      if (!union_sample_values (cnt, len, stride, nb, integral, n_ctx, cov[s], v, ml)) n_ctx = 0;
+      for (int j = 0; j < TJAMD_N_TRACT_STATS; j++) values[(i * TJAMD_N_TRACT_STATS + j) * ns + s] = v[j];
+      if (modal_len) modal_len[i * ns + s] = ml;
+      if (n_context) n_context[i * ns + s] = n_ctx;
+      if (n_len) n_len[i * ns + s] = nb;
+    }
+    if (!FULL) {
+      for (int o = 1; o < S; o <<= 1) over |= __shfl_xor (over, o, S);
+      if (lane == 0) fallback[i] = (u32) over;
+    }
+  }
+}
+
+static int union_stats_args (const char *fn, const void *d_keys, const void *d_counts, long n_union, int n_samples, const int *coverage,
+                             const void *d_tracts, long n_tracts, const void *d_out)
+{ // the checks both stats entries share, before any device call
+  int rc = tract_args (fn, d_keys, d_counts, n_union, n_samples, coverage);
+  if (rc) return rc;
+  if (n_tracts < (n_union > 0 ? 1 : 0) || n_tracts > n_union)
+    return set_err (TJAMD_ERR_ARG, "%s: n_tracts %ld for a union of %ld rows", fn, n_tracts, n_union);
+  if (n_tracts > 0 && (!d_tracts || !d_out)) return set_err (TJAMD_ERR_ARG, "%s: null tract or summary buffer", fn);
+  return TJAMD_OK;
+}
+
+static int ensure_union_fallback (tjamd_counter *c, long n)
+{ // fallback flags, and the global bars of the FULL kernels
+  int rc = ensure (c->ut_fb, (size_t) std::max (n, 1l) * 4, c->stream);
+  const size_t threads = (size_t) UT_FULL_BLOCKS * 256;
+  if (!rc) rc = ensure (c->ut_slots, threads * UT_LENGTHS * (sizeof (long long) + sizeof (int)), c->stream);
+  return rc;
+}
+
+extern "C" long tjamd_union_tract_stats (tjamd_counter *c, const void *d_keys, const void *d_counts, long n_union, int n_samples,
+                                         const tjamd_union_tract *d_tracts, long n_tracts, const int *coverage, const int *d_ref_length,
+                                         tjamd_union_tract_summary *d_summary, int *d_var, long *n_var, int *d_sel, long *n_sel)
+{
+  static const char *fn = "tjamd_union_tract_stats";
+  int rc = union_stats_args (fn, d_keys, d_counts, n_union, n_samples, coverage, d_tracts, n_tracts, d_summary);
+  if (rc) return -rc;
+  if (!c) return -set_err (TJAMD_ERR_ARG, "%s: null counter", fn);
+  if (n_var) *n_var = 0;
+  if (n_sel) *n_sel = 0;
+  if (hipSetDevice (c->device) != hipSuccess) return -set_err (TJAMD_ERR_HIP, "hipSetDevice failed");
+  c->union_stats_timed = false;
+  if (n_union == 0) return 0;
+  const long nt = n_tracts;
+  rc = ensure (c->flags, (size_t) nt * 4, c->stream);               // variable flags, then their positions in outpos
+  if (!rc) rc = ensure (c->outpos, (size_t) nt * 4, c->stream);
+  if (!rc) rc = ensure (c->keep, (size_t) nt * 4, c->stream);      // selected flags, then their positions in headpos
+  if (!rc) rc = ensure (c->headpos, (size_t) nt * 4, c->stream);
+  if (!rc) rc = ensure (c->scan_tmp, scan_tmp_words (nt) * 4 + 64, c->stream);
+  if (!rc) rc = ensure_union_fallback (c, nt);
+  if (!rc) rc = upload_coverage (c, coverage, n_samples);
+  if (rc) return -rc;
+  (void) hipEventRecord (c->ev_v0, c->stream);
+  u32 *total = (u32 *) c->scan_tmp.p + scan_tmp_words (nt);
+  int *err = (int *) c->ts_aux.p;
+  const int S = tract_segment (n_samples);
+  const size_t threads = (size_t) UT_FULL_BLOCKS * 256;
+  long long *g_cnt = (long long *) c->ut_slots.p;
+  int *g_len = (int *) (g_cnt + threads * UT_LENGTHS);
+  u32 *vf = (u32 *) c->flags.p, *sf = (u32 *) c->keep.p, *fb = (u32 *) c->ut_fb.p;
+  hipLaunchKernelGGL (union_tract_stats_kernel<false>, dim3 (tract_grid (nt, S)), dim3 (256), 0, c->stream, (const u64 *) d_keys, (const int *) d_counts,
+                      n_union, n_samples, S, (const int *) c->ts_cov.p, d_ref_length, (const UnionTract *) d_tracts, nt, (UnionSummary *) d_summary,
+                      vf, sf, fb, g_cnt, g_len, err);
+  hipLaunchKernelGGL (union_tract_stats_kernel<true>, dim3 (UT_FULL_BLOCKS), dim3 (256), 0, c->stream, (const u64 *) d_keys, (const int *) d_counts,
+                      n_union, n_samples, S, (const int *) c->ts_cov.p, d_ref_length, (const UnionTract *) d_tracts, nt, (UnionSummary *) d_summary,
+                      vf, sf, fb, g_cnt, g_len, err);
+  if (hipGetLastError () != hipSuccess) return -set_err (TJAMD_ERR_HIP, "%s: launch failed", fn);
+  rc = exclusive_scan (c, vf, (u32 *) c->outpos.p, nt, total, (u32 *) c->scan_tmp.p, scan_tmp_words (nt));
+  if (!rc) rc = exclusive_scan (c, sf, (u32 *) c->headpos.p, nt, total + 1, (u32 *) c->scan_tmp.p, scan_tmp_words (nt));
+  if (rc) return -rc;
+  if (d_var) hipLaunchKernelGGL (tract_var_scatter_kernel, dim3 (grid_for (nt)), dim3 (256), 0, c->stream, (const u32 *) vf, (const u32 *) c->outpos.p, nt, d_var);
+  if (d_sel) hipLaunchKernelGGL (tract_var_scatter_kernel, dim3 (grid_for (nt)), dim3 (256), 0, c->stream, (const u32 *) sf, (const u32 *) c->headpos.p, nt, d_sel);
+  if (hipGetLastError () != hipSuccess) return -set_err (TJAMD_ERR_HIP, "%s: list launch failed", fn);
+  (void) hipEventRecord (c->ev_v1, c->stream);
+  int h_err = 0;
+  u32 h_tot[2] = {0, 0};
+  if (hipMemcpyAsync (&h_err, err, 4, hipMemcpyDeviceToHost, c->stream) != hipSuccess || hipMemcpyAsync (h_tot, total, 8, hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
+      hipStreamSynchronize (c->stream) != hipSuccess) return -set_err (TJAMD_ERR_HIP, "%s: failed: %s", fn, hipGetErrorString (hipGetLastError ()));
+  if (h_err) return -set_err (TJAMD_ERR_ARG, "%s: the tracts must tile the union (first 0, each starting where the one before ends, the last ending at row %ld)", fn, n_union);
+  c->union_stats_timed = true;
+  if (n_var) *n_var = (long) h_tot[0];
+  if (n_sel) *n_sel = (long) h_tot[1];
+  return nt;
+}
+
+extern "C" long tjamd_union_tract_sample_stats (tjamd_counter *c, const void *d_keys, const void *d_counts, long n_union, int n_samples,
+                                                const int *coverage, const tjamd_union_tract_summary *d_summary, long n_tracts,
+                                                const int *d_list, long n_list, double *d_values, int *d_modal_len, int *d_n_context, int *d_n_len)
+{
+  static const char *fn = "tjamd_union_tract_sample_stats";
+  int rc = tract_args (fn, d_keys, d_counts, n_union, n_samples, coverage);
+  if (rc) return -rc;
+  if (n_list < 0 || n_tracts < 0 || n_tracts > n_union) return -set_err (TJAMD_ERR_ARG, "%s: n_list %ld, n_tracts %ld (union of %ld rows)", fn, n_list, n_tracts, n_union);
+  if (n_list > 0 && (!d_summary || !d_list || !d_values)) return -set_err (TJAMD_ERR_ARG, "%s: null summary, list or values buffer", fn);
+  if (!c) return -set_err (TJAMD_ERR_ARG, "%s: null counter", fn);
+  if (hipSetDevice (c->device) != hipSuccess) return -set_err (TJAMD_ERR_HIP, "hipSetDevice failed");
+  if (n_list == 0) return 0;
+  rc = ensure_union_fallback (c, n_list);
+  if (!rc) rc = upload_coverage (c, coverage, n_samples);
+  if (rc) return -rc;
+  const int S = tract_segment (n_samples);
+  const size_t threads = (size_t) UT_FULL_BLOCKS * 256;
+  long long *g_cnt = (long long *) c->ut_slots.p;
+  int *g_len = (int *) (g_cnt + threads * UT_LENGTHS);
+  int *err = (int *) c->ts_aux.p, h_err = 0;
+  hipLaunchKernelGGL (union_tract_sample_stats_kernel<false>, dim3 (tract_grid (n_list, S)), dim3 (256), 0, c->stream, (const u64 *) d_keys, (const int *) d_counts,
+                      n_union, n_samples, S, (const int *) c->ts_cov.p, (const UnionSummary *) d_summary, n_tracts, d_list, n_list, d_values, d_modal_len,
+                      d_n_context, d_n_len, (u32 *) c->ut_fb.p, g_cnt, g_len, err);
+  hipLaunchKernelGGL (union_tract_sample_stats_kernel<true>, dim3 (UT_FULL_BLOCKS), dim3 (256), 0, c->stream, (const u64 *) d_keys, (const int *) d_counts,
+                      n_union, n_samples, S, (const int *) c->ts_cov.p, (const UnionSummary *) d_summary, n_tracts, d_list, n_list, d_values, d_modal_len,
+                      d_n_context, d_n_len, (u32 *) c->ut_fb.p, g_cnt, g_len, err);
+  if (hipGetLastError () != hipSuccess || hipMemcpyAsync (&h_err, err, 4, hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
+      hipStreamSynchronize (c->stream) != hipSuccess) return -set_err (TJAMD_ERR_HIP, "%s: failed: %s", fn, hipGetErrorString (hipGetLastError ()));
+  if (h_err) return -set_err (TJAMD_ERR_ARG, "%s: a listed tract id is outside [0, %ld) or its rows outside the union", fn, n_tracts);
+  return n_list;
+}
+
+extern "C" double tjamd_last_union_tracts_ms (tjamd_counter *c)
+{ // first launch to last of the last tjamd_union_tracts, the host's wait for the retry candidates included
+  if (!c || !c->union_timed) return -1.0;
+  float ms = 0.f;
+  if (hipSetDevice (c->device) != hipSuccess || hipEventSynchronize (c->ev_u1) != hipSuccess || hipEventElapsedTime (&ms, c->ev_u0, c->ev_u1) != hipSuccess) return -1.0;
+  return (double) ms;
+}
+
+extern "C" long tjamd_last_union_tract_candidates (tjamd_counter *c) { return c ? c->union_cand : -1; }
+
+extern "C" double tjamd_last_union_tract_stats_ms (tjamd_counter *c)
+{
+  if (!c || !c->union_stats_timed) return -1.0;
+  float ms = 0.f;
+  if (hipSetDevice (c->device) != hipSuccess || hipEventSynchronize (c->ev_v1) != hipSuccess || hipEventElapsedTime (&ms, c->ev_v0, c->ev_v1) != hipSuccess) return -1.0;
   return (double) ms;
 }
 

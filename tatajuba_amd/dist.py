@@ -101,3 +101,49 @@ def tract_stats_device(counter, keys_u8, mat, coverage, tract_ids=None, ref_leng
             raise TatajubaAmdError(_err())
         out.update(values=vals[:n].cpu().numpy(), modal_len=ml[:n].cpu().numpy(), n_context=nc[:n].cpu().numpy())
     return out
+
+
+def union_tracts_device(counter, keys_u8, mat, coverage, max_distance_per_flank, levenshtein_distance, ref_length=None, per_sample=True):
+    """Tracts of a union grouped across samples on the GPU (tjamd_union_tracts, tjamd_union_tract_stats, then
+    tjamd_union_tract_sample_stats on the selected tracts): keys_u8 / mat as merge_histograms_device returns them, coverage =
+    each sample's coverage, ref_length = CUDA int32 tensor (one length per tract) or None.  Returns a dict of numpy arrays:
+    tract_id, join_type (int32 per union row), tracts (UNION_TRACT_DTYPE[n_tracts]), summary (UNION_TRACT_SUMMARY_DTYPE),
+    variable and selected (int32 ids, ascending) and, with per_sample, values (float64 [n_sel, 5, n_samples]), modal_len,
+    n_context and n_len (int32 [n_sel, n_samples]) of the selected tracts."""
+    import ctypes as C
+    import numpy as np
+    from .capi import lib, TatajubaAmdError, _err, UNION_TRACT_DTYPE, UNION_TRACT_SUMMARY_DTYPE, N_TRACT_STATS
+    dev = mat.device
+    nu, ns = int(mat.shape[0]), int(mat.shape[1])
+    cov = (C.c_int * ns)(*[int(x) for x in coverage])
+    ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
+    m = max(nu, 1)
+    ids = torch.empty(m, dtype=torch.int32, device=dev)
+    jt = torch.empty(m, dtype=torch.int32, device=dev)
+    tr = torch.empty(m * UNION_TRACT_DTYPE.itemsize, dtype=torch.uint8, device=dev)
+    torch.cuda.current_stream().synchronize()
+    nt = lib().tjamd_union_tracts(counter._h, ptr(keys_u8), ptr(mat), nu, ns, int(max_distance_per_flank), int(levenshtein_distance),
+                                  ptr(ids), ptr(jt), ptr(tr), m)
+    if nt < 0:
+        raise TatajubaAmdError(_err())
+    summ = torch.empty(max(nt, 1) * UNION_TRACT_SUMMARY_DTYPE.itemsize, dtype=torch.uint8, device=dev)
+    var = torch.empty(max(nt, 1), dtype=torch.int32, device=dev)
+    sel = torch.empty(max(nt, 1), dtype=torch.int32, device=dev)
+    nv, nsel = C.c_long(), C.c_long()
+    got = lib().tjamd_union_tract_stats(counter._h, ptr(keys_u8), ptr(mat), nu, ns, ptr(tr), nt, cov, ptr(ref_length), ptr(summ),
+                                        ptr(var), C.byref(nv), ptr(sel), C.byref(nsel))
+    if got < 0:
+        raise TatajubaAmdError(_err())
+    raw = lambda t, dt, n: np.frombuffer(t[: n * dt.itemsize].cpu().numpy().tobytes(), dtype=dt)
+    out = {"tract_id": ids[:nu].cpu().numpy(), "join_type": jt[:nu].cpu().numpy(), "tracts": raw(tr, UNION_TRACT_DTYPE, nt),
+           "summary": raw(summ, UNION_TRACT_SUMMARY_DTYPE, nt), "variable": var[: nv.value].cpu().numpy(), "selected": sel[: nsel.value].cpu().numpy()}
+    if per_sample:
+        n = nsel.value
+        vals = torch.zeros((max(n, 1), N_TRACT_STATS, ns), dtype=torch.float64, device=dev)
+        ml, nc, nl = (torch.zeros((max(n, 1), ns), dtype=torch.int32, device=dev) for _ in range(3))
+        got = lib().tjamd_union_tract_sample_stats(counter._h, ptr(keys_u8), ptr(mat), nu, ns, cov, ptr(summ), nt, ptr(sel), n,
+                                                   ptr(vals), ptr(ml), ptr(nc), ptr(nl))
+        if got < 0:
+            raise TatajubaAmdError(_err())
+        out.update(values=vals[:n].cpu().numpy(), modal_len=ml[:n].cpu().numpy(), n_context=nc[:n].cpu().numpy(), n_len=nl[:n].cpu().numpy())
+    return out
