@@ -4143,6 +4143,7 @@ struct tjamd_counter
   long last_scan_launches = 0;
   unsigned scan_seq = 0;
   size_t piece_target = TJ_SCAN_PIECE_TARGET;           // TATAJUBA_AMD_SCAN_PIECE (bytes) overrides it: tests
+  int scan_grid_cap = 0;                                // TATAJUBA_AMD_SCAN_GRID (tests): n >= 1 caps the workgroups of the scan and log-partition launches; 0: no cap
   bool buckets_clean = false;
   long plan_mismatches = 0;   // finalises whose in-kernel reading of the kept count differed from the kernel boundary's (expected: 0)
   bool ctr_clean = false;     // the scan counters are zero but for n_undefined (clear_buckets_kernel did it, no scan since)
@@ -4189,6 +4190,8 @@ extern "C" tjamd_counter *tjamd_counter_create (int device, int kmer_size)
   if (sk && !strcmp (sk, "log")) c->log_mode = 2;
   const char *fm = getenv ("TATAJUBA_AMD_FAST");          // test hook: 0 = generic scan kernel only, 2 = fast kernel hands every tile over
   if (fm && atoi (fm) >= 0 && atoi (fm) <= 2) c->fast_mode = atoi (fm);
+  const char *sg = getenv ("TATAJUBA_AMD_SCAN_GRID");     // test hook: at most n workgroups per scan / log-partition launch (one workgroup then walks many tiles or blocks)
+  if (sg && atoi (sg) >= 1) c->scan_grid_cap = atoi (sg);
   const char *sl = getenv ("TATAJUBA_AMD_BUCKET_SLACK");
   if (sl && atof (sl) >= 1.0) c->slack = atof (sl);
   HIPCHK_NULL (hipStreamCreateWithFlags (&c->own_stream, hipStreamNonBlocking));
@@ -4534,6 +4537,8 @@ static int scan_device_piece (tjamd_counter *c, const void *d_stream, size_t n_b
   const int par = (int) (c->scan_seq++ & 1u);            // per-launch counters are double-buffered (DevCounters::lc)
   if (first) HIPCHK (hipEventRecord (c->ev_s0, c->stream));
   const TileSrc plain = {nullptr, 0};
+  // (TATAJUBA_AMD_SCAN_GRID: the launches below take at most that many workgroups; the storage above stays sized for the full grids)
+  auto capped = [c] (long g) { return (unsigned) (c->scan_grid_cap >= 1 ? std::min<long> (g, (long) c->scan_grid_cap) : g); };
   // (the fast kernel counts tiles and bytes in 32 bits: a piece that could not be cut below 2 GiB -- one read longer
   // than that -- is left to the general kernel)
   const bool use_fast = c->fast_mode && n_bytes < ((size_t) 1 << 31) - (1u << 20);
@@ -4561,16 +4566,16 @@ static int scan_device_piece (tjamd_counter *c, const void *d_stream, size_t n_b
     if (use_fast) { \
       /* the fast kernel takes every tile it can vouch for and lists the others; the generic kernel then works through the list */ \
       if (WW <= 2 && use_log) \
-        hipLaunchKernelGGL ((scan_fast_kernel<(WW <= 2 ? WW : 1), true>), dim3 (fgrid_log), dim3 (FK_BLOCK), 0, c->stream, seq, (long) n_bytes, n_ftiles, c->k, mprime, BK, c->d_ctr, \
+        hipLaunchKernelGGL ((scan_fast_kernel<(WW <= 2 ? WW : 1), true>), dim3 (capped (fgrid_log)), dim3 (FK_BLOCK), 0, c->stream, seq, (long) n_bytes, n_ftiles, c->k, mprime, BK, c->d_ctr, \
                             (u32 *) c->slow.p, par, c->fast_mode == 2 ? 1 : 0, LG); \
       else \
-      hipLaunchKernelGGL (scan_fast_kernel<WW>, dim3 (fgrid), dim3 (FK_BLOCK), 0, c->stream, seq, (long) n_bytes, n_ftiles, c->k, mprime, BK, c->d_ctr, \
+      hipLaunchKernelGGL (scan_fast_kernel<WW>, dim3 (capped (fgrid)), dim3 (FK_BLOCK), 0, c->stream, seq, (long) n_bytes, n_ftiles, c->k, mprime, BK, c->d_ctr, \
                           (u32 *) c->slow.p, par, c->fast_mode == 2 ? 1 : 0, LG); \
       const TileSrc listed = {(const u32 *) c->slow.p, (long) FK_OWN}; \
-      hipLaunchKernelGGL (scan_bins_kernel<WW>, dim3 (lgrid), dim3 (TJ_SB_BLOCK), 0, c->stream, seq, (long) n_bytes, 0l, c->k, mprime, BK, c->d_ctr, fix, (u32) TJ_FIX_CAP, par, listed); \
+      hipLaunchKernelGGL (scan_bins_kernel<WW>, dim3 (capped (lgrid)), dim3 (TJ_SB_BLOCK), 0, c->stream, seq, (long) n_bytes, 0l, c->k, mprime, BK, c->d_ctr, fix, (u32) TJ_FIX_CAP, par, listed); \
     } \
     else { \
-      hipLaunchKernelGGL (scan_bins_kernel<WW>, dim3 (grid), dim3 (TJ_SB_BLOCK), 0, c->stream, seq, (long) n_bytes, n_tiles, c->k, mprime, BK, c->d_ctr, fix, (u32) TJ_FIX_CAP, par, plain); \
+      hipLaunchKernelGGL (scan_bins_kernel<WW>, dim3 (capped (grid)), dim3 (TJ_SB_BLOCK), 0, c->stream, seq, (long) n_bytes, n_tiles, c->k, mprime, BK, c->d_ctr, fix, (u32) TJ_FIX_CAP, par, plain); \
       hipLaunchKernelGGL (nrun_fixup_bins_kernel<WW>, dim3 (64), dim3 (256), 0, c->stream, seq, (long) n_bytes, c->k, mprime, BK, c->d_ctr, (const FixEntry *) fix, (u32) TJ_FIX_CAP, par); \
     } \
   } while (0)
@@ -4590,8 +4595,8 @@ static int scan_device_piece (tjamd_counter *c, const void *d_stream, size_t n_b
     HIPCHK (hipEventRecord (c->ev_pa[i], c->stream));
   }
   if (use_log) {
-    if (c->W == 1) hipLaunchKernelGGL (partition_log_kernel<1>, dim3 ((unsigned) (c->n_cu * PL_WG_PER_CU)), dim3 (PL_BLOCK), 0, c->stream, LG, BK, c->d_ctr, c->k);
-    else hipLaunchKernelGGL (partition_log_kernel<2>, dim3 ((unsigned) (c->n_cu * PL_WG_PER_CU)), dim3 (PL_BLOCK), 0, c->stream, LG, BK, c->d_ctr, c->k);
+    if (c->W == 1) hipLaunchKernelGGL (partition_log_kernel<1>, dim3 (capped ((long) c->n_cu * PL_WG_PER_CU)), dim3 (PL_BLOCK), 0, c->stream, LG, BK, c->d_ctr, c->k);
+    else hipLaunchKernelGGL (partition_log_kernel<2>, dim3 (capped ((long) c->n_cu * PL_WG_PER_CU)), dim3 (PL_BLOCK), 0, c->stream, LG, BK, c->d_ctr, c->k);
     HIPCHK (hipGetLastError ());
   }
   if (mid_events) { HIPCHK (hipEventRecord (c->ev_pb[c->n_piece_ev], c->stream)); c->n_piece_ev++; }

@@ -1,5 +1,6 @@
 """One-off differential fuzzing on the GPU box: random parameters and inputs, scan + finalise through the C ABI against
-the CPU oracle (raw count, kept records byte for byte, index ranges, coverage, status).  Not part of the test suite.
+the CPU oracle (raw count, kept records byte for byte, index ranges, coverage, status).  Not part of the test suite
+(which runs a fixed list of seeds of the same generator through every scan variant: tests/test_scan_variants.py).
 usage: python tools/fuzz_gpu.py [seconds] [seed]"""
 import os, sys, time, random
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -7,6 +8,7 @@ sys.path.insert(0, ROOT)
 import numpy as np
 import tatajuba_amd as tj
 from oracle import orc
+from tests.edge_streams import random_stream as _random_stream     # (the suite runs a fixed list of seeds through the same generator: tests/test_scan_variants.py)
 
 budget = float(sys.argv[1]) if len(sys.argv) > 1 else 120.0
 seed = int(sys.argv[2]) if len(sys.argv) > 2 else 12345
@@ -18,33 +20,7 @@ fails = 0
 
 
 def random_stream():
-    mode = rng.choice(["synth", "synth", "synth_ragged", "alphabet", "lowcomplex"])
-    if mode == "synth":
-        n = rng.choice([50, 2000, 30000, 150000, 400000])
-        L = rng.choice([36, 75, 150, 250])
-        g = rng.choice([2000, 50000, 1000000, 20000000])
-        return tj.synth_stream(n, L, g, seed_reads=rng.randrange(1 << 30), variant_seed=rng.randrange(8)), mode
-    if mode == "synth_ragged":
-        n = rng.choice([200, 3000, 20000])
-        return tj.synth_stream(n, 100, rng.choice([50000, 3000000]), seed_reads=rng.randrange(1 << 30),
-                               read_len_max=rng.choice([400, 3000, 20000])), mode
-    if mode == "alphabet":
-        ab = rng.choice(["ACGT", "ACGTN", "ACGTacgtUN-", "AT", "ACGTNNNN"])
-        reads = []
-        for _ in range(rng.choice([10, 300, 3000])):
-            L = rng.randint(0, 400)
-            s = []
-            while len(s) < L:
-                s.extend(rng.choice(ab) * rng.choice([1, 1, 1, 2, 3, 4, 6, 12, 70]))
-            reads.append("".join(s[:L]))
-        return np.frombuffer(("\n".join(reads) + "\n").encode("latin-1"), np.uint8), mode
-    # low complexity: few distinct contexts, huge counts, long tracts (length wrap), skewed buckets
-    unit = "".join(rng.choice("ACGT") for _ in range(rng.randint(1, 9)))
-    reads = []
-    for _ in range(rng.choice([100, 5000, 60000])):
-        t = rng.choice("ACGT") * rng.choice([3, 5, 9, 30, 600, 1100])
-        reads.append((unit * 12)[: rng.randint(5, 60)] + t + (unit * 12)[: rng.randint(5, 60)])
-    return np.frombuffer(("\n".join(reads) + "\n").encode(), np.uint8), mode
+    return _random_stream(rng, tj.synth_stream)
 
 
 while time.time() < t_end:

@@ -4,6 +4,8 @@
 #   quick: parity tests in the default scan mode, scan-only timing, bench line
 #   modes: the parity tests in all three TATAJUBA_AMD_FAST modes as well
 #   full : modes + the instruction counters of the scan kernels (tools/exp_valu.sh)
+# A plain `pytest -m gpu` already runs every scan / sink variant on the edge corpus (tests/test_scan_variants.py, which
+# sets the hooks per counter); "modes" here is for the whole suite -- full-size tests included -- in each mode.
 R=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}
 TAG=${1:-chk}; MODE=${2:-quick}
 O=$R/gpurun_out/$TAG
