@@ -3503,6 +3503,15 @@ __device__ __forceinline__ int meta_count (u64 meta)
   return (c & 0x80000) ? c - 0x100000 : c;
 }
 
+__device__ __forceinline__ int meta_len (u64 meta)
+{ // signed 10-bit read-back of the tract length
+  int l = (int) ((meta >> TJ_META_LEN_SHIFT) & 0x3FFull);
+  return (l & 0x200) ? l - 0x400 : l;
+}
+
+// rows i and j of a record array (three words a row) have the same context and base
+__device__ __forceinline__ bool same_context_rows (const u64 *rec, long i, long j) { return same_context (rec + 3 * i, rec + 3 * j); }
+
 __global__ void seg_heads_kernel (const u64 *__restrict__ rec, long n, u32 *__restrict__ flags, int context_only)
 {
   for (long i = blockIdx.x * (long) blockDim.x + threadIdx.x; i < n; i += (long) gridDim.x * blockDim.x) {
@@ -4087,6 +4096,25 @@ struct DevBuf
 struct DevState { alignas (256) DevCounters ctr; alignas (256) FinCounts fin; alignas (256) u32 cursors[TJ_P + 1]; alignas (256) FinPlan plan;
                   alignas (256) DevCounters snap_ctr; alignas (256) u32 snap_cursors[TJ_P + 1]; alignas (256) u32 pad[4]; };
 
+// One timed interval of a stream: an event in front of the stage's first kernel, one behind its last.  `timed` is the
+// caller's to set: true once the stage has completed, false again where a call that may fail starts (a failed call leaves
+// no timing behind); until then the interval reads as -1.
+struct StageTimer
+{
+  hipEvent_t e0 = nullptr, e1 = nullptr;
+  bool timed = false;
+  hipError_t create () { const hipError_t e = hipEventCreate (&e0); return e != hipSuccess ? e : hipEventCreate (&e1); }
+  void destroy () { if (e0) (void) hipEventDestroy (e0); if (e1) (void) hipEventDestroy (e1); }
+  hipError_t begin (hipStream_t stream) { return hipEventRecord (e0, stream); }
+  hipError_t end (hipStream_t stream) { return hipEventRecord (e1, stream); }
+  bool elapsed (int device, float &ms) const           // waits for the end event
+  { return timed && hipSetDevice (device) == hipSuccess && hipEventSynchronize (e1) == hipSuccess && hipEventElapsedTime (&ms, e0, e1) == hipSuccess; }
+  double ms (int device) const { float f = 0.f; return elapsed (device, f) ? (double) f : -1.0; }
+};
+// the intervals of a counter: the last scan call (its partition kernels between the pieces included: tjamd_last_scan_ms takes
+// them out), finalise, the kernels of tjamd_merge_samples, tjamd_tract_stats, tjamd_union_tracts, tjamd_union_tract_stats
+enum { T_SCAN, T_FIN, T_MERGE, T_TRACT, T_UNION, T_UNION_STATS, TJ_N_TIMERS };
+
 struct tjamd_counter
 {
   int device = 0, k = 0, W = 4, n_cu = 256;
@@ -4105,14 +4133,11 @@ struct tjamd_counter
 #define TJ_PIECE_EVENTS 64
   hipEvent_t ev_pa[TJ_PIECE_EVENTS] = {}, ev_pb[TJ_PIECE_EVENTS] = {};
   int n_piece_ev = 0;
-  hipEvent_t ev_m0 = nullptr, ev_m1 = nullptr; bool merge_timed = false;   // around the kernels of the last tjamd_merge_samples
-  hipEvent_t ev_t0 = nullptr, ev_t1 = nullptr; bool tract_timed = false;   // around the last tjamd_tract_stats
+  StageTimer timer[TJ_N_TIMERS];   // T_SCAN ... T_UNION_STATS
   DevBuf ts_cov, ts_aux;      // tjamd_tract_stats / tjamd_tract_sample_stats: the samples' coverages, error flag + last tract id
-  hipEvent_t ev_u0 = nullptr, ev_u1 = nullptr, ev_v0 = nullptr, ev_v1 = nullptr;   // around the last tjamd_union_tracts / tjamd_union_tract_stats
-  bool union_timed = false, union_stats_timed = false;
   long union_cand = -1;       // retry candidates of the last tjamd_union_tracts
   DevBuf ut_tot, ut_lev, ut_fb, ut_slots;   // union tracts: exact row totals, admitted edit distances, fallback flags, global bars
-  bool part_timed = false;
+  bool part_timed = false;    // the last scan call went through partition_log_kernel: timer[T_SCAN].e1 to ev_p1 is its time
   int fast_mode = 1;          // 1: scan_fast_kernel + the generic kernel on what it leaves; 0: generic kernel only; 2: fast kernel leaves everything (tests)
   u32 pool_chunks = 0, maxj = 0;
   int ch_shift = -1;          // chunk = TJ_CH0 << ch_shift records; fixed by the first scan after a reset
@@ -4131,7 +4156,6 @@ struct tjamd_counter
   bool fine_dirty = false;              // the fine bins hold an aggregation's counts that no clear_buckets_kernel has consumed yet
   bool bins_counted = false;            // clear_buckets_kernel has turned them into the ordering step's bin counts (finalise_binned: no counting pass)
   long n_kept = 0; int n_idx = 0, coverage = 0, status = -1;
-  hipEvent_t ev_s0 = nullptr, ev_s1 = nullptr, ev_f0 = nullptr, ev_f1 = nullptr;
   hipEvent_t ev_done = nullptr;                         // tjamd_finalise_begin: the counts have reached the host
   hipEvent_t ev_agg = nullptr;                          // the aggregation and the clearing of the buckets are done (order_stream waits for it)
   hipStream_t order_stream = nullptr;                   // tjamd_counter_set_order_stream: where a finalise begun with tjamd_finalise_begin runs its ordering step
@@ -4139,7 +4163,6 @@ struct tjamd_counter
   int fin_rb = 0, fin_mc = 0; bool fin_speculative = false, fin_plan_ahead = false; u64 fin_kept_cap = 0;
   hipEvent_t marks[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};   // tjamd_mark / tjamd_wait_mark
   unsigned mark_seq = 0;
-  bool scan_timed = false, fin_timed = false;
   long last_scan_launches = 0;
   unsigned scan_seq = 0;
   size_t piece_target = TJ_SCAN_PIECE_TARGET;           // TATAJUBA_AMD_SCAN_PIECE (bytes) overrides it: tests
@@ -4206,13 +4229,8 @@ extern "C" tjamd_counter *tjamd_counter_create (int device, int kmer_size)
   memset (c->h_state, 0, sizeof (DevState));
   HIPCHK_NULL (hipMemsetAsync (c->d_state, 0, sizeof (DevState), c->stream));
   HIPCHK_NULL (hipMemsetAsync (c->d_lctr, 0, sizeof (DevCounters), c->stream));
-  HIPCHK_NULL (hipEventCreate (&c->ev_s0)); HIPCHK_NULL (hipEventCreate (&c->ev_s1));
-  HIPCHK_NULL (hipEventCreate (&c->ev_f0)); HIPCHK_NULL (hipEventCreate (&c->ev_f1));
+  for (StageTimer &t : c->timer) HIPCHK_NULL (t.create ());
   HIPCHK_NULL (hipEventCreate (&c->ev_p1));
-  HIPCHK_NULL (hipEventCreate (&c->ev_m0)); HIPCHK_NULL (hipEventCreate (&c->ev_m1));
-  HIPCHK_NULL (hipEventCreate (&c->ev_t0)); HIPCHK_NULL (hipEventCreate (&c->ev_t1));
-  HIPCHK_NULL (hipEventCreate (&c->ev_u0)); HIPCHK_NULL (hipEventCreate (&c->ev_u1));
-  HIPCHK_NULL (hipEventCreate (&c->ev_v0)); HIPCHK_NULL (hipEventCreate (&c->ev_v1));
   HIPCHK_NULL (hipEventCreateWithFlags (&c->ev_done, hipEventDisableTiming));
   HIPCHK_NULL (hipEventCreateWithFlags (&c->ev_agg, hipEventDisableTiming));
   HIPCHK_NULL (hipStreamSynchronize (c->stream));
@@ -4234,17 +4252,9 @@ extern "C" void tjamd_counter_destroy (tjamd_counter *c)
   if (c->d_cursors) (void) hipFree (c->d_cursors);
   if (c->h_state) (void) hipHostFree (c->h_state);
   if (c->h_kept) (void) hipHostFree (c->h_kept);
-  if (c->ev_s0) (void) hipEventDestroy (c->ev_s0);
-  if (c->ev_s1) (void) hipEventDestroy (c->ev_s1);
+  for (StageTimer &t : c->timer) t.destroy ();
   if (c->ev_p1) (void) hipEventDestroy (c->ev_p1);
   for (int i = 0; i < TJ_PIECE_EVENTS; i++) { if (c->ev_pa[i]) (void) hipEventDestroy (c->ev_pa[i]); if (c->ev_pb[i]) (void) hipEventDestroy (c->ev_pb[i]); }
-  if (c->ev_m0) (void) hipEventDestroy (c->ev_m0);
-  if (c->ev_m1) (void) hipEventDestroy (c->ev_m1);
-  if (c->ev_t0) (void) hipEventDestroy (c->ev_t0);
-  if (c->ev_t1) (void) hipEventDestroy (c->ev_t1);
-  for (hipEvent_t ev : {c->ev_u0, c->ev_u1, c->ev_v0, c->ev_v1}) if (ev) (void) hipEventDestroy (ev);
-  if (c->ev_f0) (void) hipEventDestroy (c->ev_f0);
-  if (c->ev_f1) (void) hipEventDestroy (c->ev_f1);
   if (c->ev_done) (void) hipEventDestroy (c->ev_done);
   if (c->ev_agg) (void) hipEventDestroy (c->ev_agg);
   if (c->own_stream) (void) hipStreamDestroy (c->own_stream);
@@ -4535,7 +4545,7 @@ static int scan_device_piece (tjamd_counter *c, const void *d_stream, size_t n_b
   const Buckets BK = make_buckets (c);
   FixEntry *fix = (FixEntry *) c->fix.p;
   const int par = (int) (c->scan_seq++ & 1u);            // per-launch counters are double-buffered (DevCounters::lc)
-  if (first) HIPCHK (hipEventRecord (c->ev_s0, c->stream));
+  if (first) HIPCHK (c->timer[T_SCAN].begin (c->stream));
   const TileSrc plain = {nullptr, 0};
   // (TATAJUBA_AMD_SCAN_GRID: the launches below take at most that many workgroups; the storage above stays sized for the full grids)
   auto capped = [c] (long g) { return (unsigned) (c->scan_grid_cap >= 1 ? std::min<long> (g, (long) c->scan_grid_cap) : g); };
@@ -4586,7 +4596,7 @@ static int scan_device_piece (tjamd_counter *c, const void *d_stream, size_t n_b
   }
 #undef TJ_LAUNCH_SCAN
   HIPCHK (hipGetLastError ());
-  if (last) HIPCHK (hipEventRecord (c->ev_s1, c->stream));
+  if (last) HIPCHK (c->timer[T_SCAN].end (c->stream));
   if (first) c->n_piece_ev = 0;
   const bool mid_events = use_log && !last && c->n_piece_ev < TJ_PIECE_EVENTS;
   if (mid_events) {
@@ -4601,7 +4611,7 @@ static int scan_device_piece (tjamd_counter *c, const void *d_stream, size_t n_b
   }
   if (mid_events) { HIPCHK (hipEventRecord (c->ev_pb[c->n_piece_ev], c->stream)); c->n_piece_ev++; }
   if (last) { HIPCHK (hipEventRecord (c->ev_p1, c->stream)); c->part_timed = use_log; }
-  c->scan_timed = true;
+  c->timer[T_SCAN].timed = true;
   c->last_scan_launches = first ? 1 : c->last_scan_launches + 1;
   c->status = -1;
   return TJAMD_OK;
@@ -4895,8 +4905,8 @@ static int finalise_radix (tjamd_counter *c, long n1, int min_coverage)
   HIPCHK (hipGetLastError ());
   hipLaunchKernelGGL (cov_max_kernel, dim3 (std::min<unsigned> (grid_for (t), 256u)), dim3 (256), 0, c->stream, (const u64 *) ctab, t, &c->d_fin->coverage);
   HIPCHK (hipGetLastError ());
-  HIPCHK (hipEventRecord (c->ev_f1, c->stream));
-  c->fin_timed = true;
+  HIPCHK (c->timer[T_FIN].end (c->stream));
+  c->timer[T_FIN].timed = true;
   HIPCHK (hipMemcpyAsync (c->h_fin, c->d_fin, sizeof (FinCounts), hipMemcpyDeviceToHost, c->stream));
   HIPCHK (hipStreamSynchronize (c->stream));
   return TJAMD_OK;
@@ -4956,8 +4966,8 @@ static int finalise_binned (tjamd_counter *c, long n1, int min_coverage, long ca
   hipLaunchKernelGGL (bin_ctx_write_kernel, dim3 (256), dim3 (256), 0, st, (const u32 *) binstart, (const u32 *) binctx, (const u32 *) binout, nbins,
                       (const u32 *) tstart, (const u32 *) tend, (int *) c->idx_i.p, (int *) c->idx_f.p, (const u64 *) ctab, t, c->d_fin, plan);
   HIPCHK (hipGetLastError ());
-  HIPCHK (hipEventRecord (c->ev_f1, st));
-  c->fin_timed = true;
+  HIPCHK (c->timer[T_FIN].end (st));
+  c->timer[T_FIN].timed = true;
   if (planned) HIPCHK (hipMemcpyAsync (c->h_state, c->d_state, sizeof (DevState), hipMemcpyDeviceToHost, st));   // (counts of the sample, plan, results: one copy)
   else HIPCHK (hipMemcpyAsync (c->h_fin, c->d_fin, sizeof (FinCounts), hipMemcpyDeviceToHost, c->stream));
   if (wait) HIPCHK (hipStreamSynchronize (c->stream));
@@ -5004,7 +5014,7 @@ static int finalise_impl (tjamd_counter *c, int remove_biased, int min_coverage,
   // above one), so half of the host's running upper bound of the raw count is a safe capacity: unless that is a lot of
   // memory, the aggregation is launched without first asking the device (one host round trip less) and the exact
   // counts and error flags, copied in stream order before the buckets are cleared, are looked at afterwards.
-  c->n_kept = 0; c->n_idx = 0; c->coverage = 0; c->fin_timed = false;
+  c->n_kept = 0; c->n_idx = 0; c->coverage = 0; c->timer[T_FIN].timed = false;
   speculative = (c->raw_bound / 2 + 1) * 24 <= (8ull << 30);
   kept_cap = c->raw_bound / 2 + 1;
   if (!speculative) {
@@ -5019,7 +5029,7 @@ static int finalise_impl (tjamd_counter *c, int remove_biased, int min_coverage,
   rc = ensure (c->kept, (size_t) kept_cap * 24, c->stream);
   if (!rc) rc = ensure (c->ovf, c->pool.cap, c->stream);   // second pool for the aggregation's leftover rounds
   if (rc) return rc;
-  HIPCHK (hipEventRecord (c->ev_f0, c->stream));
+  HIPCHK (c->timer[T_FIN].begin (c->stream));
   const Buckets BK = make_buckets (c);
   // The ordering step is launched right behind the aggregation, sized on the device (plan_tail, by the aggregation's last
   // workgroup) for up to kept_cap / 8 records -- a sample keeps a per cent or so of its raw records -- so that the whole
@@ -5084,7 +5094,7 @@ second_half:
   if (plan_ahead ? c->h_state->plan.kept_overflow : c->h_fin->overflow) return set_err (TJAMD_ERR_CAPACITY, "kept list overflow");
   const long n1 = plan_ahead ? c->h_state->plan.n1 : (long) c->h_fin->n_kept;
   if (n1 == 0) {                                                               // reference :376-381
-    HIPCHK (hipEventRecord (c->ev_f1, c->stream)); c->fin_timed = true;
+    HIPCHK (c->timer[T_FIN].end (c->stream)); c->timer[T_FIN].timed = true;
     c->status = 2; if (status) *status = 2; return TJAMD_OK;
   }
 
@@ -5151,21 +5161,15 @@ extern "C" long tjamd_download_idx (tjamd_counter *c, int *idx_initial, int *idx
 
 extern "C" double tjamd_last_scan_ms (tjamd_counter *c)
 {
-  if (!c || !c->scan_timed) return -1.0;
   float ms = 0.f;
-  if (hipSetDevice (c->device) != hipSuccess || hipEventSynchronize (c->ev_s1) != hipSuccess || hipEventElapsedTime (&ms, c->ev_s0, c->ev_s1) != hipSuccess) return -1.0;
+  if (!c || !c->timer[T_SCAN].elapsed (c->device, ms)) return -1.0;
   // (a stream scanned in pieces: the partition kernels between the scans are not the scan's time)
   for (int i = 0; i < c->n_piece_ev; i++) { float p = 0.f; if (hipEventElapsedTime (&p, c->ev_pa[i], c->ev_pb[i]) == hipSuccess) ms -= p; }
   return (double) ms;
 }
 
-extern "C" double tjamd_last_merge_ms (tjamd_counter *c)
-{ // the kernels of the last tjamd_merge_samples on this counter (bin path), HIP events on its stream
-  if (!c || !c->merge_timed) return -1.0;
-  float ms = 0.f;
-  if (hipSetDevice (c->device) != hipSuccess || hipEventSynchronize (c->ev_m1) != hipSuccess || hipEventElapsedTime (&ms, c->ev_m0, c->ev_m1) != hipSuccess) return -1.0;
-  return (double) ms;
-}
+// the kernels of the last tjamd_merge_samples on this counter (bin path), HIP events on its stream
+extern "C" double tjamd_last_merge_ms (tjamd_counter *c) { return c ? c->timer[T_MERGE].ms (c->device) : -1.0; }
 
 // 1: one-word records go through the record log and partition_log_kernel (k <= 12, the default); 0: every scan kernel
 // partitions its records itself
@@ -5173,21 +5177,15 @@ extern "C" int tjamd_counter_uses_log (const tjamd_counter *c) { return (c && c-
 
 extern "C" double tjamd_last_partition_ms (tjamd_counter *c)
 { // partition_log_kernel behind the last scan launch (k <= 12, record log); 0 when the scan partitioned by itself
-  if (!c || !c->scan_timed) return -1.0;
+  if (!c || !c->timer[T_SCAN].timed) return -1.0;
   if (!c->part_timed) return 0.0;
   float ms = 0.f;
-  if (hipSetDevice (c->device) != hipSuccess || hipEventSynchronize (c->ev_p1) != hipSuccess || hipEventElapsedTime (&ms, c->ev_s1, c->ev_p1) != hipSuccess) return -1.0;
+  if (hipSetDevice (c->device) != hipSuccess || hipEventSynchronize (c->ev_p1) != hipSuccess || hipEventElapsedTime (&ms, c->timer[T_SCAN].e1, c->ev_p1) != hipSuccess) return -1.0;
   for (int i = 0; i < c->n_piece_ev; i++) { float p = 0.f; if (hipEventElapsedTime (&p, c->ev_pa[i], c->ev_pb[i]) == hipSuccess) ms += p; }   // (the pieces before the last)
   return (double) ms;
 }
 
-extern "C" double tjamd_last_finalise_ms (tjamd_counter *c)
-{
-  if (!c || !c->fin_timed) return -1.0;
-  float ms = 0.f;
-  if (hipSetDevice (c->device) != hipSuccess || hipEventSynchronize (c->ev_f1) != hipSuccess || hipEventElapsedTime (&ms, c->ev_f0, c->ev_f1) != hipSuccess) return -1.0;
-  return (double) ms;
-}
+extern "C" double tjamd_last_finalise_ms (tjamd_counter *c) { return c ? c->timer[T_FIN].ms (c->device) : -1.0; }
 
 extern "C" long tjamd_last_scan_launches (tjamd_counter *c) { return c ? c->last_scan_launches : -1; }
 extern "C" long tjamd_plan_mismatches (tjamd_counter *c) { return c ? c->plan_mismatches : -1; }
@@ -5248,8 +5246,7 @@ __global__ void group_summary_kernel (const u64 *__restrict__ kept, long n, cons
     int mode_count = 0;
     for (long j = i; j < n && (j == i || !head[j]); j++) {   // (reference: context_histogram_add_hopo_elem, src/context_histogram.c:181-222)
       const u64 m = kept[3 * j + 2];
-      int cnt = (int) ((m >> TJ_META_COUNT_SHIFT) & 0xFFFFFull);
-      if (cnt & 0x80000) cnt -= 0x100000;               // signed 20-bit field
+      const int cnt = meta_count (m);
       if (j == i || kept[3 * j] != kept[3 * (j - 1)] || kept[3 * j + 1] != kept[3 * (j - 1) + 1]) o.n_context++;
       if (j == i || mode_count < cnt) { mode_count = cnt; o.mode = (int) j; }
       o.integral += cnt; o.n_elem++;
@@ -5257,39 +5254,6 @@ __global__ void group_summary_kernel (const u64 *__restrict__ kept, long n, cons
     }
     groups[g] = o;
   }
-}
-
-extern "C" long tjamd_group_contexts (tjamd_counter *c, int max_distance_per_flank, int *group_of, tjamd_group *groups, long capacity)
-{
-  if (!c || max_distance_per_flank < 0) return -set_err (TJAMD_ERR_ARG, "bad arguments");
-  if (c->status < 0) return -set_err (TJAMD_ERR_STATE, "tjamd_group_contexts needs a finalised counter");
-  if (hipSetDevice (c->device) != hipSuccess) return -set_err (TJAMD_ERR_HIP, "hipSetDevice failed");
-  const long n = c->n_kept;
-  if (n == 0) return 0;
-  static_assert (sizeof (GroupOut) == sizeof (tjamd_group), "group layout");
-  int rc = ensure (c->headpos, (size_t) n * 4, c->stream);          // back[]
-  if (!rc) rc = ensure (c->flags, (size_t) n * 4, c->stream);      // head flags
-  if (!rc) rc = ensure (c->outpos, (size_t) n * 4, c->stream);     // groups before each element
-  if (!rc) rc = ensure (c->segid, (size_t) n * 4, c->stream);      // group_of
-  if (!rc) rc = ensure (c->scan_tmp, scan_tmp_words (n) * 4 + 64, c->stream);
-  if (!rc) rc = ensure (c->alt, (size_t) n * sizeof (GroupOut), c->stream);
-  if (rc) return -rc;
-  const u64 *kept = (const u64 *) c->kept.p;
-  u32 *total = (u32 *) c->scan_tmp.p + scan_tmp_words (n);
-  hipLaunchKernelGGL (group_back_kernel, dim3 (grid_for (n)), dim3 (256), 0, c->stream, kept, n, max_distance_per_flank, (int *) c->headpos.p);
-  hipLaunchKernelGGL (group_resolve_kernel, dim3 (grid_for (n)), dim3 (256), 0, c->stream, (const int *) c->headpos.p, n, (u32 *) c->flags.p);
-  rc = exclusive_scan (c, (const u32 *) c->flags.p, (u32 *) c->outpos.p, n, total, (u32 *) c->scan_tmp.p, scan_tmp_words (n));
-  if (rc) return -rc;
-  hipLaunchKernelGGL (group_summary_kernel, dim3 (grid_for (n)), dim3 (256), 0, c->stream, kept, n, (const u32 *) c->flags.p, (const u32 *) c->outpos.p,
-                      (int *) c->segid.p, (GroupOut *) c->alt.p);
-  if (hipGetLastError () != hipSuccess) return -set_err (TJAMD_ERR_HIP, "grouping launch failed");
-  u32 ng = 0;
-  if (hipMemcpyAsync (&ng, total, 4, hipMemcpyDeviceToHost, c->stream) != hipSuccess || hipStreamSynchronize (c->stream) != hipSuccess)
-    return -set_err (TJAMD_ERR_HIP, "grouping failed: %s", hipGetErrorString (hipGetLastError ()));
-  if ((long) ng > capacity && groups) return -set_err (TJAMD_ERR_CAPACITY, "%u groups, caller capacity %ld", ng, capacity);
-  if (group_of && hipMemcpy (group_of, c->segid.p, (size_t) n * 4, hipMemcpyDeviceToHost) != hipSuccess) return -set_err (TJAMD_ERR_HIP, "copy failed");
-  if (groups && hipMemcpy (groups, c->alt.p, (size_t) ng * sizeof (GroupOut), hipMemcpyDeviceToHost) != hipSuccess) return -set_err (TJAMD_ERR_HIP, "copy failed");
-  return (long) ng;
 }
 
 // ---- the whole grouping step of new_genomic_context_list (reference: src/context_histogram.c:245-270): an element that
@@ -5455,6 +5419,80 @@ void group_repair_kernel (const u64 *__restrict__ kept, long n, int k, int maxd,
   }
 }
 
+// The words behind the scan's own in c->scan_tmp: [0] receives the scan's total, [1] counts the candidates of the retry
+static u32 *scan_total (tjamd_counter *c, long n) { return (u32 *) c->scan_tmp.p + scan_tmp_words (n); }
+
+// scratch of queue_group_heads for n rows (retry: the retry's as well)
+static int ensure_group_scratch (tjamd_counter *c, long n, bool retry)
+{
+  int rc = ensure (c->headpos, (size_t) n * 4, c->stream);          // back[]
+  if (!rc) rc = ensure (c->flags, (size_t) n * 4, c->stream);      // head flags
+  if (!rc) rc = ensure (c->outpos, (size_t) n * 4, c->stream);     // groups before each row
+  if (!rc) rc = ensure (c->scan_tmp, scan_tmp_words (n) * 4 + 64, c->stream);
+  if (retry && !rc) rc = ensure (c->keep, (size_t) n * 4, c->stream);       // candidates of the retry
+  if (retry && !rc) rc = ensure (c->grp_jt, (size_t) n * 4, c->stream);     // join types
+  return rc;
+}
+
+// Queues the grouping of the n rows of keys (tjamd_record[n] on the device) on the counter's stream, scratch from
+// ensure_group_scratch.  It leaves the head flags (1 on the row that opens a group) in c->flags, the number of groups
+// before each row in c->outpos and the number of groups in scan_total (c, n)[0]: on the device, the caller fetches it with
+// its own results.  retry false: the flank test alone, nothing else is touched.  retry true: the edit-distance retry as
+// well, a row's count coming from count_of; the join type of every row (GJ_ADDS_CONTEXT above, not yet & 3) is left in
+// c->grp_jt, the distance that admitted each row of type 2 in lev_of, the number of candidates in *n_cand (either may be null);
+// c->keep is used up.  Fetching that number is the one host round trip.  who: what the messages begin with.
+template <class CountOf>
+static int queue_group_heads (tjamd_counter *c, const char *who, const u64 *keys, long n, int maxd, CountOf count_of,
+                              bool retry, int lev, int *lev_of, long *n_cand)
+{
+  u32 *head = (u32 *) c->flags.p, *total = scan_total (c, n), *d_cand = total + 1;
+  hipLaunchKernelGGL (group_back_kernel, dim3 (grid_for (n)), dim3 (256), 0, c->stream, keys, n, maxd, (int *) c->headpos.p);
+  hipLaunchKernelGGL (group_resolve_kernel, dim3 (grid_for (n)), dim3 (256), 0, c->stream, (const int *) c->headpos.p, n, head);
+  if (retry) {
+    if (hipMemsetAsync (d_cand, 0, 4, c->stream) != hipSuccess) return set_err (TJAMD_ERR_HIP, "memset failed");
+    // (which reading of the absent edit distance's last argument: looked up per call -- tests switch it)
+    const char *ed = getenv ("TATAJUBA_AMD_EDIT_DISTANCE");
+    const int free_end = (ed && !strcmp (ed, "free_end")) ? 1 : 0;
+    hipLaunchKernelGGL (group_speculate_kernel<CountOf>, dim3 (grid_for (n)), dim3 (256), 0, c->stream, keys, n, c->k, lev, free_end,
+                        (const u32 *) head, (u32 *) c->keep.p, (int *) c->grp_jt.p, d_cand, count_of);
+    if (hipGetLastError () != hipSuccess) return set_err (TJAMD_ERR_HIP, "%sgrouping launch failed", who);
+    u32 nc = 0;
+    if (hipMemcpyAsync (&nc, d_cand, 4, hipMemcpyDeviceToHost, c->stream) != hipSuccess || hipStreamSynchronize (c->stream) != hipSuccess)
+      return set_err (TJAMD_ERR_HIP, "%sgrouping failed: %s", who, hipGetErrorString (hipGetLastError ()));
+    if (nc) hipLaunchKernelGGL (group_repair_kernel<CountOf>, dim3 (1), dim3 (256), 0, c->stream, keys, n, c->k, maxd, lev, free_end,
+                                head, (const u32 *) c->keep.p, (int *) c->grp_jt.p, count_of, lev_of);
+    if (n_cand) *n_cand = (long) nc;
+  }
+  return exclusive_scan (c, (const u32 *) head, (u32 *) c->outpos.p, n, total, (u32 *) c->scan_tmp.p, scan_tmp_words (n));
+}
+
+extern "C" long tjamd_group_contexts (tjamd_counter *c, int max_distance_per_flank, int *group_of, tjamd_group *groups, long capacity)
+{
+  if (!c || max_distance_per_flank < 0) return -set_err (TJAMD_ERR_ARG, "bad arguments");
+  if (c->status < 0) return -set_err (TJAMD_ERR_STATE, "tjamd_group_contexts needs a finalised counter");
+  if (hipSetDevice (c->device) != hipSuccess) return -set_err (TJAMD_ERR_HIP, "hipSetDevice failed");
+  const long n = c->n_kept;
+  if (n == 0) return 0;
+  static_assert (sizeof (GroupOut) == sizeof (tjamd_group), "group layout");
+  int rc = ensure_group_scratch (c, n, false);
+  if (!rc) rc = ensure (c->segid, (size_t) n * 4, c->stream);      // group_of
+  if (!rc) rc = ensure (c->alt, (size_t) n * sizeof (GroupOut), c->stream);
+  if (rc) return -rc;
+  const u64 *kept = (const u64 *) c->kept.p;
+  rc = queue_group_heads (c, "", kept, n, max_distance_per_flank, MetaCount (), false, 0, nullptr, nullptr);   // the flank test alone
+  if (rc) return -rc;
+  hipLaunchKernelGGL (group_summary_kernel, dim3 (grid_for (n)), dim3 (256), 0, c->stream, kept, n, (const u32 *) c->flags.p, (const u32 *) c->outpos.p,
+                      (int *) c->segid.p, (GroupOut *) c->alt.p);
+  if (hipGetLastError () != hipSuccess) return -set_err (TJAMD_ERR_HIP, "grouping launch failed");
+  u32 ng = 0;
+  if (hipMemcpyAsync (&ng, scan_total (c, n), 4, hipMemcpyDeviceToHost, c->stream) != hipSuccess || hipStreamSynchronize (c->stream) != hipSuccess)
+    return -set_err (TJAMD_ERR_HIP, "grouping failed: %s", hipGetErrorString (hipGetLastError ()));
+  if ((long) ng > capacity && groups) return -set_err (TJAMD_ERR_CAPACITY, "%u groups, caller capacity %ld", ng, capacity);
+  if (group_of && hipMemcpy (group_of, c->segid.p, (size_t) n * 4, hipMemcpyDeviceToHost) != hipSuccess) return -set_err (TJAMD_ERR_HIP, "copy failed");
+  if (groups && hipMemcpy (groups, c->alt.p, (size_t) ng * sizeof (GroupOut), hipMemcpyDeviceToHost) != hipSuccess) return -set_err (TJAMD_ERR_HIP, "copy failed");
+  return (long) ng;
+}
+
 struct CtxGroupOut { int first, n_elem, n_context, mode, indel, n_len, modal_len, modal_freq; long long integral; };
 struct LenFreq { int length, freq; };
 
@@ -5470,8 +5508,7 @@ __global__ void group_histogram_kernel (const u64 *__restrict__ kept, long n, co
     for (long j = i; j < n && (j == i || !head[j]); j++) {
       const u64 m = kept[3 * j + 2];
       const int cnt = meta_count (m);
-      int len = (int) ((m >> TJ_META_LEN_SHIFT) & 0x3FFull);
-      if (len & 0x200) len -= 0x400;                    // signed 10-bit field
+      const int len = meta_len (m);
       // contexts of the histogram (reference: context_histogram_add_hopo_elem, src/context_histogram.c:184-190): one more unless
       // the distance loop met an identical context; an element taken in by the indel retry is appended whatever the list holds
       const int t = jt[j];
@@ -5506,38 +5543,19 @@ extern "C" long tjamd_context_histograms (tjamd_counter *c, int max_distance_per
   const long n = c->n_kept;
   if (n == 0) return 0;
   static_assert (sizeof (CtxGroupOut) == sizeof (tjamd_context_group) && sizeof (LenFreq) == sizeof (tjamd_length_freq), "group layout");
-  int rc = ensure (c->headpos, (size_t) n * 4, c->stream);          // back[]
-  if (!rc) rc = ensure (c->flags, (size_t) n * 4, c->stream);      // head flags
-  if (!rc) rc = ensure (c->outpos, (size_t) n * 4, c->stream);     // groups before each element
+  int rc = ensure_group_scratch (c, n, true);
   if (!rc) rc = ensure (c->segid, (size_t) n * 4, c->stream);      // group_of
-  if (!rc) rc = ensure (c->keep, (size_t) n * 4, c->stream);       // candidates of the retry
-  if (!rc) rc = ensure (c->grp_jt, (size_t) n * 4, c->stream);
   if (!rc) rc = ensure (c->grp_hist, (size_t) n * sizeof (LenFreq), c->stream);
-  if (!rc) rc = ensure (c->scan_tmp, scan_tmp_words (n) * 4 + 64, c->stream);
   if (!rc) rc = ensure (c->alt, (size_t) n * sizeof (CtxGroupOut), c->stream);
   if (rc) return -rc;
   const u64 *kept = (const u64 *) c->kept.p;
-  u32 *total = (u32 *) c->scan_tmp.p + scan_tmp_words (n), *n_cand = total + 1;
-  hipLaunchKernelGGL (group_back_kernel, dim3 (grid_for (n)), dim3 (256), 0, c->stream, kept, n, max_distance_per_flank, (int *) c->headpos.p);
-  hipLaunchKernelGGL (group_resolve_kernel, dim3 (grid_for (n)), dim3 (256), 0, c->stream, (const int *) c->headpos.p, n, (u32 *) c->flags.p);
-  if (hipMemsetAsync (n_cand, 0, 4, c->stream) != hipSuccess) return -set_err (TJAMD_ERR_HIP, "memset failed");
-  // (which reading of the absent edit distance's last argument: looked up per call -- tests switch it)
-  const char *ed = getenv ("TATAJUBA_AMD_EDIT_DISTANCE");
-  const int free_end = (ed && !strcmp (ed, "free_end")) ? 1 : 0;
-  hipLaunchKernelGGL (group_speculate_kernel<MetaCount>, dim3 (grid_for (n)), dim3 (256), 0, c->stream, kept, n, c->k, levenshtein_distance, free_end,
-                      (const u32 *) c->flags.p, (u32 *) c->keep.p, (int *) c->grp_jt.p, n_cand, MetaCount ());
-  u32 nc = 0;
-  if (hipMemcpyAsync (&nc, n_cand, 4, hipMemcpyDeviceToHost, c->stream) != hipSuccess || hipStreamSynchronize (c->stream) != hipSuccess)
-    return -set_err (TJAMD_ERR_HIP, "grouping failed: %s", hipGetErrorString (hipGetLastError ()));
-  if (nc) hipLaunchKernelGGL (group_repair_kernel<MetaCount>, dim3 (1), dim3 (256), 0, c->stream, kept, n, c->k, max_distance_per_flank, levenshtein_distance,
-                              free_end, (u32 *) c->flags.p, (const u32 *) c->keep.p, (int *) c->grp_jt.p, MetaCount (), (int *) nullptr);
-  rc = exclusive_scan (c, (const u32 *) c->flags.p, (u32 *) c->outpos.p, n, total, (u32 *) c->scan_tmp.p, scan_tmp_words (n));
+  rc = queue_group_heads (c, "", kept, n, max_distance_per_flank, MetaCount (), true, levenshtein_distance, nullptr, nullptr);
   if (rc) return -rc;
   hipLaunchKernelGGL (group_histogram_kernel, dim3 (grid_for (n)), dim3 (256), 0, c->stream, kept, n, (const u32 *) c->flags.p, (const u32 *) c->outpos.p,
                       (int *) c->grp_jt.p, (int *) c->segid.p, (CtxGroupOut *) c->alt.p, (LenFreq *) c->grp_hist.p);
   if (hipGetLastError () != hipSuccess) return -set_err (TJAMD_ERR_HIP, "grouping launch failed");
   u32 ng = 0;
-  if (hipMemcpyAsync (&ng, total, 4, hipMemcpyDeviceToHost, c->stream) != hipSuccess || hipStreamSynchronize (c->stream) != hipSuccess)
+  if (hipMemcpyAsync (&ng, scan_total (c, n), 4, hipMemcpyDeviceToHost, c->stream) != hipSuccess || hipStreamSynchronize (c->stream) != hipSuccess)
     return -set_err (TJAMD_ERR_HIP, "grouping failed: %s", hipGetErrorString (hipGetLastError ()));
   if ((long) ng > capacity && groups) return -set_err (TJAMD_ERR_CAPACITY, "%u groups, caller capacity %ld", ng, capacity);
   if (group_of && hipMemcpy (group_of, c->segid.p, (size_t) n * 4, hipMemcpyDeviceToHost) != hipSuccess) return -set_err (TJAMD_ERR_HIP, "copy failed");
@@ -5553,7 +5571,7 @@ extern "C" long tjamd_context_histograms (tjamd_counter *c, int max_distance_per
 __global__ void tract_head_kernel (const u64 *__restrict__ keys, long n, u32 *__restrict__ head)
 {
   for (long i = blockIdx.x * (long) blockDim.x + threadIdx.x; i < n; i += (long) gridDim.x * blockDim.x)
-    head[i] = (i > 0 && (keys[3 * i] != keys[3 * (i - 1)] || keys[3 * i + 1] != keys[3 * (i - 1) + 1] || ((keys[3 * i + 2] ^ keys[3 * (i - 1) + 2]) & 3ull))) ? 1u : 0u;
+    head[i] = (i > 0 && !same_context_rows (keys, i, i - 1)) ? 1u : 0u;
 }
 __global__ void tract_id_kernel (const u32 *__restrict__ excl, const u32 *__restrict__ head, long n, int *__restrict__ id)
 {
@@ -5587,7 +5605,7 @@ extern "C" long tjamd_tract_ids (tjamd_counter *c, const void *d_keys, long n, i
   if (n == 0) return 0;
   int rc = ensure_tract_id_scratch (c, n);
   if (rc) return -rc;
-  u32 *total = (u32 *) c->scan_tmp.p + scan_tmp_words (n);
+  u32 *total = scan_total (c, n);
   int *ids = d_tract_id ? d_tract_id : (int *) c->segid.p;
   rc = queue_tract_ids (c, d_keys, n, ids, total);
   if (rc) return -rc;
@@ -5634,10 +5652,8 @@ __device__ bool tract_sample_values (const u64 *__restrict__ keys, const int *__
   for (long r = first; r < end; r++) {
     const int cnt = counts[r * ns + s];
     if (cnt == 0) continue;
-    const u64 m = keys[3 * r + 2];
-    int len = (int) ((m >> TJ_META_LEN_SHIFT) & 0x3FFull);
-    if (len & 0x200) len -= 0x400;                      // signed 10-bit field, as group_histogram_kernel reads it
-    if (prev < 0 || keys[3 * r] != keys[3 * prev] || keys[3 * r + 1] != keys[3 * prev + 1] || ((m ^ keys[3 * prev + 2]) & 3ull)) nctx++;
+    const int len = meta_len (keys[3 * r + 2]);
+    if (prev < 0 || !same_context_rows (keys, r, prev)) nctx++;
     if (prev < 0 || cnt > maxc || (cnt == maxc && len > modal)) { maxc = cnt; modal = len; }
     integral += cnt;
     prev = r;
@@ -5650,8 +5666,7 @@ __device__ bool tract_sample_values (const u64 *__restrict__ keys, const int *__
   for (long r = first; r <= prev; r++) {                // the reference's sums, bar by bar (:746-747, :758-761)
     const int cnt = counts[r * ns + s];
     if (cnt == 0) continue;
-    int len = (int) ((keys[3 * r + 2] >> TJ_META_LEN_SHIFT) & 0x3FFull);
-    if (len & 0x200) len -= 0x400;
+    const int len = meta_len (keys[3 * r + 2]);
     avg += (double) ((long long) cnt * len) / I;
     const double x = (double) cnt / I;
     ent += x * log (x);
@@ -5667,6 +5682,59 @@ __device__ bool tract_sample_values (const u64 *__restrict__ keys, const int *__
 
 __device__ __forceinline__ double dmax_ref (double a, double b) { return (a < b) ? b : a; }   // relative_difference_of_vector's comparisons
 __device__ __forceinline__ double dmin_ref (double a, double b) { return (a > b) ? b : a; }
+
+// What a segment of S lanes gathers about one tract, a lane taking samples lane, lane + S, ...: the largest and smallest of
+// each of the five values over the samples that have the tract, how many have it, whether one's modal length is off the
+// reference's (ref > 0).  Both statistics kernels fill it; how a sample's five values are computed is theirs.
+struct TractSpread
+{
+  double mx[TJAMD_N_TRACT_STATS], mn[TJAMD_N_TRACT_STATS];
+  int present = 0, off_ref = 0;
+  __device__ __forceinline__ TractSpread () { for (int j = 0; j < TJAMD_N_TRACT_STATS; j++) { mx[j] = -FLT_MAX; mn[j] = FLT_MAX; } }
+  __device__ __forceinline__ void add (const double *v, int modal_len, int ref)
+  { // one sample that has the tract
+    present++;
+    if (ref > 0 && modal_len != ref) off_ref = 1;
+    for (int j = 0; j < TJAMD_N_TRACT_STATS; j++) { mx[j] = dmax_ref (mx[j], v[j]); mn[j] = dmin_ref (mn[j], v[j]); }
+  }
+  __device__ __forceinline__ void reduce (int S)
+  { // over the segment: every lane ends with the whole
+    for (int o = 1; o < S; o <<= 1) {
+      present += __shfl_xor (present, o, S);
+      off_ref |= __shfl_xor (off_ref, o, S);
+      for (int j = 0; j < TJAMD_N_TRACT_STATS; j++) {
+        mx[j] = dmax_ref (mx[j], __shfl_xor (mx[j], o, S));
+        mn[j] = dmin_ref (mn[j], __shfl_xor (mn[j], o, S));
+      }
+    }
+  }
+  __device__ __forceinline__ int finish (int ns, double *reldiff) const
+  { // relative_difference_of_vector per value; returns whether the tract is variable (update_descriptive_stats_for_this_trait)
+    for (int j = 0; j < TJAMD_N_TRACT_STATS; j++) reldiff[j] = (mx[j] > DBL_MIN) ? mx[j] - mn[j] : 0.0;
+    const double difference = reldiff[TJAMD_STAT_AVG_LENGTH] + reldiff[TJAMD_STAT_MODAL_FREQ] + reldiff[TJAMD_STAT_ENTROPY];
+    return (present < ns || difference > 1.e-5 || off_ref) ? 1 : 0;
+  }
+};
+
+// An entry of a caller's list of tracts against the summaries it names (TractSummary, UnionSummary: both begin with first,
+// n_rows): the tract's rows; no rows and err |= 1 where the id is outside [0, n_tracts) or the rows outside the union.
+template <class Summary>
+__device__ __forceinline__ void listed_tract_rows (const Summary *sum, long n_tracts, long n_union, int t, int lane, int *err, long &first, long &end)
+{
+  first = 0; end = 0;
+  if (t >= 0 && t < n_tracts) { first = sum[t].first; end = first + (long) sum[t].n_rows; }
+  const bool ok = t >= 0 && t < n_tracts && first >= 0 && first <= end && end <= n_union;
+  if (!ok) { if (lane == 0) atomicOr (err, 1); first = end = 0; }
+}
+
+// sample s of list entry i: its five values, modal length and n_context (the last two may be null)
+__device__ __forceinline__ void write_listed_sample (long i, int s, int ns, const double *v, int ml, int nc,
+                                                     double *__restrict__ values, int *__restrict__ modal_len, int *__restrict__ n_context)
+{
+  for (int j = 0; j < TJAMD_N_TRACT_STATS; j++) values[(i * TJAMD_N_TRACT_STATS + j) * ns + s] = v[j];
+  if (modal_len) modal_len[i * ns + s] = ml;
+  if (n_context) n_context[i * ns + s] = nc;
+}
 
 __global__ __launch_bounds__ (256)
 void tract_stats_kernel (const u64 *__restrict__ keys, const int *__restrict__ counts, long n_union, int ns, int S, const int *__restrict__ cov,
@@ -5685,30 +5753,17 @@ void tract_stats_kernel (const u64 *__restrict__ keys, const int *__restrict__ c
       continue;
     }
     const int ref = ref_len ? ref_len[t] : 0;
-    double mx[TJAMD_N_TRACT_STATS], mn[TJAMD_N_TRACT_STATS], v[TJAMD_N_TRACT_STATS];
-    for (int j = 0; j < TJAMD_N_TRACT_STATS; j++) { mx[j] = -FLT_MAX; mn[j] = FLT_MAX; }
-    int present = 0, off_ref = 0;
+    TractSpread sp;
     for (int s = lane; s < ns; s += S) {
+      double v[TJAMD_N_TRACT_STATS];
       int ml, nc;
-      if (!tract_sample_values (keys, counts, ns, first, end, s, cov[s], v, ml, nc)) continue;
-      present++;
-      if (ref > 0 && ml != ref) off_ref = 1;
-      for (int j = 0; j < TJAMD_N_TRACT_STATS; j++) { mx[j] = dmax_ref (mx[j], v[j]); mn[j] = dmin_ref (mn[j], v[j]); }
+      if (tract_sample_values (keys, counts, ns, first, end, s, cov[s], v, ml, nc)) sp.add (v, ml, ref);
     }
-    for (int o = 1; o < S; o <<= 1) {
-      present += __shfl_xor (present, o, S);
-      off_ref |= __shfl_xor (off_ref, o, S);
-      for (int j = 0; j < TJAMD_N_TRACT_STATS; j++) {
-        mx[j] = dmax_ref (mx[j], __shfl_xor (mx[j], o, S));
-        mn[j] = dmin_ref (mn[j], __shfl_xor (mn[j], o, S));
-      }
-    }
+    sp.reduce (S);
     if (lane == 0) {
       TractSummary o;
-      o.first = (int) first; o.n_rows = (int) (end - first); o.n_present = present;
-      for (int j = 0; j < TJAMD_N_TRACT_STATS; j++) o.reldiff[j] = (mx[j] > DBL_MIN) ? mx[j] - mn[j] : 0.0;
-      const double difference = o.reldiff[TJAMD_STAT_AVG_LENGTH] + o.reldiff[TJAMD_STAT_MODAL_FREQ] + o.reldiff[TJAMD_STAT_ENTROPY];
-      o.variable = (present < ns || difference > 1.e-5 || off_ref) ? 1 : 0;
+      o.first = (int) first; o.n_rows = (int) (end - first); o.n_present = sp.present;
+      o.variable = sp.finish (ns, o.reldiff);
       sum[t] = o;
       varflag[t] = (u32) o.variable;
     }
@@ -5729,18 +5784,13 @@ void tract_sample_stats_kernel (const u64 *__restrict__ keys, const int *__restr
   const int lane = threadIdx.x & (S - 1);
   const long segs_per_grid = (long) gridDim.x * (blockDim.x / S);
   for (long i = (blockIdx.x * (long) blockDim.x + threadIdx.x) / S; i < n_list; i += segs_per_grid) {
-    const int t = list[i];
-    long first = 0, end = 0;
-    if (t >= 0 && t < n_tracts) { first = sum[t].first; end = first + sum[t].n_rows; }
-    const bool ok = t >= 0 && t < n_tracts && first >= 0 && first <= end && end <= n_union;
-    if (!ok) { if (lane == 0) atomicOr (err, 1); first = end = 0; }
+    long first, end;
+    listed_tract_rows (sum, n_tracts, n_union, list[i], lane, err, first, end);
     for (int s = lane; s < ns; s += S) {
       double v[TJAMD_N_TRACT_STATS];
       int ml, nc;
       tract_sample_values (keys, counts, ns, first, end, s, cov[s], v, ml, nc);
-      for (int j = 0; j < TJAMD_N_TRACT_STATS; j++) values[(i * TJAMD_N_TRACT_STATS + j) * ns + s] = v[j];
-      if (modal_len) modal_len[i * ns + s] = ml;
-      if (n_context) n_context[i * ns + s] = nc;
+      write_listed_sample (i, s, ns, v, ml, nc, values, modal_len, n_context);
     }
   }
 }
@@ -5748,12 +5798,19 @@ void tract_sample_stats_kernel (const u64 *__restrict__ keys, const int *__restr
 static int tract_segment (int n_samples) { int S = 1; while (S < n_samples && S < 64) S <<= 1; return S; }
 static unsigned tract_grid (long n, int S) { return (unsigned) std::max<long> (1, std::min<long> ((n * S + 255) / 256, 65536)); }
 
-static int tract_args (const char *fn, const void *d_keys, const void *d_counts, long n_union, int n_samples, const int *coverage)
-{ // the checks both entries share, before any device call
+static int union_args (const char *fn, const void *d_keys, const void *d_counts, long n_union, int n_samples)
+{ // the checks every entry that takes a union shares, before any device call
   if (n_union < 0) return set_err (TJAMD_ERR_ARG, "%s: n_union %ld < 0", fn, n_union);
   if (n_union >= (1l << 31)) return set_err (TJAMD_ERR_CAPACITY, "%s: %ld union rows", fn, n_union);
   if (n_samples < 1 || n_samples > 4096) return set_err (TJAMD_ERR_ARG, "%s: n_samples %d outside 1..4096", fn, n_samples);
   if (n_union > 0 && (!d_keys || !d_counts)) return set_err (TJAMD_ERR_ARG, "%s: null union buffers", fn);
+  return TJAMD_OK;
+}
+
+static int tract_args (const char *fn, const void *d_keys, const void *d_counts, long n_union, int n_samples, const int *coverage)
+{ // ... and, for the statistics, the samples' coverages
+  const int rc = union_args (fn, d_keys, d_counts, n_union, n_samples);
+  if (rc) return rc;
   if (!coverage) return set_err (TJAMD_ERR_ARG, "%s: null coverage", fn);
   return TJAMD_OK;
 }
@@ -5786,9 +5843,9 @@ extern "C" long tjamd_tract_stats (tjamd_counter *c, const void *d_keys, const v
   rc = ensure_tract_id_scratch (c, n_union);
   if (!rc) rc = upload_coverage (c, coverage, n_samples);
   if (rc) return -rc;
-  c->tract_timed = false;                               // (a failed call leaves no timing behind)
-  (void) hipEventRecord (c->ev_t0, c->stream);
-  u32 *total = (u32 *) c->scan_tmp.p + scan_tmp_words (n_union);
+  c->timer[T_TRACT].timed = false;                      // (a failed call leaves no timing behind)
+  (void) c->timer[T_TRACT].begin (c->stream);
+  u32 *total = scan_total (c, n_union);
   const int *ids = d_tract_id;
   if (!ids) {                                           // the context-keyed ids of tjamd_tract_ids, in c->segid
     rc = queue_tract_ids (c, d_keys, n_union, (int *) c->segid.p, total);
@@ -5806,7 +5863,7 @@ extern "C" long tjamd_tract_stats (tjamd_counter *c, const void *d_keys, const v
   if (d_var) hipLaunchKernelGGL (tract_var_scatter_kernel, dim3 (grid_for (n_bound)), dim3 (256), 0, c->stream, (const u32 *) c->flags.p, (const u32 *) c->outpos.p,
                                  n_bound, d_var);
   if (hipGetLastError () != hipSuccess) return -set_err (TJAMD_ERR_HIP, "tract list launch failed");
-  (void) hipEventRecord (c->ev_t1, c->stream);
+  (void) c->timer[T_TRACT].end (c->stream);
   int h_err[3] = {0, 0, 0};
   u32 nv = 0;
   if (hipMemcpyAsync (h_err, err, 12, hipMemcpyDeviceToHost, c->stream) != hipSuccess || hipMemcpyAsync (&nv, total, 4, hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
@@ -5814,7 +5871,7 @@ extern "C" long tjamd_tract_stats (tjamd_counter *c, const void *d_keys, const v
   const long n_tracts = (long) h_err[1] + 1;
   if (h_err[0] || h_err[2] || n_tracts < 1) return -set_err (TJAMD_ERR_ARG, "tjamd_tract_stats: tract ids must start at 0 and go up by 0 or 1 per row");
   if (n_tracts > capacity) return -set_err (TJAMD_ERR_CAPACITY, "tjamd_tract_stats: %ld tracts, caller capacity %ld", n_tracts, capacity);
-  c->tract_timed = true;
+  c->timer[T_TRACT].timed = true;
   if (n_var) *n_var = (long) nv;
   return n_tracts;
 }
@@ -5842,13 +5899,7 @@ extern "C" long tjamd_tract_sample_stats (tjamd_counter *c, const void *d_keys, 
   return n_list;
 }
 
-extern "C" double tjamd_last_tract_stats_ms (tjamd_counter *c)
-{
-  if (!c || !c->tract_timed) return -1.0;
-  float ms = 0.f;
-  if (hipSetDevice (c->device) != hipSuccess || hipEventSynchronize (c->ev_t1) != hipSuccess || hipEventElapsedTime (&ms, c->ev_t0, c->ev_t1) != hipSuccess) return -1.0;
-  return (double) ms;
-}
+extern "C" double tjamd_last_tract_stats_ms (tjamd_counter *c) { return c ? c->timer[T_TRACT].ms (c->device) : -1.0; }
 
 // ---------------------------------------------------------------------------------------------------------------
 // N6: tracts across samples by grouping (reference: new_genomic_context_list's grouping, src/context_histogram.c:245-270,
@@ -5906,60 +5957,38 @@ extern "C" long tjamd_union_tracts (tjamd_counter *c, const void *d_keys, const 
                                     int *d_tract_id, int *d_join_type, tjamd_union_tract *d_tracts, long capacity)
 {
   static const char *fn = "tjamd_union_tracts";
-  if (n_union < 0) return -set_err (TJAMD_ERR_ARG, "%s: n_union %ld < 0", fn, n_union);
-  if (n_union >= (1l << 31)) return -set_err (TJAMD_ERR_CAPACITY, "%s: %ld union rows", fn, n_union);
-  if (n_samples < 1 || n_samples > 4096) return -set_err (TJAMD_ERR_ARG, "%s: n_samples %d outside 1..4096", fn, n_samples);
-  if (n_union > 0 && (!d_keys || !d_counts)) return -set_err (TJAMD_ERR_ARG, "%s: null union buffers", fn);
+  int rc = union_args (fn, d_keys, d_counts, n_union, n_samples);
+  if (rc) return -rc;
   if (n_union > 0 && (!d_tract_id || !d_tracts)) return -set_err (TJAMD_ERR_ARG, "%s: null tract id or tract buffer", fn);
   if (max_distance_per_flank < 0 || levenshtein_distance < 0)
     return -set_err (TJAMD_ERR_ARG, "%s: negative distance (max_distance_per_flank %d, levenshtein_distance %d)", fn, max_distance_per_flank, levenshtein_distance);
   if (capacity < (n_union > 0 ? 1 : 0)) return -set_err (TJAMD_ERR_CAPACITY, "%s: capacity %ld for a union of %ld rows", fn, capacity, n_union);
   if (!c) return -set_err (TJAMD_ERR_ARG, "%s: null counter", fn);
   if (hipSetDevice (c->device) != hipSuccess) return -set_err (TJAMD_ERR_HIP, "hipSetDevice failed");
-  c->union_timed = false; c->union_cand = -1;           // (a failed call leaves no timing behind)
+  c->timer[T_UNION].timed = false; c->union_cand = -1;  // (a failed call leaves no timing behind)
   const long n = n_union;
   if (n == 0) return 0;
-  int rc = ensure (c->headpos, (size_t) n * 4, c->stream);          // back[]
-  if (!rc) rc = ensure (c->flags, (size_t) n * 4, c->stream);      // head flags
-  if (!rc) rc = ensure (c->outpos, (size_t) n * 4, c->stream);     // tracts before each row
-  if (!rc) rc = ensure (c->keep, (size_t) n * 4, c->stream);       // candidates of the retry
-  if (!rc) rc = ensure (c->grp_jt, (size_t) n * 4, c->stream);
+  rc = ensure_group_scratch (c, n, true);
   if (!rc) rc = ensure (c->ut_tot, (size_t) n * 8, c->stream);
   if (!rc) rc = ensure (c->ut_lev, (size_t) n * 4, c->stream);
-  if (!rc) rc = ensure (c->scan_tmp, scan_tmp_words (n) * 4 + 64, c->stream);
   if (rc) return -rc;
-  const u64 *keys = (const u64 *) d_keys;
   long long *tot = (long long *) c->ut_tot.p;
-  u32 *total = (u32 *) c->scan_tmp.p + scan_tmp_words (n), *n_cand = total + 1;
-  (void) hipEventRecord (c->ev_u0, c->stream);
+  (void) c->timer[T_UNION].begin (c->stream);
   const int S = tract_segment (n_samples);
   hipLaunchKernelGGL (union_totals_kernel, dim3 (tract_grid (n, S)), dim3 (256), 0, c->stream, (const int *) d_counts, n, n_samples, S, tot);
-  hipLaunchKernelGGL (group_back_kernel, dim3 (grid_for (n)), dim3 (256), 0, c->stream, keys, n, max_distance_per_flank, (int *) c->headpos.p);
-  hipLaunchKernelGGL (group_resolve_kernel, dim3 (grid_for (n)), dim3 (256), 0, c->stream, (const int *) c->headpos.p, n, (u32 *) c->flags.p);
-  if (hipMemsetAsync (n_cand, 0, 4, c->stream) != hipSuccess) return -set_err (TJAMD_ERR_HIP, "memset failed");
-  // (the reading of the absent edit distance's last argument: looked up per call, as tjamd_context_histograms does)
-  const char *ed = getenv ("TATAJUBA_AMD_EDIT_DISTANCE");
-  const int free_end = (ed && !strcmp (ed, "free_end")) ? 1 : 0;
-  const TotalCount count_of = {tot};
-  hipLaunchKernelGGL (group_speculate_kernel<TotalCount>, dim3 (grid_for (n)), dim3 (256), 0, c->stream, keys, n, c->k, levenshtein_distance, free_end,
-                      (const u32 *) c->flags.p, (u32 *) c->keep.p, (int *) c->grp_jt.p, n_cand, count_of);
-  if (hipGetLastError () != hipSuccess) return -set_err (TJAMD_ERR_HIP, "%s: grouping launch failed", fn);
-  u32 nc = 0;
-  if (hipMemcpyAsync (&nc, n_cand, 4, hipMemcpyDeviceToHost, c->stream) != hipSuccess || hipStreamSynchronize (c->stream) != hipSuccess)
-    return -set_err (TJAMD_ERR_HIP, "%s: grouping failed: %s", fn, hipGetErrorString (hipGetLastError ()));
-  if (nc) hipLaunchKernelGGL (group_repair_kernel<TotalCount>, dim3 (1), dim3 (256), 0, c->stream, keys, n, c->k, max_distance_per_flank, levenshtein_distance,
-                              free_end, (u32 *) c->flags.p, (const u32 *) c->keep.p, (int *) c->grp_jt.p, count_of, (int *) c->ut_lev.p);
-  rc = exclusive_scan (c, (const u32 *) c->flags.p, (u32 *) c->outpos.p, n, total, (u32 *) c->scan_tmp.p, scan_tmp_words (n));
+  long n_cand = 0;
+  rc = queue_group_heads (c, "tjamd_union_tracts: ", (const u64 *) d_keys, n, max_distance_per_flank, TotalCount {tot}, true, levenshtein_distance,
+                          (int *) c->ut_lev.p, &n_cand);
   if (rc) return -rc;
   hipLaunchKernelGGL (union_tract_kernel, dim3 (grid_for (n)), dim3 (256), 0, c->stream, n, (const long long *) tot, (const u32 *) c->flags.p,
                       (const u32 *) c->outpos.p, (const int *) c->grp_jt.p, (const int *) c->ut_lev.p, capacity, d_tract_id, d_join_type, (UnionTract *) d_tracts);
   if (hipGetLastError () != hipSuccess) return -set_err (TJAMD_ERR_HIP, "%s: tract launch failed", fn);
-  (void) hipEventRecord (c->ev_u1, c->stream);
+  (void) c->timer[T_UNION].end (c->stream);
   u32 ng = 0;
-  if (hipMemcpyAsync (&ng, total, 4, hipMemcpyDeviceToHost, c->stream) != hipSuccess || hipStreamSynchronize (c->stream) != hipSuccess)
+  if (hipMemcpyAsync (&ng, scan_total (c, n), 4, hipMemcpyDeviceToHost, c->stream) != hipSuccess || hipStreamSynchronize (c->stream) != hipSuccess)
     return -set_err (TJAMD_ERR_HIP, "%s: grouping failed: %s", fn, hipGetErrorString (hipGetLastError ()));
   if ((long) ng > capacity) return -set_err (TJAMD_ERR_CAPACITY, "%s: %u tracts, caller capacity %ld", fn, ng, capacity);
-  c->union_timed = true; c->union_cand = (long) nc;
+  c->timer[T_UNION].timed = true; c->union_cand = n_cand;
   return (long) ng;
 }
 
@@ -5983,10 +6012,8 @@ __device__ int union_sample_bars (const u64 *__restrict__ keys, const int *__res
   for (long r = first; r < end; r++) {
     const int x = counts[r * ns + s];
     if (x == 0) continue;
-    const u64 m = keys[3 * r + 2];
-    int l = (int) ((m >> TJ_META_LEN_SHIFT) & 0x3FFull);
-    if (l & 0x200) l -= 0x400;                          // signed 10-bit field
-    if (prev < 0 || keys[3 * r] != keys[3 * prev] || keys[3 * r + 1] != keys[3 * prev + 1] || ((m ^ keys[3 * prev + 2]) & 3ull)) n_ctx++;
+    const int l = meta_len (keys[3 * r + 2]);
+    if (prev < 0 || !same_context_rows (keys, r, prev)) n_ctx++;
     prev = r;
     integral += x;
     if (FULL) cnt[(l + UT_LENGTHS / 2) * stride] += x;
@@ -6076,37 +6103,25 @@ void union_tract_stats_kernel (const u64 *__restrict__ keys, const int *__restri
       continue;
     }
     const int ref = ref_len ? ref_len[t] : 0;
-    double mx[TJAMD_N_TRACT_STATS], mn[TJAMD_N_TRACT_STATS], v[TJAMD_N_TRACT_STATS];
-    for (int j = 0; j < TJAMD_N_TRACT_STATS; j++) { mx[j] = -FLT_MAX; mn[j] = FLT_MAX; }
-    int present = 0, off_ref = 0, over = 0;
+    TractSpread sp;
+    int over = 0;
     for (int s = lane; s < ns; s += S) {
+      double v[TJAMD_N_TRACT_STATS];
       long long integral;
       int n_ctx, ml;
       const int nb = union_sample_bars<FULL> (keys, counts, ns, first, end, s, cnt, len, stride, integral, n_ctx);
       if (nb < 0) { over = 1; break; }
-      if (!union_sample_values (cnt, len, stride, nb, integral, n_ctx, cov[s], v, ml)) continue;
-      present++;
-      if (ref > 0 && ml != ref) off_ref = 1;
-      for (int j = 0; j < TJAMD_N_TRACT_STATS; j++) { mx[j] = dmax_ref (mx[j], v[j]); mn[j] = dmin_ref (mn[j], v[j]); }
+      if (union_sample_values (cnt, len, stride, nb, integral, n_ctx, cov[s], v, ml)) sp.add (v, ml, ref);
     }
-    for (int o = 1; o < S; o <<= 1) {
-      present += __shfl_xor (present, o, S);
-      off_ref |= __shfl_xor (off_ref, o, S);
-      over |= __shfl_xor (over, o, S);
-      for (int j = 0; j < TJAMD_N_TRACT_STATS; j++) {
-        mx[j] = dmax_ref (mx[j], __shfl_xor (mx[j], o, S));
-        mn[j] = dmin_ref (mn[j], __shfl_xor (mn[j], o, S));
-      }
-    }
+    sp.reduce (S);
+    for (int o = 1; o < S; o <<= 1) over |= __shfl_xor (over, o, S);
     if (lane != 0) continue;
     if (!FULL) fallback[t] = (u32) over;
     if (over) { varflag[t] = 0u; selflag[t] = 0u; continue; }   // (FULL never overflows: the fallback kernel writes this tract)
     UnionSummary o;
-    o.first = (int) first; o.n_rows = u.n_rows; o.n_present = present; o.lev_distance = u.lev_distance;
-    for (int j = 0; j < TJAMD_N_TRACT_STATS; j++) o.reldiff[j] = (mx[j] > DBL_MIN) ? mx[j] - mn[j] : 0.0;
-    const double difference = o.reldiff[TJAMD_STAT_AVG_LENGTH] + o.reldiff[TJAMD_STAT_MODAL_FREQ] + o.reldiff[TJAMD_STAT_ENTROPY];
-    o.variable = (present < ns || difference > 1.e-5 || off_ref) ? 1 : 0;                 // the rule of tjamd_tract_stats
-    o.selected = (present < ns || u.lev_distance > 0 || o.reldiff[TJAMD_STAT_MODAL_FREQ] > 1e-6 ||  // print_selected_g_tract_vector
+    o.first = (int) first; o.n_rows = u.n_rows; o.n_present = sp.present; o.lev_distance = u.lev_distance;
+    o.variable = sp.finish (ns, o.reldiff);
+    o.selected = (sp.present < ns || u.lev_distance > 0 || o.reldiff[TJAMD_STAT_MODAL_FREQ] > 1e-6 ||  // print_selected_g_tract_vector
                   o.reldiff[TJAMD_STAT_AVG_LENGTH] > 1e-6 || o.reldiff[TJAMD_STAT_ENTROPY] > 1e-6) ? 1 : 0;
     sum[t] = o;
     varflag[t] = (u32) o.variable; selflag[t] = (u32) o.selected;
@@ -6127,11 +6142,8 @@ void union_tract_sample_stats_kernel (const u64 *__restrict__ keys, const int *_
   const long segs_per_grid = (long) gridDim.x * (blockDim.x / S);
   for (long i = gthread / S; i < n_list; i += segs_per_grid) {
     if (FULL && !fallback[i]) continue;
-    const int t = list[i];
-    long first = 0, end = 0;
-    if (t >= 0 && t < n_tracts) { first = sum[t].first; end = first + (long) sum[t].n_rows; }
-    const bool ok = t >= 0 && t < n_tracts && first >= 0 && first <= end && end <= n_union;
-    if (!ok) { if (lane == 0) atomicOr (err, 1); first = end = 0; }
+    long first, end;
+    listed_tract_rows (sum, n_tracts, n_union, list[i], lane, err, first, end);
     int over = 0;
     for (int s = lane; s < ns; s += S) {
       double v[TJAMD_N_TRACT_STATS];
@@ -6140,9 +6152,7 @@ void union_tract_sample_stats_kernel (const u64 *__restrict__ keys, const int *_
       const int nb = union_sample_bars<FULL> (keys, counts, ns, first, end, s, cnt, len, stride, integral, n_ctx);
       if (nb < 0) { over = 1; break; }
       if (!union_sample_values (cnt, len, stride, nb, integral, n_ctx, cov[s], v, ml)) n_ctx = 0;
-      for (int j = 0; j < TJAMD_N_TRACT_STATS; j++) values[(i * TJAMD_N_TRACT_STATS + j) * ns + s] = v[j];
-      if (modal_len) modal_len[i * ns + s] = ml;
-      if (n_context) n_context[i * ns + s] = n_ctx;
+      write_listed_sample (i, s, ns, v, ml, n_ctx, values, modal_len, n_context);
       if (n_len) n_len[i * ns + s] = nb;
     }
     if (!FULL) {
@@ -6163,11 +6173,13 @@ static int union_stats_args (const char *fn, const void *d_keys, const void *d_c
   return TJAMD_OK;
 }
 
-static int ensure_union_fallback (tjamd_counter *c, long n)
-{ // fallback flags, and the global bars of the FULL kernels
+static int ensure_union_fallback (tjamd_counter *c, long n, long long *&g_cnt, int *&g_len)
+{ // fallback flags, and the global bars of the FULL kernels: g_cnt, the counts of all their threads, then g_len, the lengths
   int rc = ensure (c->ut_fb, (size_t) std::max (n, 1l) * 4, c->stream);
   const size_t threads = (size_t) UT_FULL_BLOCKS * 256;
   if (!rc) rc = ensure (c->ut_slots, threads * UT_LENGTHS * (sizeof (long long) + sizeof (int)), c->stream);
+  g_cnt = (long long *) c->ut_slots.p;                  // (null after a failed first allocation: the caller returns)
+  g_len = (int *) (g_cnt + threads * UT_LENGTHS);
   return rc;
 }
 
@@ -6182,7 +6194,7 @@ extern "C" long tjamd_union_tract_stats (tjamd_counter *c, const void *d_keys, c
   if (n_var) *n_var = 0;
   if (n_sel) *n_sel = 0;
   if (hipSetDevice (c->device) != hipSuccess) return -set_err (TJAMD_ERR_HIP, "hipSetDevice failed");
-  c->union_stats_timed = false;
+  c->timer[T_UNION_STATS].timed = false;
   if (n_union == 0) return 0;
   const long nt = n_tracts;
   rc = ensure (c->flags, (size_t) nt * 4, c->stream);               // variable flags, then their positions in outpos
@@ -6190,23 +6202,22 @@ extern "C" long tjamd_union_tract_stats (tjamd_counter *c, const void *d_keys, c
   if (!rc) rc = ensure (c->keep, (size_t) nt * 4, c->stream);      // selected flags, then their positions in headpos
   if (!rc) rc = ensure (c->headpos, (size_t) nt * 4, c->stream);
   if (!rc) rc = ensure (c->scan_tmp, scan_tmp_words (nt) * 4 + 64, c->stream);
-  if (!rc) rc = ensure_union_fallback (c, nt);
+  long long *g_cnt = nullptr;
+  int *g_len = nullptr;
+  if (!rc) rc = ensure_union_fallback (c, nt, g_cnt, g_len);
   if (!rc) rc = upload_coverage (c, coverage, n_samples);
   if (rc) return -rc;
-  (void) hipEventRecord (c->ev_v0, c->stream);
-  u32 *total = (u32 *) c->scan_tmp.p + scan_tmp_words (nt);
+  (void) c->timer[T_UNION_STATS].begin (c->stream);
+  u32 *total = scan_total (c, nt);
   int *err = (int *) c->ts_aux.p;
   const int S = tract_segment (n_samples);
-  const size_t threads = (size_t) UT_FULL_BLOCKS * 256;
-  long long *g_cnt = (long long *) c->ut_slots.p;
-  int *g_len = (int *) (g_cnt + threads * UT_LENGTHS);
   u32 *vf = (u32 *) c->flags.p, *sf = (u32 *) c->keep.p, *fb = (u32 *) c->ut_fb.p;
-  hipLaunchKernelGGL (union_tract_stats_kernel<false>, dim3 (tract_grid (nt, S)), dim3 (256), 0, c->stream, (const u64 *) d_keys, (const int *) d_counts,
-                      n_union, n_samples, S, (const int *) c->ts_cov.p, d_ref_length, (const UnionTract *) d_tracts, nt, (UnionSummary *) d_summary,
-                      vf, sf, fb, g_cnt, g_len, err);
-  hipLaunchKernelGGL (union_tract_stats_kernel<true>, dim3 (UT_FULL_BLOCKS), dim3 (256), 0, c->stream, (const u64 *) d_keys, (const int *) d_counts,
-                      n_union, n_samples, S, (const int *) c->ts_cov.p, d_ref_length, (const UnionTract *) d_tracts, nt, (UnionSummary *) d_summary,
-                      vf, sf, fb, g_cnt, g_len, err);
+  auto launch = [&] (auto kernel, unsigned grid) {
+    hipLaunchKernelGGL (kernel, dim3 (grid), dim3 (256), 0, c->stream, (const u64 *) d_keys, (const int *) d_counts, n_union, n_samples, S, (const int *) c->ts_cov.p,
+                        d_ref_length, (const UnionTract *) d_tracts, nt, (UnionSummary *) d_summary, vf, sf, fb, g_cnt, g_len, err);
+  };
+  launch (union_tract_stats_kernel<false>, tract_grid (nt, S));
+  launch (union_tract_stats_kernel<true>, (unsigned) UT_FULL_BLOCKS);
   if (hipGetLastError () != hipSuccess) return -set_err (TJAMD_ERR_HIP, "%s: launch failed", fn);
   rc = exclusive_scan (c, vf, (u32 *) c->outpos.p, nt, total, (u32 *) c->scan_tmp.p, scan_tmp_words (nt));
   if (!rc) rc = exclusive_scan (c, sf, (u32 *) c->headpos.p, nt, total + 1, (u32 *) c->scan_tmp.p, scan_tmp_words (nt));
@@ -6214,13 +6225,13 @@ extern "C" long tjamd_union_tract_stats (tjamd_counter *c, const void *d_keys, c
   if (d_var) hipLaunchKernelGGL (tract_var_scatter_kernel, dim3 (grid_for (nt)), dim3 (256), 0, c->stream, (const u32 *) vf, (const u32 *) c->outpos.p, nt, d_var);
   if (d_sel) hipLaunchKernelGGL (tract_var_scatter_kernel, dim3 (grid_for (nt)), dim3 (256), 0, c->stream, (const u32 *) sf, (const u32 *) c->headpos.p, nt, d_sel);
   if (hipGetLastError () != hipSuccess) return -set_err (TJAMD_ERR_HIP, "%s: list launch failed", fn);
-  (void) hipEventRecord (c->ev_v1, c->stream);
+  (void) c->timer[T_UNION_STATS].end (c->stream);
   int h_err = 0;
   u32 h_tot[2] = {0, 0};
   if (hipMemcpyAsync (&h_err, err, 4, hipMemcpyDeviceToHost, c->stream) != hipSuccess || hipMemcpyAsync (h_tot, total, 8, hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
       hipStreamSynchronize (c->stream) != hipSuccess) return -set_err (TJAMD_ERR_HIP, "%s: failed: %s", fn, hipGetErrorString (hipGetLastError ()));
   if (h_err) return -set_err (TJAMD_ERR_ARG, "%s: the tracts must tile the union (first 0, each starting where the one before ends, the last ending at row %ld)", fn, n_union);
-  c->union_stats_timed = true;
+  c->timer[T_UNION_STATS].timed = true;
   if (n_var) *n_var = (long) h_tot[0];
   if (n_sel) *n_sel = (long) h_tot[1];
   return nt;
@@ -6238,43 +6249,31 @@ extern "C" long tjamd_union_tract_sample_stats (tjamd_counter *c, const void *d_
   if (!c) return -set_err (TJAMD_ERR_ARG, "%s: null counter", fn);
   if (hipSetDevice (c->device) != hipSuccess) return -set_err (TJAMD_ERR_HIP, "hipSetDevice failed");
   if (n_list == 0) return 0;
-  rc = ensure_union_fallback (c, n_list);
+  long long *g_cnt = nullptr;
+  int *g_len = nullptr;
+  rc = ensure_union_fallback (c, n_list, g_cnt, g_len);
   if (!rc) rc = upload_coverage (c, coverage, n_samples);
   if (rc) return -rc;
   const int S = tract_segment (n_samples);
-  const size_t threads = (size_t) UT_FULL_BLOCKS * 256;
-  long long *g_cnt = (long long *) c->ut_slots.p;
-  int *g_len = (int *) (g_cnt + threads * UT_LENGTHS);
   int *err = (int *) c->ts_aux.p, h_err = 0;
-  hipLaunchKernelGGL (union_tract_sample_stats_kernel<false>, dim3 (tract_grid (n_list, S)), dim3 (256), 0, c->stream, (const u64 *) d_keys, (const int *) d_counts,
-                      n_union, n_samples, S, (const int *) c->ts_cov.p, (const UnionSummary *) d_summary, n_tracts, d_list, n_list, d_values, d_modal_len,
-                      d_n_context, d_n_len, (u32 *) c->ut_fb.p, g_cnt, g_len, err);
-  hipLaunchKernelGGL (union_tract_sample_stats_kernel<true>, dim3 (UT_FULL_BLOCKS), dim3 (256), 0, c->stream, (const u64 *) d_keys, (const int *) d_counts,
-                      n_union, n_samples, S, (const int *) c->ts_cov.p, (const UnionSummary *) d_summary, n_tracts, d_list, n_list, d_values, d_modal_len,
-                      d_n_context, d_n_len, (u32 *) c->ut_fb.p, g_cnt, g_len, err);
+  auto launch = [&] (auto kernel, unsigned grid) {
+    hipLaunchKernelGGL (kernel, dim3 (grid), dim3 (256), 0, c->stream, (const u64 *) d_keys, (const int *) d_counts, n_union, n_samples, S, (const int *) c->ts_cov.p,
+                        (const UnionSummary *) d_summary, n_tracts, d_list, n_list, d_values, d_modal_len, d_n_context, d_n_len, (u32 *) c->ut_fb.p, g_cnt, g_len, err);
+  };
+  launch (union_tract_sample_stats_kernel<false>, tract_grid (n_list, S));
+  launch (union_tract_sample_stats_kernel<true>, (unsigned) UT_FULL_BLOCKS);
   if (hipGetLastError () != hipSuccess || hipMemcpyAsync (&h_err, err, 4, hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
       hipStreamSynchronize (c->stream) != hipSuccess) return -set_err (TJAMD_ERR_HIP, "%s: failed: %s", fn, hipGetErrorString (hipGetLastError ()));
   if (h_err) return -set_err (TJAMD_ERR_ARG, "%s: a listed tract id is outside [0, %ld) or its rows outside the union", fn, n_tracts);
   return n_list;
 }
 
-extern "C" double tjamd_last_union_tracts_ms (tjamd_counter *c)
-{ // first launch to last of the last tjamd_union_tracts, the host's wait for the retry candidates included
-  if (!c || !c->union_timed) return -1.0;
-  float ms = 0.f;
-  if (hipSetDevice (c->device) != hipSuccess || hipEventSynchronize (c->ev_u1) != hipSuccess || hipEventElapsedTime (&ms, c->ev_u0, c->ev_u1) != hipSuccess) return -1.0;
-  return (double) ms;
-}
+// first launch to last of the last tjamd_union_tracts, the host's wait for the retry candidates included
+extern "C" double tjamd_last_union_tracts_ms (tjamd_counter *c) { return c ? c->timer[T_UNION].ms (c->device) : -1.0; }
 
 extern "C" long tjamd_last_union_tract_candidates (tjamd_counter *c) { return c ? c->union_cand : -1; }
 
-extern "C" double tjamd_last_union_tract_stats_ms (tjamd_counter *c)
-{
-  if (!c || !c->union_stats_timed) return -1.0;
-  float ms = 0.f;
-  if (hipSetDevice (c->device) != hipSuccess || hipEventSynchronize (c->ev_v1) != hipSuccess || hipEventElapsedTime (&ms, c->ev_v0, c->ev_v1) != hipSuccess) return -1.0;
-  return (double) ms;
-}
+extern "C" double tjamd_last_union_tract_stats_ms (tjamd_counter *c) { return c ? c->timer[T_UNION_STATS].ms (c->device) : -1.0; }
 
 // Peer access between two devices of this process, asked for once per ordered pair: with it hipMemcpyPeerAsync moves the
 // bytes over xGMI directly, without it the runtime stages them through host memory.  Returns 1 direct, 0 staged;
@@ -6381,7 +6380,7 @@ extern "C" long tjamd_merge_samples (tjamd_counter *c, const void *d_records, co
   u32 *tpos = (u32 *) c->headpos.p, *ttot = (u32 *) c->outpos.p;
   if (!c->bins_zeroed && hipMemsetAsync (bins, 0, (size_t) BS_MAXBINS * 4, c->stream) != hipSuccess) return -set_err (TJAMD_ERR_HIP, "memset failed");
   c->bins_zeroed = false;
-  (void) hipEventRecord (c->ev_m0, c->stream);
+  (void) c->timer[T_MERGE].begin (c->stream);
   hipLaunchKernelGGL (bin_count_kernel, dim3 (grid_for (n)), dim3 (256), 0, c->stream, (const u64 *) d_records, n, c->k, nbits, bins, (uint4 *) nullptr, 0l, 1);
   hipLaunchKernelGGL (bin_scan_kernel, dim3 (1), dim3 (1024), 0, c->stream, bins, nbins, binstart,
                       c->bin_rank_max < (u32) BS_RANK_MAX ? c->bin_rank_max : (u32) MG_RANK_MAX, c->d_fin);   // (test hook: see TATAJUBA_AMD_BIN_MAX)
@@ -6394,8 +6393,8 @@ extern "C" long tjamd_merge_samples (tjamd_counter *c, const void *d_records, co
                       (const u32 *) binout, nbins, (const FinCounts *) c->d_fin, (const u32 *) tpos, (const u32 *) ttot, n_samples,
                       (u64 *) d_out_keys, (int *) d_out_counts, capacity);
   if (hipGetLastError () != hipSuccess) return -set_err (TJAMD_ERR_HIP, "merge launch failed");
-  (void) hipEventRecord (c->ev_m1, c->stream);
-  c->merge_timed = true;
+  (void) c->timer[T_MERGE].end (c->stream);
+  c->timer[T_MERGE].timed = true;
   if (hipMemcpyAsync (c->h_fin, c->d_fin, sizeof (FinCounts), hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
       hipStreamSynchronize (c->stream) != hipSuccess) return -set_err (TJAMD_ERR_HIP, "merge failed: %s", hipGetErrorString (hipGetLastError ()));
   if (c->h_fin->sort_fallback) return merge_samples_radix (c, d_records, n, n_samples, d_out_keys, d_out_counts, capacity);
