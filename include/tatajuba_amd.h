@@ -245,7 +245,8 @@ long tjamd_tract_sample_stats (tjamd_counter *c, const void *d_keys, const void 
  *     n_present < n_samples, or lev_distance > 0, or reldiff of modal freq, avg length or entropy > 1e-6.
  *   Known limitation: only rows that are neighbours in the sort order can join, as within a sample.  That covers variants in
  *     the right flank and variants of the left flank far from the tract; a left-flank SNP next to the tract usually has
- *     unrelated rows between its two alleles, and its two tracts stay apart.
+ *     unrelated rows between its two alleles, and its two tracts stay apart.  With a reference genome, tjamd_locate and
+ *     tjamd_located_tracts (N7, below) join them: two tracts located at one place become one.
  * Names use the counter's k.  Every entry runs on the counter's stream, changes neither d_keys nor d_counts nor the
  * counter's finalised state, and returns a count or a negative TJAMD_ERR_* (tjamd_last_error starts with its name). */
 typedef struct { int first, n_rows, n_context, mode, indel, lev_distance; long long integral; } tjamd_union_tract;   /* 32 bytes */
@@ -302,6 +303,78 @@ typedef struct { int length, freq; } tjamd_length_freq;
 long tjamd_context_histograms (tjamd_counter *c, int max_distance_per_flank, int levenshtein_distance, int *group_of, int *join_type,
                                tjamd_context_group *groups, tjamd_length_freq *hist, long capacity);
 
+/* Tracts located on a reference genome by flank matching (N7; reference: find_reference_location_and_sort_hopo_counter,
+ * src/hopo_counter.c:495-572, which maps the contexts with BWA, and find_best_context_name_for_reference,
+ * src/genome_set.c:525-577, which rescans the reference around the location; BWA is not part of this library).  The genome is
+ * scanned as a stream of reads: a tract seen in a read and the same tract seen in the genome give the same canonical (base,
+ * ctx0, ctx1), so a location is found by joining keys against an index of the genome's own runs.
+ *
+ * The index.  tjamd_reference_create builds it on the counter's device and stream from the contigs as a stream of reads
+ * (every contig followed by '\n', as tjamd_read_file_stream makes of a FASTA file), with the counter's k; one wait, at
+ * the end.  One entry per maximal run of one base (A, C, G, T or U, either case counting as the same base; length >= 1)
+ * whose k bytes on each side lie in the same contig and are all A, C, G, T or U by the scan's classification: a run or a
+ * flank touching any other byte is left out (it would pack as A and give false matches), and so is a run closer than k to
+ * a contig end.  An entry holds ctx0, ctx1 and base as the scan makes them (A and C as read; T and G reverse-complemented,
+ * neg_strand = 1), the run length as a plain int (no 10-bit field), the 0-based contig, pos = the 0-based position in the
+ * contig of the run's first base in forward coordinates on either strand, and flat = pos + the lengths of all earlier
+ * contigs, delimiters not counted (the reference's refseq_offset, src/genome_set.c:527-529,537).  n_contigs counts the
+ * delimiters, plus one for a last contig without one.  tjamd_reference_download returns the entries in ascending flat. */
+typedef struct tjamd_reference tjamd_reference;
+typedef struct { uint64_t ctx0, ctx1; long long flat; int contig, pos, length, base, neg_strand, pad; } tjamd_ref_entry;   /* 48 bytes */
+tjamd_reference *tjamd_reference_create (tjamd_counter *c, const void *h_stream, size_t n_bytes);   /* NULL on failure (tjamd_last_error) */
+void tjamd_reference_destroy (tjamd_reference *ref);
+long tjamd_reference_entries (const tjamd_reference *ref);
+long tjamd_reference_contigs (const tjamd_reference *ref);
+long tjamd_reference_download (const tjamd_reference *ref, tjamd_ref_entry *out, long capacity);
+
+/* The lookup.  d_keys: device tjamd_record[n], a union as tjamd_merge_samples writes it or a counter's kept array
+ * (tjamd_kept_device_ptr); only base, ctx0 and ctx1 are read.  d_loc: device tjamd_location[n].  With d (x, y) = the number of
+ * the k base positions at which two packed flanks differ (the distance of the grouping), an entry r is a hit for a row q when
+ *   r.base == q.base, and either r.ctx0 == q.ctx0 and d (r.ctx1, q.ctx1) <= max_mismatches
+ *                           or r.ctx1 == q.ctx1 and d (r.ctx0, q.ctx0) <= max_mismatches:
+ * one flank matches exactly, the other within the limit; the run length is free.  mismatches = the distance in the inexact
+ * flank; the row's location is the hit with the fewest mismatches, then the smallest flat (the reference's best and leftmost
+ * match, src/genome_set.c:540-542); n_hits = distinct hit entries (one that is exact in both flanks counts once); ref_length
+ * and neg_strand are that entry's.  No hit: flat = contig = pos = -1, the rest 0.  Rows of one context get one result.
+ * A reference built with another k or on another device is refused, as is max_mismatches outside 0 ... k.  Waits once, at
+ * the end.  Returns the number of located rows.
+ * Out of scope: a row whose flank differs from the genome by an indel stays unlocated (such rows are placed through the
+ * tract they joined in tjamd_union_tracts); mismatches in both flanks are not matched; GFF3 features are not read; the
+ * drop-in gets no find_reference_location_and_sort_hopo_counter of its own (the weak hook stays as it is: a host program
+ * fills loc_* from this call on tjamd_kept_device_ptr). */
+typedef struct { long long flat; int contig, pos, ref_length, mismatches, neg_strand, n_hits; } tjamd_location;   /* 32 bytes */
+long tjamd_locate (tjamd_counter *c, const tjamd_reference *ref, const void *d_keys, long n, int max_mismatches, tjamd_location *d_loc);
+
+/* Tracts by location (reference: context_histograms_overlap, genomic_context_merge_histograms_at_same_location,
+ * src/context_histogram.c:88-110,364-385: two histograms mapped to one place are one tract).
+ *   d_tracts      device tjamd_union_tract[n_tracts] that tile the union (from tjamd_union_tracts; refused otherwise, as in
+ *                 tjamd_union_tract_stats), or NULL: the context-keyed tracts of tjamd_tract_ids (n_tracts is not read)
+ *   d_loc         device tjamd_location[n_union] from tjamd_locate on the same union (or the caller's own places: flat < 0
+ *                 means unlocated, and a flat of 2^45 or more is refused: the order is a sort on 48 bits of (flat + 1, base))
+ * A tract's location is that of its located row with the highest exact int64 total over the samples, the first such row
+ * on a tie; a tract without a located row is unlocated.  Tracts with the same base and the same flat become one tract.
+ * The reference's further rule for nearby but unequal locations (within mode_context_length - 1, joined by edit distance,
+ * src/context_histogram.c:98-108) makes up for alignment starts that move with the flank; here the location is the tract's
+ * own first base, the same number for every allele of one genomic tract, so the rule is not needed and not built.
+ * Output order: the unlocated tracts first, in input order (the reference puts unknown locations first,
+ * src/hopo_counter.c:561-564), then the located ones ascending by (flat, base); inside a merged tract the member tracts
+ * keep input order and rows keep union order, so the rows of one context stay contiguous.
+ *   d_perm        device int32[n_union]: output row i is input row d_perm[i]
+ *   d_out_keys    device tjamd_record[n_union], d_out_counts device int32[n_union * n_samples]: the gathered union (each may be NULL)
+ *   d_out_tracts  device tjamd_union_tract[capacity] of the new tiling: first, n_rows; n_context, integral = sums over the
+ *                 members; indel = OR, lev_distance = max of the members'; mode = the output row with the highest total, the
+ *                 first on a tie
+ *   d_tract_loc   device tjamd_location[capacity] (may be NULL): the tract's location, by the rule above on its output rows
+ *   d_ref_length  device int32[capacity] (may be NULL): that location's ref_length, 0 if unlocated
+ * The output tiles the permuted union: tjamd_union_tract_stats and tjamd_union_tract_sample_stats run on (d_out_keys,
+ * d_out_counts, d_out_tracts), and d_ref_length feeds their reference-length test.  Changes neither d_keys nor d_counts nor
+ * the counter's finalised state.  Waits once, at the end (twice with d_tracts NULL).  Returns the number of tracts; a
+ * capacity below it is TJAMD_ERR_CAPACITY. */
+long tjamd_located_tracts (tjamd_counter *c, const void *d_keys, const void *d_counts, long n_union, int n_samples,
+                           const tjamd_union_tract *d_tracts, long n_tracts, const tjamd_location *d_loc,
+                           int *d_perm, void *d_out_keys, void *d_out_counts,
+                           tjamd_union_tract *d_out_tracts, tjamd_location *d_tract_loc, int *d_ref_length, long capacity);
+
 /* release the calling thread's shared device contexts of the synchronous string scans (update_hopo_counter_from_seq on a
  * counter that never read a file, tjamd_scan_windows) now; they are released by themselves when the thread ends */
 void tjamd_thread_cleanup (void);
@@ -316,6 +389,9 @@ double tjamd_last_tract_stats_ms (tjamd_counter *c); /* the last tjamd_tract_sta
 double tjamd_last_union_tracts_ms (tjamd_counter *c);      /* the last tjamd_union_tracts, first launch to last (host waits included) */
 double tjamd_last_union_tract_stats_ms (tjamd_counter *c); /* the last tjamd_union_tract_stats, first launch to last */
 long   tjamd_last_union_tract_candidates (tjamd_counter *c); /* rows of the last tjamd_union_tracts that the indel retry was tried on first (-1: none yet) */
+double tjamd_last_reference_ms (tjamd_counter *c);         /* kernels of the last tjamd_reference_create on this counter (the copy to the device not included) */
+double tjamd_last_locate_ms (tjamd_counter *c);            /* the lookup kernel of the last tjamd_locate */
+double tjamd_last_located_tracts_ms (tjamd_counter *c);    /* the last tjamd_located_tracts, first launch to last (host waits included) */
 long   tjamd_last_scan_launches (tjamd_counter *c);
 /* finalises of this counter whose device-side sizing of the ordering step had read a stale kept count (checked against the
  * count at the next kernel boundary and repaired; expected to stay 0) */

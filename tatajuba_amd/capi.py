@@ -35,6 +35,13 @@ assert UNION_TRACT_DTYPE.itemsize == 32
 UNION_TRACT_SUMMARY_DTYPE = np.dtype([("first", "<i4"), ("n_rows", "<i4"), ("n_present", "<i4"), ("variable", "<i4"), ("selected", "<i4"),
                                       ("lev_distance", "<i4"), ("reldiff", "<f8", (N_TRACT_STATS,))])
 assert UNION_TRACT_SUMMARY_DTYPE.itemsize == 64
+# tjamd_ref_entry / tjamd_location (include/tatajuba_amd.h): the reference index and a row's place on it
+REF_ENTRY_DTYPE = np.dtype([("ctx0", "<u8"), ("ctx1", "<u8"), ("flat", "<i8"), ("contig", "<i4"), ("pos", "<i4"), ("length", "<i4"),
+                            ("base", "<i4"), ("neg_strand", "<i4"), ("pad", "<i4")])
+assert REF_ENTRY_DTYPE.itemsize == 48
+LOCATION_DTYPE = np.dtype([("flat", "<i8"), ("contig", "<i4"), ("pos", "<i4"), ("ref_length", "<i4"), ("mismatches", "<i4"),
+                           ("neg_strand", "<i4"), ("n_hits", "<i4")])
+assert LOCATION_DTYPE.itemsize == 32
 
 
 class TatajubaAmdError(RuntimeError):
@@ -102,7 +109,10 @@ EXPORTS = [
     "tjamd_download_raw", "tjamd_undefined_runs", "tjamd_upload_raw", "tjamd_finalise", "tjamd_finalise_begin", "tjamd_finalise_end", "tjamd_kept_count",
     "tjamd_n_idx", "tjamd_coverage", "tjamd_download_kept", "tjamd_download_idx", "tjamd_kept_device_ptr",
     "tjamd_merge_samples", "tjamd_gather_histograms", "tjamd_peer_access_report", "tjamd_comm_unique_id", "tjamd_comm_create", "tjamd_comm_destroy",
-    "tjamd_comm_set_stream", "tjamd_comm_rank", "tjamd_comm_world", "tjamd_comm_collectives", "tjamd_comm_count", "tjamd_comm_last_exchange", "tjamd_last_merge_ms", "tjamd_allgather_histograms", "tjamd_tract_ids", "tjamd_tract_stats", "tjamd_tract_sample_stats", "tjamd_last_tract_stats_ms", "tjamd_union_tracts", "tjamd_union_tract_stats", "tjamd_union_tract_sample_stats", "tjamd_last_union_tracts_ms", "tjamd_last_union_tract_stats_ms", "tjamd_last_union_tract_candidates", "tjamd_group_contexts", "tjamd_context_histograms", "tjamd_scan_windows", "tjamd_thread_cleanup", "tjamd_last_scan_ms", "tjamd_last_partition_ms", "tjamd_counter_uses_log", "tjamd_last_finalise_ms", "tjamd_last_scan_launches", "tjamd_plan_mismatches",
+    "tjamd_comm_set_stream", "tjamd_comm_rank", "tjamd_comm_world", "tjamd_comm_collectives", "tjamd_comm_count", "tjamd_comm_last_exchange", "tjamd_last_merge_ms", "tjamd_allgather_histograms", "tjamd_tract_ids", "tjamd_tract_stats", "tjamd_tract_sample_stats", "tjamd_last_tract_stats_ms", "tjamd_union_tracts", "tjamd_union_tract_stats", "tjamd_union_tract_sample_stats", "tjamd_last_union_tracts_ms", "tjamd_last_union_tract_stats_ms", "tjamd_last_union_tract_candidates",
+    "tjamd_reference_create", "tjamd_reference_destroy", "tjamd_reference_entries", "tjamd_reference_contigs",
+    "tjamd_reference_download", "tjamd_last_reference_ms", "tjamd_locate", "tjamd_last_locate_ms", "tjamd_located_tracts", "tjamd_last_located_tracts_ms",
+    "tjamd_group_contexts", "tjamd_context_histograms", "tjamd_scan_windows", "tjamd_thread_cleanup", "tjamd_last_scan_ms", "tjamd_last_partition_ms", "tjamd_counter_uses_log", "tjamd_last_finalise_ms", "tjamd_last_scan_launches", "tjamd_plan_mismatches",
     "tjamd_synth_stream", "tjamd_read_file_stream",
     # include/tatajuba_context.h
     "new_genomic_context_list", "del_genomic_context_list", "del_context_histogram",
@@ -213,6 +223,18 @@ def lib():
     L.tjamd_last_union_tracts_ms.restype = C.c_double; L.tjamd_last_union_tracts_ms.argtypes = [C.c_void_p]
     L.tjamd_last_union_tract_stats_ms.restype = C.c_double; L.tjamd_last_union_tract_stats_ms.argtypes = [C.c_void_p]
     L.tjamd_last_union_tract_candidates.restype = C.c_long; L.tjamd_last_union_tract_candidates.argtypes = [C.c_void_p]
+    L.tjamd_reference_create.restype = C.c_void_p; L.tjamd_reference_create.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
+    L.tjamd_reference_destroy.restype = None; L.tjamd_reference_destroy.argtypes = [C.c_void_p]
+    L.tjamd_reference_entries.restype = C.c_long; L.tjamd_reference_entries.argtypes = [C.c_void_p]
+    L.tjamd_reference_contigs.restype = C.c_long; L.tjamd_reference_contigs.argtypes = [C.c_void_p]
+    L.tjamd_reference_download.restype = C.c_long; L.tjamd_reference_download.argtypes = [C.c_void_p, C.c_void_p, C.c_long]
+    L.tjamd_locate.restype = C.c_long; L.tjamd_locate.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_long, C.c_int, C.c_void_p]
+    L.tjamd_located_tracts.restype = C.c_long
+    L.tjamd_located_tracts.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_long, C.c_int, C.c_void_p, C.c_long, C.c_void_p,
+                                       C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_long]
+    L.tjamd_last_reference_ms.restype = C.c_double; L.tjamd_last_reference_ms.argtypes = [C.c_void_p]
+    L.tjamd_last_locate_ms.restype = C.c_double; L.tjamd_last_locate_ms.argtypes = [C.c_void_p]
+    L.tjamd_last_located_tracts_ms.restype = C.c_double; L.tjamd_last_located_tracts_ms.argtypes = [C.c_void_p]
     L.tjamd_group_contexts.restype = C.c_long
     L.tjamd_group_contexts.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_long]
     L.new_genomic_context_list.restype = C.POINTER(GenomicContextListStruct); L.new_genomic_context_list.argtypes = [P]
@@ -390,6 +412,39 @@ class Comm:
     __del__ = close
 
 
+class Reference:
+    """tjamd_reference: the index of a genome's runs (contigs as a stream of reads, each followed by a newline), built on
+    the counter's device with the counter's k"""
+
+    def __init__(self, counter, stream):
+        buf = np.frombuffer(bytes(stream), dtype=np.uint8)
+        self._h = lib().tjamd_reference_create(counter._h, buf.ctypes.data if len(buf) else None, len(buf))
+        if not self._h:
+            raise TatajubaAmdError(_err())
+
+    @property
+    def n_entries(self):
+        return int(lib().tjamd_reference_entries(self._h))
+
+    @property
+    def n_contigs(self):
+        return int(lib().tjamd_reference_contigs(self._h))
+
+    def download(self):
+        out = np.zeros(self.n_entries, dtype=REF_ENTRY_DTYPE)
+        n = lib().tjamd_reference_download(self._h, out.ctypes.data if len(out) else None, len(out))
+        if n < 0:
+            raise TatajubaAmdError(_err())
+        return out[:n]
+
+    def close(self):
+        if self._h:
+            lib().tjamd_reference_destroy(self._h)
+            self._h = None
+
+    __del__ = close
+
+
 class Counter:
     """tjamd_counter: device-side per-sample accumulator (include/tatajuba_amd.h)."""
 
@@ -562,6 +617,15 @@ class Counter:
 
     def last_union_tract_candidates(self):
         return int(lib().tjamd_last_union_tract_candidates(self._h))
+
+    def last_reference_ms(self):
+        return lib().tjamd_last_reference_ms(self._h)
+
+    def last_locate_ms(self):
+        return lib().tjamd_last_locate_ms(self._h)
+
+    def last_located_tracts_ms(self):
+        return lib().tjamd_last_located_tracts_ms(self._h)
 
     def uses_log(self):
         lib().tjamd_counter_uses_log.restype = C.c_int

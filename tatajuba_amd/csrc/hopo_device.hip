@@ -4113,7 +4113,7 @@ struct StageTimer
 };
 // the intervals of a counter: the last scan call (its partition kernels between the pieces included: tjamd_last_scan_ms takes
 // them out), finalise, the kernels of tjamd_merge_samples, tjamd_tract_stats, tjamd_union_tracts, tjamd_union_tract_stats
-enum { T_SCAN, T_FIN, T_MERGE, T_TRACT, T_UNION, T_UNION_STATS, TJ_N_TIMERS };
+enum { T_SCAN, T_FIN, T_MERGE, T_TRACT, T_UNION, T_UNION_STATS, T_REF, T_LOCATE, T_LOCATED_TRACTS, TJ_N_TIMERS };   // (the last three: N7, end of the file)
 
 struct tjamd_counter
 {
@@ -4137,6 +4137,7 @@ struct tjamd_counter
   DevBuf ts_cov, ts_aux;      // tjamd_tract_stats / tjamd_tract_sample_stats: the samples' coverages, error flag + last tract id
   long union_cand = -1;       // retry candidates of the last tjamd_union_tracts
   DevBuf ut_tot, ut_lev, ut_fb, ut_slots;   // union tracts: exact row totals, admitted edit distances, fallback flags, global bars
+  DevBuf lc_work;             // N7 (reference index, locate, located tracts): one block of scratch, cut up per call
   bool part_timed = false;    // the last scan call went through partition_log_kernel: timer[T_SCAN].e1 to ev_p1 is its time
   int fast_mode = 1;          // 1: scan_fast_kernel + the generic kernel on what it leaves; 0: generic kernel only; 2: fast kernel leaves everything (tests)
   u32 pool_chunks = 0, maxj = 0;
@@ -4244,7 +4245,7 @@ extern "C" void tjamd_counter_destroy (tjamd_counter *c)
   (void) hipStreamSynchronize (c->stream);
   DevBuf *all[] = {&c->log, &c->logmeta, &c->pool, &c->table, &c->stage, &c->fix, &c->loc, &c->prefix, &c->rawlist, &c->slow, &c->alt, &c->hist, &c->flags, &c->segid, &c->headpos,
                    &c->keep, &c->outpos, &c->scan_tmp, &c->kept, &c->idx_i, &c->idx_f, &c->cov, &c->bins, &c->binstart, &c->binctx, &c->ovf, &c->grp_jt, &c->grp_hist, &c->fine,
-                   &c->ts_cov, &c->ts_aux, &c->ut_tot, &c->ut_lev, &c->ut_fb, &c->ut_slots};
+                   &c->ts_cov, &c->ts_aux, &c->ut_tot, &c->ut_lev, &c->ut_fb, &c->ut_slots, &c->lc_work};
   for (DevBuf *b : all) release (*b);
   for (hipEvent_t ev : c->marks) if (ev) (void) hipEventDestroy (ev);
   if (c->d_state) (void) hipFree (c->d_state);
@@ -6707,3 +6708,577 @@ extern "C" long tjamd_allgather_histograms (tjamd_counter *c, tjamd_comm *m, con
   }
   return -set_err (TJAMD_ERR_STATE, "the exchange did not settle on a block size");
 }
+
+// ---------------------------------------------------------------------------------------------------------------
+// N7: tracts located on a reference genome by flank matching (reference: find_reference_location_and_sort_hopo_counter,
+// src/hopo_counter.c:495-572, which asks BWA; find_best_context_name_for_reference, src/genome_set.c:525-577, which rescans
+// the reference window; context_histograms_overlap / genomic_context_merge_histograms_at_same_location,
+// src/context_histogram.c:88-110,364-385, which make one tract of two histograms at one place).  The genome is scanned as
+// a stream of reads: a tract seen in a read and the same tract seen in the genome give the same canonical (base, ctx0,
+// ctx1), so locating is a join of keys against an index of the genome's own runs, one flank exact and the other within
+// max_mismatches.  Three parts: the index (tjamd_reference), the lookup (tjamd_locate), the tracts merged by location
+// (tjamd_located_tracts).  DESIGN.md section 3.5, N7, has the layout, the thread mapping of the lookup and the measurements.
+
+struct RefEntry { u64 ctx0, ctx1; long long flat; int contig, pos, length, base, neg_strand, pad; };
+static_assert (sizeof (RefEntry) == 48 && sizeof (RefEntry) == sizeof (tjamd_ref_entry), "reference entry layout");
+struct Location { long long flat; int contig, pos, ref_length, mismatches, neg_strand, n_hits; };
+static_assert (sizeof (Location) == 32 && sizeof (Location) == sizeof (tjamd_location), "location layout");
+
+// The two orders of the index are arrays of three-word records (primary flank, secondary flank, word) sorted by
+// radix_sort_records: descending by (base, primary, secondary), entries of one key in ascending entry number -- which is
+// ascending flat position, the entries being written in stream order.  The word holds the base in bits 0-1, where the
+// sort key reads it, and the entry number in bits 12-43 (the count and mismatch fields, which the sort key does not read).
+#define LC_IDX_SHIFT 12
+#define LC_PAD_IDX   0xFFFFFFFFull      // a record beyond the last entry: smallest key, behind every entry (the sort is stable)
+
+struct tjamd_reference
+{
+  int device = 0, k = 0;
+  long n_entries = 0, n_contigs = 0;
+  RefEntry *entries = nullptr;          // ascending flat
+  u64 *ord[2] = {nullptr, nullptr};     // [0]: primary = ctx0, secondary = ctx1; [1]: the other way round
+  void *owned[4] = {nullptr, nullptr, nullptr, nullptr};
+};
+
+// byte classes of the index: 0-3 the base of an ACGTU byte (either case), 4 the contig delimiter, 5 anything else
+__device__ __forceinline__ u32 ref_class (u32 b) { return byte_is_acgtu (b) ? byte_code (b) : (b == '\n' ? 4u : 5u); }
+
+// a segment is a maximal stretch of one class; every delimiter is a segment of its own (an empty contig still counts)
+__global__ void ref_seg_flag_kernel (const uint8_t *__restrict__ seq, long n, u32 *__restrict__ flag)
+{
+  for (long i = blockIdx.x * (long) blockDim.x + threadIdx.x; i < n; i += (long) gridDim.x * blockDim.x) {
+    const u32 cl = ref_class (seq[i]);
+    flag[i] = (i == 0 || cl == 4u || cl != ref_class (seq[i - 1])) ? 1u : 0u;
+  }
+}
+
+__global__ void ref_seg_pos_kernel (const u32 *__restrict__ flag, const u32 *__restrict__ excl, long n, u32 *__restrict__ segpos)
+{ // segpos[n_seg] = n closes the last segment
+  for (long i = blockIdx.x * (long) blockDim.x + threadIdx.x; i < n; i += (long) gridDim.x * blockDim.x) {
+    if (flag[i]) segpos[excl[i]] = (u32) i;
+    if (i == n - 1) segpos[excl[i] + flag[i]] = (u32) n;
+  }
+}
+
+// which segments become entries (a run of a base whose 2k flank bytes are all ACGTU: the delimiter is not, so both
+// flanks lie in the run's contig) and which are delimiters.  Segments at and beyond *n_seg get zeros: the scans run over n.
+__global__ void ref_seg_class_kernel (const uint8_t *__restrict__ seq, long n, int k, const u32 *__restrict__ segpos, const u32 *__restrict__ n_seg,
+                                      u32 *__restrict__ vflag, u32 *__restrict__ nlflag)
+{
+  const long ns = (long) *n_seg;
+  for (long j = blockIdx.x * (long) blockDim.x + threadIdx.x; j < n; j += (long) gridDim.x * blockDim.x) {
+    u32 v = 0, nl = 0;
+    if (j < ns) {
+      const long s = segpos[j], e = (long) segpos[j + 1] - 1;
+      const u32 b = seq[s];
+      nl = b == '\n';
+      if (byte_is_acgtu (b) && s - k >= 0 && e + k < n) {
+        v = 1;
+        for (int i = 1; i <= k; i++) if (!byte_is_acgtu (seq[s - i]) || !byte_is_acgtu (seq[e + i])) { v = 0; break; }
+      }
+    }
+    vflag[j] = v; nlflag[j] = nl;
+  }
+}
+
+__global__ void ref_nlpos_kernel (const u32 *__restrict__ segpos, const u32 *__restrict__ n_seg, const u32 *__restrict__ nlflag,
+                                  const u32 *__restrict__ nlex, long n, u32 *__restrict__ nlpos)
+{
+  const long ns = (long) *n_seg;
+  for (long j = blockIdx.x * (long) blockDim.x + threadIdx.x; j < ns && j < n; j += (long) gridDim.x * blockDim.x)
+    if (nlflag[j]) nlpos[nlex[j]] = segpos[j];
+}
+
+// the entries in stream order, and the unsorted records of both orders (padded to n: the sort's size is fixed before the
+// number of entries is known to the host)
+__global__ void ref_entry_kernel (const uint8_t *__restrict__ seq, long n, int k, const u32 *__restrict__ segpos, const u32 *__restrict__ n_seg,
+                                  const u32 *__restrict__ vflag, const u32 *__restrict__ vex, const u32 *__restrict__ n_ent,
+                                  const u32 *__restrict__ nlex, const u32 *__restrict__ nlpos,
+                                  RefEntry *__restrict__ entries, u64 *__restrict__ ord0, u64 *__restrict__ ord1)
+{
+  const long ns = (long) *n_seg, ne = (long) *n_ent;
+  for (long j = blockIdx.x * (long) blockDim.x + threadIdx.x; j < n; j += (long) gridDim.x * blockDim.x) {
+    if (j >= ne) {
+      const u64 pad = LC_PAD_IDX << LC_IDX_SHIFT;
+      ord0[3 * j] = 0; ord0[3 * j + 1] = 0; ord0[3 * j + 2] = pad;
+      ord1[3 * j] = 0; ord1[3 * j + 1] = 0; ord1[3 * j + 2] = pad;
+    }
+    if (j >= ns || !vflag[j]) continue;
+    const long s = segpos[j], e = (long) segpos[j + 1] - 1;
+    u64 left = 0, right = 0;
+    for (int i = 0; i < k; i++) {
+      left |= (u64) byte_code (seq[s - k + i]) << (2 * i);
+      right |= (u64) byte_code (seq[e + 1 + i]) << (2 * i);
+    }
+    u64 c0, c1; u32 base, flag;
+    canonicalise (left, right, 0u, 0u, byte_code (seq[s]), k, c0, c1, base, flag);
+    const long x = vex[j], ct = nlex[j], cstart = ct ? (long) nlpos[ct - 1] + 1 : 0;
+    entries[x] = RefEntry {c0, c1, s - ct, (int) ct, (int) (s - cstart), (int) (e - s + 1), (int) base, flag == 2u ? 1 : 0, 0};
+    const u64 word = (u64) base | ((u64) x << LC_IDX_SHIFT);
+    ord0[3 * x] = c0; ord0[3 * x + 1] = c1; ord0[3 * x + 2] = word;
+    ord1[3 * x] = c1; ord1[3 * x + 1] = c0; ord1[3 * x + 2] = word;
+  }
+}
+
+// scratch of the three entries: u32 words cut from c->lc_work, each piece on a 256-byte boundary
+struct LcCut
+{
+  char *p; size_t used = 0;
+  explicit LcCut (void *base) : p ((char *) base) {}
+  template <class T> T *take (size_t count) { T *r = p ? (T *) (p + used) : nullptr; used += (count * sizeof (T) + 255) & ~(size_t) 255; return r; }
+};
+
+extern "C" void tjamd_reference_destroy (tjamd_reference *ref)
+{
+  if (!ref) return;
+  (void) hipSetDevice (ref->device);
+  for (void *p : ref->owned) if (p) (void) hipFree (p);
+  delete ref;
+}
+
+extern "C" tjamd_reference *tjamd_reference_create (tjamd_counter *c, const void *h_stream, size_t n_bytes)
+{
+  static const char *fn = "tjamd_reference_create";
+  if (tjamd_device_count () <= 0) { set_err (TJAMD_ERR_NO_DEVICE, "%s: TJAMD_ERR_NO_DEVICE: no HIP device visible (the index is built on the device; no CPU fallback)", fn); return NULL; }
+  if (!c) { set_err (TJAMD_ERR_ARG, "%s: null counter", fn); return NULL; }
+  if (n_bytes && !h_stream) { set_err (TJAMD_ERR_ARG, "%s: null stream", fn); return NULL; }
+  if (n_bytes >= (size_t) 1 << 31) { set_err (TJAMD_ERR_CAPACITY, "%s: a stream of %zu bytes (positions are 32-bit)", fn, n_bytes); return NULL; }
+  HIPCHK_NULL (hipSetDevice (c->device));
+  c->timer[T_REF].timed = false;
+  tjamd_reference *ref = new tjamd_reference ();
+  ref->device = c->device; ref->k = c->k;
+  const long n = (long) n_bytes;
+  if (n == 0) return ref;
+#define REF_FAIL(...) do { set_err (__VA_ARGS__); tjamd_reference_destroy (ref); return NULL; } while (0)
+  for (int pass = 0; pass < 2; pass++) {               // (sizes first, then the same cuts from the block)
+    LcCut cut (pass ? c->lc_work.p : nullptr);
+    u32 *flag = cut.take<u32> (n), *excl = cut.take<u32> (n), *segpos = cut.take<u32> (n + 1), *nlflag = cut.take<u32> (n), *nlex = cut.take<u32> (n),
+        *nlpos = cut.take<u32> (n + 1), *tot = cut.take<u32> (64);
+    if (!pass) {
+      if (ensure (c->lc_work, cut.used, c->stream) || ensure (c->stage, ((size_t) n + 255) & ~(size_t) 255, c->stream) ||
+          ensure (c->scan_tmp, scan_tmp_words (n) * 4 + 64, c->stream)) { tjamd_reference_destroy (ref); return NULL; }
+      for (int i = 0; i < 4; i++)
+        if (hipMalloc (&ref->owned[i], (size_t) n * (i ? 24 : sizeof (RefEntry))) != hipSuccess) REF_FAIL (TJAMD_ERR_HIP, "%s: hipMalloc failed for %ld bytes of genome", fn, n);
+      continue;
+    }
+    const uint8_t *seq = (const uint8_t *) c->stage.p;
+    u32 *tmp = (u32 *) c->scan_tmp.p; const size_t tw = scan_tmp_words (n);
+    u32 *n_seg = tot, *n_ent = tot + 1, *n_nl = tot + 2;
+    const dim3 g (grid_for (n)), b (256);
+    if (hipMemcpyAsync (c->stage.p, h_stream, n_bytes, hipMemcpyHostToDevice, c->stream) != hipSuccess) REF_FAIL (TJAMD_ERR_HIP, "%s: copy to device failed", fn);
+    (void) c->timer[T_REF].begin (c->stream);
+    hipLaunchKernelGGL (ref_seg_flag_kernel, g, b, 0, c->stream, seq, n, flag);
+    int rc = exclusive_scan (c, flag, excl, n, n_seg, tmp, tw);
+    hipLaunchKernelGGL (ref_seg_pos_kernel, g, b, 0, c->stream, (const u32 *) flag, (const u32 *) excl, n, segpos);
+    u32 *vflag = flag, *vex = excl;                     // (both free again once the segment positions are written)
+    hipLaunchKernelGGL (ref_seg_class_kernel, g, b, 0, c->stream, seq, n, c->k, (const u32 *) segpos, (const u32 *) n_seg, vflag, nlflag);
+    if (!rc) rc = exclusive_scan (c, vflag, vex, n, n_ent, tmp, tw);
+    if (!rc) rc = exclusive_scan (c, nlflag, nlex, n, n_nl, tmp, tw);
+    hipLaunchKernelGGL (ref_nlpos_kernel, g, b, 0, c->stream, (const u32 *) segpos, (const u32 *) n_seg, (const u32 *) nlflag, (const u32 *) nlex, n, nlpos);
+    u64 *r0 = (u64 *) ref->owned[1], *r1 = (u64 *) ref->owned[2], *r2 = (u64 *) ref->owned[3];
+    hipLaunchKernelGGL (ref_entry_kernel, g, b, 0, c->stream, seq, n, c->k, (const u32 *) segpos, (const u32 *) n_seg, (const u32 *) vflag, (const u32 *) vex,
+                        (const u32 *) n_ent, (const u32 *) nlex, (const u32 *) nlpos, (RefEntry *) ref->owned[0], r0, r1);
+    if (rc || hipGetLastError () != hipSuccess) { if (!rc) set_err (TJAMD_ERR_HIP, "%s: launch failed", fn); tjamd_reference_destroy (ref); return NULL; }
+    if (radix_sort_records (c, r0, r2, n) || radix_sort_records (c, r1, r2, n)) { tjamd_reference_destroy (ref); return NULL; }   // (results in r0 and r1, whichever blocks those now are)
+    (void) c->timer[T_REF].end (c->stream);
+    u32 h[3] = {0, 0, 0};
+    uint8_t last = 0;
+    if (hipMemcpyAsync (h, tot, sizeof (h), hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
+        hipMemcpyAsync (&last, seq + n - 1, 1, hipMemcpyDeviceToHost, c->stream) != hipSuccess || hipStreamSynchronize (c->stream) != hipSuccess)
+      REF_FAIL (TJAMD_ERR_HIP, "%s: build failed: %s", fn, hipGetErrorString (hipGetLastError ()));
+    ref->entries = (RefEntry *) ref->owned[0]; ref->ord[0] = r0; ref->ord[1] = r1;
+    ref->n_entries = (long) h[1]; ref->n_contigs = (long) h[2] + (last != '\n' ? 1 : 0);
+    for (int i = 1; i < 4; i++) if (ref->owned[i] == (void *) r2) { (void) hipFree (r2); ref->owned[i] = nullptr; }   // the sort's spare block
+    if (ref->n_entries < n) {                           // keep what the entries take, not what the stream could have held
+      const size_t ne = (size_t) std::max<long> (ref->n_entries, 1);
+      void *small[3] = {nullptr, nullptr, nullptr}, *big[3] = {ref->entries, ref->ord[0], ref->ord[1]};
+      const size_t bytes[3] = {ne * sizeof (RefEntry), ne * 24, ne * 24};
+      bool ok = true;
+      for (int i = 0; i < 3 && ok; i++) ok = hipMalloc (&small[i], bytes[i]) == hipSuccess && hipMemcpy (small[i], big[i], bytes[i], hipMemcpyDeviceToDevice) == hipSuccess;
+      if (ok) {
+        for (void *&p : ref->owned) { if (p) (void) hipFree (p); p = nullptr; }
+        for (int i = 0; i < 3; i++) ref->owned[i] = small[i];
+        ref->entries = (RefEntry *) small[0]; ref->ord[0] = (u64 *) small[1]; ref->ord[1] = (u64 *) small[2];
+      } else {                                          // (no room for the copies: the index stays in its first blocks)
+        for (void *p : small) if (p) (void) hipFree (p);
+        (void) hipGetLastError ();
+      }
+    }
+    c->timer[T_REF].timed = true;
+  }
+#undef REF_FAIL
+  return ref;
+}
+
+extern "C" long tjamd_reference_entries (const tjamd_reference *ref) { return ref ? ref->n_entries : -1; }
+extern "C" long tjamd_reference_contigs (const tjamd_reference *ref) { return ref ? ref->n_contigs : -1; }
+extern "C" long tjamd_reference_download (const tjamd_reference *ref, tjamd_ref_entry *out, long capacity)
+{
+  if (!ref || (ref->n_entries && !out)) return -set_err (TJAMD_ERR_ARG, "tjamd_reference_download: null reference or buffer");
+  if (ref->n_entries > capacity) return -set_err (TJAMD_ERR_CAPACITY, "tjamd_reference_download: %ld entries, caller capacity %ld", ref->n_entries, capacity);
+  if (ref->n_entries && (hipSetDevice (ref->device) != hipSuccess || hipMemcpy (out, ref->entries, (size_t) ref->n_entries * sizeof (RefEntry), hipMemcpyDeviceToHost) != hipSuccess))
+    return -set_err (TJAMD_ERR_HIP, "tjamd_reference_download: copy failed");
+  return ref->n_entries;
+}
+extern "C" double tjamd_last_reference_ms (tjamd_counter *c) { return c ? c->timer[T_REF].ms (c->device) : -1.0; }
+
+// ---- the lookup --------------------------------------------------------------------------------------------------
+// Thread mapping: a lane per query finds its two buckets (the entries with its base and its exact flank) by binary search
+// and walks a bucket of up to LC_LANE_WALK entries by itself: at k >= 12 nearly every bucket has 0 to 2 entries and the 64
+// lanes stay in step.  A longer bucket (thousands of entries at k = 5) is handed to the whole wavefront: the owner's query
+// and bounds are broadcast, the 64 lanes read the bucket as contiguous records and the result is reduced with shuffles, so
+// the time of a wavefront is the sum of its long buckets over 64, not the longest one times 64.
+
+#define LC_LANE_WALK 16
+
+// first record of ord[0, n) (descending by base, primary) that does not sort before / that sorts behind (base, primary)
+__device__ __forceinline__ long ord_bound (const u64 *__restrict__ ord, long n, u32 qb, u64 qp, bool behind)
+{
+  long lo = 0, hi = n;
+  while (lo < hi) {
+    const long mid = (lo + hi) >> 1;
+    const u64 p = ord[3 * mid];
+    const u32 b = (u32) ord[3 * mid + 2] & 3u;
+    const bool before = b > qb || (b == qb && (behind ? p >= qp : p > qp));
+    if (before) lo = mid + 1; else hi = mid;
+  }
+  return lo;
+}
+
+// one record against a query's inexact flank: best = (mismatches << 32 | entry number), the smallest wins
+__device__ __forceinline__ void locate_try (const u64 *__restrict__ ord, long i, u64 qs, int maxm, bool skip_exact, u64 &best, u32 &hits)
+{
+  const int d = flank_hamming (ord[3 * i + 1], qs);
+  if (d <= maxm && !(skip_exact && d == 0)) {           // (exact in both flanks: counted on the ctx0 side)
+    hits++;
+    const u64 cand = ((u64) d << 32) | ((ord[3 * i + 2] >> LC_IDX_SHIFT) & 0xFFFFFFFFull);
+    best = cand < best ? cand : best;
+  }
+}
+
+__global__ __launch_bounds__ (256)
+void locate_kernel (const u64 *__restrict__ keys, long n, const u64 *__restrict__ ord0, const u64 *__restrict__ ord1, long n_ent,
+                    const RefEntry *__restrict__ entries, int maxm, Location *__restrict__ loc, u32 *__restrict__ n_located)
+{
+  const int lane = threadIdx.x & 63;
+  const long stride = (long) gridDim.x * blockDim.x;
+  for (long q0 = blockIdx.x * (long) blockDim.x + (threadIdx.x & ~63); q0 < n; q0 += stride) {     // (uniform across a wavefront)
+    const long q = q0 + lane;
+    const bool active = q < n;
+    u64 qc[2] = {0, 0}; u32 qb = 0;
+    if (active) { qc[0] = keys[3 * q]; qc[1] = keys[3 * q + 1]; qb = (u32) keys[3 * q + 2] & 3u; }
+    u64 best = ~0ull; u32 hits = 0;
+#pragma unroll
+    for (int side = 0; side < 2; side++) {
+      const u64 *__restrict__ ord = side ? ord1 : ord0;
+      const u64 qp = qc[side], qs = qc[1 - side];
+      long lo = 0, hi = 0;
+      if (active) { lo = ord_bound (ord, n_ent, qb, qp, false); hi = ord_bound (ord, n_ent, qb, qp, true); }
+      const bool mine = hi - lo <= LC_LANE_WALK;
+      if (mine) for (long i = lo; i < hi; i++) locate_try (ord, i, qs, maxm, side == 1, best, hits);
+      u64 big = __ballot (!mine);
+      while (big) {                                     // the wavefront walks its long buckets together, one after the other
+        const int src = __ffsll ((long long) big) - 1;
+        big &= big - 1;
+        const long blo = __shfl (lo, src), bhi = __shfl (hi, src);
+        const u64 bqs = __shfl (qs, src);
+        u64 wb = ~0ull; u32 wh = 0;
+        for (long i = blo + lane; i < bhi; i += 64) locate_try (ord, i, bqs, maxm, side == 1, wb, wh);
+#pragma unroll
+        for (int o = 1; o < 64; o <<= 1) { const u64 ob = __shfl_xor (wb, o); wb = ob < wb ? ob : wb; wh += __shfl_xor (wh, o); }
+        if (lane == src) { best = wb < best ? wb : best; hits += wh; }
+      }
+    }
+    Location o = {-1, -1, -1, 0, 0, 0, 0};
+    if (hits) {
+      const RefEntry e = entries[best & 0xFFFFFFFFull];
+      o = Location {e.flat, e.contig, e.pos, e.length, (int) (best >> 32), e.neg_strand, (int) hits};
+    }
+    if (active) loc[q] = o;
+    const u64 found = __ballot (active && hits);
+    if (lane == 0 && found) atomicAdd (n_located, (u32) __popcll (found));
+  }
+}
+
+extern "C" long tjamd_locate (tjamd_counter *c, const tjamd_reference *ref, const void *d_keys, long n, int max_mismatches, tjamd_location *d_loc)
+{
+  static const char *fn = "tjamd_locate";
+  if (!c || !ref) return -set_err (TJAMD_ERR_ARG, "%s: null counter or reference", fn);
+  if (ref->k != c->k) return -set_err (TJAMD_ERR_ARG, "%s: the reference was built with k = %d, the counter has k = %d", fn, ref->k, c->k);
+  if (ref->device != c->device) return -set_err (TJAMD_ERR_ARG, "%s: the reference lives on device %d, the counter on device %d", fn, ref->device, c->device);
+  if (max_mismatches < 0 || max_mismatches > c->k) return -set_err (TJAMD_ERR_ARG, "%s: max_mismatches %d outside 0..%d", fn, max_mismatches, c->k);
+  if (n < 0) return -set_err (TJAMD_ERR_ARG, "%s: n %ld < 0", fn, n);
+  if (n >= (1l << 31)) return -set_err (TJAMD_ERR_CAPACITY, "%s: %ld rows", fn, n);
+  if (n > 0 && (!d_keys || !d_loc)) return -set_err (TJAMD_ERR_ARG, "%s: null key or location buffer", fn);
+  if (hipSetDevice (c->device) != hipSuccess) return -set_err (TJAMD_ERR_HIP, "hipSetDevice failed");
+  c->timer[T_LOCATE].timed = false;
+  if (n == 0) return 0;
+  int rc = ensure (c->lc_work, 256, c->stream);
+  if (rc) return -rc;
+  u32 *n_located = (u32 *) c->lc_work.p;
+  if (hipMemsetAsync (n_located, 0, 4, c->stream) != hipSuccess) return -set_err (TJAMD_ERR_HIP, "%s: memset failed", fn);
+  (void) c->timer[T_LOCATE].begin (c->stream);
+  hipLaunchKernelGGL (locate_kernel, dim3 (grid_for (n)), dim3 (256), 0, c->stream, (const u64 *) d_keys, n, (const u64 *) ref->ord[0], (const u64 *) ref->ord[1],
+                      ref->n_entries, (const RefEntry *) ref->entries, max_mismatches, (Location *) d_loc, n_located);
+  if (hipGetLastError () != hipSuccess) return -set_err (TJAMD_ERR_HIP, "%s: launch failed", fn);
+  (void) c->timer[T_LOCATE].end (c->stream);
+  u32 found = 0;
+  if (hipMemcpyAsync (&found, n_located, 4, hipMemcpyDeviceToHost, c->stream) != hipSuccess || hipStreamSynchronize (c->stream) != hipSuccess)
+    return -set_err (TJAMD_ERR_HIP, "%s: lookup failed: %s", fn, hipGetErrorString (hipGetLastError ()));
+  c->timer[T_LOCATE].timed = true;
+  return (long) found;
+}
+extern "C" double tjamd_last_locate_ms (tjamd_counter *c) { return c ? c->timer[T_LOCATE].ms (c->device) : -1.0; }
+
+// ---- tracts by location ------------------------------------------------------------------------------------------
+
+// the context-keyed tracts of tjamd_tract_ids as tjamd_union_tract (for a caller that passes no tracts): one thread per head
+__global__ void lt_context_tract_kernel (long n, const long long *__restrict__ total, const u32 *__restrict__ head, const u32 *__restrict__ excl,
+                                         UnionTract *__restrict__ tracts)
+{
+  for (long i = blockIdx.x * (long) blockDim.x + threadIdx.x; i < n; i += (long) gridDim.x * blockDim.x) {
+    if (i > 0 && !head[i]) continue;
+    UnionTract o = {(int) i, 0, 1, (int) i, 0, 0, 0};
+    long long mode_count = 0;
+    for (long j = i; j < n && (j == i || !head[j]); j++) {
+      const long long cj = total[j];
+      if (j == i || mode_count < cj) { mode_count = cj; o.mode = (int) j; }
+      o.integral += cj; o.n_rows++;
+    }
+    tracts[excl[i] + head[i]] = o;
+  }
+}
+
+#define LT_KEY_PASSES 6                 // 48 bits of key:
+#define LT_FLAT_MAX   (1ll << 45)       // (flat + 1) << 2 | base stays below 2^48 for flat below 2^45; larger ones are refused
+
+// a tract's sort key: 0 if it has no located row, else (flat + 1) << 2 | base of its located row with the highest total
+// (the first of equal totals).  Also checks that the tracts tile the union (err), as tjamd_union_tract_stats does.
+__global__ void lt_tract_key_kernel (const UnionTract *__restrict__ tracts, long nt, long n, const u64 *__restrict__ keys, const long long *__restrict__ total,
+                                     const Location *__restrict__ loc, u64 *__restrict__ key, u32 *__restrict__ val, int *__restrict__ err)
+{
+  for (long t = blockIdx.x * (long) blockDim.x + threadIdx.x; t < nt; t += (long) gridDim.x * blockDim.x) {
+    const long first = tracts[t].first, rows = tracts[t].n_rows;
+    const long want = t ? (long) tracts[t - 1].first + tracts[t - 1].n_rows : 0;
+    u64 kk = 0;
+    if (first != want || rows < 1 || first + rows > n || (t == nt - 1 && first + rows != n)) *err = 1;
+    else {
+      long best = -1; long long best_total = 0;
+      for (long r = first; r < first + rows; r++)
+        if (loc[r].flat >= 0 && (best < 0 || total[r] > best_total)) { best = r; best_total = total[r]; }
+      if (best >= 0 && loc[best].flat >= LT_FLAT_MAX) *err = 2;   // (the sort below would drop its upper bits)
+      else if (best >= 0) kk = ((u64) (loc[best].flat + 1) << 2) | (keys[3 * first + 2] & 3ull);
+    }
+    key[t] = kk; val[t] = (u32) t;
+  }
+}
+
+// stable ascending LSD radix sort of (64-bit key, 32-bit value) pairs, a digit of 8 bits per pass: the count / scatter
+// pair of radix_count_kernel / radix_scatter_kernel for keys that are not records
+__global__ __launch_bounds__ (256)
+void kv_count_kernel (const u64 *__restrict__ key, long n, int pass, u32 *__restrict__ hist, int nblk)
+{
+  __shared__ u32 h[256];
+  const int tid = threadIdx.x, lane = tid & 63;
+  const u64 lt = (1ull << lane) - 1ull;
+  h[tid] = 0;
+  __syncthreads ();
+  const long base = (long) blockIdx.x * RS_ITEMS;
+  for (int i = tid; i < RS_ITEMS; i += 256) {
+    const long r = base + i;
+    const bool active = r < n;
+    const u32 d = active ? (u32) (key[r] >> (8 * pass)) & 0xFFu : 0u;
+    const u64 peers = match_digit (d, active);
+    if (active && (peers & lt) == 0ull) atomicAdd (&h[d], (u32) __popcll (peers));
+  }
+  __syncthreads ();
+  hist[(long) tid * nblk + blockIdx.x] = h[tid];
+}
+
+__global__ __launch_bounds__ (256)
+void kv_scatter_kernel (const u64 *__restrict__ key, const u32 *__restrict__ val, u64 *__restrict__ key_out, u32 *__restrict__ val_out, long n, int pass,
+                        const u32 *__restrict__ offs, int nblk)
+{
+  __shared__ u32 wcnt[4][256];
+  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+  for (int i = tid; i < 1024; i += 256) (&wcnt[0][0])[i] = 0;
+  __syncthreads ();
+  const long wbase = (long) blockIdx.x * RS_ITEMS + (long) wave * RS_WAVE_ITEMS;
+  const u64 lt = (1ull << lane) - 1ull;
+  for (int r = 0; r < RS_WAVE_ITEMS / 64; r++) {
+    const long idx = wbase + r * 64 + lane;
+    const bool active = idx < n;
+    const u32 d = active ? (u32) (key[idx] >> (8 * pass)) & 0xFFu : 0u;
+    const u64 peers = match_digit (d, active);
+    if (active && (peers & lt) == 0ull) atomicAdd (&wcnt[wave][d], (u32) __popcll (peers));
+  }
+  __syncthreads ();
+  {
+    u32 run = offs[(long) tid * nblk + blockIdx.x];
+    for (int w = 0; w < 4; w++) { u32 cnt = wcnt[w][tid]; wcnt[w][tid] = run; run += cnt; }
+  }
+  __syncthreads ();
+  for (int r = 0; r < RS_WAVE_ITEMS / 64; r++) {
+    const long idx = wbase + r * 64 + lane;
+    const bool active = idx < n;
+    u64 kk = 0; u32 v = 0, d = 0;
+    if (active) { kk = key[idx]; v = val[idx]; d = (u32) (kk >> (8 * pass)) & 0xFFu; }
+    const u64 peers = match_digit (d, active);
+    const int leader = active ? (__ffsll ((long long) peers) - 1) : 0;
+    u32 old = 0;
+    if (active && lane == leader) old = atomicAdd (&wcnt[wave][d], (u32) __popcll (peers));
+    old = __shfl (old, leader);
+    if (active) { const u64 at = (u64) old + (u64) __popcll (peers & lt); key_out[at] = kk; val_out[at] = v; }
+  }
+}
+
+
+// the sorted tracts: where a merged tract starts (a new key, or no location: every unlocated tract stays alone) and the
+// rows each brings
+__global__ void lt_head_kernel (const u64 *__restrict__ key, const u32 *__restrict__ val, long nt, const UnionTract *__restrict__ tracts,
+                                u32 *__restrict__ head, u32 *__restrict__ rows)
+{
+  for (long j = blockIdx.x * (long) blockDim.x + threadIdx.x; j < nt; j += (long) gridDim.x * blockDim.x) {
+    head[j] = (j == 0 || key[j] == 0ull || key[j] != key[j - 1]) ? 1u : 0u;
+    rows[j] = (u32) max (tracts[val[j]].n_rows, 0);
+  }
+}
+
+// output row i is input row perm[i]: the sorted tract whose rows cover i (rowstart: exclusive scan of rows), its rows in union order
+__global__ void lt_perm_kernel (long n, long nt, const u32 *__restrict__ rowstart, const u32 *__restrict__ val, const UnionTract *__restrict__ tracts,
+                                const u64 *__restrict__ keys, int *__restrict__ perm, u64 *__restrict__ out_keys)
+{
+  for (long i = blockIdx.x * (long) blockDim.x + threadIdx.x; i < n; i += (long) gridDim.x * blockDim.x) {
+    long lo = 0, hi = nt;                               // last j with rowstart[j] <= i
+    while (hi - lo > 1) { const long mid = (lo + hi) >> 1; if ((long) rowstart[mid] <= i) lo = mid; else hi = mid; }
+    long r = (long) tracts[val[lo]].first + (i - (long) rowstart[lo]);
+    if (r < 0 || r >= n) r = 0;                         // (tracts that do not tile the union: refused at the end of the call)
+    perm[i] = (int) r;
+    if (out_keys) { out_keys[3 * i] = keys[3 * r]; out_keys[3 * i + 1] = keys[3 * r + 1]; out_keys[3 * i + 2] = keys[3 * r + 2]; }
+  }
+}
+
+__global__ void lt_gather_counts_kernel (const int *__restrict__ counts, const int *__restrict__ perm, long n, int ns, int *__restrict__ out)
+{
+  const long total = n * (long) ns;
+  for (long x = blockIdx.x * (long) blockDim.x + threadIdx.x; x < total; x += (long) gridDim.x * blockDim.x) {
+    const long i = x / ns; const int s = (int) (x - i * ns);
+    out[x] = counts[(long) perm[i] * ns + s];
+  }
+}
+
+// one thread per merged tract (at its first member): sums, flags, the modal output row, and the location of its located
+// row with the highest total (the first in output order on a tie: that of its first member's, all members sharing flat)
+__global__ void lt_merge_kernel (long nt, long n, const u32 *__restrict__ head, const u32 *__restrict__ hex, const u32 *__restrict__ rowstart,
+                                 const u32 *__restrict__ val, const UnionTract *__restrict__ tracts, const long long *__restrict__ total,
+                                 const Location *__restrict__ loc, long cap, UnionTract *__restrict__ out, Location *__restrict__ out_loc, int *__restrict__ ref_length)
+{
+  for (long j = blockIdx.x * (long) blockDim.x + threadIdx.x; j < nt; j += (long) gridDim.x * blockDim.x) {
+    if (!head[j]) continue;
+    const long g = hex[j];
+    if (g >= cap) continue;
+    UnionTract o = {(int) rowstart[j], 0, 0, (int) rowstart[j], 0, 0, 0};
+    long long mode_total = 0, loc_total = 0; long loc_row = -1; bool have_mode = false;
+    for (long m = j; m < nt && (m == j || !head[m]); m++) {
+      const UnionTract t = tracts[val[m]];
+      o.n_rows += t.n_rows; o.n_context += t.n_context; o.integral += t.integral; o.indel |= t.indel; o.lev_distance = max (o.lev_distance, t.lev_distance);
+      for (long x = 0; x < t.n_rows; x++) {
+        const long r = (long) t.first + x;
+        if (r < 0 || r >= n) break;
+        const long long tr = total[r];
+        if (!have_mode || tr > mode_total) { have_mode = true; mode_total = tr; o.mode = (int) ((long) rowstart[m] + x); }
+        if (loc[r].flat >= 0 && (loc_row < 0 || tr > loc_total)) { loc_row = r; loc_total = tr; }
+      }
+    }
+    out[g] = o;
+    const Location l = loc_row >= 0 ? loc[loc_row] : Location {-1, -1, -1, 0, 0, 0, 0};
+    if (out_loc) out_loc[g] = l;
+    if (ref_length) ref_length[g] = l.ref_length;
+  }
+}
+
+extern "C" long tjamd_located_tracts (tjamd_counter *c, const void *d_keys, const void *d_counts, long n_union, int n_samples,
+                                      const tjamd_union_tract *d_tracts, long n_tracts, const tjamd_location *d_loc,
+                                      int *d_perm, void *d_out_keys, void *d_out_counts,
+                                      tjamd_union_tract *d_out_tracts, tjamd_location *d_tract_loc, int *d_ref_length, long capacity)
+{
+  static const char *fn = "tjamd_located_tracts";
+  int rc = union_args (fn, d_keys, d_counts, n_union, n_samples);
+  if (rc) return -rc;
+  if (n_union > 0 && (!d_loc || !d_perm || !d_out_tracts)) return -set_err (TJAMD_ERR_ARG, "%s: null location, permutation or tract buffer", fn);
+  if (d_tracts && (n_tracts < (n_union > 0 ? 1 : 0) || n_tracts > n_union)) return -set_err (TJAMD_ERR_ARG, "%s: n_tracts %ld for a union of %ld rows", fn, n_tracts, n_union);
+  if (capacity < (n_union > 0 ? 1 : 0)) return -set_err (TJAMD_ERR_CAPACITY, "%s: capacity %ld for a union of %ld rows", fn, capacity, n_union);
+  if (!c) return -set_err (TJAMD_ERR_ARG, "%s: null counter", fn);
+  if (hipSetDevice (c->device) != hipSuccess) return -set_err (TJAMD_ERR_HIP, "hipSetDevice failed");
+  c->timer[T_LOCATED_TRACTS].timed = false;
+  const long n = n_union;
+  if (n == 0) return 0;
+  const int nblk_max = (int) ((n + RS_ITEMS - 1) / RS_ITEMS);
+  LcCut cut (nullptr);
+  UnionTract *own = nullptr; u64 *key[2] = {nullptr, nullptr}; u32 *val[2] = {nullptr, nullptr}, *head = nullptr, *hex = nullptr, *rows = nullptr, *rowstart = nullptr, *tot = nullptr;
+  for (int pass = 0; pass < 2; pass++) {
+    cut = LcCut (pass ? c->lc_work.p : nullptr);
+    own = cut.take<UnionTract> (n); key[0] = cut.take<u64> (n); key[1] = cut.take<u64> (n); val[0] = cut.take<u32> (n); val[1] = cut.take<u32> (n);
+    head = cut.take<u32> (n); hex = cut.take<u32> (n); rows = cut.take<u32> (n); rowstart = cut.take<u32> (n); tot = cut.take<u32> (64);
+    if (!pass) {
+      rc = ensure (c->lc_work, cut.used, c->stream);
+      if (!rc) rc = ensure (c->ut_tot, (size_t) n * 8, c->stream);
+      if (!rc) rc = ensure (c->hist, (size_t) 256 * nblk_max * 4, c->stream);
+      if (!rc) rc = ensure (c->scan_tmp, std::max (scan_tmp_words (256l * nblk_max), scan_tmp_words (n)) * 4 + 64, c->stream);
+      if (rc) return -rc;
+    }
+  }
+  u32 *tmp = (u32 *) c->scan_tmp.p; const size_t tw = c->scan_tmp.cap / 4;
+  long long *total = (long long *) c->ut_tot.p;
+  u32 *n_out = tot; int *err = (int *) tot + 1;
+  if (hipMemsetAsync (tot, 0, 256, c->stream) != hipSuccess) return -set_err (TJAMD_ERR_HIP, "%s: memset failed", fn);
+  (void) c->timer[T_LOCATED_TRACTS].begin (c->stream);
+  const int S = tract_segment (n_samples);
+  hipLaunchKernelGGL (union_totals_kernel, dim3 (tract_grid (n, S)), dim3 (256), 0, c->stream, (const int *) d_counts, n, n_samples, S, total);
+  const UnionTract *tracts = (const UnionTract *) d_tracts;
+  long nt = n_tracts;
+  if (!tracts) {                                        // the context-keyed tracts: their number is needed on the host (one wait more)
+    hipLaunchKernelGGL (tract_head_kernel, dim3 (grid_for (n)), dim3 (256), 0, c->stream, (const u64 *) d_keys, n, head);
+    rc = exclusive_scan (c, head, hex, n, tot + 2, tmp, tw);
+    if (rc) return -rc;
+    hipLaunchKernelGGL (lt_context_tract_kernel, dim3 (grid_for (n)), dim3 (256), 0, c->stream, n, (const long long *) total, (const u32 *) head, (const u32 *) hex, own);
+    u32 nh = 0;
+    if (hipMemcpyAsync (&nh, tot + 2, 4, hipMemcpyDeviceToHost, c->stream) != hipSuccess || hipStreamSynchronize (c->stream) != hipSuccess)
+      return -set_err (TJAMD_ERR_HIP, "%s: tract ids failed: %s", fn, hipGetErrorString (hipGetLastError ()));
+    tracts = own; nt = (long) nh + 1;
+  }
+  hipLaunchKernelGGL (lt_tract_key_kernel, dim3 (grid_for (nt)), dim3 (256), 0, c->stream, tracts, nt, n, (const u64 *) d_keys, (const long long *) total,
+                      (const Location *) d_loc, key[0], val[0], err);
+  const int nblk = (int) ((nt + RS_ITEMS - 1) / RS_ITEMS);
+  for (int p = 0; p < LT_KEY_PASSES; p++) {
+    hipLaunchKernelGGL (kv_count_kernel, dim3 (nblk), dim3 (256), 0, c->stream, (const u64 *) key[0], nt, p, (u32 *) c->hist.p, nblk);
+    rc = exclusive_scan (c, (const u32 *) c->hist.p, (u32 *) c->hist.p, 256l * nblk, nullptr, tmp, tw);
+    if (rc) return -rc;
+    hipLaunchKernelGGL (kv_scatter_kernel, dim3 (nblk), dim3 (256), 0, c->stream, (const u64 *) key[0], (const u32 *) val[0], key[1], val[1], nt, p,
+                        (const u32 *) c->hist.p, nblk);
+    std::swap (key[0], key[1]); std::swap (val[0], val[1]);
+  }
+  hipLaunchKernelGGL (lt_head_kernel, dim3 (grid_for (nt)), dim3 (256), 0, c->stream, (const u64 *) key[0], (const u32 *) val[0], nt, tracts, head, rows);
+  rc = exclusive_scan (c, head, hex, nt, n_out, tmp, tw);
+  if (!rc) rc = exclusive_scan (c, rows, rowstart, nt, nullptr, tmp, tw);
+  if (rc) return -rc;
+  hipLaunchKernelGGL (lt_perm_kernel, dim3 (grid_for (n)), dim3 (256), 0, c->stream, n, nt, (const u32 *) rowstart, (const u32 *) val[0], tracts,
+                      (const u64 *) d_keys, d_perm, (u64 *) d_out_keys);
+  if (d_out_counts)
+    hipLaunchKernelGGL (lt_gather_counts_kernel, dim3 (grid_for (n * (long) n_samples)), dim3 (256), 0, c->stream, (const int *) d_counts, (const int *) d_perm, n, n_samples,
+                        (int *) d_out_counts);
+  hipLaunchKernelGGL (lt_merge_kernel, dim3 (grid_for (nt)), dim3 (256), 0, c->stream, nt, n, (const u32 *) head, (const u32 *) hex, (const u32 *) rowstart,
+                      (const u32 *) val[0], tracts, (const long long *) total, (const Location *) d_loc, capacity, (UnionTract *) d_out_tracts,
+                      (Location *) d_tract_loc, d_ref_length);
+  if (hipGetLastError () != hipSuccess) return -set_err (TJAMD_ERR_HIP, "%s: launch failed", fn);
+  (void) c->timer[T_LOCATED_TRACTS].end (c->stream);
+  u32 h[2] = {0, 0};
+  if (hipMemcpyAsync (h, tot, 8, hipMemcpyDeviceToHost, c->stream) != hipSuccess || hipStreamSynchronize (c->stream) != hipSuccess)
+    return -set_err (TJAMD_ERR_HIP, "%s: failed: %s", fn, hipGetErrorString (hipGetLastError ()));
+  if (h[1] == 2) return -set_err (TJAMD_ERR_ARG, "%s: a location with flat >= 2^45", fn);
+  if (h[1]) return -set_err (TJAMD_ERR_ARG, "%s: the tracts do not tile the union (first 0, each starting where the one before ends, the last ending at n_union)", fn);
+  if ((long) h[0] > capacity) return -set_err (TJAMD_ERR_CAPACITY, "%s: %u tracts, caller capacity %ld", fn, h[0], capacity);
+  c->timer[T_LOCATED_TRACTS].timed = true;
+  return (long) h[0];
+}
+extern "C" double tjamd_last_located_tracts_ms (tjamd_counter *c) { return c ? c->timer[T_LOCATED_TRACTS].ms (c->device) : -1.0; }

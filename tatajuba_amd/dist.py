@@ -147,3 +147,40 @@ def union_tracts_device(counter, keys_u8, mat, coverage, max_distance_per_flank,
             raise TatajubaAmdError(_err())
         out.update(values=vals[:n].cpu().numpy(), modal_len=ml[:n].cpu().numpy(), n_context=nc[:n].cpu().numpy(), n_len=nl[:n].cpu().numpy())
     return out
+
+
+def located_tracts_device(counter, reference, keys_u8, mat, max_mismatches, tracts=None):
+    """A union located on a reference genome and its tracts merged by location on the GPU (tjamd_locate, then
+    tjamd_located_tracts): keys_u8 / mat as merge_histograms_device returns them, reference = a capi.Reference of the
+    counter's k, tracts = the uint8 CUDA tensor of tjamd_union_tract that union_tracts_device's call fills (or a numpy
+    UNION_TRACT_DTYPE array), None for the context-keyed tracts.  Returns a dict: n_located, loc (LOCATION_DTYPE per union
+    row), perm (int32), tracts (UNION_TRACT_DTYPE), tract_loc (LOCATION_DTYPE per tract), and the CUDA tensors keys, mat
+    (the permuted union), tracts_dev and ref_length (int32 per tract) that tjamd_union_tract_stats takes."""
+    import ctypes as C
+    import numpy as np
+    from .capi import lib, TatajubaAmdError, _err, UNION_TRACT_DTYPE, LOCATION_DTYPE
+    dev = mat.device
+    nu, ns = int(mat.shape[0]), int(mat.shape[1])
+    ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
+    m = max(nu, 1)
+    if isinstance(tracts, np.ndarray):
+        tracts = torch.from_numpy(np.frombuffer(tracts.astype(UNION_TRACT_DTYPE).tobytes(), dtype=np.uint8).copy()).to(dev)
+    nt_in = 0 if tracts is None else tracts.numel() // UNION_TRACT_DTYPE.itemsize
+    loc = torch.empty(m * LOCATION_DTYPE.itemsize, dtype=torch.uint8, device=dev)
+    perm = torch.empty(m, dtype=torch.int32, device=dev)
+    okeys = torch.empty_like(keys_u8)
+    omat = torch.empty_like(mat)
+    otr = torch.empty(m * UNION_TRACT_DTYPE.itemsize, dtype=torch.uint8, device=dev)
+    tloc = torch.empty(m * LOCATION_DTYPE.itemsize, dtype=torch.uint8, device=dev)
+    rlen = torch.empty(m, dtype=torch.int32, device=dev)
+    torch.cuda.current_stream().synchronize()
+    n_located = lib().tjamd_locate(counter._h, reference._h, ptr(keys_u8), nu, int(max_mismatches), ptr(loc))
+    if n_located < 0:
+        raise TatajubaAmdError(_err())
+    nt = lib().tjamd_located_tracts(counter._h, ptr(keys_u8), ptr(mat), nu, ns, ptr(tracts), nt_in, ptr(loc), ptr(perm), ptr(okeys), ptr(omat),
+                                    ptr(otr), ptr(tloc), ptr(rlen), m)
+    if nt < 0:
+        raise TatajubaAmdError(_err())
+    raw = lambda t, dt, n: np.frombuffer(t[: n * dt.itemsize].cpu().numpy().tobytes(), dtype=dt)
+    return {"n_located": int(n_located), "loc": raw(loc, LOCATION_DTYPE, nu), "perm": perm[:nu].cpu().numpy(), "tracts": raw(otr, UNION_TRACT_DTYPE, nt),
+            "tract_loc": raw(tloc, LOCATION_DTYPE, nt), "keys": okeys, "mat": omat, "tracts_dev": otr[: nt * UNION_TRACT_DTYPE.itemsize], "ref_length": rlen[:nt]}
