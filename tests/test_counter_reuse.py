@@ -1,0 +1,191 @@
+"""Scratch carried between calls.  A counter's device scratch only grows, and the entries share it (the flags, positions
+and segment ids of the scans, the histogram and the work area of the key-value sort, the row totals, the error words): a
+kernel that read scratch it had not written in this call -- the tail a larger problem left, an error word a refused call
+left -- would pass every test that takes a fresh counter.  Here one counter goes through a fixed sequence: every entry on
+a large problem (4097 rows by 70 samples), then on a small one of another shape (65 rows by 3 samples), then on the small
+one directly after each kind of refused call on the large one, with a sample scanned, the counter reset and another
+scanned, and a reference built, used, closed and built again smaller.  Every result is bit for bit that of the same call on
+a fresh counter; every output sits in a guarded buffer (tests/bounds_calls.py)."""
+import random
+
+import numpy as np
+import pytest
+
+import tatajuba_amd as tj
+from tatajuba_amd import capi
+from oracle import orc
+from tests import bounds_calls as bc
+from tests.bounds_calls import ERR_ARG, ERR_CAP, Union
+from tests.guarded import GuardedHost, frozen
+from tests.test_locate import queries_for, random_genome
+from tests.test_locate_cabi import restate_reference_index
+from tests.test_union_tracts import random_families
+from tests.test_union_tracts_cabi import oracle_union_grouping
+
+pytestmark = pytest.mark.gpu
+
+K, MAXD, LEV, MM = 10, 1, 2, 2
+
+
+class Problem:
+    """a union, what the entries need beside it (made once, on counters of their own), and a genome with queries"""
+
+    def __init__(self, name, n_rows, ns, n_fam, seed, genome_bytes, n_queries):
+        self.name = name
+        keys, mat = random_families(K, ns, seed, n_fam=n_fam)
+        assert len(keys) >= n_rows
+        rng = random.Random(seed)
+        self.u = Union(keys[:n_rows], mat[:n_rows], rng.choices(range(20, 80), k=ns))
+        self.records, self.counts = self.u.sample_records()
+        g = oracle_union_grouping(self.u.keys, self.u.mat, K, MAXD, LEV)
+        self.tracts_host = bc.tracts_from_grouping(g, self.u.n)
+        self.group_ids = g["tract_id"].astype(np.int32)
+        self.n_ctx = int(orc.tract_ids(self.u.keys)[1])
+        self.nt = len(self.tracts_host)
+        self.tracts = bc.dev(self.tracts_host)
+        self.loc_host = bc.planted_locations(self.u.keys, seed)
+        self.loc = bc.dev(self.loc_host)
+        self.genome = random_genome(rng, genome_bytes, K)
+        entries, _ = restate_reference_index(self.genome, K)
+        self.queries = bc.dev(queries_for(rng, entries, K, n_queries // 4, n_queries))
+        self.n_queries = self.queries.numel() // 24
+        prep = tj.Counter(K)                                                  # the summaries the sample statistics read
+        ts = bc.call_tract_stats(prep, self.u, self.n_ctx)
+        us = bc.call_union_tract_stats(prep, self.u, self.tracts, self.nt)
+        assert ts.rc == self.n_ctx and us.rc == self.nt
+        self.ts_summary, self.us_summary = ts["d_summary"].payload.clone(), us["d_summary"].payload.clone()
+        prep.close()
+
+
+def signature(r, *more):
+    """a call's return value, its counts and every byte of its outputs"""
+    return (r.rc, tuple(more), {name: g.view(np.uint8).tobytes() for name, g in r.outs.items() if g is not None})
+
+
+def run_reference(c, p):
+    ref = tj.Reference(c, p.genome)
+    try:
+        index = ref.download().tobytes()
+        r = bc.call_locate(c, ref, p.queries, p.n_queries, MM)
+        assert r.rc > 0
+        return signature(r, ref.n_entries, ref.n_contigs, index)
+    finally:
+        ref.close()
+
+
+ENTRIES = {
+    "tjamd_merge_samples": lambda c, p: signature(bc.call_merge_samples(c, p.records, p.counts, p.u.ns, p.u.n)),
+    "tjamd_tract_ids": lambda c, p: signature(bc.call_tract_ids(c, p.u)),
+    "tjamd_tract_stats": lambda c, p: (lambda r: signature(r, r.n_var))(bc.call_tract_stats(c, p.u, p.n_ctx)),
+    "tjamd_tract_stats (caller ids)": lambda c, p: (lambda r: signature(r, r.n_var))(bc.call_tract_stats(c, p.u, p.nt, ids=bc.dev(p.group_ids, np.int32))),
+    "tjamd_tract_sample_stats": lambda c, p: signature(bc.call_tract_sample_stats(c, p.u, p.ts_summary, p.n_ctx, bc.arange_dev(p.n_ctx))),
+    "tjamd_union_tracts": lambda c, p: signature(bc.call_union_tracts(c, p.u, MAXD, LEV, p.nt), c.last_union_tract_candidates()),
+    "tjamd_union_tract_stats": lambda c, p: (lambda r: signature(r, r.n_var, r.n_sel))(bc.call_union_tract_stats(c, p.u, p.tracts, p.nt)),
+    "tjamd_union_tract_sample_stats": lambda c, p: signature(bc.call_union_tract_sample_stats(c, p.u, p.us_summary, p.nt, bc.arange_dev(p.nt))),
+    "tjamd_reference_create, tjamd_locate": run_reference,
+    "tjamd_located_tracts": lambda c, p: signature(bc.call_located_tracts(c, p.u, p.tracts, p.nt, p.loc, p.u.n)),
+    "tjamd_located_tracts (no tracts)": lambda c, p: signature(bc.call_located_tracts(c, p.u, None, 0, p.loc, p.u.n)),
+}
+
+
+def refuse_capacity(c, p):
+    bc.call_tract_stats(c, p.u, 1).refused(ERR_CAP, "caller capacity 1")
+    bc.call_union_tracts(c, p.u, MAXD, LEV, 1).refused(ERR_CAP, "caller capacity 1")
+    bc.call_located_tracts(c, p.u, p.tracts, p.nt, p.loc, 1).refused(ERR_CAP, "caller capacity 1")
+    bc.call_merge_samples(c, p.records, p.counts, p.u.ns, 1).refused(ERR_CAP, "caller capacity 1")
+
+
+def refuse_bad_ids(c, p):
+    bad = p.group_ids.copy()
+    bad[p.u.n // 2:] += 2
+    bc.call_tract_stats(c, p.u, p.nt + 2, ids=bc.dev(bad, np.int32)).refused(ERR_ARG, "tract ids must start at 0")
+    listed = bc.dev(np.array([0, p.nt, -1], np.int32), np.int32)
+    bc.call_tract_sample_stats(c, p.u, p.ts_summary, p.n_ctx, bc.dev(np.array([0, p.n_ctx], np.int32), np.int32)).refused(ERR_ARG, "outside [0,")
+    bc.call_union_tract_sample_stats(c, p.u, p.us_summary, p.nt, listed).refused(ERR_ARG, "outside [0,")
+
+
+def refuse_tiling(c, p):
+    bad = p.tracts_host.copy()
+    bad["n_rows"][len(bad) // 2] += 1
+    bc.call_union_tract_stats(c, p.u, bc.dev(bad), len(bad)).refused(ERR_ARG, "must tile the union")
+    bc.call_located_tracts(c, p.u, bc.dev(bad), len(bad), p.loc, p.u.n).refused(ERR_ARG, "do not tile the union")
+
+
+def refuse_flat(c, p):
+    far = p.loc_host.copy()
+    far["flat"][np.flatnonzero(far["flat"] >= 0)[::3]] = 1 << 45
+    bc.call_located_tracts(c, p.u, p.tracts, p.nt, bc.dev(far), p.u.n).refused(ERR_ARG, "flat >= 2^45")
+    bc.call_located_tracts(c, p.u, None, 0, bc.dev(far), p.u.n).refused(ERR_ARG, "flat >= 2^45")
+
+
+REFUSALS = {"capacity": refuse_capacity, "bad ids": refuse_bad_ids, "tracts that do not tile": refuse_tiling, "flat too large": refuse_flat}
+
+
+def sample_state(c, m):
+    """what the host entries give of a scanned counter, before and after its finalise: every byte"""
+    L = tj.lib()
+    out = {"raw": np.sort(c.download_raw(), order=("ctx0", "ctx1", "meta")).tobytes(), "undefined": c.undefined_runs()}
+    out["status"] = c.finalise(1, 5)
+    n, ni = c.n_kept, c.n_idx
+    kept, a, b = GuardedHost(n * 40), GuardedHost(ni * 4), GuardedHost(ni * 4)
+    assert L.tjamd_download_kept(c._h, kept.c, n) == n and L.tjamd_download_idx(c._h, a.c, b.c, ni) == ni
+    gof, groups = GuardedHost(n * 4), GuardedHost(n * tj.GROUP_DTYPE.itemsize)
+    ng = L.tjamd_group_contexts(c._h, 1, gof.c, groups.c, n)
+    h = {name: GuardedHost(n * size) for name, size in (("group_of", 4), ("join_type", 4), ("groups", capi.CONTEXT_GROUP_DTYPE.itemsize), ("hist", 8))}
+    nh = L.tjamd_context_histograms(c._h, 1, 2, *[g.c for g in h.values()], n)
+    assert ng > 0 and nh > 0
+    for g in [kept, a, b, gof, groups] + list(h.values()):
+        g.check()
+    grp = h["groups"].view(capi.CONTEXT_GROUP_DTYPE, nh)
+    hist = h["hist"].view(capi.LENGTH_FREQ_DTYPE)
+    out.update(kept=kept.payload.tobytes(), idx=(a.payload.tobytes(), b.payload.tobytes()), coverage=c.coverage, group_of=gof.payload.tobytes(),
+               groups=groups.view(tj.GROUP_DTYPE, ng).tobytes(), h_group_of=h["group_of"].payload.tobytes(), h_join=h["join_type"].payload.tobytes(),
+               h_groups=grp.tobytes(), h_hist=[hist[int(f): int(f) + int(k)].tobytes() for f, k in zip(grp["first"], grp["n_len"])])
+    return out
+
+
+def test_one_counter_through_a_fixed_sequence():
+    big = Problem("big", 4097, 70, 1000, 11, 60000, 2000)
+    small = Problem("small", 65, 3, 25, 12, 9000, 100)
+    assert (big.u.n, big.u.ns, small.u.n, small.u.ns) == (4097, 70, 65, 3) and big.nt != small.nt and big.n_ctx != small.n_ctx
+    streams = {"big": tj.synth_stream(60000, 150, 300000, variant_seed=1), "small": tj.synth_stream(3000, 100, 20000, seed_reads=99, variant_seed=2)}
+    m = 3
+    fresh = {}
+    for p in (big, small):                                                    # every entry on a counter of its own
+        for name, entry in ENTRIES.items():
+            f = tj.Counter(K)
+            fresh[name, p.name] = entry(f, p)
+            f.close()
+    for name, s in streams.items():
+        f = tj.Counter(K)
+        f.scan_host(s, m)
+        fresh["sample", name] = sample_state(f, m)
+        f.close()
+    assert fresh["sample", "big"]["status"] == 0 == fresh["sample", "small"]["status"] and fresh["sample", "big"]["kept"] != fresh["sample", "small"]["kept"]
+
+    c = tj.Counter(K)
+    c.scan_host(streams["big"], m)                                            # a sample of its own: the cross-sample entries leave it as it is
+    assert sample_state(c, m) == fresh["sample", "big"]
+    kept_before = c.download_kept().tobytes()
+    for p in (big, small):                                                    # every entry on the large problem, then on the small one
+        for name, entry in ENTRIES.items():
+            assert entry(c, p) == fresh[name, p.name], (name, p.name)
+    for kind, refuse in REFUSALS.items():                                     # every entry directly after each kind of refused call
+        for name, entry in ENTRIES.items():
+            refuse(c, big)
+            assert entry(c, small) == fresh[name, "small"], (name, "after a refusal:", kind)
+    assert c.download_kept().tobytes() == kept_before and c.n_kept * 40 == len(kept_before)
+    for name, entry in ENTRIES.items():                                       # and the large problem once more, after all that
+        assert entry(c, big) == fresh[name, "big"], (name, "big again")
+    c.reset()                                                                 # forget the sample, keep the buffers; scan a smaller one
+    assert c.raw_count() == 0
+    c.scan_host(streams["small"], m)
+    assert sample_state(c, m) == fresh["sample", "small"]
+    for name, entry in ENTRIES.items():
+        assert entry(c, small) == fresh[name, "small"], (name, "after the reset")
+    c.reset()
+    stream = bc.dev(streams["big"])                                           # from device memory this time: the stream is a const input
+    with frozen(stream):
+        c.scan_device(stream.data_ptr(), stream.numel(), m)
+        assert sample_state(c, m) == fresh["sample", "big"]
+    c.close()

@@ -15,6 +15,8 @@ pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 ERR_ARG, ERR_CAP = 3, 4
+# caller ids of five rows that tjamd_tract_stats refuses (they must start at 0 and go up by 0 or 1); tests/test_buffer_bounds.py sends them too
+BAD_TRACT_IDS = ([1, 1, 1, 2, 2], [0, 2, 2, 2, 2], [0, 1, 0, 1, 1], [0, 0, -1, -1, 0], [0, 1, 2, 3, 5], [-1, 0, 0, 1, 1], [-1, -1, 0, 0, 1], [-1] * 5)
 
 
 def _torch():
@@ -128,8 +130,7 @@ def test_caller_ids_and_bad_ids(counter):
     assert nt == 4 and check_against_restatement(g1, restate_tract_stats(keys, mat, cov)) == 0
     assert (g1["n_context"] <= 1).all()
     assert counter.last_tract_stats_ms() > 0
-    for bad in ([1, 1, 1, 2, 2], [0, 2, 2, 2, 2], [0, 1, 0, 1, 1], [0, 0, -1, -1, 0], [0, 1, 2, 3, 5],
-                [-1, 0, 0, 1, 1], [-1, -1, 0, 0, 1], [-1] * 5):
+    for bad in BAD_TRACT_IDS:
         rc, err = device_stats(counter, keys, mat, cov, tract_ids=bad)
         assert rc == -ERR_ARG and "tract ids must start at 0 and go up by 0 or 1" in err, (bad, rc, err)
         assert counter.last_tract_stats_ms() == -1.0                     # a failed call leaves no timing behind

@@ -21,6 +21,8 @@ pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 ERR_ARG, ERR_CAP = 3, 4
+# (first, n_rows) of tracts that do not tile a union of five rows; tests/test_locate.py and tests/test_buffer_bounds.py send them too
+BAD_SPANS = ([(0, 3), (4, 1)], [(1, 3), (4, 1)], [(0, 4), (4, 2)], [(0, 4), (3, 2)], [(0, 5), (5, 0)], [(-1, 5), (4, 1)], [(0, 2), (2, 2)])
 TR, SU = tj.UNION_TRACT_DTYPE, tj.UNION_TRACT_SUMMARY_DTYPE
 
 
@@ -116,9 +118,9 @@ def union_of_samples(recs):
     return keys, mat
 
 
-def random_families(k, ns, seed, n_fam=600):
+def family_rows(k, ns, seed, n_fam=600):
     """families of near-identical contexts (right-flank substitutions and one-base indels, first bases of the left flank),
-    a few lengths each, counts per sample; in the merge's order"""
+    a few lengths each, counts per sample: {(base, ctx0, ctx1, length): [count per sample]}"""
     rng = random.Random(seed)
     mask = (1 << (2 * k)) - 1
     rows = {}
@@ -143,7 +145,12 @@ def random_families(k, ns, seed, n_fam=600):
     for key in list(rows):
         if not any(rows[key]):
             rows[key][0] = 1
-    return union_of_samples(sample_records(rows, ns))
+    return rows
+
+
+def random_families(k, ns, seed, n_fam=600):
+    """the union of family_rows, in the merge's order"""
+    return union_of_samples(sample_records(family_rows(k, ns, seed, n_fam), ns))
 
 
 @pytest.fixture(scope="module")
@@ -183,7 +190,7 @@ def test_hand_built_union(counter):
         return rc, L.tjamd_last_error().decode()
 
     assert stats_of([(0, 4), (4, 1)])[0] == 2
-    for bad in ([(0, 3), (4, 1)], [(1, 3), (4, 1)], [(0, 4), (4, 2)], [(0, 4), (3, 2)], [(0, 5), (5, 0)], [(-1, 5), (4, 1)], [(0, 2), (2, 2)]):
+    for bad in BAD_SPANS:
         rc, err = stats_of(bad)
         assert rc == -ERR_ARG and err.startswith("tjamd_union_tract_stats") and "must tile the union" in err, (bad, rc, err)
         assert counter.last_union_tract_stats_ms() == -1.0
