@@ -375,6 +375,10 @@ long tjamd_located_tracts (tjamd_counter *c, const void *d_keys, const void *d_c
                            int *d_perm, void *d_out_keys, void *d_out_counts,
                            tjamd_union_tract *d_out_tracts, tjamd_location *d_tract_loc, int *d_ref_length, long capacity);
 
+/* Per-sample tract variants against the reference as the fields of VCF records (N8: tjamd_tract_variants), and the contig
+ * names of a FASTA file (tjamd_read_file_names), are declared in tatajuba_variants.h, which includes this header; their
+ * timer is tjamd_last_tract_variants_ms below. */
+
 /* release the calling thread's shared device contexts of the synchronous string scans (update_hopo_counter_from_seq on a
  * counter that never read a file, tjamd_scan_windows) now; they are released by themselves when the thread ends */
 void tjamd_thread_cleanup (void);
@@ -392,6 +396,7 @@ long   tjamd_last_union_tract_candidates (tjamd_counter *c); /* rows of the last
 double tjamd_last_reference_ms (tjamd_counter *c);         /* kernels of the last tjamd_reference_create on this counter (the copy to the device not included) */
 double tjamd_last_locate_ms (tjamd_counter *c);            /* the lookup kernel of the last tjamd_locate */
 double tjamd_last_located_tracts_ms (tjamd_counter *c);    /* the last tjamd_located_tracts, first launch to last (host waits included) */
+double tjamd_last_tract_variants_ms (tjamd_counter *c);    /* the last tjamd_tract_variants, first launch to last */
 long   tjamd_last_scan_launches (tjamd_counter *c);
 /* finalises of this counter whose device-side sizing of the ordering step had read a stale kept count (checked against the
  * count at the next kernel boundary and repaired; expected to stay 0) */

@@ -1,4 +1,4 @@
-"""ctypes mirror of the C boundary (include/tatajuba_hopo.h and include/tatajuba_amd.h).
+"""ctypes mirror of the C boundary (include/tatajuba_hopo.h, include/tatajuba_amd.h and include/tatajuba_variants.h).
 
 Two views of the same library:
   * HopoCounter / Options -- the drop-in API with the reference's names (new_or_append_hopo_counter_from_file,
@@ -42,6 +42,10 @@ assert REF_ENTRY_DTYPE.itemsize == 48
 LOCATION_DTYPE = np.dtype([("flat", "<i8"), ("contig", "<i4"), ("pos", "<i4"), ("ref_length", "<i4"), ("mismatches", "<i4"),
                            ("neg_strand", "<i4"), ("n_hits", "<i4")])
 assert LOCATION_DTYPE.itemsize == 32
+# tjamd_variant (include/tatajuba_variants.h): one tract-length variant of one sample, the fields of a VCF record
+VARIANT_DTYPE = np.dtype([("flat", "<i8"), ("tract", "<i4"), ("sample", "<i4"), ("contig", "<i4"), ("pos", "<i4"), ("row", "<i4"), ("base", "<i4"),
+                          ("ref_length", "<i4"), ("alt_length", "<i4"), ("n_flank", "<i4"), ("pad", "<i4"), ("ref_flank", "<u8"), ("alt_flank", "<u8")])
+assert VARIANT_DTYPE.itemsize == 64
 
 
 class TatajubaAmdError(RuntimeError):
@@ -112,12 +116,16 @@ EXPORTS = [
     "tjamd_comm_set_stream", "tjamd_comm_rank", "tjamd_comm_world", "tjamd_comm_collectives", "tjamd_comm_count", "tjamd_comm_last_exchange", "tjamd_last_merge_ms", "tjamd_allgather_histograms", "tjamd_tract_ids", "tjamd_tract_stats", "tjamd_tract_sample_stats", "tjamd_last_tract_stats_ms", "tjamd_union_tracts", "tjamd_union_tract_stats", "tjamd_union_tract_sample_stats", "tjamd_last_union_tracts_ms", "tjamd_last_union_tract_stats_ms", "tjamd_last_union_tract_candidates",
     "tjamd_reference_create", "tjamd_reference_destroy", "tjamd_reference_entries", "tjamd_reference_contigs",
     "tjamd_reference_download", "tjamd_last_reference_ms", "tjamd_locate", "tjamd_last_locate_ms", "tjamd_located_tracts", "tjamd_last_located_tracts_ms",
+    "tjamd_last_tract_variants_ms",
     "tjamd_group_contexts", "tjamd_context_histograms", "tjamd_scan_windows", "tjamd_thread_cleanup", "tjamd_last_scan_ms", "tjamd_last_partition_ms", "tjamd_counter_uses_log", "tjamd_last_finalise_ms", "tjamd_last_scan_launches", "tjamd_plan_mismatches",
     "tjamd_synth_stream", "tjamd_read_file_stream",
     # include/tatajuba_context.h
     "new_genomic_context_list", "del_genomic_context_list", "del_context_histogram",
     "distance_between_context_histogram_and_hopo_context", "indel_distance_between_context_histogram_and_hopo_context",
 ]
+
+# what include/tatajuba_variants.h declares on top of them
+VARIANT_EXPORTS = ["tjamd_tract_variants", "tjamd_read_file_names"]
 
 
 def _share_hip_runtime_with_torch():
@@ -235,6 +243,12 @@ def lib():
     L.tjamd_last_reference_ms.restype = C.c_double; L.tjamd_last_reference_ms.argtypes = [C.c_void_p]
     L.tjamd_last_locate_ms.restype = C.c_double; L.tjamd_last_locate_ms.argtypes = [C.c_void_p]
     L.tjamd_last_located_tracts_ms.restype = C.c_double; L.tjamd_last_located_tracts_ms.argtypes = [C.c_void_p]
+    L.tjamd_tract_variants.restype = C.c_long
+    L.tjamd_tract_variants.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_long, C.c_int, C.c_void_p, C.c_long, C.c_void_p,
+                                       C.c_void_p, C.c_long, C.c_void_p, C.c_long, C.c_void_p]
+    L.tjamd_last_tract_variants_ms.restype = C.c_double; L.tjamd_last_tract_variants_ms.argtypes = [C.c_void_p]
+    L.tjamd_read_file_names.restype = C.c_long
+    L.tjamd_read_file_names.argtypes = [C.c_char_p, C.c_void_p, C.c_long, C.POINTER(C.c_long)]
     L.tjamd_group_contexts.restype = C.c_long
     L.tjamd_group_contexts.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_long]
     L.new_genomic_context_list.restype = C.POINTER(GenomicContextListStruct); L.new_genomic_context_list.argtypes = [P]
@@ -626,6 +640,9 @@ class Counter:
 
     def last_located_tracts_ms(self):
         return lib().tjamd_last_located_tracts_ms(self._h)
+
+    def last_tract_variants_ms(self):
+        return lib().tjamd_last_tract_variants_ms(self._h)
 
     def uses_log(self):
         lib().tjamd_counter_uses_log.restype = C.c_int

@@ -20,7 +20,8 @@ struct tjr_reader
   size_t marker_pos;    /* offset in blk of the marker of the next record (marker_seen) / of the record returned last */
   size_t rec_start;
   int rec_open;         /* the last tjr_next() found a record marker (rec_start is that record's) */
-  tjr_text seq, qual;
+  int keep_names;       /* tjr_keep_names(): copy the header line so that tjr_record_name() can hand out the name */
+  tjr_text seq, qual, name;
 };
 
 static int
@@ -102,6 +103,16 @@ tjr_open_mem (const unsigned char *data, size_t n_bytes, size_t start)
 }
 
 size_t tjr_record_start (const tjr_reader *r) { return r->rec_start; }
+void tjr_keep_names (tjr_reader *r, int on) { r->keep_names = on; }
+
+const char *
+tjr_record_name (const tjr_reader *r, size_t *len)
+{ /* the header line of the record returned last, up to its first space or tab */
+  size_t n = 0;
+  while (n < r->name.len && r->name.s[n] != ' ' && r->name.s[n] != '\t') n++;
+  *len = n;
+  return r->name.s ? r->name.s : "";
+}
 int tjr_record_open (const tjr_reader *r) { return r->rec_open; }
 int tjr_at_end (const tjr_reader *r) { return r->drained && r->pos >= r->end; }
 
@@ -110,7 +121,7 @@ tjr_close (tjr_reader *r)
 {
   if (!r) return;
   if (!r->in_memory) { gzclose (r->f); free (r->blk); }
-  free (r->seq.s); free (r->qual.s); free (r);
+  free (r->seq.s); free (r->qual.s); free (r->name.s); free (r);
 }
 
 long
@@ -127,8 +138,8 @@ tjr_next (tjr_reader *r, const char **seq)
   r->rec_start = r->marker_pos;
   r->rec_open = 1;
   r->marker_seen = 0;
-  r->seq.len = r->qual.len = 0;
-  if (tjr_line (r, NULL) < 0) return -1;       /* header line: name and comment are not needed */
+  r->seq.len = r->qual.len = r->name.len = 0;
+  if (tjr_line (r, r->keep_names ? &r->name : NULL) < 0) return -1;   /* header line: copied only for tjr_record_name() */
   if (r->in_memory) {
     /* The usual FASTQ record -- one sequence line, a '+' line, one quality line, all of it inside the block -- without
      * copying a byte: the sequence is handed out where it lies (the block is the caller's and outlives the call) and the

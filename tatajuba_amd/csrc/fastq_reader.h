@@ -12,6 +12,11 @@ tjr_reader *tjr_open (const char *path);                 /* NULL if the file can
  * stops reading the file there, as the reference's `>= 0` loop does). */
 long tjr_next (tjr_reader *r, const char **seq);
 void tjr_close (tjr_reader *r);
+/* tjr_keep_names (r, 1), before the first tjr_next(): the reader keeps each header line, and tjr_record_name() gives the
+ * name of the record tjr_next() returned last -- the header after its '>' / '@' up to the first space or tab, *len bytes,
+ * not terminated, valid until the next call.  Off by default: the scan path does not pay for the copy. */
+void tjr_keep_names (tjr_reader *r, int on);
+const char *tjr_record_name (const tjr_reader *r, size_t *len);
 
 /* The same reader over bytes already in memory (a plain, uncompressed file that was mapped): no copies, positions are
  * offsets into the block.  tjr_record_start() = offset of the '>' / '@' that opened the record tjr_next() returned last;

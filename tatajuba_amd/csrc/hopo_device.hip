@@ -35,6 +35,7 @@
 #include <vector>
 
 #include "../../include/tatajuba_amd.h"
+#include "../../include/tatajuba_variants.h"
 
 typedef unsigned long long u64;
 typedef unsigned int u32;
@@ -4113,7 +4114,7 @@ struct StageTimer
 };
 // the intervals of a counter: the last scan call (its partition kernels between the pieces included: tjamd_last_scan_ms takes
 // them out), finalise, the kernels of tjamd_merge_samples, tjamd_tract_stats, tjamd_union_tracts, tjamd_union_tract_stats
-enum { T_SCAN, T_FIN, T_MERGE, T_TRACT, T_UNION, T_UNION_STATS, T_REF, T_LOCATE, T_LOCATED_TRACTS, TJ_N_TIMERS };   // (the last three: N7, end of the file)
+enum { T_SCAN, T_FIN, T_MERGE, T_TRACT, T_UNION, T_UNION_STATS, T_REF, T_LOCATE, T_LOCATED_TRACTS, T_VARIANTS, TJ_N_TIMERS };   // (T_REF to T_LOCATED_TRACTS: N7, T_VARIANTS: N8, end of the file)
 
 struct tjamd_counter
 {
@@ -7282,3 +7283,176 @@ extern "C" long tjamd_located_tracts (tjamd_counter *c, const void *d_keys, cons
   return (long) h[0];
 }
 extern "C" double tjamd_last_located_tracts_ms (tjamd_counter *c) { return c ? c->timer[T_LOCATED_TRACTS].ms (c->device) : -1.0; }
+
+// ---- N8: per-sample tract variants against the reference ---------------------------------------------------------------
+// The VCF step of the reference (update_vcf_file_from_context_histogram, find_ref_alt_ht_variants_from_strings,
+// get_next_ht_location_from_same_contig, src/analyse_variable_tracts.c:147-233) on the permuted union of
+// tjamd_located_tracts; the rule is in include/tatajuba_variants.h above tjamd_tract_variants.  The index entry at a tract's
+// location holds the genome's flanks in the packing of the union rows, so the reference's comparison of two strings is an
+// XOR of two flank words and a leading-zero count.  Segment mapping of union_tract_stats_kernel: S lanes per listed tract, a
+// lane per sample (looping beyond 64); what the samples of a tract share -- its rows, its index entry (a binary search on
+// flat) and the bases the next tract leaves of the right flank -- is found by the segment's first lane and broadcast.
+// Two passes of one kernel around an exclusive scan in sample-major order: flags, then records at their scanned places, so
+// a record's place never depends on the order of atomics.  DESIGN.md section 3.5, N8.
+
+struct Variant { long long flat; int tract, sample, contig, pos, row, base, ref_length, alt_length, n_flank, pad; u64 ref_flank, alt_flank; };
+static_assert (sizeof (Variant) == 64 && sizeof (Variant) == sizeof (tjamd_variant), "variant layout");
+
+// the entry at flat (ascending flat, one run per position), -1 if there is none
+__device__ __forceinline__ long ref_entry_at (const RefEntry *__restrict__ entries, long n_ent, long long flat)
+{
+  long lo = 0, hi = n_ent;
+  while (lo < hi) {
+    const long mid = (lo + hi) >> 1;
+    if (entries[mid].flat < flat) lo = mid + 1; else hi = mid;
+  }
+  return (lo < n_ent && entries[lo].flat == flat) ? lo : -1l;
+}
+
+// !WRITE: flag[s * n_list + i] = 1 where sample s has a call in list entry i (every word is written), and the checks:
+// err |= 1 where the tracts do not tile the union, err |= 2 for a list id outside [0, n_tracts) (nothing is read outside the
+// arrays either way).  WRITE: the records, at excl[s * n_list + i], those below capacity.
+template <bool WRITE>
+__global__ __launch_bounds__ (256)
+void tract_variants_kernel (const u64 *__restrict__ keys, const int *__restrict__ counts, long n_union, int ns, int S, int k,
+                            const UnionTract *__restrict__ tracts, long n_tracts, const Location *__restrict__ tloc,
+                            const RefEntry *__restrict__ entries, long n_ent, const int *__restrict__ list, long n_list,
+                            u32 *__restrict__ flag, const u32 *__restrict__ excl, Variant *__restrict__ out, long capacity, int *__restrict__ err)
+{
+  const long gthread = blockIdx.x * (long) blockDim.x + threadIdx.x, n_threads = (long) gridDim.x * blockDim.x;
+  if (!WRITE)
+    for (long t = gthread; t < n_tracts; t += n_threads) {
+      const long first = tracts[t].first, rows = tracts[t].n_rows;
+      const long want = t ? (long) tracts[t - 1].first + tracts[t - 1].n_rows : 0l;
+      if (first != want || rows < 1 || first + rows > n_union || (t == n_tracts - 1 && first + rows != n_union)) atomicOr (err, 1);
+    }
+  const int lane = threadIdx.x & (S - 1);
+  const long segs_per_grid = n_threads / S;
+  for (long i = gthread / S; i < n_list; i += segs_per_grid) {   // (uniform across a segment)
+    const long t = list ? (long) list[i] : i;
+    long first = 0, end = 0, ent = -1;
+    int k_eff = 0;
+    if (lane == 0) {
+      if (t < 0 || t >= n_tracts) { if (!WRITE) atomicOr (err, 2); }
+      else {
+        const UnionTract u = tracts[t];
+        const Location l = tloc[t];
+        first = u.first; end = first + (long) u.n_rows;
+        if (first < 0 || u.n_rows < 1 || end > n_union) first = end = 0;   // (a broken tiling: flagged above)
+        else if (l.flat >= 0 && (ent = ref_entry_at (entries, n_ent, l.flat)) >= 0) {
+          k_eff = k;
+          if (t + 1 < n_tracts) {                       // stop at the next tract of the contig, list or no list
+            const Location nx = tloc[t + 1];
+            const long overlap = (long) l.pos + (long) entries[ent].length + (long) k - (long) nx.pos;
+            if (nx.flat >= 0 && nx.contig == l.contig && overlap > 0) k_eff = (int) max (0l, (long) k - overlap);
+          }
+        }
+      }
+    }
+    first = __shfl (first, 0, S); end = __shfl (end, 0, S); ent = __shfl (ent, 0, S); k_eff = __shfl (k_eff, 0, S);
+    for (int s = lane; s < ns; s += S) {
+      bool call = false;
+      Variant v;
+      if (ent >= 0) {
+        int best = 0;
+        long row = -1;
+        for (long r = first; r < end; r++) {            // the modal row: the highest count, the first on a tie
+          const int x = counts[r * ns + s];
+          if (x > best) { best = x; row = r; }
+        }
+        if (row >= 0) {
+          const RefEntry e = entries[ent];
+          const int La = meta_len (keys[3 * row + 2]), Lr = e.length;
+          call = La >= 1 && La != Lr;
+          if (WRITE && call) {
+            const Location l = tloc[t];
+            const u64 fr = e.neg_strand ? revcomp_k (e.ctx0, k) : e.ctx1;
+            const u64 fa = e.neg_strand ? revcomp_k (keys[3 * row], k) : keys[3 * row + 1];
+            const u64 x = (fr ^ fa) & kmask (k_eff);    // (kmask: all ones at 32 bases, nothing at 0 -- no shift by 64)
+            const int nf = x ? (63 - __clzll ((long long) x)) / 2 + 1 : 0;   // the outermost difference and everything inside it
+            v.flat = l.flat; v.tract = (int) t; v.sample = s; v.contig = l.contig; v.pos = l.pos + min (La, Lr);
+            v.row = (int) row; v.base = e.neg_strand ? 3 - e.base : e.base; v.ref_length = Lr; v.alt_length = La;
+            v.n_flank = nf; v.pad = 0; v.ref_flank = fr & kmask (nf); v.alt_flank = fa & kmask (nf);
+          }
+        }
+      }
+      const long at = (long) s * n_list + i;
+      if (!WRITE) flag[at] = call ? 1u : 0u;
+      else if (call && (long) excl[at] < capacity) out[excl[at]] = v;
+    }
+  }
+}
+
+// where each sample's records start: the scanned flags at the head of its stretch
+__global__ void variant_offsets_kernel (const u32 *__restrict__ excl, long n_list, int ns, u32 *__restrict__ offs)
+{
+  for (long s = blockIdx.x * (long) blockDim.x + threadIdx.x; s < ns; s += (long) gridDim.x * blockDim.x) offs[s] = excl[s * n_list];
+}
+
+extern "C" long tjamd_tract_variants (tjamd_counter *c, const tjamd_reference *ref, const void *d_keys, const void *d_counts, long n_union,
+                                      int n_samples, const tjamd_union_tract *d_tracts, long n_tracts, const tjamd_location *d_tract_loc,
+                                      const int *d_list, long n_list, tjamd_variant *d_out, long capacity, long *h_offsets)
+{
+  static const char *fn = "tjamd_tract_variants";
+  int rc = union_args (fn, d_keys, d_counts, n_union, n_samples);
+  if (rc) return -rc;
+  if (n_tracts < (n_union > 0 ? 1 : 0) || n_tracts > n_union) return -set_err (TJAMD_ERR_ARG, "%s: n_tracts %ld for a union of %ld rows", fn, n_tracts, n_union);
+  if (n_tracts > 0 && (!d_tracts || !d_tract_loc)) return -set_err (TJAMD_ERR_ARG, "%s: null tract or tract location buffer", fn);
+  if (!d_list) n_list = n_tracts;                       // every tract
+  if (n_list < 0) return -set_err (TJAMD_ERR_ARG, "%s: n_list %ld < 0", fn, n_list);
+  if (capacity < 0 || (capacity > 0 && !d_out)) return -set_err (TJAMD_ERR_ARG, "%s: capacity %ld with %s record buffer", fn, capacity, d_out ? "a" : "a null");
+  if (!h_offsets) return -set_err (TJAMD_ERR_ARG, "%s: null offsets", fn);
+  if (!c || !ref) return -set_err (TJAMD_ERR_ARG, "%s: null counter or reference", fn);
+  const long n_flags = n_list * (long) n_samples;
+  if (n_flags >= (1l << 31)) return -set_err (TJAMD_ERR_CAPACITY, "%s: %ld listed tracts x %d samples", fn, n_list, n_samples);
+  if (tjamd_device_count () <= 0) return -set_err (TJAMD_ERR_NO_DEVICE, "%s: TJAMD_ERR_NO_DEVICE: no HIP device visible (the variants are called on the device; no CPU fallback)", fn);
+  if (ref->k != c->k) return -set_err (TJAMD_ERR_ARG, "%s: the reference was built with k = %d, the counter has k = %d", fn, ref->k, c->k);
+  if (ref->device != c->device) return -set_err (TJAMD_ERR_ARG, "%s: the reference lives on device %d, the counter on device %d", fn, ref->device, c->device);
+  if (hipSetDevice (c->device) != hipSuccess) return -set_err (TJAMD_ERR_HIP, "hipSetDevice failed");
+  c->timer[T_VARIANTS].timed = false;
+  if (n_flags == 0) {
+    for (int s = 0; s <= n_samples; s++) h_offsets[s] = 0;
+    return 0;
+  }
+  LcCut cut (nullptr);
+  u32 *flag = nullptr, *excl = nullptr, *offs = nullptr;
+  for (int pass = 0; pass < 2; pass++) {
+    cut = LcCut (pass ? c->lc_work.p : nullptr);
+    flag = cut.take<u32> (n_flags); excl = cut.take<u32> (n_flags); offs = cut.take<u32> ((size_t) n_samples + 2);
+    if (!pass) {
+      rc = ensure (c->lc_work, cut.used, c->stream);
+      if (!rc) rc = ensure (c->scan_tmp, scan_tmp_words (n_flags) * 4 + 64, c->stream);
+      if (rc) return -rc;
+    }
+  }
+  u32 *total = offs + n_samples;                        // offs: the samples' starts, the number of records, the error flag
+  int *err = (int *) (offs + n_samples + 1);
+  if (hipMemsetAsync (total, 0, 8, c->stream) != hipSuccess) return -set_err (TJAMD_ERR_HIP, "%s: memset failed", fn);
+  (void) c->timer[T_VARIANTS].begin (c->stream);
+  const int S = tract_segment (n_samples);
+  auto launch = [&] (auto kernel) {
+    hipLaunchKernelGGL (kernel, dim3 (tract_grid (n_list, S)), dim3 (256), 0, c->stream, (const u64 *) d_keys, (const int *) d_counts, n_union, n_samples, S, c->k,
+                        (const UnionTract *) d_tracts, n_tracts, (const Location *) d_tract_loc, (const RefEntry *) ref->entries, ref->n_entries, d_list, n_list,
+                        flag, (const u32 *) excl, (Variant *) d_out, capacity, err);
+  };
+  launch (tract_variants_kernel<false>);
+  if (hipGetLastError () != hipSuccess) return -set_err (TJAMD_ERR_HIP, "%s: launch failed", fn);
+  rc = exclusive_scan (c, flag, excl, n_flags, total, (u32 *) c->scan_tmp.p, c->scan_tmp.cap / 4);
+  if (rc) return -rc;
+  hipLaunchKernelGGL (variant_offsets_kernel, dim3 (grid_for (n_samples)), dim3 (256), 0, c->stream, (const u32 *) excl, n_list, n_samples, offs);
+  launch (tract_variants_kernel<true>);                 // (guarded by capacity: the count is only read for the check below)
+  if (hipGetLastError () != hipSuccess) return -set_err (TJAMD_ERR_HIP, "%s: launch failed", fn);
+  (void) c->timer[T_VARIANTS].end (c->stream);
+  std::vector<u32> h ((size_t) n_samples + 2, 0u);
+  if (hipMemcpyAsync (h.data (), offs, h.size () * 4, hipMemcpyDeviceToHost, c->stream) != hipSuccess || hipStreamSynchronize (c->stream) != hipSuccess)
+    return -set_err (TJAMD_ERR_HIP, "%s: failed: %s", fn, hipGetErrorString (hipGetLastError ()));
+  const u32 h_err = h[(size_t) n_samples + 1];
+  const long n_rec = (long) h[(size_t) n_samples];
+  if (h_err & 1u) return -set_err (TJAMD_ERR_ARG, "%s: the tracts do not tile the union (first 0, each starting where the one before ends, the last ending at n_union)", fn);
+  if (h_err & 2u) return -set_err (TJAMD_ERR_ARG, "%s: a listed tract id is outside [0, %ld)", fn, n_tracts);
+  if (n_rec > capacity) return -set_err (TJAMD_ERR_CAPACITY, "%s: %ld records, caller capacity %ld", fn, n_rec, capacity);
+  for (int s = 0; s <= n_samples; s++) h_offsets[s] = (long) h[(size_t) s];
+  c->timer[T_VARIANTS].timed = true;
+  return n_rec;
+}
+extern "C" double tjamd_last_tract_variants_ms (tjamd_counter *c) { return c ? c->timer[T_VARIANTS].ms (c->device) : -1.0; }

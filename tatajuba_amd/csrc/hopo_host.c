@@ -7,6 +7,7 @@
  * needs results prints an error and exits, like the reference's biomcmc_error().
  */
 #include "../../include/tatajuba_amd.h"
+#include "../../include/tatajuba_variants.h"
 #include <pthread.h>
 #include <sched.h>
 #include <sys/stat.h>
@@ -341,6 +342,26 @@ tjamd_read_file_stream (const char *path, unsigned char *out, long capacity, lon
   }
   tjr_close (rd);
   if (n_reads) *n_reads = n;
+  return total;
+}
+
+/* the names of the records tjamd_read_file_stream parses, each followed by '\n' (contig names of a reference FASTA) */
+long
+tjamd_read_file_names (const char *path, char *out, long capacity, long *n_records)
+{
+  tjr_reader *rd = tjr_open (path);
+  long total = 0, n = 0;
+  const char *seq;
+  if (!rd) return -1;
+  tjr_keep_names (rd, 1);
+  while (tjr_next (rd, &seq) >= 0) {
+    size_t len;
+    const char *name = tjr_record_name (rd, &len);
+    if (out && total + (long) len + 1 <= capacity) { memcpy (out + total, name, len); out[total + (long) len] = '\n'; }
+    total += (long) len + 1; n++;
+  }
+  tjr_close (rd);
+  if (n_records) *n_records = n;
   return total;
 }
 
