@@ -1,4 +1,5 @@
-"""ctypes mirror of the C boundary (include/tatajuba_hopo.h, include/tatajuba_amd.h and include/tatajuba_variants.h).
+"""ctypes mirror of the C boundary (include/tatajuba_hopo.h, include/tatajuba_amd.h, include/tatajuba_variants.h and
+include/tatajuba_features.h).
 
 Two views of the same library:
   * HopoCounter / Options -- the drop-in API with the reference's names (new_or_append_hopo_counter_from_file,
@@ -46,6 +47,11 @@ assert LOCATION_DTYPE.itemsize == 32
 VARIANT_DTYPE = np.dtype([("flat", "<i8"), ("tract", "<i4"), ("sample", "<i4"), ("contig", "<i4"), ("pos", "<i4"), ("row", "<i4"), ("base", "<i4"),
                           ("ref_length", "<i4"), ("alt_length", "<i4"), ("n_flank", "<i4"), ("pad", "<i4"), ("ref_flank", "<u8"), ("alt_flank", "<u8")])
 assert VARIANT_DTYPE.itemsize == 64
+# tjamd_feature and tjamd_tract_feature (include/tatajuba_features.h): one feature line of a GFF3 file; a tract's feature and longest modal length
+FEATURE_DTYPE = np.dtype([("contig", "<i4"), ("start", "<i4"), ("end", "<i4"), ("cls", "<i4"), ("strand", "<i4"), ("line", "<i4"), ("type_off", "<i4"), ("id_off", "<i4")])
+assert FEATURE_DTYPE.itemsize == 32
+TRACT_FEATURE_DTYPE = np.dtype([("feature", "<i4"), ("max_length", "<i4")])
+assert TRACT_FEATURE_DTYPE.itemsize == 8
 
 
 class TatajubaAmdError(RuntimeError):
@@ -126,6 +132,9 @@ EXPORTS = [
 
 # what include/tatajuba_variants.h declares on top of them
 VARIANT_EXPORTS = ["tjamd_tract_variants", "tjamd_read_file_names"]
+# ... and include/tatajuba_features.h
+FEATURE_EXPORTS = ["tjamd_gff3_read", "tjamd_annotation_create", "tjamd_annotation_destroy", "tjamd_annotation_features", "tjamd_annotation_download",
+                   "tjamd_tract_features", "tjamd_last_annotation_ms", "tjamd_last_tract_features_ms"]
 
 
 def _share_hip_runtime_with_torch():
@@ -249,6 +258,16 @@ def lib():
     L.tjamd_last_tract_variants_ms.restype = C.c_double; L.tjamd_last_tract_variants_ms.argtypes = [C.c_void_p]
     L.tjamd_read_file_names.restype = C.c_long
     L.tjamd_read_file_names.argtypes = [C.c_char_p, C.c_void_p, C.c_long, C.POINTER(C.c_long)]
+    L.tjamd_gff3_read.restype = C.c_long
+    L.tjamd_gff3_read.argtypes = [C.c_char_p, C.c_char_p, C.c_long, C.c_void_p, C.c_long, C.c_void_p, C.c_long, C.POINTER(C.c_long), C.POINTER(C.c_long)]
+    L.tjamd_annotation_create.restype = C.c_void_p; L.tjamd_annotation_create.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_long]
+    L.tjamd_annotation_destroy.restype = None; L.tjamd_annotation_destroy.argtypes = [C.c_void_p]
+    L.tjamd_annotation_features.restype = C.c_long; L.tjamd_annotation_features.argtypes = [C.c_void_p]
+    L.tjamd_annotation_download.restype = C.c_long; L.tjamd_annotation_download.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_long]
+    L.tjamd_tract_features.restype = C.c_long
+    L.tjamd_tract_features.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_long, C.c_int, C.c_void_p, C.c_long, C.c_void_p, C.c_void_p]
+    L.tjamd_last_annotation_ms.restype = C.c_double; L.tjamd_last_annotation_ms.argtypes = [C.c_void_p]
+    L.tjamd_last_tract_features_ms.restype = C.c_double; L.tjamd_last_tract_features_ms.argtypes = [C.c_void_p]
     L.tjamd_group_contexts.restype = C.c_long
     L.tjamd_group_contexts.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_long]
     L.new_genomic_context_list.restype = C.POINTER(GenomicContextListStruct); L.new_genomic_context_list.argtypes = [P]
@@ -340,6 +359,28 @@ def read_file_stream(path):
     got = lib().tjamd_read_file_stream(os.fsencode(path), out.ctypes.data, need, C.byref(n))
     assert got == need
     return out[:need], n.value
+
+
+def read_gff3(path, names):
+    """The feature lines of a GFF3 file (plain, gzip, BGZF) -> (FEATURE_DTYPE array, the strings its type_off / id_off point
+    into, as bytes).  names: the contig names in the reference's order (what tjamd_read_file_names gives).  Host-only.
+    The lines that were skipped are counted in read_gff3.last_skipped."""
+    blob = b"".join((n if isinstance(n, bytes) else str(n).encode()) + b"\n" for n in names)
+    nb, sk = C.c_long(0), C.c_long(0)
+    n = lib().tjamd_gff3_read(os.fsencode(path), blob, len(names), None, 0, None, 0, C.byref(nb), C.byref(sk))
+    if n < 0:
+        raise FileNotFoundError(path)
+    out = np.zeros(n, dtype=FEATURE_DTYPE)
+    strings = np.zeros(max(nb.value, 1), dtype=np.uint8)
+    got = lib().tjamd_gff3_read(os.fsencode(path), blob, len(names), out.ctypes.data, n, strings.ctypes.data, nb.value, C.byref(nb), C.byref(sk))
+    assert got == n
+    read_gff3.last_skipped = sk.value
+    return out, strings[: nb.value].tobytes()
+
+
+def gff3_string(strings, off):
+    """the NUL-terminated string at an offset of read_gff3's strings"""
+    return strings[off: strings.index(b"\0", off)].decode(errors="replace")
 
 
 class EmpfreqElement(C.Structure):
@@ -454,6 +495,38 @@ class Reference:
     def close(self):
         if self._h:
             lib().tjamd_reference_destroy(self._h)
+            self._h = None
+
+    __del__ = close
+
+
+class Annotation:
+    """tjamd_annotation: the features of a GFF3 file (a FEATURE_DTYPE array, as read_gff3 gives it) as an elementary-interval
+    table on the counter's device; ref gives the number of contigs"""
+
+    def __init__(self, counter, ref, features):
+        f = np.ascontiguousarray(features, dtype=FEATURE_DTYPE)
+        self._h = lib().tjamd_annotation_create(counter._h, ref._h, f.ctypes.data if len(f) else None, len(f))
+        if not self._h:
+            raise TatajubaAmdError(_err())
+
+    @property
+    def n_features(self):
+        return int(lib().tjamd_annotation_features(self._h))
+
+    def download(self):
+        """(points, winner): the sorted points and, per index, the file index of the winning feature or -1"""
+        n = lib().tjamd_annotation_download(self._h, None, None, 0)
+        if n < 0:
+            raise TatajubaAmdError(_err())
+        points, winner = np.zeros(n, dtype=np.uint64), np.zeros(n, dtype=np.int32)
+        if n and lib().tjamd_annotation_download(self._h, points.ctypes.data, winner.ctypes.data, n) != n:
+            raise TatajubaAmdError(_err())
+        return points, winner
+
+    def close(self):
+        if getattr(self, "_h", None):
+            lib().tjamd_annotation_destroy(self._h)
             self._h = None
 
     __del__ = close
@@ -643,6 +716,12 @@ class Counter:
 
     def last_tract_variants_ms(self):
         return lib().tjamd_last_tract_variants_ms(self._h)
+
+    def last_annotation_ms(self):
+        return lib().tjamd_last_annotation_ms(self._h)
+
+    def last_tract_features_ms(self):
+        return lib().tjamd_last_tract_features_ms(self._h)
 
     def uses_log(self):
         lib().tjamd_counter_uses_log.restype = C.c_int

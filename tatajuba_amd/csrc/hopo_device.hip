@@ -36,6 +36,7 @@
 
 #include "../../include/tatajuba_amd.h"
 #include "../../include/tatajuba_variants.h"
+#include "../../include/tatajuba_features.h"
 
 typedef unsigned long long u64;
 typedef unsigned int u32;
@@ -4114,7 +4115,7 @@ struct StageTimer
 };
 // the intervals of a counter: the last scan call (its partition kernels between the pieces included: tjamd_last_scan_ms takes
 // them out), finalise, the kernels of tjamd_merge_samples, tjamd_tract_stats, tjamd_union_tracts, tjamd_union_tract_stats
-enum { T_SCAN, T_FIN, T_MERGE, T_TRACT, T_UNION, T_UNION_STATS, T_REF, T_LOCATE, T_LOCATED_TRACTS, T_VARIANTS, TJ_N_TIMERS };   // (T_REF to T_LOCATED_TRACTS: N7, T_VARIANTS: N8, end of the file)
+enum { T_SCAN, T_FIN, T_MERGE, T_TRACT, T_UNION, T_UNION_STATS, T_REF, T_LOCATE, T_LOCATED_TRACTS, T_VARIANTS, T_ANNOTATION, T_TRACT_FEATURES, TJ_N_TIMERS };   // (T_REF to T_LOCATED_TRACTS: N7, T_VARIANTS: N8, the last two: N9, end of the file)
 
 struct tjamd_counter
 {
@@ -7309,6 +7310,19 @@ __device__ __forceinline__ long ref_entry_at (const RefEntry *__restrict__ entri
   return (lo < n_ent && entries[lo].flat == flat) ? lo : -1l;
 }
 
+// a sample's modal row among rows [first, end) of the union: the highest count above 0, the first on a tie; -1 if it has none
+// (the "sample's allele" of N8 and the max_length of N9)
+__device__ __forceinline__ long modal_row (const int *__restrict__ counts, long first, long end, int ns, int s)
+{
+  int best = 0;
+  long row = -1;
+  for (long r = first; r < end; r++) {
+    const int x = counts[r * ns + s];
+    if (x > best) { best = x; row = r; }
+  }
+  return row;
+}
+
 // !WRITE: flag[s * n_list + i] = 1 where sample s has a call in list entry i (every word is written), and the checks:
 // err |= 1 where the tracts do not tile the union, err |= 2 for a list id outside [0, n_tracts) (nothing is read outside the
 // arrays either way).  WRITE: the records, at excl[s * n_list + i], those below capacity.
@@ -7354,12 +7368,7 @@ void tract_variants_kernel (const u64 *__restrict__ keys, const int *__restrict_
       bool call = false;
       Variant v;
       if (ent >= 0) {
-        int best = 0;
-        long row = -1;
-        for (long r = first; r < end; r++) {            // the modal row: the highest count, the first on a tie
-          const int x = counts[r * ns + s];
-          if (x > best) { best = x; row = r; }
-        }
+        const long row = modal_row (counts, first, end, ns, s);
         if (row >= 0) {
           const RefEntry e = entries[ent];
           const int La = meta_len (keys[3 * row + 2]), Lr = e.length;
@@ -7456,3 +7465,283 @@ extern "C" long tjamd_tract_variants (tjamd_counter *c, const tjamd_reference *r
   return n_rec;
 }
 extern "C" double tjamd_last_tract_variants_ms (tjamd_counter *c) { return c ? c->timer[T_VARIANTS].ms (c->device) : -1.0; }
+
+// ---- N9: the GFF3 feature a located tract lies in, and the longest modal length ------------------------------------------
+// genomic_context_find_features (src/context_histogram.c:331-351) asks, per located histogram, for the features that hold
+// the tract's first base, skips regions, keeps the last one and stops at the first CDS; the rule as built is in
+// include/tatajuba_features.h.  Here the features become an elementary-interval table once (tjamd_annotation): the sorted
+// start and end + 1 points of the features that are not regions, and per index the maximum of a priority that encodes the
+// rule (a CDS above everything else, the earlier CDS above the later, otherwise the later feature above the earlier).  A
+// tract is then one binary search, whatever the nesting depth and however long the features around it are.
+// Thread mapping of the build, as in locate_kernel: a lane per feature finds its range of indices by two binary searches
+// and paints a range of up to AN_LANE_PAINT indices by itself; a longer one (a gene over thousands of points) is handed
+// to the whole wavefront, which paints it as consecutive words -- its length over 64, not one lane's serial walk.  The
+// atomicMax decides a value, never a place, and a maximum does not depend on order: the table is the same from run to run.
+// DESIGN.md section 3.5, N9.
+
+struct Feature { int contig, start, end, cls, strand, line, type_off, id_off; };
+static_assert (sizeof (Feature) == 32 && sizeof (Feature) == sizeof (tjamd_feature), "feature layout");
+struct TractFeature { int feature, max_length; };
+static_assert (sizeof (TractFeature) == 8 && sizeof (TractFeature) == sizeof (tjamd_tract_feature), "tract feature layout");
+
+#define AN_LANE_PAINT   16
+#define AN_MAX_FEATURES (1l << 30)      // the priorities of file indices below 2^30 stay apart in 31 bits
+
+struct tjamd_annotation
+{
+  int device = 0;
+  long n_features = 0, n_points = 0;
+  u64 *points = nullptr;                // ascending, duplicates kept
+  u32 *prio = nullptr;                  // per index e, for [points[e], points[e + 1]): the highest priority that covers it, 0 = nothing
+};
+
+__device__ __forceinline__ u64 feature_point (int contig, u32 at) { return ((u64) (u32) contig << 32) | (u64) at; }
+__host__ __device__ __forceinline__ int priority_winner (u32 p) { return !p ? -1 : (p >> 31) ? (int) (0x7fffffffu - (p & 0x7fffffffu)) : (int) (p - 1u); }
+
+__global__ void an_flag_kernel (const Feature *__restrict__ f, long n, u32 *__restrict__ flag)
+{
+  for (long i = blockIdx.x * (long) blockDim.x + threadIdx.x; i < n; i += (long) gridDim.x * blockDim.x) flag[i] = f[i].cls != TJAMD_FEATURE_REGION ? 1u : 0u;
+}
+
+// the two points of every feature that is not a region, at twice its rank among those
+__global__ void an_points_kernel (const Feature *__restrict__ f, long n, const u32 *__restrict__ excl, u64 *__restrict__ key, u32 *__restrict__ val)
+{
+  for (long i = blockIdx.x * (long) blockDim.x + threadIdx.x; i < n; i += (long) gridDim.x * blockDim.x) {
+    const Feature x = f[i];
+    if (x.cls == TJAMD_FEATURE_REGION) continue;
+    const long j = 2l * excl[i];
+    key[j] = feature_point (x.contig, (u32) x.start); key[j + 1] = feature_point (x.contig, (u32) x.end + 1u);
+    val[j] = val[j + 1] = (u32) i;
+  }
+}
+
+// first index of points[0, n) whose point is not below q (behind = false) / is above q (behind = true)
+__device__ __forceinline__ long point_bound (const u64 *__restrict__ points, long n, u64 q, bool behind)
+{
+  long lo = 0, hi = n;
+  while (lo < hi) {
+    const long mid = (lo + hi) >> 1;
+    const u64 p = points[mid];
+    if (behind ? p <= q : p < q) lo = mid + 1; else hi = mid;
+  }
+  return lo;
+}
+
+__global__ __launch_bounds__ (256)
+void an_paint_kernel (const Feature *__restrict__ f, long n, const u64 *__restrict__ points, long np, u32 *__restrict__ prio)
+{
+  const int lane = threadIdx.x & 63;
+  const long stride = (long) gridDim.x * blockDim.x;
+  for (long i0 = blockIdx.x * (long) blockDim.x + (threadIdx.x & ~63); i0 < n; i0 += stride) {     // (uniform across a wavefront)
+    const long i = i0 + lane;
+    long lo = 0, hi = 0;
+    u32 p = 0;
+    if (i < n) {
+      const Feature x = f[i];
+      if (x.cls != TJAMD_FEATURE_REGION) {
+        lo = point_bound (points, np, feature_point (x.contig, (u32) x.start), false);
+        hi = point_bound (points, np, feature_point (x.contig, (u32) x.end + 1u), false);
+        p = x.cls == TJAMD_FEATURE_CDS ? (1u << 31) | (0x7fffffffu - (u32) i) : (u32) i + 1u;
+      }
+    }
+    const bool mine = hi - lo <= AN_LANE_PAINT;
+    if (mine) for (long e = lo; e < hi; e++) atomicMax (&prio[e], p);
+    u64 big = __ballot (!mine);
+    while (big) {                                       // the wavefront paints its long ranges together, one after the other
+      const int src = __ffsll ((long long) big) - 1;
+      big &= big - 1;
+      const long blo = __shfl (lo, src), bhi = __shfl (hi, src);
+      const u32 bp = __shfl (p, src);
+      for (long e = blo + lane; e < bhi; e += 64) atomicMax (&prio[e], bp);
+    }
+  }
+}
+
+extern "C" void tjamd_annotation_destroy (tjamd_annotation *a)
+{
+  if (!a) return;
+  (void) hipSetDevice (a->device);
+  if (a->points) (void) hipFree (a->points);
+  if (a->prio) (void) hipFree (a->prio);
+  delete a;
+}
+
+extern "C" tjamd_annotation *tjamd_annotation_create (tjamd_counter *c, const tjamd_reference *ref, const tjamd_feature *h_features, long n_features)
+{
+  static const char *fn = "tjamd_annotation_create";
+  auto refused = [&] () -> int {                        // the checks that read no handle, the devices last
+    if (!c || !ref) return set_err (TJAMD_ERR_ARG, "%s: null counter or reference", fn);
+    if (n_features < 0 || (n_features > 0 && !h_features)) return set_err (TJAMD_ERR_ARG, "%s: %ld features with %s buffer", fn, n_features, h_features ? "a" : "a null");
+    if (n_features > AN_MAX_FEATURES) return set_err (TJAMD_ERR_ARG, "%s: %ld features, more than 2^30", fn, n_features);
+    if (tjamd_device_count () <= 0) return set_err (TJAMD_ERR_NO_DEVICE, "%s: TJAMD_ERR_NO_DEVICE: no HIP device visible (the table is built on the device; no CPU fallback)", fn);
+    if (ref->device != c->device) return set_err (TJAMD_ERR_ARG, "%s: the reference lives on device %d, the counter on device %d", fn, ref->device, c->device);
+    return TJAMD_OK;
+  };
+  const int bad = refused ();
+  if (c && tjamd_device_count () > 0) c->timer[T_ANNOTATION].timed = false;   // a refused call leaves no timing behind (without a device there is no counter)
+  if (bad) return NULL;
+  const long n = n_features;
+  long nr = 0;                                          // features that are not regions
+  for (long i = 0; i < n; i++) {
+    const tjamd_feature &x = h_features[i];
+    if (x.contig < 0 || (long) x.contig >= ref->n_contigs) { set_err (TJAMD_ERR_ARG, "%s: feature %ld: contig %d outside [0, %ld)", fn, i, x.contig, ref->n_contigs); return NULL; }
+    if (x.start < 1) { set_err (TJAMD_ERR_ARG, "%s: feature %ld: start %d < 1", fn, i, x.start); return NULL; }
+    if (x.end < x.start) { set_err (TJAMD_ERR_ARG, "%s: feature %ld: end %d < start %d", fn, i, x.end, x.start); return NULL; }
+    if (x.cls < 0 || x.cls > 2) { set_err (TJAMD_ERR_ARG, "%s: feature %ld: cls %d outside 0..2", fn, i, x.cls); return NULL; }
+    nr += x.cls != TJAMD_FEATURE_REGION;
+  }
+  HIPCHK_NULL (hipSetDevice (c->device));
+  tjamd_annotation *a = new tjamd_annotation ();
+  a->device = c->device; a->n_features = n; a->n_points = 2 * nr;
+  const long np = a->n_points;
+#define AN_FAIL(...) do { set_err (__VA_ARGS__); tjamd_annotation_destroy (a); return NULL; } while (0)
+  const int nblk = (int) ((np + RS_ITEMS - 1) / RS_ITEMS);
+  LcCut cut (nullptr);
+  Feature *feat = nullptr; u32 *flag = nullptr, *excl = nullptr, *val[2] = {nullptr, nullptr}; u64 *key[2] = {nullptr, nullptr};
+  for (int pass = 0; pass < 2; pass++) {
+    cut = LcCut (pass ? c->lc_work.p : nullptr);
+    feat = cut.take<Feature> (n + 1); flag = cut.take<u32> (n + 1); excl = cut.take<u32> (n + 1);
+    key[0] = cut.take<u64> (np + 1); key[1] = cut.take<u64> (np + 1); val[0] = cut.take<u32> (np + 1); val[1] = cut.take<u32> (np + 1);
+    if (!pass && (ensure (c->lc_work, cut.used, c->stream) || ensure (c->hist, (size_t) 256 * std::max (nblk, 1) * 4, c->stream) ||
+                  ensure (c->scan_tmp, std::max (scan_tmp_words (256l * nblk), scan_tmp_words (n)) * 4 + 64, c->stream))) { tjamd_annotation_destroy (a); return NULL; }
+  }
+  if (np && (hipMalloc (&a->points, (size_t) np * 8) != hipSuccess || hipMalloc (&a->prio, (size_t) np * 4) != hipSuccess)) AN_FAIL (TJAMD_ERR_HIP, "%s: hipMalloc failed for %ld points", fn, np);
+  if (n && hipMemcpyAsync (feat, h_features, (size_t) n * sizeof (Feature), hipMemcpyHostToDevice, c->stream) != hipSuccess) AN_FAIL (TJAMD_ERR_HIP, "%s: copy to device failed", fn);
+  if (np && hipMemsetAsync (a->prio, 0, (size_t) np * 4, c->stream) != hipSuccess) AN_FAIL (TJAMD_ERR_HIP, "%s: memset failed", fn);
+  u32 *tmp = (u32 *) c->scan_tmp.p; const size_t tw = c->scan_tmp.cap / 4;
+  (void) c->timer[T_ANNOTATION].begin (c->stream);
+  hipLaunchKernelGGL (an_flag_kernel, dim3 (grid_for (n)), dim3 (256), 0, c->stream, (const Feature *) feat, n, flag);
+  if (np) {
+    int rc = exclusive_scan (c, flag, excl, n, nullptr, tmp, tw);
+    hipLaunchKernelGGL (an_points_kernel, dim3 (grid_for (n)), dim3 (256), 0, c->stream, (const Feature *) feat, n, (const u32 *) excl, key[0], val[0]);
+    int bits = 32;                                      // of a point: the position, and what the contig numbers need
+    while (bits < 64 && ((u64) (ref->n_contigs - 1) >> (bits - 32))) bits++;
+    for (int p = 0; p < (bits + 7) / 8 && !rc; p++) {
+      hipLaunchKernelGGL (kv_count_kernel, dim3 (nblk), dim3 (256), 0, c->stream, (const u64 *) key[0], np, p, (u32 *) c->hist.p, nblk);
+      rc = exclusive_scan (c, (const u32 *) c->hist.p, (u32 *) c->hist.p, 256l * nblk, nullptr, tmp, tw);
+      hipLaunchKernelGGL (kv_scatter_kernel, dim3 (nblk), dim3 (256), 0, c->stream, (const u64 *) key[0], (const u32 *) val[0], key[1], val[1], np, p,
+                          (const u32 *) c->hist.p, nblk);
+      std::swap (key[0], key[1]); std::swap (val[0], val[1]);
+    }
+    if (rc) { tjamd_annotation_destroy (a); return NULL; }
+    hipLaunchKernelGGL (an_paint_kernel, dim3 (grid_for (n)), dim3 (256), 0, c->stream, (const Feature *) feat, n, (const u64 *) key[0], np, a->prio);
+  }
+  if (hipGetLastError () != hipSuccess) AN_FAIL (TJAMD_ERR_HIP, "%s: launch failed", fn);
+  (void) c->timer[T_ANNOTATION].end (c->stream);
+  if ((np && hipMemcpyAsync (a->points, key[0], (size_t) np * 8, hipMemcpyDeviceToDevice, c->stream) != hipSuccess) || hipStreamSynchronize (c->stream) != hipSuccess)
+    AN_FAIL (TJAMD_ERR_HIP, "%s: build failed: %s", fn, hipGetErrorString (hipGetLastError ()));
+#undef AN_FAIL
+  c->timer[T_ANNOTATION].timed = true;
+  return a;
+}
+
+extern "C" long tjamd_annotation_features (const tjamd_annotation *a) { return a ? a->n_features : -1; }
+
+extern "C" long tjamd_annotation_download (const tjamd_annotation *a, uint64_t *h_points, int *h_winner, long capacity)
+{
+  static const char *fn = "tjamd_annotation_download";
+  if (!a) return -set_err (TJAMD_ERR_ARG, "%s: null annotation", fn);
+  const long np = a->n_points;
+  if (np == 0 || capacity < np) return np;
+  if (!h_points || !h_winner) return -set_err (TJAMD_ERR_ARG, "%s: null buffer", fn);
+  std::vector<u32> prio ((size_t) np);
+  if (hipSetDevice (a->device) != hipSuccess || hipMemcpy (h_points, a->points, (size_t) np * 8, hipMemcpyDeviceToHost) != hipSuccess ||
+      hipMemcpy (prio.data (), a->prio, (size_t) np * 4, hipMemcpyDeviceToHost) != hipSuccess) return -set_err (TJAMD_ERR_HIP, "%s: copy failed", fn);
+  for (long e = 0; e < np; e++) h_winner[e] = priority_winner (prio[(size_t) e]);
+  return np;
+}
+extern "C" double tjamd_last_annotation_ms (tjamd_counter *c) { return c ? c->timer[T_ANNOTATION].ms (c->device) : -1.0; }
+
+// One record per tract.  Segment mapping of union_tract_stats_kernel and tract_variants_kernel: S lanes per tract; the
+// segment's first lane looks the location up in the table (one binary search) and reads the tract's rows; with a union, a
+// lane per sample (looping beyond 64) takes the length of the sample's modal row and the segment reduces the maximum with
+// shuffles.  Without a union (keys == NULL, S = 1) a thread per tract does the lookup alone.  err |= 1: the tracts do not
+// tile the union (checked as in tract_variants_kernel; nothing is read outside the arrays either way).
+__global__ __launch_bounds__ (256)
+void tract_features_kernel (const u64 *__restrict__ keys, const int *__restrict__ counts, long n_union, int ns, int S,
+                            const UnionTract *__restrict__ tracts, long n_tracts, const Location *__restrict__ tloc,
+                            const u64 *__restrict__ points, const u32 *__restrict__ prio, long np, TractFeature *__restrict__ out, int *__restrict__ err)
+{
+  const long gthread = blockIdx.x * (long) blockDim.x + threadIdx.x, n_threads = (long) gridDim.x * blockDim.x;
+  if (keys)
+    for (long t = gthread; t < n_tracts; t += n_threads) {
+      const long first = tracts[t].first, rows = tracts[t].n_rows;
+      const long want = t ? (long) tracts[t - 1].first + tracts[t - 1].n_rows : 0l;
+      if (first != want || rows < 1 || first + rows > n_union || (t == n_tracts - 1 && first + rows != n_union)) atomicOr (err, 1);
+    }
+  const int lane = threadIdx.x & (S - 1);
+  const long segs_per_grid = n_threads / S;
+  for (long t = gthread / S; t < n_tracts; t += segs_per_grid) {   // (uniform across a segment)
+    int feature = -1, longest = 0;
+    long first = 0, end = 0;
+    if (lane == 0) {
+      const Location l = tloc[t];
+      if (l.flat >= 0 && l.contig >= 0 && l.pos >= 0) {
+        const long e = point_bound (points, np, feature_point (l.contig, (u32) l.pos + 1u), true) - 1;
+        if (e >= 0) feature = priority_winner (prio[e]);
+      }
+      if (keys) {
+        const UnionTract u = tracts[t];
+        first = u.first; end = first + (long) u.n_rows;
+        if (first < 0 || u.n_rows < 1 || end > n_union) first = end = 0;   // (a broken tiling: flagged above)
+      }
+    }
+    if (keys) {
+      first = __shfl (first, 0, S); end = __shfl (end, 0, S);
+      int best = INT_MIN;                               // (a length field may read negative: no sample is not length 0)
+      for (int s = lane; s < ns; s += S) {
+        const long row = modal_row (counts, first, end, ns, s);
+        if (row >= 0) best = max (best, meta_len (keys[3 * row + 2]));
+      }
+      for (int o = 1; o < S; o <<= 1) best = max (best, __shfl_xor (best, o, S));
+      longest = best == INT_MIN ? 0 : best;
+    }
+    if (lane == 0) out[t] = TractFeature {feature, longest};
+  }
+}
+
+extern "C" long tjamd_tract_features (tjamd_counter *c, const tjamd_annotation *a, const void *d_keys, const void *d_counts, long n_union,
+                                      int n_samples, const tjamd_union_tract *d_tracts, long n_tracts, const tjamd_location *d_tract_loc,
+                                      tjamd_tract_feature *d_out)
+{
+  static const char *fn = "tjamd_tract_features";
+  const bool have_union = d_keys && d_counts;
+  auto refused = [&] () -> int {                        // the checks that read no handle, the counter's device last
+    if (have_union) {
+      const int rc = union_args (fn, d_keys, d_counts, n_union, n_samples);
+      if (rc) return rc;
+      if (n_tracts < (n_union > 0 ? 1 : 0) || n_tracts > n_union) return set_err (TJAMD_ERR_ARG, "%s: n_tracts %ld for a union of %ld rows", fn, n_tracts, n_union);
+      if (n_tracts > 0 && !d_tracts) return set_err (TJAMD_ERR_ARG, "%s: null tract buffer", fn);
+    }
+    if (n_tracts < 0) return set_err (TJAMD_ERR_ARG, "%s: n_tracts %ld < 0", fn, n_tracts);
+    if (n_tracts >= (1l << 31)) return set_err (TJAMD_ERR_CAPACITY, "%s: %ld tracts", fn, n_tracts);
+    if (n_tracts > 0 && (!d_tract_loc || !d_out)) return set_err (TJAMD_ERR_ARG, "%s: null tract location or output buffer", fn);
+    if (!c || !a) return set_err (TJAMD_ERR_ARG, "%s: null counter or annotation", fn);
+    if (tjamd_device_count () <= 0) return set_err (TJAMD_ERR_NO_DEVICE, "%s: TJAMD_ERR_NO_DEVICE: no HIP device visible (the tracts are looked up on the device; no CPU fallback)", fn);
+    if (a->device != c->device) return set_err (TJAMD_ERR_ARG, "%s: the annotation lives on device %d, the counter on device %d", fn, a->device, c->device);
+    return TJAMD_OK;
+  };
+  int rc = refused ();
+  if (c && tjamd_device_count () > 0) c->timer[T_TRACT_FEATURES].timed = false;   // a refused call leaves no timing behind (without a device there is no counter)
+  if (rc) return -rc;
+  if (hipSetDevice (c->device) != hipSuccess) return -set_err (TJAMD_ERR_HIP, "hipSetDevice failed");
+  if (n_tracts == 0) return 0;
+  rc = ensure (c->lc_work, 256, c->stream);
+  if (rc) return -rc;
+  int *err = (int *) c->lc_work.p;
+  if (hipMemsetAsync (err, 0, 4, c->stream) != hipSuccess) return -set_err (TJAMD_ERR_HIP, "%s: memset failed", fn);
+  (void) c->timer[T_TRACT_FEATURES].begin (c->stream);
+  const int S = have_union ? tract_segment (n_samples) : 1;
+  hipLaunchKernelGGL (tract_features_kernel, dim3 (tract_grid (n_tracts, S)), dim3 (256), 0, c->stream, have_union ? (const u64 *) d_keys : (const u64 *) nullptr,
+                      (const int *) d_counts, n_union, n_samples, S, (const UnionTract *) d_tracts, n_tracts, (const Location *) d_tract_loc,
+                      (const u64 *) a->points, (const u32 *) a->prio, a->n_points, (TractFeature *) d_out, err);
+  if (hipGetLastError () != hipSuccess) return -set_err (TJAMD_ERR_HIP, "%s: launch failed", fn);
+  (void) c->timer[T_TRACT_FEATURES].end (c->stream);
+  int h_err = 0;
+  if (hipMemcpyAsync (&h_err, err, 4, hipMemcpyDeviceToHost, c->stream) != hipSuccess || hipStreamSynchronize (c->stream) != hipSuccess)
+    return -set_err (TJAMD_ERR_HIP, "%s: failed: %s", fn, hipGetErrorString (hipGetLastError ()));
+  if (h_err) return -set_err (TJAMD_ERR_ARG, "%s: the tracts do not tile the union (first 0, each starting where the one before ends, the last ending at n_union)", fn);
+  c->timer[T_TRACT_FEATURES].timed = true;
+  return n_tracts;
+}
+extern "C" double tjamd_last_tract_features_ms (tjamd_counter *c) { return c ? c->timer[T_TRACT_FEATURES].ms (c->device) : -1.0; }

@@ -8,6 +8,7 @@
  */
 #include "../../include/tatajuba_amd.h"
 #include "../../include/tatajuba_variants.h"
+#include "../../include/tatajuba_features.h"
 #include <pthread.h>
 #include <sched.h>
 #include <sys/stat.h>
@@ -15,6 +16,7 @@
 #include "fastq_reader.h"
 #include "feeder.h"
 #include "tj_inflate.h"
+#include "gff3_reader.h"
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -363,6 +365,14 @@ tjamd_read_file_names (const char *path, char *out, long capacity, long *n_recor
   tjr_close (rd);
   if (n_records) *n_records = n;
   return total;
+}
+
+/* the feature lines of a GFF3 file (gff3_reader.c; the rules are in tatajuba_features.h) */
+long
+tjamd_gff3_read (const char *path, const char *contig_names, long n_contigs, tjamd_feature *out, long capacity,
+                 char *strings, long strings_capacity, long *strings_bytes, long *n_skipped)
+{
+  return tjg_read (path, contig_names, n_contigs, out, capacity, strings, strings_capacity, strings_bytes, n_skipped);
 }
 
 /* the multi-threaded feeder into host memory (tests compare it with tjamd_read_file_stream) */
