@@ -17,6 +17,8 @@
 // bucket), orders the survivors with a bin partition + per-wavefront rank sort, and derives the index and the coverage
 // in the same pass.  File map: helpers and tile scan (scan_tiles) -> sinks (located list, bucket staging) -> bucket
 // storage -> aggregation kernels -> radix sort / scans (fallback paths, merge) -> bin kernels -> host layer (tjamd_*).
+// One program: the file has no preprocessor conditionals.  Tile sizes and occupancies are plain #defines, and the
+// Makefile makes a -D that redefines one an error (-Werror=macro-redefined) instead of another library.
 
 #include <hip/hip_runtime.h>
 #include <rccl/rccl.h>                  // types only: the library is looked up at run time (rccl_api)
@@ -114,9 +116,7 @@ struct DevCounters
   struct { u64 n_fix; u32 work, n_slow, work_slow, ticket, pad[2]; } lc[2];   // (ticket: workgroups of the generic kernel that are through, see scan_bins_kernel)
 };
 
-#ifndef TJ_TILE_GROUP
 #define TJ_TILE_GROUP 16
-#endif
 
 struct FixEntry { long long pos; long long len; };
 
@@ -182,60 +182,6 @@ __device__ __forceinline__ void classify_word_fast (u32 x, u32 prev_word, bool h
   const u32 nz = (((d & 0x7F7F7F7Fu) + 0x7F7F7F7Fu) | d) & 0x80808080u;
   start4 = __builtin_amdgcn_udot4 (nz, wts, start4, false);
 }
-
-// ---- diagnostic build only (-DTJ_STAMPS=1): where does a tile's time go?  Never enabled in the product library. ----
-#ifndef TJ_STAMPS
-#define TJ_STAMPS 0
-#endif
-#if TJ_STAMPS
-__device__ unsigned long long tj_stamp_acc[32];
-struct Stamper
-{
-  unsigned long long last, acc[16];
-  __device__ __forceinline__ void begin () { for (int i = 0; i < 16; i++) acc[i] = 0; last = __builtin_amdgcn_s_memtime (); }
-  __device__ __forceinline__ void mark (int i) { unsigned long long t = __builtin_amdgcn_s_memtime (); acc[i] += t - last; last = t; }
-  __device__ __forceinline__ void flush () { if (threadIdx.x == 0) for (int i = 0; i < 16; i++) atomicAdd (&tj_stamp_acc[i], acc[i]); }
-};
-#define ASTAMP_DECL unsigned long long a_last = __builtin_amdgcn_s_memtime (), a_acc[8] = {0, 0, 0, 0, 0, 0, 0, 0}
-#define ASTAMP(i) { unsigned long long t_ = __builtin_amdgcn_s_memtime (); a_acc[i] += t_ - a_last; a_last = t_; }
-#define ASTAMP_FLUSH if ((threadIdx.x & 63) == 0) for (int i_ = 0; i_ < 8; i_++) atomicAdd (&tj_stamp_acc[16 + i_], a_acc[i_])
-#if TJ_STAMPS == 2                                      // (the partition kernel's stamps alone)
-#define STAMP_DECL
-#define STAMP(i)
-#define STAMP_FLUSH
-#define PLSTAMP_DECL Stamper stamper; stamper.begin (); sink.stp = &stamper
-#define PLSTAMP(i) stamper.mark (i)
-#define PLSTAMP_FLUSH stamper.flush ()
-#else
-#define STAMP_DECL Stamper stamper; stamper.begin (); sink.stp = &stamper
-#define STAMP(i) stamper.mark (i)
-#define STAMP_FLUSH stamper.flush ()
-#define PLSTAMP_DECL
-#define PLSTAMP(i)
-#define PLSTAMP_FLUSH
-#endif
-#define PSTAMP(i) stp->mark (i)
-#define STAMP_MEMBER Stamper *stp;
-extern "C" int tjamd_debug_stamps (unsigned long long *out, int reset)
-{
-  unsigned long long z[32] = {0};
-  if (hipMemcpyFromSymbol (out, HIP_SYMBOL (tj_stamp_acc), 32 * 8) != hipSuccess) return 1;
-  if (reset && hipMemcpyToSymbol (HIP_SYMBOL (tj_stamp_acc), z, 32 * 8) != hipSuccess) return 1;
-  return 0;
-}
-#else
-#define ASTAMP_DECL
-#define ASTAMP(i)
-#define ASTAMP_FLUSH
-#define STAMP_DECL
-#define STAMP(i)
-#define PSTAMP(i)
-#define STAMP_FLUSH
-#define STAMP_MEMBER
-#define PLSTAMP_DECL
-#define PLSTAMP(i)
-#define PLSTAMP_FLUSH
-#endif
 
 // inclusive prefix sum over the 64 lanes of a wavefront with DPP adds (row shifts inside 16-lane rows, then the two
 // row broadcasts): 6 VALU instructions instead of 6 ds_bpermute round trips
@@ -418,13 +364,8 @@ __device__ __forceinline__ void lds_dma16 (const void *gptr, void *lds_wave_base
 {
   const u32 m0v = (u32) __builtin_amdgcn_readfirstlane ((int) (u32) (size_t) (lptr_t) lds_wave_base);
   u32 saved;                                            // (M0 is the compiler's: put it back)
-#ifdef TJ_EXP_NT
-  asm volatile ("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off nt\n\ts_mov_b32 m0, %0"
-                : "=&s"(saved) : "v"(gptr), "s"(m0v) : "memory");
-#else
   asm volatile ("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
                 : "=&s"(saved) : "v"(gptr), "s"(m0v) : "memory");
-#endif
 }
 __device__ __forceinline__ void issue_chunk (const uint8_t *__restrict__ seq, long n_bytes, long g, uint4 *lds_wave_base)
 {
@@ -505,9 +446,7 @@ __device__ __forceinline__ void scan_tiles (const uint8_t *__restrict__ seq, lon
     }
   }
 
-  STAMP_DECL;
   while (tile < n_tiles) {
-    STAMP (0);
     if (tid == 0 && tile + tgroup == grp_end) T.grp[gpar ^ 1u] = atomicAdd (work, tgroup);  // first tile of a group: reserve the next
     const long g0 = own_start (tile) - TJ_HL;           // stream position of window byte 0 (may be negative)
     const int olen = own_len (tile);                    // tract starts in window positions [TJ_HL, TJ_HL + olen) belong to this tile
@@ -568,7 +507,6 @@ __device__ __forceinline__ void scan_tiles (const uint8_t *__restrict__ seq, lon
       }
     }
     sink.tick ();
-    STAMP (1);
     // the tile after this one: the next of the group, or the first of the next group (reserved TJ_TILE_GROUP - 1 tiles ago)
     const long nt = (tile + 1 < grp_end) ? tile + 1 : (long) T.grp[gpar ^ 1u];
     {
@@ -597,12 +535,7 @@ __device__ __forceinline__ void scan_tiles (const uint8_t *__restrict__ seq, lon
         }
       }
     }
-    STAMP (2);
     lds_barrier ();
-    STAMP (3);
-#if defined(TJ_EXP_STOP_AFTER) && TJ_EXP_STOP_AFTER == 1       // experiment builds only (tools/exp_scan_pmc.sh)
-    { if (tile + 1 >= grp_end) { gpar ^= 1u; grp_end = nt + tgroup; } tile = nt; it++; continue; }
-#endif
 
     // ---- phase 2: candidate tract starts among this lane's 16 positions ------------------------------------
     {
@@ -624,12 +557,7 @@ __device__ __forceinline__ void scan_tiles (const uint8_t *__restrict__ seq, lon
       // (never more than MAXCAND in a tile: a candidate takes m' >= 2 positions -- one in the monomer mode, where MAXCAND = TILE)
       while (cand) { int b = __ffs ((int) cand) - 1; cand &= cand - 1u; T.cand[at] = (unsigned short) (p0 + b); at++; }
     }
-    STAMP (4);
     lds_barrier ();
-    STAMP (5);
-#if defined(TJ_EXP_STOP_AFTER) && TJ_EXP_STOP_AFTER == 2
-    { if (tile + 1 >= grp_end) { gpar ^= 1u; grp_end = nt + tgroup; } tile = nt; it++; continue; }
-#endif
 
     // ---- phase 3: one lane per candidate --------------------------------------------------------------------
     const int ncand = min ((int) T.ncand, G::MAXCAND);
@@ -712,21 +640,13 @@ __device__ __forceinline__ void scan_tiles (const uint8_t *__restrict__ seq, lon
           }
         }
       }
-      STAMP (6);
-#if defined(TJ_EXP_STOP_AFTER) && TJ_EXP_STOP_AFTER == 3
-      if (have) asm volatile ("" :: "v"(c0), "v"(c1), "v"(base), "v"(len10), "v"(flag), "v"(pos));
-#else
       sink.put (have, c0, c1, base, len10, flag, pos, (u32) min (ncand - cb0, BLOCK));
-#endif
-      STAMP (7);
     }
     lds_barrier ();
-    STAMP (8);
     if (tile + 1 >= grp_end) { gpar ^= 1u; grp_end = nt + tgroup; }
     tile = nt;
     it++;
   }
-  STAMP_FLUSH;
 }
 
 // Non-ACGTU runs that qualify as tracts (reference: src/hopo_counter.c:246-248: add_kmer is called with whatever the
@@ -760,7 +680,6 @@ struct ListSink
 {
   static constexpr bool K32 = false;
   u64 *out; u64 cap; DevCounters *ctr;
-  STAMP_MEMBER
   __device__ __forceinline__ void tick () {}
   __device__ __forceinline__ void put (bool have, u64 c0, u64 c1, u32 base, u32 len10, u32 flag, u64 pos, u32 round_max)
   {
@@ -868,18 +787,14 @@ __device__ __forceinline__ u32 bucket_of_rec1 (u32 lo, u32 hi)
 
 #define TJ_P        256                 // hash buckets
 #define TJ_PBITS    8
-#ifndef TJ_STAGE_WORDS
 #define TJ_STAGE_WORDS 2048
-#endif
 // TJ_STAGE_WORDS: 64-bit words of one-word records a workgroup stages in LDS between partition passes (twice that in the fast kernel)
 #define TJ_CH0      1536                // chunk size unit in records; chunks are TJ_CH0 << ch_shift with ch_shift >= 2
 #define TJ_EMPTY    0xFFFFFFFFu
 // The bucket cursors take every reservation of every workgroup (millions of atomic adds per launch): each lives on a
 // 256-byte line of its own, so that they spread over the memory channels instead of queueing up at the one or two that
 // a packed 1 KB array maps to.  cursors[TJ_P * TJ_CSTRIDE] = the next free chunk.
-#ifndef TJ_CSTRIDE
 #define TJ_CSTRIDE  64
-#endif
 
 // Bucket storage.  A bucket is a sequence of records numbered by its cursor; a workgroup reserves a run of positions
 // with one atomic add and record `pos` lives in the bucket's (pos / CH)-th chunk (runs are shorter than a chunk, so a
@@ -1016,10 +931,6 @@ struct StageSink
   Buckets B; DevCounters *ctr; int k;
   u32 bound;                                            // upper bound of the records staged (workgroup-uniform)
   u32 cur_j, cur_chunk;                                 // owner thread (tid < TJ_P): the chunk its bucket is being written to
-  STAMP_MEMBER
-#if defined(TJ_EXP_SINK) && TJ_EXP_SINK >= 4
-  u32 exp_cur = 0;
-#endif
 
   __device__ __forceinline__ void start ()
   {
@@ -1101,12 +1012,6 @@ struct StageSink
   __device__ __forceinline__ u32 partition_big (const bool final_pass = false)
   {
     lds_barrier ();                                     // every append so far is in LDS
-#if defined(TJ_EXP_SINK) && TJ_EXP_SINK == 1            // experiment builds only: records dropped
-    if (threadIdx.x == 0) L.n = 0;
-    lds_barrier ();
-    return 0u;
-#endif
-    PSTAMP (9);
     const u32 n = (u32) __builtin_amdgcn_readfirstlane ((int) L.n);
     if constexpr (PS > 0) {
       // (fewer than PS records: the caller's bound had counted candidates that were not recorded -- the round it asked
@@ -1150,14 +1055,9 @@ struct StageSink
       if (FULL || (u32) r * BLOCK < n) {
         const u32 i = (u32) tid + (u32) r * BLOCK;
         if constexpr (!FULL) bb[r] = (i < n) ? bb[r] : (u32) (TJ_P + lane);
-#if defined(TJ_EXP_SINK) && TJ_EXP_SINK == 5            // experiment: no rank atomics (wrong results; cost of the LDS atomics)
-        rk[r] = 0; if (r == 0) L.hist[bb[r]] = 7u;
-#else
         rk[r] = atomicAdd (&L.hist[bb[r]], 1u);
-#endif
       }
     lds_barrier ();
-    PSTAMP (10);
     if (tid == 0) L.n = FULL ? n - (u32) PS : 0u;       // (everybody has read it; the next appends come after the last barrier below)
     u32 cnt = 0, p0 = 0, off = 0;
     if (wave < TJ_P / 64) {
@@ -1171,15 +1071,10 @@ struct StageSink
       off = L.offs[tid];
       // reserve the bucket's run: the global atomic's round trip runs under the LDS permutation below (its result is
       // first looked at after that)
-#if defined(TJ_EXP_SINK) && TJ_EXP_SINK >= 4            // experiment builds only: a private cursor instead of the global atomic (results are wrong)
-      if (cnt) { p0 = exp_cur; exp_cur = (p0 + cnt) & 255u; }
-#else
       if (cnt) p0 = atomicAdd (&B.cursors[tid * TJ_CSTRIDE], cnt);
-#endif
     }
     else if (!FULL && wave == TJ_P / 64) L.offs[tid] = (u32) S + (u32) lane;   // (the spare entries: rank 0 lands on staging slot S + lane)
     lds_barrier ();
-    PSTAMP (11);
     if (tid < TJ_P) L.hist[tid] = 0;                    // (for the next pass)
     {
       u32 dst[RR];
@@ -1194,19 +1089,13 @@ struct StageSink
           L.bin[d] = (unsigned char) bb[r];
         }
     }
-    PSTAMP (12);
     if (wave < TJ_P / 64) {                             // where the reserved run lives: byte addresses of "sorted slot 0" for both parts
       // (tried in round 3: the usual run -- inside the chunk its bucket was written to last time, opening no new one -- worked
       // out without a branch and the rest behind one wave-wide test: 1.5 M vector and 0.5 M scalar instructions MORE per
       // launch, 1 % slower; the exec regions below are cheaper than they look)
       u64 a1 = 0, a2 = 0;
       u32 thr = 0;
-#if defined(TJ_EXP_SINK) && TJ_EXP_SINK >= 4            // (experiment: every workgroup writes to a 4 KB region of its own per bucket)
-      if (cnt && cnt <= 256u) { a1 = (u64) (size_t) B.pool + (((((u64) tid * 512u + (blockIdx.x & 511u)) * 512u) + p0) << 3) - 8ull * off; thr = off + cnt; }
-      if (0) {
-#else
       if (cnt) {
-#endif
         const u32 ch = (u32) TJ_CH0 << B.ch_shift;
         bucket_claim_ahead (B, (u32) tid, p0, cnt, ctr);
         const u32 j0 = chunk_of_pos (B, p0), j1 = chunk_of_pos (B, p0 + cnt - 1);
@@ -1223,14 +1112,12 @@ struct StageSink
       // device addresses have 48) + thr << 16 | a2]   (gbase and gbase2 lie back to back: 256 x 16 bytes)
       reinterpret_cast<uint4 *> (L.gbase)[tid] = make_uint4 ((u32) a1, (u32) (a1 >> 32) | (thr << 16), (u32) a2, (u32) (a2 >> 32));
     }
-    PSTAMP (13);
     // Everything this wave has asked global memory for so far (the cursor's atomic, chunk ids, the tile's prefetch) is waited
     // for HERE, with the compiler's own instruction, before the first store below: from now on nothing is in flight that
     // anybody waits for but stores -- otherwise the compiler, unsure on which path a chunk id was fetched, puts a vmcnt(0)
     // where the tile loop's paths meet, in the classification of every tile, and that one waits for the stores too.
     __builtin_amdgcn_s_waitcnt (0x0F70);                // vmcnt(0) alone
     lds_barrier ();
-    PSTAMP (14);
 #pragma unroll
     for (int r0 = 0; r0 < RR; r0 += H)
       if (FULL || (u32) r0 * BLOCK < n) {
@@ -1251,11 +1138,7 @@ struct StageSink
         for (int h = 0; h < H; h++) if (r0 + h < RR) {  // sorted slot i -> its place in the bucket's run (coalesced per run)
           const u32 i = (u32) tid + (u32) (r0 + h) * BLOCK;
           const u64 a = (i < cthr[h]) ? ca1[h] : ca2[h];
-#if defined(TJ_EXP_SINK) && TJ_EXP_SINK == 3
-          const bool st = a == 0x123456789ull;
-#else
           const bool st = (FULL || i < n) && a != 0ull;
-#endif
           if (st) {
             // (a pointer into the global address space, said so: made from an integer it is a generic pointer to the compiler, the
             // stores become flat_store -- which counts in lgkmcnt as well, completes out of order, and makes every later
@@ -1269,7 +1152,6 @@ struct StageSink
         }
       }
     lds_barrier ();                                     // the staging buffer is free again
-    PSTAMP (15);
     if constexpr (FULL) {
       // what was staged beyond PS opens the next pass's buffer (the appends that follow go to slots n - PS and up: no
       // slot is written from both sides)
@@ -1371,9 +1253,7 @@ struct StageSink
 
 #define TJ_SB_BLOCK 512
 #define TJ_SB_TILE  8192
-#ifndef TJ_SB_WG_PER_CU
 #define TJ_SB_WG_PER_CU 3               // grid = 3 workgroups per CU: 2 are resident (65 KB of LDS each), the queued third evens out the tail
-#endif
 
 // the qualifying runs of a non-ACGTU byte that scan_tiles has listed: their context is the tract before them (reference
 // src/hopo_counter.c:246-248).  Entries first, first + step, ...
@@ -1489,7 +1369,6 @@ struct LogSink
   u32 bound;
   u32 upto, pend, pend_id;                              // thread 0: last block index with an address in L.blk; a reservation on its way
   u64 scratch;                                          // where lanes without a record write (byte address, 64 words per workgroup)
-  STAMP_MEMBER
 
   __device__ __forceinline__ u64 block_addr (u32 id) const
   {
@@ -1570,12 +1449,8 @@ struct LogSink
 };
 
 #define FK_BLOCK    512
-#ifndef FK_WG_PER_CU
 #define FK_WG_PER_CU 2
-#endif
-#ifndef FK_LOG_WG_PER_CU
 #define FK_LOG_WG_PER_CU 3              // the log variant (no staging buffer: 35 KB of LDS)
-#endif
 // FK_WG_PER_CU: 73 KB of LDS each (the 4096-record staging buffer is worth more than a third workgroup)
 #define FK_UNIT     32                  // stream bytes per lane
 #define FK_WIN      (FK_BLOCK * FK_UNIT)
@@ -1583,20 +1458,16 @@ struct LogSink
 #define FK_HR       64
 #define FK_OWN      (FK_WIN - FK_HL - FK_HR)
 static_assert (FK_OWN == TJ_LIST_FOWN, "scan_tiles' list mode is compiled for the fast kernel's tile size");
-#ifndef FK_MAXCAND
 #define FK_MAXCAND  4096
-#endif
 // FK_MAXCAND: (a tile with more candidates goes to the generic kernel: more than one per 4 positions)
-#ifndef FK_GROUP
 #define FK_GROUP    4                   // tiles per work-counter atomic (8: 1.5 % slower, a longer tail; 2: 5 % slower)
-#endif
 
 struct FastLds
 {
   u32 code[FK_WIN / 16 + 4];            // 2-bit codes, 16 positions per word (+ zeroed pad for funnel reads)
   u32 st[FK_WIN / 32 + 4];              // run starts (byte differs from its predecessor)
   u32 lt[FK_WIN / 32 + 4];              // letters (not a read delimiter)
-  unsigned short cand[FK_MAXCAND + 2 + 64];         // (+ 64: a spare entry per lane, see FK_CAND_UNROLL)
+  unsigned short cand[FK_MAXCAND + 2 + 64];         // (+ 64: unused; the spare entry per lane of the tried variant of the candidate loop below -- kept so that the LDS layout stays as measured)
   u32 ncand[4];                         // per tile, three in rotation (zeroed two tiles ahead)
   u32 bad[4];                           // per tile, likewise: some byte outside ACGT\n
   u32 grp[2];
@@ -1808,9 +1679,7 @@ void scan_fast_kernel (const uint8_t *__restrict__ seq, long n_bytes, long n_fti
     n_sbuf = 0;
   };
 
-  STAMP_DECL;
   while (tile < nt_all) {
-    STAMP (0);
     const u32 slot = it & 3u;
     // (opaque: as a loop invariant the compiler keeps "wave == 0" as a 64-bit mask in a spilled pair of SGPRs and pays two
     // v_readlane and an s_and per tile to look at it; compared afresh it is one s_cmp)
@@ -1905,19 +1774,6 @@ void scan_fast_kernel (const uint8_t *__restrict__ seq, long n_bytes, long n_fti
         u32 at = wbase + incl - n;
         // (tried: a loop on "any lane has one left" as a scalar branch, with the idle lanes writing to spare entries -- no
         // exec mask to keep per iteration, 11 M fewer scalar instructions per launch, and 4 % slower)
-#ifdef FK_CAND_UNROLL
-        // The first FK_CAND_UNROLL candidates of every lane without a loop (a lane has 1.5 on average, 98 in 100 have at most
-        // four): the loop's exec bookkeeping and branch are three scalar instructions per turn at the pace of the wave's
-        // busiest lane; here a lane without a candidate left writes to a spare entry of its own instead
-        const u32 spare_idx = (u32) FK_MAXCAND + 2u + (u32) lane;
-#pragma unroll
-        for (int j = 0; j < FK_CAND_UNROLL; j++) {
-          const u32 b = (u32) __ffs ((int) cand) - 1u;
-          T.cand[((u32) j < n) ? at + (u32) j : spare_idx] = (unsigned short) (p0 | b);
-          cand &= cand - 1u;
-        }
-        at += (u32) FK_CAND_UNROLL;
-#endif
         while (cand) {
           const u32 b = (u32) __ffs ((int) cand) - 1u;
           cand &= cand - 1u;
@@ -1932,7 +1788,6 @@ void scan_fast_kernel (const uint8_t *__restrict__ seq, long n_bytes, long n_fti
       // need not be waited for.  It needs the predecessor word loaded outside the compiler's view, into a register that
       // the compiler then copies before the word has arrived; through LDS it would cost what it gains, 1.7 %.)
       asm volatile ("s_waitcnt vmcnt(0)" ::: "memory");
-      STAMP (1);
       if constexpr (LOG) sink.collect ();
       const uint4 va = raw[2 * tid], vb = raw[2 * tid + 1];
       x[0] = va.x; x[1] = va.y; x[2] = va.z; x[3] = va.w; x[4] = vb.x; x[5] = vb.y; x[6] = vb.z; x[7] = vb.w;
@@ -1952,43 +1807,26 @@ void scan_fast_kernel (const uint8_t *__restrict__ seq, long n_bytes, long n_fti
       }
       if (classify (std::false_type ())) T.ncand[slot] = 0x40000000u;   // (more candidates than any tile has: looked at below; later atomic adds keep it so)
     }
-    STAMP (2);
     // the tile after this one
     int nt = tile + 1;
     if (nt >= grp_end) nt = __builtin_amdgcn_readfirstlane ((int) T.grp[gpar ^ 1u]);
     asm volatile ("s_waitcnt lgkmcnt(0)" ::: "memory");   // raw has been read: it may be refilled
     prefetch (nt);
-    STAMP (3);
 
-#if defined(FK_EXP_STOP) && FK_EXP_STOP == 1          // experiment builds only (tools/exp_fast_phases.sh)
-    if (S32 == 0x12345u && L32 == 0x54321u) T.bad[3] = 1u;
-    S32 = 0;
-#endif
     find_candidates (ncand_addr + 4u * slot, false);
-    STAMP (4);
     // the records staged so far, exactly: read BEFORE the barrier -- between the barrier that ended the tile before and
     // this one nobody appends, so every wave reads the same number; behind the barrier the quick waves are already
     // appending this tile's records while a slow one has yet to look (seen: one scan in fifty lost some eighty records
     // when a wave got a larger number, partitioned on its own schedule and its barriers paired up with the others' wrongly)
     const u32 staged_v = SL.n;
     if constexpr (LOG) sink.tile_top (staged_v);
-#if !(defined(FK_EXP_NOBAR) && (FK_EXP_NOBAR & 2))
     lds_barrier ();
-#endif
-    STAMP (5);
 
     // ---- phase 3: one lane per candidate ----------------------------------------------------------------------
-#if defined(FK_EXP_STOP) && FK_EXP_STOP <= 2
-    const u32 ncand_all = (T.ncand[slot] == 0x7FFFFFFFu) ? 1u : 0u;
-#else
     const u32 ncand_all = (u32) __builtin_amdgcn_readfirstlane ((int) T.ncand[slot]);
-#endif
     // (`bound` has counted candidates, of which one in eight is not recorded -- with the true count the buffer is
     // partitioned when it is full)
     sink.bound = LOG ? 0u : (u32) __builtin_amdgcn_readfirstlane ((int) staged_v);
-#if defined(FK_EXP_LINEAR)
-    sink.bound = 0;
-#endif
     u32 ncand_now = ncand_all;
     if (ncand_all >= 0x40000000u) {
       // Second chance for a tile with a byte outside the five: if all such bytes are 'N' (the no-call of every sequencer),
@@ -2077,9 +1915,7 @@ void scan_fast_kernel (const uint8_t *__restrict__ seq, long n_bytes, long n_fti
         // `general`), without branches: lanes past the list's end work on its last entry again and are masked out at the
         // end.  The windows depend on s alone, so all their LDS reads are in flight together: run starts from s + 1,
         // letters from s - k, and 64 bits of codes from s - k (left flank, tract, right flank).
-#if !(defined(FK_EXP_STOP) && FK_EXP_STOP == 3)
         if (!all_fit) sink.reserve1 ((u32) min (ncand - cb0, FK_BLOCK));    // (may partition: before anything of this round is in registers)
-#endif
         if (cb0 + 64 * wave >= ncand) continue;            // (whole waves without a candidate in this round)
         const int ci = cb0 + tid;
         const bool valid = ci < ncand;
@@ -2105,23 +1941,13 @@ void scan_fast_kernel (const uint8_t *__restrict__ seq, long n_bytes, long n_fti
         const bool ok = bad == 0u;
         if (valid && (int) room < 0) {                     // (rare) the long tracts: appended on their own (before this wave's atomic is issued: its result register must not live across a call)
           const u64 rec = fast_general_tract (T, seq, n_bytes, tile * (long) FK_OWN - FK_HL, (int) s, k, mprime, (ncand_all >= 0x40000000u));
-#if !(defined(FK_EXP_STOP) && FK_EXP_STOP == 3)
           if (rec != 0ull) sink.store1 (atomicAdd (&sink.L.n, 1u), (u32) rec, (u32) (rec >> 32));
-#endif
         }
-#if defined(FK_EXP_STOP) && FK_EXP_STOP == 3
-        const u32 at = 0;
-#else
         // whether the tract is recorded is known: its slot in the staging buffer is asked for now (an LDS atomic per
         // wave) and the record is worked out while that is on its way
         const u64 okm = __builtin_amdgcn_ballot_w64 (ok);
         u32 araw;
-#if defined(FK_EXP_SCATTER)
-        lds_add_issue (sink.count_addr (), 0u, araw);
-#else
         lds_add_issue (sink.count_addr (), (u32) __builtin_popcountll (okm), araw);
-#endif
-#endif
         const u32 sh = u + u;
         const u32 clo = __builtin_amdgcn_alignbit (w1, w0, sh), chi = __builtin_amdgcn_alignbit (w2, w1, sh);
         const u32 l = clo & vkm;
@@ -2143,48 +1969,16 @@ void scan_fast_kernel (const uint8_t *__restrict__ seq, long n_bytes, long n_fti
         const u32 fld24 = __builtin_amdgcn_perm (0u, 0x10140C08u, (cb << 24) | 0x000C0C0Cu);
         const u32 lo = c1 | (len << 24);
         const u32 hi = c0 | fld24;
-        STAMP (6);
-#if defined(FK_EXP_STOP) && FK_EXP_STOP == 3
-        if (ok) asm volatile ("" :: "v"(lo), "v"(hi), "v"(at));
-#else
-#if defined(FK_EXP_LINEAR)                              // experiment: no staging, no partition: records to a linear log of the workgroup's own
-        {
-          const u32 at = lds_collect (araw) + (u32) __builtin_amdgcn_mbcnt_hi ((u32) (okm >> 32), __builtin_amdgcn_mbcnt_lo ((u32) okm, 0u));
-          typedef __attribute__((address_space(1))) u64 *gwords_t;
-          gwords_t q = (gwords_t) ((u64) (size_t) BK.pool + (((u64) blockIdx.x * 200000u + (at % 200000u)) << 3));
-          if (ok) *q = ((u64) hi << 32) | lo;
-        }
-#elif defined(FK_EXP_SCATTER)                           // experiment: no staging, every record straight to a private place of its bucket (wrong results)
-        (void) lds_collect (araw);
-        {
-          u32 h = __builtin_amdgcn_udot4 (lo, vh0, 0u, false);
-          h = __builtin_amdgcn_udot4 (hi & vm27, vh1, h, false);
-          const u32 bin = ok ? ((h ^ (h >> 8)) & 255u) : 256u + (u32) lane;
-          const u32 r = atomicAdd (&SL.hist[bin], 1u);
-          const uint4 e = reinterpret_cast<const uint4 *> (SL.gbase)[bin & 255u];
-          asm volatile ("" :: "v"(e.x), "v"(e.y), "v"(e.z), "v"(e.w));
-          typedef __attribute__((address_space(1))) u64 *gwords_t;
-          gwords_t q = (gwords_t) ((u64) (size_t) BK.pool + ((((u64) (bin & 255u) * 512u + (blockIdx.x & 511u)) * 512u + (r & 511u)) << 3));
-          if (ok) *q = ((u64) hi << 32) | lo;
-        }
-#else
         const u32 at = lds_collect (araw) + (u32) __builtin_amdgcn_mbcnt_hi ((u32) (okm >> 32), __builtin_amdgcn_mbcnt_lo ((u32) okm, 0u));
         if constexpr (LOG) sink.store1ok (ok, at, lo, hi, (u32) lane);
         else sink.store1v (ok ? at : (u32) sink.S + (u32) lane, lo, hi, vh0, vh1, vm27);   // (no record: a spare slot takes the write)
-#endif
-#endif
-        STAMP (7);
       }
     }
-#if !(defined(FK_EXP_NOBAR) && (FK_EXP_NOBAR & 1))     // (timing experiment only: results are wrong without it)
     lds_barrier ();
-#endif
-    STAMP (8);
     if (nt >= grp_end) { gpar ^= 1u; grp_end = nt + FK_GROUP; }
     tile = nt;
     it++;
   }
-  STAMP_FLUSH;
   flush_slow ();
   sink.finish ();
 }
@@ -2194,9 +1988,7 @@ void scan_fast_kernel (const uint8_t *__restrict__ seq, long n_bytes, long n_fti
 // to their sorted slot -- the same reservation protocol on the same bucket cursors and chunk table as every other
 // producer of raw records.
 #define PL_BLOCK 512
-#ifndef PL_WG_PER_CU
 #define PL_WG_PER_CU 2
-#endif
 template <int W>
 __global__ __launch_bounds__ (PL_BLOCK, PL_BLOCK * PL_WG_PER_CU / 256)
 void partition_log_kernel (LogSpace LG, Buckets BK, DevCounters *ctr, int k)
@@ -2222,9 +2014,6 @@ void partition_log_kernel (LogSpace LG, Buckets BK, DevCounters *ctr, int k)
   u32 cur_j = TJ_EMPTY, cur_chunk = TJ_NOCHUNK;         // owner thread (tid < TJ_P): the chunk its bucket was written to last
   lds_barrier ();
   const u32 n_blocks = min (*LG.next, LG.n_blocks);
-#if TJ_STAMPS == 2
-  Stamper stamper; stamper.begin ();
-#endif
   // (blocks in turn, static: a shared work counter would be one more address that every workgroup of the grid adds to)
   u32 b = blockIdx.x;
   if (b >= n_blocks) return;
@@ -2255,7 +2044,6 @@ void partition_log_kernel (LogSpace LG, Buckets BK, DevCounters *ctr, int k)
     const u32 bn = b + gridDim.x;
     const bool more = bn < n_blocks;                      // (uniform)
     if (more) nn = min (LG.count[bn], RB);                // (asked for now, looked at when this block is done)
-    PLSTAMP (0);
     u32 tq = tid;
     asm volatile ("" : "+v"(tq));                         // (opaque: what the compiler can derive from tid alone it hoists out of the loop -- sixteen 64-bit offsets 8 i took 32 registers and went to scratch)
     u32 pk[RR / 4];
@@ -2269,9 +2057,7 @@ void partition_log_kernel (LogSpace LG, Buckets BK, DevCounters *ctr, int k)
         pk[r >> 2] |= bin << (8u * (r & 3u));
         if (tid + r * PL_BLOCK < n) atomicAdd (&L.hist[bin], 1u);
       }
-      PLSTAMP (1);
       lds_barrier ();
-      PLSTAMP (2);
       // ---- owners: prefix, reservation, where the run lives
       if (wave < TJ_P / 64) {
         const uint4 h4 = *reinterpret_cast<const uint4 *> (&L.hist[4 * lane]);
@@ -2296,9 +2082,7 @@ void partition_log_kernel (LogSpace LG, Buckets BK, DevCounters *ctr, int k)
         }
         reinterpret_cast<uint4 *> (L.gbase)[tid] = make_uint4 ((u32) a1, (u32) (a1 >> 32) | (thr << 16), (u32) a2, (u32) (a2 >> 32));
       }
-      PLSTAMP (3);
       lds_barrier ();
-      PLSTAMP (4);
       if (tid < TJ_P) L.hist[tid] = 0;                    // (for the next block; the ranks below count in offs)
       // ---- every record to its sorted slot (offs[bucket] runs from the bucket's first slot to its last)
 #pragma unroll
@@ -2310,9 +2094,7 @@ void partition_log_kernel (LogSpace LG, Buckets BK, DevCounters *ctr, int k)
           for (int j = 0; j < W; j++) L.rec[d * W + j] = w[r][j];
           L.bin[d] = (unsigned char) bin;
         }
-      PLSTAMP (5);
       lds_barrier ();
-      PLSTAMP (6);
       // ---- copy-out: sorted slot i -> its place in the bucket's run
       for (u32 r0 = 0; r0 < RR; r0 += 4) {
         if (r0 * PL_BLOCK >= n) break;
@@ -2337,15 +2119,12 @@ void partition_log_kernel (LogSpace LG, Buckets BK, DevCounters *ctr, int k)
           }
         }
       }
-      PLSTAMP (7);
       lds_barrier ();                                     // the sorted buffer is free again
-      PLSTAMP (8);
     }
     if (!more) break;
     load_block (bn, nn);
     n = nn; b = bn;
   }
-  PLSTAMP_FLUSH;
 }
 
 template <int W>
@@ -2533,17 +2312,10 @@ __device__ __forceinline__ void plan_tail (FinCounts *fin, int k, long cap, FinP
 // aggregation starts right behind the kernel that filled it: behind partition_log_kernel the waves' wait for their loads
 // fell by more than half and the kernel from 0.160 to 0.137 ms (the time it takes behind the fused scan kernel).
 // Returns a position >= n when the bucket is used up.
-#ifndef AG_FROM_END
-#define AG_FROM_END 1
-#endif
 __device__ __forceinline__ u32 batch_start (u32 t, u32 n, u32 batch)
 {
-#if AG_FROM_END
   const u32 nb = (n + batch - 1u) / batch;
   return t < nb ? (nb - 1u - t) * batch : n;
-#else
-  return t * batch;
-#endif
 }
 
 struct Agg1Lds
@@ -2572,9 +2344,7 @@ void aggregate1_kernel (Buckets BK, u64 *ovf, int k, int remove_biased, u64 *__r
   // so the waves of a round run free of each other (no barrier in the record loop).
   const u64 *src = BK.pool;
   u64 *dst = ovf;
-  ASTAMP_DECL;
   while (n > 0) {
-    ASTAMP (0);
     for (int i = tid; i < AG1_S; i += AG_BLOCK) { L.key[i] = 0; L.cnt[2 * i] = 0; L.cnt[2 * i + 1] = 0; }
     if (tid == 0) { L.n_claimed = 0; L.n_ovf = 0; L.next_batch = 0; }
     __syncthreads ();
@@ -2621,7 +2391,6 @@ void aggregate1_kernel (Buckets BK, u64 *ovf, int k, int remove_biased, u64 *__r
     };
     u32 b_next = next_batch ();
     fetch (b_next);
-    ASTAMP (1);
     while (b_next < n) {
       const u32 b0 = b_next;
       (void) b0;
@@ -2630,22 +2399,12 @@ void aggregate1_kernel (Buckets BK, u64 *ovf, int k, int remove_biased, u64 *__r
       // the next round's loads have been issued, i.e. for those as well (vmcnt counts in order).
       asm volatile ("s_waitcnt vmcnt(0)" : "+v"(wn[0]), "+v"(wn[1]), "+v"(wn[2]), "+v"(wn[3]) :: "memory");
       static_assert (AG1_R == 4, "asm operand list");
-      ASTAMP (2);
       u64 w[AG1_R];
 #pragma unroll
       for (int r = 0; r < AG1_R; r++) w[r] = wn[r];
       const u32 valid = vn;
       b_next = next_batch ();
       fetch (b_next);
-      ASTAMP (3);
-      ASTAMP (4);
-#if defined(TJ_EXP_AGG) && TJ_EXP_AGG == 1      // experiment: loads only
-      { u64 acc = 0;
-#pragma unroll
-        for (int r = 0; r < AG1_R; r++) acc ^= w[r];
-        if (acc == 0x123456789ull) atomicAdd (&L.n_ovf, 1u);
-        continue; }
-#endif
       // Table protocol.  Slots come in aligned pairs read with one 16-byte LDS load; a key's probe chain is its home
       // pair, the next pair, ... and it lives in the first slot of the chain that was free when it arrived.  Almost
       // every record finds its key with that one load and adds to its counter (no compare-and-swap: a bucket holds
@@ -2731,10 +2490,8 @@ void aggregate1_kernel (Buckets BK, u64 *ovf, int k, int remove_biased, u64 *__r
           }
         }
       }
-      ASTAMP (5);
     }
     __syncthreads ();
-    ASTAMP (6);
 
     u32 mine = 0;
     u64 metas[AG1_S / AG_BLOCK];
@@ -2780,9 +2537,7 @@ void aggregate1_kernel (Buckets BK, u64 *ovf, int k, int remove_biased, u64 *__r
     n = L.n_ovf;
     { const u64 *t = src; src = dst; dst = (u64 *) t; }
     __syncthreads ();
-    ASTAMP (7);
   }
-  ASTAMP_FLUSH;
   plan_tail (fin, k, plan_cap, plan);
 }
 
@@ -2797,9 +2552,7 @@ void aggregate1_kernel (Buckets BK, u64 *ovf, int k, int remove_biased, u64 *__r
 // home pair settles nine records in ten.
 #define AG2_S        6144
 #define AG2_PAIRS    (AG2_S / 2)
-#ifndef AG2_CLOSE_AT
 #define AG2_CLOSE_AT 2560
-#endif
                                         // (closing early pays: at 4.6 k keys per bucket -- the long-read configuration -- a table filled to 75 % costs more in probes than the second round costs in traffic)
 #define AG2_R        4                   // records in flight per lane
 #define AG2_VALID    (1ull << 63)        // set in the stored second key word (bits 61-63 of it are not key)
@@ -4539,8 +4292,7 @@ static int scan_device_piece (tjamd_counter *c, const void *d_stream, size_t n_b
   // fast kernel: tiles of FK_OWN tract starts, two workgroups resident per CU; the list of the tiles it leaves to the generic
   // kernel (every one of them at worst), which that kernel covers with ceil (FK_OWN / TJ_SB_TILE) of its own tiles each
   const long n_ftiles = (long) ((n_bytes + FK_OWN - 1) / FK_OWN);
-  static const int fwg = getenv ("TATAJUBA_AMD_FGRID") ? atoi (getenv ("TATAJUBA_AMD_FGRID")) : FK_WG_PER_CU;     // (experiment hook: workgroups per CU)
-  const int fgrid = (int) std::min<long> (n_ftiles, (long) c->n_cu * fwg);
+  const int fgrid = (int) std::min<long> (n_ftiles, (long) c->n_cu * FK_WG_PER_CU);
   const int lgrid = (int) std::min<long> (n_ftiles * ((FK_OWN + TJ_SB_TILE - 1) / TJ_SB_TILE), (long) c->n_cu * TJ_SB_WG_PER_CU);
   if (!rc && c->fast_mode) rc = ensure (c->slow, (size_t) n_ftiles * 4 + 64, c->stream);
   if (rc) return rc;
