@@ -10,13 +10,17 @@
  *   DIR/tract_locations.tsv            every tract: contig, position, strand (+, -, or . if unlocated), the reference's tract
  *                                      length, mismatches of the best hit, number of hits
  * -x is the number of mismatches allowed in the inexact flank (1); the other options are selected_tracts.c's.
+ * -g max_edits adds the second pass (tatajuba_locate.h): the rows tjamd_locate left unlocated are tried by a banded edit
+ * distance of up to max_edits edits in both flanks together, each flank shifted by up to -s max_shift bases (3); one more
+ * line on the standard output gives the rows it located.  Without -g nothing changes.
  *
  *   gcc -O2 -I include examples/located_tracts.c -L tatajuba_amd -ltatajuba_amd -Wl,-rpath,$PWD/tatajuba_amd -o located_tracts
- *   ./located_tracts -r reference.fa [-x 1] [-k 10] [-m 3] [-c 5] [-d 1] [-l -1] [-o .] sample1.fastq[.gz] sample2.fastq[.gz] ...   */
+ *   ./located_tracts -r reference.fa [-x 1] [-g G] [-s 3] [-k 10] [-m 3] [-c 5] [-d 1] [-l -1] [-o .] sample1.fastq[.gz] sample2.fastq[.gz] ...   */
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
 #include <tatajuba_amd.h>
+#include <tatajuba_locate.h>
 
 #define MAX_SAMPLES 64
 
@@ -45,8 +49,8 @@ main (int argc, char **argv)
 {
   tjamd_counter *ctr[MAX_SAMPLES];
   const char *files[MAX_SAMPLES], *outdir = ".", *reference = NULL;
-  long counts[MAX_SAMPLES], total, n_union, n_grouped, n_tracts, n_located, n_sel = 0, i, cap, ref_bytes, n_contigs = 0;
-  int n = 0, k = 10, m = 3, cov = 5, maxd = 1, lev = -1, mism = 1, coverage[MAX_SAMPLES], a, j, ndev = tjamd_device_count (), status;
+  long counts[MAX_SAMPLES], total, n_union, n_grouped, n_tracts, n_located, n_gapped = 0, n_sel = 0, i, cap, ref_bytes, n_contigs = 0;
+  int n = 0, k = 10, m = 3, cov = 5, maxd = 1, lev = -1, mism = 1, max_edits = -1, max_shift = TJAMD_MAX_SHIFT, coverage[MAX_SAMPLES], a, j, ndev = tjamd_device_count (), status;
   const void *d_records = NULL;
   void *d_keys, *d_counts, *d_ids, *d_grouped, *d_loc, *d_perm, *d_pkeys, *d_pcounts, *d_tracts, *d_tloc, *d_reflen, *d_summary, *d_sel;
   unsigned char *ref_stream;
@@ -63,11 +67,13 @@ main (int argc, char **argv)
     else if (!strcmp (argv[a], "-d") && a + 1 < argc) maxd = atoi (argv[++a]);
     else if (!strcmp (argv[a], "-l") && a + 1 < argc) lev = atoi (argv[++a]);
     else if (!strcmp (argv[a], "-x") && a + 1 < argc) mism = atoi (argv[++a]);
+    else if (!strcmp (argv[a], "-g") && a + 1 < argc) max_edits = atoi (argv[++a]);
+    else if (!strcmp (argv[a], "-s") && a + 1 < argc) max_shift = atoi (argv[++a]);
     else if (!strcmp (argv[a], "-r") && a + 1 < argc) reference = argv[++a];
     else if (!strcmp (argv[a], "-o") && a + 1 < argc) outdir = argv[++a];
     else if (n < MAX_SAMPLES) files[n++] = argv[a];
   }
-  if (n < 1 || !reference) { fprintf (stderr, "usage: %s -r reference.fa [-x X] [-k K] [-m M] [-c C] [-d D] [-l L] [-o DIR] sample.fastq[.gz] ...\n", argv[0]); return 2; }
+  if (n < 1 || !reference) { fprintf (stderr, "usage: %s -r reference.fa [-x X] [-g G] [-s S] [-k K] [-m M] [-c C] [-d D] [-l L] [-o DIR] sample.fastq[.gz] ...\n", argv[0]); return 2; }
   if (ndev < 1) { fprintf (stderr, "tatajuba_amd error: no HIP device is visible (there is no CPU fallback)\n"); return 1; }
   if (maxd < 0) maxd = 0;                                 /* src/main.c:190-192 */
   if (maxd > k / 2) maxd = k / 2;
@@ -110,6 +116,11 @@ main (int argc, char **argv)
   d_loc = tjamd_device_alloc (ctr[0], (size_t) cap * sizeof (tjamd_location));
   n_located = tjamd_locate (ctr[0], ref, d_keys, n_union, mism, (tjamd_location *) d_loc);
   if (n_located < 0) return fail ("locate");
+  if (max_edits >= 0) {                                   /* the second pass, on the rows left unlocated */
+    if (tjamd_reference_add_seeds (ctr[0], ref) < 0) return fail ("seed order");
+    n_gapped = tjamd_locate_gapped (ctr[0], ref, d_keys, n_union, max_edits, max_shift, (tjamd_location *) d_loc, NULL);
+    if (n_gapped < 0) return fail ("gapped locate");
+  }
 
   /* tracts at one place become one; the union permuted into the order of the places; then summaries and the selected ids */
   d_perm = tjamd_device_alloc (ctr[0], (size_t) cap * sizeof (int));
@@ -133,6 +144,7 @@ main (int argc, char **argv)
       tjamd_device_download (ctr[0], h_sel, d_sel, (size_t) n_sel * sizeof (int))) return fail ("download");
   printf ("%ld contigs, %ld runs indexed; %ld of %ld union rows located; %ld grouped tracts -> %ld tracts by location\n", n_contigs,
           tjamd_reference_entries (ref), n_located, n_union, n_grouped, n_tracts);
+  if (max_edits >= 0) printf ("%ld more union rows located within %d edits and a shift of %d\n", n_gapped, max_edits, max_shift);
 
   /* :398: no GFF3, so every selected tract is "not annotated" */
   printf ("From %d tracts, %d interesting ones are annotated and %d interesting ones are not annotated\n", (int) n_tracts, 0, (int) n_sel);

@@ -338,8 +338,9 @@ long tjamd_reference_download (const tjamd_reference *ref, tjamd_ref_entry *out,
  * and neg_strand are that entry's.  No hit: flat = contig = pos = -1, the rest 0.  Rows of one context get one result.
  * A reference built with another k or on another device is refused, as is max_mismatches outside 0 ... k.  Waits once, at
  * the end.  Returns the number of located rows.
- * Out of scope: a row whose flank differs from the genome by an indel stays unlocated (such rows are placed through the
- * tract they joined in tjamd_union_tracts); mismatches in both flanks are not matched; GFF3 features are read in tatajuba_features.h; the
+ * Out of scope here: a row whose flank differs from the genome by an indel, or that has mismatches in both flanks, stays
+ * unlocated by this call; tjamd_locate_gapped (N10, tatajuba_locate.h) is the second pass that tries those rows by a banded
+ * edit distance.  GFF3 features are read in tatajuba_features.h; the
  * drop-in gets no find_reference_location_and_sort_hopo_counter of its own (the weak hook stays as it is: a host program
  * fills loc_* from this call on tjamd_kept_device_ptr). */
 typedef struct { long long flat; int contig, pos, ref_length, mismatches, neg_strand, n_hits; } tjamd_location;   /* 32 bytes */
@@ -378,6 +379,10 @@ long tjamd_located_tracts (tjamd_counter *c, const void *d_keys, const void *d_c
 /* Per-sample tract variants against the reference as the fields of VCF records (N8: tjamd_tract_variants), and the contig
  * names of a FASTA file (tjamd_read_file_names), are declared in tatajuba_variants.h, which includes this header; their
  * timer is tjamd_last_tract_variants_ms below. */
+
+/* The second pass of the lookup for rows whose flanks differ from the genome by indels or in both flanks (N10: the seed
+ * order of the index, the banded flank distance and the gapped lookup) is declared, with its timers, in tatajuba_locate.h,
+ * which includes this header. */
 
 /* The GFF3 feature a located tract lies in and its longest modal length (N9: tjamd_gff3_read, tjamd_annotation_create and
  * its kin, tjamd_tract_features) are declared, with their timers, in tatajuba_features.h, which includes this header. */

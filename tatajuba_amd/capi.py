@@ -135,6 +135,10 @@ VARIANT_EXPORTS = ["tjamd_tract_variants", "tjamd_read_file_names"]
 # ... and include/tatajuba_features.h
 FEATURE_EXPORTS = ["tjamd_gff3_read", "tjamd_annotation_create", "tjamd_annotation_destroy", "tjamd_annotation_features", "tjamd_annotation_download",
                    "tjamd_tract_features", "tjamd_last_annotation_ms", "tjamd_last_tract_features_ms"]
+# ... and include/tatajuba_locate.h
+LOCATE_EXPORTS = ["tjamd_flank_edit_distance", "tjamd_reference_add_seeds", "tjamd_reference_has_seeds", "tjamd_locate_gapped",
+                  "tjamd_last_seed_order_ms", "tjamd_last_locate_gapped_ms"]
+MAX_SHIFT = 3                     # TJAMD_MAX_SHIFT
 
 
 def _share_hip_runtime_with_torch():
@@ -252,6 +256,13 @@ def lib():
     L.tjamd_last_reference_ms.restype = C.c_double; L.tjamd_last_reference_ms.argtypes = [C.c_void_p]
     L.tjamd_last_locate_ms.restype = C.c_double; L.tjamd_last_locate_ms.argtypes = [C.c_void_p]
     L.tjamd_last_located_tracts_ms.restype = C.c_double; L.tjamd_last_located_tracts_ms.argtypes = [C.c_void_p]
+    L.tjamd_flank_edit_distance.restype = C.c_int; L.tjamd_flank_edit_distance.argtypes = [C.c_uint64, C.c_uint64, C.c_int, C.c_int, C.c_int]
+    L.tjamd_reference_add_seeds.restype = C.c_long; L.tjamd_reference_add_seeds.argtypes = [C.c_void_p, C.c_void_p]
+    L.tjamd_reference_has_seeds.restype = C.c_int; L.tjamd_reference_has_seeds.argtypes = [C.c_void_p]
+    L.tjamd_locate_gapped.restype = C.c_long
+    L.tjamd_locate_gapped.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_long, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
+    L.tjamd_last_seed_order_ms.restype = C.c_double; L.tjamd_last_seed_order_ms.argtypes = [C.c_void_p]
+    L.tjamd_last_locate_gapped_ms.restype = C.c_double; L.tjamd_last_locate_gapped_ms.argtypes = [C.c_void_p]
     L.tjamd_tract_variants.restype = C.c_long
     L.tjamd_tract_variants.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_long, C.c_int, C.c_void_p, C.c_long, C.c_void_p,
                                        C.c_void_p, C.c_long, C.c_void_p, C.c_long, C.c_void_p]
@@ -467,6 +478,14 @@ class Comm:
     __del__ = close
 
 
+def flank_edit_distance(a, b, k, side, max_shift):
+    """tjamd_flank_edit_distance: the banded edit distance of two packed flanks, anchored at the tract (host arithmetic)"""
+    d = lib().tjamd_flank_edit_distance(int(a), int(b), k, side, max_shift)
+    if d < 0:
+        raise TatajubaAmdError(_err())
+    return int(d)
+
+
 class Reference:
     """tjamd_reference: the index of a genome's runs (contigs as a stream of reads, each followed by a newline), built on
     the counter's device with the counter's k"""
@@ -476,6 +495,17 @@ class Reference:
         self._h = lib().tjamd_reference_create(counter._h, buf.ctypes.data if len(buf) else None, len(buf))
         if not self._h:
             raise TatajubaAmdError(_err())
+
+    def add_seeds(self, counter):
+        """tjamd_reference_add_seeds: the seed order tjamd_locate_gapped needs (built once); -> number of entries"""
+        n = lib().tjamd_reference_add_seeds(counter._h, self._h)
+        if n < 0:
+            raise TatajubaAmdError(_err())
+        return int(n)
+
+    @property
+    def has_seeds(self):
+        return bool(lib().tjamd_reference_has_seeds(self._h))
 
     @property
     def n_entries(self):
@@ -713,6 +743,19 @@ class Counter:
 
     def last_located_tracts_ms(self):
         return lib().tjamd_last_located_tracts_ms(self._h)
+
+    def locate_gapped(self, ref, d_keys, n, max_edits, max_shift, d_loc, d_how=None):
+        """tjamd_locate_gapped on device pointers (ints): d_loc is in/out, d_how may be None; -> rows located by this call"""
+        got = lib().tjamd_locate_gapped(self._h, ref._h, d_keys, n, max_edits, max_shift, d_loc, d_how)
+        if got < 0:
+            raise TatajubaAmdError(_err())
+        return int(got)
+
+    def last_seed_order_ms(self):
+        return lib().tjamd_last_seed_order_ms(self._h)
+
+    def last_locate_gapped_ms(self):
+        return lib().tjamd_last_locate_gapped_ms(self._h)
 
     def last_tract_variants_ms(self):
         return lib().tjamd_last_tract_variants_ms(self._h)

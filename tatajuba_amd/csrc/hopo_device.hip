@@ -39,6 +39,7 @@
 #include "../../include/tatajuba_amd.h"
 #include "../../include/tatajuba_variants.h"
 #include "../../include/tatajuba_features.h"
+#include "../../include/tatajuba_locate.h"
 
 typedef unsigned long long u64;
 typedef unsigned int u32;
@@ -3868,7 +3869,7 @@ struct StageTimer
 };
 // the intervals of a counter: the last scan call (its partition kernels between the pieces included: tjamd_last_scan_ms takes
 // them out), finalise, the kernels of tjamd_merge_samples, tjamd_tract_stats, tjamd_union_tracts, tjamd_union_tract_stats
-enum { T_SCAN, T_FIN, T_MERGE, T_TRACT, T_UNION, T_UNION_STATS, T_REF, T_LOCATE, T_LOCATED_TRACTS, T_VARIANTS, T_ANNOTATION, T_TRACT_FEATURES, TJ_N_TIMERS };   // (T_REF to T_LOCATED_TRACTS: N7, T_VARIANTS: N8, the last two: N9, end of the file)
+enum { T_SCAN, T_FIN, T_MERGE, T_TRACT, T_UNION, T_UNION_STATS, T_REF, T_LOCATE, T_LOCATED_TRACTS, T_VARIANTS, T_ANNOTATION, T_TRACT_FEATURES, T_SEED_ORDER, T_LOCATE_GAPPED, TJ_N_TIMERS };   // (T_REF to T_LOCATED_TRACTS: N7, T_VARIANTS: N8, the next two: N9, end of the file; the last two: N10)
 
 struct tjamd_counter
 {
@@ -6492,6 +6493,8 @@ struct tjamd_reference
   RefEntry *entries = nullptr;          // ascending flat
   u64 *ord[2] = {nullptr, nullptr};     // [0]: primary = ctx0, secondary = ctx1; [1]: the other way round
   void *owned[4] = {nullptr, nullptr, nullptr, nullptr};
+  u64 *seed = nullptr;                  // N10 (tjamd_reference_add_seeds): primary = rev_k (ctx1), secondary = ctx0; a block of its own
+  bool has_seeds = false;
 };
 
 // byte classes of the index: 0-3 the base of an ACGTU byte (either case), 4 the contig delimiter, 5 anything else
@@ -6587,6 +6590,7 @@ extern "C" void tjamd_reference_destroy (tjamd_reference *ref)
   if (!ref) return;
   (void) hipSetDevice (ref->device);
   for (void *p : ref->owned) if (p) (void) hipFree (p);
+  if (ref->seed) (void) hipFree (ref->seed);
   delete ref;
 }
 
@@ -6783,6 +6787,240 @@ extern "C" long tjamd_locate (tjamd_counter *c, const tjamd_reference *ref, cons
   return (long) found;
 }
 extern "C" double tjamd_last_locate_ms (tjamd_counter *c) { return c ? c->timer[T_LOCATE].ms (c->device) : -1.0; }
+
+// ---- N10: the second pass of the lookup: flanks that differ from the genome by indels, or in both flanks -----------------
+// The reference maps context + tract with BWA, by edit distance over the whole string (src/hopo_counter.c:495-572), and allows
+// shifts of up to three bases per flank when it rescans (distance_between_context_kmer_pair_with_edit_shift, :81-113).
+// Here: a banded unit-cost edit distance per flank, anchored at the tract and free at the outer end, on the entries that
+// share the inner half of one flank with the row (the seed).  include/tatajuba_locate.h has the rule, DESIGN.md section 3.5,
+// N10, the order, the mapping and the measurements.
+
+#define LG_MAX_SHIFT TJAMD_MAX_SHIFT
+#define LG_INF       1000
+
+__host__ __device__ __forceinline__ u64 flank_mask (int k) { return (k >= 32) ? ~0ull : ((1ull << (2 * k)) - 1ull); }   // (no shift by 64)
+
+// the k bases of a packed flank in reverse order (no complement): base i goes to base k - 1 - i.  1 <= k <= 32.
+__host__ __device__ __forceinline__ u64 rev_k (u64 x, int k)
+{
+  x = ((x >> 2) & 0x3333333333333333ull) | ((x & 0x3333333333333333ull) << 2);
+  x = ((x >> 4) & 0x0F0F0F0F0F0F0F0Full) | ((x & 0x0F0F0F0F0F0F0F0Full) << 4);
+  return __builtin_bswap64 (x) >> (64 - 2 * k);
+}
+
+// d_B (q, r) of two inner-first flanks (inner base i at bits 2i, nothing above base k - 1): row i of the band holds
+// D[i][i - B ... i + B] in 2B + 1 registers (cell t is column j = i + t - B; every index below is a compile-time number once
+// the loops over t are unrolled).  win holds r[i - 1 - B ... i - 1 + B], the bases row i compares q[i - 1] with, base t at bits
+// 2t; it moves on by one base per row, so no shift reaches 64 bits at k = 32.  Columns beyond k only feed columns beyond k
+// and are left out at the end; columns below 0 are LG_INF.
+template <int B>
+__host__ __device__ __forceinline__ int flank_edit_distance (u64 q, u64 r, int k)
+{
+  constexpr int W = 2 * B + 1;
+  int prev[W], cur[W];
+#pragma unroll
+  for (int t = 0; t < W; t++) prev[t] = t >= B ? t - B : LG_INF;        // D[0][j] = j
+  u64 win = (r << (2 * B)) & ((1ull << (2 * W)) - 1ull);
+  int col = k <= B ? k : LG_INF;                                        // the last column, D[i][k] for i >= k - B: D[0][k] = k
+  for (int i = 1; i <= k; i++) {
+    const u32 qi = (u32) q & 3u;
+    q >>= 2;
+#pragma unroll
+    for (int t = 0; t < W; t++) {
+      const int j = i + t - B;
+      int v = prev[t] + (((u32) (win >> (2 * t)) & 3u) != qi ? 1 : 0);
+      if (t + 1 < W) v = min (v, prev[t + 1] + 1);
+      if (t > 0) v = min (v, cur[t - 1] + 1);
+      v = j < 0 ? LG_INF : (j == 0 ? i : v);
+      cur[t] = v;
+      col = j == k ? min (col, v) : col;
+    }
+#pragma unroll
+    for (int t = 0; t < W; t++) prev[t] = cur[t];
+    const int nb = i + B;                                               // the base that enters the window for row i + 1
+    win = (win >> 2) | ((nb < k ? (r >> (2 * nb)) & 3ull : 0ull) << (4 * B));
+  }
+  int best = col;                                                       // the last row: D[k][k - B ... k]
+#pragma unroll
+  for (int t = 0; t <= B; t++) best = min (best, prev[t]);
+  return best;
+}
+
+// the same for a caller on the host: the packed flanks as the index and the union rows hold them (side 0: ctx0, inner base
+// at the high end; side 1: ctx1, inner base at bit 0).  No device call: a CPU test runs the kernel's own arithmetic.
+extern "C" int tjamd_flank_edit_distance (uint64_t a, uint64_t b, int k, int side, int max_shift)
+{
+  static const char *fn = "tjamd_flank_edit_distance";
+  if (k < 1 || k > 32) return -set_err (TJAMD_ERR_ARG, "%s: k %d outside 1..32", fn, k);
+  if (side < 0 || side > 1) return -set_err (TJAMD_ERR_ARG, "%s: side %d outside 0..1", fn, side);
+  if (max_shift < 0 || max_shift > LG_MAX_SHIFT) return -set_err (TJAMD_ERR_ARG, "%s: max_shift %d outside 0..%d", fn, max_shift, LG_MAX_SHIFT);
+  u64 q = a & flank_mask (k), r = b & flank_mask (k);
+  if (side == 0) { q = rev_k (q, k); r = rev_k (r, k); }
+  switch (max_shift) {
+    case 0: return flank_edit_distance<0> (q, r, k);
+    case 1: return flank_edit_distance<1> (q, r, k);
+    case 2: return flank_edit_distance<2> (q, r, k);
+    default: return flank_edit_distance<3> (q, r, k);
+  }
+}
+
+// the unsorted records of the third order: (rev_k (ctx1), ctx0, word) -- the inner bases of ctx1 are its low bits, reversed
+// they are the high bits, and the entries that share them with a row are a contiguous range, as those of ctx0 are in ord[0]
+__global__ void ref_seed_kernel (const RefEntry *__restrict__ entries, long n, int k, u64 *__restrict__ rec)
+{
+  for (long x = blockIdx.x * (long) blockDim.x + threadIdx.x; x < n; x += (long) gridDim.x * blockDim.x) {
+    const u64 c0 = entries[x].ctx0, c1 = entries[x].ctx1;
+    rec[3 * x] = rev_k (c1, k); rec[3 * x + 1] = c0; rec[3 * x + 2] = (u64) (u32) entries[x].base | ((u64) x << LC_IDX_SHIFT);
+  }
+}
+
+extern "C" int tjamd_reference_has_seeds (const tjamd_reference *ref) { return ref && ref->has_seeds ? 1 : 0; }
+
+extern "C" long tjamd_reference_add_seeds (tjamd_counter *c, tjamd_reference *ref)
+{
+  static const char *fn = "tjamd_reference_add_seeds";
+  if (!c || !ref) return -set_err (TJAMD_ERR_ARG, "%s: null counter or reference", fn);
+  if (ref->k != c->k) return -set_err (TJAMD_ERR_ARG, "%s: the reference was built with k = %d, the counter has k = %d", fn, ref->k, c->k);
+  if (ref->device != c->device) return -set_err (TJAMD_ERR_ARG, "%s: the reference lives on device %d, the counter on device %d", fn, ref->device, c->device);
+  if (ref->has_seeds) return ref->n_entries;
+  if (hipSetDevice (c->device) != hipSuccess) return -set_err (TJAMD_ERR_HIP, "hipSetDevice failed");
+  c->timer[T_SEED_ORDER].timed = false;
+  const long n = ref->n_entries;
+  if (n == 0) { ref->has_seeds = true; return 0; }
+  const size_t bytes = (size_t) n * 24;
+  int rc = ensure (c->lc_work, bytes, c->stream);           // the sort's spare block
+  if (rc) return -rc;
+  void *block = nullptr;
+  if (hipMalloc (&block, bytes) != hipSuccess) { (void) hipGetLastError (); return -set_err (TJAMD_ERR_HIP, "%s: hipMalloc failed for %ld entries", fn, n); }
+  // the sort swaps its two blocks once per pass: start in the one that leaves the result in the reference's own
+  u64 *a = (key_passes (c->k) & 1) ? (u64 *) c->lc_work.p : (u64 *) block, *b = (key_passes (c->k) & 1) ? (u64 *) block : (u64 *) c->lc_work.p;
+  (void) c->timer[T_SEED_ORDER].begin (c->stream);
+  hipLaunchKernelGGL (ref_seed_kernel, dim3 (grid_for (n)), dim3 (256), 0, c->stream, (const RefEntry *) ref->entries, n, c->k, a);
+  if (hipGetLastError () != hipSuccess) { (void) hipFree (block); return -set_err (TJAMD_ERR_HIP, "%s: launch failed", fn); }
+  rc = radix_sort_records (c, a, b, n);
+  if (rc) { (void) hipStreamSynchronize (c->stream); (void) hipFree (block); return -rc; }
+  (void) c->timer[T_SEED_ORDER].end (c->stream);
+  if (hipStreamSynchronize (c->stream) != hipSuccess) {
+    const hipError_t e = hipGetLastError ();
+    (void) hipFree (block);
+    return -set_err (TJAMD_ERR_HIP, "%s: sort failed: %s", fn, hipGetErrorString (e));
+  }
+  if (a != (u64 *) block) {                                // (the parity of key_passes chose the starting block: cannot happen)
+    (void) hipFree (block);
+    return -set_err (TJAMD_ERR_STATE, "%s: the sorted order did not end in the reference's block after %d passes", fn, key_passes (c->k));
+  }
+  ref->seed = (u64 *) block; ref->has_seeds = true;
+  c->timer[T_SEED_ORDER].timed = true;
+  return n;
+}
+extern "C" double tjamd_last_seed_order_ms (tjamd_counter *c) { return c ? c->timer[T_SEED_ORDER].ms (c->device) : -1.0; }
+
+// ---- the gapped lookup ---------------------------------------------------------------------------------------------
+// Thread mapping: that of locate_kernel, for its reason (at k >= 12 nearly every range is short and the 64 lanes stay in
+// step; a long range costs its length over 64).  The two ranges of a row are the entries with its base and the inner h
+// bases of its ctx0 (in ord[0]) or of its ctx1 (in the seed order).  A lane runs both banded distances on each candidate;
+// 64 lanes on 64 candidates run the same k rows of the same band.
+
+// one record of order `side` against a row: both flanks inner-first (q0, q1: the row's; seed_mask: the inner h bases).
+// An entry that shares the row's ctx0 seed is counted in ord[0] only.  best = (edits << 32 | entry number), the smallest wins.
+template <int B>
+__device__ __forceinline__ void gapped_try (const u64 *__restrict__ ord, long i, int side, int k, u64 q0, u64 q1, u64 seed_mask, int max_edits, u64 &best, u32 &hits)
+{
+  const u64 p = ord[3 * i], s = ord[3 * i + 1];
+  const u64 r0 = rev_k (side ? s : p, k), r1 = side ? rev_k (p, k) : s;
+  if (side && ((r0 ^ q0) & seed_mask) == 0ull) return;
+  const int d = flank_edit_distance<B> (q0, r0, k) + flank_edit_distance<B> (q1, r1, k);
+  if (d <= max_edits) {
+    hits++;
+    const u64 cand = ((u64) d << 32) | ((ord[3 * i + 2] >> LC_IDX_SHIFT) & 0xFFFFFFFFull);
+    best = cand < best ? cand : best;
+  }
+}
+
+template <int B>
+__global__ __launch_bounds__ (256)
+void locate_gapped_kernel (const u64 *__restrict__ keys, long n, const u64 *__restrict__ ord0, const u64 *__restrict__ ords, long n_ent,
+                           const RefEntry *__restrict__ entries, int k, int max_edits, Location *loc, int *__restrict__ how, u32 *__restrict__ n_located)
+{
+  const int lane = threadIdx.x & 63;
+  const long stride = (long) gridDim.x * blockDim.x;
+  const int h = (k + 1) / 2, sh = 2 * (k - h);                          // (sh <= 32)
+  const u64 seed_mask = flank_mask (h), rest = (1ull << sh) - 1ull;
+  for (long q0 = blockIdx.x * (long) blockDim.x + (threadIdx.x & ~63); q0 < n; q0 += stride) {     // (uniform across a wavefront)
+    const long q = q0 + lane;
+    const bool active = q < n;
+    const bool todo = active && loc[q].flat < 0;                        // (a located row skips the searches, not the hand-offs)
+    u64 qc0 = 0, qc1 = 0; u32 qb = 0;
+    if (todo) { qc0 = keys[3 * q]; qc1 = keys[3 * q + 1]; qb = (u32) keys[3 * q + 2] & 3u; }
+    const u64 qi0 = rev_k (qc0, k), qi1 = qc1;                          // inner-first
+    u64 best = ~0ull; u32 hits = 0;
+#pragma unroll
+    for (int side = 0; side < 2; side++) {
+      const u64 *__restrict__ ord = side ? ords : ord0;
+      const u64 top = (side ? rev_k (qc1, k) : qc0) | rest, bottom = top & ~rest;     // every primary flank with the row's inner h bases
+      long lo = 0, hi = 0;
+      if (todo) { lo = ord_bound (ord, n_ent, qb, top, false); hi = ord_bound (ord, n_ent, qb, bottom, true); }
+      const bool mine = hi - lo <= LC_LANE_WALK;
+      if (mine) for (long i = lo; i < hi; i++) gapped_try<B> (ord, i, side, k, qi0, qi1, seed_mask, max_edits, best, hits);
+      u64 big = __ballot (!mine);
+      while (big) {                                     // the wavefront walks its long ranges together, one after the other
+        const int src = __ffsll ((long long) big) - 1;
+        big &= big - 1;
+        const long blo = __shfl (lo, src), bhi = __shfl (hi, src);
+        const u64 b0 = __shfl (qi0, src), b1 = __shfl (qi1, src);
+        u64 wb = ~0ull; u32 wh = 0;
+        for (long i = blo + lane; i < bhi; i += 64) gapped_try<B> (ord, i, side, k, b0, b1, seed_mask, max_edits, wb, wh);
+#pragma unroll
+        for (int o = 1; o < 64; o <<= 1) { const u64 ob = __shfl_xor (wb, o); wb = ob < wb ? ob : wb; wh += __shfl_xor (wh, o); }
+        if (lane == src) { best = wb < best ? wb : best; hits += wh; }
+      }
+    }
+    if (todo && hits) {
+      const RefEntry e = entries[best & 0xFFFFFFFFull];
+      loc[q] = Location {e.flat, e.contig, e.pos, e.length, (int) (best >> 32), e.neg_strand, (int) hits};
+    }
+    if (active && how) how[q] = !todo ? 0 : (hits ? 1 : -1);
+    const u64 found = __ballot (todo && hits);
+    if (lane == 0 && found) atomicAdd (n_located, (u32) __popcll (found));
+  }
+}
+
+extern "C" long tjamd_locate_gapped (tjamd_counter *c, const tjamd_reference *ref, const void *d_keys, long n, int max_edits, int max_shift,
+                                     tjamd_location *d_loc, int *d_how)
+{
+  static const char *fn = "tjamd_locate_gapped";
+  // (what can be refused without reading the counter or the reference comes first)
+  if (!c || !ref) return -set_err (TJAMD_ERR_ARG, "%s: null counter or reference", fn);
+  if (max_shift < 0 || max_shift > LG_MAX_SHIFT) return -set_err (TJAMD_ERR_ARG, "%s: max_shift %d outside 0..%d", fn, max_shift, LG_MAX_SHIFT);
+  if (max_edits < 0) return -set_err (TJAMD_ERR_ARG, "%s: max_edits %d outside 0..k", fn, max_edits);
+  if (n < 0) return -set_err (TJAMD_ERR_ARG, "%s: n %ld < 0", fn, n);
+  if (n >= (1l << 31)) return -set_err (TJAMD_ERR_CAPACITY, "%s: %ld rows", fn, n);
+  if (n > 0 && (!d_keys || !d_loc)) return -set_err (TJAMD_ERR_ARG, "%s: null key or location buffer", fn);
+  if (ref->k != c->k) return -set_err (TJAMD_ERR_ARG, "%s: the reference was built with k = %d, the counter has k = %d", fn, ref->k, c->k);
+  if (ref->device != c->device) return -set_err (TJAMD_ERR_ARG, "%s: the reference lives on device %d, the counter on device %d", fn, ref->device, c->device);
+  if (!ref->has_seeds) return -set_err (TJAMD_ERR_ARG, "%s: the reference has no seed order (tjamd_reference_add_seeds comes first)", fn);
+  if (max_edits > c->k) return -set_err (TJAMD_ERR_ARG, "%s: max_edits %d outside 0..%d", fn, max_edits, c->k);
+  if (hipSetDevice (c->device) != hipSuccess) return -set_err (TJAMD_ERR_HIP, "hipSetDevice failed");
+  c->timer[T_LOCATE_GAPPED].timed = false;
+  if (n == 0) return 0;
+  int rc = ensure (c->lc_work, 256, c->stream);
+  if (rc) return -rc;
+  u32 *n_located = (u32 *) c->lc_work.p;
+  if (hipMemsetAsync (n_located, 0, 4, c->stream) != hipSuccess) return -set_err (TJAMD_ERR_HIP, "%s: memset failed", fn);
+  (void) c->timer[T_LOCATE_GAPPED].begin (c->stream);
+#define LG_LAUNCH(B) hipLaunchKernelGGL (locate_gapped_kernel<B>, dim3 (grid_for (n)), dim3 (256), 0, c->stream, (const u64 *) d_keys, n, (const u64 *) ref->ord[0], \
+                                         (const u64 *) ref->seed, ref->n_entries, (const RefEntry *) ref->entries, c->k, max_edits, (Location *) d_loc, d_how, n_located)
+  switch (max_shift) { case 0: LG_LAUNCH (0); break; case 1: LG_LAUNCH (1); break; case 2: LG_LAUNCH (2); break; default: LG_LAUNCH (3); break; }
+#undef LG_LAUNCH
+  if (hipGetLastError () != hipSuccess) return -set_err (TJAMD_ERR_HIP, "%s: launch failed", fn);
+  (void) c->timer[T_LOCATE_GAPPED].end (c->stream);
+  u32 found = 0;
+  if (hipMemcpyAsync (&found, n_located, 4, hipMemcpyDeviceToHost, c->stream) != hipSuccess || hipStreamSynchronize (c->stream) != hipSuccess)
+    return -set_err (TJAMD_ERR_HIP, "%s: lookup failed: %s", fn, hipGetErrorString (hipGetLastError ()));
+  c->timer[T_LOCATE_GAPPED].timed = true;
+  return (long) found;
+}
+extern "C" double tjamd_last_locate_gapped_ms (tjamd_counter *c) { return c ? c->timer[T_LOCATE_GAPPED].ms (c->device) : -1.0; }
 
 // ---- tracts by location ------------------------------------------------------------------------------------------
 
