@@ -387,6 +387,9 @@ long tjamd_located_tracts (tjamd_counter *c, const void *d_keys, const void *d_c
 /* The GFF3 feature a located tract lies in and its longest modal length (N9: tjamd_gff3_read, tjamd_annotation_create and
  * its kin, tjamd_tract_features) are declared, with their timers, in tatajuba_features.h, which includes this header. */
 
+/* The coding effect of a variant record (N11: tjamd_translate, tjamd_gff3_read_phase, tjamd_coding_create and its kin,
+ * tjamd_variant_effects) is declared, with its timers, in tatajuba_effects.h, which includes this header. */
+
 /* release the calling thread's shared device contexts of the synchronous string scans (update_hopo_counter_from_seq on a
  * counter that never read a file, tjamd_scan_windows) now; they are released by themselves when the thread ends */
 void tjamd_thread_cleanup (void);

@@ -52,6 +52,13 @@ FEATURE_DTYPE = np.dtype([("contig", "<i4"), ("start", "<i4"), ("end", "<i4"), (
 assert FEATURE_DTYPE.itemsize == 32
 TRACT_FEATURE_DTYPE = np.dtype([("feature", "<i4"), ("max_length", "<i4")])
 assert TRACT_FEATURE_DTYPE.itemsize == 8
+# tjamd_cds and tjamd_effect (include/tatajuba_effects.h): where a feature's protein ends; what a variant record does to it
+CDS_DTYPE = np.dtype([("aa_len", "<i4"), ("has_stop", "<i4"), ("n_codons", "<i4"), ("phase", "<i4")])
+assert CDS_DTYPE.itemsize == 16
+EFFECT_DTYPE = np.dtype([("feature", "<i4"), ("cls", "<i4"), ("cds_pos", "<i4"), ("first_diff", "<i4"), ("ref_aa_len", "<i4"), ("alt_aa_len", "<i4"),
+                         ("flags", "<i4"), ("pad", "<i4"), ("ref_aa", "<u8"), ("alt_aa", "<u8")])
+assert EFFECT_DTYPE.itemsize == 48
+EFFECT_CLASSES = ["NONE", "BOUNDARY", "IDENTICAL", "INFRAME", "FRAMESHIFT"]      # TJAMD_EFFECT_*
 
 
 class TatajubaAmdError(RuntimeError):
@@ -138,6 +145,9 @@ FEATURE_EXPORTS = ["tjamd_gff3_read", "tjamd_annotation_create", "tjamd_annotati
 # ... and include/tatajuba_locate.h
 LOCATE_EXPORTS = ["tjamd_flank_edit_distance", "tjamd_reference_add_seeds", "tjamd_reference_has_seeds", "tjamd_locate_gapped",
                   "tjamd_last_seed_order_ms", "tjamd_last_locate_gapped_ms"]
+# ... and include/tatajuba_effects.h
+EFFECT_EXPORTS = ["tjamd_translate", "tjamd_gff3_read_phase", "tjamd_coding_create", "tjamd_coding_destroy", "tjamd_coding_features", "tjamd_coding_download",
+                  "tjamd_variant_effects", "tjamd_last_coding_ms", "tjamd_last_variant_effects_ms"]
 MAX_SHIFT = 3                     # TJAMD_MAX_SHIFT
 
 
@@ -279,6 +289,16 @@ def lib():
     L.tjamd_tract_features.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_long, C.c_int, C.c_void_p, C.c_long, C.c_void_p, C.c_void_p]
     L.tjamd_last_annotation_ms.restype = C.c_double; L.tjamd_last_annotation_ms.argtypes = [C.c_void_p]
     L.tjamd_last_tract_features_ms.restype = C.c_double; L.tjamd_last_tract_features_ms.argtypes = [C.c_void_p]
+    L.tjamd_translate.restype = C.c_long; L.tjamd_translate.argtypes = [C.c_char_p, C.c_long, C.c_int, C.c_void_p, C.c_long]
+    L.tjamd_gff3_read_phase.restype = C.c_long; L.tjamd_gff3_read_phase.argtypes = [C.c_char_p, C.c_char_p, C.c_long, C.c_void_p, C.c_long]
+    L.tjamd_coding_create.restype = C.c_void_p; L.tjamd_coding_create.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_long, C.c_void_p]
+    L.tjamd_coding_destroy.restype = None; L.tjamd_coding_destroy.argtypes = [C.c_void_p]
+    L.tjamd_coding_features.restype = C.c_long; L.tjamd_coding_features.argtypes = [C.c_void_p]
+    L.tjamd_coding_download.restype = C.c_long; L.tjamd_coding_download.argtypes = [C.c_void_p, C.c_void_p, C.c_long]
+    L.tjamd_variant_effects.restype = C.c_long
+    L.tjamd_variant_effects.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_long, C.c_void_p, C.c_long, C.c_void_p]
+    L.tjamd_last_coding_ms.restype = C.c_double; L.tjamd_last_coding_ms.argtypes = [C.c_void_p]
+    L.tjamd_last_variant_effects_ms.restype = C.c_double; L.tjamd_last_variant_effects_ms.argtypes = [C.c_void_p]
     L.tjamd_group_contexts.restype = C.c_long
     L.tjamd_group_contexts.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_long]
     L.new_genomic_context_list.restype = C.POINTER(GenomicContextListStruct); L.new_genomic_context_list.argtypes = [P]
@@ -387,6 +407,30 @@ def read_gff3(path, names):
     assert got == n
     read_gff3.last_skipped = sk.value
     return out, strings[: nb.value].tobytes()
+
+
+def read_gff3_phase(path, names):
+    """Column 8 of the feature lines read_gff3 keeps, in its order -> int8 array (0, 1, 2; -1 for '.' or anything else).
+    Host-only."""
+    blob = b"".join((n if isinstance(n, bytes) else str(n).encode()) + b"\n" for n in names)
+    n = lib().tjamd_gff3_read_phase(os.fsencode(path), blob, len(names), None, 0)
+    if n < 0:
+        raise FileNotFoundError(path)
+    out = np.zeros(n, dtype=np.int8)
+    got = lib().tjamd_gff3_read_phase(os.fsencode(path), blob, len(names), out.ctypes.data if n else None, n)
+    assert got == n
+    return out
+
+
+def translate(dna, reverse=False):
+    """tjamd_translate: the amino acids of a DNA string's whole codons (of its reverse complement with reverse), no stop
+    handling -> str.  Host-only."""
+    b = dna if isinstance(dna, bytes) else str(dna).encode()
+    out = np.zeros(max(len(b) // 3, 1), dtype=np.uint8)
+    n = lib().tjamd_translate(b, len(b), 1 if reverse else 0, out.ctypes.data, len(b) // 3)
+    if n < 0:
+        raise TatajubaAmdError(_err())
+    return out[:n].tobytes().decode()
 
 
 def gff3_string(strings, off):
@@ -557,6 +601,40 @@ class Annotation:
     def close(self):
         if getattr(self, "_h", None):
             lib().tjamd_annotation_destroy(self._h)
+            self._h = None
+
+    __del__ = close
+
+
+class Coding:
+    """tjamd_coding: the genome's bases (the stream a Reference was built from) and the coding features of a GFF3 file (a
+    FEATURE_DTYPE array, with the phases read_gff3_phase gives, or None) as a table on the counter's device"""
+
+    def __init__(self, counter, stream, features, phase=None):
+        buf = np.frombuffer(bytes(stream), dtype=np.uint8)
+        f = np.ascontiguousarray(features, dtype=FEATURE_DTYPE)
+        ph = None if phase is None else np.ascontiguousarray(phase, dtype=np.int8)
+        assert ph is None or len(ph) == len(f)
+        self._h = lib().tjamd_coding_create(counter._h, buf.ctypes.data if len(buf) else None, len(buf), f.ctypes.data if len(f) else None, len(f),
+                                            ph.ctypes.data if ph is not None and len(ph) else None)
+        if not self._h:
+            raise TatajubaAmdError(_err())
+
+    @property
+    def n_features(self):
+        return int(lib().tjamd_coding_features(self._h))
+
+    def download(self):
+        """a CDS_DTYPE record per feature: -1 everywhere for a feature that is not coding"""
+        out = np.zeros(self.n_features, dtype=CDS_DTYPE)
+        n = lib().tjamd_coding_download(self._h, out.ctypes.data if len(out) else None, len(out))
+        if n < 0:
+            raise TatajubaAmdError(_err())
+        return out[:n]
+
+    def close(self):
+        if getattr(self, "_h", None):
+            lib().tjamd_coding_destroy(self._h)
             self._h = None
 
     __del__ = close
@@ -765,6 +843,17 @@ class Counter:
 
     def last_tract_features_ms(self):
         return lib().tjamd_last_tract_features_ms(self._h)
+
+    def variant_effects(self, coding, d_variants, n, d_out, d_tract_feat=None, n_tracts=0):
+        """tjamd_variant_effects on device pointers: n VARIANT_DTYPE records -> n EFFECT_DTYPE records at d_out; d_tract_feat:
+        the TRACT_FEATURE_DTYPE records of tjamd_tract_features (None: no record has a feature).  -> n"""
+        return self._chkn(lib().tjamd_variant_effects(self._h, coding._h, d_variants, n, d_tract_feat, n_tracts, d_out))
+
+    def last_coding_ms(self):
+        return lib().tjamd_last_coding_ms(self._h)
+
+    def last_variant_effects_ms(self):
+        return lib().tjamd_last_variant_effects_ms(self._h)
 
     def uses_log(self):
         lib().tjamd_counter_uses_log.restype = C.c_int

@@ -125,9 +125,10 @@ tjg_equals_nocase (const char *s, size_t len, const char *word)
   return 1;
 }
 
-/* one pass over the lines: counts always; writes records and strings if out != NULL */
+/* one pass over the lines: counts always; writes records and strings if out != NULL, and column 8 of every kept line
+ * (0, 1, 2; -1 for anything else) if phase != NULL */
 static long
-tjg_parse (const tjg_text *t, const tjg_name *names, long n_names, tjamd_feature *out, char *strings, long *bytes_out, long *skipped_out)
+tjg_parse (const tjg_text *t, const tjg_name *names, long n_names, tjamd_feature *out, char *strings, signed char *phase, long *bytes_out, long *skipped_out)
 {
   long n = 0, bytes = 0, skipped = 0, line_no = 0;
   size_t at = 0;
@@ -171,6 +172,7 @@ tjg_parse (const tjg_text *t, const tjg_name *names, long n_names, tjamd_feature
         strings[f.id_off + (long) id_len] = '\0';
         out[n] = f;
       }
+      if (phase) phase[n] = (signed char) ((TJG_LEN (7) == 1 && col[7][0] >= '0' && col[7][0] <= '2') ? col[7][0] - '0' : -1);
 #undef TJG_LEN
       bytes += (long) type_len + 1 + (long) id_len + 1;
       n++;
@@ -180,20 +182,20 @@ tjg_parse (const tjg_text *t, const tjg_name *names, long n_names, tjamd_feature
   return n;
 }
 
-long
-tjg_read (const char *path, const char *contig_names, long n_contigs, tjamd_feature *out, long capacity,
-          char *strings, long strings_capacity, long *strings_bytes, long *n_skipped)
+/* the file's text and the sorted names; 0, or -1 if the file cannot be opened or is damaged */
+static int
+tjg_open (const char *path, const char *contig_names, long n_contigs, tjg_text *text, tjg_name **names_out, long *n_names_out)
 {
-  tjg_text raw, text;
+  tjg_text raw;
   tjg_name *names = NULL;
-  long n, bytes = 0, skipped = 0, i, n_names = 0;
+  long i, n_names = 0;
   const char *p = contig_names;
   if (!path || tjg_load (path, &raw)) return -1;
   if (raw.n >= 2 && raw.p[0] == 0x1f && raw.p[1] == 0x8b) {
-    const int rc = tjg_gunzip (&raw, &text);
+    const int rc = tjg_gunzip (&raw, text);
     free (raw.p);
     if (rc) return -1;
-  } else text = raw;
+  } else *text = raw;
   if (n_contigs > 0 && contig_names) names = (tjg_name *) malloc ((size_t) n_contigs * sizeof (tjg_name));
   for (i = 0; names && i < n_contigs; i++) {
     const char *e = p;
@@ -202,11 +204,37 @@ tjg_read (const char *path, const char *contig_names, long n_contigs, tjamd_feat
     n_names++; p = e + 1;
   }
   if (names) qsort (names, (size_t) n_names, sizeof (tjg_name), tjg_name_cmp);
-  n = tjg_parse (&text, names, n_names, NULL, NULL, &bytes, &skipped);
+  *names_out = names; *n_names_out = n_names;
+  return 0;
+}
+
+long
+tjg_read (const char *path, const char *contig_names, long n_contigs, tjamd_feature *out, long capacity,
+          char *strings, long strings_capacity, long *strings_bytes, long *n_skipped)
+{
+  tjg_text text;
+  tjg_name *names = NULL;
+  long n, bytes = 0, skipped = 0, n_names = 0;
+  if (tjg_open (path, contig_names, n_contigs, &text, &names, &n_names)) return -1;
+  n = tjg_parse (&text, names, n_names, NULL, NULL, NULL, &bytes, &skipped);
   if (bytes >= 0x7fffffffl) n = -1;                     /* (the offsets are ints) */
-  else if (out && strings && n <= capacity && bytes <= strings_capacity) (void) tjg_parse (&text, names, n_names, out, strings, &bytes, &skipped);
+  else if (out && strings && n <= capacity && bytes <= strings_capacity) (void) tjg_parse (&text, names, n_names, out, strings, NULL, &bytes, &skipped);
   free (names); free (text.p);
   if (strings_bytes) *strings_bytes = bytes;
   if (n_skipped) *n_skipped = skipped;
+  return n;
+}
+
+long
+tjg_read_phase (const char *path, const char *contig_names, long n_contigs, signed char *out, long capacity)
+{
+  tjg_text text;
+  tjg_name *names = NULL;
+  long n, bytes = 0, skipped = 0, n_names = 0;
+  if (tjg_open (path, contig_names, n_contigs, &text, &names, &n_names)) return -1;
+  n = tjg_parse (&text, names, n_names, NULL, NULL, NULL, &bytes, &skipped);
+  if (bytes >= 0x7fffffffl) n = -1;                     /* (what tjg_read refuses) */
+  else if (out && n <= capacity) (void) tjg_parse (&text, names, n_names, NULL, NULL, out, &bytes, &skipped);
+  free (names); free (text.p);
   return n;
 }

@@ -8,4 +8,7 @@
 long tjg_read (const char *path, const char *contig_names, long n_contigs, tjamd_feature *out, long capacity,
                char *strings, long strings_capacity, long *strings_bytes, long *n_skipped);
 
+/* what tjamd_gff3_read_phase (include/tatajuba_effects.h) returns and writes: column 8 of the lines tjg_read keeps */
+long tjg_read_phase (const char *path, const char *contig_names, long n_contigs, signed char *out, long capacity);
+
 #endif

@@ -39,6 +39,7 @@
 #include "../../include/tatajuba_amd.h"
 #include "../../include/tatajuba_variants.h"
 #include "../../include/tatajuba_features.h"
+#include "../../include/tatajuba_effects.h"
 #include "../../include/tatajuba_locate.h"
 
 typedef unsigned long long u64;
@@ -3869,7 +3870,7 @@ struct StageTimer
 };
 // the intervals of a counter: the last scan call (its partition kernels between the pieces included: tjamd_last_scan_ms takes
 // them out), finalise, the kernels of tjamd_merge_samples, tjamd_tract_stats, tjamd_union_tracts, tjamd_union_tract_stats
-enum { T_SCAN, T_FIN, T_MERGE, T_TRACT, T_UNION, T_UNION_STATS, T_REF, T_LOCATE, T_LOCATED_TRACTS, T_VARIANTS, T_ANNOTATION, T_TRACT_FEATURES, T_SEED_ORDER, T_LOCATE_GAPPED, TJ_N_TIMERS };   // (T_REF to T_LOCATED_TRACTS: N7, T_VARIANTS: N8, the next two: N9, end of the file; the last two: N10)
+enum { T_SCAN, T_FIN, T_MERGE, T_TRACT, T_UNION, T_UNION_STATS, T_REF, T_LOCATE, T_LOCATED_TRACTS, T_VARIANTS, T_ANNOTATION, T_TRACT_FEATURES, T_SEED_ORDER, T_LOCATE_GAPPED, T_CODING, T_VARIANT_EFFECTS, TJ_N_TIMERS };   // (T_REF to T_LOCATED_TRACTS: N7, T_VARIANTS: N8, the next two: N9; then two of N10; the last two: N11, end of the file)
 
 struct tjamd_counter
 {
@@ -7735,3 +7736,401 @@ extern "C" long tjamd_tract_features (tjamd_counter *c, const tjamd_annotation *
   return n_tracts;
 }
 extern "C" double tjamd_last_tract_features_ms (tjamd_counter *c) { return c ? c->timer[T_TRACT_FEATURES].ms (c->device) : -1.0; }
+
+// ---- N11: the coding effect of a variant record ---------------------------------------------------------------------------
+// The rule is in include/tatajuba_effects.h.  The table (tjamd_coding) keeps the genome as one code per byte, the contig
+// starts and one row per feature: the clipped span and, for a coding feature, where its protein ends.  The lookup
+// (variant_effects_kernel) classifies a record by translating the reference and the alternative sequence from the edit's codon
+// on.  Thread mapping of both kernels, as in locate_kernel and an_paint_kernel: the serial part of one item (a CDS's scan for
+// its stop, a record's walk to the alternative's stop) belongs to the whole wavefront, 64 consecutive codons per step, so
+// its time is the item's length over 64 and not one lane's walk while 63 wait.  DESIGN.md section 3.5, N11.
+
+struct Cds { int aa_len, has_stop, n_codons, phase; };
+static_assert (sizeof (Cds) == 16 && sizeof (Cds) == sizeof (tjamd_cds), "cds layout");
+struct Effect { int feature, cls, cds_pos, first_diff, ref_aa_len, alt_aa_len, flags, pad; u64 ref_aa, alt_aa; };
+static_assert (sizeof (Effect) == 48 && sizeof (Effect) == sizeof (tjamd_effect), "effect layout");
+// a feature's row: its tjamd_cds, then the span as the lookup needs it (start is the 0-based S, len the clipped length)
+struct CodRow { Cds cds; int start, len, contig, strand; };
+static_assert (sizeof (CodRow) == 32, "coding row layout");
+
+#define CD_MAX_FEATURES (1l << 30)
+#define CD_STOPS 0x0105000000000000ull  // bit i: codon index i is a stop (TAA = 48, TAG = 50, TGA = 56)
+
+// the code of a base: A C G T/U in either case are 0 to 3, every other byte is 4
+__host__ __device__ __forceinline__ u32 base_code5 (u32 b)
+{
+  const u32 l = b | 0x20u;
+  return l == 'a' ? 0u : l == 'c' ? 1u : l == 'g' ? 2u : (l == 't' || l == 'u') ? 3u : 4u;
+}
+__host__ __device__ __forceinline__ u32 code_complement (u32 c) { return c < 4u ? 3u - c : 4u; }
+
+// The standard genetic code by codon index b0 << 4 | b1 << 2 | b2 (A, C, G, T = 0 .. 3), written out from its definition:
+// third-base families (ACx T, CCx P, CGx R, CTx L, GCx A, GGx G, GTx V, TCx S), the purine / pyrimidine pairs (AAr K, AAy N, AGr
+// R, AGy S, CAr Q, CAy H, GAr E, GAy D, TAy Y, TGy C, TTr L, TTy F), ATA ATC ATT I, ATG M, TGG W, and the stops TAA TAG TGA.
+__host__ __device__ __forceinline__ char aa_table_byte (u32 i)
+{
+  return "KNKNTTTTRSRSIIMI" "QHQHPPPPRRRRLLLL" "EDEDAAAAGGGGVVVV" "*Y*YSSSS*CWCLFLF"[i & 63u];
+}
+// the amino acid of three codes; tab holds the 64 bytes of aa_table_byte (on the device a copy in LDS: the lanes of a
+// wavefront index it apart).  The one routine of tjamd_translate and of the kernels.
+__host__ __device__ __forceinline__ u32 amino_acid (const char *tab, u32 b0, u32 b1, u32 b2)
+{
+  return (b0 | b1 | b2) > 3u ? (u32) 'X' : (u32) (unsigned char) tab[(b0 << 4) | (b1 << 2) | b2];
+}
+__host__ __device__ __forceinline__ bool codon_is_stop (u32 b0, u32 b1, u32 b2)
+{
+  return (b0 | b1 | b2) <= 3u && ((CD_STOPS >> ((b0 << 4) | (b1 << 2) | b2)) & 1ull);
+}
+
+extern "C" long tjamd_translate (const char *dna, long n, int reverse, char *out, long capacity)
+{
+  static const char *fn = "tjamd_translate";
+  if (n < 0) return -set_err (TJAMD_ERR_ARG, "%s: n %ld < 0", fn, n);
+  if (n > 0 && !dna) return -set_err (TJAMD_ERR_ARG, "%s: null dna", fn);
+  const long na = n / 3;
+  if (capacity < na) return na;
+  if (na > 0 && !out) return -set_err (TJAMD_ERR_ARG, "%s: null output buffer", fn);
+  char tab[64];
+  for (u32 i = 0; i < 64u; i++) tab[i] = aa_table_byte (i);
+  auto code = [&] (long j) -> u32 { return reverse ? code_complement (base_code5 ((unsigned char) dna[n - 1 - j])) : base_code5 ((unsigned char) dna[j]); };
+  for (long i = 0; i < na; i++) out[i] = (char) amino_acid (tab, code (3 * i), code (3 * i + 1), code (3 * i + 2));
+  return na;
+}
+
+struct tjamd_coding
+{
+  int device = 0;
+  long n_features = 0, n_contigs = 0, n_bytes = 0;
+  uint8_t *codes = nullptr;             // one code per byte of the stream (a delimiter is a 4 like any other byte that is no base)
+  u32 *cstart = nullptr;                // [n_contigs + 1]: contig c begins at cstart[c] and is cstart[c + 1] - 1 - cstart[c] long
+  CodRow *rows = nullptr;               // [n_features]
+};
+
+// one code per byte; the delimiters flagged for the scan that numbers the contigs
+__global__ void cd_code_kernel (const uint8_t *__restrict__ seq, long n, uint8_t *__restrict__ codes, u32 *__restrict__ nlflag)
+{
+  for (long i = blockIdx.x * (long) blockDim.x + threadIdx.x; i < n; i += (long) gridDim.x * blockDim.x) {
+    const u32 b = seq[i];
+    codes[i] = (uint8_t) base_code5 (b);
+    nlflag[i] = b == '\n' ? 1u : 0u;
+  }
+}
+
+// cstart[0] = 0; behind the c-th delimiter begins contig c; a last contig without a delimiter ends as if one stood at n
+__global__ void cd_cstart_kernel (const uint8_t *__restrict__ seq, long n, const u32 *__restrict__ nlflag, const u32 *__restrict__ nlex, u32 *__restrict__ cstart)
+{
+  for (long i = blockIdx.x * (long) blockDim.x + threadIdx.x; i < n; i += (long) gridDim.x * blockDim.x) {
+    if (i == 0) cstart[0] = 0u;
+    if (nlflag[i]) cstart[nlex[i] + 1u] = (u32) i + 1u;
+    else if (i == n - 1) cstart[nlex[i] + 1u] = (u32) n + 1u;
+  }
+}
+
+// CDS-oriented base j of a span of len codes that begins at g: the span on strand 0, its reverse complement on strand 1
+__device__ __forceinline__ u32 span_code (const uint8_t *__restrict__ g, long len, int strand, long j)
+{
+  return strand ? code_complement (g[len - 1 - j]) : (u32) g[j];
+}
+
+// One wavefront per feature.  A coding feature: 64 codons per step, lane l on codon 64 * step + l (192 consecutive bytes a
+// step), a ballot of "is a stop" whose lowest bit is the first stop; the wavefront leaves at the first step that has one.
+__global__ __launch_bounds__ (256)
+void cds_scan_kernel (const uint8_t *__restrict__ codes, const u32 *__restrict__ cstart, const Feature *__restrict__ f, const signed char *__restrict__ phase,
+                      long n, CodRow *__restrict__ rows)
+{
+  const int lane = threadIdx.x & 63;
+  const long n_waves = (long) gridDim.x * (blockDim.x >> 6);
+  for (long i = blockIdx.x * (long) (blockDim.x >> 6) + (threadIdx.x >> 6); i < n; i += n_waves) {     // (uniform across a wavefront)
+    const Feature x = f[i];
+    if (x.cls != TJAMD_FEATURE_CDS || (x.strand != 0 && x.strand != 1)) {
+      if (lane == 0) rows[i] = CodRow {Cds {-1, -1, -1, -1}, x.start - 1, 0, x.contig, x.strand};
+      continue;
+    }
+    const long c0 = cstart[x.contig], clen = (long) cstart[x.contig + 1] - 1 - c0;
+    const long S = (long) x.start - 1, E = min ((long) x.end, clen) - 1, len = max (E - S + 1, 0l);
+    int ph = phase ? (int) phase[i] : 0;
+    if (ph != 1 && ph != 2) ph = 0;
+    const long nc = max (len - ph, 0l) / 3;
+    const uint8_t *g = codes + c0 + S;                  // (read only inside [0, len))
+    long first_stop = -1;
+    for (long at = 0; at < nc; at += 64) {
+      const long cdn = at + lane;
+      bool stop = false;
+      if (cdn < nc) {
+        const long j = 3 * cdn + ph;
+        stop = codon_is_stop (span_code (g, len, x.strand, j), span_code (g, len, x.strand, j + 1), span_code (g, len, x.strand, j + 2));
+      }
+      const u64 m = __ballot (stop);
+      if (m) { first_stop = at + __ffsll ((long long) m) - 1; break; }
+    }
+    if (lane == 0) rows[i] = CodRow {Cds {(int) (first_stop >= 0 ? first_stop : nc), first_stop >= 0 ? 1 : 0, (int) nc, ph}, (int) S, (int) len, x.contig, x.strand};
+  }
+}
+
+extern "C" void tjamd_coding_destroy (tjamd_coding *cod)
+{
+  if (!cod) return;
+  (void) hipSetDevice (cod->device);
+  if (cod->codes) (void) hipFree (cod->codes);
+  if (cod->cstart) (void) hipFree (cod->cstart);
+  if (cod->rows) (void) hipFree (cod->rows);
+  delete cod;
+}
+
+extern "C" tjamd_coding *tjamd_coding_create (tjamd_counter *c, const void *h_stream, size_t n_bytes,
+                                              const tjamd_feature *h_features, long n_features, const signed char *h_phase)
+{
+  static const char *fn = "tjamd_coding_create";
+  long n_contigs = 0;
+  auto refused = [&] () -> int {                        // the checks that read no handle: the caller's host buffers, then the device
+    if (!c) return set_err (TJAMD_ERR_ARG, "%s: null counter", fn);
+    if (n_bytes && !h_stream) return set_err (TJAMD_ERR_ARG, "%s: null stream", fn);
+    if (n_bytes >= (size_t) 1 << 31) return set_err (TJAMD_ERR_CAPACITY, "%s: a stream of %zu bytes (positions are 32-bit)", fn, n_bytes);
+    if (n_features < 0 || (n_features > 0 && !h_features)) return set_err (TJAMD_ERR_ARG, "%s: %ld features with %s buffer", fn, n_features, h_features ? "a" : "a null");
+    if (n_features > CD_MAX_FEATURES) return set_err (TJAMD_ERR_ARG, "%s: %ld features, more than 2^30", fn, n_features);
+    const char *s = (const char *) h_stream;
+    for (size_t at = 0; at < n_bytes; n_contigs++) {
+      const char *nl = (const char *) memchr (s + at, '\n', n_bytes - at);
+      at = nl ? (size_t) (nl - s) + 1 : n_bytes;
+    }
+    for (long i = 0; i < n_features; i++) {
+      const tjamd_feature &x = h_features[i];
+      if (x.contig < 0 || (long) x.contig >= n_contigs) return set_err (TJAMD_ERR_ARG, "%s: feature %ld: contig %d outside [0, %ld)", fn, i, x.contig, n_contigs);
+      if (x.start < 1) return set_err (TJAMD_ERR_ARG, "%s: feature %ld: start %d < 1", fn, i, x.start);
+      if (x.end < x.start) return set_err (TJAMD_ERR_ARG, "%s: feature %ld: end %d < start %d", fn, i, x.end, x.start);
+    }
+    if (tjamd_device_count () <= 0) return set_err (TJAMD_ERR_NO_DEVICE, "%s: TJAMD_ERR_NO_DEVICE: no HIP device visible (the table is built on the device; no CPU fallback)", fn);
+    return TJAMD_OK;
+  };
+  const int bad = refused ();
+  if (c && tjamd_device_count () > 0) c->timer[T_CODING].timed = false;   // a refused call leaves no timing behind (without a device there is no counter)
+  if (bad) return NULL;
+  HIPCHK_NULL (hipSetDevice (c->device));
+  tjamd_coding *cod = new tjamd_coding ();
+  cod->device = c->device; cod->n_features = n_features; cod->n_contigs = n_contigs; cod->n_bytes = (long) n_bytes;
+  const long n = (long) n_bytes, nf = n_features;
+#define CD_FAIL(...) do { set_err (__VA_ARGS__); tjamd_coding_destroy (cod); return NULL; } while (0)
+  LcCut cut (nullptr);
+  u32 *nlflag = nullptr, *nlex = nullptr; Feature *feat = nullptr; signed char *phase = nullptr;
+  for (int pass = 0; pass < 2; pass++) {
+    cut = LcCut (pass ? c->lc_work.p : nullptr);
+    nlflag = cut.take<u32> (n + 1); nlex = cut.take<u32> (n + 1); feat = cut.take<Feature> (nf + 1); phase = cut.take<signed char> (nf + 1);
+    if (!pass && (ensure (c->lc_work, cut.used, c->stream) || ensure (c->stage, ((size_t) n + 255) & ~(size_t) 255, c->stream) ||
+                  ensure (c->scan_tmp, scan_tmp_words (n) * 4 + 64, c->stream))) { tjamd_coding_destroy (cod); return NULL; }
+  }
+  if (hipMalloc (&cod->codes, (size_t) std::max<long> (n, 1)) != hipSuccess || hipMalloc (&cod->cstart, (size_t) (n_contigs + 2) * 4) != hipSuccess ||
+      hipMalloc (&cod->rows, (size_t) std::max<long> (nf, 1) * sizeof (CodRow)) != hipSuccess) CD_FAIL (TJAMD_ERR_HIP, "%s: hipMalloc failed for %ld bytes of genome and %ld features", fn, n, nf);
+  if ((n && hipMemcpyAsync (c->stage.p, h_stream, n_bytes, hipMemcpyHostToDevice, c->stream) != hipSuccess) ||
+      (nf && hipMemcpyAsync (feat, h_features, (size_t) nf * sizeof (Feature), hipMemcpyHostToDevice, c->stream) != hipSuccess) ||
+      (nf && h_phase && hipMemcpyAsync (phase, h_phase, (size_t) nf, hipMemcpyHostToDevice, c->stream) != hipSuccess)) CD_FAIL (TJAMD_ERR_HIP, "%s: copy to device failed", fn);
+  (void) c->timer[T_CODING].begin (c->stream);
+  if (n) {
+    const uint8_t *seq = (const uint8_t *) c->stage.p;
+    hipLaunchKernelGGL (cd_code_kernel, dim3 (grid_for (n)), dim3 (256), 0, c->stream, seq, n, cod->codes, nlflag);
+    if (exclusive_scan (c, nlflag, nlex, n, nullptr, (u32 *) c->scan_tmp.p, c->scan_tmp.cap / 4)) { tjamd_coding_destroy (cod); return NULL; }
+    hipLaunchKernelGGL (cd_cstart_kernel, dim3 (grid_for (n)), dim3 (256), 0, c->stream, seq, n, (const u32 *) nlflag, (const u32 *) nlex, cod->cstart);
+  }
+  if (nf)                                               // (features need contigs, contigs need bytes: n > 0 here)
+    hipLaunchKernelGGL (cds_scan_kernel, dim3 ((unsigned) std::min<long> ((nf + 3) / 4, 65536)), dim3 (256), 0, c->stream, (const uint8_t *) cod->codes,
+                        (const u32 *) cod->cstart, (const Feature *) feat, h_phase ? (const signed char *) phase : (const signed char *) nullptr, nf, cod->rows);
+  if (hipGetLastError () != hipSuccess) CD_FAIL (TJAMD_ERR_HIP, "%s: launch failed", fn);
+  (void) c->timer[T_CODING].end (c->stream);
+  if (hipStreamSynchronize (c->stream) != hipSuccess) CD_FAIL (TJAMD_ERR_HIP, "%s: build failed: %s", fn, hipGetErrorString (hipGetLastError ()));
+#undef CD_FAIL
+  c->timer[T_CODING].timed = true;
+  return cod;
+}
+
+extern "C" long tjamd_coding_features (const tjamd_coding *cod) { return cod ? cod->n_features : -1; }
+
+extern "C" long tjamd_coding_download (const tjamd_coding *cod, tjamd_cds *out, long capacity)
+{
+  static const char *fn = "tjamd_coding_download";
+  if (!cod) return -set_err (TJAMD_ERR_ARG, "%s: null coding table", fn);
+  const long nf = cod->n_features;
+  if (nf == 0 || capacity < nf) return nf;
+  if (!out) return -set_err (TJAMD_ERR_ARG, "%s: null buffer", fn);
+  if (hipSetDevice (cod->device) != hipSuccess ||
+      hipMemcpy2D (out, sizeof (Cds), cod->rows, sizeof (CodRow), sizeof (Cds), (size_t) nf, hipMemcpyDeviceToHost) != hipSuccess) return -set_err (TJAMD_ERR_HIP, "%s: copy failed", fn);
+  return nf;
+}
+extern "C" double tjamd_last_coding_ms (tjamd_counter *c) { return c ? c->timer[T_CODING].ms (c->device) : -1.0; }
+
+// what the wavefront needs of an owner's record: the span, where the edit sits in it and what ALT is made of
+struct Walk
+{
+  const uint8_t *g;                     // the span's first code (forward)
+  long len, alt_len;                    // of the span, of the alternative span
+  long e, n_ref, n_alt, n_run;          // the edit's offset in the span (p - S), |REF|, |ALT|, ALT's run of the base
+  u32 base; u64 flank;                  // the run base, ALT's flank bases
+  int strand, phase;
+};
+
+// CDS-oriented base j of the alternative span: a genome code, the run base or two bits of alt_flank, chosen by its index
+__device__ __forceinline__ u32 alt_code (const Walk &w, long j)
+{
+  const long x = w.strand ? w.alt_len - 1 - j : j;      // forward index in the alternative span
+  u32 cd;
+  if (x < w.e) cd = w.g[x];
+  else if (x < w.e + w.n_alt) { const long t = x - w.e; cd = t < w.n_run ? w.base : (u32) (w.flank >> (2 * (t - w.n_run))) & 3u; }
+  else cd = w.g[x - w.n_alt + w.n_ref];
+  return w.strand ? code_complement (cd) : cd;
+}
+__device__ __forceinline__ u32 ref_symbol (const Walk &w, const char *tab, long cdn)
+{
+  const long j = 3 * cdn + w.phase;
+  return amino_acid (tab, span_code (w.g, w.len, w.strand, j), span_code (w.g, w.len, w.strand, j + 1), span_code (w.g, w.len, w.strand, j + 2));
+}
+__device__ __forceinline__ u32 alt_symbol (const Walk &w, const char *tab, long cdn)
+{
+  const long j = 3 * cdn + w.phase;
+  return amino_acid (tab, alt_code (w, j), alt_code (w, j + 1), alt_code (w, j + 2));
+}
+
+// err bits: 1 contig, 2 pos or q, 4 n_flank, 8 a length, 16 tract, 32 feature index (tjamd_variant_effects names them)
+__global__ __launch_bounds__ (256)
+void variant_effects_kernel (const uint8_t *__restrict__ codes, const u32 *__restrict__ cstart, long n_contigs, const CodRow *__restrict__ rows, long n_features,
+                             const Variant *__restrict__ var, long n, const TractFeature *__restrict__ tf, long n_tracts, Effect *__restrict__ out, int *__restrict__ err)
+{
+  __shared__ char tab[64];                              // the lanes index the amino acids apart: LDS, not a constant array
+  if (threadIdx.x < 64) tab[threadIdx.x] = aa_table_byte (threadIdx.x);
+  __syncthreads ();
+  const int lane = threadIdx.x & 63;
+  const long stride = (long) gridDim.x * blockDim.x;
+  for (long i0 = blockIdx.x * (long) blockDim.x + (threadIdx.x & ~63); i0 < n; i0 += stride) {     // (uniform across a wavefront)
+    const long i = i0 + lane;
+    bool walk = false;
+    Walk w = {codes, 0, 0, 0, 0, 0, 0, 0u, 0ull, 0, 0};
+    Effect r = {-1, TJAMD_EFFECT_NONE, 0, -1, 0, 0, 0, 0, 0ull, 0ull};
+    long c_first = 0, p_ref = 0;                        // the walk's first codon; the symbols of P_ref
+    int delta = 0;
+    if (i < n) {
+      const Variant v = var[i];
+      int bad = 0, f = -1;
+      long clen = 0, c0 = 0;
+      if (v.contig < 0 || (long) v.contig >= n_contigs) bad |= 1;
+      else { c0 = cstart[v.contig]; clen = (long) cstart[v.contig + 1] - 1 - c0; }
+      if (v.n_flank < 0 || v.n_flank > 32) bad |= 4;
+      if (v.ref_length < 1 || v.alt_length < 1) bad |= 8;
+      const long Lr = v.ref_length, La = v.alt_length, nfl = v.n_flank;
+      const long n_ref = max (Lr - La, 0l) + 1 + nfl, n_alt = max (La - Lr, 0l) + 1 + nfl;
+      const long p = (long) v.pos - 1, q = p + n_ref - 1;
+      if (!bad && (v.pos < 1 || q >= clen)) bad |= 2;
+      if (tf) {
+        if (v.tract < 0 || (long) v.tract >= n_tracts) bad |= 16;
+        else { f = tf[v.tract].feature; if (f < -1 || (long) f >= n_features) { bad |= 32; f = -1; } }
+      }
+      if (bad) atomicOr (err, bad);                     // (the call is refused; the record is left alone)
+      else {
+        r.feature = f;
+        CodRow row = {Cds {-1, -1, -1, -1}, 0, 0, 0, 0};
+        if (f >= 0) row = rows[f];
+        if (row.cds.aa_len >= 0) {
+          const long S = row.start, E = S + row.len - 1;
+          r.ref_aa_len = row.cds.aa_len; r.flags = row.cds.has_stop ? TJAMD_EFFECT_REF_STOP : 0;
+          if (row.contig != v.contig || p < S || q > E) r.cls = TJAMD_EFFECT_BOUNDARY;
+          else {
+            walk = true;
+            w.g = codes + c0 + S; w.len = row.len; w.alt_len = (long) row.len + n_alt - n_ref;
+            w.e = p - S; w.n_ref = n_ref; w.n_alt = n_alt; w.n_run = max (La - Lr, 0l) + 1;
+            w.base = (u32) v.base & 3u; w.flank = v.alt_flank; w.strand = row.strand; w.phase = row.cds.phase;
+            r.cds_pos = (int) (row.strand ? E - q : p + 1 - S);
+            const long same = row.strand ? E - q : p - S;                   // CDS-oriented bases in front of the edit: equal in both
+            c_first = max (same - (long) row.cds.phase, 0l) / 3;
+            p_ref = (long) row.cds.aa_len + row.cds.has_stop;
+            delta = (int) ((La - Lr) % 3);
+          }
+        }
+        if (!walk) out[i] = r;
+      }
+    }
+    u64 owners = __ballot (walk);
+    while (owners) {                                    // the wavefront walks its records together, one after the other
+      const int src = __ffsll ((long long) owners) - 1;
+      owners &= owners - 1;
+      Walk o;
+      o.g = (const uint8_t *) __shfl ((unsigned long long) w.g, src);
+      o.len = __shfl (w.len, src); o.alt_len = __shfl (w.alt_len, src); o.e = __shfl (w.e, src); o.n_ref = __shfl (w.n_ref, src);
+      o.n_alt = __shfl (w.n_alt, src); o.n_run = __shfl (w.n_run, src); o.base = __shfl (w.base, src); o.flank = __shfl (w.flank, src);
+      o.strand = __shfl (w.strand, src); o.phase = __shfl (w.phase, src);
+      const long first = __shfl (c_first, src), np_ref = __shfl (p_ref, src);
+      const long nc_alt = max (o.alt_len - (long) o.phase, 0l) / 3;
+      long first_diff = -1, alt_stop = -1;
+      // codons [0, first) are the same bases in both: a reference that stops among them is the alternative too
+      if (np_ref <= first && __shfl (r.flags, src) != 0) alt_stop = np_ref - 1;   // (flags: so far the REF_STOP bit alone)
+      else
+        for (long at = first; at < nc_alt; at += 64) {
+          const long cdn = at + lane;
+          u32 a = 0, b = 0;
+          if (cdn < nc_alt) a = alt_symbol (o, tab, cdn);
+          if (cdn < np_ref) b = ref_symbol (o, tab, cdn);
+          const u64 stops = __ballot (a == (u32) '*');
+          const u64 diffs = __ballot (cdn < nc_alt && cdn < np_ref && a != b);
+          const int s = stops ? __ffsll ((long long) stops) - 1 : 64, d = diffs ? __ffsll ((long long) diffs) - 1 : 64;
+          if (first_diff < 0 && d <= s && d < 64) first_diff = at + d;
+          if (s < 64) { alt_stop = at + s; break; }
+        }
+      const long np_alt = alt_stop >= 0 ? alt_stop + 1 : nc_alt;
+      if (first_diff < 0 && np_alt != np_ref) first_diff = min (np_alt, np_ref);
+      u64 wr = 0, wa = 0;                                // lanes 0 to 7 translate the two windows
+      if (first_diff >= 0 && lane < 8) {
+        const long cdn = first_diff + lane;
+        if (cdn < np_ref) wr = (u64) ref_symbol (o, tab, cdn) << (8 * lane);
+        if (cdn < np_alt) wa = (u64) alt_symbol (o, tab, cdn) << (8 * lane);
+      }
+      for (int x = 1; x < 8; x <<= 1) { wr |= __shfl_xor (wr, x); wa |= __shfl_xor (wa, x); }
+      wr = __shfl (wr, 0); wa = __shfl (wa, 0);
+      if (lane == src) {
+        r.first_diff = (int) first_diff;
+        r.cls = first_diff < 0 ? TJAMD_EFFECT_IDENTICAL : delta == 0 ? TJAMD_EFFECT_INFRAME : TJAMD_EFFECT_FRAMESHIFT;
+        r.alt_aa_len = (int) (alt_stop >= 0 ? alt_stop : nc_alt);
+        if (alt_stop >= 0) r.flags |= TJAMD_EFFECT_ALT_STOP;
+        r.ref_aa = wr; r.alt_aa = wa;
+        out[i] = r;
+      }
+    }
+  }
+}
+
+extern "C" long tjamd_variant_effects (tjamd_counter *c, const tjamd_coding *cod, const tjamd_variant *d_variants, long n,
+                                       const tjamd_tract_feature *d_tract_feat, long n_tracts, tjamd_effect *d_out)
+{
+  static const char *fn = "tjamd_variant_effects";
+  auto refused = [&] () -> int {                        // the checks that read no handle, the counter's device last
+    if (n < 0) return set_err (TJAMD_ERR_ARG, "%s: n %ld < 0", fn, n);
+    if (n >= (1l << 31)) return set_err (TJAMD_ERR_CAPACITY, "%s: %ld records", fn, n);
+    if (n > 0 && (!d_variants || !d_out)) return set_err (TJAMD_ERR_ARG, "%s: null variant or output buffer", fn);
+    if (d_tract_feat && n_tracts < 0) return set_err (TJAMD_ERR_ARG, "%s: n_tracts %ld < 0", fn, n_tracts);
+    if (!c || !cod) return set_err (TJAMD_ERR_ARG, "%s: null counter or coding table", fn);
+    if (tjamd_device_count () <= 0) return set_err (TJAMD_ERR_NO_DEVICE, "%s: TJAMD_ERR_NO_DEVICE: no HIP device visible (the records are classified on the device; no CPU fallback)", fn);
+    if (cod->device != c->device) return set_err (TJAMD_ERR_ARG, "%s: the coding table lives on device %d, the counter on device %d", fn, cod->device, c->device);
+    return TJAMD_OK;
+  };
+  int rc = refused ();
+  if (c && tjamd_device_count () > 0) c->timer[T_VARIANT_EFFECTS].timed = false;   // a refused call leaves no timing behind (without a device there is no counter)
+  if (rc) return -rc;
+  if (hipSetDevice (c->device) != hipSuccess) return -set_err (TJAMD_ERR_HIP, "hipSetDevice failed");
+  if (n == 0) return 0;
+  rc = ensure (c->lc_work, 256, c->stream);
+  if (rc) return -rc;
+  int *err = (int *) c->lc_work.p;
+  if (hipMemsetAsync (err, 0, 4, c->stream) != hipSuccess) return -set_err (TJAMD_ERR_HIP, "%s: memset failed", fn);
+  (void) c->timer[T_VARIANT_EFFECTS].begin (c->stream);
+  hipLaunchKernelGGL (variant_effects_kernel, dim3 ((unsigned) std::min<long> ((n + 255) / 256, 65536)), dim3 (256), 0, c->stream, (const uint8_t *) cod->codes,
+                      (const u32 *) cod->cstart, cod->n_contigs, (const CodRow *) cod->rows, cod->n_features, (const Variant *) d_variants, n,
+                      (const TractFeature *) d_tract_feat, n_tracts, (Effect *) d_out, err);
+  if (hipGetLastError () != hipSuccess) return -set_err (TJAMD_ERR_HIP, "%s: launch failed", fn);
+  (void) c->timer[T_VARIANT_EFFECTS].end (c->stream);
+  int h_err = 0;
+  if (hipMemcpyAsync (&h_err, err, 4, hipMemcpyDeviceToHost, c->stream) != hipSuccess || hipStreamSynchronize (c->stream) != hipSuccess)
+    return -set_err (TJAMD_ERR_HIP, "%s: failed: %s", fn, hipGetErrorString (hipGetLastError ()));
+  if (h_err & 1) return -set_err (TJAMD_ERR_ARG, "%s: a record's contig is outside [0, %ld)", fn, cod->n_contigs);
+  if (h_err & 2) return -set_err (TJAMD_ERR_ARG, "%s: a record has pos < 1 or a REF that ends beyond its contig", fn);
+  if (h_err & 4) return -set_err (TJAMD_ERR_ARG, "%s: a record's n_flank is outside 0..32", fn);
+  if (h_err & 8) return -set_err (TJAMD_ERR_ARG, "%s: a record has ref_length or alt_length < 1", fn);
+  if (h_err & 16) return -set_err (TJAMD_ERR_ARG, "%s: a record's tract is outside [0, %ld)", fn, n_tracts);
+  if (h_err & 32) return -set_err (TJAMD_ERR_ARG, "%s: a tract's feature index is outside [-1, %ld)", fn, cod->n_features);
+  c->timer[T_VARIANT_EFFECTS].timed = true;
+  return n;
+}
+extern "C" double tjamd_last_variant_effects_ms (tjamd_counter *c) { return c ? c->timer[T_VARIANT_EFFECTS].ms (c->device) : -1.0; }

@@ -9,6 +9,7 @@
 #include "../../include/tatajuba_amd.h"
 #include "../../include/tatajuba_variants.h"
 #include "../../include/tatajuba_features.h"
+#include "../../include/tatajuba_effects.h"
 #include <pthread.h>
 #include <sched.h>
 #include <sys/stat.h>
@@ -373,6 +374,13 @@ tjamd_gff3_read (const char *path, const char *contig_names, long n_contigs, tja
                  char *strings, long strings_capacity, long *strings_bytes, long *n_skipped)
 {
   return tjg_read (path, contig_names, n_contigs, out, capacity, strings, strings_capacity, strings_bytes, n_skipped);
+}
+
+/* column 8 of the same lines (gff3_reader.c; tatajuba_effects.h) */
+long
+tjamd_gff3_read_phase (const char *path, const char *contig_names, long n_contigs, signed char *out, long capacity)
+{
+  return tjg_read_phase (path, contig_names, n_contigs, out, capacity);
 }
 
 /* the multi-threaded feeder into host memory (tests compare it with tjamd_read_file_stream) */
