@@ -1,0 +1,336 @@
+/* merged_vcf.c -- one multi-sample VCF with every sample's tract-length variants against the reference genome, through the C
+ * ABI and nothing else.  The reference program writes one VCF per sample and leaves the rest to its user (docs/tutorial.md,
+ * "Downstream analyses": sort | uniq over the files, or bcftools norm, index and merge); here the pipeline of sample_vcfs.c
+ * (scan, finalise, gather, merge, group, index the reference, locate, tracts by location, statistics, tjamd_tract_variants on
+ * the variable tracts) is followed by tjamd_merge_variants on the records where they are, on the device:
+ *   DIR/merged.vcf            sample_vcfs.c's header with ##INFO lines for AC and AN and one column per sample; one row per
+ *                             site, ALT comma-separated in allele order, haploid GT 1, 2, ... or "." where the sample has no record:
+ *                             contig  POS  .  REF  ALT1,ALT2  .  .  AC=n1,n2;AN=n_called;TID=tid_%06d  GT  g0  g1 ...
+ *   DIR/unique_variants.vcf   with -u: the tutorial's concatenation, one row per distinct allele in N8's own form (the record
+ *                             d_unique holds), one column all_samples
+ *   DIR/variant_effects.tsv   with -e annotation.gff3: tjamd_variant_effects on d_unique only, one line per allele: variant_effects.c's
+ *                             columns without the sample, then the number of samples that carry the allele
+ * The other options are sample_vcfs.c's.
+ *
+ *   gcc -O2 -I include examples/merged_vcf.c -L tatajuba_amd -ltatajuba_amd -Wl,-rpath,$PWD/tatajuba_amd -o merged_vcf
+ *   ./merged_vcf -r reference.fa [-u] [-e annotation.gff3] [-x 1] [-g G] [-s 3] [-k 10] [-m 3] [-c 5] [-d 1] [-l -1] [-o .] sample1.fastq[.gz] ...   */
+#include <stdio.h>
+#include <stdlib.h>
+#include <string.h>
+#include <tatajuba_sites.h>
+#include <tatajuba_effects.h>
+#include <tatajuba_locate.h>
+
+#define MAX_SAMPLES 64
+
+static int
+fail (const char *what)
+{
+  fprintf (stderr, "%s: %s\n", what, tjamd_last_error ());
+  return 1;
+}
+
+/* the up to eight symbols of a window, "." if it is empty (variant_effects.c) */
+static const char *
+window_text (uint64_t w, char *buf)
+{
+  int j;
+  for (j = 0; j < 8 && ((w >> (8 * j)) & 0xff); j++) buf[j] = (char) ((w >> (8 * j)) & 0xff);
+  buf[j] = '\0';
+  return j ? buf : ".";
+}
+
+/* REF and ALT of a variant record in N8's own form (sample_vcfs.c) */
+static void
+print_ref_alt (FILE *fout, const tjamd_variant *v)
+{
+  const char B = "ACGT"[v->base & 3];
+  int j, n_ref = (v->ref_length > v->alt_length ? v->ref_length - v->alt_length : 0) + 1,
+         n_alt = (v->alt_length > v->ref_length ? v->alt_length - v->ref_length : 0) + 1;
+  for (j = 0; j < n_ref; j++) fputc (B, fout);
+  for (j = 0; j < v->n_flank; j++) fputc ("ACGT"[(v->ref_flank >> (2 * j)) & 3], fout);
+  fputc ('\t', fout);
+  for (j = 0; j < n_alt; j++) fputc (B, fout);
+  for (j = 0; j < v->n_flank; j++) fputc ("ACGT"[(v->alt_flank >> (2 * j)) & 3], fout);
+}
+
+static FILE *
+open_output (const char *outdir, const char *name)
+{
+  size_t len = strlen (outdir) + strlen (name) + 2;
+  char *path = (char *) malloc (len);
+  FILE *f;
+  snprintf (path, len, "%s/%s", outdir, name);
+  f = fopen (path, "w");
+  if (!f) fprintf (stderr, "cannot write %s\n", path);
+  free (path);
+  return f;
+}
+
+int
+main (int argc, char **argv)
+{
+  tjamd_counter *ctr[MAX_SAMPLES];
+  const char *files[MAX_SAMPLES], *outdir = ".", *reference = NULL, *gff = NULL;
+  static const char *class_name[5] = {"NONE", "BOUNDARY", "IDENTICAL", "INFRAME", "FRAMESHIFT"};
+  long counts[MAX_SAMPLES], total, n_union, n_grouped, n_tracts, n_located, n_gapped = 0, n_var = 0, n_rec, i, cap, ref_bytes, n_contigs = 0, n_names = 0, name_bytes;
+  long offsets[MAX_SAMPLES + 1], *contig_len, var_cap, n_sites, n_alleles = 0, s, text_cap = 0;
+  int with_unique = 0;
+  int n = 0, k = 10, m = 3, cov = 5, maxd = 1, lev = -1, mism = 1, max_edits = -1, max_shift = TJAMD_MAX_SHIFT, coverage[MAX_SAMPLES], a, ndev = tjamd_device_count (), status;
+  const void *d_records = NULL;
+  void *d_keys, *d_counts, *d_ids, *d_grouped, *d_loc, *d_perm, *d_pkeys, *d_pcounts, *d_tracts, *d_tloc, *d_reflen, *d_summary, *d_var, *d_variants, *d_sites, *d_alleles, *d_genotype, *d_unique;
+  unsigned char *ref_stream;
+  char *names, **contig_name;
+  tjamd_reference *ref;
+  tjamd_variant *h_unique;
+  tjamd_site *h_sites;
+  tjamd_allele *h_alleles;
+  int16_t *h_genotype;
+  char *text, **sample_name;
+  FILE *fout;
+
+  for (a = 1; a < argc; a++) {
+    if (!strcmp (argv[a], "-k") && a + 1 < argc) k = atoi (argv[++a]);
+    else if (!strcmp (argv[a], "-m") && a + 1 < argc) m = atoi (argv[++a]);
+    else if (!strcmp (argv[a], "-c") && a + 1 < argc) cov = atoi (argv[++a]);
+    else if (!strcmp (argv[a], "-d") && a + 1 < argc) maxd = atoi (argv[++a]);
+    else if (!strcmp (argv[a], "-l") && a + 1 < argc) lev = atoi (argv[++a]);
+    else if (!strcmp (argv[a], "-x") && a + 1 < argc) mism = atoi (argv[++a]);
+    else if (!strcmp (argv[a], "-g") && a + 1 < argc) max_edits = atoi (argv[++a]);      /* the second pass of the lookup, as in located_tracts.c */
+    else if (!strcmp (argv[a], "-s") && a + 1 < argc) max_shift = atoi (argv[++a]);
+    else if (!strcmp (argv[a], "-r") && a + 1 < argc) reference = argv[++a];
+    else if (!strcmp (argv[a], "-o") && a + 1 < argc) outdir = argv[++a];
+    else if (!strcmp (argv[a], "-e") && a + 1 < argc) gff = argv[++a];
+    else if (!strcmp (argv[a], "-u")) with_unique = 1;
+    else if (n < MAX_SAMPLES) files[n++] = argv[a];
+  }
+  if (n < 1 || !reference) { fprintf (stderr, "usage: %s -r reference.fa [-u] [-e annotation.gff3] [-x X] [-g G] [-s S] [-k K] [-m M] [-c C] [-d D] [-l L] [-o DIR] sample.fastq[.gz] ...\n", argv[0]); return 2; }
+  if (ndev < 1) { fprintf (stderr, "tatajuba_amd error: no HIP device is visible (there is no CPU fallback)\n"); return 1; }
+  if (maxd < 0) maxd = 0;                                 /* src/main.c:190-192 */
+  if (maxd > k / 2) maxd = k / 2;
+  if (lev < 0) lev = maxd + 1;
+
+  for (a = 0; a < n; a++) {
+    long n_reads = 0, bytes = tjamd_read_file_stream (files[a], NULL, 0, &n_reads);
+    unsigned char *buf;
+    if (bytes < 0) { fprintf (stderr, "cannot read %s\n", files[a]); return 1; }
+    buf = (unsigned char *) malloc ((size_t) bytes + 1);
+    tjamd_read_file_stream (files[a], buf, bytes, &n_reads);
+    ctr[a] = tjamd_counter_create (a % ndev, k);
+    if (!ctr[a] || tjamd_scan_host (ctr[a], buf, (size_t) bytes, m) || tjamd_finalise (ctr[a], 1, cov, &status)) return fail (files[a]);
+    coverage[a] = tjamd_coverage (ctr[a]);
+    free (buf);
+  }
+
+  total = tjamd_gather_histograms (ctr[0], ctr, n, &d_records, counts);
+  if (total < 0) return fail ("gather");
+  d_keys = tjamd_device_alloc (ctr[0], (size_t) (total ? total : 1) * 24);
+  d_counts = tjamd_device_alloc (ctr[0], (size_t) (total ? total : 1) * (size_t) n * 4);
+  n_union = tjamd_merge_samples (ctr[0], d_records, counts, n, d_keys, d_counts, total);
+  if (n_union < 0) return fail ("merge");
+
+  /* the tracts by grouping, as in selected_tracts.c (a union of n_union rows has at most n_union of them) */
+  cap = n_union ? n_union : 1;
+  d_ids = tjamd_device_alloc (ctr[0], (size_t) cap * sizeof (int));
+  d_grouped = tjamd_device_alloc (ctr[0], (size_t) cap * sizeof (tjamd_union_tract));
+  n_grouped = tjamd_union_tracts (ctr[0], d_keys, d_counts, n_union, n, maxd, lev, (int *) d_ids, NULL, (tjamd_union_tract *) d_grouped, cap);
+  if (n_grouped < 0) return fail ("union tracts");
+
+  /* the reference: its contigs as a stream of reads -> the index of its runs; every union row -> its place */
+  ref_bytes = tjamd_read_file_stream (reference, NULL, 0, &n_contigs);
+  if (ref_bytes < 0) { fprintf (stderr, "cannot read %s\n", reference); return 1; }
+  ref_stream = (unsigned char *) malloc ((size_t) ref_bytes + 1);
+  tjamd_read_file_stream (reference, ref_stream, ref_bytes, &n_contigs);
+  ref = tjamd_reference_create (ctr[0], ref_stream, (size_t) ref_bytes);
+  if (!ref) return fail (reference);
+  /* contig names from the FASTA's headers, contig lengths from the delimiters of its stream */
+  name_bytes = tjamd_read_file_names (reference, NULL, 0, &n_names);
+  if (name_bytes < 0 || n_names != n_contigs) { fprintf (stderr, "cannot read the contig names of %s\n", reference); return 1; }
+  names = (char *) malloc ((size_t) name_bytes + 1);
+  tjamd_read_file_names (reference, names, name_bytes, &n_names);
+  contig_name = (char **) malloc ((size_t) (n_contigs ? n_contigs : 1) * sizeof (char *));
+  contig_len = (long *) malloc ((size_t) (n_contigs ? n_contigs : 1) * sizeof (long));
+  {
+    char *p = names;
+    long from = 0, at, c = 0;
+    for (i = 0; i < n_contigs; i++) { contig_name[i] = p; p = strchr (p, '\n'); *p++ = '\0'; }
+    for (at = 0; at < ref_bytes && c < n_contigs; at++) if (ref_stream[at] == '\n') { contig_len[c++] = at - from; from = at + 1; }
+  }
+  d_loc = tjamd_device_alloc (ctr[0], (size_t) cap * sizeof (tjamd_location));
+  n_located = tjamd_locate (ctr[0], ref, d_keys, n_union, mism, (tjamd_location *) d_loc);
+  if (n_located < 0) return fail ("locate");
+  if (max_edits >= 0) {
+    if (tjamd_reference_add_seeds (ctr[0], ref) < 0) return fail ("seed order");
+    n_gapped = tjamd_locate_gapped (ctr[0], ref, d_keys, n_union, max_edits, max_shift, (tjamd_location *) d_loc, NULL);
+    if (n_gapped < 0) return fail ("gapped locate");
+  }
+
+  /* tracts at one place become one; the union permuted into the order of the places; then summaries and the selected ids */
+  d_perm = tjamd_device_alloc (ctr[0], (size_t) cap * sizeof (int));
+  d_pkeys = tjamd_device_alloc (ctr[0], (size_t) cap * 24);
+  d_pcounts = tjamd_device_alloc (ctr[0], (size_t) cap * (size_t) n * 4);
+  d_tracts = tjamd_device_alloc (ctr[0], (size_t) cap * sizeof (tjamd_union_tract));
+  d_tloc = tjamd_device_alloc (ctr[0], (size_t) cap * sizeof (tjamd_location));
+  d_reflen = tjamd_device_alloc (ctr[0], (size_t) cap * sizeof (int));
+  n_tracts = tjamd_located_tracts (ctr[0], d_keys, d_counts, n_union, n, (const tjamd_union_tract *) d_grouped, n_grouped, (const tjamd_location *) d_loc,
+                                   (int *) d_perm, d_pkeys, d_pcounts, (tjamd_union_tract *) d_tracts, (tjamd_location *) d_tloc, (int *) d_reflen, cap);
+  if (n_tracts < 0) return fail ("located tracts");
+  d_summary = tjamd_device_alloc (ctr[0], (size_t) (n_tracts ? n_tracts : 1) * sizeof (tjamd_union_tract_summary));
+  d_var = tjamd_device_alloc (ctr[0], (size_t) (n_tracts ? n_tracts : 1) * sizeof (int));
+  if (tjamd_union_tract_stats (ctr[0], d_pkeys, d_pcounts, n_union, n, (const tjamd_union_tract *) d_tracts, n_tracts, coverage, (const int *) d_reflen,
+                               (tjamd_union_tract_summary *) d_summary, (int *) d_var, &n_var, NULL, NULL) < 0) return fail ("tract statistics");
+
+  /* the variants of the variable tracts: at most one record per (variable tract, sample), sample by sample */
+  var_cap = n_var > 0 ? n_var * n : 1;
+  d_variants = tjamd_device_alloc (ctr[0], (size_t) var_cap * sizeof (tjamd_variant));
+  n_rec = tjamd_tract_variants (ctr[0], ref, d_pkeys, d_pcounts, n_union, n, (const tjamd_union_tract *) d_tracts, n_tracts, (const tjamd_location *) d_tloc,
+                                (const int *) d_var, n_var, (tjamd_variant *) d_variants, var_cap, offsets);
+  if (n_rec < 0) return fail ("tract variants");
+
+  /* the records of all samples -> sites, their alleles, a genotype per (site, sample), one record per allele */
+  cap = n_rec ? n_rec : 1;
+  d_sites = tjamd_device_alloc (ctr[0], (size_t) cap * sizeof (tjamd_site));
+  d_alleles = tjamd_device_alloc (ctr[0], (size_t) cap * sizeof (tjamd_allele));
+  d_genotype = tjamd_device_alloc (ctr[0], (size_t) cap * (size_t) n * sizeof (int16_t));
+  d_unique = tjamd_device_alloc (ctr[0], (size_t) cap * sizeof (tjamd_variant));
+  n_sites = tjamd_merge_variants (ctr[0], k, (const tjamd_variant *) d_variants, n_rec, n, n_tracts, (tjamd_site *) d_sites, cap, (tjamd_allele *) d_alleles, cap,
+                                  (int16_t *) d_genotype, NULL, (tjamd_variant *) d_unique, &n_alleles);
+  if (n_sites < 0) return fail ("merge variants");
+  h_sites = (tjamd_site *) malloc ((size_t) (n_sites ? n_sites : 1) * sizeof (tjamd_site));
+  h_alleles = (tjamd_allele *) malloc ((size_t) (n_alleles ? n_alleles : 1) * sizeof (tjamd_allele));
+  h_genotype = (int16_t *) malloc ((size_t) (n_sites ? n_sites : 1) * (size_t) n * sizeof (int16_t));
+  h_unique = (tjamd_variant *) malloc ((size_t) (n_alleles ? n_alleles : 1) * sizeof (tjamd_variant));
+  if (tjamd_device_download (ctr[0], h_sites, d_sites, (size_t) n_sites * sizeof (tjamd_site)) ||
+      tjamd_device_download (ctr[0], h_alleles, d_alleles, (size_t) n_alleles * sizeof (tjamd_allele)) ||
+      tjamd_device_download (ctr[0], h_genotype, d_genotype, (size_t) n_sites * (size_t) n * sizeof (int16_t)) ||
+      tjamd_device_download (ctr[0], h_unique, d_unique, (size_t) n_alleles * sizeof (tjamd_variant))) return fail ("download");
+  printf ("%ld contigs, %ld runs indexed; %ld of %ld union rows located; %ld tracts by location, %ld variable; %ld variants in %d samples\n", n_contigs,
+          tjamd_reference_entries (ref), n_located, n_union, n_tracts, n_var, n_rec, n);
+  if (max_edits >= 0) printf ("%ld more union rows located within %d edits and a shift of %d\n", n_gapped, max_edits, max_shift);
+  printf ("%ld sites with %ld distinct alleles\n", n_sites, n_alleles);
+
+  sample_name = (char **) malloc ((size_t) n * sizeof (char *));
+  for (a = 0; a < n; a++) {
+    const char *slash = strrchr (files[a], '/'), *base = slash ? slash + 1 : files[a];
+    size_t len = strlen (base) + 1;
+    char *p;
+    sample_name[a] = (char *) malloc (len);
+    snprintf (sample_name[a], len, "%s", base);
+    for (p = sample_name[a]; *p; p++) if (*p == '/' || *p == '"' || *p == '\'' || *p == ' ' || *p == '\\') *p = '_';      /* as sample_vcfs.c names it */
+  }
+  for (s = 0; s < n_sites; s++) {                         /* the longest text of any site */
+    long len = tjamd_site_ref_alt (h_sites + s, NULL, k, NULL, 0);
+    if (len > text_cap) text_cap = len;
+    for (i = 0; i < h_sites[s].n_alleles; i++) {
+      len = tjamd_site_ref_alt (h_sites + s, h_alleles + h_sites[s].first_allele + i, k, NULL, 0);
+      if (len > text_cap) text_cap = len;
+    }
+  }
+  text = (char *) malloc ((size_t) text_cap + 1);
+
+  if (!(fout = open_output (outdir, "merged.vcf"))) return 1;
+  fprintf (fout, "##fileformat=VCFv4.2\n##FORMAT=<ID=GT,Number=1,Type=String,Description=\"Genotype\">\n"
+                 "##INFO=<ID=AC,Number=A,Type=Integer,Description=\"samples that carry each ALT allele\">\n"
+                 "##INFO=<ID=AN,Number=1,Type=Integer,Description=\"samples with a call\">\n"
+                 "##INFO=<ID=TID,Number=A,Type=String,Description=\"tract ID\">\n");
+  for (i = 0; i < n_contigs; i++) fprintf (fout, "##contig=<ID=%s,length=%ld>\n", contig_name[i], contig_len[i]);
+  fprintf (fout, "#CHROM\tPOS\tID\tREF\tALT\tQUAL\tFILTER\tINFO\tFORMAT");
+  for (a = 0; a < n; a++) fprintf (fout, "\t%s", sample_name[a]);
+  fputc ('\n', fout);
+  for (s = 0; s < n_sites; s++) {
+    const tjamd_site *site = h_sites + s;
+    const tjamd_allele *al = h_alleles + site->first_allele;
+    if (tjamd_site_ref_alt (site, NULL, k, text, (int) text_cap + 1) < 0) { fprintf (stderr, "site %ld has no text\n", s); return 1; }
+    fprintf (fout, "%s\t%d\t.\t%s\t", contig_name[site->contig], site->pos, text);
+    for (i = 0; i < site->n_alleles; i++) {
+      if (tjamd_site_ref_alt (site, al + i, k, text, (int) text_cap + 1) < 0) { fprintf (stderr, "site %ld has no text\n", s); return 1; }
+      fprintf (fout, "%s%s", i ? "," : "", text);
+    }
+    fprintf (fout, "\t.\t.\tAC=");
+    for (i = 0; i < site->n_alleles; i++) fprintf (fout, "%s%d", i ? "," : "", al[i].n_samples);
+    fprintf (fout, ";AN=%d;TID=tid_%06d\tGT", site->n_called, site->tract);
+    for (a = 0; a < n; a++) {
+      const int g = h_genotype[s * n + a];
+      if (g < 0) fprintf (fout, "\t."); else fprintf (fout, "\t%d", g);
+    }
+    fputc ('\n', fout);
+  }
+  fclose (fout);
+
+  if (with_unique) {                                      /* every distinct event once, as N8 wrote it for the first sample that has it */
+    if (!(fout = open_output (outdir, "unique_variants.vcf"))) return 1;
+    fprintf (fout, "##fileformat=VCFv4.2\n##FORMAT=<ID=GT,Number=1,Type=String,Description=\"Genotype\">\n"
+                   "##INFO=<ID=TID,Number=A,Type=String,Description=\"tract ID\">\n");
+    for (i = 0; i < n_contigs; i++) fprintf (fout, "##contig=<ID=%s,length=%ld>\n", contig_name[i], contig_len[i]);
+    fprintf (fout, "#CHROM\tPOS\tID\tREF\tALT\tQUAL\tFILTER\tINFO\tFORMAT\tall_samples\n");
+    for (i = 0; i < n_alleles; i++) {
+      const tjamd_variant *v = h_unique + i;
+      fprintf (fout, "%s\t%d\t.\t", contig_name[v->contig], v->pos);
+      print_ref_alt (fout, v);
+      fprintf (fout, "\t.\t.\tTID=tid_%06d\tGT\t1\n", v->tract);
+    }
+    fclose (fout);
+  }
+
+  if (gff) {                                              /* the effect of every distinct allele, walked once */
+    long n_features, string_bytes = 0, n_skipped = 0, n_class[5] = {0, 0, 0, 0, 0};
+    tjamd_feature *features;
+    tjamd_effect *h_effects;
+    signed char *phase;
+    char *strings, *blob = (char *) malloc ((size_t) name_bytes + 1);
+    void *d_tf, *d_effects;
+    tjamd_annotation *ann;
+    tjamd_coding *cod;
+    for (i = 0, a = 0; i < n_contigs; i++) a += sprintf (blob + a, "%s\n", contig_name[i]);      /* the names as tjamd_gff3_read takes them */
+    n_features = tjamd_gff3_read (gff, blob, n_contigs, NULL, 0, NULL, 0, &string_bytes, &n_skipped);
+    if (n_features < 0) { fprintf (stderr, "cannot read %s\n", gff); return 1; }
+    features = (tjamd_feature *) malloc ((size_t) (n_features ? n_features : 1) * sizeof (tjamd_feature));
+    strings = (char *) malloc ((size_t) string_bytes + 1);
+    phase = (signed char *) malloc ((size_t) (n_features ? n_features : 1));
+    tjamd_gff3_read (gff, blob, n_contigs, features, n_features, strings, string_bytes, &string_bytes, &n_skipped);
+    if (tjamd_gff3_read_phase (gff, blob, n_contigs, phase, n_features) != n_features) { fprintf (stderr, "cannot read the phases of %s\n", gff); return 1; }
+    ann = tjamd_annotation_create (ctr[0], ref, features, n_features);
+    if (!ann) return fail (gff);
+    cod = tjamd_coding_create (ctr[0], ref_stream, (size_t) ref_bytes, features, n_features, phase);
+    if (!cod) return fail ("coding table");
+    d_tf = tjamd_device_alloc (ctr[0], (size_t) (n_tracts ? n_tracts : 1) * sizeof (tjamd_tract_feature));
+    d_effects = tjamd_device_alloc (ctr[0], (size_t) (n_alleles ? n_alleles : 1) * sizeof (tjamd_effect));
+    if (tjamd_tract_features (ctr[0], ann, d_pkeys, d_pcounts, n_union, n, (const tjamd_union_tract *) d_tracts, n_tracts, (const tjamd_location *) d_tloc,
+                              (tjamd_tract_feature *) d_tf) < 0) return fail ("tract features");
+    if (tjamd_variant_effects (ctr[0], cod, (const tjamd_variant *) d_unique, n_alleles, (const tjamd_tract_feature *) d_tf, n_tracts, (tjamd_effect *) d_effects) < 0)
+      return fail ("variant effects");
+    h_effects = (tjamd_effect *) malloc ((size_t) (n_alleles ? n_alleles : 1) * sizeof (tjamd_effect));
+    if (tjamd_device_download (ctr[0], h_effects, d_effects, (size_t) n_alleles * sizeof (tjamd_effect))) return fail ("download");
+    if (!(fout = open_output (outdir, "variant_effects.tsv"))) return 1;
+    fprintf (fout, "tract_id\tcontig_name\tpos\tref\talt\tfeature\teffect\tcds_pos\tfirst_diff\tref_aa\talt_aa\tref_aa_len\talt_aa_len\tn_samples\n");
+    for (i = 0; i < n_alleles; i++) {
+      const tjamd_variant *v = h_unique + i;
+      const tjamd_effect *e = h_effects + i;
+      char wr[9], wa[9];
+      fprintf (fout, "tid_%06d\t%s\t%d\t", v->tract, contig_name[v->contig], v->pos);
+      print_ref_alt (fout, v);
+      fprintf (fout, "\t%s\t%s\t%d\t%d\t%s\t%s\t%d\t%d\t%d\n", e->feature >= 0 ? strings + features[e->feature].id_off : "unannotated", class_name[e->cls], e->cds_pos,
+               e->first_diff + 1, window_text (e->ref_aa, wr), window_text (e->alt_aa, wa), e->ref_aa_len, e->alt_aa_len, h_alleles[i].n_samples);
+      n_class[e->cls]++;
+    }
+    fclose (fout);
+    printf ("%ld alleles: %ld outside coding features, %ld across a boundary, %ld identical, %ld in frame, %ld frameshifts\n", n_alleles,
+            n_class[TJAMD_EFFECT_NONE], n_class[TJAMD_EFFECT_BOUNDARY], n_class[TJAMD_EFFECT_IDENTICAL], n_class[TJAMD_EFFECT_INFRAME], n_class[TJAMD_EFFECT_FRAMESHIFT]);
+    tjamd_coding_destroy (cod);
+    tjamd_annotation_destroy (ann);
+    tjamd_device_free (ctr[0], d_tf); tjamd_device_free (ctr[0], d_effects);
+    free (features); free (strings); free (phase); free (blob); free (h_effects);
+  }
+
+  tjamd_reference_destroy (ref);
+  tjamd_device_free (ctr[0], d_keys); tjamd_device_free (ctr[0], d_counts); tjamd_device_free (ctr[0], d_ids); tjamd_device_free (ctr[0], d_grouped);
+  tjamd_device_free (ctr[0], d_loc); tjamd_device_free (ctr[0], d_perm); tjamd_device_free (ctr[0], d_pkeys); tjamd_device_free (ctr[0], d_pcounts);
+  tjamd_device_free (ctr[0], d_tracts); tjamd_device_free (ctr[0], d_tloc); tjamd_device_free (ctr[0], d_reflen);
+  tjamd_device_free (ctr[0], d_summary); tjamd_device_free (ctr[0], d_var); tjamd_device_free (ctr[0], d_variants);
+  tjamd_device_free (ctr[0], d_sites); tjamd_device_free (ctr[0], d_alleles); tjamd_device_free (ctr[0], d_genotype); tjamd_device_free (ctr[0], d_unique);
+  free (h_sites); free (h_alleles); free (h_genotype); free (h_unique); free (text); free (ref_stream);
+  for (a = 0; a < n; a++) free (sample_name[a]);
+  free (sample_name); free (names); free (contig_name); free (contig_len);
+  for (a = 0; a < n; a++) tjamd_counter_destroy (ctr[a]);
+  return 0;
+}

@@ -390,6 +390,10 @@ long tjamd_located_tracts (tjamd_counter *c, const void *d_keys, const void *d_c
 /* The coding effect of a variant record (N11: tjamd_translate, tjamd_gff3_read_phase, tjamd_coding_create and its kin,
  * tjamd_variant_effects) is declared, with its timers, in tatajuba_effects.h, which includes this header. */
 
+/* The per-sample variant records merged into multi-sample sites, their distinct alleles and a genotype per sample (N12:
+ * tjamd_merge_variants, tjamd_site_ref_alt) are declared, with their timer, in tatajuba_sites.h, which includes
+ * tatajuba_variants.h and through it this header. */
+
 /* release the calling thread's shared device contexts of the synchronous string scans (update_hopo_counter_from_seq on a
  * counter that never read a file, tjamd_scan_windows) now; they are released by themselves when the thread ends */
 void tjamd_thread_cleanup (void);

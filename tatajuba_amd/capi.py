@@ -59,6 +59,14 @@ EFFECT_DTYPE = np.dtype([("feature", "<i4"), ("cls", "<i4"), ("cds_pos", "<i4"),
                          ("flags", "<i4"), ("pad", "<i4"), ("ref_aa", "<u8"), ("alt_aa", "<u8")])
 assert EFFECT_DTYPE.itemsize == 48
 EFFECT_CLASSES = ["NONE", "BOUNDARY", "IDENTICAL", "INFRAME", "FRAMESHIFT"]      # TJAMD_EFFECT_*
+# tjamd_site and tjamd_allele (include/tatajuba_sites.h): a tract with records, merged over the samples; one of its distinct alleles
+SITE_DTYPE = np.dtype([("flat", "<i8"), ("tract", "<i4"), ("contig", "<i4"), ("pos", "<i4"), ("base", "<i4"), ("ref_length", "<i4"), ("min_length", "<i4"),
+                       ("n_flank", "<i4"), ("n_alleles", "<i4"), ("first_allele", "<i4"), ("n_called", "<i4"), ("first_record", "<i4"), ("pad", "<i4"),
+                       ("ref_flank", "<u8")])
+assert SITE_DTYPE.itemsize == 64
+ALLELE_DTYPE = np.dtype([("site", "<i4"), ("alt_length", "<i4"), ("n_flank", "<i4"), ("n_samples", "<i4"), ("first_record", "<i4"), ("pad", "<i4"),
+                         ("alt_flank", "<u8")])
+assert ALLELE_DTYPE.itemsize == 32
 
 
 class TatajubaAmdError(RuntimeError):
@@ -148,6 +156,8 @@ LOCATE_EXPORTS = ["tjamd_flank_edit_distance", "tjamd_reference_add_seeds", "tja
 # ... and include/tatajuba_effects.h
 EFFECT_EXPORTS = ["tjamd_translate", "tjamd_gff3_read_phase", "tjamd_coding_create", "tjamd_coding_destroy", "tjamd_coding_features", "tjamd_coding_download",
                   "tjamd_variant_effects", "tjamd_last_coding_ms", "tjamd_last_variant_effects_ms"]
+# ... and include/tatajuba_sites.h
+SITE_EXPORTS = ["tjamd_merge_variants", "tjamd_site_ref_alt", "tjamd_last_merge_variants_ms"]
 MAX_SHIFT = 3                     # TJAMD_MAX_SHIFT
 
 
@@ -299,6 +309,11 @@ def lib():
     L.tjamd_variant_effects.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_long, C.c_void_p, C.c_long, C.c_void_p]
     L.tjamd_last_coding_ms.restype = C.c_double; L.tjamd_last_coding_ms.argtypes = [C.c_void_p]
     L.tjamd_last_variant_effects_ms.restype = C.c_double; L.tjamd_last_variant_effects_ms.argtypes = [C.c_void_p]
+    L.tjamd_merge_variants.restype = C.c_long
+    L.tjamd_merge_variants.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_long, C.c_int, C.c_long, C.c_void_p, C.c_long, C.c_void_p, C.c_long,
+                                       C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.tjamd_site_ref_alt.restype = C.c_int; L.tjamd_site_ref_alt.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int]
+    L.tjamd_last_merge_variants_ms.restype = C.c_double; L.tjamd_last_merge_variants_ms.argtypes = [C.c_void_p]
     L.tjamd_group_contexts.restype = C.c_long
     L.tjamd_group_contexts.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_long]
     L.new_genomic_context_list.restype = C.POINTER(GenomicContextListStruct); L.new_genomic_context_list.argtypes = [P]
@@ -431,6 +446,18 @@ def translate(dna, reverse=False):
     if n < 0:
         raise TatajubaAmdError(_err())
     return out[:n].tobytes().decode()
+
+
+def site_ref_alt(site, allele, k):
+    """the text of a SITE_DTYPE record's REF (allele None) or of one of its ALLELE_DTYPE records' ALT (host only)"""
+    sb = np.asarray(site, SITE_DTYPE).reshape(1).tobytes()
+    ab = None if allele is None else np.asarray(allele, ALLELE_DTYPE).reshape(1).tobytes()
+    n = lib().tjamd_site_ref_alt(sb, ab, k, None, 0)
+    if n < 0:
+        raise TatajubaAmdError("tjamd_site_ref_alt: a site or allele that has no text")
+    out = C.create_string_buffer(n + 1)
+    assert lib().tjamd_site_ref_alt(sb, ab, k, out, n + 1) == n
+    return out.value.decode()
 
 
 def gff3_string(strings, off):
@@ -854,6 +881,19 @@ class Counter:
 
     def last_variant_effects_ms(self):
         return lib().tjamd_last_variant_effects_ms(self._h)
+
+    def merge_variants(self, kmer_size, d_records, n_records, n_samples, n_tracts, d_sites, site_capacity, d_alleles, allele_capacity,
+                       d_genotype=None, d_allele_of=None, d_unique=None):
+        """tjamd_merge_variants on device pointers: n_records VARIANT_DTYPE records -> SITE_DTYPE records at d_sites, ALLELE_DTYPE
+        records at d_alleles; optionally int16 genotypes [site][sample], the allele of every input record (int32) and one
+        VARIANT_DTYPE record per allele.  -> (number of sites, number of alleles)"""
+        n_alleles = C.c_long(-1)
+        n_sites = self._chkn(lib().tjamd_merge_variants(self._h, kmer_size, d_records, n_records, n_samples, n_tracts, d_sites, site_capacity,
+                                                        d_alleles, allele_capacity, d_genotype, d_allele_of, d_unique, C.byref(n_alleles)))
+        return n_sites, n_alleles.value
+
+    def last_merge_variants_ms(self):
+        return lib().tjamd_last_merge_variants_ms(self._h)
 
     def uses_log(self):
         lib().tjamd_counter_uses_log.restype = C.c_int

@@ -40,6 +40,7 @@
 #include "../../include/tatajuba_variants.h"
 #include "../../include/tatajuba_features.h"
 #include "../../include/tatajuba_effects.h"
+#include "../../include/tatajuba_sites.h"
 #include "../../include/tatajuba_locate.h"
 
 typedef unsigned long long u64;
@@ -3870,7 +3871,7 @@ struct StageTimer
 };
 // the intervals of a counter: the last scan call (its partition kernels between the pieces included: tjamd_last_scan_ms takes
 // them out), finalise, the kernels of tjamd_merge_samples, tjamd_tract_stats, tjamd_union_tracts, tjamd_union_tract_stats
-enum { T_SCAN, T_FIN, T_MERGE, T_TRACT, T_UNION, T_UNION_STATS, T_REF, T_LOCATE, T_LOCATED_TRACTS, T_VARIANTS, T_ANNOTATION, T_TRACT_FEATURES, T_SEED_ORDER, T_LOCATE_GAPPED, T_CODING, T_VARIANT_EFFECTS, TJ_N_TIMERS };   // (T_REF to T_LOCATED_TRACTS: N7, T_VARIANTS: N8, the next two: N9; then two of N10; the last two: N11, end of the file)
+enum { T_SCAN, T_FIN, T_MERGE, T_TRACT, T_UNION, T_UNION_STATS, T_REF, T_LOCATE, T_LOCATED_TRACTS, T_VARIANTS, T_ANNOTATION, T_TRACT_FEATURES, T_SEED_ORDER, T_LOCATE_GAPPED, T_CODING, T_VARIANT_EFFECTS, T_MERGE_VARIANTS, TJ_N_TIMERS };   // (T_REF to T_LOCATED_TRACTS: N7, T_VARIANTS: N8, the next two: N9; then two of N10; two of N11; the last: N12, end of the file)
 
 struct tjamd_counter
 {
@@ -8134,3 +8135,317 @@ extern "C" long tjamd_variant_effects (tjamd_counter *c, const tjamd_coding *cod
   return n;
 }
 extern "C" double tjamd_last_variant_effects_ms (tjamd_counter *c) { return c ? c->timer[T_VARIANT_EFFECTS].ms (c->device) : -1.0; }
+
+// ---- N12: the per-sample variant records merged into multi-sample sites ------------------------------------------------
+// The reference leaves this to its user (docs/tutorial.md, "Downstream analyses": sort | uniq over the per-sample VCF files,
+// or bcftools norm / merge); the rule as built is in include/tatajuba_sites.h.  Every record of one tract has the tract's
+// index entry as its anchor, so equal alleles are equal (tract, alt_length, n_flank, alt_flank) and the merge is a stable sort
+// of that key with the input index as value (kv_count_kernel / kv_scatter_kernel, only the 8-bit passes the key's width
+// needs), head flags against the predecessor, two scans, a segmented reduction per site and one writing pass.  Equal keys
+// stay in ascending input index, so an allele's first record is its head.  Thread mapping of the reduction as in
+// locate_kernel / an_paint_kernel: a lane per site walks up to MV_LANE_WALK records itself, a longer site (at most n_samples
+// records, 4096) is handed to the wavefront and reduced with __shfl_xor.  Nothing is written to the caller's buffers before
+// every check has been made: the writing kernels return when the error flag is up.  The flag is the only global atomic.
+// DESIGN.md section 3.5, N12.
+
+struct Site { long long flat; int tract, contig, pos, base, ref_length, min_length, n_flank, n_alleles, first_allele, n_called, first_record, pad; u64 ref_flank; };
+struct Allele { int site, alt_length, n_flank, n_samples, first_record, pad; u64 alt_flank; };
+static_assert (sizeof (Site) == 64 && sizeof (Site) == sizeof (tjamd_site), "site layout");
+static_assert (sizeof (Allele) == 32 && sizeof (Allele) == sizeof (tjamd_allele), "allele layout");
+struct MvAgg { u64 ref_flank; int n_flank, min_length, pos; u32 first_record; };   // what a site's records have in common, before anything is written
+
+#define MV_LANE_WALK   16               // records of a site one lane walks by itself
+#define MV_MAX_SAMPLES 4096
+#define MV_MAX_LENGTH  1023             // alt_length has 10 bits in the key, as in the union's rows
+// err bits: 1 tract, 2 sample, 4 n_flank, 8 alt_length, 16 a (tract, sample) pair twice, 32 the records of a tract disagree, 64 ref_flank
+// (tjamd_merge_variants names them)
+
+__device__ __forceinline__ int mv_nf (int n_flank) { return min (max (n_flank, 0), 32); }   // (a refused n_flank never reaches a shift)
+__device__ __forceinline__ u64 mv_shfl_xor64 (u64 x, int o)
+{
+  const u32 lo = __shfl_xor ((u32) x, o), hi = __shfl_xor ((u32) (x >> 32), o);
+  return ((u64) hi << 32) | lo;
+}
+
+// mode 0: the whole key in one word, (tract, alt_length : 10, n_flank : 6, alt_flank : 2k), and the record's own checks;
+// mode 1: the flank word of a two-word key, and the checks; mode 2: the other word, of record val_in[j] (the order the sort
+// of the flank word left).  A refused record gets key 0.  val[j] = j in modes 0 and 1.
+__global__ void mv_key_kernel (const Variant *__restrict__ rec, long n, int mode, int k, int ns, long n_tracts, const u32 *__restrict__ val_in,
+                               u64 *__restrict__ key, u32 *__restrict__ val, int *__restrict__ err)
+{
+  for (long j = blockIdx.x * (long) blockDim.x + threadIdx.x; j < n; j += (long) gridDim.x * blockDim.x) {
+    const long i = mode == 2 ? (long) val_in[j] : j;
+    const int tract = rec[i].tract, sample = rec[i].sample, la = rec[i].alt_length, nf = rec[i].n_flank;
+    int e = 0;
+    if (tract < 0 || tract >= n_tracts) e |= 1;
+    if (sample < 0 || sample >= ns) e |= 2;
+    if (nf < 0 || nf > k) e |= 4;
+    if (la < 0 || la > MV_MAX_LENGTH) e |= 8;
+    u64 kk = 0;
+    if (!e) {
+      const u64 fl = rec[i].alt_flank & kmask (nf);
+      const u64 rest = ((u64) tract << 16) | ((u64) la << 6) | (u64) nf;
+      kk = mode == 1 ? fl : mode == 2 ? rest : ((rest << (2 * k)) | fl);   // (mode 0: 2k + 16 + the tract's bits <= 64, so 2k <= 48)
+    }
+    key[j] = kk;
+    if (mode != 2) { val[j] = (u32) j; if (e) atomicOr (err, e); }
+  }
+}
+
+// the sorted records against their predecessors: where an allele and where a site begins, the sample of each (for the
+// reduction's check of pairs), and err |= 32 where two records of one tract do not have the same place, base and length
+__global__ void mv_head_kernel (const Variant *__restrict__ rec, const u32 *__restrict__ val, long n, u32 *__restrict__ ahead, u32 *__restrict__ shead,
+                                u32 *__restrict__ smp, int *__restrict__ err)
+{
+  for (long j = blockIdx.x * (long) blockDim.x + threadIdx.x; j < n; j += (long) gridDim.x * blockDim.x) {
+    const Variant *r = rec + val[j];
+    u32 ah = 1u, sh = 1u;
+    if (j > 0) {
+      const Variant *p = rec + val[j - 1];
+      const int nf = mv_nf (r->n_flank);
+      sh = r->tract != p->tract ? 1u : 0u;
+      ah = (sh || r->alt_length != p->alt_length || nf != mv_nf (p->n_flank) || ((r->alt_flank ^ p->alt_flank) & kmask (nf)) != 0ull) ? 1u : 0u;
+      if (!sh && (r->flat != p->flat || r->contig != p->contig || r->base != p->base || r->ref_length != p->ref_length)) atomicOr (err, 32);
+    }
+    ahead[j] = ah; shead[j] = sh; smp[j] = (u32) r->sample;
+  }
+}
+
+// where allele a and site s begin in the sorted order, with the end behind the last of each
+__global__ void mv_start_kernel (long n, const u32 *__restrict__ ahead, const u32 *__restrict__ aex, const u32 *__restrict__ shead, const u32 *__restrict__ sex,
+                                 u32 *__restrict__ astart, u32 *__restrict__ sstart)
+{
+  for (long j = blockIdx.x * (long) blockDim.x + threadIdx.x; j < n; j += (long) gridDim.x * blockDim.x) {
+    if (ahead[j]) astart[aex[j]] = (u32) j;
+    if (shead[j]) sstart[sex[j]] = (u32) j;
+    if (j == n - 1) { astart[aex[j] + ahead[j]] = (u32) n; sstart[sex[j] + shead[j]] = (u32) n; }
+  }
+}
+
+// per site: F = the largest n_flank and the ref_flank of a record that has it (the largest of them: they are equal, or the
+// call is refused), the smallest alt_length, pos and input index; then every record against them: err |= 64 for a ref_flank
+// that differs on the record's own bases, err |= 16 for a sample that comes twice.
+__global__ __launch_bounds__ (256)
+void mv_site_kernel (const Variant *__restrict__ rec, const u32 *__restrict__ val, const u32 *__restrict__ smp, const u32 *__restrict__ sstart,
+                     const u32 *__restrict__ tot, int ns, MvAgg *__restrict__ agg, int *__restrict__ err)
+{
+  __shared__ u32 seen[4][MV_MAX_SAMPLES / 32];          // per wavefront: the samples of the site it is walking
+  if (__any (*(volatile int *) err != 0)) return;       // (a refused sample never reaches `seen`)
+  const long n_sites = tot[1];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const long n_threads = (long) gridDim.x * blockDim.x;
+  for (long s0 = blockIdx.x * (long) blockDim.x + wave * 64; s0 < n_sites; s0 += n_threads) {   // (uniform across a wavefront)
+    const long s = s0 + lane;
+    const bool have = s < n_sites;
+    u32 b = 0, e = 0;
+    if (have) { b = sstart[s]; e = sstart[s + 1]; }
+    const bool crowded = have && (long) e - (long) b > (long) ns;   // more records than samples: one of them comes twice
+    const bool wide = have && !crowded && e - b > (u32) MV_LANE_WALK;
+    if (have && !crowded && !wide) {
+      int F = -1, ml = 0x7fffffff, ps = 0x7fffffff, bad = 0;
+      u32 fr = ~0u;
+      u64 fl = 0;
+      for (u32 j = b; j < e; j++) {
+        const u32 i = val[j];
+        const int nf = mv_nf (rec[i].n_flank);
+        const u64 f = rec[i].ref_flank & kmask (nf);
+        if (nf > F || (nf == F && f > fl)) { F = nf; fl = f; }
+        ml = min (ml, rec[i].alt_length); ps = min (ps, rec[i].pos); fr = min (fr, i);
+      }
+      for (u32 j = b; j < e; j++) {
+        const u32 i = val[j];
+        if (((rec[i].ref_flank ^ fl) & kmask (mv_nf (rec[i].n_flank))) != 0ull) bad |= 64;
+        for (u32 j2 = b; j2 < j; j2++) if (smp[j2] == smp[j]) bad |= 16;
+      }
+      if (bad) atomicOr (err, bad);
+      const MvAgg g = {fl, F, min (ml, rec[val[b]].ref_length), ps, fr};
+      agg[s] = g;
+    }
+    if (crowded) atomicOr (err, 16);
+    u64 todo = __ballot (wide);
+    while (todo) {                                      // the wide sites of these 64, one after the other, all lanes on each
+      const int src = __ffsll ((long long) todo) - 1;
+      todo &= todo - 1ull;
+      const u32 wb = __shfl (b, src), we = __shfl (e, src);
+      int F = -1, ml = 0x7fffffff, ps = 0x7fffffff, bad = 0;
+      u32 fr = ~0u;
+      u64 fl = 0;
+      for (u32 j = wb + lane; j < we; j += 64) {
+        const u32 i = val[j];
+        const int nf = mv_nf (rec[i].n_flank);
+        const u64 f = rec[i].ref_flank & kmask (nf);
+        if (nf > F || (nf == F && f > fl)) { F = nf; fl = f; }
+        ml = min (ml, rec[i].alt_length); ps = min (ps, rec[i].pos); fr = min (fr, i);
+      }
+      for (int o = 32; o; o >>= 1) {
+        const int F2 = __shfl_xor (F, o);
+        const u64 fl2 = mv_shfl_xor64 (fl, o);
+        if (F2 > F || (F2 == F && fl2 > fl)) { F = F2; fl = fl2; }
+        ml = min (ml, __shfl_xor (ml, o)); ps = min (ps, __shfl_xor (ps, o)); fr = min (fr, __shfl_xor (fr, o));
+      }
+      seen[wave][lane] = 0u; seen[wave][lane + 64] = 0u;
+      __threadfence_block ();                           // (one wavefront: its LDS operations keep their order; the fence keeps the compiler's)
+      for (u32 j = wb + lane; j < we; j += 64) {
+        const u32 i = val[j], sm = smp[j];
+        if (((rec[i].ref_flank ^ fl) & kmask (mv_nf (rec[i].n_flank))) != 0ull) bad |= 64;
+        if (sm < (u32) ns && (atomicOr (&seen[wave][sm >> 5], 1u << (sm & 31u)) & (1u << (sm & 31u)))) bad |= 16;
+      }
+      __threadfence_block ();
+      if (bad) atomicOr (err, bad);
+      if (lane == 0) {
+        const MvAgg g = {fl, F, min (ml, rec[val[wb]].ref_length), ps, fr};
+        agg[s0 + src] = g;
+      }
+    }
+  }
+}
+
+// the genotype rows of the sites found, those below the capacity: no record
+__global__ void mv_fill_kernel (const u32 *__restrict__ tot, long site_cap, int ns, int16_t *__restrict__ gt, const int *__restrict__ err)
+{
+  if (*err) return;
+  const long cells = min ((long) tot[1], site_cap) * (long) ns;
+  for (long x = blockIdx.x * (long) blockDim.x + threadIdx.x; x < cells; x += (long) gridDim.x * blockDim.x) gt[x] = (int16_t) -1;
+}
+
+// one thread per sorted record: its allele index and genotype cell; an allele's head writes the allele and its record, a
+// site's head the site.  Nothing at or beyond a capacity.
+__global__ void mv_write_kernel (const Variant *__restrict__ rec, const u32 *__restrict__ val, long n, int ns, const u32 *__restrict__ ahead, const u32 *__restrict__ aex,
+                                 const u32 *__restrict__ shead, const u32 *__restrict__ sex, const u32 *__restrict__ astart, const u32 *__restrict__ sstart,
+                                 const MvAgg *__restrict__ agg, const u32 *__restrict__ tot, Site *__restrict__ sites, long site_cap, Allele *__restrict__ alleles, long allele_cap,
+                                 int16_t *__restrict__ gt, int *__restrict__ allele_of, Variant *__restrict__ unique, const int *__restrict__ err)
+{
+  if (*err) return;
+  const u32 n_alleles = tot[0];
+  for (long j = blockIdx.x * (long) blockDim.x + threadIdx.x; j < n; j += (long) gridDim.x * blockDim.x) {
+    const u32 i = val[j];
+    const Variant r = rec[i];
+    const u32 a = aex[j] + ahead[j] - 1u, s = sex[j] + shead[j] - 1u;
+    const u32 sb = sstart[s], a0 = aex[sb];             // (a site's head is an allele's head: the alleles in front of it are its number)
+    const MvAgg g = agg[s];
+    if (allele_of) allele_of[i] = (int) a;
+    if (gt && (long) s < site_cap) gt[(long) s * ns + r.sample] = (int16_t) (a - a0 + 1u);
+    if (ahead[j] && (long) a < allele_cap) {
+      const u64 own = kmask (mv_nf (r.n_flank));          // (k = 32: kmask, not a shift by 64)
+      Allele o;
+      o.site = (int) s; o.alt_length = r.alt_length; o.n_flank = r.n_flank; o.n_samples = (int) (astart[a + 1] - (u32) j); o.first_record = (int) i; o.pad = 0;
+      o.alt_flank = (r.alt_flank & own) | (g.ref_flank & ~own);
+      alleles[a] = o;
+      if (unique) unique[a] = r;
+    }
+    if (shead[j] && (long) s < site_cap) {
+      const u32 se = sstart[s + 1], a1 = (long) se < n ? aex[se] : n_alleles;
+      Site o;
+      o.flat = r.flat; o.tract = r.tract; o.contig = r.contig; o.pos = g.pos; o.base = r.base; o.ref_length = r.ref_length; o.min_length = g.min_length;
+      o.n_flank = g.n_flank; o.n_alleles = (int) (a1 - a0); o.first_allele = (int) a0; o.n_called = (int) (se - sb); o.first_record = (int) g.first_record; o.pad = 0;
+      o.ref_flank = g.ref_flank;
+      sites[s] = o;
+    }
+  }
+}
+
+static int mv_tract_bits (long n_tracts) { int b = 0; while (b < 31 && (1l << b) < n_tracts) b++; return b; }   // the bits of tract ids below n_tracts
+
+extern "C" long tjamd_merge_variants (tjamd_counter *c, int kmer_size, const tjamd_variant *d_records, long n_records, int n_samples, long n_tracts,
+                                      tjamd_site *d_sites, long site_capacity, tjamd_allele *d_alleles, long allele_capacity,
+                                      int16_t *d_genotype, int *d_allele_of, tjamd_variant *d_unique, long *h_n_alleles)
+{
+  static const char *fn = "tjamd_merge_variants";
+  const long n = n_records;
+  auto refused = [&] () -> int {                        // the checks that read no handle, the device last
+    if (!c) return set_err (TJAMD_ERR_ARG, "%s: null counter", fn);
+    if (n < 0 || n >= (1l << 31)) return set_err (TJAMD_ERR_ARG, "%s: n_records %ld outside 0..2^31-1", fn, n);
+    if (n_samples < 1 || n_samples > MV_MAX_SAMPLES) return set_err (TJAMD_ERR_ARG, "%s: n_samples %d outside 1..4096", fn, n_samples);
+    if (kmer_size < 2 || kmer_size > 32) return set_err (TJAMD_ERR_ARG, "%s: kmer_size %d outside [2,32]", fn, kmer_size);
+    if (n_tracts < 0) return set_err (TJAMD_ERR_ARG, "%s: n_tracts %ld < 0", fn, n_tracts);
+    if (site_capacity < 0 || allele_capacity < 0) return set_err (TJAMD_ERR_ARG, "%s: capacities %ld and %ld", fn, site_capacity, allele_capacity);
+    if (n > 0 && !d_records) return set_err (TJAMD_ERR_ARG, "%s: null record buffer", fn);
+    if ((site_capacity > 0 && !d_sites) || (allele_capacity > 0 && !d_alleles)) return set_err (TJAMD_ERR_ARG, "%s: null site or allele buffer", fn);
+    if (!h_n_alleles) return set_err (TJAMD_ERR_ARG, "%s: null h_n_alleles", fn);
+    if (tjamd_device_count () <= 0) return set_err (TJAMD_ERR_NO_DEVICE, "%s: TJAMD_ERR_NO_DEVICE: no HIP device visible (the records are merged on the device; no CPU fallback)", fn);
+    return TJAMD_OK;
+  };
+  int rc = refused ();
+  if (c && tjamd_device_count () > 0) c->timer[T_MERGE_VARIANTS].timed = false;   // a refused call leaves no timing behind (without a device there is no counter)
+  if (rc) return -rc;
+  if (hipSetDevice (c->device) != hipSuccess) return -set_err (TJAMD_ERR_HIP, "hipSetDevice failed");
+  if (n == 0) { *h_n_alleles = 0; return 0; }
+  const int k = kmer_size, tbits = mv_tract_bits (n_tracts);
+  const bool one_word = tbits + 16 + 2 * k <= 64;
+  const int nblk = (int) ((n + RS_ITEMS - 1) / RS_ITEMS);
+  LcCut cut (nullptr);
+  u64 *key[2] = {nullptr, nullptr}; u32 *val[2] = {nullptr, nullptr}, *ahead = nullptr, *shead = nullptr, *aex = nullptr, *sex = nullptr, *smp = nullptr,
+      *astart = nullptr, *sstart = nullptr, *tot = nullptr;
+  MvAgg *agg = nullptr;
+  for (int pass = 0; pass < 2; pass++) {
+    cut = LcCut (pass ? c->lc_work.p : nullptr);
+    key[0] = cut.take<u64> (n); key[1] = cut.take<u64> (n); val[0] = cut.take<u32> (n); val[1] = cut.take<u32> (n);
+    ahead = cut.take<u32> (n); shead = cut.take<u32> (n); aex = cut.take<u32> (n); sex = cut.take<u32> (n); smp = cut.take<u32> (n);
+    astart = cut.take<u32> ((size_t) n + 1); sstart = cut.take<u32> ((size_t) n + 1); agg = cut.take<MvAgg> (n); tot = cut.take<u32> (64);
+    if (!pass) {
+      rc = ensure (c->lc_work, cut.used, c->stream);
+      if (!rc) rc = ensure (c->hist, (size_t) 256 * nblk * 4, c->stream);
+      if (!rc) rc = ensure (c->scan_tmp, std::max (scan_tmp_words (256l * nblk), scan_tmp_words (n)) * 4 + 64, c->stream);
+      if (rc) return -rc;
+    }
+  }
+  u32 *tmp = (u32 *) c->scan_tmp.p; const size_t tw = c->scan_tmp.cap / 4;
+  int *err = (int *) tot + 2;                           // tot: the alleles, the sites, the error flag
+  if (hipMemsetAsync (tot, 0, 256, c->stream) != hipSuccess) return -set_err (TJAMD_ERR_HIP, "%s: memset failed", fn);
+  (void) c->timer[T_MERGE_VARIANTS].begin (c->stream);
+  const Variant *rec = (const Variant *) d_records;
+  const unsigned grid = grid_for (n);
+  auto sort_passes = [&] (int bits) -> int {            // stable, on the low `bits` of key[0]: the result is in key[0], val[0] again
+    for (int p = 0; p < (bits + 7) / 8; p++) {
+      hipLaunchKernelGGL (kv_count_kernel, dim3 (nblk), dim3 (256), 0, c->stream, (const u64 *) key[0], n, p, (u32 *) c->hist.p, nblk);
+      const int r = exclusive_scan (c, (const u32 *) c->hist.p, (u32 *) c->hist.p, 256l * nblk, nullptr, tmp, tw);
+      if (r) return r;
+      hipLaunchKernelGGL (kv_scatter_kernel, dim3 (nblk), dim3 (256), 0, c->stream, (const u64 *) key[0], (const u32 *) val[0], key[1], val[1], n, p,
+                          (const u32 *) c->hist.p, nblk);
+      std::swap (key[0], key[1]); std::swap (val[0], val[1]);
+    }
+    return TJAMD_OK;
+  };
+  if (one_word) {
+    hipLaunchKernelGGL (mv_key_kernel, dim3 (grid), dim3 (256), 0, c->stream, rec, n, 0, k, n_samples, n_tracts, (const u32 *) nullptr, key[0], val[0], err);
+    rc = sort_passes (tbits + 16 + 2 * k);
+  } else {                                              // the flank word first, then the rest: the second sort keeps the first one's order
+    hipLaunchKernelGGL (mv_key_kernel, dim3 (grid), dim3 (256), 0, c->stream, rec, n, 1, k, n_samples, n_tracts, (const u32 *) nullptr, key[0], val[0], err);
+    rc = sort_passes (2 * k);
+    if (!rc) {
+      hipLaunchKernelGGL (mv_key_kernel, dim3 (grid), dim3 (256), 0, c->stream, rec, n, 2, k, n_samples, n_tracts, (const u32 *) val[0], key[0], (u32 *) nullptr, err);
+      rc = sort_passes (tbits + 16);
+    }
+  }
+  if (rc) return -rc;
+  hipLaunchKernelGGL (mv_head_kernel, dim3 (grid), dim3 (256), 0, c->stream, rec, (const u32 *) val[0], n, ahead, shead, smp, err);
+  rc = exclusive_scan (c, ahead, aex, n, tot, tmp, tw);
+  if (!rc) rc = exclusive_scan (c, shead, sex, n, tot + 1, tmp, tw);
+  if (rc) return -rc;
+  hipLaunchKernelGGL (mv_start_kernel, dim3 (grid), dim3 (256), 0, c->stream, n, (const u32 *) ahead, (const u32 *) aex, (const u32 *) shead, (const u32 *) sex, astart, sstart);
+  hipLaunchKernelGGL (mv_site_kernel, dim3 (grid), dim3 (256), 0, c->stream, rec, (const u32 *) val[0], (const u32 *) smp, (const u32 *) sstart, (const u32 *) tot, n_samples, agg, err);
+  if (d_genotype)
+    hipLaunchKernelGGL (mv_fill_kernel, dim3 (grid_for (std::min (n, site_capacity) * (long) n_samples)), dim3 (256), 0, c->stream, (const u32 *) tot, site_capacity, n_samples,
+                        d_genotype, (const int *) err);
+  hipLaunchKernelGGL (mv_write_kernel, dim3 (grid), dim3 (256), 0, c->stream, rec, (const u32 *) val[0], n, n_samples, (const u32 *) ahead, (const u32 *) aex,
+                      (const u32 *) shead, (const u32 *) sex, (const u32 *) astart, (const u32 *) sstart, (const MvAgg *) agg, (const u32 *) tot,
+                      (Site *) d_sites, site_capacity, (Allele *) d_alleles, allele_capacity, d_genotype, d_allele_of, (Variant *) d_unique, (const int *) err);
+  if (hipGetLastError () != hipSuccess) return -set_err (TJAMD_ERR_HIP, "%s: launch failed", fn);
+  (void) c->timer[T_MERGE_VARIANTS].end (c->stream);
+  u32 h[3] = {0, 0, 0};
+  if (hipMemcpyAsync (h, tot, 12, hipMemcpyDeviceToHost, c->stream) != hipSuccess || hipStreamSynchronize (c->stream) != hipSuccess)
+    return -set_err (TJAMD_ERR_HIP, "%s: failed: %s", fn, hipGetErrorString (hipGetLastError ()));
+  if (h[2] & 1u) return -set_err (TJAMD_ERR_ARG, "%s: a record's tract is outside [0, %ld)", fn, n_tracts);
+  if (h[2] & 2u) return -set_err (TJAMD_ERR_ARG, "%s: a record's sample is outside [0, %d)", fn, n_samples);
+  if (h[2] & 4u) return -set_err (TJAMD_ERR_ARG, "%s: a record's n_flank is outside 0..%d", fn, k);
+  if (h[2] & 8u) return -set_err (TJAMD_ERR_ARG, "%s: a record's alt_length is outside 0..%d", fn, MV_MAX_LENGTH);
+  if (h[2] & 32u) return -set_err (TJAMD_ERR_ARG, "%s: records of one tract disagree in flat, contig, base or ref_length", fn);
+  if (h[2] & 16u) return -set_err (TJAMD_ERR_ARG, "%s: a (tract, sample) pair occurs twice", fn);
+  if (h[2] & 64u) return -set_err (TJAMD_ERR_ARG, "%s: records of one tract disagree in ref_flank on their own n_flank bases", fn);
+  if ((long) h[1] > site_capacity || (long) h[0] > allele_capacity)
+    return -set_err (TJAMD_ERR_CAPACITY, "%s: %u sites and %u alleles, caller capacities %ld and %ld", fn, h[1], h[0], site_capacity, allele_capacity);
+  *h_n_alleles = (long) h[0];
+  c->timer[T_MERGE_VARIANTS].timed = true;
+  return (long) h[1];
+}
+extern "C" double tjamd_last_merge_variants_ms (tjamd_counter *c) { return c ? c->timer[T_MERGE_VARIANTS].ms (c->device) : -1.0; }

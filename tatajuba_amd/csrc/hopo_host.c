@@ -10,6 +10,7 @@
 #include "../../include/tatajuba_variants.h"
 #include "../../include/tatajuba_features.h"
 #include "../../include/tatajuba_effects.h"
+#include "../../include/tatajuba_sites.h"
 #include <pthread.h>
 #include <sched.h>
 #include <sys/stat.h>
@@ -381,6 +382,26 @@ long
 tjamd_gff3_read_phase (const char *path, const char *contig_names, long n_contigs, signed char *out, long capacity)
 {
   return tjg_read_phase (path, contig_names, n_contigs, out, capacity);
+}
+
+/* REF or an allele's ALT of a merged site as text (the rule is in tatajuba_sites.h): B^(length - min_length + 1), then the
+ * first F bases of the flank word */
+int
+tjamd_site_ref_alt (const tjamd_site *site, const tjamd_allele *allele, int kmer_size, char *out, int capacity)
+{
+  long run, total, j;
+  uint64_t flank;
+  if (!site || kmer_size < 1 || kmer_size > 32 || site->n_flank < 0 || site->n_flank > kmer_size || site->base < 0 || site->base > 3) return -1;
+  run = (long) (allele ? allele->alt_length : site->ref_length) - (long) site->min_length + 1;
+  if (run < 1 || run > (1l << 30)) return -1;
+  flank = allele ? allele->alt_flank : site->ref_flank;
+  total = run + site->n_flank;
+  if (out && (long) capacity > total) {
+    for (j = 0; j < run; j++) out[j] = "ACGT"[site->base];
+    for (j = 0; j < site->n_flank; j++) out[run + j] = "ACGT"[(flank >> (2 * j)) & 3];
+    out[total] = '\0';
+  }
+  return (int) total;
 }
 
 /* the multi-threaded feeder into host memory (tests compare it with tjamd_read_file_stream) */
