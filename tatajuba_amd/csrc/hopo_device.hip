@@ -35,6 +35,7 @@
 #include <float.h>
 #include <algorithm>
 #include <vector>
+#include <memory>
 
 #include "../../include/tatajuba_amd.h"
 #include "../../include/tatajuba_variants.h"
@@ -3950,6 +3951,51 @@ static int ensure (DevBuf &b, size_t bytes, hipStream_t stream, size_t keep_byte
 
 static void release (DevBuf &b) { if (b.p) (void) hipFree (b.p); b.p = nullptr; b.cap = 0; }
 
+// One call's use of a timer of its counter.  Construction clears `timed` (where the entry does that relative to its checks is
+// the entry's choice; a null counter, or one that stands for a counter where there is no device, is left alone), begin ()
+// and end () record on the counter's stream, done () marks the interval as good.  A call that leaves by any other way has
+// no timing: "a failed call leaves no timing behind" holds without the author's care.
+struct Stage
+{
+  tjamd_counter *c; StageTimer *t;
+  Stage (tjamd_counter *c_, int slot) : c (c_), t (c_ && tjamd_device_count () > 0 ? &c_->timer[slot] : nullptr) { if (t) t->timed = false; }
+  void begin () { (void) t->begin (c->stream); }
+  void end () { (void) t->end (c->stream); }
+  void done () { t->timed = true; }
+};
+
+// The scratch of one call, cut from c->lc_work: each piece is listed once, in the order it lies in the block, on a 256-byte
+// boundary.  take () only notes the caller's pointer and the piece's offset; commit () grows the block once (which may
+// free and replace it) and then hands every piece out.  Until then the pointers hold nothing.
+struct ScratchCut
+{
+  struct Piece { void *at; size_t offset; void (*put) (void *at, char *p); } piece[16];
+  int n = 0; size_t used = 0;
+  template <class T> void take (T *&p, size_t count)
+  {
+    p = nullptr;
+    if (n < 16) piece[n] = Piece {&p, used, [] (void *at, char *q) { *(T **) at = (T *) q; }};
+    n++; used += (count * sizeof (T) + 255) & ~(size_t) 255;
+  }
+  int commit (tjamd_counter *c)
+  {
+    if (n > 16) return set_err (TJAMD_ERR_STATE, "a scratch cut of %d pieces (16 at most)", n);
+    const int rc = ensure (c->lc_work, used, c->stream);
+    for (int i = 0; i < n && !rc; i++) piece[i].put (piece[i].at, (char *) c->lc_work.p + piece[i].offset);
+    return rc;
+  }
+};
+
+// The tail of a call, behind its stage's end (): the error of its launches, the copy of `words` 32-bit words from d to the
+// host (none: the wait alone) on the counter's stream, the wait for the stream.  Decoding the words is the caller's.
+static int read_back (tjamd_counter *c, const char *fn, const void *d, void *h, size_t words)
+{
+  hipError_t e = hipGetLastError ();
+  if (e == hipSuccess && words) e = hipMemcpyAsync (h, d, words * 4, hipMemcpyDeviceToHost, c->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize (c->stream);
+  return e == hipSuccess ? TJAMD_OK : set_err (TJAMD_ERR_HIP, "%s: failed: %s", fn, hipGetErrorString (e));
+}
+
 extern "C" tjamd_counter *tjamd_counter_create (int device, int kmer_size)
 {
   int n = tjamd_device_count ();
@@ -5221,7 +5267,7 @@ static int queue_group_heads (tjamd_counter *c, const char *who, const u64 *keys
                                 head, (const u32 *) c->keep.p, (int *) c->grp_jt.p, count_of, lev_of);
     if (n_cand) *n_cand = (long) nc;
   }
-  return exclusive_scan (c, (const u32 *) head, (u32 *) c->outpos.p, n, total, (u32 *) c->scan_tmp.p, scan_tmp_words (n));
+  return exclusive_scan (c, (const u32 *) head, (u32 *) c->outpos.p, n, total, (u32 *) c->scan_tmp.p, c->scan_tmp.cap / 4);
 }
 
 extern "C" long tjamd_group_contexts (tjamd_counter *c, int max_distance_per_flank, int *group_of, tjamd_group *groups, long capacity)
@@ -5241,10 +5287,9 @@ extern "C" long tjamd_group_contexts (tjamd_counter *c, int max_distance_per_fla
   if (rc) return -rc;
   hipLaunchKernelGGL (group_summary_kernel, dim3 (grid_for (n)), dim3 (256), 0, c->stream, kept, n, (const u32 *) c->flags.p, (const u32 *) c->outpos.p,
                       (int *) c->segid.p, (GroupOut *) c->alt.p);
-  if (hipGetLastError () != hipSuccess) return -set_err (TJAMD_ERR_HIP, "grouping launch failed");
   u32 ng = 0;
-  if (hipMemcpyAsync (&ng, scan_total (c, n), 4, hipMemcpyDeviceToHost, c->stream) != hipSuccess || hipStreamSynchronize (c->stream) != hipSuccess)
-    return -set_err (TJAMD_ERR_HIP, "grouping failed: %s", hipGetErrorString (hipGetLastError ()));
+  rc = read_back (c, "tjamd_group_contexts", scan_total (c, n), &ng, 1);
+  if (rc) return -rc;
   if ((long) ng > capacity && groups) return -set_err (TJAMD_ERR_CAPACITY, "%u groups, caller capacity %ld", ng, capacity);
   if (group_of && hipMemcpy (group_of, c->segid.p, (size_t) n * 4, hipMemcpyDeviceToHost) != hipSuccess) return -set_err (TJAMD_ERR_HIP, "copy failed");
   if (groups && hipMemcpy (groups, c->alt.p, (size_t) ng * sizeof (GroupOut), hipMemcpyDeviceToHost) != hipSuccess) return -set_err (TJAMD_ERR_HIP, "copy failed");
@@ -5311,10 +5356,9 @@ extern "C" long tjamd_context_histograms (tjamd_counter *c, int max_distance_per
   if (rc) return -rc;
   hipLaunchKernelGGL (group_histogram_kernel, dim3 (grid_for (n)), dim3 (256), 0, c->stream, kept, n, (const u32 *) c->flags.p, (const u32 *) c->outpos.p,
                       (int *) c->grp_jt.p, (int *) c->segid.p, (CtxGroupOut *) c->alt.p, (LenFreq *) c->grp_hist.p);
-  if (hipGetLastError () != hipSuccess) return -set_err (TJAMD_ERR_HIP, "grouping launch failed");
   u32 ng = 0;
-  if (hipMemcpyAsync (&ng, scan_total (c, n), 4, hipMemcpyDeviceToHost, c->stream) != hipSuccess || hipStreamSynchronize (c->stream) != hipSuccess)
-    return -set_err (TJAMD_ERR_HIP, "grouping failed: %s", hipGetErrorString (hipGetLastError ()));
+  rc = read_back (c, "tjamd_context_histograms", scan_total (c, n), &ng, 1);
+  if (rc) return -rc;
   if ((long) ng > capacity && groups) return -set_err (TJAMD_ERR_CAPACITY, "%u groups, caller capacity %ld", ng, capacity);
   if (group_of && hipMemcpy (group_of, c->segid.p, (size_t) n * 4, hipMemcpyDeviceToHost) != hipSuccess) return -set_err (TJAMD_ERR_HIP, "copy failed");
   if (join_type && hipMemcpy (join_type, c->grp_jt.p, (size_t) n * 4, hipMemcpyDeviceToHost) != hipSuccess) return -set_err (TJAMD_ERR_HIP, "copy failed");
@@ -5349,7 +5393,7 @@ static int ensure_tract_id_scratch (tjamd_counter *c, long n)
 static int queue_tract_ids (tjamd_counter *c, const void *d_keys, long n, int *ids, u32 *total)
 {
   hipLaunchKernelGGL (tract_head_kernel, dim3 (grid_for (n)), dim3 (256), 0, c->stream, (const u64 *) d_keys, n, (u32 *) c->flags.p);
-  int rc = exclusive_scan (c, (const u32 *) c->flags.p, (u32 *) c->outpos.p, n, total, (u32 *) c->scan_tmp.p, scan_tmp_words (n));
+  int rc = exclusive_scan (c, (const u32 *) c->flags.p, (u32 *) c->outpos.p, n, total, (u32 *) c->scan_tmp.p, c->scan_tmp.cap / 4);
   if (rc) return rc;
   hipLaunchKernelGGL (tract_id_kernel, dim3 (grid_for (n)), dim3 (256), 0, c->stream, (const u32 *) c->outpos.p, (const u32 *) c->flags.p, n, ids);
   if (hipGetLastError () != hipSuccess) return set_err (TJAMD_ERR_HIP, "tract id launch failed");
@@ -5368,8 +5412,8 @@ extern "C" long tjamd_tract_ids (tjamd_counter *c, const void *d_keys, long n, i
   rc = queue_tract_ids (c, d_keys, n, ids, total);
   if (rc) return -rc;
   u32 nh = 0;
-  if (hipMemcpyAsync (&nh, total, 4, hipMemcpyDeviceToHost, c->stream) != hipSuccess || hipStreamSynchronize (c->stream) != hipSuccess)
-    return -set_err (TJAMD_ERR_HIP, "tract ids failed: %s", hipGetErrorString (hipGetLastError ()));
+  rc = read_back (c, "tjamd_tract_ids", total, &nh, 1);
+  if (rc) return -rc;
   if (h_tract_id && hipMemcpy (h_tract_id, ids, (size_t) n * 4, hipMemcpyDeviceToHost) != hipSuccess) return -set_err (TJAMD_ERR_HIP, "copy failed");
   return (long) nh + 1;
 }
@@ -5601,8 +5645,8 @@ extern "C" long tjamd_tract_stats (tjamd_counter *c, const void *d_keys, const v
   rc = ensure_tract_id_scratch (c, n_union);
   if (!rc) rc = upload_coverage (c, coverage, n_samples);
   if (rc) return -rc;
-  c->timer[T_TRACT].timed = false;                      // (a failed call leaves no timing behind)
-  (void) c->timer[T_TRACT].begin (c->stream);
+  Stage st (c, T_TRACT);
+  st.begin ();
   u32 *total = scan_total (c, n_union);
   const int *ids = d_tract_id;
   if (!ids) {                                           // the context-keyed ids of tjamd_tract_ids, in c->segid
@@ -5616,12 +5660,12 @@ extern "C" long tjamd_tract_stats (tjamd_counter *c, const void *d_keys, const v
   hipLaunchKernelGGL (tract_stats_kernel, dim3 (tract_grid (n_bound, S)), dim3 (256), 0, c->stream, (const u64 *) d_keys, (const int *) d_counts, n_union,
                       n_samples, S, (const int *) c->ts_cov.p, d_ref_length, (TractSummary *) d_summary, n_bound, err, (u32 *) c->flags.p);
   if (hipGetLastError () != hipSuccess) return -set_err (TJAMD_ERR_HIP, "tract stats launch failed");
-  rc = exclusive_scan (c, (const u32 *) c->flags.p, (u32 *) c->outpos.p, n_bound, total, (u32 *) c->scan_tmp.p, scan_tmp_words (n_bound));
+  rc = exclusive_scan (c, (const u32 *) c->flags.p, (u32 *) c->outpos.p, n_bound, total, (u32 *) c->scan_tmp.p, c->scan_tmp.cap / 4);
   if (rc) return -rc;
   if (d_var) hipLaunchKernelGGL (tract_var_scatter_kernel, dim3 (grid_for (n_bound)), dim3 (256), 0, c->stream, (const u32 *) c->flags.p, (const u32 *) c->outpos.p,
                                  n_bound, d_var);
   if (hipGetLastError () != hipSuccess) return -set_err (TJAMD_ERR_HIP, "tract list launch failed");
-  (void) c->timer[T_TRACT].end (c->stream);
+  st.end ();
   int h_err[3] = {0, 0, 0};
   u32 nv = 0;
   if (hipMemcpyAsync (h_err, err, 12, hipMemcpyDeviceToHost, c->stream) != hipSuccess || hipMemcpyAsync (&nv, total, 4, hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
@@ -5629,7 +5673,7 @@ extern "C" long tjamd_tract_stats (tjamd_counter *c, const void *d_keys, const v
   const long n_tracts = (long) h_err[1] + 1;
   if (h_err[0] || h_err[2] || n_tracts < 1) return -set_err (TJAMD_ERR_ARG, "tjamd_tract_stats: tract ids must start at 0 and go up by 0 or 1 per row");
   if (n_tracts > capacity) return -set_err (TJAMD_ERR_CAPACITY, "tjamd_tract_stats: %ld tracts, caller capacity %ld", n_tracts, capacity);
-  c->timer[T_TRACT].timed = true;
+  st.done ();
   if (n_var) *n_var = (long) nv;
   return n_tracts;
 }
@@ -5651,8 +5695,8 @@ extern "C" long tjamd_tract_sample_stats (tjamd_counter *c, const void *d_keys, 
   int *err = (int *) c->ts_aux.p, h_err = 0;
   hipLaunchKernelGGL (tract_sample_stats_kernel, dim3 (tract_grid (n_list, S)), dim3 (256), 0, c->stream, (const u64 *) d_keys, (const int *) d_counts, n_union,
                       n_samples, S, (const int *) c->ts_cov.p, (const TractSummary *) d_summary, n_tracts, d_list, n_list, d_values, d_modal_len, d_n_context, err);
-  if (hipGetLastError () != hipSuccess || hipMemcpyAsync (&h_err, err, 4, hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
-      hipStreamSynchronize (c->stream) != hipSuccess) return -set_err (TJAMD_ERR_HIP, "tract sample stats failed: %s", hipGetErrorString (hipGetLastError ()));
+  rc = read_back (c, "tjamd_tract_sample_stats", err, &h_err, 1);
+  if (rc) return -rc;
   if (h_err) return -set_err (TJAMD_ERR_ARG, "tjamd_tract_sample_stats: a listed tract id is outside [0, %ld) or its rows outside the union", n_tracts);
   return n_list;
 }
@@ -5723,7 +5767,8 @@ extern "C" long tjamd_union_tracts (tjamd_counter *c, const void *d_keys, const 
   if (capacity < (n_union > 0 ? 1 : 0)) return -set_err (TJAMD_ERR_CAPACITY, "%s: capacity %ld for a union of %ld rows", fn, capacity, n_union);
   if (!c) return -set_err (TJAMD_ERR_ARG, "%s: null counter", fn);
   if (hipSetDevice (c->device) != hipSuccess) return -set_err (TJAMD_ERR_HIP, "hipSetDevice failed");
-  c->timer[T_UNION].timed = false; c->union_cand = -1;  // (a failed call leaves no timing behind)
+  Stage st (c, T_UNION);
+  c->union_cand = -1;
   const long n = n_union;
   if (n == 0) return 0;
   rc = ensure_group_scratch (c, n, true);
@@ -5731,7 +5776,7 @@ extern "C" long tjamd_union_tracts (tjamd_counter *c, const void *d_keys, const 
   if (!rc) rc = ensure (c->ut_lev, (size_t) n * 4, c->stream);
   if (rc) return -rc;
   long long *tot = (long long *) c->ut_tot.p;
-  (void) c->timer[T_UNION].begin (c->stream);
+  st.begin ();
   const int S = tract_segment (n_samples);
   hipLaunchKernelGGL (union_totals_kernel, dim3 (tract_grid (n, S)), dim3 (256), 0, c->stream, (const int *) d_counts, n, n_samples, S, tot);
   long n_cand = 0;
@@ -5740,13 +5785,13 @@ extern "C" long tjamd_union_tracts (tjamd_counter *c, const void *d_keys, const 
   if (rc) return -rc;
   hipLaunchKernelGGL (union_tract_kernel, dim3 (grid_for (n)), dim3 (256), 0, c->stream, n, (const long long *) tot, (const u32 *) c->flags.p,
                       (const u32 *) c->outpos.p, (const int *) c->grp_jt.p, (const int *) c->ut_lev.p, capacity, d_tract_id, d_join_type, (UnionTract *) d_tracts);
-  if (hipGetLastError () != hipSuccess) return -set_err (TJAMD_ERR_HIP, "%s: tract launch failed", fn);
-  (void) c->timer[T_UNION].end (c->stream);
+  st.end ();
   u32 ng = 0;
-  if (hipMemcpyAsync (&ng, scan_total (c, n), 4, hipMemcpyDeviceToHost, c->stream) != hipSuccess || hipStreamSynchronize (c->stream) != hipSuccess)
-    return -set_err (TJAMD_ERR_HIP, "%s: grouping failed: %s", fn, hipGetErrorString (hipGetLastError ()));
+  rc = read_back (c, fn, scan_total (c, n), &ng, 1);
+  if (rc) return -rc;
   if ((long) ng > capacity) return -set_err (TJAMD_ERR_CAPACITY, "%s: %u tracts, caller capacity %ld", fn, ng, capacity);
-  c->timer[T_UNION].timed = true; c->union_cand = n_cand;
+  st.done ();
+  c->union_cand = n_cand;
   return (long) ng;
 }
 
@@ -5952,7 +5997,7 @@ extern "C" long tjamd_union_tract_stats (tjamd_counter *c, const void *d_keys, c
   if (n_var) *n_var = 0;
   if (n_sel) *n_sel = 0;
   if (hipSetDevice (c->device) != hipSuccess) return -set_err (TJAMD_ERR_HIP, "hipSetDevice failed");
-  c->timer[T_UNION_STATS].timed = false;
+  Stage st (c, T_UNION_STATS);
   if (n_union == 0) return 0;
   const long nt = n_tracts;
   rc = ensure (c->flags, (size_t) nt * 4, c->stream);               // variable flags, then their positions in outpos
@@ -5965,7 +6010,7 @@ extern "C" long tjamd_union_tract_stats (tjamd_counter *c, const void *d_keys, c
   if (!rc) rc = ensure_union_fallback (c, nt, g_cnt, g_len);
   if (!rc) rc = upload_coverage (c, coverage, n_samples);
   if (rc) return -rc;
-  (void) c->timer[T_UNION_STATS].begin (c->stream);
+  st.begin ();
   u32 *total = scan_total (c, nt);
   int *err = (int *) c->ts_aux.p;
   const int S = tract_segment (n_samples);
@@ -5977,19 +6022,19 @@ extern "C" long tjamd_union_tract_stats (tjamd_counter *c, const void *d_keys, c
   launch (union_tract_stats_kernel<false>, tract_grid (nt, S));
   launch (union_tract_stats_kernel<true>, (unsigned) UT_FULL_BLOCKS);
   if (hipGetLastError () != hipSuccess) return -set_err (TJAMD_ERR_HIP, "%s: launch failed", fn);
-  rc = exclusive_scan (c, vf, (u32 *) c->outpos.p, nt, total, (u32 *) c->scan_tmp.p, scan_tmp_words (nt));
-  if (!rc) rc = exclusive_scan (c, sf, (u32 *) c->headpos.p, nt, total + 1, (u32 *) c->scan_tmp.p, scan_tmp_words (nt));
+  rc = exclusive_scan (c, vf, (u32 *) c->outpos.p, nt, total, (u32 *) c->scan_tmp.p, c->scan_tmp.cap / 4);
+  if (!rc) rc = exclusive_scan (c, sf, (u32 *) c->headpos.p, nt, total + 1, (u32 *) c->scan_tmp.p, c->scan_tmp.cap / 4);
   if (rc) return -rc;
   if (d_var) hipLaunchKernelGGL (tract_var_scatter_kernel, dim3 (grid_for (nt)), dim3 (256), 0, c->stream, (const u32 *) vf, (const u32 *) c->outpos.p, nt, d_var);
   if (d_sel) hipLaunchKernelGGL (tract_var_scatter_kernel, dim3 (grid_for (nt)), dim3 (256), 0, c->stream, (const u32 *) sf, (const u32 *) c->headpos.p, nt, d_sel);
   if (hipGetLastError () != hipSuccess) return -set_err (TJAMD_ERR_HIP, "%s: list launch failed", fn);
-  (void) c->timer[T_UNION_STATS].end (c->stream);
+  st.end ();
   int h_err = 0;
   u32 h_tot[2] = {0, 0};
   if (hipMemcpyAsync (&h_err, err, 4, hipMemcpyDeviceToHost, c->stream) != hipSuccess || hipMemcpyAsync (h_tot, total, 8, hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
       hipStreamSynchronize (c->stream) != hipSuccess) return -set_err (TJAMD_ERR_HIP, "%s: failed: %s", fn, hipGetErrorString (hipGetLastError ()));
   if (h_err) return -set_err (TJAMD_ERR_ARG, "%s: the tracts must tile the union (first 0, each starting where the one before ends, the last ending at row %ld)", fn, n_union);
-  c->timer[T_UNION_STATS].timed = true;
+  st.done ();
   if (n_var) *n_var = (long) h_tot[0];
   if (n_sel) *n_sel = (long) h_tot[1];
   return nt;
@@ -6020,8 +6065,8 @@ extern "C" long tjamd_union_tract_sample_stats (tjamd_counter *c, const void *d_
   };
   launch (union_tract_sample_stats_kernel<false>, tract_grid (n_list, S));
   launch (union_tract_sample_stats_kernel<true>, (unsigned) UT_FULL_BLOCKS);
-  if (hipGetLastError () != hipSuccess || hipMemcpyAsync (&h_err, err, 4, hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
-      hipStreamSynchronize (c->stream) != hipSuccess) return -set_err (TJAMD_ERR_HIP, "%s: failed: %s", fn, hipGetErrorString (hipGetLastError ()));
+  rc = read_back (c, fn, err, &h_err, 1);
+  if (rc) return -rc;
   if (h_err) return -set_err (TJAMD_ERR_ARG, "%s: a listed tract id is outside [0, %ld) or its rows outside the union", fn, n_tracts);
   return n_list;
 }
@@ -6138,7 +6183,8 @@ extern "C" long tjamd_merge_samples (tjamd_counter *c, const void *d_records, co
   u32 *tpos = (u32 *) c->headpos.p, *ttot = (u32 *) c->outpos.p;
   if (!c->bins_zeroed && hipMemsetAsync (bins, 0, (size_t) BS_MAXBINS * 4, c->stream) != hipSuccess) return -set_err (TJAMD_ERR_HIP, "memset failed");
   c->bins_zeroed = false;
-  (void) c->timer[T_MERGE].begin (c->stream);
+  Stage st (c, T_MERGE);
+  st.begin ();
   hipLaunchKernelGGL (bin_count_kernel, dim3 (grid_for (n)), dim3 (256), 0, c->stream, (const u64 *) d_records, n, c->k, nbits, bins, (uint4 *) nullptr, 0l, 1);
   hipLaunchKernelGGL (bin_scan_kernel, dim3 (1), dim3 (1024), 0, c->stream, bins, nbins, binstart,
                       c->bin_rank_max < (u32) BS_RANK_MAX ? c->bin_rank_max : (u32) MG_RANK_MAX, c->d_fin);   // (test hook: see TATAJUBA_AMD_BIN_MAX)
@@ -6151,8 +6197,8 @@ extern "C" long tjamd_merge_samples (tjamd_counter *c, const void *d_records, co
                       (const u32 *) binout, nbins, (const FinCounts *) c->d_fin, (const u32 *) tpos, (const u32 *) ttot, n_samples,
                       (u64 *) d_out_keys, (int *) d_out_counts, capacity);
   if (hipGetLastError () != hipSuccess) return -set_err (TJAMD_ERR_HIP, "merge launch failed");
-  (void) c->timer[T_MERGE].end (c->stream);
-  c->timer[T_MERGE].timed = true;
+  st.end ();
+  st.done ();                                           // (the merge's own time, whatever the read-back below finds)
   if (hipMemcpyAsync (c->h_fin, c->d_fin, sizeof (FinCounts), hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
       hipStreamSynchronize (c->stream) != hipSuccess) return -set_err (TJAMD_ERR_HIP, "merge failed: %s", hipGetErrorString (hipGetLastError ()));
   if (c->h_fin->sort_fallback) return merge_samples_radix (c, d_records, n, n_samples, d_out_keys, d_out_counts, capacity);
@@ -6579,14 +6625,6 @@ __global__ void ref_entry_kernel (const uint8_t *__restrict__ seq, long n, int k
   }
 }
 
-// scratch of the three entries: u32 words cut from c->lc_work, each piece on a 256-byte boundary
-struct LcCut
-{
-  char *p; size_t used = 0;
-  explicit LcCut (void *base) : p ((char *) base) {}
-  template <class T> T *take (size_t count) { T *r = p ? (T *) (p + used) : nullptr; used += (count * sizeof (T) + 255) & ~(size_t) 255; return r; }
-};
-
 extern "C" void tjamd_reference_destroy (tjamd_reference *ref)
 {
   if (!ref) return;
@@ -6604,70 +6642,64 @@ extern "C" tjamd_reference *tjamd_reference_create (tjamd_counter *c, const void
   if (n_bytes && !h_stream) { set_err (TJAMD_ERR_ARG, "%s: null stream", fn); return NULL; }
   if (n_bytes >= (size_t) 1 << 31) { set_err (TJAMD_ERR_CAPACITY, "%s: a stream of %zu bytes (positions are 32-bit)", fn, n_bytes); return NULL; }
   HIPCHK_NULL (hipSetDevice (c->device));
-  c->timer[T_REF].timed = false;
-  tjamd_reference *ref = new tjamd_reference ();
+  Stage st (c, T_REF);
+  std::unique_ptr<tjamd_reference, void (*) (tjamd_reference *)> ref (new tjamd_reference (), tjamd_reference_destroy);
   ref->device = c->device; ref->k = c->k;
   const long n = (long) n_bytes;
-  if (n == 0) return ref;
-#define REF_FAIL(...) do { set_err (__VA_ARGS__); tjamd_reference_destroy (ref); return NULL; } while (0)
-  for (int pass = 0; pass < 2; pass++) {               // (sizes first, then the same cuts from the block)
-    LcCut cut (pass ? c->lc_work.p : nullptr);
-    u32 *flag = cut.take<u32> (n), *excl = cut.take<u32> (n), *segpos = cut.take<u32> (n + 1), *nlflag = cut.take<u32> (n), *nlex = cut.take<u32> (n),
-        *nlpos = cut.take<u32> (n + 1), *tot = cut.take<u32> (64);
-    if (!pass) {
-      if (ensure (c->lc_work, cut.used, c->stream) || ensure (c->stage, ((size_t) n + 255) & ~(size_t) 255, c->stream) ||
-          ensure (c->scan_tmp, scan_tmp_words (n) * 4 + 64, c->stream)) { tjamd_reference_destroy (ref); return NULL; }
-      for (int i = 0; i < 4; i++)
-        if (hipMalloc (&ref->owned[i], (size_t) n * (i ? 24 : sizeof (RefEntry))) != hipSuccess) REF_FAIL (TJAMD_ERR_HIP, "%s: hipMalloc failed for %ld bytes of genome", fn, n);
-      continue;
-    }
-    const uint8_t *seq = (const uint8_t *) c->stage.p;
-    u32 *tmp = (u32 *) c->scan_tmp.p; const size_t tw = scan_tmp_words (n);
-    u32 *n_seg = tot, *n_ent = tot + 1, *n_nl = tot + 2;
-    const dim3 g (grid_for (n)), b (256);
-    if (hipMemcpyAsync (c->stage.p, h_stream, n_bytes, hipMemcpyHostToDevice, c->stream) != hipSuccess) REF_FAIL (TJAMD_ERR_HIP, "%s: copy to device failed", fn);
-    (void) c->timer[T_REF].begin (c->stream);
-    hipLaunchKernelGGL (ref_seg_flag_kernel, g, b, 0, c->stream, seq, n, flag);
-    int rc = exclusive_scan (c, flag, excl, n, n_seg, tmp, tw);
-    hipLaunchKernelGGL (ref_seg_pos_kernel, g, b, 0, c->stream, (const u32 *) flag, (const u32 *) excl, n, segpos);
-    u32 *vflag = flag, *vex = excl;                     // (both free again once the segment positions are written)
-    hipLaunchKernelGGL (ref_seg_class_kernel, g, b, 0, c->stream, seq, n, c->k, (const u32 *) segpos, (const u32 *) n_seg, vflag, nlflag);
-    if (!rc) rc = exclusive_scan (c, vflag, vex, n, n_ent, tmp, tw);
-    if (!rc) rc = exclusive_scan (c, nlflag, nlex, n, n_nl, tmp, tw);
-    hipLaunchKernelGGL (ref_nlpos_kernel, g, b, 0, c->stream, (const u32 *) segpos, (const u32 *) n_seg, (const u32 *) nlflag, (const u32 *) nlex, n, nlpos);
-    u64 *r0 = (u64 *) ref->owned[1], *r1 = (u64 *) ref->owned[2], *r2 = (u64 *) ref->owned[3];
-    hipLaunchKernelGGL (ref_entry_kernel, g, b, 0, c->stream, seq, n, c->k, (const u32 *) segpos, (const u32 *) n_seg, (const u32 *) vflag, (const u32 *) vex,
-                        (const u32 *) n_ent, (const u32 *) nlex, (const u32 *) nlpos, (RefEntry *) ref->owned[0], r0, r1);
-    if (rc || hipGetLastError () != hipSuccess) { if (!rc) set_err (TJAMD_ERR_HIP, "%s: launch failed", fn); tjamd_reference_destroy (ref); return NULL; }
-    if (radix_sort_records (c, r0, r2, n) || radix_sort_records (c, r1, r2, n)) { tjamd_reference_destroy (ref); return NULL; }   // (results in r0 and r1, whichever blocks those now are)
-    (void) c->timer[T_REF].end (c->stream);
-    u32 h[3] = {0, 0, 0};
-    uint8_t last = 0;
-    if (hipMemcpyAsync (h, tot, sizeof (h), hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
-        hipMemcpyAsync (&last, seq + n - 1, 1, hipMemcpyDeviceToHost, c->stream) != hipSuccess || hipStreamSynchronize (c->stream) != hipSuccess)
-      REF_FAIL (TJAMD_ERR_HIP, "%s: build failed: %s", fn, hipGetErrorString (hipGetLastError ()));
-    ref->entries = (RefEntry *) ref->owned[0]; ref->ord[0] = r0; ref->ord[1] = r1;
-    ref->n_entries = (long) h[1]; ref->n_contigs = (long) h[2] + (last != '\n' ? 1 : 0);
-    for (int i = 1; i < 4; i++) if (ref->owned[i] == (void *) r2) { (void) hipFree (r2); ref->owned[i] = nullptr; }   // the sort's spare block
-    if (ref->n_entries < n) {                           // keep what the entries take, not what the stream could have held
-      const size_t ne = (size_t) std::max<long> (ref->n_entries, 1);
-      void *small[3] = {nullptr, nullptr, nullptr}, *big[3] = {ref->entries, ref->ord[0], ref->ord[1]};
-      const size_t bytes[3] = {ne * sizeof (RefEntry), ne * 24, ne * 24};
-      bool ok = true;
-      for (int i = 0; i < 3 && ok; i++) ok = hipMalloc (&small[i], bytes[i]) == hipSuccess && hipMemcpy (small[i], big[i], bytes[i], hipMemcpyDeviceToDevice) == hipSuccess;
-      if (ok) {
-        for (void *&p : ref->owned) { if (p) (void) hipFree (p); p = nullptr; }
-        for (int i = 0; i < 3; i++) ref->owned[i] = small[i];
-        ref->entries = (RefEntry *) small[0]; ref->ord[0] = (u64 *) small[1]; ref->ord[1] = (u64 *) small[2];
-      } else {                                          // (no room for the copies: the index stays in its first blocks)
-        for (void *p : small) if (p) (void) hipFree (p);
-        (void) hipGetLastError ();
-      }
-    }
-    c->timer[T_REF].timed = true;
+  if (n == 0) return ref.release ();
+  ScratchCut cut;
+  u32 *flag, *excl, *segpos, *nlflag, *nlex, *nlpos, *tot;
+  cut.take (flag, n); cut.take (excl, n); cut.take (segpos, n + 1); cut.take (nlflag, n); cut.take (nlex, n); cut.take (nlpos, n + 1); cut.take (tot, 64);
+  if (cut.commit (c) || ensure (c->stage, ((size_t) n + 255) & ~(size_t) 255, c->stream) || ensure (c->scan_tmp, scan_tmp_words (n) * 4 + 64, c->stream)) return NULL;
+  for (int i = 0; i < 4; i++)
+    if (hipMalloc (&ref->owned[i], (size_t) n * (i ? 24 : sizeof (RefEntry))) != hipSuccess) { set_err (TJAMD_ERR_HIP, "%s: hipMalloc failed for %ld bytes of genome", fn, n); return NULL; }
+  const uint8_t *seq = (const uint8_t *) c->stage.p;
+  u32 *tmp = (u32 *) c->scan_tmp.p; const size_t tw = c->scan_tmp.cap / 4;
+  u32 *n_seg = tot, *n_ent = tot + 1, *n_nl = tot + 2;
+  const dim3 g (grid_for (n)), b (256);
+  if (hipMemcpyAsync (c->stage.p, h_stream, n_bytes, hipMemcpyHostToDevice, c->stream) != hipSuccess) { set_err (TJAMD_ERR_HIP, "%s: copy to device failed", fn); return NULL; }
+  st.begin ();
+  hipLaunchKernelGGL (ref_seg_flag_kernel, g, b, 0, c->stream, seq, n, flag);
+  int rc = exclusive_scan (c, flag, excl, n, n_seg, tmp, tw);
+  hipLaunchKernelGGL (ref_seg_pos_kernel, g, b, 0, c->stream, (const u32 *) flag, (const u32 *) excl, n, segpos);
+  u32 *vflag = flag, *vex = excl;                       // (both free again once the segment positions are written)
+  hipLaunchKernelGGL (ref_seg_class_kernel, g, b, 0, c->stream, seq, n, c->k, (const u32 *) segpos, (const u32 *) n_seg, vflag, nlflag);
+  if (!rc) rc = exclusive_scan (c, vflag, vex, n, n_ent, tmp, tw);
+  if (!rc) rc = exclusive_scan (c, nlflag, nlex, n, n_nl, tmp, tw);
+  hipLaunchKernelGGL (ref_nlpos_kernel, g, b, 0, c->stream, (const u32 *) segpos, (const u32 *) n_seg, (const u32 *) nlflag, (const u32 *) nlex, n, nlpos);
+  u64 *r0 = (u64 *) ref->owned[1], *r1 = (u64 *) ref->owned[2], *r2 = (u64 *) ref->owned[3];
+  hipLaunchKernelGGL (ref_entry_kernel, g, b, 0, c->stream, seq, n, c->k, (const u32 *) segpos, (const u32 *) n_seg, (const u32 *) vflag, (const u32 *) vex,
+                      (const u32 *) n_ent, (const u32 *) nlex, (const u32 *) nlpos, (RefEntry *) ref->owned[0], r0, r1);
+  if (rc || hipGetLastError () != hipSuccess) { if (!rc) set_err (TJAMD_ERR_HIP, "%s: launch failed", fn); return NULL; }
+  if (radix_sort_records (c, r0, r2, n) || radix_sort_records (c, r1, r2, n)) return NULL;   // (results in r0 and r1, whichever blocks those now are)
+  st.end ();
+  u32 h[3] = {0, 0, 0};
+  uint8_t last = 0;
+  if (hipMemcpyAsync (h, tot, sizeof (h), hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
+      hipMemcpyAsync (&last, seq + n - 1, 1, hipMemcpyDeviceToHost, c->stream) != hipSuccess || hipStreamSynchronize (c->stream) != hipSuccess) {
+    set_err (TJAMD_ERR_HIP, "%s: build failed: %s", fn, hipGetErrorString (hipGetLastError ()));
+    return NULL;
   }
-#undef REF_FAIL
-  return ref;
+  ref->entries = (RefEntry *) ref->owned[0]; ref->ord[0] = r0; ref->ord[1] = r1;
+  ref->n_entries = (long) h[1]; ref->n_contigs = (long) h[2] + (last != '\n' ? 1 : 0);
+  for (int i = 1; i < 4; i++) if (ref->owned[i] == (void *) r2) { (void) hipFree (r2); ref->owned[i] = nullptr; }   // the sort's spare block
+  if (ref->n_entries < n) {                             // keep what the entries take, not what the stream could have held
+    const size_t ne = (size_t) std::max<long> (ref->n_entries, 1);
+    void *small[3] = {nullptr, nullptr, nullptr}, *big[3] = {ref->entries, ref->ord[0], ref->ord[1]};
+    const size_t bytes[3] = {ne * sizeof (RefEntry), ne * 24, ne * 24};
+    bool ok = true;
+    for (int i = 0; i < 3 && ok; i++) ok = hipMalloc (&small[i], bytes[i]) == hipSuccess && hipMemcpy (small[i], big[i], bytes[i], hipMemcpyDeviceToDevice) == hipSuccess;
+    if (ok) {
+      for (void *&p : ref->owned) { if (p) (void) hipFree (p); p = nullptr; }
+      for (int i = 0; i < 3; i++) ref->owned[i] = small[i];
+      ref->entries = (RefEntry *) small[0]; ref->ord[0] = (u64 *) small[1]; ref->ord[1] = (u64 *) small[2];
+    } else {                                            // (no room for the copies: the index stays in its first blocks)
+      for (void *p : small) if (p) (void) hipFree (p);
+      (void) hipGetLastError ();
+    }
+  }
+  st.done ();
+  return ref.release ();
 }
 
 extern "C" long tjamd_reference_entries (const tjamd_reference *ref) { return ref ? ref->n_entries : -1; }
@@ -6771,21 +6803,20 @@ extern "C" long tjamd_locate (tjamd_counter *c, const tjamd_reference *ref, cons
   if (n >= (1l << 31)) return -set_err (TJAMD_ERR_CAPACITY, "%s: %ld rows", fn, n);
   if (n > 0 && (!d_keys || !d_loc)) return -set_err (TJAMD_ERR_ARG, "%s: null key or location buffer", fn);
   if (hipSetDevice (c->device) != hipSuccess) return -set_err (TJAMD_ERR_HIP, "hipSetDevice failed");
-  c->timer[T_LOCATE].timed = false;
+  Stage st (c, T_LOCATE);
   if (n == 0) return 0;
   int rc = ensure (c->lc_work, 256, c->stream);
   if (rc) return -rc;
   u32 *n_located = (u32 *) c->lc_work.p;
   if (hipMemsetAsync (n_located, 0, 4, c->stream) != hipSuccess) return -set_err (TJAMD_ERR_HIP, "%s: memset failed", fn);
-  (void) c->timer[T_LOCATE].begin (c->stream);
+  st.begin ();
   hipLaunchKernelGGL (locate_kernel, dim3 (grid_for (n)), dim3 (256), 0, c->stream, (const u64 *) d_keys, n, (const u64 *) ref->ord[0], (const u64 *) ref->ord[1],
                       ref->n_entries, (const RefEntry *) ref->entries, max_mismatches, (Location *) d_loc, n_located);
-  if (hipGetLastError () != hipSuccess) return -set_err (TJAMD_ERR_HIP, "%s: launch failed", fn);
-  (void) c->timer[T_LOCATE].end (c->stream);
+  st.end ();
   u32 found = 0;
-  if (hipMemcpyAsync (&found, n_located, 4, hipMemcpyDeviceToHost, c->stream) != hipSuccess || hipStreamSynchronize (c->stream) != hipSuccess)
-    return -set_err (TJAMD_ERR_HIP, "%s: lookup failed: %s", fn, hipGetErrorString (hipGetLastError ()));
-  c->timer[T_LOCATE].timed = true;
+  rc = read_back (c, fn, n_located, &found, 1);
+  if (rc) return -rc;
+  st.done ();
   return (long) found;
 }
 extern "C" double tjamd_last_locate_ms (tjamd_counter *c) { return c ? c->timer[T_LOCATE].ms (c->device) : -1.0; }
@@ -6886,7 +6917,7 @@ extern "C" long tjamd_reference_add_seeds (tjamd_counter *c, tjamd_reference *re
   if (ref->device != c->device) return -set_err (TJAMD_ERR_ARG, "%s: the reference lives on device %d, the counter on device %d", fn, ref->device, c->device);
   if (ref->has_seeds) return ref->n_entries;
   if (hipSetDevice (c->device) != hipSuccess) return -set_err (TJAMD_ERR_HIP, "hipSetDevice failed");
-  c->timer[T_SEED_ORDER].timed = false;
+  Stage st (c, T_SEED_ORDER);
   const long n = ref->n_entries;
   if (n == 0) { ref->has_seeds = true; return 0; }
   const size_t bytes = (size_t) n * 24;
@@ -6896,23 +6927,20 @@ extern "C" long tjamd_reference_add_seeds (tjamd_counter *c, tjamd_reference *re
   if (hipMalloc (&block, bytes) != hipSuccess) { (void) hipGetLastError (); return -set_err (TJAMD_ERR_HIP, "%s: hipMalloc failed for %ld entries", fn, n); }
   // the sort swaps its two blocks once per pass: start in the one that leaves the result in the reference's own
   u64 *a = (key_passes (c->k) & 1) ? (u64 *) c->lc_work.p : (u64 *) block, *b = (key_passes (c->k) & 1) ? (u64 *) block : (u64 *) c->lc_work.p;
-  (void) c->timer[T_SEED_ORDER].begin (c->stream);
+  st.begin ();
   hipLaunchKernelGGL (ref_seed_kernel, dim3 (grid_for (n)), dim3 (256), 0, c->stream, (const RefEntry *) ref->entries, n, c->k, a);
   if (hipGetLastError () != hipSuccess) { (void) hipFree (block); return -set_err (TJAMD_ERR_HIP, "%s: launch failed", fn); }
   rc = radix_sort_records (c, a, b, n);
   if (rc) { (void) hipStreamSynchronize (c->stream); (void) hipFree (block); return -rc; }
-  (void) c->timer[T_SEED_ORDER].end (c->stream);
-  if (hipStreamSynchronize (c->stream) != hipSuccess) {
-    const hipError_t e = hipGetLastError ();
-    (void) hipFree (block);
-    return -set_err (TJAMD_ERR_HIP, "%s: sort failed: %s", fn, hipGetErrorString (e));
-  }
+  st.end ();
+  rc = read_back (c, fn, nullptr, nullptr, 0);
+  if (rc) { (void) hipFree (block); return -rc; }
   if (a != (u64 *) block) {                                // (the parity of key_passes chose the starting block: cannot happen)
     (void) hipFree (block);
     return -set_err (TJAMD_ERR_STATE, "%s: the sorted order did not end in the reference's block after %d passes", fn, key_passes (c->k));
   }
   ref->seed = (u64 *) block; ref->has_seeds = true;
-  c->timer[T_SEED_ORDER].timed = true;
+  st.done ();
   return n;
 }
 extern "C" double tjamd_last_seed_order_ms (tjamd_counter *c) { return c ? c->timer[T_SEED_ORDER].ms (c->device) : -1.0; }
@@ -7003,23 +7031,22 @@ extern "C" long tjamd_locate_gapped (tjamd_counter *c, const tjamd_reference *re
   if (!ref->has_seeds) return -set_err (TJAMD_ERR_ARG, "%s: the reference has no seed order (tjamd_reference_add_seeds comes first)", fn);
   if (max_edits > c->k) return -set_err (TJAMD_ERR_ARG, "%s: max_edits %d outside 0..%d", fn, max_edits, c->k);
   if (hipSetDevice (c->device) != hipSuccess) return -set_err (TJAMD_ERR_HIP, "hipSetDevice failed");
-  c->timer[T_LOCATE_GAPPED].timed = false;
+  Stage st (c, T_LOCATE_GAPPED);
   if (n == 0) return 0;
   int rc = ensure (c->lc_work, 256, c->stream);
   if (rc) return -rc;
   u32 *n_located = (u32 *) c->lc_work.p;
   if (hipMemsetAsync (n_located, 0, 4, c->stream) != hipSuccess) return -set_err (TJAMD_ERR_HIP, "%s: memset failed", fn);
-  (void) c->timer[T_LOCATE_GAPPED].begin (c->stream);
+  st.begin ();
 #define LG_LAUNCH(B) hipLaunchKernelGGL (locate_gapped_kernel<B>, dim3 (grid_for (n)), dim3 (256), 0, c->stream, (const u64 *) d_keys, n, (const u64 *) ref->ord[0], \
                                          (const u64 *) ref->seed, ref->n_entries, (const RefEntry *) ref->entries, c->k, max_edits, (Location *) d_loc, d_how, n_located)
   switch (max_shift) { case 0: LG_LAUNCH (0); break; case 1: LG_LAUNCH (1); break; case 2: LG_LAUNCH (2); break; default: LG_LAUNCH (3); break; }
 #undef LG_LAUNCH
-  if (hipGetLastError () != hipSuccess) return -set_err (TJAMD_ERR_HIP, "%s: launch failed", fn);
-  (void) c->timer[T_LOCATE_GAPPED].end (c->stream);
+  st.end ();
   u32 found = 0;
-  if (hipMemcpyAsync (&found, n_located, 4, hipMemcpyDeviceToHost, c->stream) != hipSuccess || hipStreamSynchronize (c->stream) != hipSuccess)
-    return -set_err (TJAMD_ERR_HIP, "%s: lookup failed: %s", fn, hipGetErrorString (hipGetLastError ()));
-  c->timer[T_LOCATE_GAPPED].timed = true;
+  rc = read_back (c, fn, n_located, &found, 1);
+  if (rc) return -rc;
+  st.done ();
   return (long) found;
 }
 extern "C" double tjamd_last_locate_gapped_ms (tjamd_counter *c) { return c ? c->timer[T_LOCATE_GAPPED].ms (c->device) : -1.0; }
@@ -7126,6 +7153,31 @@ void kv_scatter_kernel (const u64 *__restrict__ key, const u32 *__restrict__ val
   }
 }
 
+// scratch of kv_sort for up to n_sort pairs: the blocks' histograms, and room in c->scan_tmp for their scan and for the
+// caller's own scans of up to n_scan words (then 64 bytes).  Called before a stage begins: growing a buffer waits for the stream.
+static int reserve_sort (tjamd_counter *c, long n_sort, long n_scan)
+{
+  const long nh = 256l * ((n_sort + RS_ITEMS - 1) / RS_ITEMS);
+  const int rc = ensure (c->hist, (size_t) nh * 4, c->stream);
+  return rc ? rc : ensure (c->scan_tmp, std::max (scan_tmp_words (nh), scan_tmp_words (n_scan)) * 4 + 64, c->stream);
+}
+
+// Queues the sort of the n pairs (key[0][i], val[0][i]) on the low `bits` of the key, ascending and stable: one pass per
+// 8 bits between the two halves, whose pointers are swapped so that the result is in key[0] and val[0] again.
+static int kv_sort (tjamd_counter *c, u64 *(&key)[2], u32 *(&val)[2], long n, int bits)
+{
+  const int nblk = (int) ((n + RS_ITEMS - 1) / RS_ITEMS);
+  for (int p = 0; p < (bits + 7) / 8; p++) {
+    hipLaunchKernelGGL (kv_count_kernel, dim3 (nblk), dim3 (256), 0, c->stream, (const u64 *) key[0], n, p, (u32 *) c->hist.p, nblk);
+    const int rc = exclusive_scan (c, (const u32 *) c->hist.p, (u32 *) c->hist.p, 256l * nblk, nullptr, (u32 *) c->scan_tmp.p, c->scan_tmp.cap / 4);
+    if (rc) return rc;
+    hipLaunchKernelGGL (kv_scatter_kernel, dim3 (nblk), dim3 (256), 0, c->stream, (const u64 *) key[0], (const u32 *) val[0], key[1], val[1], n, p,
+                        (const u32 *) c->hist.p, nblk);
+    std::swap (key[0], key[1]); std::swap (val[0], val[1]);
+  }
+  return TJAMD_OK;
+}
+
 
 // the sorted tracts: where a merged tract starts (a new key, or no location: every unlocated tract stays alone) and the
 // rows each brings
@@ -7204,29 +7256,22 @@ extern "C" long tjamd_located_tracts (tjamd_counter *c, const void *d_keys, cons
   if (capacity < (n_union > 0 ? 1 : 0)) return -set_err (TJAMD_ERR_CAPACITY, "%s: capacity %ld for a union of %ld rows", fn, capacity, n_union);
   if (!c) return -set_err (TJAMD_ERR_ARG, "%s: null counter", fn);
   if (hipSetDevice (c->device) != hipSuccess) return -set_err (TJAMD_ERR_HIP, "hipSetDevice failed");
-  c->timer[T_LOCATED_TRACTS].timed = false;
+  Stage st (c, T_LOCATED_TRACTS);
   const long n = n_union;
   if (n == 0) return 0;
-  const int nblk_max = (int) ((n + RS_ITEMS - 1) / RS_ITEMS);
-  LcCut cut (nullptr);
-  UnionTract *own = nullptr; u64 *key[2] = {nullptr, nullptr}; u32 *val[2] = {nullptr, nullptr}, *head = nullptr, *hex = nullptr, *rows = nullptr, *rowstart = nullptr, *tot = nullptr;
-  for (int pass = 0; pass < 2; pass++) {
-    cut = LcCut (pass ? c->lc_work.p : nullptr);
-    own = cut.take<UnionTract> (n); key[0] = cut.take<u64> (n); key[1] = cut.take<u64> (n); val[0] = cut.take<u32> (n); val[1] = cut.take<u32> (n);
-    head = cut.take<u32> (n); hex = cut.take<u32> (n); rows = cut.take<u32> (n); rowstart = cut.take<u32> (n); tot = cut.take<u32> (64);
-    if (!pass) {
-      rc = ensure (c->lc_work, cut.used, c->stream);
-      if (!rc) rc = ensure (c->ut_tot, (size_t) n * 8, c->stream);
-      if (!rc) rc = ensure (c->hist, (size_t) 256 * nblk_max * 4, c->stream);
-      if (!rc) rc = ensure (c->scan_tmp, std::max (scan_tmp_words (256l * nblk_max), scan_tmp_words (n)) * 4 + 64, c->stream);
-      if (rc) return -rc;
-    }
-  }
+  ScratchCut cut;
+  UnionTract *own; u64 *key[2]; u32 *val[2], *head, *hex, *rows, *rowstart, *tot;
+  cut.take (own, n); cut.take (key[0], n); cut.take (key[1], n); cut.take (val[0], n); cut.take (val[1], n);
+  cut.take (head, n); cut.take (hex, n); cut.take (rows, n); cut.take (rowstart, n); cut.take (tot, 64);
+  rc = cut.commit (c);
+  if (!rc) rc = ensure (c->ut_tot, (size_t) n * 8, c->stream);
+  if (!rc) rc = reserve_sort (c, n, n);                 // (sized before the number of tracts is known: at most one per row)
+  if (rc) return -rc;
   u32 *tmp = (u32 *) c->scan_tmp.p; const size_t tw = c->scan_tmp.cap / 4;
   long long *total = (long long *) c->ut_tot.p;
   u32 *n_out = tot; int *err = (int *) tot + 1;
   if (hipMemsetAsync (tot, 0, 256, c->stream) != hipSuccess) return -set_err (TJAMD_ERR_HIP, "%s: memset failed", fn);
-  (void) c->timer[T_LOCATED_TRACTS].begin (c->stream);
+  st.begin ();
   const int S = tract_segment (n_samples);
   hipLaunchKernelGGL (union_totals_kernel, dim3 (tract_grid (n, S)), dim3 (256), 0, c->stream, (const int *) d_counts, n, n_samples, S, total);
   const UnionTract *tracts = (const UnionTract *) d_tracts;
@@ -7237,21 +7282,14 @@ extern "C" long tjamd_located_tracts (tjamd_counter *c, const void *d_keys, cons
     if (rc) return -rc;
     hipLaunchKernelGGL (lt_context_tract_kernel, dim3 (grid_for (n)), dim3 (256), 0, c->stream, n, (const long long *) total, (const u32 *) head, (const u32 *) hex, own);
     u32 nh = 0;
-    if (hipMemcpyAsync (&nh, tot + 2, 4, hipMemcpyDeviceToHost, c->stream) != hipSuccess || hipStreamSynchronize (c->stream) != hipSuccess)
-      return -set_err (TJAMD_ERR_HIP, "%s: tract ids failed: %s", fn, hipGetErrorString (hipGetLastError ()));
+    rc = read_back (c, fn, tot + 2, &nh, 1);
+    if (rc) return -rc;
     tracts = own; nt = (long) nh + 1;
   }
   hipLaunchKernelGGL (lt_tract_key_kernel, dim3 (grid_for (nt)), dim3 (256), 0, c->stream, tracts, nt, n, (const u64 *) d_keys, (const long long *) total,
                       (const Location *) d_loc, key[0], val[0], err);
-  const int nblk = (int) ((nt + RS_ITEMS - 1) / RS_ITEMS);
-  for (int p = 0; p < LT_KEY_PASSES; p++) {
-    hipLaunchKernelGGL (kv_count_kernel, dim3 (nblk), dim3 (256), 0, c->stream, (const u64 *) key[0], nt, p, (u32 *) c->hist.p, nblk);
-    rc = exclusive_scan (c, (const u32 *) c->hist.p, (u32 *) c->hist.p, 256l * nblk, nullptr, tmp, tw);
-    if (rc) return -rc;
-    hipLaunchKernelGGL (kv_scatter_kernel, dim3 (nblk), dim3 (256), 0, c->stream, (const u64 *) key[0], (const u32 *) val[0], key[1], val[1], nt, p,
-                        (const u32 *) c->hist.p, nblk);
-    std::swap (key[0], key[1]); std::swap (val[0], val[1]);
-  }
+  rc = kv_sort (c, key, val, nt, 8 * LT_KEY_PASSES);
+  if (rc) return -rc;
   hipLaunchKernelGGL (lt_head_kernel, dim3 (grid_for (nt)), dim3 (256), 0, c->stream, (const u64 *) key[0], (const u32 *) val[0], nt, tracts, head, rows);
   rc = exclusive_scan (c, head, hex, nt, n_out, tmp, tw);
   if (!rc) rc = exclusive_scan (c, rows, rowstart, nt, nullptr, tmp, tw);
@@ -7264,15 +7302,14 @@ extern "C" long tjamd_located_tracts (tjamd_counter *c, const void *d_keys, cons
   hipLaunchKernelGGL (lt_merge_kernel, dim3 (grid_for (nt)), dim3 (256), 0, c->stream, nt, n, (const u32 *) head, (const u32 *) hex, (const u32 *) rowstart,
                       (const u32 *) val[0], tracts, (const long long *) total, (const Location *) d_loc, capacity, (UnionTract *) d_out_tracts,
                       (Location *) d_tract_loc, d_ref_length);
-  if (hipGetLastError () != hipSuccess) return -set_err (TJAMD_ERR_HIP, "%s: launch failed", fn);
-  (void) c->timer[T_LOCATED_TRACTS].end (c->stream);
+  st.end ();
   u32 h[2] = {0, 0};
-  if (hipMemcpyAsync (h, tot, 8, hipMemcpyDeviceToHost, c->stream) != hipSuccess || hipStreamSynchronize (c->stream) != hipSuccess)
-    return -set_err (TJAMD_ERR_HIP, "%s: failed: %s", fn, hipGetErrorString (hipGetLastError ()));
+  rc = read_back (c, fn, tot, h, 2);
+  if (rc) return -rc;
   if (h[1] == 2) return -set_err (TJAMD_ERR_ARG, "%s: a location with flat >= 2^45", fn);
   if (h[1]) return -set_err (TJAMD_ERR_ARG, "%s: the tracts do not tile the union (first 0, each starting where the one before ends, the last ending at n_union)", fn);
   if ((long) h[0] > capacity) return -set_err (TJAMD_ERR_CAPACITY, "%s: %u tracts, caller capacity %ld", fn, h[0], capacity);
-  c->timer[T_LOCATED_TRACTS].timed = true;
+  st.done ();
   return (long) h[0];
 }
 extern "C" double tjamd_last_located_tracts_ms (tjamd_counter *c) { return c ? c->timer[T_LOCATED_TRACTS].ms (c->device) : -1.0; }
@@ -7410,26 +7447,21 @@ extern "C" long tjamd_tract_variants (tjamd_counter *c, const tjamd_reference *r
   if (ref->k != c->k) return -set_err (TJAMD_ERR_ARG, "%s: the reference was built with k = %d, the counter has k = %d", fn, ref->k, c->k);
   if (ref->device != c->device) return -set_err (TJAMD_ERR_ARG, "%s: the reference lives on device %d, the counter on device %d", fn, ref->device, c->device);
   if (hipSetDevice (c->device) != hipSuccess) return -set_err (TJAMD_ERR_HIP, "hipSetDevice failed");
-  c->timer[T_VARIANTS].timed = false;
+  Stage st (c, T_VARIANTS);
   if (n_flags == 0) {
     for (int s = 0; s <= n_samples; s++) h_offsets[s] = 0;
     return 0;
   }
-  LcCut cut (nullptr);
-  u32 *flag = nullptr, *excl = nullptr, *offs = nullptr;
-  for (int pass = 0; pass < 2; pass++) {
-    cut = LcCut (pass ? c->lc_work.p : nullptr);
-    flag = cut.take<u32> (n_flags); excl = cut.take<u32> (n_flags); offs = cut.take<u32> ((size_t) n_samples + 2);
-    if (!pass) {
-      rc = ensure (c->lc_work, cut.used, c->stream);
-      if (!rc) rc = ensure (c->scan_tmp, scan_tmp_words (n_flags) * 4 + 64, c->stream);
-      if (rc) return -rc;
-    }
-  }
+  ScratchCut cut;
+  u32 *flag, *excl, *offs;
+  cut.take (flag, n_flags); cut.take (excl, n_flags); cut.take (offs, (size_t) n_samples + 2);
+  rc = cut.commit (c);
+  if (!rc) rc = ensure (c->scan_tmp, scan_tmp_words (n_flags) * 4 + 64, c->stream);
+  if (rc) return -rc;
   u32 *total = offs + n_samples;                        // offs: the samples' starts, the number of records, the error flag
   int *err = (int *) (offs + n_samples + 1);
   if (hipMemsetAsync (total, 0, 8, c->stream) != hipSuccess) return -set_err (TJAMD_ERR_HIP, "%s: memset failed", fn);
-  (void) c->timer[T_VARIANTS].begin (c->stream);
+  st.begin ();
   const int S = tract_segment (n_samples);
   auto launch = [&] (auto kernel) {
     hipLaunchKernelGGL (kernel, dim3 (tract_grid (n_list, S)), dim3 (256), 0, c->stream, (const u64 *) d_keys, (const int *) d_counts, n_union, n_samples, S, c->k,
@@ -7442,18 +7474,17 @@ extern "C" long tjamd_tract_variants (tjamd_counter *c, const tjamd_reference *r
   if (rc) return -rc;
   hipLaunchKernelGGL (variant_offsets_kernel, dim3 (grid_for (n_samples)), dim3 (256), 0, c->stream, (const u32 *) excl, n_list, n_samples, offs);
   launch (tract_variants_kernel<true>);                 // (guarded by capacity: the count is only read for the check below)
-  if (hipGetLastError () != hipSuccess) return -set_err (TJAMD_ERR_HIP, "%s: launch failed", fn);
-  (void) c->timer[T_VARIANTS].end (c->stream);
+  st.end ();
   std::vector<u32> h ((size_t) n_samples + 2, 0u);
-  if (hipMemcpyAsync (h.data (), offs, h.size () * 4, hipMemcpyDeviceToHost, c->stream) != hipSuccess || hipStreamSynchronize (c->stream) != hipSuccess)
-    return -set_err (TJAMD_ERR_HIP, "%s: failed: %s", fn, hipGetErrorString (hipGetLastError ()));
+  rc = read_back (c, fn, offs, h.data (), h.size ());
+  if (rc) return -rc;
   const u32 h_err = h[(size_t) n_samples + 1];
   const long n_rec = (long) h[(size_t) n_samples];
   if (h_err & 1u) return -set_err (TJAMD_ERR_ARG, "%s: the tracts do not tile the union (first 0, each starting where the one before ends, the last ending at n_union)", fn);
   if (h_err & 2u) return -set_err (TJAMD_ERR_ARG, "%s: a listed tract id is outside [0, %ld)", fn, n_tracts);
   if (n_rec > capacity) return -set_err (TJAMD_ERR_CAPACITY, "%s: %ld records, caller capacity %ld", fn, n_rec, capacity);
   for (int s = 0; s <= n_samples; s++) h_offsets[s] = (long) h[(size_t) s];
-  c->timer[T_VARIANTS].timed = true;
+  st.done ();
   return n_rec;
 }
 extern "C" double tjamd_last_tract_variants_ms (tjamd_counter *c) { return c ? c->timer[T_VARIANTS].ms (c->device) : -1.0; }
@@ -7570,7 +7601,7 @@ extern "C" tjamd_annotation *tjamd_annotation_create (tjamd_counter *c, const tj
     return TJAMD_OK;
   };
   const int bad = refused ();
-  if (c && tjamd_device_count () > 0) c->timer[T_ANNOTATION].timed = false;   // a refused call leaves no timing behind (without a device there is no counter)
+  Stage st (c, T_ANNOTATION);                           // (a refused call leaves no timing behind)
   if (bad) return NULL;
   const long n = n_features;
   long nr = 0;                                          // features that are not regions
@@ -7583,48 +7614,33 @@ extern "C" tjamd_annotation *tjamd_annotation_create (tjamd_counter *c, const tj
     nr += x.cls != TJAMD_FEATURE_REGION;
   }
   HIPCHK_NULL (hipSetDevice (c->device));
-  tjamd_annotation *a = new tjamd_annotation ();
+  std::unique_ptr<tjamd_annotation, void (*) (tjamd_annotation *)> a (new tjamd_annotation (), tjamd_annotation_destroy);
   a->device = c->device; a->n_features = n; a->n_points = 2 * nr;
   const long np = a->n_points;
-#define AN_FAIL(...) do { set_err (__VA_ARGS__); tjamd_annotation_destroy (a); return NULL; } while (0)
-  const int nblk = (int) ((np + RS_ITEMS - 1) / RS_ITEMS);
-  LcCut cut (nullptr);
-  Feature *feat = nullptr; u32 *flag = nullptr, *excl = nullptr, *val[2] = {nullptr, nullptr}; u64 *key[2] = {nullptr, nullptr};
-  for (int pass = 0; pass < 2; pass++) {
-    cut = LcCut (pass ? c->lc_work.p : nullptr);
-    feat = cut.take<Feature> (n + 1); flag = cut.take<u32> (n + 1); excl = cut.take<u32> (n + 1);
-    key[0] = cut.take<u64> (np + 1); key[1] = cut.take<u64> (np + 1); val[0] = cut.take<u32> (np + 1); val[1] = cut.take<u32> (np + 1);
-    if (!pass && (ensure (c->lc_work, cut.used, c->stream) || ensure (c->hist, (size_t) 256 * std::max (nblk, 1) * 4, c->stream) ||
-                  ensure (c->scan_tmp, std::max (scan_tmp_words (256l * nblk), scan_tmp_words (n)) * 4 + 64, c->stream))) { tjamd_annotation_destroy (a); return NULL; }
-  }
-  if (np && (hipMalloc (&a->points, (size_t) np * 8) != hipSuccess || hipMalloc (&a->prio, (size_t) np * 4) != hipSuccess)) AN_FAIL (TJAMD_ERR_HIP, "%s: hipMalloc failed for %ld points", fn, np);
-  if (n && hipMemcpyAsync (feat, h_features, (size_t) n * sizeof (Feature), hipMemcpyHostToDevice, c->stream) != hipSuccess) AN_FAIL (TJAMD_ERR_HIP, "%s: copy to device failed", fn);
-  if (np && hipMemsetAsync (a->prio, 0, (size_t) np * 4, c->stream) != hipSuccess) AN_FAIL (TJAMD_ERR_HIP, "%s: memset failed", fn);
-  u32 *tmp = (u32 *) c->scan_tmp.p; const size_t tw = c->scan_tmp.cap / 4;
-  (void) c->timer[T_ANNOTATION].begin (c->stream);
+  ScratchCut cut;
+  Feature *feat; u32 *flag, *excl, *val[2]; u64 *key[2];
+  cut.take (feat, n + 1); cut.take (flag, n + 1); cut.take (excl, n + 1);
+  cut.take (key[0], np + 1); cut.take (key[1], np + 1); cut.take (val[0], np + 1); cut.take (val[1], np + 1);
+  if (cut.commit (c) || reserve_sort (c, np, n)) return NULL;
+  if (np && (hipMalloc (&a->points, (size_t) np * 8) != hipSuccess || hipMalloc (&a->prio, (size_t) np * 4) != hipSuccess)) { set_err (TJAMD_ERR_HIP, "%s: hipMalloc failed for %ld points", fn, np); return NULL; }
+  if (n && hipMemcpyAsync (feat, h_features, (size_t) n * sizeof (Feature), hipMemcpyHostToDevice, c->stream) != hipSuccess) { set_err (TJAMD_ERR_HIP, "%s: copy to device failed", fn); return NULL; }
+  if (np && hipMemsetAsync (a->prio, 0, (size_t) np * 4, c->stream) != hipSuccess) { set_err (TJAMD_ERR_HIP, "%s: memset failed", fn); return NULL; }
+  st.begin ();
   hipLaunchKernelGGL (an_flag_kernel, dim3 (grid_for (n)), dim3 (256), 0, c->stream, (const Feature *) feat, n, flag);
   if (np) {
-    int rc = exclusive_scan (c, flag, excl, n, nullptr, tmp, tw);
+    int rc = exclusive_scan (c, flag, excl, n, nullptr, (u32 *) c->scan_tmp.p, c->scan_tmp.cap / 4);
     hipLaunchKernelGGL (an_points_kernel, dim3 (grid_for (n)), dim3 (256), 0, c->stream, (const Feature *) feat, n, (const u32 *) excl, key[0], val[0]);
     int bits = 32;                                      // of a point: the position, and what the contig numbers need
     while (bits < 64 && ((u64) (ref->n_contigs - 1) >> (bits - 32))) bits++;
-    for (int p = 0; p < (bits + 7) / 8 && !rc; p++) {
-      hipLaunchKernelGGL (kv_count_kernel, dim3 (nblk), dim3 (256), 0, c->stream, (const u64 *) key[0], np, p, (u32 *) c->hist.p, nblk);
-      rc = exclusive_scan (c, (const u32 *) c->hist.p, (u32 *) c->hist.p, 256l * nblk, nullptr, tmp, tw);
-      hipLaunchKernelGGL (kv_scatter_kernel, dim3 (nblk), dim3 (256), 0, c->stream, (const u64 *) key[0], (const u32 *) val[0], key[1], val[1], np, p,
-                          (const u32 *) c->hist.p, nblk);
-      std::swap (key[0], key[1]); std::swap (val[0], val[1]);
-    }
-    if (rc) { tjamd_annotation_destroy (a); return NULL; }
+    if (!rc) rc = kv_sort (c, key, val, np, bits);
+    if (rc) return NULL;
     hipLaunchKernelGGL (an_paint_kernel, dim3 (grid_for (n)), dim3 (256), 0, c->stream, (const Feature *) feat, n, (const u64 *) key[0], np, a->prio);
   }
-  if (hipGetLastError () != hipSuccess) AN_FAIL (TJAMD_ERR_HIP, "%s: launch failed", fn);
-  (void) c->timer[T_ANNOTATION].end (c->stream);
-  if ((np && hipMemcpyAsync (a->points, key[0], (size_t) np * 8, hipMemcpyDeviceToDevice, c->stream) != hipSuccess) || hipStreamSynchronize (c->stream) != hipSuccess)
-    AN_FAIL (TJAMD_ERR_HIP, "%s: build failed: %s", fn, hipGetErrorString (hipGetLastError ()));
-#undef AN_FAIL
-  c->timer[T_ANNOTATION].timed = true;
-  return a;
+  st.end ();
+  if (np && hipMemcpyAsync (a->points, key[0], (size_t) np * 8, hipMemcpyDeviceToDevice, c->stream) != hipSuccess) { set_err (TJAMD_ERR_HIP, "%s: copy of the points failed", fn); return NULL; }
+  if (read_back (c, fn, nullptr, nullptr, 0)) return NULL;
+  st.done ();
+  return a.release ();
 }
 
 extern "C" long tjamd_annotation_features (const tjamd_annotation *a) { return a ? a->n_features : -1; }
@@ -7714,7 +7730,7 @@ extern "C" long tjamd_tract_features (tjamd_counter *c, const tjamd_annotation *
     return TJAMD_OK;
   };
   int rc = refused ();
-  if (c && tjamd_device_count () > 0) c->timer[T_TRACT_FEATURES].timed = false;   // a refused call leaves no timing behind (without a device there is no counter)
+  Stage st (c, T_TRACT_FEATURES);                       // (a refused call leaves no timing behind)
   if (rc) return -rc;
   if (hipSetDevice (c->device) != hipSuccess) return -set_err (TJAMD_ERR_HIP, "hipSetDevice failed");
   if (n_tracts == 0) return 0;
@@ -7722,18 +7738,17 @@ extern "C" long tjamd_tract_features (tjamd_counter *c, const tjamd_annotation *
   if (rc) return -rc;
   int *err = (int *) c->lc_work.p;
   if (hipMemsetAsync (err, 0, 4, c->stream) != hipSuccess) return -set_err (TJAMD_ERR_HIP, "%s: memset failed", fn);
-  (void) c->timer[T_TRACT_FEATURES].begin (c->stream);
+  st.begin ();
   const int S = have_union ? tract_segment (n_samples) : 1;
   hipLaunchKernelGGL (tract_features_kernel, dim3 (tract_grid (n_tracts, S)), dim3 (256), 0, c->stream, have_union ? (const u64 *) d_keys : (const u64 *) nullptr,
                       (const int *) d_counts, n_union, n_samples, S, (const UnionTract *) d_tracts, n_tracts, (const Location *) d_tract_loc,
                       (const u64 *) a->points, (const u32 *) a->prio, a->n_points, (TractFeature *) d_out, err);
-  if (hipGetLastError () != hipSuccess) return -set_err (TJAMD_ERR_HIP, "%s: launch failed", fn);
-  (void) c->timer[T_TRACT_FEATURES].end (c->stream);
+  st.end ();
   int h_err = 0;
-  if (hipMemcpyAsync (&h_err, err, 4, hipMemcpyDeviceToHost, c->stream) != hipSuccess || hipStreamSynchronize (c->stream) != hipSuccess)
-    return -set_err (TJAMD_ERR_HIP, "%s: failed: %s", fn, hipGetErrorString (hipGetLastError ()));
+  rc = read_back (c, fn, err, &h_err, 1);
+  if (rc) return -rc;
   if (h_err) return -set_err (TJAMD_ERR_ARG, "%s: the tracts do not tile the union (first 0, each starting where the one before ends, the last ending at n_union)", fn);
-  c->timer[T_TRACT_FEATURES].timed = true;
+  st.done ();
   return n_tracts;
 }
 extern "C" double tjamd_last_tract_features_ms (tjamd_counter *c) { return c ? c->timer[T_TRACT_FEATURES].ms (c->device) : -1.0; }
@@ -7904,42 +7919,35 @@ extern "C" tjamd_coding *tjamd_coding_create (tjamd_counter *c, const void *h_st
     return TJAMD_OK;
   };
   const int bad = refused ();
-  if (c && tjamd_device_count () > 0) c->timer[T_CODING].timed = false;   // a refused call leaves no timing behind (without a device there is no counter)
+  Stage st (c, T_CODING);                               // (a refused call leaves no timing behind)
   if (bad) return NULL;
   HIPCHK_NULL (hipSetDevice (c->device));
-  tjamd_coding *cod = new tjamd_coding ();
+  std::unique_ptr<tjamd_coding, void (*) (tjamd_coding *)> cod (new tjamd_coding (), tjamd_coding_destroy);
   cod->device = c->device; cod->n_features = n_features; cod->n_contigs = n_contigs; cod->n_bytes = (long) n_bytes;
   const long n = (long) n_bytes, nf = n_features;
-#define CD_FAIL(...) do { set_err (__VA_ARGS__); tjamd_coding_destroy (cod); return NULL; } while (0)
-  LcCut cut (nullptr);
-  u32 *nlflag = nullptr, *nlex = nullptr; Feature *feat = nullptr; signed char *phase = nullptr;
-  for (int pass = 0; pass < 2; pass++) {
-    cut = LcCut (pass ? c->lc_work.p : nullptr);
-    nlflag = cut.take<u32> (n + 1); nlex = cut.take<u32> (n + 1); feat = cut.take<Feature> (nf + 1); phase = cut.take<signed char> (nf + 1);
-    if (!pass && (ensure (c->lc_work, cut.used, c->stream) || ensure (c->stage, ((size_t) n + 255) & ~(size_t) 255, c->stream) ||
-                  ensure (c->scan_tmp, scan_tmp_words (n) * 4 + 64, c->stream))) { tjamd_coding_destroy (cod); return NULL; }
-  }
+  ScratchCut cut;
+  u32 *nlflag, *nlex; Feature *feat; signed char *phase;
+  cut.take (nlflag, n + 1); cut.take (nlex, n + 1); cut.take (feat, nf + 1); cut.take (phase, nf + 1);
+  if (cut.commit (c) || ensure (c->stage, ((size_t) n + 255) & ~(size_t) 255, c->stream) || ensure (c->scan_tmp, scan_tmp_words (n) * 4 + 64, c->stream)) return NULL;
   if (hipMalloc (&cod->codes, (size_t) std::max<long> (n, 1)) != hipSuccess || hipMalloc (&cod->cstart, (size_t) (n_contigs + 2) * 4) != hipSuccess ||
-      hipMalloc (&cod->rows, (size_t) std::max<long> (nf, 1) * sizeof (CodRow)) != hipSuccess) CD_FAIL (TJAMD_ERR_HIP, "%s: hipMalloc failed for %ld bytes of genome and %ld features", fn, n, nf);
+      hipMalloc (&cod->rows, (size_t) std::max<long> (nf, 1) * sizeof (CodRow)) != hipSuccess) { set_err (TJAMD_ERR_HIP, "%s: hipMalloc failed for %ld bytes of genome and %ld features", fn, n, nf); return NULL; }
   if ((n && hipMemcpyAsync (c->stage.p, h_stream, n_bytes, hipMemcpyHostToDevice, c->stream) != hipSuccess) ||
       (nf && hipMemcpyAsync (feat, h_features, (size_t) nf * sizeof (Feature), hipMemcpyHostToDevice, c->stream) != hipSuccess) ||
-      (nf && h_phase && hipMemcpyAsync (phase, h_phase, (size_t) nf, hipMemcpyHostToDevice, c->stream) != hipSuccess)) CD_FAIL (TJAMD_ERR_HIP, "%s: copy to device failed", fn);
-  (void) c->timer[T_CODING].begin (c->stream);
+      (nf && h_phase && hipMemcpyAsync (phase, h_phase, (size_t) nf, hipMemcpyHostToDevice, c->stream) != hipSuccess)) { set_err (TJAMD_ERR_HIP, "%s: copy to device failed", fn); return NULL; }
+  st.begin ();
   if (n) {
     const uint8_t *seq = (const uint8_t *) c->stage.p;
     hipLaunchKernelGGL (cd_code_kernel, dim3 (grid_for (n)), dim3 (256), 0, c->stream, seq, n, cod->codes, nlflag);
-    if (exclusive_scan (c, nlflag, nlex, n, nullptr, (u32 *) c->scan_tmp.p, c->scan_tmp.cap / 4)) { tjamd_coding_destroy (cod); return NULL; }
+    if (exclusive_scan (c, nlflag, nlex, n, nullptr, (u32 *) c->scan_tmp.p, c->scan_tmp.cap / 4)) return NULL;
     hipLaunchKernelGGL (cd_cstart_kernel, dim3 (grid_for (n)), dim3 (256), 0, c->stream, seq, n, (const u32 *) nlflag, (const u32 *) nlex, cod->cstart);
   }
   if (nf)                                               // (features need contigs, contigs need bytes: n > 0 here)
     hipLaunchKernelGGL (cds_scan_kernel, dim3 ((unsigned) std::min<long> ((nf + 3) / 4, 65536)), dim3 (256), 0, c->stream, (const uint8_t *) cod->codes,
                         (const u32 *) cod->cstart, (const Feature *) feat, h_phase ? (const signed char *) phase : (const signed char *) nullptr, nf, cod->rows);
-  if (hipGetLastError () != hipSuccess) CD_FAIL (TJAMD_ERR_HIP, "%s: launch failed", fn);
-  (void) c->timer[T_CODING].end (c->stream);
-  if (hipStreamSynchronize (c->stream) != hipSuccess) CD_FAIL (TJAMD_ERR_HIP, "%s: build failed: %s", fn, hipGetErrorString (hipGetLastError ()));
-#undef CD_FAIL
-  c->timer[T_CODING].timed = true;
-  return cod;
+  st.end ();
+  if (read_back (c, fn, nullptr, nullptr, 0)) return NULL;
+  st.done ();
+  return cod.release ();
 }
 
 extern "C" long tjamd_coding_features (const tjamd_coding *cod) { return cod ? cod->n_features : -1; }
@@ -8108,7 +8116,7 @@ extern "C" long tjamd_variant_effects (tjamd_counter *c, const tjamd_coding *cod
     return TJAMD_OK;
   };
   int rc = refused ();
-  if (c && tjamd_device_count () > 0) c->timer[T_VARIANT_EFFECTS].timed = false;   // a refused call leaves no timing behind (without a device there is no counter)
+  Stage st (c, T_VARIANT_EFFECTS);                      // (a refused call leaves no timing behind)
   if (rc) return -rc;
   if (hipSetDevice (c->device) != hipSuccess) return -set_err (TJAMD_ERR_HIP, "hipSetDevice failed");
   if (n == 0) return 0;
@@ -8116,22 +8124,21 @@ extern "C" long tjamd_variant_effects (tjamd_counter *c, const tjamd_coding *cod
   if (rc) return -rc;
   int *err = (int *) c->lc_work.p;
   if (hipMemsetAsync (err, 0, 4, c->stream) != hipSuccess) return -set_err (TJAMD_ERR_HIP, "%s: memset failed", fn);
-  (void) c->timer[T_VARIANT_EFFECTS].begin (c->stream);
+  st.begin ();
   hipLaunchKernelGGL (variant_effects_kernel, dim3 ((unsigned) std::min<long> ((n + 255) / 256, 65536)), dim3 (256), 0, c->stream, (const uint8_t *) cod->codes,
                       (const u32 *) cod->cstart, cod->n_contigs, (const CodRow *) cod->rows, cod->n_features, (const Variant *) d_variants, n,
                       (const TractFeature *) d_tract_feat, n_tracts, (Effect *) d_out, err);
-  if (hipGetLastError () != hipSuccess) return -set_err (TJAMD_ERR_HIP, "%s: launch failed", fn);
-  (void) c->timer[T_VARIANT_EFFECTS].end (c->stream);
+  st.end ();
   int h_err = 0;
-  if (hipMemcpyAsync (&h_err, err, 4, hipMemcpyDeviceToHost, c->stream) != hipSuccess || hipStreamSynchronize (c->stream) != hipSuccess)
-    return -set_err (TJAMD_ERR_HIP, "%s: failed: %s", fn, hipGetErrorString (hipGetLastError ()));
+  rc = read_back (c, fn, err, &h_err, 1);
+  if (rc) return -rc;
   if (h_err & 1) return -set_err (TJAMD_ERR_ARG, "%s: a record's contig is outside [0, %ld)", fn, cod->n_contigs);
   if (h_err & 2) return -set_err (TJAMD_ERR_ARG, "%s: a record has pos < 1 or a REF that ends beyond its contig", fn);
   if (h_err & 4) return -set_err (TJAMD_ERR_ARG, "%s: a record's n_flank is outside 0..32", fn);
   if (h_err & 8) return -set_err (TJAMD_ERR_ARG, "%s: a record has ref_length or alt_length < 1", fn);
   if (h_err & 16) return -set_err (TJAMD_ERR_ARG, "%s: a record's tract is outside [0, %ld)", fn, n_tracts);
   if (h_err & 32) return -set_err (TJAMD_ERR_ARG, "%s: a tract's feature index is outside [-1, %ld)", fn, cod->n_features);
-  c->timer[T_VARIANT_EFFECTS].timed = true;
+  st.done ();
   return n;
 }
 extern "C" double tjamd_last_variant_effects_ms (tjamd_counter *c) { return c ? c->timer[T_VARIANT_EFFECTS].ms (c->device) : -1.0; }
@@ -8366,55 +8373,35 @@ extern "C" long tjamd_merge_variants (tjamd_counter *c, int kmer_size, const tja
     return TJAMD_OK;
   };
   int rc = refused ();
-  if (c && tjamd_device_count () > 0) c->timer[T_MERGE_VARIANTS].timed = false;   // a refused call leaves no timing behind (without a device there is no counter)
+  Stage st (c, T_MERGE_VARIANTS);                       // (a refused call leaves no timing behind)
   if (rc) return -rc;
   if (hipSetDevice (c->device) != hipSuccess) return -set_err (TJAMD_ERR_HIP, "hipSetDevice failed");
   if (n == 0) { *h_n_alleles = 0; return 0; }
   const int k = kmer_size, tbits = mv_tract_bits (n_tracts);
   const bool one_word = tbits + 16 + 2 * k <= 64;
-  const int nblk = (int) ((n + RS_ITEMS - 1) / RS_ITEMS);
-  LcCut cut (nullptr);
-  u64 *key[2] = {nullptr, nullptr}; u32 *val[2] = {nullptr, nullptr}, *ahead = nullptr, *shead = nullptr, *aex = nullptr, *sex = nullptr, *smp = nullptr,
-      *astart = nullptr, *sstart = nullptr, *tot = nullptr;
-  MvAgg *agg = nullptr;
-  for (int pass = 0; pass < 2; pass++) {
-    cut = LcCut (pass ? c->lc_work.p : nullptr);
-    key[0] = cut.take<u64> (n); key[1] = cut.take<u64> (n); val[0] = cut.take<u32> (n); val[1] = cut.take<u32> (n);
-    ahead = cut.take<u32> (n); shead = cut.take<u32> (n); aex = cut.take<u32> (n); sex = cut.take<u32> (n); smp = cut.take<u32> (n);
-    astart = cut.take<u32> ((size_t) n + 1); sstart = cut.take<u32> ((size_t) n + 1); agg = cut.take<MvAgg> (n); tot = cut.take<u32> (64);
-    if (!pass) {
-      rc = ensure (c->lc_work, cut.used, c->stream);
-      if (!rc) rc = ensure (c->hist, (size_t) 256 * nblk * 4, c->stream);
-      if (!rc) rc = ensure (c->scan_tmp, std::max (scan_tmp_words (256l * nblk), scan_tmp_words (n)) * 4 + 64, c->stream);
-      if (rc) return -rc;
-    }
-  }
+  ScratchCut cut;
+  u64 *key[2]; u32 *val[2], *ahead, *shead, *aex, *sex, *smp, *astart, *sstart, *tot; MvAgg *agg;
+  cut.take (key[0], n); cut.take (key[1], n); cut.take (val[0], n); cut.take (val[1], n);
+  cut.take (ahead, n); cut.take (shead, n); cut.take (aex, n); cut.take (sex, n); cut.take (smp, n);
+  cut.take (astart, (size_t) n + 1); cut.take (sstart, (size_t) n + 1); cut.take (agg, n); cut.take (tot, 64);
+  rc = cut.commit (c);
+  if (!rc) rc = reserve_sort (c, n, n);
+  if (rc) return -rc;
   u32 *tmp = (u32 *) c->scan_tmp.p; const size_t tw = c->scan_tmp.cap / 4;
   int *err = (int *) tot + 2;                           // tot: the alleles, the sites, the error flag
   if (hipMemsetAsync (tot, 0, 256, c->stream) != hipSuccess) return -set_err (TJAMD_ERR_HIP, "%s: memset failed", fn);
-  (void) c->timer[T_MERGE_VARIANTS].begin (c->stream);
+  st.begin ();
   const Variant *rec = (const Variant *) d_records;
   const unsigned grid = grid_for (n);
-  auto sort_passes = [&] (int bits) -> int {            // stable, on the low `bits` of key[0]: the result is in key[0], val[0] again
-    for (int p = 0; p < (bits + 7) / 8; p++) {
-      hipLaunchKernelGGL (kv_count_kernel, dim3 (nblk), dim3 (256), 0, c->stream, (const u64 *) key[0], n, p, (u32 *) c->hist.p, nblk);
-      const int r = exclusive_scan (c, (const u32 *) c->hist.p, (u32 *) c->hist.p, 256l * nblk, nullptr, tmp, tw);
-      if (r) return r;
-      hipLaunchKernelGGL (kv_scatter_kernel, dim3 (nblk), dim3 (256), 0, c->stream, (const u64 *) key[0], (const u32 *) val[0], key[1], val[1], n, p,
-                          (const u32 *) c->hist.p, nblk);
-      std::swap (key[0], key[1]); std::swap (val[0], val[1]);
-    }
-    return TJAMD_OK;
-  };
   if (one_word) {
     hipLaunchKernelGGL (mv_key_kernel, dim3 (grid), dim3 (256), 0, c->stream, rec, n, 0, k, n_samples, n_tracts, (const u32 *) nullptr, key[0], val[0], err);
-    rc = sort_passes (tbits + 16 + 2 * k);
+    rc = kv_sort (c, key, val, n, tbits + 16 + 2 * k);
   } else {                                              // the flank word first, then the rest: the second sort keeps the first one's order
     hipLaunchKernelGGL (mv_key_kernel, dim3 (grid), dim3 (256), 0, c->stream, rec, n, 1, k, n_samples, n_tracts, (const u32 *) nullptr, key[0], val[0], err);
-    rc = sort_passes (2 * k);
+    rc = kv_sort (c, key, val, n, 2 * k);
     if (!rc) {
       hipLaunchKernelGGL (mv_key_kernel, dim3 (grid), dim3 (256), 0, c->stream, rec, n, 2, k, n_samples, n_tracts, (const u32 *) val[0], key[0], (u32 *) nullptr, err);
-      rc = sort_passes (tbits + 16);
+      rc = kv_sort (c, key, val, n, tbits + 16);
     }
   }
   if (rc) return -rc;
@@ -8430,11 +8417,10 @@ extern "C" long tjamd_merge_variants (tjamd_counter *c, int kmer_size, const tja
   hipLaunchKernelGGL (mv_write_kernel, dim3 (grid), dim3 (256), 0, c->stream, rec, (const u32 *) val[0], n, n_samples, (const u32 *) ahead, (const u32 *) aex,
                       (const u32 *) shead, (const u32 *) sex, (const u32 *) astart, (const u32 *) sstart, (const MvAgg *) agg, (const u32 *) tot,
                       (Site *) d_sites, site_capacity, (Allele *) d_alleles, allele_capacity, d_genotype, d_allele_of, (Variant *) d_unique, (const int *) err);
-  if (hipGetLastError () != hipSuccess) return -set_err (TJAMD_ERR_HIP, "%s: launch failed", fn);
-  (void) c->timer[T_MERGE_VARIANTS].end (c->stream);
+  st.end ();
   u32 h[3] = {0, 0, 0};
-  if (hipMemcpyAsync (h, tot, 12, hipMemcpyDeviceToHost, c->stream) != hipSuccess || hipStreamSynchronize (c->stream) != hipSuccess)
-    return -set_err (TJAMD_ERR_HIP, "%s: failed: %s", fn, hipGetErrorString (hipGetLastError ()));
+  rc = read_back (c, fn, tot, h, 3);
+  if (rc) return -rc;
   if (h[2] & 1u) return -set_err (TJAMD_ERR_ARG, "%s: a record's tract is outside [0, %ld)", fn, n_tracts);
   if (h[2] & 2u) return -set_err (TJAMD_ERR_ARG, "%s: a record's sample is outside [0, %d)", fn, n_samples);
   if (h[2] & 4u) return -set_err (TJAMD_ERR_ARG, "%s: a record's n_flank is outside 0..%d", fn, k);
@@ -8445,7 +8431,7 @@ extern "C" long tjamd_merge_variants (tjamd_counter *c, int kmer_size, const tja
   if ((long) h[1] > site_capacity || (long) h[0] > allele_capacity)
     return -set_err (TJAMD_ERR_CAPACITY, "%s: %u sites and %u alleles, caller capacities %ld and %ld", fn, h[1], h[0], site_capacity, allele_capacity);
   *h_n_alleles = (long) h[0];
-  c->timer[T_MERGE_VARIANTS].timed = true;
+  st.done ();
   return (long) h[1];
 }
 extern "C" double tjamd_last_merge_variants_ms (tjamd_counter *c) { return c ? c->timer[T_MERGE_VARIANTS].ms (c->device) : -1.0; }

@@ -13,6 +13,7 @@ from tests.guarded import GuardedDevice, GuardedHost, frozen
 
 ERR_ARG, ERR_CAP = 3, 4
 TS, TR, SU, LOC = tj.TRACT_SUMMARY_DTYPE, tj.UNION_TRACT_DTYPE, tj.UNION_TRACT_SUMMARY_DTYPE, tj.LOCATION_DTYPE
+VAR, TF, EF, ST, AL = tj.VARIANT_DTYPE, tj.TRACT_FEATURE_DTYPE, tj.EFFECT_DTYPE, tj.SITE_DTYPE, tj.ALLELE_DTYPE
 N_STATS = 5                              # TJAMD_N_TRACT_STATS
 
 # row counts, tract counts and query counts of the device entries: one on each side of, and at, every constant by which the
@@ -245,6 +246,56 @@ def call_located_tracts(c, u, tracts, nt, loc, cap, n=None, null=()):
                                            *[_p(outs[name]) for name in DEVICE["tjamd_located_tracts"]], cap)
         _checked(outs)
     return Result(rc, outs)
+
+
+def call_locate_gapped(c, ref, kd, n, max_edits, max_shift):
+    """kd: device bytes of tjamd_record[>= n]; d_loc goes in with no row located, so the call tries every row"""
+    from tests.test_locate_cabi import NOWHERE
+    outs = _buffers({"d_loc": n * LOC.itemsize, "d_how": n * 4}, ())
+    outs["d_loc"].payload.copy_(dev(np.array([NOWHERE] * n, LOC)))
+    with frozen(kd):
+        rc = tj.lib().tjamd_locate_gapped(c._h, ref._h, _p(kd), n, max_edits, max_shift, _p(outs["d_loc"]), _p(outs["d_how"]))
+        _checked(outs)
+    return Result(rc, outs)
+
+
+def call_tract_variants(c, ref, u, tracts, nt, tract_loc, cap, lst=None):
+    """tracts, tract_loc: device bytes of tjamd_union_tract[nt] and tjamd_location[nt]; lst: device int32 tensor, or None (every tract)"""
+    outs = _buffers({"d_out": cap * VAR.itemsize, "h_offsets": (u.ns + 1) * 8}, (), host=("h_offsets",))
+    with frozen(u.kd, u.md, tracts, tract_loc, lst):
+        rc = tj.lib().tjamd_tract_variants(c._h, ref._h, _p(u.kd), _p(u.md), u.n, u.ns, _p(tracts), nt, _p(tract_loc), _p(lst), 0 if lst is None else int(lst.numel()),
+                                           _p(outs["d_out"]), cap, _p(outs["h_offsets"]))
+        _checked(outs)
+    return Result(rc, outs)
+
+
+def call_tract_features(c, ann, u, tracts, nt, tract_loc):
+    outs = _buffers({"d_out": nt * TF.itemsize}, ())
+    with frozen(u.kd, u.md, tracts, tract_loc):
+        rc = tj.lib().tjamd_tract_features(c._h, ann._h, _p(u.kd), _p(u.md), u.n, u.ns, _p(tracts), nt, _p(tract_loc), _p(outs["d_out"]))
+        _checked(outs)
+    return Result(rc, outs)
+
+
+def call_variant_effects(c, cod, variants, n, tract_feat=None, nt=0):
+    """variants: device bytes of tjamd_variant[n]; tract_feat: device bytes of tjamd_tract_feature[nt], or None"""
+    outs = _buffers({"d_out": n * EF.itemsize}, ())
+    with frozen(variants, tract_feat):
+        rc = tj.lib().tjamd_variant_effects(c._h, cod._h, _p(variants), n, _p(tract_feat), nt, _p(outs["d_out"]))
+        _checked(outs)
+    return Result(rc, outs)
+
+
+def call_merge_variants(c, k, variants, n, ns, nt, site_cap, allele_cap):
+    """variants: device bytes of tjamd_variant[n]; every optional output is asked for"""
+    outs = _buffers({"d_sites": site_cap * ST.itemsize, "d_alleles": allele_cap * AL.itemsize, "d_genotype": site_cap * ns * 2, "d_allele_of": n * 4,
+                     "d_unique": allele_cap * VAR.itemsize}, ())
+    na = C.c_long(-1)
+    with frozen(variants):
+        rc = tj.lib().tjamd_merge_variants(c._h, k, _p(variants), n, ns, nt, _p(outs["d_sites"]), site_cap, _p(outs["d_alleles"]), allele_cap,
+                                           _p(outs["d_genotype"]), _p(outs["d_allele_of"]), _p(outs["d_unique"]), C.byref(na))
+        _checked(outs)
+    return Result(rc, outs, n_alleles=na.value)
 
 
 # ---- the outputs in the shape the suite's checks take (tests/test_tract_stats.py, test_union_tracts.py, test_locate.py) ----

@@ -4,8 +4,10 @@ kernel that read scratch it had not written in this call -- the tail a larger pr
 left -- would pass every test that takes a fresh counter.  Here one counter goes through a fixed sequence: every entry on
 a large problem (4097 rows by 70 samples), then on a small one of another shape (65 rows by 3 samples), then on the small
 one directly after each kind of refused call on the large one, with a sample scanned, the counter reset and another
-scanned, and a reference built, used, closed and built again smaller.  Every result is bit for bit that of the same call on
-a fresh counter; every output sits in a guarded buffer (tests/bounds_calls.py)."""
+scanned, and a reference built, used, closed and built again smaller; the annotation layer (variants, features, the seed
+order and the gapped lookup, coding effects, merged sites) goes through the same sequence on tracts placed on the genome.
+Every result is bit for bit that of the same call on a fresh counter; every output sits in a guarded buffer
+(tests/bounds_calls.py)."""
 import random
 
 import numpy as np
@@ -16,9 +18,10 @@ from tatajuba_amd import capi
 from oracle import orc
 from tests import bounds_calls as bc
 from tests.bounds_calls import ERR_ARG, ERR_CAP, Union
+from tests.test_effects import features_of
 from tests.guarded import GuardedHost, frozen
 from tests.test_locate import queries_for, random_genome
-from tests.test_locate_cabi import restate_reference_index
+from tests.test_locate_cabi import contigs_of, restate_reference_index
 from tests.test_union_tracts import random_families
 from tests.test_union_tracts_cabi import oracle_union_grouping
 
@@ -54,6 +57,36 @@ class Problem:
         us = bc.call_union_tract_stats(prep, self.u, self.tracts, self.nt)
         assert ts.rc == self.n_ctx and us.rc == self.nt
         self.ts_summary, self.us_summary = ts["d_summary"].payload.clone(), us["d_summary"].payload.clone()
+        # the annotation layer: every tract placed on an entry of the genome's index (in turn), a handful of features on the
+        # genome, and the variant records tjamd_tract_variants itself gives
+        at = entries[np.arange(self.nt) % len(entries)]
+        tl = np.zeros(self.nt, tj.LOCATION_DTYPE)
+        for f, g in (("flat", "flat"), ("contig", "contig"), ("pos", "pos"), ("ref_length", "length"), ("neg_strand", "neg_strand")):
+            tl[f] = at[g]
+        tl["n_hits"] = 1
+        self.tract_loc = bc.dev(tl)
+        sizes = [len(s) for s in contigs_of(self.genome)]
+        last = len(sizes) - 1
+        self.features = features_of([(0, 1, sizes[0], 0, 0), (0, 1, sizes[0] // 2, 2, 0), (0, 4, sizes[0] // 3, 1, 0), (0, sizes[0] // 2, sizes[0] - 2, 1, 1),
+                                     (last, 1, sizes[last], 0, 0), (last, 2, sizes[last] - 1, 1, 0), (3, 10, 300, 1, 1)])
+        ref, ann, cod = tj.Reference(prep, self.genome), None, None
+        try:
+            assert ref.add_seeds(prep) == ref.n_entries == len(entries) > 0
+            ann, cod = tj.Annotation(prep, ref, self.features), tj.Coding(prep, self.genome, self.features)
+            tv = bc.call_tract_variants(prep, ref, self.u, self.tracts, self.nt, self.tract_loc, self.nt * self.u.ns)
+            tf = bc.call_tract_features(prep, ann, self.u, self.tracts, self.nt, self.tract_loc)
+            assert tv.rc > 0 and tf.rc == self.nt > 0
+            self.n_variants, self.variants = tv.rc, tv["d_out"].payload[: tv.rc * tj.VARIANT_DTYPE.itemsize].clone()
+            self.tract_feat = tf["d_out"].payload.clone()
+            lg = bc.call_locate_gapped(prep, ref, self.queries, self.n_queries, MM, MM)
+            ve = bc.call_variant_effects(prep, cod, self.variants, self.n_variants, self.tract_feat, self.nt)
+            mv = bc.call_merge_variants(prep, K, self.variants, self.n_variants, self.u.ns, self.nt, self.nt, self.n_variants)
+            assert lg.rc > 0 and ve.rc == self.n_variants and mv.rc > 0 and mv.n_alleles >= mv.rc
+            self.n_sites, self.n_alleles = mv.rc, mv.n_alleles
+        finally:
+            for h in (cod, ann, ref):
+                if h is not None:
+                    h.close()
         prep.close()
 
 
@@ -73,6 +106,37 @@ def run_reference(c, p):
         ref.close()
 
 
+def with_reference(c, p, call, seeds=False):
+    """a call that takes the genome's index, built on this counter for the call"""
+    ref = tj.Reference(c, p.genome)
+    try:
+        assert not seeds or ref.add_seeds(c) == ref.n_entries
+        r = call(ref)
+        assert r.rc > 0
+        return signature(r, ref.has_seeds)
+    finally:
+        ref.close()
+
+
+def run_features(c, p):
+    ref = tj.Reference(c, p.genome)
+    ann = tj.Annotation(c, ref, p.features)
+    try:
+        table = tuple(x.tobytes() for x in ann.download())
+        return signature(bc.call_tract_features(c, ann, p.u, p.tracts, p.nt, p.tract_loc), table)
+    finally:
+        ann.close()
+        ref.close()
+
+
+def run_effects(c, p):
+    cod = tj.Coding(c, p.genome, p.features)
+    try:
+        return signature(bc.call_variant_effects(c, cod, p.variants, p.n_variants, p.tract_feat, p.nt), cod.download().tobytes())
+    finally:
+        cod.close()
+
+
 ENTRIES = {
     "tjamd_merge_samples": lambda c, p: signature(bc.call_merge_samples(c, p.records, p.counts, p.u.ns, p.u.n)),
     "tjamd_tract_ids": lambda c, p: signature(bc.call_tract_ids(c, p.u)),
@@ -85,6 +149,11 @@ ENTRIES = {
     "tjamd_reference_create, tjamd_locate": run_reference,
     "tjamd_located_tracts": lambda c, p: signature(bc.call_located_tracts(c, p.u, p.tracts, p.nt, p.loc, p.u.n)),
     "tjamd_located_tracts (no tracts)": lambda c, p: signature(bc.call_located_tracts(c, p.u, None, 0, p.loc, p.u.n)),
+    "tjamd_tract_variants": lambda c, p: with_reference(c, p, lambda ref: bc.call_tract_variants(c, ref, p.u, p.tracts, p.nt, p.tract_loc, p.n_variants)),
+    "tjamd_annotation_create, tjamd_tract_features": run_features,
+    "tjamd_reference_add_seeds, tjamd_locate_gapped": lambda c, p: with_reference(c, p, lambda ref: bc.call_locate_gapped(c, ref, p.queries, p.n_queries, MM, MM), seeds=True),
+    "tjamd_coding_create, tjamd_variant_effects": run_effects,
+    "tjamd_merge_variants": lambda c, p: (lambda r: signature(r, r.n_alleles))(bc.call_merge_variants(c, K, p.variants, p.n_variants, p.u.ns, p.nt, p.n_sites, p.n_alleles)),
 }
 
 
@@ -118,7 +187,39 @@ def refuse_flat(c, p):
     bc.call_located_tracts(c, p.u, None, 0, bc.dev(far), p.u.n).refused(ERR_ARG, "flat >= 2^45")
 
 
-REFUSALS = {"capacity": refuse_capacity, "bad ids": refuse_bad_ids, "tracts that do not tile": refuse_tiling, "flat too large": refuse_flat}
+def refuse_on_the_genome(c, p):
+    """the entries that take the genome's index or a table built on it"""
+    bad = p.tracts_host.copy()
+    bad["n_rows"][len(bad) // 2] += 1
+    ref = tj.Reference(c, p.genome)
+    ann = tj.Annotation(c, ref, p.features)
+    try:
+        for f in (lambda: tj.Annotation(c, ref, features_of([(ref.n_contigs, 1, 2, 1, 0)])), lambda: tj.Coding(c, p.genome, features_of([(0, 5, 4, 1, 0)]))):
+            with pytest.raises(tj.TatajubaAmdError, match="feature 0"):
+                f()
+        bc.call_locate_gapped(c, ref, p.queries, p.n_queries, MM, MM).refused(ERR_ARG, "no seed order")
+        bc.call_tract_features(c, ann, p.u, bc.dev(bad), len(bad), p.tract_loc).refused(ERR_ARG, "do not tile the union")
+        listed = bc.dev(np.array([0, p.nt], np.int32), np.int32)
+        bc.call_tract_variants(c, ref, p.u, p.tracts, p.nt, p.tract_loc, p.n_variants, lst=listed).refused(ERR_ARG, "a listed tract id is outside")
+    finally:
+        ann.close()
+        ref.close()
+
+
+def refuse_records(c, p):
+    v = np.frombuffer(p.variants.cpu().numpy().tobytes(), tj.VARIANT_DTYPE).copy()
+    twice = bc.dev(np.concatenate([v, v[:1]]))
+    bc.call_merge_variants(c, K, twice, len(v) + 1, p.u.ns, p.nt, p.n_sites, p.n_alleles).refused(ERR_ARG, "pair occurs twice")
+    v["contig"][len(v) // 2] = 1 << 20
+    cod = tj.Coding(c, p.genome, p.features)
+    try:
+        bc.call_variant_effects(c, cod, bc.dev(v), len(v), p.tract_feat, p.nt).refused(ERR_ARG, "contig is outside")
+    finally:
+        cod.close()
+
+
+REFUSALS = {"capacity": refuse_capacity, "bad ids": refuse_bad_ids, "tracts that do not tile": refuse_tiling, "flat too large": refuse_flat,
+            "on the genome": refuse_on_the_genome, "bad records": refuse_records}
 
 
 def sample_state(c, m):
