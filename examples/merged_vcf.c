@@ -6,6 +6,8 @@
  *   DIR/merged.vcf            sample_vcfs.c's header with ##INFO lines for AC and AN and one column per sample; one row per
  *                             site, ALT comma-separated in allele order, haploid GT 1, 2, ... or "." where the sample has no record:
  *                             contig  POS  .  REF  ALT1,ALT2  .  .  AC=n1,n2;AN=n_called;TID=tid_%06d  GT  g0  g1 ...
+ *                             with -D: tjamd_site_depths after the merge; FORMAT is GT:DP:AD, GT is 0 where the sample's reads
+ *                             show the genome's own length and "." only where it was not seen, AN counts the reference samples too
  *   DIR/unique_variants.vcf   with -u: the tutorial's concatenation, one row per distinct allele in N8's own form (the record
  *                             d_unique holds), one column all_samples
  *   DIR/variant_effects.tsv   with -e annotation.gff3: tjamd_variant_effects on d_unique only, one line per allele: variant_effects.c's
@@ -13,11 +15,11 @@
  * The other options are sample_vcfs.c's.
  *
  *   gcc -O2 -I include examples/merged_vcf.c -L tatajuba_amd -ltatajuba_amd -Wl,-rpath,$PWD/tatajuba_amd -o merged_vcf
- *   ./merged_vcf -r reference.fa [-u] [-e annotation.gff3] [-x 1] [-g G] [-s 3] [-k 10] [-m 3] [-c 5] [-d 1] [-l -1] [-o .] sample1.fastq[.gz] ...   */
+ *   ./merged_vcf -r reference.fa [-u] [-D] [-e annotation.gff3] [-x 1] [-g G] [-s 3] [-k 10] [-m 3] [-c 5] [-d 1] [-l -1] [-o .] sample1.fastq[.gz] ...   */
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
-#include <tatajuba_sites.h>
+#include <tatajuba_depths.h>
 #include <tatajuba_effects.h>
 #include <tatajuba_locate.h>
 
@@ -75,10 +77,11 @@ main (int argc, char **argv)
   static const char *class_name[5] = {"NONE", "BOUNDARY", "IDENTICAL", "INFRAME", "FRAMESHIFT"};
   long counts[MAX_SAMPLES], total, n_union, n_grouped, n_tracts, n_located, n_gapped = 0, n_var = 0, n_rec, i, cap, ref_bytes, n_contigs = 0, n_names = 0, name_bytes;
   long offsets[MAX_SAMPLES + 1], *contig_len, var_cap, n_sites, n_alleles = 0, s, text_cap = 0;
-  int with_unique = 0;
+  int with_unique = 0, with_depths = 0;
   int n = 0, k = 10, m = 3, cov = 5, maxd = 1, lev = -1, mism = 1, max_edits = -1, max_shift = TJAMD_MAX_SHIFT, coverage[MAX_SAMPLES], a, ndev = tjamd_device_count (), status;
   const void *d_records = NULL;
-  void *d_keys, *d_counts, *d_ids, *d_grouped, *d_loc, *d_perm, *d_pkeys, *d_pcounts, *d_tracts, *d_tloc, *d_reflen, *d_summary, *d_var, *d_variants, *d_sites, *d_alleles, *d_genotype, *d_unique;
+  void *d_keys, *d_counts, *d_ids, *d_grouped, *d_loc, *d_perm, *d_pkeys, *d_pcounts, *d_tracts, *d_tloc, *d_reflen, *d_summary, *d_var, *d_variants, *d_sites, *d_alleles, *d_genotype, *d_unique,
+       *d_dp = NULL, *d_ad = NULL, *d_sd = NULL;
   unsigned char *ref_stream;
   char *names, **contig_name;
   tjamd_reference *ref;
@@ -86,6 +89,8 @@ main (int argc, char **argv)
   tjamd_site *h_sites;
   tjamd_allele *h_alleles;
   int16_t *h_genotype;
+  int *h_dp = NULL, *h_ad = NULL;
+  tjamd_site_depth *h_sd = NULL;
   char *text, **sample_name;
   FILE *fout;
 
@@ -102,9 +107,10 @@ main (int argc, char **argv)
     else if (!strcmp (argv[a], "-o") && a + 1 < argc) outdir = argv[++a];
     else if (!strcmp (argv[a], "-e") && a + 1 < argc) gff = argv[++a];
     else if (!strcmp (argv[a], "-u")) with_unique = 1;
+    else if (!strcmp (argv[a], "-D")) with_depths = 1;
     else if (n < MAX_SAMPLES) files[n++] = argv[a];
   }
-  if (n < 1 || !reference) { fprintf (stderr, "usage: %s -r reference.fa [-u] [-e annotation.gff3] [-x X] [-g G] [-s S] [-k K] [-m M] [-c C] [-d D] [-l L] [-o DIR] sample.fastq[.gz] ...\n", argv[0]); return 2; }
+  if (n < 1 || !reference) { fprintf (stderr, "usage: %s -r reference.fa [-u] [-D] [-e annotation.gff3] [-x X] [-g G] [-s S] [-k K] [-m M] [-c C] [-d D] [-l L] [-o DIR] sample.fastq[.gz] ...\n", argv[0]); return 2; }
   if (ndev < 1) { fprintf (stderr, "tatajuba_amd error: no HIP device is visible (there is no CPU fallback)\n"); return 1; }
   if (maxd < 0) maxd = 0;                                 /* src/main.c:190-192 */
   if (maxd > k / 2) maxd = k / 2;
@@ -196,6 +202,21 @@ main (int argc, char **argv)
   n_sites = tjamd_merge_variants (ctr[0], k, (const tjamd_variant *) d_variants, n_rec, n, n_tracts, (tjamd_site *) d_sites, cap, (tjamd_allele *) d_alleles, cap,
                                   (int16_t *) d_genotype, NULL, (tjamd_variant *) d_unique, &n_alleles);
   if (n_sites < 0) return fail ("merge variants");
+  if (with_depths) {                                      /* the same union and tiling once more: depths, and 0 or -1 where N12 has -1 */
+    const size_t cells = (size_t) (n_sites ? n_sites : 1) * (size_t) n, ad_cells = (size_t) (n_sites + n_alleles ? n_sites + n_alleles : 1) * (size_t) n;
+    d_dp = tjamd_device_alloc (ctr[0], cells * sizeof (int));
+    d_ad = tjamd_device_alloc (ctr[0], ad_cells * sizeof (int));
+    d_sd = tjamd_device_alloc (ctr[0], (size_t) (n_sites ? n_sites : 1) * sizeof (tjamd_site_depth));
+    if (tjamd_site_depths (ctr[0], ref, d_pkeys, d_pcounts, n_union, n, (const tjamd_union_tract *) d_tracts, n_tracts, (const tjamd_location *) d_tloc,
+                           (const tjamd_site *) d_sites, n_sites, (const tjamd_allele *) d_alleles, n_alleles, (int16_t *) d_genotype, (int *) d_dp, (int *) d_ad,
+                           (tjamd_site_depth *) d_sd) < 0) return fail ("site depths");
+    h_dp = (int *) malloc (cells * sizeof (int));
+    h_ad = (int *) malloc (ad_cells * sizeof (int));
+    h_sd = (tjamd_site_depth *) malloc ((size_t) (n_sites ? n_sites : 1) * sizeof (tjamd_site_depth));
+    if (tjamd_device_download (ctr[0], h_dp, d_dp, (size_t) n_sites * (size_t) n * sizeof (int)) ||
+        tjamd_device_download (ctr[0], h_ad, d_ad, (size_t) (n_sites + n_alleles) * (size_t) n * sizeof (int)) ||
+        tjamd_device_download (ctr[0], h_sd, d_sd, (size_t) n_sites * sizeof (tjamd_site_depth))) return fail ("download");
+  }
   h_sites = (tjamd_site *) malloc ((size_t) (n_sites ? n_sites : 1) * sizeof (tjamd_site));
   h_alleles = (tjamd_allele *) malloc ((size_t) (n_alleles ? n_alleles : 1) * sizeof (tjamd_allele));
   h_genotype = (int16_t *) malloc ((size_t) (n_sites ? n_sites : 1) * (size_t) n * sizeof (int16_t));
@@ -229,10 +250,12 @@ main (int argc, char **argv)
   text = (char *) malloc ((size_t) text_cap + 1);
 
   if (!(fout = open_output (outdir, "merged.vcf"))) return 1;
-  fprintf (fout, "##fileformat=VCFv4.2\n##FORMAT=<ID=GT,Number=1,Type=String,Description=\"Genotype\">\n"
-                 "##INFO=<ID=AC,Number=A,Type=Integer,Description=\"samples that carry each ALT allele\">\n"
-                 "##INFO=<ID=AN,Number=1,Type=Integer,Description=\"samples with a call\">\n"
-                 "##INFO=<ID=TID,Number=A,Type=String,Description=\"tract ID\">\n");
+  fprintf (fout, "##fileformat=VCFv4.2\n##FORMAT=<ID=GT,Number=1,Type=String,Description=\"Genotype\">\n");
+  if (with_depths) fprintf (fout, "##FORMAT=<ID=DP,Number=1,Type=Integer,Description=\"reads on the tract\">\n"
+                                  "##FORMAT=<ID=AD,Number=R,Type=Integer,Description=\"reads on the reference length and on each ALT allele\">\n");
+  fprintf (fout, "##INFO=<ID=AC,Number=A,Type=Integer,Description=\"samples that carry each ALT allele\">\n"
+                 "##INFO=<ID=AN,Number=1,Type=Integer,Description=\"%s\">\n"
+                 "##INFO=<ID=TID,Number=A,Type=String,Description=\"tract ID\">\n", with_depths ? "samples with a genotype, the reference's included" : "samples with a call");
   for (i = 0; i < n_contigs; i++) fprintf (fout, "##contig=<ID=%s,length=%ld>\n", contig_name[i], contig_len[i]);
   fprintf (fout, "#CHROM\tPOS\tID\tREF\tALT\tQUAL\tFILTER\tINFO\tFORMAT");
   for (a = 0; a < n; a++) fprintf (fout, "\t%s", sample_name[a]);
@@ -248,10 +271,14 @@ main (int argc, char **argv)
     }
     fprintf (fout, "\t.\t.\tAC=");
     for (i = 0; i < site->n_alleles; i++) fprintf (fout, "%s%d", i ? "," : "", al[i].n_samples);
-    fprintf (fout, ";AN=%d;TID=tid_%06d\tGT", site->n_called, site->tract);
+    fprintf (fout, ";AN=%d;TID=tid_%06d\tGT%s", with_depths ? n - h_sd[s].n_missing : site->n_called, site->tract, with_depths ? ":DP:AD" : "");
     for (a = 0; a < n; a++) {
       const int g = h_genotype[s * n + a];
       if (g < 0) fprintf (fout, "\t."); else fprintf (fout, "\t%d", g);
+      if (with_depths) {                                  /* the site's AD rows: REF, then its alleles */
+        fprintf (fout, ":%d:", h_dp[s * n + a]);
+        for (i = 0; i <= site->n_alleles; i++) fprintf (fout, "%s%d", i ? "," : "", h_ad[(site->first_allele + s + i) * n + a]);
+      }
     }
     fputc ('\n', fout);
   }
@@ -327,6 +354,7 @@ main (int argc, char **argv)
   tjamd_device_free (ctr[0], d_loc); tjamd_device_free (ctr[0], d_perm); tjamd_device_free (ctr[0], d_pkeys); tjamd_device_free (ctr[0], d_pcounts);
   tjamd_device_free (ctr[0], d_tracts); tjamd_device_free (ctr[0], d_tloc); tjamd_device_free (ctr[0], d_reflen);
   tjamd_device_free (ctr[0], d_summary); tjamd_device_free (ctr[0], d_var); tjamd_device_free (ctr[0], d_variants);
+  if (with_depths) { tjamd_device_free (ctr[0], d_dp); tjamd_device_free (ctr[0], d_ad); tjamd_device_free (ctr[0], d_sd); free (h_dp); free (h_ad); free (h_sd); }
   tjamd_device_free (ctr[0], d_sites); tjamd_device_free (ctr[0], d_alleles); tjamd_device_free (ctr[0], d_genotype); tjamd_device_free (ctr[0], d_unique);
   free (h_sites); free (h_alleles); free (h_genotype); free (h_unique); free (text); free (ref_stream);
   for (a = 0; a < n; a++) free (sample_name[a]);

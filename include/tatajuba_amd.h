@@ -394,6 +394,10 @@ long tjamd_located_tracts (tjamd_counter *c, const void *d_keys, const void *d_c
  * tjamd_merge_variants, tjamd_site_ref_alt) are declared, with their timer, in tatajuba_sites.h, which includes
  * tatajuba_variants.h and through it this header. */
 
+/* The read depths of the merged sites and the genotype that tells a reference sample from an unseen one (N13:
+ * tjamd_site_depths) are declared, with their timer, in tatajuba_depths.h, which includes tatajuba_sites.h and through it this
+ * header. */
+
 /* release the calling thread's shared device contexts of the synchronous string scans (update_hopo_counter_from_seq on a
  * counter that never read a file, tjamd_scan_windows) now; they are released by themselves when the thread ends */
 void tjamd_thread_cleanup (void);

@@ -42,7 +42,8 @@ extern "C" {
  *   kmer_size outside 1 .. 32, a site n_flank outside 0 .. kmer_size, a base outside 0 .. 3 or a length below min_length.
  * Genotype: d_genotype[site * n_samples + s] is the 1-based index, within the site, of sample s's allele, and -1 where s has
  *   no record there: bcftools merge's ".".  N8 does not say whether a sample without a record equals the reference or was not
- *   seen, and this step does not guess.  Rows at or beyond the number of sites are not written.
+ *   seen, and this step does not guess: tjamd_site_depths (tatajuba_depths.h, N13) reads the union's counts and tells the two
+ *   apart.  Rows at or beyond the number of sites are not written.
  * d_allele_of[i] (optional) is the global allele index of input record i; d_unique[a] (optional) is record first_record of
  *   allele a, unchanged: the input of tjamd_variant_effects that walks every distinct allele once.
  * Returns the number of sites and sets *h_n_alleles.  n_records == 0 returns 0 and sets it to 0, with no launch.
@@ -59,7 +60,8 @@ extern "C" {
  * Changes none of its inputs nor the counter's finalised state.  Waits once, at the end.  No atomic decides a place (the error
  *   flag is the only global atomic): two runs give the same bytes.
  * Not built: left-alignment to the base in front of the run (bcftools norm's form; the anchor here is N8's, the last base the
- *   alleles share); phasing of two tracts; a reference genotype 0 for samples that N8 leaves without a record; gzip output. */
+ *   alleles share); phasing of two tracts; gzip output.  (A reference genotype 0 for samples that N8 leaves without a record is
+ *   N13's, tatajuba_depths.h.) */
 typedef struct { long long flat; int tract, contig, pos, base, ref_length, min_length, n_flank,
                  n_alleles, first_allele, n_called, first_record, pad; uint64_t ref_flank; } tjamd_site;    /* 64 bytes */
 typedef struct { int site, alt_length, n_flank, n_samples, first_record, pad; uint64_t alt_flank; } tjamd_allele;   /* 32 bytes */

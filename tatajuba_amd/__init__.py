@@ -9,4 +9,5 @@ from .capi import (Counter, Comm, Reference, Annotation, REF_ENTRY_DTYPE, LOCATI
                    LOCATED_DTYPE, GROUP_DTYPE, TRACT_SUMMARY_DTYPE, UNION_TRACT_DTYPE, UNION_TRACT_SUMMARY_DTYPE, decode_meta, TatajubaAmdError, read_file_stream, EXPORTS, VARIANT_EXPORTS, FEATURE_EXPORTS, LOCATE_EXPORTS, MAX_SHIFT, flank_edit_distance,
                    read_gff3, gff3_string,
                    Coding, CDS_DTYPE, EFFECT_DTYPE, EFFECT_CLASSES, EFFECT_EXPORTS, translate, read_gff3_phase,
-                   SITE_DTYPE, ALLELE_DTYPE, SITE_EXPORTS, site_ref_alt)
+                   SITE_DTYPE, ALLELE_DTYPE, SITE_EXPORTS, site_ref_alt,
+                   SITE_DEPTH_DTYPE, DEPTH_EXPORTS)

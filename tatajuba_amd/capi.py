@@ -67,6 +67,8 @@ assert SITE_DTYPE.itemsize == 64
 ALLELE_DTYPE = np.dtype([("site", "<i4"), ("alt_length", "<i4"), ("n_flank", "<i4"), ("n_samples", "<i4"), ("first_record", "<i4"), ("pad", "<i4"),
                          ("alt_flank", "<u8")])
 assert ALLELE_DTYPE.itemsize == 32
+SITE_DEPTH_DTYPE = np.dtype([("n_ref", "<i4"), ("n_missing", "<i4"), ("depth", "<i8")])      # tjamd_site_depth (include/tatajuba_depths.h)
+assert SITE_DEPTH_DTYPE.itemsize == 16
 
 
 class TatajubaAmdError(RuntimeError):
@@ -158,6 +160,8 @@ EFFECT_EXPORTS = ["tjamd_translate", "tjamd_gff3_read_phase", "tjamd_coding_crea
                   "tjamd_variant_effects", "tjamd_last_coding_ms", "tjamd_last_variant_effects_ms"]
 # ... and include/tatajuba_sites.h
 SITE_EXPORTS = ["tjamd_merge_variants", "tjamd_site_ref_alt", "tjamd_last_merge_variants_ms"]
+# ... and include/tatajuba_depths.h
+DEPTH_EXPORTS = ["tjamd_site_depths", "tjamd_last_site_depths_ms"]
 MAX_SHIFT = 3                     # TJAMD_MAX_SHIFT
 
 
@@ -314,6 +318,10 @@ def lib():
                                        C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     L.tjamd_site_ref_alt.restype = C.c_int; L.tjamd_site_ref_alt.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int]
     L.tjamd_last_merge_variants_ms.restype = C.c_double; L.tjamd_last_merge_variants_ms.argtypes = [C.c_void_p]
+    L.tjamd_site_depths.restype = C.c_long
+    L.tjamd_site_depths.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_long, C.c_int, C.c_void_p, C.c_long, C.c_void_p,
+                                    C.c_void_p, C.c_long, C.c_void_p, C.c_long, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.tjamd_last_site_depths_ms.restype = C.c_double; L.tjamd_last_site_depths_ms.argtypes = [C.c_void_p]
     L.tjamd_group_contexts.restype = C.c_long
     L.tjamd_group_contexts.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_long]
     L.new_genomic_context_list.restype = C.POINTER(GenomicContextListStruct); L.new_genomic_context_list.argtypes = [P]
@@ -894,6 +902,17 @@ class Counter:
 
     def last_merge_variants_ms(self):
         return lib().tjamd_last_merge_variants_ms(self._h)
+
+    def site_depths(self, ref, d_keys, d_counts, n_union, n_samples, d_tracts, n_tracts, d_tract_loc, d_sites, n_sites, d_alleles, n_alleles,
+                    d_genotype=None, d_depth=None, d_allele_depth=None, d_summary=None):
+        """tjamd_site_depths on device pointers: the permuted union and tiling tjamd_tract_variants was given and the sites and
+        alleles of tjamd_merge_variants -> optionally int16 genotypes [site][sample] (0 = reference, -1 = not seen), int32 DP
+        [site][sample], int32 AD [(n_sites + n_alleles)][sample] and one SITE_DEPTH_DTYPE record per site.  -> n_sites"""
+        return self._chkn(lib().tjamd_site_depths(self._h, ref._h, d_keys, d_counts, n_union, n_samples, d_tracts, n_tracts, d_tract_loc,
+                                                  d_sites, n_sites, d_alleles, n_alleles, d_genotype, d_depth, d_allele_depth, d_summary))
+
+    def last_site_depths_ms(self):
+        return lib().tjamd_last_site_depths_ms(self._h)
 
     def uses_log(self):
         lib().tjamd_counter_uses_log.restype = C.c_int

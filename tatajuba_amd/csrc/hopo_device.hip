@@ -42,6 +42,7 @@
 #include "../../include/tatajuba_features.h"
 #include "../../include/tatajuba_effects.h"
 #include "../../include/tatajuba_sites.h"
+#include "../../include/tatajuba_depths.h"
 #include "../../include/tatajuba_locate.h"
 
 typedef unsigned long long u64;
@@ -3872,7 +3873,7 @@ struct StageTimer
 };
 // the intervals of a counter: the last scan call (its partition kernels between the pieces included: tjamd_last_scan_ms takes
 // them out), finalise, the kernels of tjamd_merge_samples, tjamd_tract_stats, tjamd_union_tracts, tjamd_union_tract_stats
-enum { T_SCAN, T_FIN, T_MERGE, T_TRACT, T_UNION, T_UNION_STATS, T_REF, T_LOCATE, T_LOCATED_TRACTS, T_VARIANTS, T_ANNOTATION, T_TRACT_FEATURES, T_SEED_ORDER, T_LOCATE_GAPPED, T_CODING, T_VARIANT_EFFECTS, T_MERGE_VARIANTS, TJ_N_TIMERS };   // (T_REF to T_LOCATED_TRACTS: N7, T_VARIANTS: N8, the next two: N9; then two of N10; two of N11; the last: N12, end of the file)
+enum { T_SCAN, T_FIN, T_MERGE, T_TRACT, T_UNION, T_UNION_STATS, T_REF, T_LOCATE, T_LOCATED_TRACTS, T_VARIANTS, T_ANNOTATION, T_TRACT_FEATURES, T_SEED_ORDER, T_LOCATE_GAPPED, T_CODING, T_VARIANT_EFFECTS, T_MERGE_VARIANTS, T_SITE_DEPTHS, TJ_N_TIMERS };   // (T_REF to T_LOCATED_TRACTS: N7, T_VARIANTS: N8, the next two: N9; then two of N10; two of N11; then N12 and N13, end of the file)
 
 struct tjamd_counter
 {
@@ -8435,3 +8436,241 @@ extern "C" long tjamd_merge_variants (tjamd_counter *c, int kmer_size, const tja
   return (long) h[1];
 }
 extern "C" double tjamd_last_merge_variants_ms (tjamd_counter *c) { return c ? c->timer[T_MERGE_VARIANTS].ms (c->device) : -1.0; }
+
+// ---- N13: per-site read depths and reference genotypes of the merged sites ------------------------------------------------
+// What tjamd_merge_variants cannot know from N8's records: whether a sample without a record equals the reference or has no
+// read on the tract.  The count matrix of the union tells; the rule as built is in include/tatajuba_depths.h.  Segment mapping
+// of tract_variants_kernel: S lanes per site, a lane per sample (looping beyond 64), a count row read as S consecutive words;
+// what the samples share -- the tract's rows, its index entry, k_eff, the site's allele range -- is found by the segment's first
+// lane and broadcast.  A row's class (REF, an allele of the site, OTHER) does not depend on the sample: the lanes of a segment
+// classify a chunk of S rows, one row each (key load, revcomp_k on the negative strand, XOR under kmask (k_eff), one __clzll,
+// the search among the site's alleles), and then every lane walks the chunk for its own sample and takes each row's class with
+// __shfl.  DP, the modal row with its class and length, and eight class accumulators (REF and seven alleles; selected by
+// unrolled compares, nothing indexed, nothing in scratch memory) stay in registers; a site with more than eight classes walks
+// its rows once more per further eight.  Two passes of one kernel: the first makes every check, leaves what a site's samples
+// share in scratch and writes nothing else, the second returns while the flag is up and reads neither tiling nor sites again.  DESIGN.md section 3.5, N13.
+
+struct SiteDepth { int n_ref, n_missing; long long depth; };
+static_assert (sizeof (SiteDepth) == 16 && sizeof (SiteDepth) == sizeof (tjamd_site_depth), "site depth layout");
+struct SdShared { int first, end, k_eff, a0, na, Lr, neg, ok; u64 fr; };   // what the samples of a site share, from the first pass to the second
+
+#define SD_GROUP 8                      // class accumulators of one walk
+// err bits: 1 tiling, 2 site.tract, 4 the site against its tract's location and entry, 8 the allele chain, 16 n_alleles < 1,
+// 32 allele.site, 64 allele.n_flank, 128 a modal row that no allele holds, 256 n_called (tjamd_site_depths names them)
+
+__device__ __forceinline__ long long sd_shfl_xor64 (long long x, int o, int S)
+{
+  const u32 lo = __shfl_xor ((u32) x, o, S), hi = __shfl_xor ((u32) ((u64) x >> 32), o, S);
+  return (long long) (((u64) hi << 32) | lo);
+}
+__device__ __forceinline__ long long sd_shfl64 (long long x, int from, int S)
+{
+  const u32 lo = __shfl ((u32) x, from, S), hi = __shfl ((u32) ((u64) x >> 32), from, S);
+  return (long long) (((u64) hi << 32) | lo);
+}
+__device__ __forceinline__ int sd_saturated (long long x) { return x > 0x7fffffffll ? 0x7fffffff : (int) x; }
+
+template <bool WRITE>
+__global__ __launch_bounds__ (256)
+void site_depths_kernel (const u64 *__restrict__ keys, const int *__restrict__ counts, long n_union, int ns, int S, int k,
+                         const UnionTract *__restrict__ tracts, long n_tracts, const Location *__restrict__ tloc,
+                         const RefEntry *__restrict__ entries, long n_ent, const Site *__restrict__ sites, long n_sites,
+                         const Allele *__restrict__ alleles, long n_alleles, int16_t *__restrict__ gt, int *__restrict__ dp, int *__restrict__ ad,
+                         SiteDepth *__restrict__ summary, SdShared *__restrict__ shared, int *__restrict__ err)
+{
+  const long gthread = blockIdx.x * (long) blockDim.x + threadIdx.x, n_threads = (long) gridDim.x * blockDim.x;
+  if (WRITE) { if (*(volatile int *) err != 0) return; }   // (the first pass is complete: every thread reads the same word)
+  else
+    for (long t = gthread; t < n_tracts; t += n_threads) {
+      const long first = tracts[t].first, rows = tracts[t].n_rows;
+      const long want = t ? (long) tracts[t - 1].first + tracts[t - 1].n_rows : 0l;
+      if (first != want || rows < 1 || first + rows > n_union || (t == n_tracts - 1 && first + rows != n_union)) atomicOr (err, 1);
+    }
+  const int lane = threadIdx.x & (S - 1);
+  const int log_S = __ffs (S) - 1;                       // (S is a power of two)
+  const long segs_per_grid = n_threads >> log_S;
+  for (long i = gthread >> log_S; i < n_sites; i += segs_per_grid) {   // (uniform across a segment)
+    int first = 0, end = 0, ent = -1, a0 = 0;           // (rows, entries and alleles are fewer than 2^31: the entry checks it)
+    int k_eff = 0, na = 0, n_called = 0, Lr = 0, neg = 0;
+    u64 fr = 0;                                         // the entry's length, strand and forward right flank
+    if (WRITE) {                                        // (one address per segment)
+      const SdShared p = shared[i];
+      first = p.first; end = p.end; k_eff = p.k_eff; a0 = p.a0; na = p.na; Lr = p.Lr; neg = p.neg; fr = p.fr; ent = p.ok - 1;
+    }
+    else if (lane == 0) {
+      const Site site = sites[i];
+      const long t = site.tract;
+      int bad = 0;
+      n_called = site.n_called;
+      const long a_want = i ? (long) sites[i - 1].first_allele + (long) sites[i - 1].n_alleles : 0l;
+      a0 = site.first_allele; na = site.n_alleles;
+      if (na < 1) bad |= 16;
+      if ((long) a0 != a_want || (i == n_sites - 1 && (long) a0 + (long) na != n_alleles)) bad |= 8;
+      if (a0 < 0 || na < 1 || (long) a0 + (long) na > n_alleles) { if (na >= 1) bad |= 8; a0 = 0; na = 0; }   // (nothing is read outside the alleles)
+      if (t < 0 || t >= n_tracts) bad |= 2;
+      else {
+        const UnionTract u = tracts[t];
+        const Location l = tloc[t];
+        if (u.first < 0 || u.n_rows < 1 || (long) u.first + (long) u.n_rows > n_union) first = end = 0;   // (a broken tiling: flagged above)
+        else { first = u.first; end = u.first + u.n_rows; }
+        if (first < end && l.flat >= 0 && (ent = (int) ref_entry_at (entries, n_ent, l.flat)) >= 0) {
+          k_eff = k;
+          if (t + 1 < n_tracts) {                       // stop at the next tract of the contig, as N8 does
+            const Location nx = tloc[t + 1];
+            const long overlap = (long) l.pos + (long) entries[ent].length + (long) k - (long) nx.pos;
+            if (nx.flat >= 0 && nx.contig == l.contig && overlap > 0) k_eff = (int) max (0l, (long) k - overlap);
+          }
+          if (site.flat != l.flat || site.contig != l.contig || site.ref_length != entries[ent].length) { bad |= 4; ent = -1; }
+        }
+        if (first < end && ent < 0) bad |= 4;
+      }
+      if (bad) { ent = -1; atomicOr (err, bad); }
+      if (ent >= 0) { const RefEntry e = entries[ent]; Lr = e.length; neg = e.neg_strand; fr = e.neg_strand ? revcomp_k (e.ctx0, k) : e.ctx1; }
+      const SdShared p = {first, end, k_eff, a0, na, Lr, neg, ent >= 0 ? 1 : 0, fr};
+      shared[i] = p;
+    }
+    if (!WRITE) {
+      first = __shfl (first, 0, S); end = __shfl (end, 0, S); ent = __shfl (ent, 0, S); a0 = __shfl (a0, 0, S);
+      k_eff = __shfl (k_eff, 0, S); na = __shfl (na, 0, S); n_called = __shfl (n_called, 0, S); Lr = __shfl (Lr, 0, S); neg = __shfl (neg, 0, S);
+      fr = (u64) sd_shfl64 ((long long) fr, 0, S);
+      int bad = 0;                                      // the site's alleles, a lane each
+      for (int a = lane; a < na; a += S) {
+        if (alleles[a0 + a].site != (int) i) bad |= 32;
+        if (alleles[a0 + a].n_flank < 0 || alleles[a0 + a].n_flank > k) bad |= 64;
+      }
+      if (bad) atomicOr (err, bad);
+    }
+    if (ent < 0) continue;                              // (refused; uniform across the segment)
+    const int n_groups = WRITE && ad ? (na + 1 + SD_GROUP - 1) / SD_GROUP : 1;
+    int n_ref = 0, n_missing = 0, n_alt = 0;
+    long long depth = 0;
+    for (int s0 = 0; s0 < ns; s0 += S) {                // (every lane of the segment stays in the loop: the shuffles need them)
+      const int s = s0 + lane;
+      const bool mine = s < ns;
+      for (int grp = 0; grp < n_groups; grp++) {
+        const int c0 = grp * SD_GROUP;                  // the classes of this walk: [c0, c0 + SD_GROUP)
+        long long sum = 0, acc0 = 0, acc1 = 0, acc2 = 0, acc3 = 0, acc4 = 0, acc5 = 0, acc6 = 0, acc7 = 0;
+        int best = 0, m_cls = -1, m_la = 0;
+        for (int base = first, n_here; base < end; base += n_here) {      // a chunk of S rows (no sum beyond `end`: it may be near 2^31)
+          const long r_own = (long) base + lane;
+          n_here = min (S, end - base);
+          int cls = -1, la = 0;                         // this lane's row of the chunk
+          if (r_own < end) {
+            la = meta_len (keys[3 * r_own + 2]);
+            if (la == Lr && la >= 1) cls = 0;
+            else if (la >= 1) {
+              const u64 fa = neg ? revcomp_k (keys[3 * r_own], k) : keys[3 * r_own + 1];
+              const u64 x = (fr ^ fa) & kmask (k_eff);
+              const int nf = x ? (63 - __clzll ((long long) x)) / 2 + 1 : 0;
+              #pragma unroll 1
+              for (int a = 0; a < na; a++) {
+                const Allele al = alleles[a0 + a];
+                if (al.alt_length == la && al.n_flank == nf && ((al.alt_flank ^ fa) & kmask (nf)) == 0ull) { cls = a + 1; break; }
+              }
+            }
+          }
+          #pragma unroll 1
+          for (int r = 0; r < n_here; r++) {
+            const int c = __shfl (cls, r, S), l = __shfl (la, r, S);
+            const int x = mine ? max (counts[(long) (base + r) * ns + s], 0) : 0;   // (counts <= 0 contribute nothing)
+            const int g = c - c0;
+            const bool better = x > best;               // (the first on a tie)
+            sum += x;
+            best = better ? x : best; m_cls = better ? c : m_cls; m_la = better ? l : m_la;
+            acc0 += g == 0 ? x : 0; acc1 += g == 1 ? x : 0; acc2 += g == 2 ? x : 0; acc3 += g == 3 ? x : 0;
+            acc4 += g == 4 ? x : 0; acc5 += g == 5 ? x : 0; acc6 += g == 6 ? x : 0; acc7 += g == 7 ? x : 0;
+          }
+        }
+        if (grp == 0 && mine) {
+          int g = -1;
+          if (best > 0 && m_la >= 1) {
+            if (m_cls >= 0) g = m_cls;
+            else if (!WRITE) atomicOr (err, 128);       // N8 has a record here that the alleles do not hold
+          }
+          n_ref += g == 0; n_missing += g < 0; n_alt += g > 0; depth += sum;
+          if (WRITE) {
+            if (gt) gt[i * ns + s] = (int16_t) g;
+            if (dp) dp[i * ns + s] = sd_saturated (sum);
+          }
+        }
+        if (WRITE && ad && mine) {
+          int *row = ad + ((long) a0 + i + c0) * ns + s;
+          const int left = na + 1 - c0;                 // the classes from c0 on
+          if (left > 0) row[0] = sd_saturated (acc0);
+          if (left > 1) row[(long) ns] = sd_saturated (acc1);
+          if (left > 2) row[2l * ns] = sd_saturated (acc2);
+          if (left > 3) row[3l * ns] = sd_saturated (acc3);
+          if (left > 4) row[4l * ns] = sd_saturated (acc4);
+          if (left > 5) row[5l * ns] = sd_saturated (acc5);
+          if (left > 6) row[6l * ns] = sd_saturated (acc6);
+          if (left > 7) row[7l * ns] = sd_saturated (acc7);
+        }
+      }
+    }
+    for (int o = S >> 1; o; o >>= 1) {
+      n_ref += __shfl_xor (n_ref, o, S); n_missing += __shfl_xor (n_missing, o, S); n_alt += __shfl_xor (n_alt, o, S);
+      depth += sd_shfl_xor64 (depth, o, S);
+    }
+    if (lane == 0) {
+      if (!WRITE) { if (n_alt != n_called) atomicOr (err, 256); }
+      else if (summary) { const SiteDepth o = {n_ref, n_missing, depth}; summary[i] = o; }
+    }
+  }
+}
+
+extern "C" long tjamd_site_depths (tjamd_counter *c, const tjamd_reference *ref, const void *d_keys, const void *d_counts, long n_union, int n_samples,
+                                   const tjamd_union_tract *d_tracts, long n_tracts, const tjamd_location *d_tract_loc,
+                                   const tjamd_site *d_sites, long n_sites, const tjamd_allele *d_alleles, long n_alleles,
+                                   int16_t *d_genotype, int *d_depth, int *d_allele_depth, tjamd_site_depth *d_summary)
+{
+  static const char *fn = "tjamd_site_depths";
+  if (!c || !ref) return -set_err (TJAMD_ERR_ARG, "%s: null counter or reference", fn);
+  int rc = union_args (fn, d_keys, d_counts, n_union, n_samples);
+  if (rc) return -rc;
+  if (n_tracts < (n_union > 0 ? 1 : 0) || n_tracts > n_union) return -set_err (TJAMD_ERR_ARG, "%s: n_tracts %ld for a union of %ld rows", fn, n_tracts, n_union);
+  if (n_tracts > 0 && (!d_tracts || !d_tract_loc)) return -set_err (TJAMD_ERR_ARG, "%s: null tract or tract location buffer", fn);
+  if (n_sites < 0 || n_alleles < 0) return -set_err (TJAMD_ERR_ARG, "%s: n_sites %ld, n_alleles %ld: a count below 0", fn, n_sites, n_alleles);
+  if ((n_sites > 0 && !d_sites) || (n_alleles > 0 && !d_alleles)) return -set_err (TJAMD_ERR_ARG, "%s: null site or allele buffer", fn);
+  if (n_sites > n_tracts) return -set_err (TJAMD_ERR_ARG, "%s: %ld sites for %ld tracts", fn, n_sites, n_tracts);
+  if (n_alleles < n_sites) return -set_err (TJAMD_ERR_ARG, "%s: %ld alleles for %ld sites (a site has at least one)", fn, n_alleles, n_sites);
+  if (n_alleles >= (1l << 31) || (n_sites + n_alleles) * (long) n_samples >= (1l << 31))
+    return -set_err (TJAMD_ERR_ARG, "%s: (%ld sites + %ld alleles) x %d samples: 2^31 cells or more", fn, n_sites, n_alleles, n_samples);
+  if (tjamd_device_count () <= 0) return -set_err (TJAMD_ERR_NO_DEVICE, "%s: TJAMD_ERR_NO_DEVICE: no HIP device visible (the depths are counted on the device; no CPU fallback)", fn);
+  if (ref->n_entries >= (1l << 31)) return -set_err (TJAMD_ERR_CAPACITY, "%s: %ld index entries", fn, ref->n_entries);
+  Stage st (c, T_SITE_DEPTHS);                          // (a refused call leaves no timing behind)
+  if (ref->k != c->k) return -set_err (TJAMD_ERR_ARG, "%s: the reference was built with k = %d, the counter has k = %d", fn, ref->k, c->k);
+  if (ref->device != c->device) return -set_err (TJAMD_ERR_ARG, "%s: the reference lives on device %d, the counter on device %d", fn, ref->device, c->device);
+  if (hipSetDevice (c->device) != hipSuccess) return -set_err (TJAMD_ERR_HIP, "hipSetDevice failed");
+  if (n_sites == 0) return 0;
+  ScratchCut cut;
+  int *err; SdShared *shared;
+  cut.take (err, 64); cut.take (shared, (size_t) n_sites);
+  rc = cut.commit (c);
+  if (rc) return -rc;
+  if (hipMemsetAsync (err, 0, 256, c->stream) != hipSuccess) return -set_err (TJAMD_ERR_HIP, "%s: memset failed", fn);
+  st.begin ();
+  const int S = tract_segment (n_samples);
+  auto launch = [&] (auto kernel) {
+    hipLaunchKernelGGL (kernel, dim3 (tract_grid (n_sites, S)), dim3 (256), 0, c->stream, (const u64 *) d_keys, (const int *) d_counts, n_union, n_samples, S, c->k,
+                        (const UnionTract *) d_tracts, n_tracts, (const Location *) d_tract_loc, (const RefEntry *) ref->entries, ref->n_entries,
+                        (const Site *) d_sites, n_sites, (const Allele *) d_alleles, n_alleles, d_genotype, d_depth, d_allele_depth, (SiteDepth *) d_summary, shared, err);
+  };
+  launch (site_depths_kernel<false>);                   // every check; nothing of the caller's is written
+  launch (site_depths_kernel<true>);                    // returns while the flag is up
+  st.end ();
+  u32 h_err = 0;
+  rc = read_back (c, fn, err, &h_err, 1);
+  if (rc) return -rc;
+  if (h_err & 1u) return -set_err (TJAMD_ERR_ARG, "%s: the tracts do not tile the union (first 0, each starting where the one before ends, the last ending at n_union)", fn);
+  if (h_err & 2u) return -set_err (TJAMD_ERR_ARG, "%s: a site's tract is outside [0, %ld)", fn, n_tracts);
+  if (h_err & 16u) return -set_err (TJAMD_ERR_ARG, "%s: a site has n_alleles < 1", fn);
+  if (h_err & 8u) return -set_err (TJAMD_ERR_ARG, "%s: first_allele and n_alleles of the sites do not chain from 0 to %ld", fn, n_alleles);
+  if (h_err & 4u) return -set_err (TJAMD_ERR_ARG, "%s: a site has no index entry, or its flat, contig or ref_length is not its tract's", fn);
+  if (h_err & 32u) return -set_err (TJAMD_ERR_ARG, "%s: an allele's site is not the site that holds it", fn);
+  if (h_err & 64u) return -set_err (TJAMD_ERR_ARG, "%s: an allele's n_flank is outside 0..%d", fn, c->k);
+  if (h_err & 128u) return -set_err (TJAMD_ERR_ARG, "%s: a sample's modal row is a variant that the site's alleles do not hold (sites of another union or list)", fn);
+  if (h_err & 256u) return -set_err (TJAMD_ERR_ARG, "%s: a site's n_called is not the number of samples with an allele (sites merged from another list or a subset)", fn);
+  st.done ();
+  return n_sites;
+}
+extern "C" double tjamd_last_site_depths_ms (tjamd_counter *c) { return c ? c->timer[T_SITE_DEPTHS].ms (c->device) : -1.0; }
