@@ -5610,6 +5610,20 @@ static int union_args (const char *fn, const void *d_keys, const void *d_counts,
   return TJAMD_OK;
 }
 
+static int tract_count_arg (const char *fn, long n_tracts, long n_union)
+{ // tracts that tile a union: one at least unless it is empty, one per row at most
+  return (n_tracts < (n_union > 0 ? 1 : 0) || n_tracts > n_union) ? set_err (TJAMD_ERR_ARG, "%s: n_tracts %ld for a union of %ld rows", fn, n_tracts, n_union) : TJAMD_OK;
+}
+static int tiled_union_args (const char *fn, const void *d_keys, const void *d_counts, long n_union, int n_samples, const void *d_tracts, long n_tracts, const void *d_tract_loc)
+{ // ... a union, the tracts that tile it and a location per tract (N8, N13)
+  int rc = union_args (fn, d_keys, d_counts, n_union, n_samples);
+  if (!rc) rc = tract_count_arg (fn, n_tracts, n_union);
+  if (!rc && n_tracts > 0 && (!d_tracts || !d_tract_loc)) rc = set_err (TJAMD_ERR_ARG, "%s: null tract or tract location buffer", fn);
+  return rc;
+}
+// the refusal after the device found the tiling broken (tjamd_union_tract_stats words its own, which its callers match on)
+static const char TILING_REFUSED[] = "%s: the tracts do not tile the union (first 0, each starting where the one before ends, the last ending at n_union)";
+
 static int tract_args (const char *fn, const void *d_keys, const void *d_counts, long n_union, int n_samples, const int *coverage)
 { // ... and, for the statistics, the samples' coverages
   const int rc = union_args (fn, d_keys, d_counts, n_union, n_samples);
@@ -5716,6 +5730,31 @@ struct UnionTract { int first, n_rows, n_context, mode, indel, lev_distance; lon
 static_assert (sizeof (UnionTract) == 32 && sizeof (UnionTract) == sizeof (tjamd_union_tract), "union tract layout");
 struct UnionSummary { int first, n_rows, n_present, variable, selected, lev_distance; double reldiff[TJAMD_N_TRACT_STATS]; };
 static_assert (sizeof (UnionSummary) == 64 && sizeof (UnionSummary) == sizeof (tjamd_union_tract_summary), "union summary layout");
+
+// The tracts a caller passes (statistics, located tracts, N8, N9, N13) must tile the union: the first at row 0, each starting
+// where the one before ends, the last ending at n_union.  tract_rows: a tract's rows [first, end), none where they do not lie
+// inside the union, which keeps a refused call from reading outside it; breaks_tiling: whether tract t does; check_tiling: the
+// whole grid, a thread per tract, err |= 1 where one does.
+__device__ __forceinline__ void tract_rows (const UnionTract &u, long n_union, long &first, long &end)
+{
+  first = u.first; end = first + (long) u.n_rows;
+  if (first < 0 || u.n_rows < 1 || end > n_union) first = end = 0;
+}
+__device__ __forceinline__ bool breaks_tiling (const UnionTract *__restrict__ tracts, long n_tracts, long n_union, long t)
+{
+  long first, end;
+  tract_rows (tracts[t], n_union, first, end);
+  const long want = t ? (long) tracts[t - 1].first + (long) tracts[t - 1].n_rows : 0l;
+  return first == end || first != want || (t == n_tracts - 1 && end != n_union);
+}
+__device__ __forceinline__ void check_tiling (const UnionTract *__restrict__ tracts, long n_tracts, long n_union, int *__restrict__ err)
+{
+  for (long t = blockIdx.x * (long) blockDim.x + threadIdx.x; t < n_tracts; t += (long) gridDim.x * blockDim.x)
+    if (breaks_tiling (tracts, n_tracts, n_union, t)) atomicOr (err, 1);
+}
+// a 64-bit word from lane `from` / from lane ^ o of a segment of `width` lanes
+__device__ __forceinline__ u64 shfl64 (u64 x, int from, int width = 64) { const u32 lo = __shfl ((u32) x, from, width), hi = __shfl ((u32) (x >> 32), from, width); return ((u64) hi << 32) | lo; }
+__device__ __forceinline__ u64 shfl_xor64 (u64 x, int o, int width = 64) { const u32 lo = __shfl_xor ((u32) x, o, width), hi = __shfl_xor ((u32) (x >> 32), o, width); return ((u64) hi << 32) | lo; }
 
 // exact row totals: one segment of S lanes per row, a lane summing samples lane, lane + S, ... (S contiguous words per step)
 __global__ __launch_bounds__ (256)
@@ -5901,8 +5940,7 @@ void union_tract_stats_kernel (const u64 *__restrict__ keys, const int *__restri
     if (FULL && !fallback[t]) continue;
     const UnionTract u = tracts[t];
     const long first = u.first, end = first + (long) u.n_rows;
-    const long prev_end = t ? (long) tracts[t - 1].first + (long) tracts[t - 1].n_rows : 0l;
-    if (first < 0 || u.n_rows < 1 || first != prev_end || end > n_union || (t == n_tracts - 1 && end != n_union)) {
+    if (breaks_tiling (tracts, n_tracts, n_union, t)) {
       if (lane == 0) { atomicOr (err, 1); varflag[t] = 0u; selflag[t] = 0u; if (!FULL) fallback[t] = 0u; }
       continue;
     }
@@ -5966,17 +6004,6 @@ void union_tract_sample_stats_kernel (const u64 *__restrict__ keys, const int *_
   }
 }
 
-static int union_stats_args (const char *fn, const void *d_keys, const void *d_counts, long n_union, int n_samples, const int *coverage,
-                             const void *d_tracts, long n_tracts, const void *d_out)
-{ // the checks both stats entries share, before any device call
-  int rc = tract_args (fn, d_keys, d_counts, n_union, n_samples, coverage);
-  if (rc) return rc;
-  if (n_tracts < (n_union > 0 ? 1 : 0) || n_tracts > n_union)
-    return set_err (TJAMD_ERR_ARG, "%s: n_tracts %ld for a union of %ld rows", fn, n_tracts, n_union);
-  if (n_tracts > 0 && (!d_tracts || !d_out)) return set_err (TJAMD_ERR_ARG, "%s: null tract or summary buffer", fn);
-  return TJAMD_OK;
-}
-
 static int ensure_union_fallback (tjamd_counter *c, long n, long long *&g_cnt, int *&g_len)
 { // fallback flags, and the global bars of the FULL kernels: g_cnt, the counts of all their threads, then g_len, the lengths
   int rc = ensure (c->ut_fb, (size_t) std::max (n, 1l) * 4, c->stream);
@@ -5992,8 +6019,10 @@ extern "C" long tjamd_union_tract_stats (tjamd_counter *c, const void *d_keys, c
                                          tjamd_union_tract_summary *d_summary, int *d_var, long *n_var, int *d_sel, long *n_sel)
 {
   static const char *fn = "tjamd_union_tract_stats";
-  int rc = union_stats_args (fn, d_keys, d_counts, n_union, n_samples, coverage, d_tracts, n_tracts, d_summary);
+  int rc = tract_args (fn, d_keys, d_counts, n_union, n_samples, coverage);   // (the coverage before the tracts: not tiled_union_args)
+  if (!rc) rc = tract_count_arg (fn, n_tracts, n_union);
   if (rc) return -rc;
+  if (n_tracts > 0 && (!d_tracts || !d_summary)) return -set_err (TJAMD_ERR_ARG, "%s: null tract or summary buffer", fn);
   if (!c) return -set_err (TJAMD_ERR_ARG, "%s: null counter", fn);
   if (n_var) *n_var = 0;
   if (n_sel) *n_sel = 0;
@@ -6546,6 +6575,13 @@ struct tjamd_reference
   bool has_seeds = false;
 };
 
+static int reference_of_counter (const char *fn, const tjamd_reference *ref, const tjamd_counter *c)
+{ // the reference belongs to the counter: the same k, the same device (neither is null)
+  if (ref->k != c->k) return set_err (TJAMD_ERR_ARG, "%s: the reference was built with k = %d, the counter has k = %d", fn, ref->k, c->k);
+  if (ref->device != c->device) return set_err (TJAMD_ERR_ARG, "%s: the reference lives on device %d, the counter on device %d", fn, ref->device, c->device);
+  return TJAMD_OK;
+}
+
 // byte classes of the index: 0-3 the base of an ACGTU byte (either case), 4 the contig delimiter, 5 anything else
 __device__ __forceinline__ u32 ref_class (u32 b) { return byte_is_acgtu (b) ? byte_code (b) : (b == '\n' ? 4u : 5u); }
 
@@ -6797,8 +6833,7 @@ extern "C" long tjamd_locate (tjamd_counter *c, const tjamd_reference *ref, cons
 {
   static const char *fn = "tjamd_locate";
   if (!c || !ref) return -set_err (TJAMD_ERR_ARG, "%s: null counter or reference", fn);
-  if (ref->k != c->k) return -set_err (TJAMD_ERR_ARG, "%s: the reference was built with k = %d, the counter has k = %d", fn, ref->k, c->k);
-  if (ref->device != c->device) return -set_err (TJAMD_ERR_ARG, "%s: the reference lives on device %d, the counter on device %d", fn, ref->device, c->device);
+  if (const int bad = reference_of_counter (fn, ref, c)) return -bad;
   if (max_mismatches < 0 || max_mismatches > c->k) return -set_err (TJAMD_ERR_ARG, "%s: max_mismatches %d outside 0..%d", fn, max_mismatches, c->k);
   if (n < 0) return -set_err (TJAMD_ERR_ARG, "%s: n %ld < 0", fn, n);
   if (n >= (1l << 31)) return -set_err (TJAMD_ERR_CAPACITY, "%s: %ld rows", fn, n);
@@ -6914,8 +6949,7 @@ extern "C" long tjamd_reference_add_seeds (tjamd_counter *c, tjamd_reference *re
 {
   static const char *fn = "tjamd_reference_add_seeds";
   if (!c || !ref) return -set_err (TJAMD_ERR_ARG, "%s: null counter or reference", fn);
-  if (ref->k != c->k) return -set_err (TJAMD_ERR_ARG, "%s: the reference was built with k = %d, the counter has k = %d", fn, ref->k, c->k);
-  if (ref->device != c->device) return -set_err (TJAMD_ERR_ARG, "%s: the reference lives on device %d, the counter on device %d", fn, ref->device, c->device);
+  if (const int bad = reference_of_counter (fn, ref, c)) return -bad;
   if (ref->has_seeds) return ref->n_entries;
   if (hipSetDevice (c->device) != hipSuccess) return -set_err (TJAMD_ERR_HIP, "hipSetDevice failed");
   Stage st (c, T_SEED_ORDER);
@@ -7027,8 +7061,7 @@ extern "C" long tjamd_locate_gapped (tjamd_counter *c, const tjamd_reference *re
   if (n < 0) return -set_err (TJAMD_ERR_ARG, "%s: n %ld < 0", fn, n);
   if (n >= (1l << 31)) return -set_err (TJAMD_ERR_CAPACITY, "%s: %ld rows", fn, n);
   if (n > 0 && (!d_keys || !d_loc)) return -set_err (TJAMD_ERR_ARG, "%s: null key or location buffer", fn);
-  if (ref->k != c->k) return -set_err (TJAMD_ERR_ARG, "%s: the reference was built with k = %d, the counter has k = %d", fn, ref->k, c->k);
-  if (ref->device != c->device) return -set_err (TJAMD_ERR_ARG, "%s: the reference lives on device %d, the counter on device %d", fn, ref->device, c->device);
+  if (const int bad = reference_of_counter (fn, ref, c)) return -bad;
   if (!ref->has_seeds) return -set_err (TJAMD_ERR_ARG, "%s: the reference has no seed order (tjamd_reference_add_seeds comes first)", fn);
   if (max_edits > c->k) return -set_err (TJAMD_ERR_ARG, "%s: max_edits %d outside 0..%d", fn, max_edits, c->k);
   if (hipSetDevice (c->device) != hipSuccess) return -set_err (TJAMD_ERR_HIP, "hipSetDevice failed");
@@ -7075,15 +7108,14 @@ __global__ void lt_context_tract_kernel (long n, const long long *__restrict__ t
 #define LT_FLAT_MAX   (1ll << 45)       // (flat + 1) << 2 | base stays below 2^48 for flat below 2^45; larger ones are refused
 
 // a tract's sort key: 0 if it has no located row, else (flat + 1) << 2 | base of its located row with the highest total
-// (the first of equal totals).  Also checks that the tracts tile the union (err), as tjamd_union_tract_stats does.
+// (the first of equal totals).  Also checks that the tracts tile the union (err = 1 where breaks_tiling says so).
 __global__ void lt_tract_key_kernel (const UnionTract *__restrict__ tracts, long nt, long n, const u64 *__restrict__ keys, const long long *__restrict__ total,
                                      const Location *__restrict__ loc, u64 *__restrict__ key, u32 *__restrict__ val, int *__restrict__ err)
 {
   for (long t = blockIdx.x * (long) blockDim.x + threadIdx.x; t < nt; t += (long) gridDim.x * blockDim.x) {
     const long first = tracts[t].first, rows = tracts[t].n_rows;
-    const long want = t ? (long) tracts[t - 1].first + tracts[t - 1].n_rows : 0;
     u64 kk = 0;
-    if (first != want || rows < 1 || first + rows > n || (t == nt - 1 && first + rows != n)) *err = 1;
+    if (breaks_tiling (tracts, nt, n, t)) *err = 1;
     else {
       long best = -1; long long best_total = 0;
       for (long r = first; r < first + rows; r++)
@@ -7253,7 +7285,7 @@ extern "C" long tjamd_located_tracts (tjamd_counter *c, const void *d_keys, cons
   int rc = union_args (fn, d_keys, d_counts, n_union, n_samples);
   if (rc) return -rc;
   if (n_union > 0 && (!d_loc || !d_perm || !d_out_tracts)) return -set_err (TJAMD_ERR_ARG, "%s: null location, permutation or tract buffer", fn);
-  if (d_tracts && (n_tracts < (n_union > 0 ? 1 : 0) || n_tracts > n_union)) return -set_err (TJAMD_ERR_ARG, "%s: n_tracts %ld for a union of %ld rows", fn, n_tracts, n_union);
+  if (d_tracts && (rc = tract_count_arg (fn, n_tracts, n_union))) return -rc;   // (no tracts: the context-keyed ones, n_tracts unread)
   if (capacity < (n_union > 0 ? 1 : 0)) return -set_err (TJAMD_ERR_CAPACITY, "%s: capacity %ld for a union of %ld rows", fn, capacity, n_union);
   if (!c) return -set_err (TJAMD_ERR_ARG, "%s: null counter", fn);
   if (hipSetDevice (c->device) != hipSuccess) return -set_err (TJAMD_ERR_HIP, "hipSetDevice failed");
@@ -7308,7 +7340,7 @@ extern "C" long tjamd_located_tracts (tjamd_counter *c, const void *d_keys, cons
   rc = read_back (c, fn, tot, h, 2);
   if (rc) return -rc;
   if (h[1] == 2) return -set_err (TJAMD_ERR_ARG, "%s: a location with flat >= 2^45", fn);
-  if (h[1]) return -set_err (TJAMD_ERR_ARG, "%s: the tracts do not tile the union (first 0, each starting where the one before ends, the last ending at n_union)", fn);
+  if (h[1]) return -set_err (TJAMD_ERR_ARG, TILING_REFUSED, fn);
   if ((long) h[0] > capacity) return -set_err (TJAMD_ERR_CAPACITY, "%s: %u tracts, caller capacity %ld", fn, h[0], capacity);
   st.done ();
   return (long) h[0];
@@ -7319,10 +7351,9 @@ extern "C" double tjamd_last_located_tracts_ms (tjamd_counter *c) { return c ? c
 // The VCF step of the reference (update_vcf_file_from_context_histogram, find_ref_alt_ht_variants_from_strings,
 // get_next_ht_location_from_same_contig, src/analyse_variable_tracts.c:147-233) on the permuted union of
 // tjamd_located_tracts; the rule is in include/tatajuba_variants.h above tjamd_tract_variants.  The index entry at a tract's
-// location holds the genome's flanks in the packing of the union rows, so the reference's comparison of two strings is an
-// XOR of two flank words and a leading-zero count.  Segment mapping of union_tract_stats_kernel: S lanes per listed tract, a
-// lane per sample (looping beyond 64); what the samples of a tract share -- its rows, its index entry (a binary search on
-// flat) and the bases the next tract leaves of the right flank -- is found by the segment's first lane and broadcast.
+// location holds the genome's flanks in the packing of the union rows, so the reference's comparison of two strings is word
+// arithmetic (row_right_flank).  Segment mapping of union_tract_stats_kernel: S lanes per listed tract, a lane per sample (looping
+// beyond 64); what they share -- tract_rows, located_tract -- is found by the segment's first lane and broadcast.
 // Two passes of one kernel around an exclusive scan in sample-major order: flags, then records at their scanned places, so
 // a record's place never depends on the order of atomics.  DESIGN.md section 3.5, N8.
 
@@ -7338,6 +7369,33 @@ __device__ __forceinline__ long ref_entry_at (const RefEntry *__restrict__ entri
     if (entries[mid].flat < flat) lo = mid + 1; else hi = mid;
   }
   return (lo < n_ent && entries[lo].flat == flat) ? lo : -1l;
+}
+
+// A located tract (N8, N13; run by a segment's first lane): the entry at tract t's location, -1 where it has no location or no
+// entry sits there, and k_eff, the bases of its right flank that the next tract of the same contig leaves (k where none is near)
+__device__ __forceinline__ long located_tract (const Location *__restrict__ tloc, long n_tracts, long t, const RefEntry *__restrict__ entries, long n_ent, int k, int &k_eff)
+{
+  const Location l = tloc[t];
+  const long ent = l.flat >= 0 ? ref_entry_at (entries, n_ent, l.flat) : -1l;
+  k_eff = ent < 0 ? 0 : k;
+  if (ent >= 0 && t + 1 < n_tracts) {                   // stop at the next tract of the contig, whether a caller lists it or not
+    const Location nx = tloc[t + 1];
+    const long overlap = (long) l.pos + (long) entries[ent].length + (long) k - (long) nx.pos;
+    if (nx.flat >= 0 && nx.contig == l.contig && overlap > 0) k_eff = (int) max (0l, (long) k - overlap);
+  }
+  return ent;
+}
+
+// The allele rule, which the VCF output rests on.  entry_right_flank: the forward right flank of an entry.  row_right_flank: that
+// of a union row on the entry's strand, and n_flank: how many of its first k_eff bases hold every difference from fr, the outermost
+// one and everything inside it (kmask: all ones at 32 bases, nothing at 0 -- no shift by 64)
+__device__ __forceinline__ u64 entry_right_flank (const RefEntry &e, int k) { return e.neg_strand ? revcomp_k (e.ctx0, k) : e.ctx1; }
+__device__ __forceinline__ u64 row_right_flank (const u64 *__restrict__ keys, long row, int neg, int k, int k_eff, u64 fr, int &n_flank)
+{
+  const u64 fa = neg ? revcomp_k (keys[3 * row], k) : keys[3 * row + 1];
+  const u64 x = (fr ^ fa) & kmask (k_eff);
+  n_flank = x ? (63 - __clzll ((long long) x)) / 2 + 1 : 0;
+  return fa;
 }
 
 // a sample's modal row among rows [first, end) of the union: the highest count above 0, the first on a tie; -1 if it has none
@@ -7364,12 +7422,7 @@ void tract_variants_kernel (const u64 *__restrict__ keys, const int *__restrict_
                             u32 *__restrict__ flag, const u32 *__restrict__ excl, Variant *__restrict__ out, long capacity, int *__restrict__ err)
 {
   const long gthread = blockIdx.x * (long) blockDim.x + threadIdx.x, n_threads = (long) gridDim.x * blockDim.x;
-  if (!WRITE)
-    for (long t = gthread; t < n_tracts; t += n_threads) {
-      const long first = tracts[t].first, rows = tracts[t].n_rows;
-      const long want = t ? (long) tracts[t - 1].first + tracts[t - 1].n_rows : 0l;
-      if (first != want || rows < 1 || first + rows > n_union || (t == n_tracts - 1 && first + rows != n_union)) atomicOr (err, 1);
-    }
+  if (!WRITE) check_tiling (tracts, n_tracts, n_union, err);
   const int lane = threadIdx.x & (S - 1);
   const long segs_per_grid = n_threads / S;
   for (long i = gthread / S; i < n_list; i += segs_per_grid) {   // (uniform across a segment)
@@ -7378,20 +7431,8 @@ void tract_variants_kernel (const u64 *__restrict__ keys, const int *__restrict_
     int k_eff = 0;
     if (lane == 0) {
       if (t < 0 || t >= n_tracts) { if (!WRITE) atomicOr (err, 2); }
-      else {
-        const UnionTract u = tracts[t];
-        const Location l = tloc[t];
-        first = u.first; end = first + (long) u.n_rows;
-        if (first < 0 || u.n_rows < 1 || end > n_union) first = end = 0;   // (a broken tiling: flagged above)
-        else if (l.flat >= 0 && (ent = ref_entry_at (entries, n_ent, l.flat)) >= 0) {
-          k_eff = k;
-          if (t + 1 < n_tracts) {                       // stop at the next tract of the contig, list or no list
-            const Location nx = tloc[t + 1];
-            const long overlap = (long) l.pos + (long) entries[ent].length + (long) k - (long) nx.pos;
-            if (nx.flat >= 0 && nx.contig == l.contig && overlap > 0) k_eff = (int) max (0l, (long) k - overlap);
-          }
-        }
-      }
+      else tract_rows (tracts[t], n_union, first, end);   // (none of a broken tiling, flagged above: then no entry either)
+      if (first < end) ent = located_tract (tloc, n_tracts, t, entries, n_ent, k, k_eff);
     }
     first = __shfl (first, 0, S); end = __shfl (end, 0, S); ent = __shfl (ent, 0, S); k_eff = __shfl (k_eff, 0, S);
     for (int s = lane; s < ns; s += S) {
@@ -7405,10 +7446,8 @@ void tract_variants_kernel (const u64 *__restrict__ keys, const int *__restrict_
           call = La >= 1 && La != Lr;
           if (WRITE && call) {
             const Location l = tloc[t];
-            const u64 fr = e.neg_strand ? revcomp_k (e.ctx0, k) : e.ctx1;
-            const u64 fa = e.neg_strand ? revcomp_k (keys[3 * row], k) : keys[3 * row + 1];
-            const u64 x = (fr ^ fa) & kmask (k_eff);    // (kmask: all ones at 32 bases, nothing at 0 -- no shift by 64)
-            const int nf = x ? (63 - __clzll ((long long) x)) / 2 + 1 : 0;   // the outermost difference and everything inside it
+            int nf;
+            const u64 fr = entry_right_flank (e, k), fa = row_right_flank (keys, row, e.neg_strand, k, k_eff, fr, nf);
             v.flat = l.flat; v.tract = (int) t; v.sample = s; v.contig = l.contig; v.pos = l.pos + min (La, Lr);
             v.row = (int) row; v.base = e.neg_strand ? 3 - e.base : e.base; v.ref_length = Lr; v.alt_length = La;
             v.n_flank = nf; v.pad = 0; v.ref_flank = fr & kmask (nf); v.alt_flank = fa & kmask (nf);
@@ -7433,10 +7472,8 @@ extern "C" long tjamd_tract_variants (tjamd_counter *c, const tjamd_reference *r
                                       const int *d_list, long n_list, tjamd_variant *d_out, long capacity, long *h_offsets)
 {
   static const char *fn = "tjamd_tract_variants";
-  int rc = union_args (fn, d_keys, d_counts, n_union, n_samples);
+  int rc = tiled_union_args (fn, d_keys, d_counts, n_union, n_samples, d_tracts, n_tracts, d_tract_loc);
   if (rc) return -rc;
-  if (n_tracts < (n_union > 0 ? 1 : 0) || n_tracts > n_union) return -set_err (TJAMD_ERR_ARG, "%s: n_tracts %ld for a union of %ld rows", fn, n_tracts, n_union);
-  if (n_tracts > 0 && (!d_tracts || !d_tract_loc)) return -set_err (TJAMD_ERR_ARG, "%s: null tract or tract location buffer", fn);
   if (!d_list) n_list = n_tracts;                       // every tract
   if (n_list < 0) return -set_err (TJAMD_ERR_ARG, "%s: n_list %ld < 0", fn, n_list);
   if (capacity < 0 || (capacity > 0 && !d_out)) return -set_err (TJAMD_ERR_ARG, "%s: capacity %ld with %s record buffer", fn, capacity, d_out ? "a" : "a null");
@@ -7445,8 +7482,7 @@ extern "C" long tjamd_tract_variants (tjamd_counter *c, const tjamd_reference *r
   const long n_flags = n_list * (long) n_samples;
   if (n_flags >= (1l << 31)) return -set_err (TJAMD_ERR_CAPACITY, "%s: %ld listed tracts x %d samples", fn, n_list, n_samples);
   if (tjamd_device_count () <= 0) return -set_err (TJAMD_ERR_NO_DEVICE, "%s: TJAMD_ERR_NO_DEVICE: no HIP device visible (the variants are called on the device; no CPU fallback)", fn);
-  if (ref->k != c->k) return -set_err (TJAMD_ERR_ARG, "%s: the reference was built with k = %d, the counter has k = %d", fn, ref->k, c->k);
-  if (ref->device != c->device) return -set_err (TJAMD_ERR_ARG, "%s: the reference lives on device %d, the counter on device %d", fn, ref->device, c->device);
+  if (const int bad = reference_of_counter (fn, ref, c)) return -bad;
   if (hipSetDevice (c->device) != hipSuccess) return -set_err (TJAMD_ERR_HIP, "hipSetDevice failed");
   Stage st (c, T_VARIANTS);
   if (n_flags == 0) {
@@ -7481,7 +7517,7 @@ extern "C" long tjamd_tract_variants (tjamd_counter *c, const tjamd_reference *r
   if (rc) return -rc;
   const u32 h_err = h[(size_t) n_samples + 1];
   const long n_rec = (long) h[(size_t) n_samples];
-  if (h_err & 1u) return -set_err (TJAMD_ERR_ARG, "%s: the tracts do not tile the union (first 0, each starting where the one before ends, the last ending at n_union)", fn);
+  if (h_err & 1u) return -set_err (TJAMD_ERR_ARG, TILING_REFUSED, fn);
   if (h_err & 2u) return -set_err (TJAMD_ERR_ARG, "%s: a listed tract id is outside [0, %ld)", fn, n_tracts);
   if (n_rec > capacity) return -set_err (TJAMD_ERR_CAPACITY, "%s: %ld records, caller capacity %ld", fn, n_rec, capacity);
   for (int s = 0; s <= n_samples; s++) h_offsets[s] = (long) h[(size_t) s];
@@ -7665,19 +7701,14 @@ extern "C" double tjamd_last_annotation_ms (tjamd_counter *c) { return c ? c->ti
 // segment's first lane looks the location up in the table (one binary search) and reads the tract's rows; with a union, a
 // lane per sample (looping beyond 64) takes the length of the sample's modal row and the segment reduces the maximum with
 // shuffles.  Without a union (keys == NULL, S = 1) a thread per tract does the lookup alone.  err |= 1: the tracts do not
-// tile the union (checked as in tract_variants_kernel; nothing is read outside the arrays either way).
+// tile the union (check_tiling; tract_rows reads nothing outside the arrays either way).
 __global__ __launch_bounds__ (256)
 void tract_features_kernel (const u64 *__restrict__ keys, const int *__restrict__ counts, long n_union, int ns, int S,
                             const UnionTract *__restrict__ tracts, long n_tracts, const Location *__restrict__ tloc,
                             const u64 *__restrict__ points, const u32 *__restrict__ prio, long np, TractFeature *__restrict__ out, int *__restrict__ err)
 {
   const long gthread = blockIdx.x * (long) blockDim.x + threadIdx.x, n_threads = (long) gridDim.x * blockDim.x;
-  if (keys)
-    for (long t = gthread; t < n_tracts; t += n_threads) {
-      const long first = tracts[t].first, rows = tracts[t].n_rows;
-      const long want = t ? (long) tracts[t - 1].first + tracts[t - 1].n_rows : 0l;
-      if (first != want || rows < 1 || first + rows > n_union || (t == n_tracts - 1 && first + rows != n_union)) atomicOr (err, 1);
-    }
+  if (keys) check_tiling (tracts, n_tracts, n_union, err);
   const int lane = threadIdx.x & (S - 1);
   const long segs_per_grid = n_threads / S;
   for (long t = gthread / S; t < n_tracts; t += segs_per_grid) {   // (uniform across a segment)
@@ -7689,11 +7720,7 @@ void tract_features_kernel (const u64 *__restrict__ keys, const int *__restrict_
         const long e = point_bound (points, np, feature_point (l.contig, (u32) l.pos + 1u), true) - 1;
         if (e >= 0) feature = priority_winner (prio[e]);
       }
-      if (keys) {
-        const UnionTract u = tracts[t];
-        first = u.first; end = first + (long) u.n_rows;
-        if (first < 0 || u.n_rows < 1 || end > n_union) first = end = 0;   // (a broken tiling: flagged above)
-      }
+      if (keys) tract_rows (tracts[t], n_union, first, end);   // (none of a broken tiling: flagged above)
     }
     if (keys) {
       first = __shfl (first, 0, S); end = __shfl (end, 0, S);
@@ -7717,9 +7744,9 @@ extern "C" long tjamd_tract_features (tjamd_counter *c, const tjamd_annotation *
   const bool have_union = d_keys && d_counts;
   auto refused = [&] () -> int {                        // the checks that read no handle, the counter's device last
     if (have_union) {
-      const int rc = union_args (fn, d_keys, d_counts, n_union, n_samples);
+      int rc = union_args (fn, d_keys, d_counts, n_union, n_samples);   // (the locations are checked with the output, below: not tiled_union_args)
+      if (!rc) rc = tract_count_arg (fn, n_tracts, n_union);
       if (rc) return rc;
-      if (n_tracts < (n_union > 0 ? 1 : 0) || n_tracts > n_union) return set_err (TJAMD_ERR_ARG, "%s: n_tracts %ld for a union of %ld rows", fn, n_tracts, n_union);
       if (n_tracts > 0 && !d_tracts) return set_err (TJAMD_ERR_ARG, "%s: null tract buffer", fn);
     }
     if (n_tracts < 0) return set_err (TJAMD_ERR_ARG, "%s: n_tracts %ld < 0", fn, n_tracts);
@@ -7748,7 +7775,7 @@ extern "C" long tjamd_tract_features (tjamd_counter *c, const tjamd_annotation *
   int h_err = 0;
   rc = read_back (c, fn, err, &h_err, 1);
   if (rc) return -rc;
-  if (h_err) return -set_err (TJAMD_ERR_ARG, "%s: the tracts do not tile the union (first 0, each starting where the one before ends, the last ending at n_union)", fn);
+  if (h_err) return -set_err (TJAMD_ERR_ARG, TILING_REFUSED, fn);
   st.done ();
   return n_tracts;
 }
@@ -8169,11 +8196,6 @@ struct MvAgg { u64 ref_flank; int n_flank, min_length, pos; u32 first_record; };
 // (tjamd_merge_variants names them)
 
 __device__ __forceinline__ int mv_nf (int n_flank) { return min (max (n_flank, 0), 32); }   // (a refused n_flank never reaches a shift)
-__device__ __forceinline__ u64 mv_shfl_xor64 (u64 x, int o)
-{
-  const u32 lo = __shfl_xor ((u32) x, o), hi = __shfl_xor ((u32) (x >> 32), o);
-  return ((u64) hi << 32) | lo;
-}
 
 // mode 0: the whole key in one word, (tract, alt_length : 10, n_flank : 6, alt_flank : 2k), and the record's own checks;
 // mode 1: the flank word of a two-word key, and the checks; mode 2: the other word, of record val_in[j] (the order the sort
@@ -8287,7 +8309,7 @@ void mv_site_kernel (const Variant *__restrict__ rec, const u32 *__restrict__ va
       }
       for (int o = 32; o; o >>= 1) {
         const int F2 = __shfl_xor (F, o);
-        const u64 fl2 = mv_shfl_xor64 (fl, o);
+        const u64 fl2 = shfl_xor64 (fl, o);
         if (F2 > F || (F2 == F && fl2 > fl)) { F = F2; fl = fl2; }
         ml = min (ml, __shfl_xor (ml, o)); ps = min (ps, __shfl_xor (ps, o)); fr = min (fr, __shfl_xor (fr, o));
       }
@@ -8441,9 +8463,9 @@ extern "C" double tjamd_last_merge_variants_ms (tjamd_counter *c) { return c ? c
 // What tjamd_merge_variants cannot know from N8's records: whether a sample without a record equals the reference or has no
 // read on the tract.  The count matrix of the union tells; the rule as built is in include/tatajuba_depths.h.  Segment mapping
 // of tract_variants_kernel: S lanes per site, a lane per sample (looping beyond 64), a count row read as S consecutive words;
-// what the samples share -- the tract's rows, its index entry, k_eff, the site's allele range -- is found by the segment's first
-// lane and broadcast.  A row's class (REF, an allele of the site, OTHER) does not depend on the sample: the lanes of a segment
-// classify a chunk of S rows, one row each (key load, revcomp_k on the negative strand, XOR under kmask (k_eff), one __clzll,
+// what the samples share -- the tract's rows (tract_rows), its index entry and k_eff (located_tract), the site's allele range -- is
+// found by the segment's first lane and broadcast.  A row's class (REF, an allele of the site, OTHER) does not depend on the sample:
+// the lanes of a segment classify a chunk of S rows, one row each (row_right_flank, the rule N8's records were written by, then
 // the search among the site's alleles), and then every lane walks the chunk for its own sample and takes each row's class with
 // __shfl.  DP, the modal row with its class and length, and eight class accumulators (REF and seven alleles; selected by
 // unrolled compares, nothing indexed, nothing in scratch memory) stay in registers; a site with more than eight classes walks
@@ -8458,16 +8480,6 @@ struct SdShared { int first, end, k_eff, a0, na, Lr, neg, ok; u64 fr; };   // wh
 // err bits: 1 tiling, 2 site.tract, 4 the site against its tract's location and entry, 8 the allele chain, 16 n_alleles < 1,
 // 32 allele.site, 64 allele.n_flank, 128 a modal row that no allele holds, 256 n_called (tjamd_site_depths names them)
 
-__device__ __forceinline__ long long sd_shfl_xor64 (long long x, int o, int S)
-{
-  const u32 lo = __shfl_xor ((u32) x, o, S), hi = __shfl_xor ((u32) ((u64) x >> 32), o, S);
-  return (long long) (((u64) hi << 32) | lo);
-}
-__device__ __forceinline__ long long sd_shfl64 (long long x, int from, int S)
-{
-  const u32 lo = __shfl ((u32) x, from, S), hi = __shfl ((u32) ((u64) x >> 32), from, S);
-  return (long long) (((u64) hi << 32) | lo);
-}
 __device__ __forceinline__ int sd_saturated (long long x) { return x > 0x7fffffffll ? 0x7fffffff : (int) x; }
 
 template <bool WRITE>
@@ -8480,12 +8492,7 @@ void site_depths_kernel (const u64 *__restrict__ keys, const int *__restrict__ c
 {
   const long gthread = blockIdx.x * (long) blockDim.x + threadIdx.x, n_threads = (long) gridDim.x * blockDim.x;
   if (WRITE) { if (*(volatile int *) err != 0) return; }   // (the first pass is complete: every thread reads the same word)
-  else
-    for (long t = gthread; t < n_tracts; t += n_threads) {
-      const long first = tracts[t].first, rows = tracts[t].n_rows;
-      const long want = t ? (long) tracts[t - 1].first + tracts[t - 1].n_rows : 0l;
-      if (first != want || rows < 1 || first + rows > n_union || (t == n_tracts - 1 && first + rows != n_union)) atomicOr (err, 1);
-    }
+  else check_tiling (tracts, n_tracts, n_union, err);
   const int lane = threadIdx.x & (S - 1);
   const int log_S = __ffs (S) - 1;                       // (S is a power of two)
   const long segs_per_grid = n_threads >> log_S;
@@ -8507,32 +8514,24 @@ void site_depths_kernel (const u64 *__restrict__ keys, const int *__restrict__ c
       if (na < 1) bad |= 16;
       if ((long) a0 != a_want || (i == n_sites - 1 && (long) a0 + (long) na != n_alleles)) bad |= 8;
       if (a0 < 0 || na < 1 || (long) a0 + (long) na > n_alleles) { if (na >= 1) bad |= 8; a0 = 0; na = 0; }   // (nothing is read outside the alleles)
+      long t_first = 0, t_end = 0;
       if (t < 0 || t >= n_tracts) bad |= 2;
-      else {
-        const UnionTract u = tracts[t];
+      else tract_rows (tracts[t], n_union, t_first, t_end);   // (none of a broken tiling: flagged above)
+      first = (int) t_first; end = (int) t_end;
+      if (first < end) {                                // the site is its tract's: the entry there, and what N12 copied from the records
         const Location l = tloc[t];
-        if (u.first < 0 || u.n_rows < 1 || (long) u.first + (long) u.n_rows > n_union) first = end = 0;   // (a broken tiling: flagged above)
-        else { first = u.first; end = u.first + u.n_rows; }
-        if (first < end && l.flat >= 0 && (ent = (int) ref_entry_at (entries, n_ent, l.flat)) >= 0) {
-          k_eff = k;
-          if (t + 1 < n_tracts) {                       // stop at the next tract of the contig, as N8 does
-            const Location nx = tloc[t + 1];
-            const long overlap = (long) l.pos + (long) entries[ent].length + (long) k - (long) nx.pos;
-            if (nx.flat >= 0 && nx.contig == l.contig && overlap > 0) k_eff = (int) max (0l, (long) k - overlap);
-          }
-          if (site.flat != l.flat || site.contig != l.contig || site.ref_length != entries[ent].length) { bad |= 4; ent = -1; }
-        }
-        if (first < end && ent < 0) bad |= 4;
+        ent = (int) located_tract (tloc, n_tracts, t, entries, n_ent, k, k_eff);
+        if (ent < 0 || site.flat != l.flat || site.contig != l.contig || site.ref_length != entries[ent].length) { bad |= 4; ent = -1; }
       }
       if (bad) { ent = -1; atomicOr (err, bad); }
-      if (ent >= 0) { const RefEntry e = entries[ent]; Lr = e.length; neg = e.neg_strand; fr = e.neg_strand ? revcomp_k (e.ctx0, k) : e.ctx1; }
+      if (ent >= 0) { const RefEntry e = entries[ent]; Lr = e.length; neg = e.neg_strand; fr = entry_right_flank (e, k); }
       const SdShared p = {first, end, k_eff, a0, na, Lr, neg, ent >= 0 ? 1 : 0, fr};
       shared[i] = p;
     }
     if (!WRITE) {
       first = __shfl (first, 0, S); end = __shfl (end, 0, S); ent = __shfl (ent, 0, S); a0 = __shfl (a0, 0, S);
       k_eff = __shfl (k_eff, 0, S); na = __shfl (na, 0, S); n_called = __shfl (n_called, 0, S); Lr = __shfl (Lr, 0, S); neg = __shfl (neg, 0, S);
-      fr = (u64) sd_shfl64 ((long long) fr, 0, S);
+      fr = shfl64 (fr, 0, S);
       int bad = 0;                                      // the site's alleles, a lane each
       for (int a = lane; a < na; a += S) {
         if (alleles[a0 + a].site != (int) i) bad |= 32;
@@ -8559,9 +8558,8 @@ void site_depths_kernel (const u64 *__restrict__ keys, const int *__restrict__ c
             la = meta_len (keys[3 * r_own + 2]);
             if (la == Lr && la >= 1) cls = 0;
             else if (la >= 1) {
-              const u64 fa = neg ? revcomp_k (keys[3 * r_own], k) : keys[3 * r_own + 1];
-              const u64 x = (fr ^ fa) & kmask (k_eff);
-              const int nf = x ? (63 - __clzll ((long long) x)) / 2 + 1 : 0;
+              int nf;
+              const u64 fa = row_right_flank (keys, r_own, neg, k, k_eff, fr, nf);
               #pragma unroll 1
               for (int a = 0; a < na; a++) {
                 const Allele al = alleles[a0 + a];
@@ -8609,7 +8607,7 @@ void site_depths_kernel (const u64 *__restrict__ keys, const int *__restrict__ c
     }
     for (int o = S >> 1; o; o >>= 1) {
       n_ref += __shfl_xor (n_ref, o, S); n_missing += __shfl_xor (n_missing, o, S); n_alt += __shfl_xor (n_alt, o, S);
-      depth += sd_shfl_xor64 (depth, o, S);
+      depth += (long long) shfl_xor64 ((u64) depth, o, S);
     }
     if (lane == 0) {
       if (!WRITE) { if (n_alt != n_called) atomicOr (err, 256); }
@@ -8625,10 +8623,8 @@ extern "C" long tjamd_site_depths (tjamd_counter *c, const tjamd_reference *ref,
 {
   static const char *fn = "tjamd_site_depths";
   if (!c || !ref) return -set_err (TJAMD_ERR_ARG, "%s: null counter or reference", fn);
-  int rc = union_args (fn, d_keys, d_counts, n_union, n_samples);
+  int rc = tiled_union_args (fn, d_keys, d_counts, n_union, n_samples, d_tracts, n_tracts, d_tract_loc);
   if (rc) return -rc;
-  if (n_tracts < (n_union > 0 ? 1 : 0) || n_tracts > n_union) return -set_err (TJAMD_ERR_ARG, "%s: n_tracts %ld for a union of %ld rows", fn, n_tracts, n_union);
-  if (n_tracts > 0 && (!d_tracts || !d_tract_loc)) return -set_err (TJAMD_ERR_ARG, "%s: null tract or tract location buffer", fn);
   if (n_sites < 0 || n_alleles < 0) return -set_err (TJAMD_ERR_ARG, "%s: n_sites %ld, n_alleles %ld: a count below 0", fn, n_sites, n_alleles);
   if ((n_sites > 0 && !d_sites) || (n_alleles > 0 && !d_alleles)) return -set_err (TJAMD_ERR_ARG, "%s: null site or allele buffer", fn);
   if (n_sites > n_tracts) return -set_err (TJAMD_ERR_ARG, "%s: %ld sites for %ld tracts", fn, n_sites, n_tracts);
@@ -8638,8 +8634,7 @@ extern "C" long tjamd_site_depths (tjamd_counter *c, const tjamd_reference *ref,
   if (tjamd_device_count () <= 0) return -set_err (TJAMD_ERR_NO_DEVICE, "%s: TJAMD_ERR_NO_DEVICE: no HIP device visible (the depths are counted on the device; no CPU fallback)", fn);
   if (ref->n_entries >= (1l << 31)) return -set_err (TJAMD_ERR_CAPACITY, "%s: %ld index entries", fn, ref->n_entries);
   Stage st (c, T_SITE_DEPTHS);                          // (a refused call leaves no timing behind)
-  if (ref->k != c->k) return -set_err (TJAMD_ERR_ARG, "%s: the reference was built with k = %d, the counter has k = %d", fn, ref->k, c->k);
-  if (ref->device != c->device) return -set_err (TJAMD_ERR_ARG, "%s: the reference lives on device %d, the counter on device %d", fn, ref->device, c->device);
+  if (const int bad = reference_of_counter (fn, ref, c)) return -bad;
   if (hipSetDevice (c->device) != hipSuccess) return -set_err (TJAMD_ERR_HIP, "hipSetDevice failed");
   if (n_sites == 0) return 0;
   ScratchCut cut;
@@ -8661,7 +8656,7 @@ extern "C" long tjamd_site_depths (tjamd_counter *c, const tjamd_reference *ref,
   u32 h_err = 0;
   rc = read_back (c, fn, err, &h_err, 1);
   if (rc) return -rc;
-  if (h_err & 1u) return -set_err (TJAMD_ERR_ARG, "%s: the tracts do not tile the union (first 0, each starting where the one before ends, the last ending at n_union)", fn);
+  if (h_err & 1u) return -set_err (TJAMD_ERR_ARG, TILING_REFUSED, fn);
   if (h_err & 2u) return -set_err (TJAMD_ERR_ARG, "%s: a site's tract is outside [0, %ld)", fn, n_tracts);
   if (h_err & 16u) return -set_err (TJAMD_ERR_ARG, "%s: a site has n_alleles < 1", fn);
   if (h_err & 8u) return -set_err (TJAMD_ERR_ARG, "%s: first_allele and n_alleles of the sites do not chain from 0 to %ld", fn, n_alleles);
