@@ -8,6 +8,9 @@
  *                             contig  POS  .  REF  ALT1,ALT2  .  .  AC=n1,n2;AN=n_called;TID=tid_%06d  GT  g0  g1 ...
  *                             with -D: tjamd_site_depths after the merge; FORMAT is GT:DP:AD, GT is 0 where the sample's reads
  *                             show the genome's own length and "." only where it was not seen, AN counts the reference samples too
+ *   DIR/sample_distances.tsv  with -M: tjamd_sample_distances on the genotype matrix the run has (that of the depths with -D, that of
+ *                             the merge without, where samples that equal the reference count as not called), one row per pair
+ *                             of samples a <= b: sample_a  sample_b  n_both  n_differ  length_diff
  *   DIR/unique_variants.vcf   with -u: the tutorial's concatenation, one row per distinct allele in N8's own form (the record
  *                             d_unique holds), one column all_samples
  *   DIR/variant_effects.tsv   with -e annotation.gff3: tjamd_variant_effects on d_unique only, one line per allele: variant_effects.c's
@@ -15,11 +18,11 @@
  * The other options are sample_vcfs.c's.
  *
  *   gcc -O2 -I include examples/merged_vcf.c -L tatajuba_amd -ltatajuba_amd -Wl,-rpath,$PWD/tatajuba_amd -o merged_vcf
- *   ./merged_vcf -r reference.fa [-u] [-D] [-e annotation.gff3] [-x 1] [-g G] [-s 3] [-k 10] [-m 3] [-c 5] [-d 1] [-l -1] [-o .] sample1.fastq[.gz] ...   */
+ *   ./merged_vcf -r reference.fa [-u] [-D] [-M] [-e annotation.gff3] [-x 1] [-g G] [-s 3] [-k 10] [-m 3] [-c 5] [-d 1] [-l -1] [-o .] sample1.fastq[.gz] ...   */
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
-#include <tatajuba_depths.h>
+#include <tatajuba_distances.h>
 #include <tatajuba_effects.h>
 #include <tatajuba_locate.h>
 
@@ -77,7 +80,7 @@ main (int argc, char **argv)
   static const char *class_name[5] = {"NONE", "BOUNDARY", "IDENTICAL", "INFRAME", "FRAMESHIFT"};
   long counts[MAX_SAMPLES], total, n_union, n_grouped, n_tracts, n_located, n_gapped = 0, n_var = 0, n_rec, i, cap, ref_bytes, n_contigs = 0, n_names = 0, name_bytes;
   long offsets[MAX_SAMPLES + 1], *contig_len, var_cap, n_sites, n_alleles = 0, s, text_cap = 0;
-  int with_unique = 0, with_depths = 0;
+  int with_unique = 0, with_depths = 0, with_distances = 0;
   int n = 0, k = 10, m = 3, cov = 5, maxd = 1, lev = -1, mism = 1, max_edits = -1, max_shift = TJAMD_MAX_SHIFT, coverage[MAX_SAMPLES], a, ndev = tjamd_device_count (), status;
   const void *d_records = NULL;
   void *d_keys, *d_counts, *d_ids, *d_grouped, *d_loc, *d_perm, *d_pkeys, *d_pcounts, *d_tracts, *d_tloc, *d_reflen, *d_summary, *d_var, *d_variants, *d_sites, *d_alleles, *d_genotype, *d_unique,
@@ -91,6 +94,7 @@ main (int argc, char **argv)
   int16_t *h_genotype;
   int *h_dp = NULL, *h_ad = NULL;
   tjamd_site_depth *h_sd = NULL;
+  tjamd_sample_distance *h_dist = NULL;
   char *text, **sample_name;
   FILE *fout;
 
@@ -108,9 +112,10 @@ main (int argc, char **argv)
     else if (!strcmp (argv[a], "-e") && a + 1 < argc) gff = argv[++a];
     else if (!strcmp (argv[a], "-u")) with_unique = 1;
     else if (!strcmp (argv[a], "-D")) with_depths = 1;
+    else if (!strcmp (argv[a], "-M")) with_distances = 1;
     else if (n < MAX_SAMPLES) files[n++] = argv[a];
   }
-  if (n < 1 || !reference) { fprintf (stderr, "usage: %s -r reference.fa [-u] [-D] [-e annotation.gff3] [-x X] [-g G] [-s S] [-k K] [-m M] [-c C] [-d D] [-l L] [-o DIR] sample.fastq[.gz] ...\n", argv[0]); return 2; }
+  if (n < 1 || !reference) { fprintf (stderr, "usage: %s -r reference.fa [-u] [-D] [-M] [-e annotation.gff3] [-x X] [-g G] [-s S] [-k K] [-m M] [-c C] [-d D] [-l L] [-o DIR] sample.fastq[.gz] ...\n", argv[0]); return 2; }
   if (ndev < 1) { fprintf (stderr, "tatajuba_amd error: no HIP device is visible (there is no CPU fallback)\n"); return 1; }
   if (maxd < 0) maxd = 0;                                 /* src/main.c:190-192 */
   if (maxd > k / 2) maxd = k / 2;
@@ -217,6 +222,14 @@ main (int argc, char **argv)
         tjamd_device_download (ctr[0], h_ad, d_ad, (size_t) (n_sites + n_alleles) * (size_t) n * sizeof (int)) ||
         tjamd_device_download (ctr[0], h_sd, d_sd, (size_t) n_sites * sizeof (tjamd_site_depth))) return fail ("download");
   }
+  if (with_distances) {                                   /* how far apart the samples are, on the genotypes the run has by now */
+    void *d_dist = tjamd_device_alloc (ctr[0], (size_t) n * (size_t) n * sizeof (tjamd_sample_distance));
+    if (tjamd_sample_distances (ctr[0], (const tjamd_site *) d_sites, n_sites, (const tjamd_allele *) d_alleles, n_alleles, (const int16_t *) d_genotype, n,
+                                (tjamd_sample_distance *) d_dist) < 0) return fail ("sample distances");
+    h_dist = (tjamd_sample_distance *) malloc ((size_t) n * (size_t) n * sizeof (tjamd_sample_distance));
+    if (tjamd_device_download (ctr[0], h_dist, d_dist, (size_t) n * (size_t) n * sizeof (tjamd_sample_distance))) return fail ("download");
+    tjamd_device_free (ctr[0], d_dist);
+  }
   h_sites = (tjamd_site *) malloc ((size_t) (n_sites ? n_sites : 1) * sizeof (tjamd_site));
   h_alleles = (tjamd_allele *) malloc ((size_t) (n_alleles ? n_alleles : 1) * sizeof (tjamd_allele));
   h_genotype = (int16_t *) malloc ((size_t) (n_sites ? n_sites : 1) * (size_t) n * sizeof (int16_t));
@@ -283,6 +296,18 @@ main (int argc, char **argv)
     fputc ('\n', fout);
   }
   fclose (fout);
+
+  if (with_distances) {                                   /* the upper triangle with the diagonal, by the names of the VCF's columns */
+    int b;
+    if (!(fout = open_output (outdir, "sample_distances.tsv"))) return 1;
+    fprintf (fout, "sample_a\tsample_b\tn_both\tn_differ\tlength_diff\n");
+    for (a = 0; a < n; a++) for (b = a; b < n; b++) {
+      const tjamd_sample_distance *x = h_dist + (size_t) a * (size_t) n + b;
+      fprintf (fout, "%s\t%s\t%d\t%d\t%lld\n", sample_name[a], sample_name[b], x->n_both, x->n_differ, x->length_diff);
+    }
+    fclose (fout);
+    free (h_dist);
+  }
 
   if (with_unique) {                                      /* every distinct event once, as N8 wrote it for the first sample that has it */
     if (!(fout = open_output (outdir, "unique_variants.vcf"))) return 1;

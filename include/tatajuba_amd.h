@@ -398,6 +398,9 @@ long tjamd_located_tracts (tjamd_counter *c, const void *d_keys, const void *d_c
  * tjamd_site_depths) are declared, with their timer, in tatajuba_depths.h, which includes tatajuba_sites.h and through it this
  * header. */
 
+/* The pairwise distances of the samples over the merged sites (N14: tjamd_sample_distances) are declared, with their timer,
+ * in tatajuba_distances.h, which includes tatajuba_depths.h and through it this header. */
+
 /* release the calling thread's shared device contexts of the synchronous string scans (update_hopo_counter_from_seq on a
  * counter that never read a file, tjamd_scan_windows) now; they are released by themselves when the thread ends */
 void tjamd_thread_cleanup (void);

@@ -69,6 +69,8 @@ ALLELE_DTYPE = np.dtype([("site", "<i4"), ("alt_length", "<i4"), ("n_flank", "<i
 assert ALLELE_DTYPE.itemsize == 32
 SITE_DEPTH_DTYPE = np.dtype([("n_ref", "<i4"), ("n_missing", "<i4"), ("depth", "<i8")])      # tjamd_site_depth (include/tatajuba_depths.h)
 assert SITE_DEPTH_DTYPE.itemsize == 16
+SAMPLE_DISTANCE_DTYPE = np.dtype([("n_both", "<i4"), ("n_differ", "<i4"), ("length_diff", "<i8")])      # tjamd_sample_distance (include/tatajuba_distances.h)
+assert SAMPLE_DISTANCE_DTYPE.itemsize == 16
 
 
 class TatajubaAmdError(RuntimeError):
@@ -162,6 +164,8 @@ EFFECT_EXPORTS = ["tjamd_translate", "tjamd_gff3_read_phase", "tjamd_coding_crea
 SITE_EXPORTS = ["tjamd_merge_variants", "tjamd_site_ref_alt", "tjamd_last_merge_variants_ms"]
 # ... and include/tatajuba_depths.h
 DEPTH_EXPORTS = ["tjamd_site_depths", "tjamd_last_site_depths_ms"]
+# ... and include/tatajuba_distances.h
+DISTANCE_EXPORTS = ["tjamd_sample_distances", "tjamd_last_sample_distances_ms"]
 MAX_SHIFT = 3                     # TJAMD_MAX_SHIFT
 
 
@@ -322,6 +326,9 @@ def lib():
     L.tjamd_site_depths.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_long, C.c_int, C.c_void_p, C.c_long, C.c_void_p,
                                     C.c_void_p, C.c_long, C.c_void_p, C.c_long, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     L.tjamd_last_site_depths_ms.restype = C.c_double; L.tjamd_last_site_depths_ms.argtypes = [C.c_void_p]
+    L.tjamd_sample_distances.restype = C.c_long
+    L.tjamd_sample_distances.argtypes = [C.c_void_p, C.c_void_p, C.c_long, C.c_void_p, C.c_long, C.c_void_p, C.c_int, C.c_void_p]
+    L.tjamd_last_sample_distances_ms.restype = C.c_double; L.tjamd_last_sample_distances_ms.argtypes = [C.c_void_p]
     L.tjamd_group_contexts.restype = C.c_long
     L.tjamd_group_contexts.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_long]
     L.new_genomic_context_list.restype = C.POINTER(GenomicContextListStruct); L.new_genomic_context_list.argtypes = [P]
@@ -913,6 +920,15 @@ class Counter:
 
     def last_site_depths_ms(self):
         return lib().tjamd_last_site_depths_ms(self._h)
+
+    def sample_distances(self, d_sites, n_sites, d_alleles, n_alleles, d_genotype, n_samples, d_out):
+        """tjamd_sample_distances on device pointers: the sites and alleles of tjamd_merge_variants and an int16 genotype matrix
+        [site][sample] (that of tjamd_site_depths, or of tjamd_merge_variants) -> one SAMPLE_DISTANCE_DTYPE record per pair of
+        samples at d_out, [sample][sample], full and symmetric.  -> n_sites"""
+        return self._chkn(lib().tjamd_sample_distances(self._h, d_sites, n_sites, d_alleles, n_alleles, d_genotype, n_samples, d_out))
+
+    def last_sample_distances_ms(self):
+        return lib().tjamd_last_sample_distances_ms(self._h)
 
     def uses_log(self):
         lib().tjamd_counter_uses_log.restype = C.c_int

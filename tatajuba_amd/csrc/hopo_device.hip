@@ -43,6 +43,7 @@
 #include "../../include/tatajuba_effects.h"
 #include "../../include/tatajuba_sites.h"
 #include "../../include/tatajuba_depths.h"
+#include "../../include/tatajuba_distances.h"
 #include "../../include/tatajuba_locate.h"
 
 typedef unsigned long long u64;
@@ -3873,7 +3874,7 @@ struct StageTimer
 };
 // the intervals of a counter: the last scan call (its partition kernels between the pieces included: tjamd_last_scan_ms takes
 // them out), finalise, the kernels of tjamd_merge_samples, tjamd_tract_stats, tjamd_union_tracts, tjamd_union_tract_stats
-enum { T_SCAN, T_FIN, T_MERGE, T_TRACT, T_UNION, T_UNION_STATS, T_REF, T_LOCATE, T_LOCATED_TRACTS, T_VARIANTS, T_ANNOTATION, T_TRACT_FEATURES, T_SEED_ORDER, T_LOCATE_GAPPED, T_CODING, T_VARIANT_EFFECTS, T_MERGE_VARIANTS, T_SITE_DEPTHS, TJ_N_TIMERS };   // (T_REF to T_LOCATED_TRACTS: N7, T_VARIANTS: N8, the next two: N9; then two of N10; two of N11; then N12 and N13, end of the file)
+enum { T_SCAN, T_FIN, T_MERGE, T_TRACT, T_UNION, T_UNION_STATS, T_REF, T_LOCATE, T_LOCATED_TRACTS, T_VARIANTS, T_ANNOTATION, T_TRACT_FEATURES, T_SEED_ORDER, T_LOCATE_GAPPED, T_CODING, T_VARIANT_EFFECTS, T_MERGE_VARIANTS, T_SITE_DEPTHS, T_SAMPLE_DISTANCES, TJ_N_TIMERS };   // (T_REF to T_LOCATED_TRACTS: N7, T_VARIANTS: N8, the next two: N9; then two of N10; two of N11; then N12, N13 and N14, end of the file)
 
 struct tjamd_counter
 {
@@ -3928,6 +3929,7 @@ struct tjamd_counter
   unsigned scan_seq = 0;
   size_t piece_target = TJ_SCAN_PIECE_TARGET;           // TATAJUBA_AMD_SCAN_PIECE (bytes) overrides it: tests
   int scan_grid_cap = 0;                                // TATAJUBA_AMD_SCAN_GRID (tests): n >= 1 caps the workgroups of the scan and log-partition launches; 0: no cap
+  int dist_blocks = 0;                                  // TATAJUBA_AMD_DISTANCE_BLOCKS (tests): the workgroups tjamd_sample_distances splits its sites for; 0: four per CU
   bool buckets_clean = false;
   long plan_mismatches = 0;   // finalises whose in-kernel reading of the kept count differed from the kernel boundary's (expected: 0)
   bool ctr_clean = false;     // the scan counters are zero but for n_undefined (clear_buckets_kernel did it, no scan since)
@@ -4021,6 +4023,8 @@ extern "C" tjamd_counter *tjamd_counter_create (int device, int kmer_size)
   if (fm && atoi (fm) >= 0 && atoi (fm) <= 2) c->fast_mode = atoi (fm);
   const char *sg = getenv ("TATAJUBA_AMD_SCAN_GRID");     // test hook: at most n workgroups per scan / log-partition launch (one workgroup then walks many tiles or blocks)
   if (sg && atoi (sg) >= 1) c->scan_grid_cap = atoi (sg);
+  const char *db = getenv ("TATAJUBA_AMD_DISTANCE_BLOCKS");   // test hook: tjamd_sample_distances aims at n workgroups when it splits the sites (1: never splits)
+  if (db && atoi (db) >= 1) c->dist_blocks = atoi (db);
   const char *sl = getenv ("TATAJUBA_AMD_BUCKET_SLACK");
   if (sl && atof (sl) >= 1.0) c->slack = atof (sl);
   HIPCHK_NULL (hipStreamCreateWithFlags (&c->own_stream, hipStreamNonBlocking));
@@ -8669,3 +8673,323 @@ extern "C" long tjamd_site_depths (tjamd_counter *c, const tjamd_reference *ref,
   return n_sites;
 }
 extern "C" double tjamd_last_site_depths_ms (tjamd_counter *c) { return c ? c->timer[T_SITE_DEPTHS].ms (c->device) : -1.0; }
+
+// ---- N14: pairwise sample distances over the merged sites -------------------------------------------------------------------
+// The site x sample genotype matrix of N12 / N13 reduced to a sample x sample matrix of (n_both, n_differ, length_diff); the rule
+// as built is in include/tatajuba_distances.h.  The first step since the scan whose cost is arithmetic: S^2 T / 2 cell pairs.
+// A workgroup owns a tile of E x E sample pairs on or above the diagonal and a slice of the sites.  Per chunk of SDIST_CELLS / E
+// sites it stages the genotypes of its two sample tiles into LDS and, beside each, the cell's length (ref_length or the allele's
+// alt_length), which the check pass has looked up once per cell and left in scratch, an int per cell (looked up while staging,
+// by every tile that stages the cell, the gather of 32-byte alleles took more time than the arithmetic at 1024 samples); then
+// every thread walks the chunk's sites for a register block of 4 x 4 pairs, reading four cells
+// of either tile as one 16-byte LDS load.  E is 64 where the tile pairs alone fill the device (16 x 16 threads, every thread
+// walks every site) and 32, 16 or 8 below (8 x 8, 4 x 4, 2 x 2 pair threads, and the 4, 16 or 64 thread groups that this leaves
+// take every 4th, 16th or 64th site of the chunk; their sums meet in LDS atomics at the end of the workgroup).  A pair of cells costs six vector
+// instructions and no branch: the AND of the two cells' called masks (made once per cell), n_both minus that mask, a compare
+// and a carry-add for the equal calls, a bit select and one v_sad_u32 that adds |La - Lb| to a 32-bit sum; the 32-bit sums are flushed into 64-bit ones before they can overflow (the
+// bound is the chunk's largest staged length: see the kernel).  Where the sites are split over workgroups (few tile pairs) every workgroup stores its
+// tile in scratch and a third kernel sums the slices in their order; otherwise a tile is stored at once.  No atomic reaches
+// global memory but the error flag's (device-wide atomics on the matrix, tried first, took more time than the arithmetic at 1024
+// samples).  Off-diagonal tiles are written to both halves.  Two or three kernels; the first makes every check and writes
+// nothing of the caller's, the others return while the flag is up.
+// DESIGN.md section 3.5, N14.
+
+struct SampleDistance { int n_both, n_differ; long long length_diff; };
+static_assert (sizeof (SampleDistance) == 16 && sizeof (SampleDistance) == sizeof (tjamd_sample_distance), "sample distance layout");
+
+#define SDIST_CELLS 2048                // cells of one sample tile in a chunk: E samples x SDIST_CELLS / E sites (4 arrays of ints: 32 KB of LDS)
+// err bits: 1 a genotype cell, 8 the allele chain, 16 n_alleles < 1, 32 allele.site, 64 alt_length, 128 ref_length (tjamd_sample_distances names them)
+
+__global__ __launch_bounds__ (256)
+void sample_distances_check_kernel (const Site *__restrict__ sites, long n_sites, const Allele *__restrict__ alleles, long n_alleles,
+                                    const int16_t *__restrict__ gt, int ns, int *__restrict__ lens, int *__restrict__ err)
+{
+  const long gthread = blockIdx.x * (long) blockDim.x + threadIdx.x, n_threads = (long) gridDim.x * blockDim.x;
+  int bad = 0;
+  for (long i = gthread; i < n_sites; i += n_threads) {
+    const int a0 = sites[i].first_allele, na = sites[i].n_alleles;
+    const long a_want = i ? (long) sites[i - 1].first_allele + (long) sites[i - 1].n_alleles : 0l;
+    if (na < 1) bad |= 16;
+    if ((long) a0 != a_want || (i == n_sites - 1 && (long) a0 + (long) na != n_alleles)) bad |= 8;
+    if (sites[i].ref_length < 0) bad |= 128;
+  }
+  for (long a = gthread; a < n_alleles; a += n_threads) {   // (where the chain holds, an allele lies in one site's range: its own)
+    const long s = alleles[a].site;
+    const int len = alleles[a].alt_length;
+    if (s < 0 || s >= n_sites || a < (long) sites[s].first_allele || a >= (long) sites[s].first_allele + (long) sites[s].n_alleles) bad |= 32;
+    if (len < 0 || len > 1023) bad |= 64;
+  }
+  const int n_cells = (int) (n_sites * ns);             // (below 2^31: the entry checks it)
+  for (long x = gthread; x < n_cells; x += n_threads) {   // every cell's length, looked up here once and not by every tile that stages the cell
+    const int g = gt[x], site = (int) x / ns;
+    int len = 0;
+    if (g < -1 || g > sites[site].n_alleles) bad |= 1;
+    else if (g == 0) len = sites[site].ref_length;
+    else if (g > 0) {
+      const long a = (long) sites[site].first_allele + g - 1;
+      if (a >= 0 && a < n_alleles) len = alleles[a].alt_length;   // (otherwise the chain is broken: flagged above)
+    }
+    lens[x] = len;                                      // (scratch)
+  }
+  if (bad) atomicOr (err, bad);
+}
+
+// a pair's sums into the matrix, and into its other half for a pair of an off-diagonal tile
+__device__ __forceinline__ void sdist_emit (SampleDistance *__restrict__ out, int ns, int a, int b, bool mirror, const SampleDistance &o)
+{
+  if (a >= ns || b >= ns) return;
+  out[(long) a * ns + b] = o;
+  if (mirror) out[(long) b * ns + a] = o;
+}
+
+// the tile pair (ti <= tj) with number p: row ti of the upper triangle has n_tiles - ti of them
+__device__ __forceinline__ void sdist_tile_pair (int p, int n_tiles, int &ti, int &tj)
+{
+  ti = 0;
+  while (p >= n_tiles - ti) { p -= n_tiles - ti; ti++; }
+  tj = ti + p;
+}
+
+template <int E>                                        // the tile's edge in samples: 8, 16, 32 or 64
+__global__ __launch_bounds__ (256)
+void sample_distances_kernel (const int16_t *__restrict__ gt, const int *__restrict__ lens, long n_sites, int ns,
+                              int n_tiles, long per_slice, SampleDistance *__restrict__ partial, SampleDistance *__restrict__ out, const int *__restrict__ err)
+{
+  constexpr int CH = SDIST_CELLS / E;                   // sites of a chunk
+  constexpr int T = E / 4;                              // pair threads along an edge of the tile
+  constexpr int Z = 256 / (T * T);                      // thread groups that share the sites of a chunk
+  static_assert (T * T * Z == 256 && CH % Z == 0 && E * E * 16 <= (Z > 1 ? 4 * SDIST_CELLS * 4 : 1 << 30), "tile shape");
+  __shared__ __attribute__ ((aligned (16))) int lds[4 * SDIST_CELLS];
+  __shared__ int l_max[2];                              // the largest length staged in a chunk (1023 at least), by the chunk's parity
+  if (*(volatile const int *) err != 0) return;
+  int *const gA = lds, *const lA = lds + SDIST_CELLS, *const gB = lds + 2 * SDIST_CELLS, *const lB = lds + 3 * SDIST_CELLS;
+  int ti, tj;
+  sdist_tile_pair (blockIdx.x, n_tiles, ti, tj);
+  const int a0 = ti * E, b0 = tj * E;
+  const long s_begin = blockIdx.y * per_slice, s_end = min (n_sites, s_begin + per_slice);
+  const int tid = threadIdx.x, tx = tid % T, ty = (tid / T) % T, z = tid / (T * T);   // tx: along b (consecutive lanes, consecutive columns of the output), ty: along a
+  int nb[4][4], same[4][4];                             // sites with both called; with the same call in both (n_differ is their difference)
+  u32 ld32[4][4];                                       // length differences since the last flush ...
+  u64 ld[4][4];                                         // ... and before it
+  #pragma unroll
+  for (int r = 0; r < 4; r++)
+    #pragma unroll
+    for (int q = 0; q < 4; q++) { nb[r][q] = 0; same[r][q] = 0; ld32[r][q] = 0u; ld[r][q] = 0ull; }
+  if (tid == 0) l_max[0] = 1023;
+  __syncthreads ();
+  int parity = 0;
+  for (long c0 = s_begin; c0 < s_end; c0 += CH, parity ^= 1) {
+    // Staging, SDIST_CELLS / 256 cells of either tile a thread: a row of E samples is E consecutive int16 of the matrix and E
+    // consecutive lengths of the check pass.  Every load is issued before anything waits for one.  A missing cell is staged as
+    // -1 in one tile and -2 in the other, so that two equal words are two calls of one allele; its length is 0.  A length
+    // beyond an allele's 1023 raises the chunk's largest.
+    int g_st[2][SDIST_CELLS / 256], len_st[2][SDIST_CELLS / 256];
+    #pragma unroll
+    for (int j = 0; j < SDIST_CELLS / 256; j++) {
+      const int x = tid + 256 * j;
+      const long site = c0 + x / E;
+      #pragma unroll
+      for (int h = 0; h < 2; h++) {
+        const int sample = (h ? b0 : a0) + x % E;
+        const bool in = site < s_end && sample < ns;
+        g_st[h][j] = in ? (int) gt[site * ns + sample] : -1;
+        len_st[h][j] = in ? lens[site * ns + sample] : 0;
+      }
+    }
+    #pragma unroll
+    for (int j = 0; j < SDIST_CELLS / 256; j++)
+      #pragma unroll
+      for (int h = 0; h < 2; h++) {
+        const int x = tid + 256 * j, g = g_st[h][j], len = len_st[h][j];
+        if (len > 1023) atomicMax (l_max + parity, len);
+        (h ? gB : gA)[x] = g < 0 ? -1 - h : g;
+        (h ? lB : lA)[x] = len;
+      }
+    __syncthreads ();
+    if (tid == 0) l_max[parity ^ 1] = 1023;             // (the next chunk's: last read before the barrier that ended the chunk before, raised again behind the one that ends this)
+    // A site adds |La - Lb| <= max (La, Lb) <= the chunk's largest length to a pair: the 32-bit sums of floor ((2^32 - 1) / largest)
+    // sites cannot overflow.  With lengths as tracts have them that is more than a chunk, and the flush is the one at its end.
+    const int flush_every = (int) min (0xffffffffu / (u32) l_max[parity], (u32) CH);
+    const int n_here = (int) min ((long) CH, s_end - c0);
+    int since = 0;
+    for (int i = z; i < n_here; i += Z) {
+      const int4 ga = *(const int4 *) (gA + i * E + 4 * ty), la = *(const int4 *) (lA + i * E + 4 * ty);
+      const int4 gb = *(const int4 *) (gB + i * E + 4 * tx), lb = *(const int4 *) (lB + i * E + 4 * tx);
+      const int gav[4] = {ga.x, ga.y, ga.z, ga.w}, lav[4] = {la.x, la.y, la.z, la.w}, gbv[4] = {gb.x, gb.y, gb.z, gb.w}, lbv[4] = {lb.x, lb.y, lb.z, lb.w};
+      u32 ca[4], cb[4];                                 // all ones where the cell is called (a missing one has the sign bit), once per cell
+      #pragma unroll
+      for (int r = 0; r < 4; r++) {
+        ca[r] = ~(u32) (gav[r] >> 31); cb[r] = ~(u32) (gbv[r] >> 31);
+        asm ("" : "+v" (ca[r])); asm ("" : "+v" (cb[r]));   // (words from here on: told that they are sign masks, the compiler turns every use below into a compare and a select)
+      }
+      #pragma unroll
+      for (int r = 0; r < 4; r++)
+        #pragma unroll
+        for (int q = 0; q < 4; q++) {                   // (masks, no branch: the sixteen pairs stay one straight run of instructions)
+          const u32 c = ca[r] & cb[q];                  // all ones where both are called
+          nb[r][q] -= (int) c;
+          same[r][q] += gav[r] == gbv[q] ? 1 : 0;       // (a missing cell equals nothing in the other tile)
+          const u32 x = ((u32) lav[r] & c) | ((u32) lbv[q] & ~c);   // b's own length where the pair does not count: a difference of 0
+          ld32[r][q] = __usad (x, (u32) lbv[q], ld32[r][q]);   // (lengths are 0 .. 2^31 - 1)
+        }
+      if (++since == flush_every) {
+        since = 0;
+        #pragma unroll
+        for (int r = 0; r < 4; r++)
+          #pragma unroll
+          for (int q = 0; q < 4; q++) { ld[r][q] += ld32[r][q]; ld32[r][q] = 0u; }
+      }
+    }
+    #pragma unroll
+    for (int r = 0; r < 4; r++)
+      #pragma unroll
+      for (int q = 0; q < 4; q++) { ld[r][q] += ld32[r][q]; ld32[r][q] = 0u; }
+    __syncthreads ();
+  }
+  const bool mirror = ti != tj;                         // (a diagonal tile holds both halves itself)
+  // where the sites are split, the whole tile goes to this workgroup's place in scratch: [slice][tile pair][E * E]
+  SampleDistance *const mine = partial ? partial + ((long) blockIdx.y * gridDim.x + blockIdx.x) * (E * E) : nullptr;
+  if constexpr (Z == 1) {
+    #pragma unroll
+    for (int r = 0; r < 4; r++)
+      #pragma unroll
+      for (int q = 0; q < 4; q++) {
+        const SampleDistance o = {nb[r][q], nb[r][q] - same[r][q], (long long) ld[r][q]};
+        if (mine) mine[(4 * ty + r) * E + 4 * tx + q] = o;
+        else sdist_emit (out, ns, a0 + 4 * ty + r, b0 + 4 * tx + q, mirror, o);
+      }
+  }
+  else {                                                // the thread groups' sums meet in the staging area (the loop's last barrier is behind every read of it)
+    int *const acc_nb = lds, *const acc_nd = lds + E * E;
+    u64 *const acc_ld = (u64 *) (lds + 2 * E * E);
+    for (int x = tid; x < E * E; x += 256) { acc_nb[x] = 0; acc_nd[x] = 0; acc_ld[x] = 0ull; }
+    __syncthreads ();
+    #pragma unroll
+    for (int r = 0; r < 4; r++)
+      #pragma unroll
+      for (int q = 0; q < 4; q++) {
+        const int x = (4 * ty + r) * E + 4 * tx + q;
+        if (nb[r][q]) atomicAdd (acc_nb + x, nb[r][q]);
+        if (nb[r][q] - same[r][q]) atomicAdd (acc_nd + x, nb[r][q] - same[r][q]);
+        if (ld[r][q]) atomicAdd (acc_ld + x, ld[r][q]);
+      }
+    __syncthreads ();
+    for (int x = tid; x < E * E; x += 256) {
+      const SampleDistance o = {acc_nb[x], acc_nd[x], (long long) acc_ld[x]};
+      if (mine) mine[x] = o;
+      else sdist_emit (out, ns, a0 + x / E, b0 + x % E, mirror, o);
+    }
+  }
+}
+
+// the slices' tiles summed: R lanes per cell of a tile pair (a power of two up to 16), lane l takes slices l, l + R, ...; the
+// lanes' sums meet in shuffles (integer sums: the order does not show)
+__global__ __launch_bounds__ (256)
+void sample_distances_reduce_kernel (const SampleDistance *__restrict__ partial, int n_slices, int n_tiles, int E, int R, int ns, SampleDistance *__restrict__ out,
+                                     const int *__restrict__ err)
+{
+  if (*(volatile const int *) err != 0) return;
+  const long cells = (long) n_tiles * (n_tiles + 1) / 2 * (E * E);
+  const long n_threads = (long) gridDim.x * blockDim.x;   // (a multiple of R: the lanes of a cell stay together)
+  const int l = threadIdx.x & (R - 1);
+  for (long t = blockIdx.x * (long) blockDim.x + threadIdx.x; t < cells * R; t += n_threads) {   // (cells * R is a multiple of 64: a wavefront leaves the loop as one)
+    const long x = t / R;
+    int n_both = 0, n_differ = 0;
+    u64 length_diff = 0;
+    for (int s = l; s < n_slices; s += R) {
+      const SampleDistance q = partial[s * cells + x];
+      n_both += q.n_both; n_differ += q.n_differ; length_diff += (u64) q.length_diff;
+    }
+    for (int o = R >> 1; o; o >>= 1) {
+      n_both += __shfl_xor (n_both, o, R); n_differ += __shfl_xor (n_differ, o, R); length_diff += shfl_xor64 (length_diff, o, R);
+    }
+    if (l == 0) {
+      const int w = (int) (x % (E * E));
+      int ti, tj;
+      sdist_tile_pair ((int) (x / (E * E)), n_tiles, ti, tj);
+      const SampleDistance o = {n_both, n_differ, (long long) length_diff};
+      sdist_emit (out, ns, ti * E + w / E, tj * E + w % E, ti != tj, o);
+    }
+  }
+}
+
+extern "C" long tjamd_sample_distances (tjamd_counter *c, const tjamd_site *d_sites, long n_sites, const tjamd_allele *d_alleles, long n_alleles,
+                                        const int16_t *d_genotype, int n_samples, tjamd_sample_distance *d_out)
+{
+  static const char *fn = "tjamd_sample_distances";
+  if (!c) return -set_err (TJAMD_ERR_ARG, "%s: null counter", fn);
+  if (!d_out) return -set_err (TJAMD_ERR_ARG, "%s: null d_out", fn);
+  if (n_sites < 0 || n_alleles < 0) return -set_err (TJAMD_ERR_ARG, "%s: n_sites %ld, n_alleles %ld: a count below 0", fn, n_sites, n_alleles);
+  if ((n_sites > 0 && (!d_sites || !d_genotype)) || (n_alleles > 0 && !d_alleles)) return -set_err (TJAMD_ERR_ARG, "%s: null site, allele or genotype buffer", fn);
+  if (n_samples < 1 || n_samples > 4096) return -set_err (TJAMD_ERR_ARG, "%s: n_samples %d outside 1..4096", fn, n_samples);
+  if (n_alleles < n_sites) return -set_err (TJAMD_ERR_ARG, "%s: %ld alleles for %ld sites (a site has at least one)", fn, n_alleles, n_sites);
+  if (n_alleles >= (1l << 31)) return -set_err (TJAMD_ERR_ARG, "%s: %ld alleles: 2^31 or more", fn, n_alleles);
+  if (n_sites * (long) n_samples >= (1l << 31)) return -set_err (TJAMD_ERR_ARG, "%s: %ld sites x %d samples: 2^31 cells or more", fn, n_sites, n_samples);
+  if (tjamd_device_count () <= 0) return -set_err (TJAMD_ERR_NO_DEVICE, "%s: TJAMD_ERR_NO_DEVICE: no HIP device visible (the distances are summed on the device; no CPU fallback)", fn);
+  Stage st (c, T_SAMPLE_DISTANCES);                     // (a refused call leaves no timing behind)
+  if (hipSetDevice (c->device) != hipSuccess) return -set_err (TJAMD_ERR_HIP, "hipSetDevice failed");
+  const long n_out = (long) n_samples * n_samples;
+  int rc;
+  if (n_sites == 0) {                                   // no site: every pair has nothing in common
+    if (hipMemsetAsync (d_out, 0, (size_t) n_out * sizeof (SampleDistance), c->stream) != hipSuccess) return -set_err (TJAMD_ERR_HIP, "%s: memset failed", fn);
+    rc = read_back (c, fn, nullptr, nullptr, 0);
+    return rc ? -rc : 0;
+  }
+  // the decomposition: tiles of E x E pairs on or above the diagonal, E = 64 where that alone gives half the workgroups aimed at
+  // (four per CU), otherwise 32, and 16 or 8 where the samples are no more; the sites in slices of whole chunks, as many as bring
+  // the workgroups to that number (few samples: many slices, their tiles summed from scratch; many samples: one, stored at once).
+  // The scratch is one tile per workgroup: it is bounded by the workgroups aimed at, not by S^2 x slices (16 MB at most: 1024
+  // tiles of edge 32); and the lengths of the check pass, an int per genotype cell: twice the matrix, 2 GB at 125 000 sites x
+  // 4096 samples, under 8 GB at the 2^31 cells accepted.  They are ints because ref_length is one (runs of the test genomes pass
+  // 1500, the tests go to 2^31 - 1); an int16 copy for inputs whose lengths all fit would halve that and take a third off what a
+  // tile stages, behind a reduction over the sites ahead of the launch and four more instances of the tile kernel: not built.
+  const long want = c->dist_blocks ? c->dist_blocks : 4l * c->n_cu;
+  const long n_tiles64 = (n_samples + 63) / 64;
+  const int E = n_samples <= 8 ? 8 : n_samples <= 16 ? 16 : n_tiles64 * (n_tiles64 + 1) / 2 >= (want + 1) / 2 ? 64 : 32;
+  const int n_tiles = (n_samples + E - 1) / E;
+  const long n_pairs = (long) n_tiles * (n_tiles + 1) / 2, chunk = SDIST_CELLS / E, n_chunks = (n_sites + chunk - 1) / chunk;
+  long n_slices = std::max (1l, std::min (n_chunks, want / n_pairs));
+  const long per_slice = (n_chunks + n_slices - 1) / n_slices * chunk;
+  n_slices = (n_sites + per_slice - 1) / per_slice;
+  ScratchCut cut;
+  int *err, *lens; SampleDistance *partial;
+  cut.take (err, 64); cut.take (lens, (size_t) (n_sites * n_samples)); cut.take (partial, n_slices > 1 ? (size_t) (n_slices * n_pairs) * E * E : 0);
+  rc = cut.commit (c);
+  if (rc) return -rc;
+  if (n_slices == 1) partial = nullptr;
+  if (hipMemsetAsync (err, 0, 256, c->stream) != hipSuccess) return -set_err (TJAMD_ERR_HIP, "%s: memset failed", fn);
+  const Site *sites = (const Site *) d_sites;
+  const Allele *alleles = (const Allele *) d_alleles;
+  SampleDistance *out = (SampleDistance *) d_out;
+  const long check_items = std::max (n_sites * n_samples, n_alleles);
+  st.begin ();
+  hipLaunchKernelGGL (sample_distances_check_kernel, dim3 ((unsigned) std::min ((check_items + 255) / 256, 8l * c->n_cu)), dim3 (256), 0, c->stream,
+                      sites, n_sites, alleles, n_alleles, d_genotype, n_samples, lens, err);
+  auto launch = [&] (auto kernel) {
+    hipLaunchKernelGGL (kernel, dim3 ((unsigned) n_pairs, (unsigned) n_slices), dim3 (256), 0, c->stream, d_genotype, (const int *) lens, n_sites, n_samples,
+                        n_tiles, per_slice, partial, out, (const int *) err);
+  };
+  if (E == 8) launch (sample_distances_kernel<8>);
+  else if (E == 16) launch (sample_distances_kernel<16>);
+  else if (E == 32) launch (sample_distances_kernel<32>);
+  else launch (sample_distances_kernel<64>);
+  if (partial) {
+    int R = 1;                                          // lanes per cell: as many as there are slices, 16 at most
+    while (R < 16 && R < n_slices) R <<= 1;
+    hipLaunchKernelGGL (sample_distances_reduce_kernel, dim3 ((unsigned) std::min ((n_pairs * E * E * R + 255) / 256, 8l * c->n_cu)), dim3 (256), 0, c->stream,
+                        (const SampleDistance *) partial, (int) n_slices, n_tiles, E, R, n_samples, out, (const int *) err);
+  }
+  st.end ();
+  u32 h_err = 0;
+  rc = read_back (c, fn, err, &h_err, 1);
+  if (rc) return -rc;
+  if (h_err & 16u) return -set_err (TJAMD_ERR_ARG, "%s: a site has n_alleles < 1", fn);
+  if (h_err & 8u) return -set_err (TJAMD_ERR_ARG, "%s: first_allele and n_alleles of the sites do not chain from 0 to %ld", fn, n_alleles);
+  if (h_err & 32u) return -set_err (TJAMD_ERR_ARG, "%s: an allele's site is not the site that holds it", fn);
+  if (h_err & 64u) return -set_err (TJAMD_ERR_ARG, "%s: an allele's alt_length is outside 0..1023", fn);
+  if (h_err & 128u) return -set_err (TJAMD_ERR_ARG, "%s: a site's ref_length is below 0", fn);
+  if (h_err & 1u) return -set_err (TJAMD_ERR_ARG, "%s: a genotype cell is below -1 or above its site's n_alleles", fn);
+  st.done ();
+  return n_sites;
+}
+extern "C" double tjamd_last_sample_distances_ms (tjamd_counter *c) { return c ? c->timer[T_SAMPLE_DISTANCES].ms (c->device) : -1.0; }
