@@ -11,6 +11,9 @@
  *   DIR/sample_distances.tsv  with -M: tjamd_sample_distances on the genotype matrix the run has (that of the depths with -D, that of
  *                             the merge without, where samples that equal the reference count as not called), one row per pair
  *                             of samples a <= b: sample_a  sample_b  n_both  n_differ  length_diff
+ *   DIR/sample_linkage.tsv    with -C T (which implies -M): tjamd_sample_linkage on that matrix, by n_differ over the pairs with at
+ *                             least one site in common; one line per link, in the order single linkage merges: sample_a  sample_b  key
+ *   DIR/sample_clusters.tsv   with -C T: tjamd_linkage_clusters at threshold T, one line per sample: sample  cluster
  *   DIR/unique_variants.vcf   with -u: the tutorial's concatenation, one row per distinct allele in N8's own form (the record
  *                             d_unique holds), one column all_samples
  *   DIR/variant_effects.tsv   with -e annotation.gff3: tjamd_variant_effects on d_unique only, one line per allele: variant_effects.c's
@@ -18,11 +21,11 @@
  * The other options are sample_vcfs.c's.
  *
  *   gcc -O2 -I include examples/merged_vcf.c -L tatajuba_amd -ltatajuba_amd -Wl,-rpath,$PWD/tatajuba_amd -o merged_vcf
- *   ./merged_vcf -r reference.fa [-u] [-D] [-M] [-e annotation.gff3] [-x 1] [-g G] [-s 3] [-k 10] [-m 3] [-c 5] [-d 1] [-l -1] [-o .] sample1.fastq[.gz] ...   */
+ *   ./merged_vcf -r reference.fa [-u] [-D] [-M] [-C T] [-e annotation.gff3] [-x 1] [-g G] [-s 3] [-k 10] [-m 3] [-c 5] [-d 1] [-l -1] [-o .] sample1.fastq[.gz] ...   */
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
-#include <tatajuba_distances.h>
+#include <tatajuba_linkage.h>
 #include <tatajuba_effects.h>
 #include <tatajuba_locate.h>
 
@@ -80,7 +83,11 @@ main (int argc, char **argv)
   static const char *class_name[5] = {"NONE", "BOUNDARY", "IDENTICAL", "INFRAME", "FRAMESHIFT"};
   long counts[MAX_SAMPLES], total, n_union, n_grouped, n_tracts, n_located, n_gapped = 0, n_var = 0, n_rec, i, cap, ref_bytes, n_contigs = 0, n_names = 0, name_bytes;
   long offsets[MAX_SAMPLES + 1], *contig_len, var_cap, n_sites, n_alleles = 0, s, text_cap = 0;
-  int with_unique = 0, with_depths = 0, with_distances = 0;
+  int with_unique = 0, with_depths = 0, with_distances = 0, with_clusters = 0;
+  long long cut = 0;
+  long n_links = 0, n_clusters = 0;
+  tjamd_link *h_links = NULL;
+  int *h_cluster = NULL;
   int n = 0, k = 10, m = 3, cov = 5, maxd = 1, lev = -1, mism = 1, max_edits = -1, max_shift = TJAMD_MAX_SHIFT, coverage[MAX_SAMPLES], a, ndev = tjamd_device_count (), status;
   const void *d_records = NULL;
   void *d_keys, *d_counts, *d_ids, *d_grouped, *d_loc, *d_perm, *d_pkeys, *d_pcounts, *d_tracts, *d_tloc, *d_reflen, *d_summary, *d_var, *d_variants, *d_sites, *d_alleles, *d_genotype, *d_unique,
@@ -113,9 +120,10 @@ main (int argc, char **argv)
     else if (!strcmp (argv[a], "-u")) with_unique = 1;
     else if (!strcmp (argv[a], "-D")) with_depths = 1;
     else if (!strcmp (argv[a], "-M")) with_distances = 1;
+    else if (!strcmp (argv[a], "-C") && a + 1 < argc) { cut = atoll (argv[++a]); with_clusters = with_distances = 1; }
     else if (n < MAX_SAMPLES) files[n++] = argv[a];
   }
-  if (n < 1 || !reference) { fprintf (stderr, "usage: %s -r reference.fa [-u] [-D] [-M] [-e annotation.gff3] [-x X] [-g G] [-s S] [-k K] [-m M] [-c C] [-d D] [-l L] [-o DIR] sample.fastq[.gz] ...\n", argv[0]); return 2; }
+  if (n < 1 || !reference) { fprintf (stderr, "usage: %s -r reference.fa [-u] [-D] [-M] [-C T] [-e annotation.gff3] [-x X] [-g G] [-s S] [-k K] [-m M] [-c C] [-d D] [-l L] [-o DIR] sample.fastq[.gz] ...\n", argv[0]); return 2; }
   if (ndev < 1) { fprintf (stderr, "tatajuba_amd error: no HIP device is visible (there is no CPU fallback)\n"); return 1; }
   if (maxd < 0) maxd = 0;                                 /* src/main.c:190-192 */
   if (maxd > k / 2) maxd = k / 2;
@@ -228,6 +236,18 @@ main (int argc, char **argv)
                                 (tjamd_sample_distance *) d_dist) < 0) return fail ("sample distances");
     h_dist = (tjamd_sample_distance *) malloc ((size_t) n * (size_t) n * sizeof (tjamd_sample_distance));
     if (tjamd_device_download (ctr[0], h_dist, d_dist, (size_t) n * (size_t) n * sizeof (tjamd_sample_distance))) return fail ("download");
+    if (with_clusters) {                                  /* the tree of the samples from the matrix where it is, and its cut at T */
+      void *d_links = tjamd_device_alloc (ctr[0], (size_t) n * sizeof (tjamd_link)), *d_cluster = tjamd_device_alloc (ctr[0], (size_t) n * sizeof (int));
+      n_links = tjamd_sample_linkage (ctr[0], (const tjamd_sample_distance *) d_dist, n, TJAMD_LINK_DIFFER, 1, (tjamd_link *) d_links);
+      if (n_links < 0) return fail ("sample linkage");
+      n_clusters = tjamd_linkage_clusters (ctr[0], (const tjamd_link *) d_links, n_links, n, cut, (int *) d_cluster);
+      if (n_clusters < 0) return fail ("linkage clusters");
+      h_links = (tjamd_link *) malloc ((size_t) n * sizeof (tjamd_link));
+      h_cluster = (int *) malloc ((size_t) n * sizeof (int));
+      if (tjamd_device_download (ctr[0], h_links, d_links, (size_t) n_links * sizeof (tjamd_link)) ||
+          tjamd_device_download (ctr[0], h_cluster, d_cluster, (size_t) n * sizeof (int))) return fail ("download");
+      tjamd_device_free (ctr[0], d_links); tjamd_device_free (ctr[0], d_cluster);
+    }
     tjamd_device_free (ctr[0], d_dist);
   }
   h_sites = (tjamd_site *) malloc ((size_t) (n_sites ? n_sites : 1) * sizeof (tjamd_site));
@@ -307,6 +327,16 @@ main (int argc, char **argv)
     }
     fclose (fout);
     free (h_dist);
+  }
+  if (with_clusters) {
+    if (!(fout = open_output (outdir, "sample_linkage.tsv"))) return 1;
+    for (i = 0; i < n_links; i++) fprintf (fout, "%s\t%s\t%lld\n", sample_name[h_links[i].a], sample_name[h_links[i].b], h_links[i].key);
+    fclose (fout);
+    if (!(fout = open_output (outdir, "sample_clusters.tsv"))) return 1;
+    for (a = 0; a < n; a++) fprintf (fout, "%s\t%d\n", sample_name[a], h_cluster[a]);
+    fclose (fout);
+    printf ("%ld links, %ld clusters at %lld\n", n_links, n_clusters, cut);
+    free (h_links); free (h_cluster);
   }
 
   if (with_unique) {                                      /* every distinct event once, as N8 wrote it for the first sample that has it */

@@ -401,6 +401,10 @@ long tjamd_located_tracts (tjamd_counter *c, const void *d_keys, const void *d_c
 /* The pairwise distances of the samples over the merged sites (N14: tjamd_sample_distances) are declared, with their timer,
  * in tatajuba_distances.h, which includes tatajuba_depths.h and through it this header. */
 
+/* The single-linkage tree of the samples over that matrix and its clusters at a threshold (N15: tjamd_sample_linkage,
+ * tjamd_linkage_clusters) are declared, with their timers, in tatajuba_linkage.h, which includes tatajuba_distances.h and
+ * through it this header. */
+
 /* release the calling thread's shared device contexts of the synchronous string scans (update_hopo_counter_from_seq on a
  * counter that never read a file, tjamd_scan_windows) now; they are released by themselves when the thread ends */
 void tjamd_thread_cleanup (void);

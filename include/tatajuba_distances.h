@@ -47,7 +47,8 @@ extern "C" {
  *   (2 GB at 125 000 sites x 4096 samples, under 8 GB at the limit of 2^31 cells); and, only where the sites are split, one
  *   tile of 16-byte sums per workgroup, 16 MB at most on 256 compute units.  Nothing grows with n_samples^2 x slices.  The
  *   lengths are ints and not int16 because ref_length is one.  A call whose scratch cannot be had returns TJAMD_ERR_HIP.
- * Not built: a site list or mask; weights; a tree or a clustering; any distance on read depths. */
+ * Not built: a site list or mask; weights; any distance on read depths.  A tree and a clustering are not built here: the
+ *   single-linkage ones are the next step, tatajuba_linkage.h. */
 typedef struct { int n_both, n_differ; long long length_diff; } tjamd_sample_distance;   /* 16 bytes */
 
 long tjamd_sample_distances (tjamd_counter *c,

@@ -11,4 +11,5 @@ from .capi import (Counter, Comm, Reference, Annotation, REF_ENTRY_DTYPE, LOCATI
                    Coding, CDS_DTYPE, EFFECT_DTYPE, EFFECT_CLASSES, EFFECT_EXPORTS, translate, read_gff3_phase,
                    SITE_DTYPE, ALLELE_DTYPE, SITE_EXPORTS, site_ref_alt,
                    SITE_DEPTH_DTYPE, DEPTH_EXPORTS,
-                   SAMPLE_DISTANCE_DTYPE, DISTANCE_EXPORTS)
+                   SAMPLE_DISTANCE_DTYPE, DISTANCE_EXPORTS,
+                   LINK_DTYPE, LINK_DIFFER, LINK_LENGTH, LINK_DIFFER_RATE, LINKAGE_EXPORTS)

@@ -71,6 +71,9 @@ SITE_DEPTH_DTYPE = np.dtype([("n_ref", "<i4"), ("n_missing", "<i4"), ("depth", "
 assert SITE_DEPTH_DTYPE.itemsize == 16
 SAMPLE_DISTANCE_DTYPE = np.dtype([("n_both", "<i4"), ("n_differ", "<i4"), ("length_diff", "<i8")])      # tjamd_sample_distance (include/tatajuba_distances.h)
 assert SAMPLE_DISTANCE_DTYPE.itemsize == 16
+LINK_DTYPE = np.dtype([("a", "<i4"), ("b", "<i4"), ("key", "<i8")])      # tjamd_link (include/tatajuba_linkage.h)
+assert LINK_DTYPE.itemsize == 16
+LINK_DIFFER, LINK_LENGTH, LINK_DIFFER_RATE = 0, 1, 2                     # TJAMD_LINK_*: the metric of tjamd_sample_linkage
 
 
 class TatajubaAmdError(RuntimeError):
@@ -166,6 +169,8 @@ SITE_EXPORTS = ["tjamd_merge_variants", "tjamd_site_ref_alt", "tjamd_last_merge_
 DEPTH_EXPORTS = ["tjamd_site_depths", "tjamd_last_site_depths_ms"]
 # ... and include/tatajuba_distances.h
 DISTANCE_EXPORTS = ["tjamd_sample_distances", "tjamd_last_sample_distances_ms"]
+# ... and include/tatajuba_linkage.h
+LINKAGE_EXPORTS = ["tjamd_sample_linkage", "tjamd_linkage_clusters", "tjamd_last_sample_linkage_ms", "tjamd_last_linkage_clusters_ms"]
 MAX_SHIFT = 3                     # TJAMD_MAX_SHIFT
 
 
@@ -329,6 +334,12 @@ def lib():
     L.tjamd_sample_distances.restype = C.c_long
     L.tjamd_sample_distances.argtypes = [C.c_void_p, C.c_void_p, C.c_long, C.c_void_p, C.c_long, C.c_void_p, C.c_int, C.c_void_p]
     L.tjamd_last_sample_distances_ms.restype = C.c_double; L.tjamd_last_sample_distances_ms.argtypes = [C.c_void_p]
+    L.tjamd_sample_linkage.restype = C.c_long
+    L.tjamd_sample_linkage.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]
+    L.tjamd_linkage_clusters.restype = C.c_long
+    L.tjamd_linkage_clusters.argtypes = [C.c_void_p, C.c_void_p, C.c_long, C.c_int, C.c_longlong, C.c_void_p]
+    L.tjamd_last_sample_linkage_ms.restype = C.c_double; L.tjamd_last_sample_linkage_ms.argtypes = [C.c_void_p]
+    L.tjamd_last_linkage_clusters_ms.restype = C.c_double; L.tjamd_last_linkage_clusters_ms.argtypes = [C.c_void_p]
     L.tjamd_group_contexts.restype = C.c_long
     L.tjamd_group_contexts.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_long]
     L.new_genomic_context_list.restype = C.POINTER(GenomicContextListStruct); L.new_genomic_context_list.argtypes = [P]
@@ -929,6 +940,23 @@ class Counter:
 
     def last_sample_distances_ms(self):
         return lib().tjamd_last_sample_distances_ms(self._h)
+
+    def sample_linkage(self, d_dist, n_samples, metric, min_both, d_links):
+        """tjamd_sample_linkage on device pointers: the [sample][sample] matrix of tjamd_sample_distances -> the single-linkage
+        tree of the samples under the metric (LINK_DIFFER, LINK_LENGTH, LINK_DIFFER_RATE) over the pairs with n_both >= min_both,
+        one LINK_DTYPE record per merge at d_links, ascending in (key, a, b).  -> n_links"""
+        return self._chkn(lib().tjamd_sample_linkage(self._h, d_dist, n_samples, metric, min_both, d_links))
+
+    def linkage_clusters(self, d_links, n_links, n_samples, threshold, d_cluster):
+        """tjamd_linkage_clusters on device pointers: the links with key <= threshold -> a dense cluster id per sample at
+        d_cluster (int32), clusters numbered in the order of their smallest member.  -> n_clusters"""
+        return self._chkn(lib().tjamd_linkage_clusters(self._h, d_links, n_links, n_samples, threshold, d_cluster))
+
+    def last_sample_linkage_ms(self):
+        return lib().tjamd_last_sample_linkage_ms(self._h)
+
+    def last_linkage_clusters_ms(self):
+        return lib().tjamd_last_linkage_clusters_ms(self._h)
 
     def uses_log(self):
         lib().tjamd_counter_uses_log.restype = C.c_int

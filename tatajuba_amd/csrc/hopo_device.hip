@@ -44,6 +44,7 @@
 #include "../../include/tatajuba_sites.h"
 #include "../../include/tatajuba_depths.h"
 #include "../../include/tatajuba_distances.h"
+#include "../../include/tatajuba_linkage.h"
 #include "../../include/tatajuba_locate.h"
 
 typedef unsigned long long u64;
@@ -3874,7 +3875,7 @@ struct StageTimer
 };
 // the intervals of a counter: the last scan call (its partition kernels between the pieces included: tjamd_last_scan_ms takes
 // them out), finalise, the kernels of tjamd_merge_samples, tjamd_tract_stats, tjamd_union_tracts, tjamd_union_tract_stats
-enum { T_SCAN, T_FIN, T_MERGE, T_TRACT, T_UNION, T_UNION_STATS, T_REF, T_LOCATE, T_LOCATED_TRACTS, T_VARIANTS, T_ANNOTATION, T_TRACT_FEATURES, T_SEED_ORDER, T_LOCATE_GAPPED, T_CODING, T_VARIANT_EFFECTS, T_MERGE_VARIANTS, T_SITE_DEPTHS, T_SAMPLE_DISTANCES, TJ_N_TIMERS };   // (T_REF to T_LOCATED_TRACTS: N7, T_VARIANTS: N8, the next two: N9; then two of N10; two of N11; then N12, N13 and N14, end of the file)
+enum { T_SCAN, T_FIN, T_MERGE, T_TRACT, T_UNION, T_UNION_STATS, T_REF, T_LOCATE, T_LOCATED_TRACTS, T_VARIANTS, T_ANNOTATION, T_TRACT_FEATURES, T_SEED_ORDER, T_LOCATE_GAPPED, T_CODING, T_VARIANT_EFFECTS, T_MERGE_VARIANTS, T_SITE_DEPTHS, T_SAMPLE_DISTANCES, T_SAMPLE_LINKAGE, T_LINKAGE_CLUSTERS, TJ_N_TIMERS };   // (T_REF to T_LOCATED_TRACTS: N7, T_VARIANTS: N8, the next two: N9; then two of N10; two of N11; then N12, N13, N14 and the two of N15, end of the file)
 
 struct tjamd_counter
 {
@@ -3930,6 +3931,7 @@ struct tjamd_counter
   size_t piece_target = TJ_SCAN_PIECE_TARGET;           // TATAJUBA_AMD_SCAN_PIECE (bytes) overrides it: tests
   int scan_grid_cap = 0;                                // TATAJUBA_AMD_SCAN_GRID (tests): n >= 1 caps the workgroups of the scan and log-partition launches; 0: no cap
   int dist_blocks = 0;                                  // TATAJUBA_AMD_DISTANCE_BLOCKS (tests): the workgroups tjamd_sample_distances splits its sites for; 0: four per CU
+  int link_small = 1;                                   // TATAJUBA_AMD_LINKAGE_SMALL (tests): 0: tjamd_sample_linkage never takes its single-workgroup path (64 samples and fewer)
   bool buckets_clean = false;
   long plan_mismatches = 0;   // finalises whose in-kernel reading of the kept count differed from the kernel boundary's (expected: 0)
   bool ctr_clean = false;     // the scan counters are zero but for n_undefined (clear_buckets_kernel did it, no scan since)
@@ -4025,6 +4027,8 @@ extern "C" tjamd_counter *tjamd_counter_create (int device, int kmer_size)
   if (sg && atoi (sg) >= 1) c->scan_grid_cap = atoi (sg);
   const char *db = getenv ("TATAJUBA_AMD_DISTANCE_BLOCKS");   // test hook: tjamd_sample_distances aims at n workgroups when it splits the sites (1: never splits)
   if (db && atoi (db) >= 1) c->dist_blocks = atoi (db);
+  const char *ls = getenv ("TATAJUBA_AMD_LINKAGE_SMALL");    // test hook: 0 sends every tjamd_sample_linkage through the key pass, the rounds and the sort kernel
+  if (ls && !strcmp (ls, "0")) c->link_small = 0;
   const char *sl = getenv ("TATAJUBA_AMD_BUCKET_SLACK");
   if (sl && atof (sl) >= 1.0) c->slack = atof (sl);
   HIPCHK_NULL (hipStreamCreateWithFlags (&c->own_stream, hipStreamNonBlocking));
@@ -8993,3 +8997,409 @@ extern "C" long tjamd_sample_distances (tjamd_counter *c, const tjamd_site *d_si
   return n_sites;
 }
 extern "C" double tjamd_last_sample_distances_ms (tjamd_counter *c) { return c ? c->timer[T_SAMPLE_DISTANCES].ms (c->device) : -1.0; }
+
+// ---- N15: the single-linkage tree of the samples and its clusters at a threshold ---------------------------------------------
+// N14's sample x sample matrix reduced to the minimum spanning forest of its pairs under the total order (key, a, b), and a list
+// of links cut at a threshold into dense cluster ids; the rule as built is in include/tatajuba_linkage.h.  Boruvka and not Prim:
+// a few passes over the matrix at memory rate, not n_samples dependent steps.
+//   1. linkage_keys_kernel: tiles of 32 x 32 cells; a workgroup reads its tile (a, b) in rows and stages the tile (b, a), read in
+//      rows as well, in LDS, so that a cell meets its mirror without a load that strides by a row.  Every cell is checked, and
+//      a u64 key per cell goes to scratch (all ones: no edge, the diagonal, the padding column that makes a row's length even),
+//      so that the rounds read 8 bytes a cell and not 16.  Raises the error flag; writes nothing of the caller's.
+//   2. ceil (log2 n_samples) rounds of two kernels, launched without a look at the device in between:
+//      (a) linkage_rowmin_kernel: a wavefront per row a takes the minimum of (key, b) over the b in another component, two keys
+//          (16 bytes) a lane and load, then six cross-lane steps.  For one a, (min (a, b), max (a, b)) ascends with b: (key, b)
+//          is the order of the rule.
+//      (b, c) linkage_merge_kernel, one workgroup with the labels in LDS: the components' minima in two phases of LDS atomics
+//          (the smallest key of a component, then the smallest packed pair among the rows that hold that key: integer minima, no
+//          order shows); every component hooks onto the other end of its edge, a mutual pick is broken by the smaller label,
+//          each chosen edge is appended once; the labels are flattened by pointer jumping.  A round with no edge at all sets
+//          the `done` word, and every later kernel of the rounds returns at once when it reads it.  Nothing waits for another
+//          workgroup.
+//   3. linkage_sort_kernel: one workgroup sorts the links by (key, a, b) in LDS (a bitonic network over 12-byte entries: the
+//      order needs 88 bits, the shared key-value sort has 64) and stores them.
+// Up to 64 samples linkage_small_kernel does the three steps as one workgroup in one launch, the key matrix in LDS.
+// linkage_clusters_kernel: one workgroup, labels in LDS; checks every link, hooks the larger label of a link at or under the
+// threshold onto the smaller by an LDS atomic minimum, jumps pointers, until a pass changes nothing; a scan over the roots gives
+// the dense ids.  DESIGN.md section 3.5, N15.
+
+struct Link { int a, b; long long key; };
+static_assert (sizeof (Link) == 16 && sizeof (Link) == sizeof (tjamd_link), "link layout");
+struct LinkRowBest { u64 key; int b, pad; };            // a row's smallest (key, b) into another component; key LINK_NONE: none
+struct LinkEdge { u64 key; u32 pair, pad; };            // a chosen edge before the sort: pair = a << 12 | b, a < b < 4096
+
+#define LINK_NONE (~0ull)
+#define LINK_TILE 32                                    // cells along an edge of a tile of the key pass
+#define LINK_MAX 4096                                   // samples: the labels of one workgroup's LDS
+// flags of a call: [0] error bits (1 a cell's values, 2 a cell and its mirror; clusters: 1 a link), [1] done (clusters: the number of clusters),
+// [2] links appended so far, [3] rounds that merged something
+
+// the checks of a cell d against the rule and against its mirror m (error bits into `bad`), and its key: LINK_NONE for no edge
+__device__ __forceinline__ u64 linkage_key (const SampleDistance &d, const SampleDistance &m, bool diagonal, int metric, int min_both, int &bad)
+{
+  if (d.n_both < 0 || d.n_differ < 0 || d.n_differ > d.n_both || d.length_diff < 0) { bad |= 1; return LINK_NONE; }
+  if (d.n_both != m.n_both || d.n_differ != m.n_differ || d.length_diff != m.length_diff) { bad |= 2; return LINK_NONE; }
+  if (diagonal || d.n_both < min_both) return LINK_NONE;
+  // (min_both >= 1: the divisor is not 0; n_differ <= n_both < 2^31: the product is below 2^63 and the quotient 2^32 at most)
+  return metric == TJAMD_LINK_DIFFER ? (u64) d.n_differ : metric == TJAMD_LINK_LENGTH ? (u64) d.length_diff : ((u64) d.n_differ << 32) / (u64) d.n_both;
+}
+
+__global__ __launch_bounds__ (256)
+void linkage_keys_kernel (const SampleDistance *__restrict__ dist, int ns, int ld, int metric, int min_both, u64 *__restrict__ keys, int *__restrict__ comp,
+                          int *__restrict__ flags)
+{
+  __shared__ __attribute__ ((aligned (16))) SampleDistance mirror[LINK_TILE * (LINK_TILE + 1)];   // (rows of 33: a column is read without bank conflicts)
+  const int tid = threadIdx.x, a0 = blockIdx.y * LINK_TILE, b0 = blockIdx.x * LINK_TILE;
+  if (blockIdx.y == 0 && tid < LINK_TILE && b0 + tid < ld) comp[b0 + tid] = b0 + tid;   // every sample its own component (ld <= the array's length)
+  #pragma unroll
+  for (int j = 0; j < LINK_TILE * LINK_TILE / 256; j++) {   // the tile (b, a), in its rows
+    const int x = tid + 256 * j, q = x / LINK_TILE, r = x % LINK_TILE, b = b0 + q, a = a0 + r;
+    if (a < ns && b < ns) mirror[q * (LINK_TILE + 1) + r] = dist[(long) b * ns + a];
+  }
+  __syncthreads ();
+  int bad = 0;
+  #pragma unroll
+  for (int j = 0; j < LINK_TILE * LINK_TILE / 256; j++) {
+    const int x = tid + 256 * j, r = x / LINK_TILE, q = x % LINK_TILE, a = a0 + r, b = b0 + q;
+    if (a >= ns || b >= ld) continue;
+    u64 key = LINK_NONE;
+    if (b < ns) key = linkage_key (dist[(long) a * ns + b], mirror[q * (LINK_TILE + 1) + r], a == b, metric, min_both, bad);
+    keys[(long) a * ld + b] = key;                      // (scratch)
+  }
+  if (bad) atomicOr (flags, bad);
+}
+
+__global__ __launch_bounds__ (256)
+void linkage_rowmin_kernel (const u64 *__restrict__ keys, int ns, int ld, const int *__restrict__ comp, LinkRowBest *__restrict__ rowbest, const int *__restrict__ flags)
+{
+  if ((((volatile const int *) flags)[0] | ((volatile const int *) flags)[1]) != 0) return;
+  const int lane = threadIdx.x & 63, a = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (a >= ns) return;                                  // (a whole wavefront)
+  const int ca = comp[a];
+  const ulonglong2 *row = (const ulonglong2 *) (keys + (long) a * ld);   // (ld is even and the matrix starts on a 256-byte boundary: 16-byte loads)
+  const int2 *comp2 = (const int2 *) comp;
+  u64 bk = LINK_NONE;
+  int bb = 0x7fffffff;
+  #pragma unroll 4
+  for (int p = lane; p < ld / 2; p += 64) {             // (a lane's b ascend: the first of equal keys stays)
+    const ulonglong2 k = row[p];
+    const int2 cb = comp2[p];
+    if (cb.x != ca && k.x < bk) { bk = k.x; bb = 2 * p; }
+    if (cb.y != ca && k.y < bk) { bk = k.y; bb = 2 * p + 1; }
+  }
+  for (int o = 32; o; o >>= 1) {
+    const u64 ok = shfl_xor64 (bk, o);
+    const int ob = __shfl_xor (bb, o);
+    if (ok < bk || (ok == bk && ob < bb)) { bk = ok; bb = ob; }
+  }
+  if (lane == 0) rowbest[a] = LinkRowBest {bk, bb, 0};
+}
+
+__global__ __launch_bounds__ (1024)
+void linkage_merge_kernel (const LinkRowBest *__restrict__ rowbest, int ns, int n_jump, int *__restrict__ comp, LinkEdge *__restrict__ edges, int *__restrict__ flags)
+{
+  __shared__ u64 cbkey[LINK_MAX];                       // per root: its component's smallest key ...
+  __shared__ u32 cbpair[LINK_MAX];                      // ... and the smallest pair among the rows that hold it
+  __shared__ unsigned short par[LINK_MAX];              // the labels while they are hooked and flattened
+  __shared__ int n_new;
+  if ((((volatile const int *) flags)[0] | ((volatile const int *) flags)[1]) != 0) return;
+  const int tid = threadIdx.x, base = flags[2];
+  u64 key[LINK_MAX / 1024];
+  int other[LINK_MAX / 1024], cv[LINK_MAX / 1024];
+  #pragma unroll
+  for (int j = 0; j < LINK_MAX / 1024; j++) {
+    const int v = tid + 1024 * j;
+    key[j] = LINK_NONE; other[j] = 0; cv[j] = 0;
+    if (v < ns) {
+      const LinkRowBest rb = rowbest[v];
+      key[j] = rb.key; other[j] = rb.b; cv[j] = comp[v];
+      cbkey[v] = LINK_NONE; cbpair[v] = ~0u; par[v] = (unsigned short) cv[j];
+    }
+  }
+  if (tid == 0) n_new = 0;
+  __syncthreads ();
+  #pragma unroll
+  for (int j = 0; j < LINK_MAX / 1024; j++)
+    if (key[j] != LINK_NONE) atomicMin (&cbkey[cv[j]], key[j]);
+  __syncthreads ();
+  #pragma unroll
+  for (int j = 0; j < LINK_MAX / 1024; j++) {
+    const int v = tid + 1024 * j;
+    if (key[j] != LINK_NONE && key[j] == cbkey[cv[j]]) atomicMin (&cbpair[cv[j]], (u32) min (v, other[j]) << 12 | (u32) max (v, other[j]));
+  }
+  __syncthreads ();
+  #pragma unroll
+  for (int j = 0; j < LINK_MAX / 1024; j++) {
+    const int v = tid + 1024 * j;
+    if (v < ns && cv[j] == v && cbkey[v] != LINK_NONE) {   // a root with an edge: one end of it is in v's component, t is the other end's
+      const u32 pair = cbpair[v];
+      const int lo = (int) (pair >> 12), hi = (int) (pair & 4095u), t = comp[comp[lo] == v ? hi : lo];
+      const bool mutual = cbpair[t] == pair && cbkey[t] == cbkey[v];   // (t chose the same edge: the one cycle a strict order allows)
+      if (!mutual || v > t) {
+        par[v] = (unsigned short) t;
+        edges[base + atomicAdd (&n_new, 1)] = LinkEdge {cbkey[v], pair, 0u};   // (a forest: fewer than ns edges in all)
+      }
+    }
+  }
+  __syncthreads ();
+  if (n_new == 0) { if (tid == 0) flags[1] = 1; return; }   // no component has an edge: the forest is complete
+  for (int it = 0; it < n_jump; it++) {                 // a label read while its owner replaces it is an ancestor either way
+    #pragma unroll
+    for (int j = 0; j < LINK_MAX / 1024; j++) {
+      const int v = tid + 1024 * j;
+      if (v < ns) par[v] = par[par[v]];
+    }
+    __syncthreads ();
+  }
+  #pragma unroll
+  for (int j = 0; j < LINK_MAX / 1024; j++) {
+    const int v = tid + 1024 * j;
+    if (v < ns) comp[v] = par[v];
+  }
+  if (tid == 0) { flags[2] = base + n_new; flags[3] += 1; }
+}
+
+__global__ __launch_bounds__ (1024)
+void linkage_sort_kernel (const LinkEdge *__restrict__ edges, int P, Link *__restrict__ out, const int *__restrict__ flags)
+{
+  __shared__ u64 skey[LINK_MAX];
+  __shared__ u32 spair[LINK_MAX];
+  if (((volatile const int *) flags)[0] != 0) return;
+  const int tid = threadIdx.x, n = flags[2];            // (n <= P, a power of two up to LINK_MAX)
+  for (int i = tid; i < P; i += 1024) {
+    const bool in = i < n;
+    skey[i] = in ? edges[i].key : LINK_NONE; spair[i] = in ? edges[i].pair : ~0u;
+  }
+  __syncthreads ();
+  for (int k = 2; k <= P; k <<= 1)
+    for (int j = k >> 1; j > 0; j >>= 1) {
+      for (int t = tid; t < P / 2; t += 1024) {
+        const int i = ((t & ~(j - 1)) << 1) | (t & (j - 1)), l = i | j;
+        const u64 ki = skey[i], kl = skey[l];
+        const u32 pi = spair[i], pl = spair[l];
+        const bool above = ki > kl || (ki == kl && pi > pl);
+        if (above == ((i & k) == 0)) { skey[i] = kl; skey[l] = ki; spair[i] = pl; spair[l] = pi; }
+      }
+      __syncthreads ();
+    }
+  for (int i = tid; i < n; i += 1024) out[i] = Link {(int) (spair[i] >> 12), (int) (spair[i] & 4095u), (long long) skey[i]};
+}
+
+// Up to LINK_SMALL samples the key matrix fits in LDS (32 KB) and one workgroup does steps 1 to 3 in one launch: the same
+// checks, rounds and sort, a lane per sample.  Waves take the rows in turn for the row minimum; thread v is sample v in the
+// merge.  Barriers of one workgroup, nothing else, order the steps.
+#define LINK_SMALL 64
+
+__global__ __launch_bounds__ (256)
+void linkage_small_kernel (const SampleDistance *__restrict__ dist, int ns, int metric, int min_both, int n_rounds, Link *__restrict__ out, int *__restrict__ flags)
+{
+  __shared__ u64 keys[LINK_SMALL * LINK_SMALL], rowkey[LINK_SMALL], cbkey[LINK_SMALL], ekey[LINK_SMALL];
+  __shared__ u32 cbpair[LINK_SMALL], epair[LINK_SMALL];
+  __shared__ int comp[LINK_SMALL], par[LINK_SMALL], rowb[LINK_SMALL], n_new, n_links, bad_any;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, v = tid;
+  if (tid == 0) { n_links = 0; bad_any = 0; }
+  if (tid < LINK_SMALL) { comp[tid] = tid; ekey[tid] = LINK_NONE; epair[tid] = ~0u; }
+  __syncthreads ();
+  int bad = 0;
+  for (int x = tid; x < ns * ns; x += 256) {            // step 1: every cell beside its mirror (a matrix of 64 KB at most: the strided read is of no account)
+    const int a = x / ns, b = x % ns;
+    keys[a * LINK_SMALL + b] = linkage_key (dist[x], dist[b * ns + a], a == b, metric, min_both, bad);
+  }
+  if (bad) atomicOr (&bad_any, bad);
+  __syncthreads ();
+  if (bad_any) { if (tid == 0) flags[0] = bad_any; return; }   // (the whole workgroup; nothing of the caller's is written)
+  for (int r = 0; r < n_rounds; r++) {                  // step 2
+    for (int a = wave; a < ns; a += 4) {                // (a) a wavefront per row, lane b
+      u64 bk = LINK_NONE;
+      int bb = lane;
+      if (lane < ns && comp[lane] != comp[a]) bk = keys[a * LINK_SMALL + lane];
+      for (int o = 32; o; o >>= 1) {
+        const u64 ok = shfl_xor64 (bk, o);
+        const int ob = __shfl_xor (bb, o);
+        if (ok < bk || (ok == bk && ob < bb)) { bk = ok; bb = ob; }
+      }
+      if (lane == 0) { rowkey[a] = bk; rowb[a] = bb; cbkey[a] = LINK_NONE; cbpair[a] = ~0u; par[a] = comp[a]; }
+    }
+    if (tid == 0) n_new = 0;
+    __syncthreads ();
+    const bool has = v < ns && rowkey[v] != LINK_NONE;  // (b) the components' minima, in two phases
+    const int cv = v < ns ? comp[v] : 0;
+    if (has) atomicMin (&cbkey[cv], rowkey[v]);
+    __syncthreads ();
+    if (has && rowkey[v] == cbkey[cv]) atomicMin (&cbpair[cv], (u32) min (v, rowb[v]) << 12 | (u32) max (v, rowb[v]));
+    __syncthreads ();
+    if (v < ns && cv == v && cbkey[v] != LINK_NONE) {   // (c) hook and append, as linkage_merge_kernel does
+      const u32 pair = cbpair[v];
+      const int lo = (int) (pair >> 12), hi = (int) (pair & 4095u), t = comp[comp[lo] == v ? hi : lo];
+      const bool mutual = cbpair[t] == pair && cbkey[t] == cbkey[v];
+      if (!mutual || v > t) {
+        par[v] = t;
+        const int at = n_links + atomicAdd (&n_new, 1);
+        ekey[at] = cbkey[v]; epair[at] = pair;
+      }
+    }
+    __syncthreads ();
+    if (n_new == 0) break;                              // (the whole workgroup) the forest is complete
+    for (int it = 0; it < n_rounds; it++) {
+      if (v < ns) par[v] = par[par[v]];
+      __syncthreads ();
+    }
+    if (v < ns) comp[v] = par[v];
+    if (tid == 0) n_links += n_new;
+    __syncthreads ();
+  }
+  for (int k = 2; k <= LINK_SMALL; k <<= 1)             // step 3: the bitonic network over all 64 places, the empty ones last
+    for (int j = k >> 1; j > 0; j >>= 1) {
+      if (tid < LINK_SMALL / 2) {
+        const int i = ((tid & ~(j - 1)) << 1) | (tid & (j - 1)), l = i | j;
+        const u64 ki = ekey[i], kl = ekey[l];
+        const u32 pi = epair[i], pl = epair[l];
+        const bool above = ki > kl || (ki == kl && pi > pl);
+        if (above == ((i & k) == 0)) { ekey[i] = kl; ekey[l] = ki; epair[i] = pl; epair[l] = pi; }
+      }
+      __syncthreads ();
+    }
+  if (tid < n_links) out[tid] = Link {(int) (epair[tid] >> 12), (int) (epair[tid] & 4095u), (long long) ekey[tid]};
+  if (tid == 0) flags[2] = n_links;
+}
+
+extern "C" long tjamd_sample_linkage (tjamd_counter *c, const tjamd_sample_distance *d_dist, int n_samples, int metric, int min_both, tjamd_link *d_links)
+{
+  static const char *fn = "tjamd_sample_linkage";
+  if (!c) return -set_err (TJAMD_ERR_ARG, "%s: null counter", fn);
+  if (!d_dist) return -set_err (TJAMD_ERR_ARG, "%s: null d_dist", fn);
+  if (!d_links && n_samples > 1) return -set_err (TJAMD_ERR_ARG, "%s: null d_links", fn);
+  if (n_samples < 1 || n_samples > LINK_MAX) return -set_err (TJAMD_ERR_ARG, "%s: n_samples %d outside 1..4096", fn, n_samples);
+  if (metric < TJAMD_LINK_DIFFER || metric > TJAMD_LINK_DIFFER_RATE) return -set_err (TJAMD_ERR_ARG, "%s: metric %d outside 0..2", fn, metric);
+  if (min_both < 1) return -set_err (TJAMD_ERR_ARG, "%s: min_both %d below 1", fn, min_both);
+  if (tjamd_device_count () <= 0) return -set_err (TJAMD_ERR_NO_DEVICE, "%s: TJAMD_ERR_NO_DEVICE: no HIP device visible (the tree is built on the device; no CPU fallback)", fn);
+  Stage st (c, T_SAMPLE_LINKAGE);                       // (a refused call leaves no timing behind)
+  if (hipSetDevice (c->device) != hipSuccess) return -set_err (TJAMD_ERR_HIP, "hipSetDevice failed");
+  int rc;
+  if (n_samples == 1) {                                 // one sample: no pair, no kernel
+    rc = read_back (c, fn, nullptr, nullptr, 0);
+    return rc ? -rc : 0;
+  }
+  const int ld = (n_samples + 1) & ~1;                  // a row of keys: an even number of them, 16-byte loads
+  int n_rounds = 0, P = 2;
+  while ((1 << n_rounds) < n_samples) n_rounds++;       // every round at least halves the components that still have an edge
+  while (P < n_samples - 1) P <<= 1;
+  const bool small = n_samples <= LINK_SMALL && c->link_small;   // one workgroup, one launch
+  ScratchCut cut;
+  int *flags, *comp; LinkRowBest *rowbest; LinkEdge *edges; u64 *keys;
+  cut.take (flags, 64); cut.take (comp, small ? 0 : (size_t) ld + 64); cut.take (rowbest, small ? 0 : (size_t) n_samples); cut.take (edges, small ? 0 : (size_t) n_samples);
+  cut.take (keys, small ? 0 : (size_t) n_samples * ld);
+  rc = cut.commit (c);
+  if (rc) return -rc;
+  if (hipMemsetAsync (flags, 0, 256, c->stream) != hipSuccess) return -set_err (TJAMD_ERR_HIP, "%s: memset failed", fn);
+  st.begin ();
+  if (small)
+    hipLaunchKernelGGL (linkage_small_kernel, dim3 (1), dim3 (256), 0, c->stream, (const SampleDistance *) d_dist, n_samples, metric, min_both, n_rounds, (Link *) d_links, flags);
+  else {
+    hipLaunchKernelGGL (linkage_keys_kernel, dim3 ((unsigned) ((ld + LINK_TILE - 1) / LINK_TILE), (unsigned) ((n_samples + LINK_TILE - 1) / LINK_TILE)), dim3 (256), 0, c->stream,
+                        (const SampleDistance *) d_dist, n_samples, ld, metric, min_both, keys, comp, flags);
+    for (int r = 0; r < n_rounds; r++) {
+      hipLaunchKernelGGL (linkage_rowmin_kernel, dim3 ((unsigned) ((n_samples + 3) / 4)), dim3 (256), 0, c->stream, (const u64 *) keys, n_samples, ld, (const int *) comp,
+                          rowbest, (const int *) flags);
+      hipLaunchKernelGGL (linkage_merge_kernel, dim3 (1), dim3 (1024), 0, c->stream, (const LinkRowBest *) rowbest, n_samples, n_rounds, comp, edges, flags);
+    }
+    hipLaunchKernelGGL (linkage_sort_kernel, dim3 (1), dim3 (1024), 0, c->stream, (const LinkEdge *) edges, P, (Link *) d_links, (const int *) flags);
+  }
+  st.end ();
+  u32 h_flags[4] = {0, 0, 0, 0};
+  rc = read_back (c, fn, flags, h_flags, 4);
+  if (rc) return -rc;
+  if (h_flags[0] & 1u) return -set_err (TJAMD_ERR_ARG, "%s: a cell has n_both < 0, n_differ < 0, n_differ > n_both or length_diff < 0", fn);
+  if (h_flags[0] & 2u) return -set_err (TJAMD_ERR_ARG, "%s: a cell (a, b) differs from the cell (b, a)", fn);
+  st.done ();
+  return (long) h_flags[2];
+}
+extern "C" double tjamd_last_sample_linkage_ms (tjamd_counter *c) { return c ? c->timer[T_SAMPLE_LINKAGE].ms (c->device) : -1.0; }
+
+__global__ __launch_bounds__ (1024)
+void linkage_clusters_kernel (const Link *__restrict__ links, long n_links, int ns, long long threshold, int *__restrict__ cluster, int *__restrict__ flags)
+{
+  __shared__ int lab[LINK_MAX], rank[LINK_MAX], sums[2][1024];
+  volatile int *const vlab = lab;                       // (labels move under the reader: every read is a load)
+  const int tid = threadIdx.x;
+  int bad = 0;
+  for (long i = tid; i < n_links; i += 1024) {          // every link, whatever the threshold, before anything is written
+    const Link l = links[i];
+    if (l.a < 0 || l.a >= l.b || l.b >= ns || l.key < 0) bad = 1;
+  }
+  if (__syncthreads_or (bad)) { if (tid == 0) flags[0] = 1; return; }
+  for (int v = tid; v < ns; v += 1024) lab[v] = v;
+  __syncthreads ();
+  // lab[v] <= v and lab[v] is in v's component, always.  A pass that changes nothing: the two ends of every link have one label,
+  // so a component has one label, a member of it that is at most its smallest member.
+  while (threshold >= 0) {
+    int changed = 0;
+    for (long i = tid; i < n_links; i += 1024) {
+      const Link l = links[i];
+      if (l.key > threshold) continue;
+      const int la = vlab[l.a], lb = vlab[l.b];
+      if (la != lb) { atomicMin (&lab[max (la, lb)], min (la, lb)); changed = 1; }
+    }
+    if (!__syncthreads_or (changed)) break;
+    for (;;) {                                          // pointer jumping until every label is a root
+      int jumped = 0;
+      for (int v = tid; v < ns; v += 1024) {
+        const int p = vlab[v], pp = vlab[p];
+        if (pp != p) { vlab[v] = pp; jumped = 1; }
+      }
+      if (!__syncthreads_or (jumped)) break;
+    }
+  }
+  // dense ids: the roots counted in the order of their index, four consecutive samples a thread
+  int mine = 0;
+  #pragma unroll
+  for (int j = 0; j < LINK_MAX / 1024; j++) {
+    const int v = (LINK_MAX / 1024) * tid + j;
+    if (v < ns && lab[v] == v) mine++;
+  }
+  sums[0][tid] = mine;
+  __syncthreads ();
+  int s = 0;
+  for (int o = 1; o < 1024; o <<= 1, s ^= 1) {
+    sums[s ^ 1][tid] = sums[s][tid] + (tid >= o ? sums[s][tid - o] : 0);
+    __syncthreads ();
+  }
+  int at = sums[s][tid] - mine;
+  #pragma unroll
+  for (int j = 0; j < LINK_MAX / 1024; j++) {
+    const int v = (LINK_MAX / 1024) * tid + j;
+    if (v < ns && lab[v] == v) rank[v] = at++;
+  }
+  __syncthreads ();
+  for (int v = tid; v < ns; v += 1024) cluster[v] = rank[lab[v]];
+  if (tid == 0) flags[1] = sums[s][1023];
+}
+
+extern "C" long tjamd_linkage_clusters (tjamd_counter *c, const tjamd_link *d_links, long n_links, int n_samples, long long threshold, int *d_cluster)
+{
+  static const char *fn = "tjamd_linkage_clusters";
+  if (!c) return -set_err (TJAMD_ERR_ARG, "%s: null counter", fn);
+  if (!d_cluster) return -set_err (TJAMD_ERR_ARG, "%s: null d_cluster", fn);
+  if (n_links < 0 || n_links > (1l << 24)) return -set_err (TJAMD_ERR_ARG, "%s: n_links %ld outside 0..2^24", fn, n_links);
+  if (!d_links && n_links > 0) return -set_err (TJAMD_ERR_ARG, "%s: null d_links", fn);
+  if (n_samples < 1 || n_samples > LINK_MAX) return -set_err (TJAMD_ERR_ARG, "%s: n_samples %d outside 1..4096", fn, n_samples);
+  if (tjamd_device_count () <= 0) return -set_err (TJAMD_ERR_NO_DEVICE, "%s: TJAMD_ERR_NO_DEVICE: no HIP device visible (the tree is cut on the device; no CPU fallback)", fn);
+  Stage st (c, T_LINKAGE_CLUSTERS);                     // (a refused call leaves no timing behind)
+  if (hipSetDevice (c->device) != hipSuccess) return -set_err (TJAMD_ERR_HIP, "hipSetDevice failed");
+  ScratchCut cut;
+  int *flags;
+  cut.take (flags, 64);
+  int rc = cut.commit (c);
+  if (rc) return -rc;
+  if (hipMemsetAsync (flags, 0, 256, c->stream) != hipSuccess) return -set_err (TJAMD_ERR_HIP, "%s: memset failed", fn);
+  st.begin ();
+  hipLaunchKernelGGL (linkage_clusters_kernel, dim3 (1), dim3 (1024), 0, c->stream, (const Link *) d_links, n_links, n_samples, threshold, d_cluster, flags);
+  st.end ();
+  u32 h_flags[2] = {0, 0};
+  rc = read_back (c, fn, flags, h_flags, 2);
+  if (rc) return -rc;
+  if (h_flags[0]) return -set_err (TJAMD_ERR_ARG, "%s: a link has a < 0, a >= b, b >= n_samples or key < 0", fn);
+  st.done ();
+  return (long) h_flags[1];
+}
+extern "C" double tjamd_last_linkage_clusters_ms (tjamd_counter *c) { return c ? c->timer[T_LINKAGE_CLUSTERS].ms (c->device) : -1.0; }
