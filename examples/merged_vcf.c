@@ -14,6 +14,10 @@
  *   DIR/sample_linkage.tsv    with -C T (which implies -M): tjamd_sample_linkage on that matrix, by n_differ over the pairs with at
  *                             least one site in common; one line per link, in the order single linkage merges: sample_a  sample_b  key
  *   DIR/sample_clusters.tsv   with -C T: tjamd_linkage_clusters at threshold T, one line per sample: sample  cluster
+ *   DIR/cluster_sites.tsv     with -G (only together with -C T): tjamd_group_sites on that genotype matrix with the clusters as the groups and a
+ *                             min_called of 1: the sites at which every called sample of a cluster carries one genotype that no called
+ *                             sample outside it carries, one line per (site, cluster) in that order: cluster  contig  POS  REF  the
+ *                             genotype's text (REF again for genotype 0)  the cluster's called samples
  *   DIR/unique_variants.vcf   with -u: the tutorial's concatenation, one row per distinct allele in N8's own form (the record
  *                             d_unique holds), one column all_samples
  *   DIR/variant_effects.tsv   with -e annotation.gff3: tjamd_variant_effects on d_unique only, one line per allele: variant_effects.c's
@@ -21,11 +25,11 @@
  * The other options are sample_vcfs.c's.
  *
  *   gcc -O2 -I include examples/merged_vcf.c -L tatajuba_amd -ltatajuba_amd -Wl,-rpath,$PWD/tatajuba_amd -o merged_vcf
- *   ./merged_vcf -r reference.fa [-u] [-D] [-M] [-C T] [-e annotation.gff3] [-x 1] [-g G] [-s 3] [-k 10] [-m 3] [-c 5] [-d 1] [-l -1] [-o .] sample1.fastq[.gz] ...   */
+ *   ./merged_vcf -r reference.fa [-u] [-D] [-M] [-C T [-G]] [-e annotation.gff3] [-x 1] [-g G] [-s 3] [-k 10] [-m 3] [-c 5] [-d 1] [-l -1] [-o .] sample1.fastq[.gz] ...   */
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
-#include <tatajuba_linkage.h>
+#include <tatajuba_groups.h>
 #include <tatajuba_effects.h>
 #include <tatajuba_locate.h>
 
@@ -83,11 +87,12 @@ main (int argc, char **argv)
   static const char *class_name[5] = {"NONE", "BOUNDARY", "IDENTICAL", "INFRAME", "FRAMESHIFT"};
   long counts[MAX_SAMPLES], total, n_union, n_grouped, n_tracts, n_located, n_gapped = 0, n_var = 0, n_rec, i, cap, ref_bytes, n_contigs = 0, n_names = 0, name_bytes;
   long offsets[MAX_SAMPLES + 1], *contig_len, var_cap, n_sites, n_alleles = 0, s, text_cap = 0;
-  int with_unique = 0, with_depths = 0, with_distances = 0, with_clusters = 0;
+  int with_unique = 0, with_depths = 0, with_distances = 0, with_clusters = 0, with_groups = 0;
   long long cut = 0;
-  long n_links = 0, n_clusters = 0;
+  long n_links = 0, n_clusters = 0, n_marks = 0;
   tjamd_link *h_links = NULL;
   int *h_cluster = NULL;
+  tjamd_group_mark *h_marks = NULL;
   int n = 0, k = 10, m = 3, cov = 5, maxd = 1, lev = -1, mism = 1, max_edits = -1, max_shift = TJAMD_MAX_SHIFT, coverage[MAX_SAMPLES], a, ndev = tjamd_device_count (), status;
   const void *d_records = NULL;
   void *d_keys, *d_counts, *d_ids, *d_grouped, *d_loc, *d_perm, *d_pkeys, *d_pcounts, *d_tracts, *d_tloc, *d_reflen, *d_summary, *d_var, *d_variants, *d_sites, *d_alleles, *d_genotype, *d_unique,
@@ -121,9 +126,10 @@ main (int argc, char **argv)
     else if (!strcmp (argv[a], "-D")) with_depths = 1;
     else if (!strcmp (argv[a], "-M")) with_distances = 1;
     else if (!strcmp (argv[a], "-C") && a + 1 < argc) { cut = atoll (argv[++a]); with_clusters = with_distances = 1; }
+    else if (!strcmp (argv[a], "-G")) with_groups = 1;
     else if (n < MAX_SAMPLES) files[n++] = argv[a];
   }
-  if (n < 1 || !reference) { fprintf (stderr, "usage: %s -r reference.fa [-u] [-D] [-M] [-C T] [-e annotation.gff3] [-x X] [-g G] [-s S] [-k K] [-m M] [-c C] [-d D] [-l L] [-o DIR] sample.fastq[.gz] ...\n", argv[0]); return 2; }
+  if (n < 1 || !reference || (with_groups && !with_clusters)) { fprintf (stderr, "usage: %s -r reference.fa [-u] [-D] [-M] [-C T [-G]] [-e annotation.gff3] [-x X] [-g G] [-s S] [-k K] [-m M] [-c C] [-d D] [-l L] [-o DIR] sample.fastq[.gz] ...\n", argv[0]); return 2; }
   if (ndev < 1) { fprintf (stderr, "tatajuba_amd error: no HIP device is visible (there is no CPU fallback)\n"); return 1; }
   if (maxd < 0) maxd = 0;                                 /* src/main.c:190-192 */
   if (maxd > k / 2) maxd = k / 2;
@@ -246,6 +252,18 @@ main (int argc, char **argv)
       h_cluster = (int *) malloc ((size_t) n * sizeof (int));
       if (tjamd_device_download (ctr[0], h_links, d_links, (size_t) n_links * sizeof (tjamd_link)) ||
           tjamd_device_download (ctr[0], h_cluster, d_cluster, (size_t) n * sizeof (int))) return fail ("download");
+      if (with_groups) {                                  /* what sets each cluster apart: the genotypes and the labels where they are; sized first, the list is short */
+        void *d_marks;
+        long rc = tjamd_group_sites (ctr[0], (const tjamd_site *) d_sites, n_sites, (const int16_t *) d_genotype, n, (const int *) d_cluster, (int) n_clusters, 1,
+                                     NULL, NULL, NULL, NULL, 0, &n_marks);
+        if (rc < 0 && rc != -TJAMD_ERR_CAPACITY) return fail ("group sites");
+        d_marks = tjamd_device_alloc (ctr[0], (size_t) (n_marks ? n_marks : 1) * sizeof (tjamd_group_mark));
+        if (tjamd_group_sites (ctr[0], (const tjamd_site *) d_sites, n_sites, (const int16_t *) d_genotype, n, (const int *) d_cluster, (int) n_clusters, 1,
+                               NULL, NULL, NULL, (tjamd_group_mark *) d_marks, n_marks, &n_marks) < 0) return fail ("group sites");
+        h_marks = (tjamd_group_mark *) malloc ((size_t) (n_marks ? n_marks : 1) * sizeof (tjamd_group_mark));
+        if (tjamd_device_download (ctr[0], h_marks, d_marks, (size_t) n_marks * sizeof (tjamd_group_mark))) return fail ("download");
+        tjamd_device_free (ctr[0], d_marks);
+      }
       tjamd_device_free (ctr[0], d_links); tjamd_device_free (ctr[0], d_cluster);
     }
     tjamd_device_free (ctr[0], d_dist);
@@ -337,6 +355,20 @@ main (int argc, char **argv)
     fclose (fout);
     printf ("%ld links, %ld clusters at %lld\n", n_links, n_clusters, cut);
     free (h_links); free (h_cluster);
+  }
+  if (with_groups) {
+    if (!(fout = open_output (outdir, "cluster_sites.tsv"))) return 1;
+    for (i = 0; i < n_marks; i++) {
+      const tjamd_site *site = h_sites + h_marks[i].site;
+      const tjamd_allele *al = h_marks[i].genotype > 0 ? h_alleles + site->first_allele + h_marks[i].genotype - 1 : NULL;
+      if (tjamd_site_ref_alt (site, NULL, k, text, (int) text_cap + 1) < 0) { fprintf (stderr, "site %d has no text\n", h_marks[i].site); return 1; }
+      fprintf (fout, "%d\t%s\t%d\t%s\t", h_marks[i].group, contig_name[site->contig], site->pos, text);
+      if (tjamd_site_ref_alt (site, al, k, text, (int) text_cap + 1) < 0) { fprintf (stderr, "site %d has no text\n", h_marks[i].site); return 1; }
+      fprintf (fout, "%s\t%d\n", text, h_marks[i].n_called);
+    }
+    fclose (fout);
+    printf ("%ld marks of %ld clusters\n", n_marks, n_clusters);
+    free (h_marks);
   }
 
   if (with_unique) {                                      /* every distinct event once, as N8 wrote it for the first sample that has it */

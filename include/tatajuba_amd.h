@@ -405,6 +405,9 @@ long tjamd_located_tracts (tjamd_counter *c, const void *d_keys, const void *d_c
  * tjamd_linkage_clusters) are declared, with their timers, in tatajuba_linkage.h, which includes tatajuba_distances.h and
  * through it this header. */
 
+/* The sites that set a group of samples apart from the rest (N16: tjamd_group_sites) are declared, with their timer, in
+ * tatajuba_groups.h, which includes tatajuba_linkage.h and through it this header. */
+
 /* release the calling thread's shared device contexts of the synchronous string scans (update_hopo_counter_from_seq on a
  * counter that never read a file, tjamd_scan_windows) now; they are released by themselves when the thread ends */
 void tjamd_thread_cleanup (void);

@@ -74,6 +74,10 @@ assert SAMPLE_DISTANCE_DTYPE.itemsize == 16
 LINK_DTYPE = np.dtype([("a", "<i4"), ("b", "<i4"), ("key", "<i8")])      # tjamd_link (include/tatajuba_linkage.h)
 assert LINK_DTYPE.itemsize == 16
 LINK_DIFFER, LINK_LENGTH, LINK_DIFFER_RATE = 0, 1, 2                     # TJAMD_LINK_*: the metric of tjamd_sample_linkage
+GROUP_CALL_DTYPE = np.dtype([("n_called", "<i4"), ("fixed", "<i4"), ("n_outside", "<i4"), ("mark", "<i4")])            # tjamd_group_call (include/tatajuba_groups.h)
+GROUP_SITE_DTYPE = np.dtype([("n_called", "<i4"), ("n_genotypes", "<i4"), ("n_marks", "<i4"), ("first_group", "<i4")])  # tjamd_group_site
+GROUP_MARK_DTYPE = np.dtype([("site", "<i4"), ("group", "<i4"), ("genotype", "<i4"), ("n_called", "<i4")])             # tjamd_group_mark
+assert GROUP_CALL_DTYPE.itemsize == 16 and GROUP_SITE_DTYPE.itemsize == 16 and GROUP_MARK_DTYPE.itemsize == 16
 
 
 class TatajubaAmdError(RuntimeError):
@@ -171,6 +175,8 @@ DEPTH_EXPORTS = ["tjamd_site_depths", "tjamd_last_site_depths_ms"]
 DISTANCE_EXPORTS = ["tjamd_sample_distances", "tjamd_last_sample_distances_ms"]
 # ... and include/tatajuba_linkage.h
 LINKAGE_EXPORTS = ["tjamd_sample_linkage", "tjamd_linkage_clusters", "tjamd_last_sample_linkage_ms", "tjamd_last_linkage_clusters_ms"]
+# ... and include/tatajuba_groups.h
+GROUP_EXPORTS = ["tjamd_group_sites", "tjamd_last_group_sites_ms"]
 MAX_SHIFT = 3                     # TJAMD_MAX_SHIFT
 
 
@@ -340,6 +346,10 @@ def lib():
     L.tjamd_linkage_clusters.argtypes = [C.c_void_p, C.c_void_p, C.c_long, C.c_int, C.c_longlong, C.c_void_p]
     L.tjamd_last_sample_linkage_ms.restype = C.c_double; L.tjamd_last_sample_linkage_ms.argtypes = [C.c_void_p]
     L.tjamd_last_linkage_clusters_ms.restype = C.c_double; L.tjamd_last_linkage_clusters_ms.argtypes = [C.c_void_p]
+    L.tjamd_group_sites.restype = C.c_long
+    L.tjamd_group_sites.argtypes = [C.c_void_p, C.c_void_p, C.c_long, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_long,
+                                    C.POINTER(C.c_long)]
+    L.tjamd_last_group_sites_ms.restype = C.c_double; L.tjamd_last_group_sites_ms.argtypes = [C.c_void_p]
     L.tjamd_group_contexts.restype = C.c_long
     L.tjamd_group_contexts.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_long]
     L.new_genomic_context_list.restype = C.POINTER(GenomicContextListStruct); L.new_genomic_context_list.argtypes = [P]
@@ -957,6 +967,25 @@ class Counter:
 
     def last_linkage_clusters_ms(self):
         return lib().tjamd_last_linkage_clusters_ms(self._h)
+
+    def group_sites(self, d_sites, n_sites, d_genotype, n_samples, d_group, n_groups, min_called, d_calls=None, d_site_out=None, d_group_marks=None,
+                    d_marks=None, mark_capacity=0):
+        """tjamd_group_sites on device pointers: the int16 genotypes [site][sample] of n_sites SITE_DTYPE records read by the
+        group of every sample (int32 at d_group, -1: takes no part) -> optionally GROUP_CALL_DTYPE [site][group] at d_calls,
+        GROUP_SITE_DTYPE [site] at d_site_out, int32 marks per group at d_group_marks and the marked (site, group) pairs as
+        GROUP_MARK_DTYPE at d_marks.  -> the number of marks; more than mark_capacity raises, and .n_marks of the error is the
+        number to size for"""
+        n_marks = C.c_long(-1)
+        rc = lib().tjamd_group_sites(self._h, d_sites, n_sites, d_genotype, n_samples, d_group, n_groups, min_called, d_calls, d_site_out, d_group_marks,
+                                     d_marks, mark_capacity, C.byref(n_marks))
+        if rc < 0:
+            e = TatajubaAmdError(_err())
+            e.n_marks = n_marks.value
+            raise e
+        return rc
+
+    def last_group_sites_ms(self):
+        return lib().tjamd_last_group_sites_ms(self._h)
 
     def uses_log(self):
         lib().tjamd_counter_uses_log.restype = C.c_int

@@ -45,6 +45,7 @@
 #include "../../include/tatajuba_depths.h"
 #include "../../include/tatajuba_distances.h"
 #include "../../include/tatajuba_linkage.h"
+#include "../../include/tatajuba_groups.h"
 #include "../../include/tatajuba_locate.h"
 
 typedef unsigned long long u64;
@@ -3875,7 +3876,7 @@ struct StageTimer
 };
 // the intervals of a counter: the last scan call (its partition kernels between the pieces included: tjamd_last_scan_ms takes
 // them out), finalise, the kernels of tjamd_merge_samples, tjamd_tract_stats, tjamd_union_tracts, tjamd_union_tract_stats
-enum { T_SCAN, T_FIN, T_MERGE, T_TRACT, T_UNION, T_UNION_STATS, T_REF, T_LOCATE, T_LOCATED_TRACTS, T_VARIANTS, T_ANNOTATION, T_TRACT_FEATURES, T_SEED_ORDER, T_LOCATE_GAPPED, T_CODING, T_VARIANT_EFFECTS, T_MERGE_VARIANTS, T_SITE_DEPTHS, T_SAMPLE_DISTANCES, T_SAMPLE_LINKAGE, T_LINKAGE_CLUSTERS, TJ_N_TIMERS };   // (T_REF to T_LOCATED_TRACTS: N7, T_VARIANTS: N8, the next two: N9; then two of N10; two of N11; then N12, N13, N14 and the two of N15, end of the file)
+enum { T_SCAN, T_FIN, T_MERGE, T_TRACT, T_UNION, T_UNION_STATS, T_REF, T_LOCATE, T_LOCATED_TRACTS, T_VARIANTS, T_ANNOTATION, T_TRACT_FEATURES, T_SEED_ORDER, T_LOCATE_GAPPED, T_CODING, T_VARIANT_EFFECTS, T_MERGE_VARIANTS, T_SITE_DEPTHS, T_SAMPLE_DISTANCES, T_SAMPLE_LINKAGE, T_LINKAGE_CLUSTERS, T_GROUP_SITES, TJ_N_TIMERS };   // (T_REF to T_LOCATED_TRACTS: N7, T_VARIANTS: N8, the next two: N9; then two of N10; two of N11; then N12, N13, N14, the two of N15 and N16, end of the file)
 
 struct tjamd_counter
 {
@@ -3932,6 +3933,7 @@ struct tjamd_counter
   int scan_grid_cap = 0;                                // TATAJUBA_AMD_SCAN_GRID (tests): n >= 1 caps the workgroups of the scan and log-partition launches; 0: no cap
   int dist_blocks = 0;                                  // TATAJUBA_AMD_DISTANCE_BLOCKS (tests): the workgroups tjamd_sample_distances splits its sites for; 0: four per CU
   int link_small = 1;                                   // TATAJUBA_AMD_LINKAGE_SMALL (tests): 0: tjamd_sample_linkage never takes its single-workgroup path (64 samples and fewer)
+  int groups_small = 1;                                 // TATAJUBA_AMD_GROUPS_SMALL (tests): 0: tjamd_group_sites never takes its wavefront-per-site form (64 samples and fewer)
   bool buckets_clean = false;
   long plan_mismatches = 0;   // finalises whose in-kernel reading of the kept count differed from the kernel boundary's (expected: 0)
   bool ctr_clean = false;     // the scan counters are zero but for n_undefined (clear_buckets_kernel did it, no scan since)
@@ -4029,6 +4031,8 @@ extern "C" tjamd_counter *tjamd_counter_create (int device, int kmer_size)
   if (db && atoi (db) >= 1) c->dist_blocks = atoi (db);
   const char *ls = getenv ("TATAJUBA_AMD_LINKAGE_SMALL");    // test hook: 0 sends every tjamd_sample_linkage through the key pass, the rounds and the sort kernel
   if (ls && !strcmp (ls, "0")) c->link_small = 0;
+  const char *gs = getenv ("TATAJUBA_AMD_GROUPS_SMALL");     // test hook: 0 sends every tjamd_group_sites through the workgroup-per-run form with its LDS tables
+  if (gs && !strcmp (gs, "0")) c->groups_small = 0;
   const char *sl = getenv ("TATAJUBA_AMD_BUCKET_SLACK");
   if (sl && atof (sl) >= 1.0) c->slack = atof (sl);
   HIPCHK_NULL (hipStreamCreateWithFlags (&c->own_stream, hipStreamNonBlocking));
@@ -9403,3 +9407,345 @@ extern "C" long tjamd_linkage_clusters (tjamd_counter *c, const tjamd_link *d_li
   return (long) h_flags[1];
 }
 extern "C" double tjamd_last_linkage_clusters_ms (tjamd_counter *c) { return c ? c->timer[T_LINKAGE_CLUSTERS].ms (c->device) : -1.0; }
+
+// ---- N16: the sites that set a group of samples apart from the rest --------------------------------------------------------
+// The site x sample genotype matrix reduced per site under the key (group, genotype); the rule as built is in
+// include/tatajuba_groups.h.  Three steps: a pass that makes every check, counts the marks of every site into scratch and sums
+// the marks of every group there, and writes nothing of the caller's; the shared scan of the sites' counts; a pass that returns
+// while the error flag is up and otherwise computes every site again (the matrix is 2 bytes a cell; the calls are not kept) and
+// writes the four outputs, a mark at its site's offset plus its rank among the site's marks.  The two passes are one kernel
+// compiled twice.  A site's work has two forms, chosen by n_samples alone:
+//   up to 64 samples, group_sites_small_kernel: a wavefront per site, a lane per sample.  The membership masks do not depend on
+//     the site: lane r keeps the r-th smallest group that has a member and __ballot (label == group), made once per wavefront.
+//     Per site called = __ballot (g >= 0) among those who take part; per group with a member the genotype x of its first called
+//     lane and same = __ballot (g == x): fixed iff the group's called mask lies inside `same`, n_outside the popcount of `same`
+//     among the other groups' called.  All of it is wave-uniform 64-bit mask arithmetic; no LDS atomic.
+//   beyond, group_sites_large_kernel: a workgroup of 1024 walks a run of sites, a thread keeping the labels of its four
+//     samples in registers.  Per site LDS atomics into a table per group (count, smallest and largest genotype: fixed iff they
+//     are equal) and a table of counts per genotype (0 .. n_alleles <= n_samples: hence that bound); a wavefront first folds its
+//     lanes of equal (group, genotype), up to eight such keys, into one atomic each, because few groups and few alleles are the
+//     usual case and would otherwise meet on one address.  Then a thread per group forms n_outside = count[fixed] - n_called and
+//     the mark, and clears its own entry; the marks of 64 groups are a __ballot word in LDS, from which a site's count, its
+//     first group and a mark's rank are popcounts.  The genotype counts are cleared up to the site's n_alleles.  66 KB of LDS: two
+//     workgroups to a CU.  Nothing waits for another workgroup.
+// Global atomics: the error flag, and a group's marks once per workgroup (from registers and LDS, not per site) into scratch,
+// from where the second pass copies them out: d_group_marks is not touched by a refused call.  DESIGN.md section 3.5, N16.
+
+struct GroupCall { int n_called, fixed, n_outside, mark; };
+struct GroupSite { int n_called, n_genotypes, n_marks, first_group; };
+struct GroupMark { int site, group, genotype, n_called; };
+static_assert (sizeof (GroupCall) == 16 && sizeof (GroupCall) == sizeof (tjamd_group_call), "group call layout");
+static_assert (sizeof (GroupSite) == 16 && sizeof (GroupSite) == sizeof (tjamd_group_site), "group site layout");
+static_assert (sizeof (GroupMark) == 16 && sizeof (GroupMark) == sizeof (tjamd_group_mark), "group mark layout");
+
+#define GRP_MAX 4096                                    // samples, groups and, by the rule's bound, alleles of a site
+#define GRP_SMALL 64                                    // samples up to which a wavefront takes a site
+#define GRP_THREADS 1024
+#define GRP_PER (GRP_MAX / GRP_THREADS)                 // samples, and groups, of a thread of the second form
+#define GRP_FOLD 8                                      // distinct (group, genotype) keys a wavefront folds before its lanes go alone
+#define GRP_NONE 0x7fffffff
+// words of a call: [0] error bits (1 a label, 2 a site's n_alleles, 4 a cell), [1] the number of marks (the scan's total);
+// from word 64 on: the marks of every group
+struct GroupArgs
+{
+  const Site *sites; long n_sites; const int16_t *geno; int ns; const int *group; int n_groups, min_called;
+  GroupCall *calls; GroupSite *site_out; int *group_marks; GroupMark *marks; long cap;
+  int *flags, *gm; u32 *cnt;                            // cnt: a site's marks (written by the first pass), then their offsets (read by the second)
+};
+
+__device__ __forceinline__ u64 readlane64 (u64 x, int from)
+{
+  return ((u64) (u32) __builtin_amdgcn_readlane ((int) (x >> 32), from) << 32) | (u32) __builtin_amdgcn_readlane ((int) x, from);
+}
+
+template <bool EMIT>
+__global__ __launch_bounds__ (256)
+void group_sites_small_kernel (const GroupArgs A)
+{
+  __shared__ int s_marks[4][GRP_SMALL];
+  if (EMIT && ((volatile const int *) A.flags)[0] != 0) return;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, ns = A.ns, n_groups = A.n_groups;
+  if (EMIT && A.group_marks && blockIdx.x == 0)
+    for (int G = tid; G < n_groups; G += 256) A.group_marks[G] = A.gm[G];
+  int bad = 0, label = -1;
+  if (lane < ns) {
+    label = A.group[lane];
+    if (label < -1 || label >= n_groups) { bad |= 1; label = -1; }
+  }
+  const u64 taking = __ballot (label >= 0);
+  int gid = GRP_NONE, ng = 0, my_marks = 0;             // lane r: the r-th smallest group that has a member, and its members
+  u64 gmask = 0;
+  for (int cur = -1; ng < GRP_SMALL; ng++) {
+    int next = label > cur ? label : GRP_NONE;
+    for (int o = 32; o; o >>= 1) next = min (next, __shfl_xor (next, o));
+    next = __builtin_amdgcn_readfirstlane (next);
+    if (next == GRP_NONE) break;
+    const u64 m = __ballot (label == next);
+    if (lane == ng) { gid = next; gmask = m; }
+    cur = next;
+  }
+  for (long i = (long) blockIdx.x * 4 + wave; i < A.n_sites; i += (long) gridDim.x * 4) {
+    const int na = A.sites[i].n_alleles;
+    if (na < 1 || na > ns) {                            // (the whole wavefront)
+      bad |= 2;
+      if (!EMIT && lane == 0) A.cnt[i] = 0;
+      continue;
+    }
+    int g = -1;
+    if (lane < ns) {
+      g = A.geno[i * ns + lane];
+      if (g < -1 || g > na) { bad |= 4; g = -1; }
+    }
+    const u64 called = __ballot (g >= 0) & taking;      // those who take part only: nobody else is a member or an outsider
+    const long at = EMIT ? (long) A.cnt[i] : 0;
+    int n_marks = 0, first = -1;
+    GroupCall mine = {0, -1, 0, 0};                     // lane r: the call of the r-th group
+    for (int r = 0; r < ng; r++) {
+      const u64 members = readlane64 (gmask, r), cm = called & members, others = called & ~members;
+      GroupCall q = {(int) __popcll (cm), -1, 0, 0};
+      if (cm) {
+        const int x = __builtin_amdgcn_readlane (g, __ffsll ((long long) cm) - 1);
+        const u64 same = __ballot (g == x);
+        q.fixed = (cm & ~same) ? -2 : x;
+        if (q.fixed >= 0) {
+          q.n_outside = __popcll (same & others);
+          q.mark = q.n_called >= A.min_called && q.n_outside == 0 && others != 0;
+        }
+      }
+      if (q.mark) {
+        const int G = __builtin_amdgcn_readlane (gid, r);
+        if (first < 0) first = G;
+        if (EMIT && A.marks && lane == 0 && at + n_marks < A.cap) A.marks[at + n_marks] = GroupMark {(int) i, G, q.fixed, q.n_called};
+        n_marks++;
+        if (!EMIT && lane == r) my_marks++;
+      }
+      if (EMIT && lane == r) mine = q;
+    }
+    if (!EMIT) {
+      if (lane == 0) A.cnt[i] = (u32) n_marks;
+      continue;
+    }
+    if (A.site_out) {
+      int n_genotypes = 0;
+      for (u64 rem = called; rem; n_genotypes++)        // one step per distinct genotype
+        rem &= ~__ballot (g == __builtin_amdgcn_readlane (g, __ffsll ((long long) rem) - 1));
+      if (lane == 0) A.site_out[i] = GroupSite {(int) __popcll (called), n_genotypes, n_marks, first};
+    }
+    if (A.calls)
+      for (int base = 0; base < n_groups; base += 64) { // a lane per group: the place of G among the groups that have a member
+        const int G = base + lane;
+        int lo = 0, hi = ng;
+        for (int it = 0; it < 7; it++) {
+          const int mid = (lo + hi) >> 1, v = __shfl (gid, mid & 63);
+          if (lo < hi) { if (v < G) lo = mid + 1; else hi = mid; }
+        }
+        const int r = lo & 63, at_r = __shfl (gid, r);  // (every lane takes part in every exchange: a lane that sits out is read as 0)
+        const bool has = lo < ng && at_r == G;
+        GroupCall q = {__shfl (mine.n_called, r), __shfl (mine.fixed, r), __shfl (mine.n_outside, r), __shfl (mine.mark, r)};
+        if (!has) q = GroupCall {0, -1, 0, 0};
+        if (G < n_groups) A.calls[i * n_groups + G] = q;
+      }
+  }
+  if (EMIT) return;
+  if (bad) atomicOr (A.flags, bad);
+  s_marks[wave][lane] = my_marks;                       // every wavefront has the same list of groups
+  __syncthreads ();
+  if (tid < ng) {
+    const int n = s_marks[0][tid] + s_marks[1][tid] + s_marks[2][tid] + s_marks[3][tid];
+    if (n) atomicAdd (&A.gm[gid], n);
+  }
+}
+
+// a wavefront's called samples into the two tables of the site: lanes of one (group, genotype) first fold into one lane
+__device__ __forceinline__ void group_tally (bool active, int G, int g, int lane, int *g_cnt, int *g_min, int *g_max, int *x_cnt)
+{
+  const int key = G << 13 | g;                          // (g <= 4096)
+  u64 rem = __ballot (active);
+  #pragma unroll 1
+  for (int it = 0; it < GRP_FOLD && rem; it++) {
+    const int j = __ffsll ((long long) rem) - 1;
+    const u64 m = __ballot (active && key == __builtin_amdgcn_readlane (key, j));
+    if (lane == j) {
+      const int n = __popcll (m);
+      atomicAdd (&g_cnt[G], n); atomicMin (&g_min[G], g); atomicMax (&g_max[G], g); atomicAdd (&x_cnt[g], n);
+    }
+    rem &= ~m;
+    if ((m >> lane) & 1ull) active = false;
+  }
+  if (active) { atomicAdd (&g_cnt[G], 1); atomicMin (&g_min[G], g); atomicMax (&g_max[G], g); atomicAdd (&x_cnt[g], 1); }
+}
+
+template <bool EMIT>
+__global__ __launch_bounds__ (GRP_THREADS)
+void group_sites_large_kernel (const GroupArgs A, long per_block)
+{
+  __shared__ int g_cnt[GRP_MAX], g_min[GRP_MAX], g_max[GRP_MAX], x_cnt[GRP_MAX + 1];
+  __shared__ u64 markbits[GRP_MAX / 64];
+  __shared__ int s_called, s_ngeno;
+  if (EMIT && ((volatile const int *) A.flags)[0] != 0) return;
+  const int tid = threadIdx.x, lane = tid & 63, ns = A.ns, n_groups = A.n_groups;
+  if (EMIT && A.group_marks && blockIdx.x == 0)
+    for (int G = tid; G < n_groups; G += GRP_THREADS) A.group_marks[G] = A.gm[G];
+  int bad = 0, label[GRP_PER], gmarks[GRP_PER];
+  #pragma unroll
+  for (int j = 0; j < GRP_PER; j++) {
+    const int s = tid + GRP_THREADS * j;
+    label[j] = -1; gmarks[j] = 0;
+    if (s < ns) {
+      label[j] = A.group[s];
+      if (label[j] < -1 || label[j] >= n_groups) { bad |= 1; label[j] = -1; }
+    }
+    g_cnt[s] = 0; g_min[s] = GRP_NONE; g_max[s] = -1; x_cnt[s] = 0;
+  }
+  if (tid < GRP_MAX / 64) markbits[tid] = 0;
+  if (tid == 0) { x_cnt[GRP_MAX] = 0; s_called = 0; s_ngeno = 0; }
+  __syncthreads ();
+  const long i0 = (long) blockIdx.x * per_block, i1 = min (A.n_sites, i0 + per_block);
+  for (long i = i0; i < i1; i++) {
+    const int na = A.sites[i].n_alleles;
+    if (na < 1 || na > ns) {                            // (the whole workgroup; the tables are clean)
+      bad |= 2;
+      if (!EMIT && tid == 0) A.cnt[i] = 0;
+      continue;
+    }
+    #pragma unroll
+    for (int j = 0; j < GRP_PER; j++) {
+      const int s = tid + GRP_THREADS * j;
+      if (GRP_THREADS * j + (tid & ~63) >= ns) break;   // (a whole wavefront)
+      int g = -1;
+      if (s < ns) {
+        g = A.geno[i * ns + s];
+        if (g < -1 || g > na) { bad |= 4; g = -1; }
+      }
+      const bool active = g >= 0 && label[j] >= 0;
+      const int n = __popcll (__ballot (active));
+      if (n && lane == 0) atomicAdd (&s_called, n);
+      group_tally (active, label[j], g, lane, g_cnt, g_min, g_max, x_cnt);
+    }
+    __syncthreads ();
+    const int all_called = s_called;
+    u32 marked = 0;                                     // bit j: this thread's j-th group is marked here
+    #pragma unroll
+    for (int j = 0; j < GRP_PER; j++) {                 // a thread per group
+      const int G = tid + GRP_THREADS * j;
+      if (GRP_THREADS * j + (tid & ~63) >= n_groups) continue;   // (a whole wavefront)
+      int nc = 0, fixed = -1, n_outside = 0, mark = 0;
+      if (G < n_groups) {
+        nc = g_cnt[G];
+        if (nc) {
+          const int lo = g_min[G], hi = g_max[G];
+          fixed = lo == hi ? lo : -2;
+          if (fixed >= 0) {
+            n_outside = x_cnt[fixed] - nc;
+            mark = nc >= A.min_called && n_outside == 0 && all_called > nc;
+          }
+          if (!(EMIT && mark)) { g_cnt[G] = 0; g_min[G] = GRP_NONE; g_max[G] = -1; }   // (a marked group's entry is its record until the list has it)
+        }
+        if (EMIT && A.calls) A.calls[i * n_groups + G] = GroupCall {nc, fixed, n_outside, mark};
+      }
+      const u64 mb = __ballot (mark != 0);
+      if (lane == 0) markbits[G >> 6] = mb;
+      if (!EMIT) gmarks[j] += mark;
+      marked |= (u32) mark << j;
+    }
+    if (EMIT && A.site_out) {                           // the genotypes that somebody carries
+      int nz = 0;
+      for (int x = tid; x <= na; x += GRP_THREADS) nz += x_cnt[x] != 0;
+      for (int o = 32; o; o >>= 1) nz += __shfl_xor (nz, o);
+      if (nz && lane == 0) atomicAdd (&s_ngeno, nz);
+    }
+    __syncthreads ();
+    if (tid < 64) {                                     // the site's marks from the words of its groups (those beyond n_groups stay 0)
+      const u64 w = markbits[tid];
+      int n_marks = __popcll (w), first = w ? tid * 64 + __ffsll ((long long) w) - 1 : GRP_NONE;
+      for (int o = 32; o; o >>= 1) { n_marks += __shfl_xor (n_marks, o); first = min (first, __shfl_xor (first, o)); }
+      if (tid == 0) {
+        if (!EMIT) A.cnt[i] = (u32) n_marks;
+        else if (A.site_out) A.site_out[i] = GroupSite {s_called, s_ngeno, n_marks, first == GRP_NONE ? -1 : first};
+        s_called = 0; s_ngeno = 0;
+      }
+    }
+    if (EMIT && marked) {
+      #pragma unroll 1
+      for (int j = 0; j < GRP_PER; j++) {
+        if (!((marked >> j) & 1u)) continue;
+        const int G = tid + GRP_THREADS * j, nc = g_cnt[G], fixed = g_min[G];
+        g_cnt[G] = 0; g_min[G] = GRP_NONE; g_max[G] = -1;
+        if (!A.marks) continue;
+        long pos = (long) A.cnt[i] + __popcll (markbits[G >> 6] & ((1ull << (G & 63)) - 1ull));   // its rank: the marked groups below it
+        #pragma unroll 1
+        for (int w = 0; w < (G >> 6); w++) pos += __popcll (markbits[w]);
+        if (pos < A.cap) A.marks[pos] = GroupMark {(int) i, G, fixed, nc};
+      }
+    }
+    for (int x = tid; x <= na; x += GRP_THREADS) x_cnt[x] = 0;   // what this site could touch
+    __syncthreads ();
+  }
+  if (EMIT) return;
+  if (bad) atomicOr (A.flags, bad);
+  #pragma unroll
+  for (int j = 0; j < GRP_PER; j++)
+    if (gmarks[j]) atomicAdd (&A.gm[tid + GRP_THREADS * j], gmarks[j]);
+}
+
+extern "C" long tjamd_group_sites (tjamd_counter *c, const tjamd_site *d_sites, long n_sites, const int16_t *d_genotype, int n_samples, const int *d_group, int n_groups,
+                                   int min_called, tjamd_group_call *d_calls, tjamd_group_site *d_site_out, int *d_group_marks, tjamd_group_mark *d_marks, long mark_capacity,
+                                   long *h_n_marks)
+{
+  static const char *fn = "tjamd_group_sites";
+  if (!c) return -set_err (TJAMD_ERR_ARG, "%s: null counter", fn);
+  if (n_sites < 0) return -set_err (TJAMD_ERR_ARG, "%s: n_sites %ld below 0", fn, n_sites);
+  if (n_sites > 0 && (!d_sites || !d_genotype)) return -set_err (TJAMD_ERR_ARG, "%s: null site or genotype buffer", fn);
+  if (!d_group) return -set_err (TJAMD_ERR_ARG, "%s: null d_group", fn);
+  if (n_samples < 1 || n_samples > GRP_MAX) return -set_err (TJAMD_ERR_ARG, "%s: n_samples %d outside 1..4096", fn, n_samples);
+  if (n_groups < 1 || n_groups > GRP_MAX) return -set_err (TJAMD_ERR_ARG, "%s: n_groups %d outside 1..4096", fn, n_groups);
+  if (min_called < 1) return -set_err (TJAMD_ERR_ARG, "%s: min_called %d below 1", fn, min_called);
+  if (mark_capacity < 0) return -set_err (TJAMD_ERR_ARG, "%s: mark_capacity %ld below 0", fn, mark_capacity);
+  if (!d_marks && mark_capacity > 0) return -set_err (TJAMD_ERR_ARG, "%s: null d_marks with a capacity of %ld", fn, mark_capacity);
+  if (n_sites >= (1l << 31) || n_sites * (long) n_samples >= (1l << 31)) return -set_err (TJAMD_ERR_ARG, "%s: %ld sites x %d samples: 2^31 cells or more", fn, n_sites, n_samples);
+  if (d_calls && n_sites * (long) n_groups >= (1l << 31)) return -set_err (TJAMD_ERR_ARG, "%s: %ld sites x %d groups: 2^31 calls or more", fn, n_sites, n_groups);
+  if (tjamd_device_count () <= 0) return -set_err (TJAMD_ERR_NO_DEVICE, "%s: TJAMD_ERR_NO_DEVICE: no HIP device visible (the sites are read by group on the device; no CPU fallback)", fn);
+  Stage st (c, T_GROUP_SITES);                          // (a call that returns no count leaves no timing behind)
+  if (hipSetDevice (c->device) != hipSuccess) return -set_err (TJAMD_ERR_HIP, "hipSetDevice failed");
+  int rc;
+  if (n_sites == 0) {                                   // no site: no mark, no kernel
+    if (d_group_marks && hipMemsetAsync (d_group_marks, 0, (size_t) n_groups * sizeof (int), c->stream) != hipSuccess) return -set_err (TJAMD_ERR_HIP, "%s: memset failed", fn);
+    rc = read_back (c, fn, nullptr, nullptr, 0);
+    if (rc) return -rc;
+    if (h_n_marks) *h_n_marks = 0;
+    return 0;
+  }
+  ScratchCut cut;
+  int *flags; u32 *cnt;
+  cut.take (flags, (size_t) 64 + n_groups); cut.take (cnt, (size_t) n_sites);
+  rc = cut.commit (c);
+  if (!rc) rc = ensure (c->scan_tmp, scan_tmp_words (n_sites) * 4 + 64, c->stream);
+  if (rc) return -rc;
+  if (hipMemsetAsync (flags, 0, ((size_t) 64 + n_groups) * sizeof (int), c->stream) != hipSuccess) return -set_err (TJAMD_ERR_HIP, "%s: memset failed", fn);
+  const GroupArgs A = {(const Site *) d_sites, n_sites, d_genotype, n_samples, d_group, n_groups, min_called, (GroupCall *) d_calls, (GroupSite *) d_site_out, d_group_marks,
+                       (GroupMark *) d_marks, mark_capacity, flags, flags + 64, cnt};
+  const bool small = n_samples <= GRP_SMALL && c->groups_small;
+  // the first form: wavefronts that take a site each in turn, sixteen or more a wavefront where there are that many; the second: two workgroups a CU, each a run of sites
+  const long blocks = small ? std::max (1l, std::min ((n_sites + 63) / 64, 8l * c->n_cu)) : std::min (n_sites, 2l * c->n_cu);
+  const long per_block = (n_sites + blocks - 1) / blocks;
+  const unsigned grid = (unsigned) (small ? blocks : (n_sites + per_block - 1) / per_block);
+  st.begin ();
+  if (small) hipLaunchKernelGGL (group_sites_small_kernel<false>, dim3 (grid), dim3 (256), 0, c->stream, A);
+  else hipLaunchKernelGGL (group_sites_large_kernel<false>, dim3 (grid), dim3 (GRP_THREADS), 0, c->stream, A, per_block);
+  rc = exclusive_scan (c, cnt, cnt, n_sites, (u32 *) flags + 1, (u32 *) c->scan_tmp.p, c->scan_tmp.cap / 4);
+  if (rc) return -rc;
+  if (small) hipLaunchKernelGGL (group_sites_small_kernel<true>, dim3 (grid), dim3 (256), 0, c->stream, A);
+  else hipLaunchKernelGGL (group_sites_large_kernel<true>, dim3 (grid), dim3 (GRP_THREADS), 0, c->stream, A, per_block);
+  st.end ();
+  u32 h[2] = {0, 0};
+  rc = read_back (c, fn, flags, h, 2);
+  if (rc) return -rc;
+  if (h[0] & 1u) return -set_err (TJAMD_ERR_ARG, "%s: a label is below -1 or not below n_groups %d", fn, n_groups);
+  if (h[0] & 2u) return -set_err (TJAMD_ERR_ARG, "%s: a site has n_alleles < 1 or above n_samples %d", fn, n_samples);
+  if (h[0] & 4u) return -set_err (TJAMD_ERR_ARG, "%s: a genotype cell is below -1 or above its site's n_alleles", fn);
+  if (h_n_marks) *h_n_marks = (long) h[1];
+  if ((long) h[1] > mark_capacity) return -set_err (TJAMD_ERR_CAPACITY, "%s: %u marks, caller capacity %ld", fn, h[1], mark_capacity);
+  st.done ();
+  return (long) h[1];
+}
+extern "C" double tjamd_last_group_sites_ms (tjamd_counter *c) { return c ? c->timer[T_GROUP_SITES].ms (c->device) : -1.0; }
