@@ -3878,6 +3878,12 @@ struct StageTimer
 // them out), finalise, the kernels of tjamd_merge_samples, tjamd_tract_stats, tjamd_union_tracts, tjamd_union_tract_stats
 enum { T_SCAN, T_FIN, T_MERGE, T_TRACT, T_UNION, T_UNION_STATS, T_REF, T_LOCATE, T_LOCATED_TRACTS, T_VARIANTS, T_ANNOTATION, T_TRACT_FEATURES, T_SEED_ORDER, T_LOCATE_GAPPED, T_CODING, T_VARIANT_EFFECTS, T_MERGE_VARIANTS, T_SITE_DEPTHS, T_SAMPLE_DISTANCES, T_SAMPLE_LINKAGE, T_LINKAGE_CLUSTERS, T_GROUP_SITES, TJ_N_TIMERS };   // (T_REF to T_LOCATED_TRACTS: N7, T_VARIANTS: N8, the next two: N9; then two of N10; two of N11; then N12, N13, N14, the two of N15 and N16, end of the file)
 
+// A finalise between its two halves: finalise_queue fills this in, finalise_collect reads it and sets the state back to
+// FIN_IDLE (nothing begun).  FIN_EVENT: begun, ev_done says when the counts have arrived; FIN_ARRIVED: begun, the stream has
+// been waited for and nothing is left to wait for; FIN_SETTLED: the outcome was clear at once (no raw records), c->status has it.
+enum FinState { FIN_IDLE, FIN_EVENT, FIN_ARRIVED, FIN_SETTLED };
+struct FinCarry { FinState state = FIN_IDLE; int remove_biased = 0, min_coverage = 0; bool speculative = false, plan_ahead = false; u64 kept_cap = 0; };
+
 struct tjamd_counter
 {
   int device = 0, k = 0, W = 4, n_cu = 256;
@@ -3896,7 +3902,7 @@ struct tjamd_counter
 #define TJ_PIECE_EVENTS 64
   hipEvent_t ev_pa[TJ_PIECE_EVENTS] = {}, ev_pb[TJ_PIECE_EVENTS] = {};
   int n_piece_ev = 0;
-  StageTimer timer[TJ_N_TIMERS];   // T_SCAN ... T_UNION_STATS
+  StageTimer timer[TJ_N_TIMERS];
   DevBuf ts_cov, ts_aux;      // tjamd_tract_stats / tjamd_tract_sample_stats: the samples' coverages, error flag + last tract id
   long union_cand = -1;       // retry candidates of the last tjamd_union_tracts
   DevBuf ut_tot, ut_lev, ut_fb, ut_slots;   // union tracts: exact row totals, admitted edit distances, fallback flags, global bars
@@ -3923,8 +3929,7 @@ struct tjamd_counter
   hipEvent_t ev_done = nullptr;                         // tjamd_finalise_begin: the counts have reached the host
   hipEvent_t ev_agg = nullptr;                          // the aggregation and the clearing of the buckets are done (order_stream waits for it)
   hipStream_t order_stream = nullptr;                   // tjamd_counter_set_order_stream: where a finalise begun with tjamd_finalise_begin runs its ordering step
-  int fin_pending = 0;                                  // 1: begun, results not looked at yet (tjamd_finalise_end)
-  int fin_rb = 0, fin_mc = 0; bool fin_speculative = false, fin_plan_ahead = false; u64 fin_kept_cap = 0;
+  FinCarry fin;                                         // what finalise_queue leaves for finalise_collect
   hipEvent_t marks[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};   // tjamd_mark / tjamd_wait_mark
   unsigned mark_seq = 0;
   long last_scan_launches = 0;
@@ -3957,6 +3962,22 @@ static int ensure (DevBuf &b, size_t bytes, hipStream_t stream, size_t keep_byte
 }
 
 static void release (DevBuf &b) { if (b.p) (void) hipFree (b.p); b.p = nullptr; b.cap = 0; }
+
+// The record width of a counter (c->W: 1, 2 or 4 words) as a compile-time constant: f is called with
+// std::integral_constant<int, W>, so that `constexpr int W = decltype (w)::value` names the kernel instance to launch.
+template <class F> static void with_width (int W, F &&f)
+{
+  switch (W) {
+    case 1: f (std::integral_constant<int, 1> ()); break;
+    case 2: f (std::integral_constant<int, 2> ()); break;
+    default: f (std::integral_constant<int, 4> ()); break;
+  }
+}
+
+// the T_FIN interval ends here on this stream, and counts
+static int end_fin_interval (tjamd_counter *c, hipStream_t stream) { HIPCHK (c->timer[T_FIN].end (stream)); c->timer[T_FIN].timed = true; return TJAMD_OK; }
+// this finalise is over with status s: in the counter, and through the caller's pointer where there is one
+static int finalise_status (tjamd_counter *c, int *status, int s) { c->status = s; if (status) *status = s; return TJAMD_OK; }
 
 // One call's use of a timer of its counter.  Construction clears `timed` (where the entry does that relative to its checks is
 // the entry's choice; a null counter, or one that stands for a counter where there is no device, is left alone), begin ()
@@ -4010,7 +4031,9 @@ extern "C" tjamd_counter *tjamd_counter_create (int device, int kmer_size)
   if (device < 0 || device >= n) { set_err (TJAMD_ERR_ARG, "device %d out of range [0,%d)", device, n); return NULL; }
   if (kmer_size < 2 || kmer_size > 32) { set_err (TJAMD_ERR_ARG, "kmer_size %d outside [2,32] (reference clamp: src/main.c:184-185)", kmer_size); return NULL; }
   HIPCHK_NULL (hipSetDevice (device));
-  tjamd_counter *c = new tjamd_counter ();
+  // (a failure below leaves through tjamd_counter_destroy, which takes a counter built this far)
+  std::unique_ptr<tjamd_counter, void (*) (tjamd_counter *)> made (new tjamd_counter (), tjamd_counter_destroy);
+  tjamd_counter *const c = made.get ();
   c->device = device; c->k = kmer_size;
   c->W = (kmer_size <= 12) ? 1 : (kmer_size <= 28) ? 2 : 4;
   hipDeviceProp_t prop;
@@ -4052,14 +4075,14 @@ extern "C" tjamd_counter *tjamd_counter_create (int device, int kmer_size)
   HIPCHK_NULL (hipEventCreateWithFlags (&c->ev_done, hipEventDisableTiming));
   HIPCHK_NULL (hipEventCreateWithFlags (&c->ev_agg, hipEventDisableTiming));
   HIPCHK_NULL (hipStreamSynchronize (c->stream));
-  return c;
+  return made.release ();
 }
 
 extern "C" void tjamd_counter_destroy (tjamd_counter *c)
 {
   if (!c) return;
   (void) hipSetDevice (c->device);
-  (void) hipStreamSynchronize (c->stream);
+  if (c->stream) (void) hipStreamSynchronize (c->stream);   // (null: tjamd_counter_create got no further than that)
   DevBuf *all[] = {&c->log, &c->logmeta, &c->pool, &c->table, &c->stage, &c->fix, &c->loc, &c->prefix, &c->rawlist, &c->slow, &c->alt, &c->hist, &c->flags, &c->segid, &c->headpos,
                    &c->keep, &c->outpos, &c->scan_tmp, &c->kept, &c->idx_i, &c->idx_f, &c->cov, &c->bins, &c->binstart, &c->binctx, &c->ovf, &c->grp_jt, &c->grp_hist, &c->fine,
                    &c->ts_cov, &c->ts_aux, &c->ut_tot, &c->ut_lev, &c->ut_fb, &c->ut_slots, &c->lc_work};
@@ -4138,7 +4161,7 @@ extern "C" int tjamd_counter_reset (tjamd_counter *c)
   if (!c) return set_err (TJAMD_ERR_ARG, "null counter");
   HIPCHK (hipSetDevice (c->device));
   // (the memset is not needed right after a finalise whose counts the host has seen: clear_buckets_kernel zeroed the rest)
-  if (!(c->ctr_clean && c->fin_pending == 0 && c->n_undefined == 0)) HIPCHK (hipMemsetAsync (c->d_ctr, 0, sizeof (DevCounters), c->stream));
+  if (!(c->ctr_clean && c->fin.state == FIN_IDLE && c->n_undefined == 0)) HIPCHK (hipMemsetAsync (c->d_ctr, 0, sizeof (DevCounters), c->stream));
   int rc = clear_buckets (c);
   c->ctr_clean = true;
   if (rc) return rc;
@@ -4248,7 +4271,6 @@ static int sync_counters (tjamd_counter *c)
   return apply_counter_copies (c);
 }
 
-// room for `add` more raw records (an upper bound), wherever the hash sends them, written by `grid` workgroups
 static void choose_chunk_size (tjamd_counter *c, u64 records)
 { // fixed by the first scan (or reservation) after a reset: at most ~16 k chunks for this many records
   if (c->ch_shift >= 0) return;
@@ -4285,12 +4307,11 @@ static int ensure_table (tjamd_counter *c, u64 need_maxj)
   return TJAMD_OK;
 }
 
-static int ensure_buckets (tjamd_counter *c, u64 add, int grid)
+// room for `add` more raw records (an upper bound), wherever the hash sends them
+static int ensure_buckets (tjamd_counter *c, u64 add)
 {
   choose_chunk_size (c, add);
   const u64 ch = (u64) TJ_CH0 << c->ch_shift;
-  const u64 pad_bucket = 0;                             // (no padding records any more)
-  (void) grid;
   // one chunk per bucket is always claimed ahead of the cursor
   const u64 need_chunks = c->chunk_bound + (add + ch - 1) / ch + 2 * TJ_P;
   c->buckets_clean = false; c->ctr_clean = false;
@@ -4302,7 +4323,7 @@ static int ensure_buckets (tjamd_counter *c, u64 add, int grid)
   rc = ensure_table (c, need_maxj);
   if (rc) return rc;
   c->chunk_bound = need_chunks;
-  c->bucket_bound += add + pad_bucket;
+  c->bucket_bound += add;
   return TJAMD_OK;
 }
 
@@ -4348,7 +4369,7 @@ static int scan_device_piece (tjamd_counter *c, const void *d_stream, size_t n_b
   const u64 bound = (u64) ((double) (n_bytes / (size_t) mprime + 1) * c->slack);
   const long n_tiles = (long) ((n_bytes + TJ_SB_TILE - 1) / TJ_SB_TILE);
   const int grid = (int) std::min<long> (n_tiles, (long) c->n_cu * TJ_SB_WG_PER_CU);
-  rc = ensure_buckets (c, bound, grid + 1);             // + the fix-up kernel's block-per-record inserts
+  rc = ensure_buckets (c, bound);
   c->raw_bound += (u64) (n_bytes / (size_t) mprime) + 1u;
   if (!rc) rc = ensure (c->fix, (size_t) TJ_FIX_CAP * sizeof (FixEntry), c->stream);
   // fast kernel: tiles of FK_OWN tract starts, two workgroups resident per CU; the list of the tiles it leaves to the generic
@@ -4388,30 +4409,26 @@ static int scan_device_piece (tjamd_counter *c, const void *d_stream, size_t n_b
     LG.log = (u64 *) c->log.p; LG.next = meta + par; LG.next_other = meta + (par ^ 1); LG.count = meta + 2; LG.n_blocks = (u32) n_blocks;
     c->log_next_clean[par] = false; c->log_next_clean[par ^ 1] = true;
   }
-  else c->log_next_clean[par ^ 1] = c->log_next_clean[par ^ 1] && true;
-#define TJ_LAUNCH_SCAN(WW) do { \
-    if (use_fast) { \
-      /* the fast kernel takes every tile it can vouch for and lists the others; the generic kernel then works through the list */ \
-      if (WW <= 2 && use_log) \
-        hipLaunchKernelGGL ((scan_fast_kernel<(WW <= 2 ? WW : 1), true>), dim3 (capped (fgrid_log)), dim3 (FK_BLOCK), 0, c->stream, seq, (long) n_bytes, n_ftiles, c->k, mprime, BK, c->d_ctr, \
-                            (u32 *) c->slow.p, par, c->fast_mode == 2 ? 1 : 0, LG); \
-      else \
-      hipLaunchKernelGGL (scan_fast_kernel<WW>, dim3 (capped (fgrid)), dim3 (FK_BLOCK), 0, c->stream, seq, (long) n_bytes, n_ftiles, c->k, mprime, BK, c->d_ctr, \
-                          (u32 *) c->slow.p, par, c->fast_mode == 2 ? 1 : 0, LG); \
-      const TileSrc listed = {(const u32 *) c->slow.p, (long) FK_OWN}; \
-      hipLaunchKernelGGL (scan_bins_kernel<WW>, dim3 (capped (lgrid)), dim3 (TJ_SB_BLOCK), 0, c->stream, seq, (long) n_bytes, 0l, c->k, mprime, BK, c->d_ctr, fix, (u32) TJ_FIX_CAP, par, listed); \
-    } \
-    else { \
-      hipLaunchKernelGGL (scan_bins_kernel<WW>, dim3 (capped (grid)), dim3 (TJ_SB_BLOCK), 0, c->stream, seq, (long) n_bytes, n_tiles, c->k, mprime, BK, c->d_ctr, fix, (u32) TJ_FIX_CAP, par, plain); \
-      hipLaunchKernelGGL (nrun_fixup_bins_kernel<WW>, dim3 (64), dim3 (256), 0, c->stream, seq, (long) n_bytes, c->k, mprime, BK, c->d_ctr, (const FixEntry *) fix, (u32) TJ_FIX_CAP, par); \
-    } \
-  } while (0)
-  switch (c->W) {
-    case 1: TJ_LAUNCH_SCAN (1); break;
-    case 2: TJ_LAUNCH_SCAN (2); break;
-    default: TJ_LAUNCH_SCAN (4); break;
-  }
-#undef TJ_LAUNCH_SCAN
+  with_width (c->W, [&] (auto w) {
+    constexpr int W = decltype (w)::value;
+    if (use_fast) {
+      // the fast kernel takes every tile it can vouch for and lists the others; the generic kernel then works through the list
+      if (use_log) {
+        if constexpr (W <= 2)                             // (the log form exists for W <= 2 only: log_mode is 2 at most)
+          hipLaunchKernelGGL ((scan_fast_kernel<W, true>), dim3 (capped (fgrid_log)), dim3 (FK_BLOCK), 0, c->stream, seq, (long) n_bytes, n_ftiles, c->k, mprime, BK, c->d_ctr,
+                              (u32 *) c->slow.p, par, c->fast_mode == 2 ? 1 : 0, LG);
+      }
+      else
+        hipLaunchKernelGGL (scan_fast_kernel<W>, dim3 (capped (fgrid)), dim3 (FK_BLOCK), 0, c->stream, seq, (long) n_bytes, n_ftiles, c->k, mprime, BK, c->d_ctr,
+                            (u32 *) c->slow.p, par, c->fast_mode == 2 ? 1 : 0, LG);
+      const TileSrc listed = {(const u32 *) c->slow.p, (long) FK_OWN};
+      hipLaunchKernelGGL (scan_bins_kernel<W>, dim3 (capped (lgrid)), dim3 (TJ_SB_BLOCK), 0, c->stream, seq, (long) n_bytes, 0l, c->k, mprime, BK, c->d_ctr, fix, (u32) TJ_FIX_CAP, par, listed);
+    }
+    else {
+      hipLaunchKernelGGL (scan_bins_kernel<W>, dim3 (capped (grid)), dim3 (TJ_SB_BLOCK), 0, c->stream, seq, (long) n_bytes, n_tiles, c->k, mprime, BK, c->d_ctr, fix, (u32) TJ_FIX_CAP, par, plain);
+      hipLaunchKernelGGL (nrun_fixup_bins_kernel<W>, dim3 (64), dim3 (256), 0, c->stream, seq, (long) n_bytes, c->k, mprime, BK, c->d_ctr, (const FixEntry *) fix, (u32) TJ_FIX_CAP, par);
+    }
+  });
   HIPCHK (hipGetLastError ());
   if (last) HIPCHK (c->timer[T_SCAN].end (c->stream));
   if (first) c->n_piece_ev = 0;
@@ -4422,8 +4439,10 @@ static int scan_device_piece (tjamd_counter *c, const void *d_stream, size_t n_b
     HIPCHK (hipEventRecord (c->ev_pa[i], c->stream));
   }
   if (use_log) {
-    if (c->W == 1) hipLaunchKernelGGL (partition_log_kernel<1>, dim3 (capped ((long) c->n_cu * PL_WG_PER_CU)), dim3 (PL_BLOCK), 0, c->stream, LG, BK, c->d_ctr, c->k);
-    else hipLaunchKernelGGL (partition_log_kernel<2>, dim3 (capped ((long) c->n_cu * PL_WG_PER_CU)), dim3 (PL_BLOCK), 0, c->stream, LG, BK, c->d_ctr, c->k);
+    with_width (c->W, [&] (auto w) {
+      constexpr int W = decltype (w)::value;
+      if constexpr (W <= 2) hipLaunchKernelGGL (partition_log_kernel<W>, dim3 (capped ((long) c->n_cu * PL_WG_PER_CU)), dim3 (PL_BLOCK), 0, c->stream, LG, BK, c->d_ctr, c->k);
+    });
     HIPCHK (hipGetLastError ());
   }
   if (mid_events) { HIPCHK (hipEventRecord (c->ev_pb[c->n_piece_ev], c->stream)); c->n_piece_ev++; }
@@ -4581,11 +4600,9 @@ extern "C" long tjamd_download_raw (tjamd_counter *c, tjamd_record *out, long ca
   if (rc) return -rc;
   if (hipMemsetAsync (c->prefix.p, 0, 8, c->stream) != hipSuccess) return -set_err (TJAMD_ERR_HIP, "memset failed");
   const Buckets BK = make_buckets (c);
-  switch (c->W) {
-    case 1: hipLaunchKernelGGL (unpack_buckets_kernel<1>, dim3 (TJ_P), dim3 (256), 0, c->stream, BK, c->k, (u64 *) c->rawlist.p, (u64) n, (u64 *) c->prefix.p); break;
-    case 2: hipLaunchKernelGGL (unpack_buckets_kernel<2>, dim3 (TJ_P), dim3 (256), 0, c->stream, BK, c->k, (u64 *) c->rawlist.p, (u64) n, (u64 *) c->prefix.p); break;
-    default: hipLaunchKernelGGL (unpack_buckets_kernel<4>, dim3 (TJ_P), dim3 (256), 0, c->stream, BK, c->k, (u64 *) c->rawlist.p, (u64) n, (u64 *) c->prefix.p); break;
-  }
+  with_width (c->W, [&] (auto w) {
+    hipLaunchKernelGGL (unpack_buckets_kernel<decltype (w)::value>, dim3 (TJ_P), dim3 (256), 0, c->stream, BK, c->k, (u64 *) c->rawlist.p, (u64) n, (u64 *) c->prefix.p);
+  });
   u64 n_out = 0;
   if (hipGetLastError () != hipSuccess || hipStreamSynchronize (c->stream) != hipSuccess ||
       hipMemcpy (&n_out, c->prefix.p, 8, hipMemcpyDeviceToHost) != hipSuccess ||
@@ -4600,18 +4617,16 @@ extern "C" int tjamd_upload_raw (tjamd_counter *c, const hopo_element *elems, lo
   if (n == 0) return TJAMD_OK;
   HIPCHK (hipSetDevice (c->device));
   int rc = sync_counters (c);
-  if (!rc) rc = ensure_buckets (c, (u64) n, 0);
+  if (!rc) rc = ensure_buckets (c, (u64) n);
   c->raw_bound += (u64) n;
   if (!rc) rc = ensure (c->stage, (size_t) n * 40, c->stream);
   if (rc) return rc;
   HIPCHK (hipMemcpyAsync (c->stage.p, elems, (size_t) n * 40, hipMemcpyHostToDevice, c->stream));
   const unsigned grid = (unsigned) std::min<long> ((n + 255) / 256, 2048);
   const Buckets BK = make_buckets (c);
-  switch (c->W) {
-    case 1: hipLaunchKernelGGL (bin_elems_kernel<1>, dim3 (grid), dim3 (256), 0, c->stream, (const u64 *) c->stage.p, n, c->k, BK, c->d_ctr); break;
-    case 2: hipLaunchKernelGGL (bin_elems_kernel<2>, dim3 (grid), dim3 (256), 0, c->stream, (const u64 *) c->stage.p, n, c->k, BK, c->d_ctr); break;
-    default: hipLaunchKernelGGL (bin_elems_kernel<4>, dim3 (grid), dim3 (256), 0, c->stream, (const u64 *) c->stage.p, n, c->k, BK, c->d_ctr); break;
-  }
+  with_width (c->W, [&] (auto w) {
+    hipLaunchKernelGGL (bin_elems_kernel<decltype (w)::value>, dim3 (grid), dim3 (256), 0, c->stream, (const u64 *) c->stage.p, n, c->k, BK, c->d_ctr);
+  });
   HIPCHK (hipGetLastError ());
   c->status = -1;
   return sync_counters (c);
@@ -4722,8 +4737,7 @@ static int finalise_radix (tjamd_counter *c, long n1, int min_coverage)
   HIPCHK (hipGetLastError ());
   hipLaunchKernelGGL (cov_max_kernel, dim3 (std::min<unsigned> (grid_for (t), 256u)), dim3 (256), 0, c->stream, (const u64 *) ctab, t, &c->d_fin->coverage);
   HIPCHK (hipGetLastError ());
-  HIPCHK (c->timer[T_FIN].end (c->stream));
-  c->timer[T_FIN].timed = true;
+  if ((rc = end_fin_interval (c, c->stream))) return rc;
   HIPCHK (hipMemcpyAsync (c->h_fin, c->d_fin, sizeof (FinCounts), hipMemcpyDeviceToHost, c->stream));
   HIPCHK (hipStreamSynchronize (c->stream));
   return TJAMD_OK;
@@ -4750,7 +4764,7 @@ static int finalise_binned (tjamd_counter *c, long n1, int min_coverage, long ca
   int cov_direct = 0;
   const int log2t = planned ? cov_table_bits (n1) : cov_plan_bits (n1, c->k, &cov_direct);
   const long t = 1l << log2t;
-  // the aggregation has counted the kept records into the finest bins (finalise_impl): no counting pass
+  // the aggregation has counted the kept records into the finest bins (finalise_queue): no counting pass
   const bool fused = planned && c->bins_counted;
   c->bins_counted = false;
   int rc = ensure (c->alt, (size_t) n1 * 24, c->stream);
@@ -4783,8 +4797,7 @@ static int finalise_binned (tjamd_counter *c, long n1, int min_coverage, long ca
   hipLaunchKernelGGL (bin_ctx_write_kernel, dim3 (256), dim3 (256), 0, st, (const u32 *) binstart, (const u32 *) binctx, (const u32 *) binout, nbins,
                       (const u32 *) tstart, (const u32 *) tend, (int *) c->idx_i.p, (int *) c->idx_f.p, (const u64 *) ctab, t, c->d_fin, plan);
   HIPCHK (hipGetLastError ());
-  HIPCHK (c->timer[T_FIN].end (st));
-  c->timer[T_FIN].timed = true;
+  if ((rc = end_fin_interval (c, st))) return rc;
   if (planned) HIPCHK (hipMemcpyAsync (c->h_state, c->d_state, sizeof (DevState), hipMemcpyDeviceToHost, st));   // (counts of the sample, plan, results: one copy)
   else HIPCHK (hipMemcpyAsync (c->h_fin, c->d_fin, sizeof (FinCounts), hipMemcpyDeviceToHost, c->stream));
   if (wait) HIPCHK (hipStreamSynchronize (c->stream));
@@ -4792,74 +4805,51 @@ static int finalise_binned (tjamd_counter *c, long n1, int min_coverage, long ca
   return TJAMD_OK;
 }
 
-// tjamd_finalise in two halves: _begin queues everything (one stream, no host synchronisation when the ordering step can be
-// planned on the device) and _end waits for the counts -- an event, not the stream: what the caller has queued behind
-// (the next sample's scan on another counter of the same stream) runs on -- and finishes the bookkeeping.
-static int finalise_impl (tjamd_counter *c, int remove_biased, int min_coverage, int *status, int phase);
-
-extern "C" int tjamd_finalise (tjamd_counter *c, int remove_biased, int min_coverage, int *status)
-{
-  int rc = finalise_impl (c, remove_biased, min_coverage, status, 0);
-  return rc;
-}
-extern "C" int tjamd_finalise_begin (tjamd_counter *c, int remove_biased, int min_coverage)
-{
-  const int rc = finalise_impl (c, remove_biased, min_coverage, nullptr, 1);
-  if (!rc && c->fin_pending == 0) c->fin_pending = 3;   // (the outcome was clear at once, e.g. no raw records: _end reports it)
-  return rc;
-}
-extern "C" int tjamd_finalise_end (tjamd_counter *c, int *status)
-{
-  if (!c) return set_err (TJAMD_ERR_ARG, "null counter");
-  if (!c->fin_pending) return set_err (TJAMD_ERR_STATE, "tjamd_finalise_end without tjamd_finalise_begin");
-  if (c->fin_pending == 3) { c->fin_pending = 0; if (status) *status = c->status; return TJAMD_OK; }
-  return finalise_impl (c, c->fin_rb, c->fin_mc, status, 2);
-}
-
-// phase 0: all of it; 1: up to the point where the host has to know the counts; 2: from there
-static int finalise_impl (tjamd_counter *c, int remove_biased, int min_coverage, int *status, int phase)
+// A finalise in two halves.  finalise_queue queues everything (one stream, no host synchronisation when the ordering step can
+// be planned on the device); finalise_collect waits for the counts -- after tjamd_finalise_begin an event, not the stream:
+// what the caller has queued behind (the next sample's scan on another counter of the same stream) runs on -- and finishes
+// the bookkeeping.  c->fin carries what the second half needs to know of the first.
+// wait: the ordering step planned ahead ends with a synchronisation of the stream (tjamd_finalise), not with ev_done
+static int finalise_queue (tjamd_counter *c, int remove_biased, int min_coverage, bool wait)
 {
   if (!c) return set_err (TJAMD_ERR_ARG, "null counter");
   HIPCHK (hipSetDevice (c->device));
-  bool speculative = c->fin_speculative, plan_ahead = c->fin_plan_ahead;
-  u64 kept_cap = c->fin_kept_cap;
-  int rc = TJAMD_OK;
-  if (phase == 2) goto second_half;
-  c->fin_pending = 0;
-  {
+  FinCarry &f = c->fin;
+  f = FinCarry {FIN_IDLE, remove_biased, min_coverage};   // (idle until all of it is queued: a failure below leaves nothing begun)
   // The raw count sizes the kept list.  A survivor stands for at least two raw records (both strands seen, or a count
   // above one), so half of the host's running upper bound of the raw count is a safe capacity: unless that is a lot of
   // memory, the aggregation is launched without first asking the device (one host round trip less) and the exact
   // counts and error flags, copied in stream order before the buckets are cleared, are looked at afterwards.
   c->n_kept = 0; c->n_idx = 0; c->coverage = 0; c->timer[T_FIN].timed = false;
-  speculative = (c->raw_bound / 2 + 1) * 24 <= (8ull << 30);
-  kept_cap = c->raw_bound / 2 + 1;
-  if (!speculative) {
+  f.speculative = (c->raw_bound / 2 + 1) * 24 <= (8ull << 30);
+  f.kept_cap = c->raw_bound / 2 + 1;
+  int rc = TJAMD_OK;
+  if (!f.speculative) {
     rc = sync_counters (c);
     if (rc) return rc;
-    if (c->n_raw_known == 0) { c->status = 1; if (status) *status = 1; return TJAMD_OK; }     // reference: src/hopo_counter.c:345-349
+    if (c->n_raw_known == 0) { f.state = FIN_SETTLED; return finalise_status (c, nullptr, 1); }     // reference: src/hopo_counter.c:345-349
     if (c->n_raw_known >= (1l << 31)) return set_err (TJAMD_ERR_CAPACITY, "%ld raw records exceed the reference's int n_elem", c->n_raw_known);
-    kept_cap = (u64) c->n_raw_known / 2 + 1;
+    f.kept_cap = (u64) c->n_raw_known / 2 + 1;
   }
 
   // steps 1-2: per-bucket hash aggregation + filter (reference :351-374)
-  rc = ensure (c->kept, (size_t) kept_cap * 24, c->stream);
+  rc = ensure (c->kept, (size_t) f.kept_cap * 24, c->stream);
   if (!rc) rc = ensure (c->ovf, c->pool.cap, c->stream);   // second pool for the aggregation's leftover rounds
   if (rc) return rc;
   HIPCHK (c->timer[T_FIN].begin (c->stream));
   const Buckets BK = make_buckets (c);
   // The ordering step is launched right behind the aggregation, sized on the device (plan_tail, by the aggregation's last
   // workgroup) for up to kept_cap / 8 records -- a sample keeps a per cent or so of its raw records -- so that the whole
-  // finalise has one host round trip; if more were kept, its kernels do nothing and the step is run again below with
-  // the count in hand.
-  long plan_cap = (long) std::min<u64> (kept_cap, std::max<u64> (kept_cap / 8, 1u << 16));
+  // finalise has one host round trip; if more were kept, its kernels do nothing and the step is run again by
+  // finalise_collect with the count in hand.
+  long plan_cap = (long) std::min<u64> (f.kept_cap, std::max<u64> (f.kept_cap / 8, 1u << 16));
   if (const char *pc = getenv ("TATAJUBA_AMD_PLAN_CAP")) plan_cap = std::max (1l, std::min (plan_cap, atol (pc)));     // (tests: make the second attempt happen)
-  plan_ahead = speculative && getenv ("TATAJUBA_AMD_NO_PLAN") == nullptr;
-  FinPlan *const d_plan = plan_ahead ? &c->d_state->plan : nullptr;
+  f.plan_ahead = f.speculative && getenv ("TATAJUBA_AMD_NO_PLAN") == nullptr;
+  FinPlan *const d_plan = f.plan_ahead ? &c->d_state->plan : nullptr;
   // with the ordering step planned ahead the aggregation counts what it keeps into the finest bins of that step
   // (clear_buckets_kernel, next on the stream, sums them to the bins the plan asks for and zeroes them again)
   u32 *fine = nullptr;
-  if (plan_ahead && getenv ("TATAJUBA_AMD_NO_FUSED_BINS") == nullptr) {
+  if (f.plan_ahead && getenv ("TATAJUBA_AMD_NO_FUSED_BINS") == nullptr) {
     const bool fresh = c->fine.p == nullptr;
     rc = ensure (c->fine, (size_t) BS_MAXBINS * 4, c->stream);
     if (rc) return rc;
@@ -4868,38 +4858,37 @@ static int finalise_impl (tjamd_counter *c, int remove_biased, int min_coverage,
     fine = (u32 *) c->fine.p;
     c->fine_dirty = true;
   }
-  const int fbits = fine_bin_bits (c->k);
-  switch (c->W) {
-    case 1: hipLaunchKernelGGL (aggregate1_kernel, dim3 (TJ_P), dim3 (AG_BLOCK), 0, c->stream, BK, (u64 *) c->ovf.p, c->k, remove_biased, (u64 *) c->kept.p, kept_cap, c->d_fin, plan_cap, d_plan, fine, fbits); break;
-    case 2: hipLaunchKernelGGL (aggregate2_kernel, dim3 (TJ_P), dim3 (AG_BLOCK), 0, c->stream, BK, (u64 *) c->ovf.p, c->k, remove_biased, (u64 *) c->kept.p, kept_cap, c->d_fin, plan_cap, d_plan, fine, fbits); break;
-    default: hipLaunchKernelGGL (aggregate4_kernel, dim3 (TJ_P), dim3 (AG_BLOCK), 0, c->stream, BK, (u64 *) c->ovf.p, c->k, remove_biased, (u64 *) c->kept.p, kept_cap, c->d_fin, plan_cap, d_plan, fine, fbits); break;
-  }
+  const auto aggregate = c->W == 1 ? aggregate1_kernel : c->W == 2 ? aggregate2_kernel : aggregate4_kernel;   // (named kernels: profiles cite them)
+  hipLaunchKernelGGL (aggregate, dim3 (TJ_P), dim3 (AG_BLOCK), 0, c->stream, BK, (u64 *) c->ovf.p, c->k, remove_biased, (u64 *) c->kept.p, f.kept_cap, c->d_fin, plan_cap, d_plan, fine, fine_bin_bits (c->k));
   HIPCHK (hipGetLastError ());
   // counters, bucket sizes and the aggregation's own counts, in one copy; then the buckets are emptied (the aggregation
   // consumed them: leftover rounds reuse their fronts) together with the counts the next aggregation adds to
   // (with the ordering step planned ahead the copy waits until that has run: clear_buckets_kernel keeps what it zeroes)
-  rc = plan_ahead ? TJAMD_OK : queue_counter_copies (c);
-  if (!rc) rc = clear_buckets (c, plan_ahead);
+  rc = f.plan_ahead ? TJAMD_OK : queue_counter_copies (c);
+  if (!rc) rc = clear_buckets (c, f.plan_ahead);
   if (rc) return rc;
-  c->fin_rb = remove_biased; c->fin_mc = min_coverage; c->fin_speculative = speculative; c->fin_plan_ahead = plan_ahead; c->fin_kept_cap = kept_cap;
-  if (plan_ahead) { rc = finalise_binned (c, 0, min_coverage, plan_cap, phase != 1); if (rc) return rc; }   // (ends with a copy of the counts and a synchronisation, or an event)
+  if (f.plan_ahead) { rc = finalise_binned (c, 0, min_coverage, plan_cap, wait); if (rc) return rc; }   // (ends with a copy of the counts and a synchronisation, or an event)
   else HIPCHK (hipStreamSynchronize (c->stream));
-  }
-  if (phase == 1) { c->fin_pending = plan_ahead ? 1 : 2; return TJAMD_OK; }    // (2: nothing left to wait for)
-second_half:
-  if (phase == 2) {
-    if (c->fin_pending == 1) HIPCHK (hipEventSynchronize (c->ev_done));
-    c->fin_pending = 0;
-  }
-  if (speculative) {
-    rc = apply_counter_copies (c, plan_ahead);
+  f.state = f.plan_ahead && !wait ? FIN_EVENT : FIN_ARRIVED;
+  return TJAMD_OK;
+}
+
+static int finalise_collect (tjamd_counter *c, int *status)
+{
+  FinCarry &f = c->fin;
+  if (f.state == FIN_SETTLED) { f.state = FIN_IDLE; return finalise_status (c, status, c->status); }
+  if (f.state == FIN_EVENT) HIPCHK (hipEventSynchronize (c->ev_done));
+  f.state = FIN_IDLE;
+  int rc = TJAMD_OK;
+  if (f.speculative) {
+    rc = apply_counter_copies (c, f.plan_ahead);
     const long n = c->n_raw_known;
     c->n_raw_known = 0; c->raw_bound = 0; c->bucket_bound = 0; c->chunk_bound = TJ_P;      // (the buckets are empty again)
     if (rc) return rc;
-    if (n == 0) { c->status = 1; if (status) *status = 1; return TJAMD_OK; }                // reference: src/hopo_counter.c:345-349
+    if (n == 0) return finalise_status (c, status, 1);                                      // reference: src/hopo_counter.c:345-349
     if (n >= (1l << 31)) return set_err (TJAMD_ERR_CAPACITY, "%ld raw records exceed the reference's int n_elem", n);
   }
-  if (plan_ahead) {
+  if (f.plan_ahead) {
     // what the aggregation's last workgroup read against what the kernel boundary behind it shows (the
     // last-workgroup pattern has no fence); a difference is repaired by sizing the ordering step again, from the exact count
     FinPlan &pl = c->h_state->plan;
@@ -4908,25 +4897,34 @@ second_half:
       pl.n1 = pl.n1_exact; pl.kept_overflow = pl.ovf_exact; pl.ok = 0;
     }
   }
-  if (plan_ahead ? c->h_state->plan.kept_overflow : c->h_fin->overflow) return set_err (TJAMD_ERR_CAPACITY, "kept list overflow");
-  const long n1 = plan_ahead ? c->h_state->plan.n1 : (long) c->h_fin->n_kept;
+  if (f.plan_ahead ? c->h_state->plan.kept_overflow : c->h_fin->overflow) return set_err (TJAMD_ERR_CAPACITY, "kept list overflow");
+  const long n1 = f.plan_ahead ? c->h_state->plan.n1 : (long) c->h_fin->n_kept;
   if (n1 == 0) {                                                               // reference :376-381
-    HIPCHK (c->timer[T_FIN].end (c->stream)); c->timer[T_FIN].timed = true;
-    c->status = 2; if (status) *status = 2; return TJAMD_OK;
+    rc = end_fin_interval (c, c->stream);
+    return rc ? rc : finalise_status (c, status, 2);
   }
 
   // steps 3-4 + coverage: bin partition, then one pass per bin sorts it and derives the context index ranges and the
   // coverage table entries; the stable radix passes + separate index kernels take over if a bin is too full.
   c->n_kept = n1;
-  if (!(plan_ahead && c->h_state->plan.ok)) rc = finalise_binned (c, n1, min_coverage);   // (not done yet, or more kept than planned for)
-  if (!rc && c->h_fin->sort_fallback) rc = finalise_radix (c, n1, min_coverage);
+  if (!(f.plan_ahead && c->h_state->plan.ok)) rc = finalise_binned (c, n1, f.min_coverage);   // (not done yet, or more kept than planned for)
+  if (!rc && c->h_fin->sort_fallback) rc = finalise_radix (c, n1, f.min_coverage);
   if (rc) return rc;
   c->n_idx = (int) c->h_fin->n_idx;
-  if (c->n_idx == 0) { c->status = 3; if (status) *status = 3; return TJAMD_OK; }   // reference :406-411 (coverage not estimated)
+  if (c->n_idx == 0) return finalise_status (c, status, 3);   // reference :406-411 (coverage not estimated)
   c->coverage = c->h_fin->coverage;
-  c->status = 0;
-  if (status) *status = 0;
-  return TJAMD_OK;
+  return finalise_status (c, status, 0);
+}
+
+extern "C" int tjamd_finalise (tjamd_counter *c, int remove_biased, int min_coverage, int *status)
+{ const int rc = finalise_queue (c, remove_biased, min_coverage, true); return rc ? rc : finalise_collect (c, status); }
+extern "C" int tjamd_finalise_begin (tjamd_counter *c, int remove_biased, int min_coverage) { return finalise_queue (c, remove_biased, min_coverage, false); }
+extern "C" int tjamd_finalise_end (tjamd_counter *c, int *status)
+{
+  if (!c) return set_err (TJAMD_ERR_ARG, "null counter");
+  if (c->fin.state == FIN_IDLE) return set_err (TJAMD_ERR_STATE, "tjamd_finalise_end without tjamd_finalise_begin");
+  if (c->fin.state != FIN_SETTLED) HIPCHK (hipSetDevice (c->device));   // (settled: nothing is asked of the device)
+  return finalise_collect (c, status);
 }
 
 extern "C" long tjamd_kept_count (tjamd_counter *c) { return c ? c->n_kept : -1; }

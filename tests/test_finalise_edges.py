@@ -149,3 +149,42 @@ def test_one_counter_through_fallback_small_three_rounds_nothing_kept_and_small_
             f = (0, 0) if name.startswith("bucket_sizes") else (1, F.get(name).min_coverage)
             assert check_corpus(monkeypatch, name, path, [f], counter=c) == 1
         c.close()
+
+
+def test_one_counter_through_every_outcome_of_begin_and_end(monkeypatch):
+    """tjamd_finalise_begin / tjamd_finalise_end on one counter through status 0, status 2 (nothing kept) and status 3 (no
+    context deep enough), with the small kept set again at the end: the same bytes as the first time, so nothing of the two in
+    between is left in the counter.  An end without a begin raises, before the first begin and after an end.  On the planned
+    paths the end waits for the event of the begin; without the plan the begin has waited for the stream and the end has
+    nothing left to wait for."""
+    small, nothing = "kept_counts-k10-n3073", "bucket_sizes-k10-1"
+    own = (1, F.get(small).min_coverage)
+    # (3073 keys, each read twice: the depths of all contexts together are 6146, so none of them reaches 6147)
+    unreached = (1, 2 * 3073 + 1)
+    assert F.reference(nothing, [(0, 0)])["fin"][(0, 0)]["status"] == 2
+    assert F.reference(small, [unreached])["fin"][unreached]["status"] == 3
+    ref = {small: F.reference(small, [own, unreached, (1, 0)]), nothing: F.reference(nothing, [(0, 0)])}
+
+    def step(c, path, name, f):
+        what = "%s %s filter=%s (two calls, one counter)" % (name, path, f)
+        assert set_path(monkeypatch, path, ref[name]["n1"].get(f[0]))
+        fill(c, name, ref[name], what)
+        got = finalised(c, f, True)
+        compare(got, ref[name]["fin"][f], what)
+        return got
+
+    for path in ("default", "noplan", "cap"):
+        c = tj.Counter(10)
+        with pytest.raises(tj.TatajubaAmdError, match="without tjamd_finalise_begin"):
+            c.finalise_end()
+        first = step(c, path, small, own)
+        assert first["status"] == 0
+        with pytest.raises(tj.TatajubaAmdError, match="without tjamd_finalise_begin"):
+            c.finalise_end()
+        assert step(c, path, nothing, (0, 0))["status"] == 2
+        assert step(c, path, small, unreached)["status"] == 3
+        again = step(c, path, small, own)
+        assert (again["status"], again["kept"], again["n_idx"], again["coverage"]) == (0, first["kept"], first["n_idx"], first["coverage"]), path
+        assert (again["idx"][0] == first["idx"][0]).all() and (again["idx"][1] == first["idx"][1]).all(), path
+        assert c.plan_mismatches() == 0
+        c.close()
