@@ -18,6 +18,14 @@
  *                             min_called of 1: the sites at which every called sample of a cluster carries one genotype that no called
  *                             sample outside it carries, one line per (site, cluster) in that order: cluster  contig  POS  REF  the
  *                             genotype's text (REF again for genotype 0)  the cluster's called samples
+ *   DIR/sample_tree.nwk       with -N (only together with -C T): tjamd_linkage_tree on the links and tjamd_clade_sites on that genotype matrix with a
+ *                             min_called of 1; one Newick line per root of the tree, the roots in the order of their smallest sample:
+ *                             (left,right)label:length; with a sample's name for a leaf, the number of sites that support the clade
+ *                             (d_node_marks) as an inner node's label, and as a branch's length the key of the parent's link minus the key of
+ *                             the child's own (0 for a leaf); a root's branch has length 0
+ *   DIR/clade_sites.tsv       with -N: the sites at which every called sample of a node's clade carries one genotype that no called sample
+ *                             outside it carries, one line per (site, node) in that order: node  contig  POS  REF  the genotype's text
+ *                             (REF again for genotype 0)  the clade's called samples
  *   DIR/unique_variants.vcf   with -u: the tutorial's concatenation, one row per distinct allele in N8's own form (the record
  *                             d_unique holds), one column all_samples
  *   DIR/variant_effects.tsv   with -e annotation.gff3: tjamd_variant_effects on d_unique only, one line per allele: variant_effects.c's
@@ -25,11 +33,11 @@
  * The other options are sample_vcfs.c's.
  *
  *   gcc -O2 -I include examples/merged_vcf.c -L tatajuba_amd -ltatajuba_amd -Wl,-rpath,$PWD/tatajuba_amd -o merged_vcf
- *   ./merged_vcf -r reference.fa [-u] [-D] [-M] [-C T [-G]] [-e annotation.gff3] [-x 1] [-g G] [-s 3] [-k 10] [-m 3] [-c 5] [-d 1] [-l -1] [-o .] sample1.fastq[.gz] ...   */
+ *   ./merged_vcf -r reference.fa [-u] [-D] [-M] [-C T [-G] [-N]] [-e annotation.gff3] [-x 1] [-g G] [-s 3] [-k 10] [-m 3] [-c 5] [-d 1] [-l -1] [-o .] sample1.fastq[.gz] ...   */
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
-#include <tatajuba_groups.h>
+#include <tatajuba_clades.h>
 #include <tatajuba_effects.h>
 #include <tatajuba_locate.h>
 
@@ -79,6 +87,18 @@ open_output (const char *outdir, const char *name)
   return f;
 }
 
+/* a child of the tree in Newick: a sample's name, or (left,right) and the node's marks; then the branch to its parent */
+static void
+print_clade (FILE *fout, int child, long long parent_key, const tjamd_tree_node *nodes, const tjamd_link *links, const int *node_marks, char **sample_name)
+{
+  if (child < 0) { fprintf (fout, "%s:%lld", sample_name[-1 - child], parent_key); return; }
+  fputc ('(', fout);
+  print_clade (fout, nodes[child].left, links[child].key, nodes, links, node_marks, sample_name);
+  fputc (',', fout);
+  print_clade (fout, nodes[child].right, links[child].key, nodes, links, node_marks, sample_name);
+  fprintf (fout, ")%d:%lld", node_marks[child], parent_key - links[child].key);
+}
+
 int
 main (int argc, char **argv)
 {
@@ -87,12 +107,15 @@ main (int argc, char **argv)
   static const char *class_name[5] = {"NONE", "BOUNDARY", "IDENTICAL", "INFRAME", "FRAMESHIFT"};
   long counts[MAX_SAMPLES], total, n_union, n_grouped, n_tracts, n_located, n_gapped = 0, n_var = 0, n_rec, i, cap, ref_bytes, n_contigs = 0, n_names = 0, name_bytes;
   long offsets[MAX_SAMPLES + 1], *contig_len, var_cap, n_sites, n_alleles = 0, s, text_cap = 0;
-  int with_unique = 0, with_depths = 0, with_distances = 0, with_clusters = 0, with_groups = 0;
+  int with_unique = 0, with_depths = 0, with_distances = 0, with_clusters = 0, with_groups = 0, with_clades = 0;
   long long cut = 0;
   long n_links = 0, n_clusters = 0, n_marks = 0;
   tjamd_link *h_links = NULL;
   int *h_cluster = NULL;
-  tjamd_group_mark *h_marks = NULL;
+  tjamd_group_mark *h_marks = NULL, *h_clade_marks = NULL;
+  tjamd_tree_node *h_nodes = NULL;
+  int *h_order = NULL, *h_node_marks = NULL;
+  long n_clade_marks = 0;
   int n = 0, k = 10, m = 3, cov = 5, maxd = 1, lev = -1, mism = 1, max_edits = -1, max_shift = TJAMD_MAX_SHIFT, coverage[MAX_SAMPLES], a, ndev = tjamd_device_count (), status;
   const void *d_records = NULL;
   void *d_keys, *d_counts, *d_ids, *d_grouped, *d_loc, *d_perm, *d_pkeys, *d_pcounts, *d_tracts, *d_tloc, *d_reflen, *d_summary, *d_var, *d_variants, *d_sites, *d_alleles, *d_genotype, *d_unique,
@@ -127,9 +150,10 @@ main (int argc, char **argv)
     else if (!strcmp (argv[a], "-M")) with_distances = 1;
     else if (!strcmp (argv[a], "-C") && a + 1 < argc) { cut = atoll (argv[++a]); with_clusters = with_distances = 1; }
     else if (!strcmp (argv[a], "-G")) with_groups = 1;
+    else if (!strcmp (argv[a], "-N")) with_clades = 1;
     else if (n < MAX_SAMPLES) files[n++] = argv[a];
   }
-  if (n < 1 || !reference || (with_groups && !with_clusters)) { fprintf (stderr, "usage: %s -r reference.fa [-u] [-D] [-M] [-C T [-G]] [-e annotation.gff3] [-x X] [-g G] [-s S] [-k K] [-m M] [-c C] [-d D] [-l L] [-o DIR] sample.fastq[.gz] ...\n", argv[0]); return 2; }
+  if (n < 1 || !reference || ((with_groups || with_clades) && !with_clusters)) { fprintf (stderr, "usage: %s -r reference.fa [-u] [-D] [-M] [-C T [-G] [-N]] [-e annotation.gff3] [-x X] [-g G] [-s S] [-k K] [-m M] [-c C] [-d D] [-l L] [-o DIR] sample.fastq[.gz] ...\n", argv[0]); return 2; }
   if (ndev < 1) { fprintf (stderr, "tatajuba_amd error: no HIP device is visible (there is no CPU fallback)\n"); return 1; }
   if (maxd < 0) maxd = 0;                                 /* src/main.c:190-192 */
   if (maxd > k / 2) maxd = k / 2;
@@ -264,6 +288,27 @@ main (int argc, char **argv)
         if (tjamd_device_download (ctr[0], h_marks, d_marks, (size_t) n_marks * sizeof (tjamd_group_mark))) return fail ("download");
         tjamd_device_free (ctr[0], d_marks);
       }
+      if (with_clades) {                                  /* the links as a tree, and what supports each of its clades: no threshold; sized first, the list is short */
+        void *d_nodes = tjamd_device_alloc (ctr[0], (size_t) n * sizeof (tjamd_tree_node)), *d_order = tjamd_device_alloc (ctr[0], (size_t) n * sizeof (int)),
+             *d_node_marks = tjamd_device_alloc (ctr[0], (size_t) n * sizeof (int)), *d_marks;
+        long rc;
+        if (tjamd_linkage_tree (ctr[0], (const tjamd_link *) d_links, n_links, n, (tjamd_tree_node *) d_nodes, (int *) d_order) < 0) return fail ("linkage tree");
+        rc = tjamd_clade_sites (ctr[0], (const tjamd_site *) d_sites, n_sites, (const int16_t *) d_genotype, n, (const tjamd_tree_node *) d_nodes, (int) n_links, (const int *) d_order, 1,
+                                NULL, NULL, NULL, NULL, 0, &n_clade_marks);
+        if (rc < 0 && rc != -TJAMD_ERR_CAPACITY) return fail ("clade sites");
+        d_marks = tjamd_device_alloc (ctr[0], (size_t) (n_clade_marks ? n_clade_marks : 1) * sizeof (tjamd_group_mark));
+        if (tjamd_clade_sites (ctr[0], (const tjamd_site *) d_sites, n_sites, (const int16_t *) d_genotype, n, (const tjamd_tree_node *) d_nodes, (int) n_links, (const int *) d_order, 1,
+                               NULL, NULL, (int *) d_node_marks, (tjamd_group_mark *) d_marks, n_clade_marks, &n_clade_marks) < 0) return fail ("clade sites");
+        h_nodes = (tjamd_tree_node *) malloc ((size_t) n * sizeof (tjamd_tree_node));
+        h_order = (int *) malloc ((size_t) n * sizeof (int));
+        h_node_marks = (int *) malloc ((size_t) n * sizeof (int));
+        h_clade_marks = (tjamd_group_mark *) malloc ((size_t) (n_clade_marks ? n_clade_marks : 1) * sizeof (tjamd_group_mark));
+        if (tjamd_device_download (ctr[0], h_nodes, d_nodes, (size_t) n_links * sizeof (tjamd_tree_node)) ||
+            tjamd_device_download (ctr[0], h_order, d_order, (size_t) n * sizeof (int)) ||
+            tjamd_device_download (ctr[0], h_node_marks, d_node_marks, (size_t) n_links * sizeof (int)) ||
+            tjamd_device_download (ctr[0], h_clade_marks, d_marks, (size_t) n_clade_marks * sizeof (tjamd_group_mark))) return fail ("download");
+        tjamd_device_free (ctr[0], d_nodes); tjamd_device_free (ctr[0], d_order); tjamd_device_free (ctr[0], d_node_marks); tjamd_device_free (ctr[0], d_marks);
+      }
       tjamd_device_free (ctr[0], d_links); tjamd_device_free (ctr[0], d_cluster);
     }
     tjamd_device_free (ctr[0], d_dist);
@@ -354,8 +399,32 @@ main (int argc, char **argv)
     for (a = 0; a < n; a++) fprintf (fout, "%s\t%d\n", sample_name[a], h_cluster[a]);
     fclose (fout);
     printf ("%ld links, %ld clusters at %lld\n", n_links, n_clusters, cut);
-    free (h_links); free (h_cluster);
   }
+  if (with_clades) {
+    long n_roots = 0;
+    if (!(fout = open_output (outdir, "sample_tree.nwk"))) return 1;
+    for (a = 0; a < n; n_roots++) {                       /* a root starts where the one before it ends: the last node that starts there, or a sample alone */
+      int root = -1 - h_order[a], width = 1;
+      for (i = 0; i < n_links; i++) if (h_nodes[i].first == a) { root = (int) i; width = h_nodes[i].size; }
+      print_clade (fout, root, root >= 0 ? h_links[root].key : 0, h_nodes, h_links, h_node_marks, sample_name);
+      fprintf (fout, ";\n");
+      a += width;
+    }
+    fclose (fout);
+    if (!(fout = open_output (outdir, "clade_sites.tsv"))) return 1;
+    for (i = 0; i < n_clade_marks; i++) {
+      const tjamd_site *site = h_sites + h_clade_marks[i].site;
+      const tjamd_allele *al = h_clade_marks[i].genotype > 0 ? h_alleles + site->first_allele + h_clade_marks[i].genotype - 1 : NULL;
+      if (tjamd_site_ref_alt (site, NULL, k, text, (int) text_cap + 1) < 0) { fprintf (stderr, "site %d has no text\n", h_clade_marks[i].site); return 1; }
+      fprintf (fout, "%d\t%s\t%d\t%s\t", h_clade_marks[i].group, contig_name[site->contig], site->pos, text);
+      if (tjamd_site_ref_alt (site, al, k, text, (int) text_cap + 1) < 0) { fprintf (stderr, "site %d has no text\n", h_clade_marks[i].site); return 1; }
+      fprintf (fout, "%s\t%d\n", text, h_clade_marks[i].n_called);
+    }
+    fclose (fout);
+    printf ("%ld marks of %ld nodes in %ld trees\n", n_clade_marks, n_links, n_roots);
+    free (h_nodes); free (h_order); free (h_node_marks); free (h_clade_marks);
+  }
+  if (with_clusters) { free (h_links); free (h_cluster); }
   if (with_groups) {
     if (!(fout = open_output (outdir, "cluster_sites.tsv"))) return 1;
     for (i = 0; i < n_marks; i++) {

@@ -408,6 +408,10 @@ long tjamd_located_tracts (tjamd_counter *c, const void *d_keys, const void *d_c
 /* The sites that set a group of samples apart from the rest (N16: tjamd_group_sites) are declared, with their timer, in
  * tatajuba_groups.h, which includes tatajuba_linkage.h and through it this header. */
 
+/* The links of that tree as nodes with children and a leaf order, and the sites that support each of its clades without a
+ * cut (N17: tjamd_linkage_tree, tjamd_clade_sites), are declared, with their timers, in tatajuba_clades.h, which includes
+ * tatajuba_groups.h and through it this header. */
+
 /* release the calling thread's shared device contexts of the synchronous string scans (update_hopo_counter_from_seq on a
  * counter that never read a file, tjamd_scan_windows) now; they are released by themselves when the thread ends */
 void tjamd_thread_cleanup (void);

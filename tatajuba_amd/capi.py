@@ -78,6 +78,8 @@ GROUP_CALL_DTYPE = np.dtype([("n_called", "<i4"), ("fixed", "<i4"), ("n_outside"
 GROUP_SITE_DTYPE = np.dtype([("n_called", "<i4"), ("n_genotypes", "<i4"), ("n_marks", "<i4"), ("first_group", "<i4")])  # tjamd_group_site
 GROUP_MARK_DTYPE = np.dtype([("site", "<i4"), ("group", "<i4"), ("genotype", "<i4"), ("n_called", "<i4")])             # tjamd_group_mark
 assert GROUP_CALL_DTYPE.itemsize == 16 and GROUP_SITE_DTYPE.itemsize == 16 and GROUP_MARK_DTYPE.itemsize == 16
+TREE_NODE_DTYPE = np.dtype([("left", "<i4"), ("right", "<i4"), ("first", "<i4"), ("size", "<i4")])    # tjamd_tree_node (include/tatajuba_clades.h)
+assert TREE_NODE_DTYPE.itemsize == 16
 
 
 class TatajubaAmdError(RuntimeError):
@@ -177,6 +179,8 @@ DISTANCE_EXPORTS = ["tjamd_sample_distances", "tjamd_last_sample_distances_ms"]
 LINKAGE_EXPORTS = ["tjamd_sample_linkage", "tjamd_linkage_clusters", "tjamd_last_sample_linkage_ms", "tjamd_last_linkage_clusters_ms"]
 # ... and include/tatajuba_groups.h
 GROUP_EXPORTS = ["tjamd_group_sites", "tjamd_last_group_sites_ms"]
+# ... and include/tatajuba_clades.h
+CLADE_EXPORTS = ["tjamd_linkage_tree", "tjamd_clade_sites", "tjamd_last_linkage_tree_ms", "tjamd_last_clade_sites_ms"]
 MAX_SHIFT = 3                     # TJAMD_MAX_SHIFT
 
 
@@ -350,6 +354,13 @@ def lib():
     L.tjamd_group_sites.argtypes = [C.c_void_p, C.c_void_p, C.c_long, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_long,
                                     C.POINTER(C.c_long)]
     L.tjamd_last_group_sites_ms.restype = C.c_double; L.tjamd_last_group_sites_ms.argtypes = [C.c_void_p]
+    L.tjamd_linkage_tree.restype = C.c_long
+    L.tjamd_linkage_tree.argtypes = [C.c_void_p, C.c_void_p, C.c_long, C.c_int, C.c_void_p, C.c_void_p]
+    L.tjamd_clade_sites.restype = C.c_long
+    L.tjamd_clade_sites.argtypes = [C.c_void_p, C.c_void_p, C.c_long, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                    C.c_long, C.POINTER(C.c_long)]
+    L.tjamd_last_linkage_tree_ms.restype = C.c_double; L.tjamd_last_linkage_tree_ms.argtypes = [C.c_void_p]
+    L.tjamd_last_clade_sites_ms.restype = C.c_double; L.tjamd_last_clade_sites_ms.argtypes = [C.c_void_p]
     L.tjamd_group_contexts.restype = C.c_long
     L.tjamd_group_contexts.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_long]
     L.new_genomic_context_list.restype = C.POINTER(GenomicContextListStruct); L.new_genomic_context_list.argtypes = [P]
@@ -986,6 +997,34 @@ class Counter:
 
     def last_group_sites_ms(self):
         return lib().tjamd_last_group_sites_ms(self._h)
+
+    def linkage_tree(self, d_links, n_links, n_samples, d_nodes, d_order):
+        """tjamd_linkage_tree on device pointers: n_links LINK_DTYPE records over n_samples samples -> one TREE_NODE_DTYPE per
+        link at d_nodes (children, and the clade as an interval of the leaf order) and the leaf order (int32) at d_order.
+        -> n_links"""
+        return self._chkn(lib().tjamd_linkage_tree(self._h, d_links, n_links, n_samples, d_nodes, d_order))
+
+    def clade_sites(self, d_sites, n_sites, d_genotype, n_samples, d_nodes, n_nodes, d_order, min_called, d_calls=None, d_site_out=None, d_node_marks=None,
+                    d_marks=None, mark_capacity=0):
+        """tjamd_clade_sites on device pointers: the int16 genotypes [site][sample] of n_sites SITE_DTYPE records read by the
+        clade of every node (TREE_NODE_DTYPE at d_nodes: an interval of the leaf order at d_order) -> optionally
+        GROUP_CALL_DTYPE [site][node] at d_calls, GROUP_SITE_DTYPE [site] at d_site_out, int32 marks per node at d_node_marks
+        and the marked (site, node) pairs as GROUP_MARK_DTYPE at d_marks.  -> the number of marks; more than mark_capacity
+        raises, and .n_marks of the error is the number to size for"""
+        n_marks = C.c_long(-1)
+        rc = lib().tjamd_clade_sites(self._h, d_sites, n_sites, d_genotype, n_samples, d_nodes, n_nodes, d_order, min_called, d_calls, d_site_out, d_node_marks,
+                                     d_marks, mark_capacity, C.byref(n_marks))
+        if rc < 0:
+            e = TatajubaAmdError(_err())
+            e.n_marks = n_marks.value
+            raise e
+        return rc
+
+    def last_linkage_tree_ms(self):
+        return lib().tjamd_last_linkage_tree_ms(self._h)
+
+    def last_clade_sites_ms(self):
+        return lib().tjamd_last_clade_sites_ms(self._h)
 
     def uses_log(self):
         lib().tjamd_counter_uses_log.restype = C.c_int

@@ -46,6 +46,7 @@
 #include "../../include/tatajuba_distances.h"
 #include "../../include/tatajuba_linkage.h"
 #include "../../include/tatajuba_groups.h"
+#include "../../include/tatajuba_clades.h"
 #include "../../include/tatajuba_locate.h"
 
 typedef unsigned long long u64;
@@ -3876,7 +3877,7 @@ struct StageTimer
 };
 // the intervals of a counter: the last scan call (its partition kernels between the pieces included: tjamd_last_scan_ms takes
 // them out), finalise, the kernels of tjamd_merge_samples, tjamd_tract_stats, tjamd_union_tracts, tjamd_union_tract_stats
-enum { T_SCAN, T_FIN, T_MERGE, T_TRACT, T_UNION, T_UNION_STATS, T_REF, T_LOCATE, T_LOCATED_TRACTS, T_VARIANTS, T_ANNOTATION, T_TRACT_FEATURES, T_SEED_ORDER, T_LOCATE_GAPPED, T_CODING, T_VARIANT_EFFECTS, T_MERGE_VARIANTS, T_SITE_DEPTHS, T_SAMPLE_DISTANCES, T_SAMPLE_LINKAGE, T_LINKAGE_CLUSTERS, T_GROUP_SITES, TJ_N_TIMERS };   // (T_REF to T_LOCATED_TRACTS: N7, T_VARIANTS: N8, the next two: N9; then two of N10; two of N11; then N12, N13, N14, the two of N15 and N16, end of the file)
+enum { T_SCAN, T_FIN, T_MERGE, T_TRACT, T_UNION, T_UNION_STATS, T_REF, T_LOCATE, T_LOCATED_TRACTS, T_VARIANTS, T_ANNOTATION, T_TRACT_FEATURES, T_SEED_ORDER, T_LOCATE_GAPPED, T_CODING, T_VARIANT_EFFECTS, T_MERGE_VARIANTS, T_SITE_DEPTHS, T_SAMPLE_DISTANCES, T_SAMPLE_LINKAGE, T_LINKAGE_CLUSTERS, T_GROUP_SITES, T_LINKAGE_TREE, T_CLADE_SITES, TJ_N_TIMERS };   // (T_REF to T_LOCATED_TRACTS: N7, T_VARIANTS: N8, the next two: N9; then two of N10; two of N11; then N12, N13, N14, the two of N15, N16 and the two of N17, end of the file)
 
 // A finalise between its two halves: finalise_queue fills this in, finalise_collect reads it and sets the state back to
 // FIN_IDLE (nothing begun).  FIN_EVENT: begun, ev_done says when the counts have arrived; FIN_ARRIVED: begun, the stream has
@@ -3939,6 +3940,7 @@ struct tjamd_counter
   int dist_blocks = 0;                                  // TATAJUBA_AMD_DISTANCE_BLOCKS (tests): the workgroups tjamd_sample_distances splits its sites for; 0: four per CU
   int link_small = 1;                                   // TATAJUBA_AMD_LINKAGE_SMALL (tests): 0: tjamd_sample_linkage never takes its single-workgroup path (64 samples and fewer)
   int groups_small = 1;                                 // TATAJUBA_AMD_GROUPS_SMALL (tests): 0: tjamd_group_sites never takes its wavefront-per-site form (64 samples and fewer)
+  int clades_small = 1;                                 // TATAJUBA_AMD_CLADES_SMALL (tests): 0: tjamd_clade_sites never takes its wavefront-per-site form (64 samples and fewer)
   bool buckets_clean = false;
   long plan_mismatches = 0;   // finalises whose in-kernel reading of the kept count differed from the kernel boundary's (expected: 0)
   bool ctr_clean = false;     // the scan counters are zero but for n_undefined (clear_buckets_kernel did it, no scan since)
@@ -4056,6 +4058,8 @@ extern "C" tjamd_counter *tjamd_counter_create (int device, int kmer_size)
   if (ls && !strcmp (ls, "0")) c->link_small = 0;
   const char *gs = getenv ("TATAJUBA_AMD_GROUPS_SMALL");     // test hook: 0 sends every tjamd_group_sites through the workgroup-per-run form with its LDS tables
   if (gs && !strcmp (gs, "0")) c->groups_small = 0;
+  const char *cs = getenv ("TATAJUBA_AMD_CLADES_SMALL");     // test hook: 0 sends every tjamd_clade_sites through the workgroup-per-run form with its LDS scans
+  if (cs && !strcmp (cs, "0")) c->clades_small = 0;
   const char *sl = getenv ("TATAJUBA_AMD_BUCKET_SLACK");
   if (sl && atof (sl) >= 1.0) c->slack = atof (sl);
   HIPCHK_NULL (hipStreamCreateWithFlags (&c->own_stream, hipStreamNonBlocking));
@@ -9747,3 +9751,498 @@ extern "C" long tjamd_group_sites (tjamd_counter *c, const tjamd_site *d_sites, 
   return (long) h[1];
 }
 extern "C" double tjamd_last_group_sites_ms (tjamd_counter *c) { return c ? c->timer[T_GROUP_SITES].ms (c->device) : -1.0; }
+
+// ---- N17: the tree of the links as nodes, and the sites that support each of its clades ------------------------------------
+// The rules as built are in include/tatajuba_clades.h.
+// linkage_tree_kernel: one workgroup.  All lanes check the ends of every link and pack them into LDS; lane 0 then steps through
+//   the links in their order with a union-find in LDS whose root is always its component's smallest member (path halving), so
+//   that `left` needs no second table, and writes children and sizes into LDS; a cycle ends the walk.  Both checks come before
+//   any store to the caller.  The roots, ascending, are the samples that are their own label: a scan of their sizes lays them
+//   out; lane 0 walks the nodes from the last to the first and hands each child its first position, a leaf its place in the
+//   order.  The walk of one lane is the cost of the call; a tree is built once.
+// clade_sites: N16's three steps (a pass that checks and counts, the shared scan, the same kernel compiled with the stores),
+//   with the clade as the group.  A clade is an interval of the leaf order, so a node's record comes from prefix counts over
+//   that order and costs the same at any depth of the tree:
+//   up to 64 samples, clade_sites_small_kernel: a wavefront per site, a lane per leaf position, then a lane per node.  Per
+//     site the ballot of the called positions, per lane the number of called samples that carry its genotype, and the ballot
+//     of the change points (a called position whose genotype differs from the nearest called one before it).  A node's called
+//     members are called & its interval mask; its genotype is that of their first position p0, fixed iff no change point lies
+//     behind p0 inside the interval; both come to the node's lane by one exchange each.  The nodes' intervals sit packed in
+//     LDS, made once per workgroup.
+//   beyond, clade_sites_large_kernel: a workgroup of 1024 walks a run of sites, four consecutive positions a thread.  A scan
+//     of the called flags gives pc[p], the called samples before p, and compacts the called genotypes into gc[rank] in leaf
+//     order; a second scan over the ranks counts the change points up to each rank (kr).  Node j with the interval [f, f + n):
+//     r0 = pc[f], r1 = pc[f + n], n_called = r1 - r0, its genotype gc[r0], fixed iff kr[r1 - 1] == kr[r0].  The carriers of
+//     a genotype are counted as in N16 (LDS atomics behind a fold of equal lanes), the marks of 64 nodes are a ballot word.
+// Global atomics: the error flag, and a node's marks once per workgroup into scratch (the small form: once per mark for the
+// nodes from the 64th on, which a tree of 64 samples does not have).
+
+struct TreeNode { int left, right, first, size; };
+static_assert (sizeof (TreeNode) == 16 && sizeof (TreeNode) == sizeof (tjamd_tree_node), "tree node layout");
+
+#define CLD_MAX 4096                                    // samples, nodes and, by the rule's bound, alleles of a site
+#define CLD_SMALL 64                                    // samples up to which a wavefront takes a site
+#define CLD_THREADS 1024
+#define CLD_PER (CLD_MAX / CLD_THREADS)                 // leaf positions, and nodes, of a thread of the second form
+#define CLD_FOLD 8                                      // distinct genotypes a wavefront folds before its lanes go alone
+#define CLD_WAVE_SITES 64                               // sites a wavefront of the first form is sized for, where there are that many
+
+__global__ __launch_bounds__ (1024)
+void linkage_tree_kernel (const Link *__restrict__ links, int n_links, int ns, TreeNode *__restrict__ nodes, int *__restrict__ order, int *__restrict__ flags)
+{
+  __shared__ int uf[CLD_MAX], cnode[CLD_MAX];           // a sample's label; per root (its component's smallest member) the node that is the component, or -1 - sample
+  __shared__ int nl[CLD_MAX], nr[CLD_MAX], nsz[CLD_MAX], nfi[CLD_MAX];   // the nodes; nfi: a link's packed ends on the way up, a node's first position on the way down
+  __shared__ int sums[2][1024];
+  __shared__ int s_cycle;
+  const int tid = threadIdx.x;
+  int bad = 0;
+  for (int j = tid; j < n_links; j += 1024) {
+    const Link l = links[j];
+    const bool ok = l.a >= 0 && l.a < l.b && l.b < ns;
+    if (!ok) bad = 1;
+    nfi[j] = ok ? (l.a | l.b << 16) : 0;
+  }
+  for (int v = tid; v < ns; v += 1024) { uf[v] = v; cnode[v] = -1 - v; }
+  if (tid == 0) s_cycle = 0;
+  if (__syncthreads_or (bad)) { if (tid == 0) flags[0] = 1; return; }
+  if (tid == 0)
+    for (int j = 0; j < n_links; j++) {
+      int ra = nfi[j] & 0xffff, rb = nfi[j] >> 16;
+      while (uf[ra] != ra) { const int up = uf[uf[ra]]; uf[ra] = up; ra = up; }
+      while (uf[rb] != rb) { const int up = uf[uf[rb]]; uf[rb] = up; rb = up; }
+      if (ra == rb) { s_cycle = 1; break; }
+      const int lo = min (ra, rb), hi = max (ra, rb), cl = cnode[lo], cr = cnode[hi];
+      nl[j] = cl; nr[j] = cr; nsz[j] = (cl >= 0 ? nsz[cl] : 1) + (cr >= 0 ? nsz[cr] : 1);
+      uf[hi] = lo; cnode[lo] = j;
+    }
+  __syncthreads ();
+  if (s_cycle) { if (tid == 0) flags[0] = 2; return; }
+  // the roots in the order of their smallest member, four consecutive samples a thread
+  int mine = 0;
+  #pragma unroll
+  for (int j = 0; j < CLD_PER; j++) {
+    const int v = CLD_PER * tid + j;
+    if (v < ns && uf[v] == v) mine += cnode[v] >= 0 ? nsz[cnode[v]] : 1;
+  }
+  sums[0][tid] = mine;
+  __syncthreads ();
+  int s = 0;
+  for (int o = 1; o < 1024; o <<= 1, s ^= 1) {
+    sums[s ^ 1][tid] = sums[s][tid] + (tid >= o ? sums[s][tid - o] : 0);
+    __syncthreads ();
+  }
+  int at = sums[s][tid] - mine;
+  #pragma unroll
+  for (int j = 0; j < CLD_PER; j++) {
+    const int v = CLD_PER * tid + j;
+    if (v < ns && uf[v] == v) {
+      const int cn = cnode[v];
+      if (cn >= 0) { nfi[cn] = at; at += nsz[cn]; } else order[at++] = v;
+    }
+  }
+  __syncthreads ();
+  if (tid == 0)
+    for (int j = n_links - 1; j >= 0; j--) {            // a parent comes before its children
+      const int f = nfi[j], l = nl[j], r = nr[j], fr = f + (l >= 0 ? nsz[l] : 1);
+      if (l >= 0) nfi[l] = f; else order[f] = -1 - l;
+      if (r >= 0) nfi[r] = fr; else order[fr] = -1 - r;
+    }
+  __syncthreads ();
+  for (int j = tid; j < n_links; j += 1024) nodes[j] = TreeNode {nl[j], nr[j], nfi[j], nsz[j]};
+}
+
+extern "C" long tjamd_linkage_tree (tjamd_counter *c, const tjamd_link *d_links, long n_links, int n_samples, tjamd_tree_node *d_nodes, int *d_order)
+{
+  static const char *fn = "tjamd_linkage_tree";
+  if (!c) return -set_err (TJAMD_ERR_ARG, "%s: null counter", fn);
+  if (!d_order) return -set_err (TJAMD_ERR_ARG, "%s: null d_order", fn);
+  if (n_samples < 1 || n_samples > CLD_MAX) return -set_err (TJAMD_ERR_ARG, "%s: n_samples %d outside 1..4096", fn, n_samples);
+  if (n_links < 0 || n_links > n_samples - 1) return -set_err (TJAMD_ERR_ARG, "%s: n_links %ld outside 0..n_samples - 1 = %d", fn, n_links, n_samples - 1);
+  if (n_links > 0 && (!d_links || !d_nodes)) return -set_err (TJAMD_ERR_ARG, "%s: null link or node buffer", fn);
+  if (tjamd_device_count () <= 0) return -set_err (TJAMD_ERR_NO_DEVICE, "%s: TJAMD_ERR_NO_DEVICE: no HIP device visible (the tree is built on the device; no CPU fallback)", fn);
+  Stage st (c, T_LINKAGE_TREE);                         // (a refused call leaves no timing behind)
+  if (hipSetDevice (c->device) != hipSuccess) return -set_err (TJAMD_ERR_HIP, "hipSetDevice failed");
+  ScratchCut cut;
+  int *flags;
+  cut.take (flags, 64);
+  int rc = cut.commit (c);
+  if (rc) return -rc;
+  if (hipMemsetAsync (flags, 0, 256, c->stream) != hipSuccess) return -set_err (TJAMD_ERR_HIP, "%s: memset failed", fn);
+  st.begin ();
+  hipLaunchKernelGGL (linkage_tree_kernel, dim3 (1), dim3 (1024), 0, c->stream, (const Link *) d_links, (int) n_links, n_samples, (TreeNode *) d_nodes, d_order, flags);
+  st.end ();
+  u32 h_flags[1] = {0};
+  rc = read_back (c, fn, flags, h_flags, 1);
+  if (rc) return -rc;
+  if (h_flags[0] == 1) return -set_err (TJAMD_ERR_ARG, "%s: a link has a < 0, a >= b or b >= n_samples", fn);
+  if (h_flags[0] == 2) return -set_err (TJAMD_ERR_ARG, "%s: a link joins two samples that the links before it have joined: a cycle", fn);
+  st.done ();
+  return n_links;
+}
+extern "C" double tjamd_last_linkage_tree_ms (tjamd_counter *c) { return c ? c->timer[T_LINKAGE_TREE].ms (c->device) : -1.0; }
+
+// words of a call: [0] error bits (1 the order, 2 a node, 4 a site's n_alleles, 8 a cell), [1] the number of marks (the scan's
+// total); from word 64 on: the marks of every node
+struct CladeArgs
+{
+  const Site *sites; long n_sites; const int16_t *geno; int ns; const TreeNode *nodes; int n_nodes; const int *order; int min_called;
+  GroupCall *calls; GroupSite *site_out; int *node_marks; GroupMark *marks; long cap;
+  int *flags, *nm; u32 *cnt;                            // cnt: a site's marks (written by the first pass), then their offsets (read by the second)
+};
+
+template <bool EMIT>
+__global__ __launch_bounds__ (256)
+void clade_sites_small_kernel (const CladeArgs A)
+{
+  __shared__ int s_node[CLD_MAX];                       // first | size << 8 of every node (both at most 64); 0: no node, or a refused one
+  __shared__ int s_seen[4][CLD_SMALL], s_marks[4][CLD_SMALL];
+  if (EMIT && ((volatile const int *) A.flags)[0] != 0) return;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, ns = A.ns, n_nodes = A.n_nodes;
+  if (EMIT && A.node_marks && blockIdx.x == 0)
+    for (int j = tid; j < n_nodes; j += 256) A.node_marks[j] = A.nm[j];
+  int bad = 0, my_marks = 0;
+  for (int j = tid; j < n_nodes; j += 256) {
+    const TreeNode nd = A.nodes[j];
+    const bool ok = nd.size >= 2 && nd.size <= ns && nd.first >= 0 && nd.first <= ns - nd.size;
+    if (!ok) bad |= 2;
+    s_node[j] = ok ? (nd.first | nd.size << 8) : 0;
+  }
+  int smp = lane;                                       // the sample at this lane's leaf position
+  if (lane < ns) {
+    smp = A.order[lane];
+    if (smp < 0 || smp >= ns) { bad |= 1; smp = lane; }
+  }
+  s_seen[wave][lane] = 0;
+  __syncthreads ();
+  if (lane < ns) s_seen[wave][smp] = 1;
+  __syncthreads ();
+  if (lane < ns && !s_seen[wave][lane]) bad |= 1;       // ns positions on ns samples: one sample left out is one sample twice
+  const u64 below = (1ull << lane) - 1ull;
+  for (long i = (long) blockIdx.x * 4 + wave; i < A.n_sites; i += (long) gridDim.x * 4) {
+    const int na = A.sites[i].n_alleles;
+    if (na < 1 || na > ns) {                            // (the whole wavefront)
+      bad |= 4;
+      if (!EMIT && lane == 0) A.cnt[i] = 0;
+      continue;
+    }
+    int g = -1;
+    if (lane < ns) {
+      g = A.geno[i * ns + smp];
+      if (g < -1 || g > na) { bad |= 8; g = -1; }
+    }
+    const u64 called = __ballot (g >= 0);
+    const int all_called = __popcll (called);
+    int carriers = 0, n_genotypes = 0;                  // the called samples that carry this lane's genotype; one step per distinct genotype
+    for (u64 rem = called; rem; n_genotypes++) {
+      const u64 m = __ballot (g == __builtin_amdgcn_readlane (g, __ffsll ((long long) rem) - 1));
+      if ((m >> lane) & 1ull) carriers = __popcll (m);
+      rem &= ~m;
+    }
+    const u64 before = called & below;
+    const int prev = __shfl (g, before ? 63 - __clzll ((long long) before) : lane);
+    const u64 change = __ballot (g >= 0 && before != 0 && prev != g);
+    const long at = EMIT ? (long) A.cnt[i] : 0;
+    int n_marks = 0, first = -1;
+    for (int base = 0; base < n_nodes; base += 64) {    // a lane per node
+      const int j = base + lane, v = j < n_nodes ? s_node[j] : 0, f = v & 0xff, sz = v >> 8;
+      const u64 mask = sz == 0 ? 0ull : (sz >= 64 ? ~0ull : (1ull << sz) - 1ull) << f, cm = called & mask;
+      const int p0 = cm ? __ffsll ((long long) cm) - 1 : 0;
+      const int x = __shfl (g, p0), nx = __shfl (carriers, p0);   // (every lane takes part in every exchange)
+      GroupCall q = {(int) __popcll (cm), -1, 0, 0};
+      if (cm) {
+        q.fixed = (change & mask & ~((2ull << p0) - 1ull)) ? -2 : x;
+        if (q.fixed >= 0) {
+          q.n_outside = nx - q.n_called;
+          q.mark = q.n_called >= A.min_called && q.n_outside == 0 && all_called > q.n_called;
+        }
+      }
+      if (EMIT && A.calls && j < n_nodes) A.calls[i * n_nodes + j] = q;
+      const u64 mb = __ballot (q.mark != 0);
+      if (mb) {
+        if (first < 0) first = base + __ffsll ((long long) mb) - 1;
+        if (q.mark) {
+          if (EMIT) {
+            const long pos = at + n_marks + __popcll (mb & below);
+            if (A.marks && pos < A.cap) A.marks[pos] = GroupMark {(int) i, j, q.fixed, q.n_called};
+          }
+          else if (base == 0) my_marks++;
+          else atomicAdd (&A.nm[j], 1);
+        }
+        n_marks += __popcll (mb);
+      }
+    }
+    if (!EMIT) {
+      if (lane == 0) A.cnt[i] = (u32) n_marks;
+      continue;
+    }
+    if (A.site_out && lane == 0) A.site_out[i] = GroupSite {all_called, n_genotypes, n_marks, first};
+  }
+  if (EMIT) return;
+  if (bad) atomicOr (A.flags, bad);
+  s_marks[wave][lane] = my_marks;
+  __syncthreads ();
+  if (tid < min (n_nodes, 64)) {
+    const int n = s_marks[0][tid] + s_marks[1][tid] + s_marks[2][tid] + s_marks[3][tid];
+    if (n) atomicAdd (&A.nm[tid], n);
+  }
+}
+
+// a wavefront's called samples into the table of the site's genotypes: lanes of one genotype first fold into one lane
+__device__ __forceinline__ void clade_tally (bool active, int g, int lane, int *x_cnt)
+{
+  u64 rem = __ballot (active);
+  #pragma unroll 1
+  for (int it = 0; it < CLD_FOLD && rem; it++) {
+    const int j = __ffsll ((long long) rem) - 1;
+    const u64 m = __ballot (active && g == __builtin_amdgcn_readlane (g, j));
+    if (lane == j) atomicAdd (&x_cnt[g], (int) __popcll (m));
+    rem &= ~m;
+    if ((m >> lane) & 1ull) active = false;
+  }
+  if (active) atomicAdd (&x_cnt[g], 1);
+}
+
+// the sum of `mine` over the threads before this one in a workgroup of 1024, and over all of them; one barrier.  wsum: 16 words
+// that nobody reads or writes between the barrier before the call and the barrier after it
+__device__ __forceinline__ int clade_scan (int mine, int tid, int *wsum, int &total)
+{
+  const int lane = tid & 63, wave = tid >> 6;
+  int incl = mine;
+  #pragma unroll
+  for (int o = 1; o < 64; o <<= 1) {
+    const int v = __shfl_up (incl, o);
+    if (lane >= o) incl += v;
+  }
+  if (lane == 63) wsum[wave] = incl;
+  __syncthreads ();
+  const int w = lane & (CLD_THREADS / 64 - 1);          // every sixteen lanes hold the sixteen sums and fold them among themselves
+  int all = wsum[w], before = w < wave ? all : 0;
+  #pragma unroll
+  for (int o = 1; o < CLD_THREADS / 64; o <<= 1) { all += __shfl_xor (all, o); before += __shfl_xor (before, o); }
+  total = all;
+  return before + incl - mine;
+}
+
+template <bool EMIT>
+__global__ __launch_bounds__ (CLD_THREADS)
+void clade_sites_large_kernel (const CladeArgs A, long per_block)
+{
+  __shared__ int pc[CLD_MAX + 1], gc[CLD_MAX], kr[CLD_MAX], x_cnt[CLD_MAX + 1];
+  __shared__ u64 markbits[CLD_MAX / 64];
+  __shared__ int wsum[2][CLD_THREADS / 64];
+  __shared__ int s_ngeno;
+  if (EMIT && ((volatile const int *) A.flags)[0] != 0) return;
+  const int tid = threadIdx.x, lane = tid & 63, ns = A.ns, n_nodes = A.n_nodes;
+  if (EMIT && A.node_marks && blockIdx.x == 0)
+    for (int j = tid; j < n_nodes; j += CLD_THREADS) A.node_marks[j] = A.nm[j];
+  int bad = 0, smp[CLD_PER], node[CLD_PER], nmarks[CLD_PER];   // node: first | size << 16; 0: no node, or a refused one
+  #pragma unroll
+  for (int k = 0; k < CLD_PER; k++) {
+    const int p = CLD_PER * tid + k, j = tid + CLD_THREADS * k;   // a thread's leaf positions are consecutive, its nodes a workgroup apart
+    smp[k] = p; node[k] = 0; nmarks[k] = 0;
+    if (p < ns) {
+      smp[k] = A.order[p];
+      if (smp[k] < 0 || smp[k] >= ns) { bad |= 1; smp[k] = p; }
+    }
+    if (j < n_nodes) {
+      const TreeNode nd = A.nodes[j];
+      if (nd.size >= 2 && nd.size <= ns && nd.first >= 0 && nd.first <= ns - nd.size) node[k] = nd.first | nd.size << 16;
+      else bad |= 2;
+    }
+    x_cnt[j] = 0;
+  }
+  if (tid < CLD_MAX / 64) markbits[tid] = 0;
+  if (tid == 0) { x_cnt[CLD_MAX] = 0; s_ngeno = 0; }
+  __syncthreads ();
+  #pragma unroll
+  for (int k = 0; k < CLD_PER; k++)
+    if (CLD_PER * tid + k < ns) x_cnt[smp[k]] = 1;
+  __syncthreads ();
+  #pragma unroll
+  for (int k = 0; k < CLD_PER; k++) {                   // ns positions on ns samples: one sample left out is one sample twice
+    const int j = tid + CLD_THREADS * k;
+    if (j < ns && !x_cnt[j]) bad |= 1;
+    x_cnt[j] = 0;
+  }
+  __syncthreads ();
+  const long i0 = (long) blockIdx.x * per_block, i1 = min (A.n_sites, i0 + per_block);
+  for (long i = i0; i < i1; i++) {
+    const int na = A.sites[i].n_alleles;
+    if (na < 1 || na > ns) {                            // (the whole workgroup; the tables are clean)
+      bad |= 4;
+      if (!EMIT && tid == 0) A.cnt[i] = 0;
+      continue;
+    }
+    int g[CLD_PER], mine = 0;
+    #pragma unroll
+    for (int k = 0; k < CLD_PER; k++) {
+      const int p = CLD_PER * tid + k;
+      g[k] = -1;
+      if (p < ns) {
+        g[k] = A.geno[i * ns + smp[k]];
+        if (g[k] < -1 || g[k] > na) { bad |= 8; g[k] = -1; }
+      }
+      mine += g[k] >= 0;
+    }
+    int all_called;
+    int r = clade_scan (mine, tid, wsum[0], all_called);
+    #pragma unroll
+    for (int k = 0; k < CLD_PER; k++) {
+      const int p = CLD_PER * tid + k;
+      if (p < ns) {
+        pc[p] = r;
+        if (g[k] >= 0) gc[r++] = g[k];
+      }
+    }
+    if (tid == 0) pc[ns] = all_called;
+    if (CLD_PER * (tid & ~63) < ns) {                   // (a whole wavefront)
+      const u64 packed = (u64) (g[0] + 1) | (u64) (g[1] + 1) << 16 | (u64) (g[2] + 1) << 32 | (u64) (g[3] + 1) << 48;   // (one body for the four)
+      static_assert (CLD_PER == 4, "four genotypes in a word");
+      #pragma unroll 1
+      for (int k = 0; k < CLD_PER; k++) {
+        const int gk = (int) ((packed >> (16 * k)) & 0xffffull) - 1;
+        clade_tally (gk >= 0, gk, lane, x_cnt);
+      }
+    }
+    __syncthreads ();
+    u32 ch = 0;                                         // bit k: a change point, a called rank whose genotype differs from the rank before it
+    #pragma unroll
+    for (int k = 0; k < CLD_PER; k++) {
+      const int rr = CLD_PER * tid + k;
+      ch |= (u32) (rr >= 1 && rr < all_called && gc[rr] != gc[rr - 1]) << k;
+    }
+    int all_changes;
+    int kb = clade_scan (__popc (ch), tid, wsum[1], all_changes);
+    #pragma unroll
+    for (int k = 0; k < CLD_PER; k++) {
+      const int rr = CLD_PER * tid + k;
+      kb += (ch >> k) & 1u;
+      if (rr < all_called) kr[rr] = kb;
+    }
+    __syncthreads ();
+    u32 marked = 0;                                     // bit k: this thread's k-th node is marked here
+    #pragma unroll 1
+    for (int k = 0; k < CLD_PER; k++) {                 // a thread per node, one body for the four
+      const int j = tid + CLD_THREADS * k, nd = k == 0 ? node[0] : k == 1 ? node[1] : k == 2 ? node[2] : node[3];
+      if (CLD_THREADS * k + (tid & ~63) >= n_nodes) break;   // (a whole wavefront)
+      int nc = 0, fixed = -1, n_outside = 0, mark = 0;
+      if (nd) {
+        const int r0 = pc[nd & 0xffff], r1 = pc[(nd & 0xffff) + (nd >> 16)];
+        nc = r1 - r0;
+        if (nc) {
+          const int x = gc[r0];
+          fixed = kr[r1 - 1] != kr[r0] ? -2 : x;
+          if (fixed >= 0) {
+            n_outside = x_cnt[x] - nc;
+            mark = nc >= A.min_called && n_outside == 0 && all_called > nc;
+          }
+        }
+      }
+      if (EMIT && A.calls && j < n_nodes) A.calls[i * n_nodes + j] = GroupCall {nc, fixed, n_outside, mark};
+      const u64 mb = __ballot (mark != 0);
+      if (lane == 0) markbits[j >> 6] = mb;
+      if (!EMIT) { nmarks[0] += mark & (k == 0); nmarks[1] += mark & (k == 1); nmarks[2] += mark & (k == 2); nmarks[3] += mark & (k == 3); }
+      marked |= (u32) mark << k;
+    }
+    if (EMIT && A.site_out) {                           // the genotypes that somebody carries
+      int nzx = 0;
+      for (int x = tid; x <= na; x += CLD_THREADS) nzx += x_cnt[x] != 0;
+      for (int o = 32; o; o >>= 1) nzx += __shfl_xor (nzx, o);
+      if (nzx && lane == 0) atomicAdd (&s_ngeno, nzx);
+    }
+    __syncthreads ();
+    if (tid < 64) {                                     // the site's marks from the words of its nodes (those beyond n_nodes stay 0)
+      const u64 w = markbits[tid];
+      int n_marks = __popcll (w), first = w ? tid * 64 + __ffsll ((long long) w) - 1 : GRP_NONE;
+      for (int o = 32; o; o >>= 1) { n_marks += __shfl_xor (n_marks, o); first = min (first, __shfl_xor (first, o)); }
+      if (tid == 0) {
+        if (!EMIT) A.cnt[i] = (u32) n_marks;
+        else if (A.site_out) A.site_out[i] = GroupSite {all_called, s_ngeno, n_marks, first == GRP_NONE ? -1 : first};
+        s_ngeno = 0;
+      }
+    }
+    if (EMIT && marked && A.marks) {
+      #pragma unroll 1
+      for (int k = 0; k < CLD_PER; k++) {
+        if (!((marked >> k) & 1u)) continue;
+        const int j = tid + CLD_THREADS * k, nd = k == 0 ? node[0] : k == 1 ? node[1] : k == 2 ? node[2] : node[3];
+        const int r0 = pc[nd & 0xffff], r1 = pc[(nd & 0xffff) + (nd >> 16)];   // (the site's tables stand until the next barrier)
+        long pos = (long) A.cnt[i] + __popcll (markbits[j >> 6] & ((1ull << (j & 63)) - 1ull));   // its rank: the marked nodes below it
+        #pragma unroll 1
+        for (int w = 0; w < (j >> 6); w++) pos += __popcll (markbits[w]);
+        if (pos < A.cap) A.marks[pos] = GroupMark {(int) i, j, gc[r0], r1 - r0};
+      }
+    }
+    for (int x = tid; x <= na; x += CLD_THREADS) x_cnt[x] = 0;   // what this site could touch
+    __syncthreads ();
+  }
+  if (EMIT) return;
+  if (bad) atomicOr (A.flags, bad);
+  #pragma unroll
+  for (int k = 0; k < CLD_PER; k++)
+    if (nmarks[k]) atomicAdd (&A.nm[tid + CLD_THREADS * k], nmarks[k]);
+}
+
+extern "C" long tjamd_clade_sites (tjamd_counter *c, const tjamd_site *d_sites, long n_sites, const int16_t *d_genotype, int n_samples, const tjamd_tree_node *d_nodes, int n_nodes,
+                                   const int *d_order, int min_called, tjamd_group_call *d_calls, tjamd_group_site *d_site_out, int *d_node_marks, tjamd_group_mark *d_marks,
+                                   long mark_capacity, long *h_n_marks)
+{
+  static const char *fn = "tjamd_clade_sites";
+  if (!c) return -set_err (TJAMD_ERR_ARG, "%s: null counter", fn);
+  if (n_sites < 0) return -set_err (TJAMD_ERR_ARG, "%s: n_sites %ld below 0", fn, n_sites);
+  if (n_sites > 0 && (!d_sites || !d_genotype)) return -set_err (TJAMD_ERR_ARG, "%s: null site or genotype buffer", fn);
+  if (!d_order) return -set_err (TJAMD_ERR_ARG, "%s: null d_order", fn);
+  if (n_samples < 1 || n_samples > CLD_MAX) return -set_err (TJAMD_ERR_ARG, "%s: n_samples %d outside 1..4096", fn, n_samples);
+  if (n_nodes < 0 || n_nodes > CLD_MAX) return -set_err (TJAMD_ERR_ARG, "%s: n_nodes %d outside 0..4096", fn, n_nodes);
+  if (!d_nodes && n_nodes > 0) return -set_err (TJAMD_ERR_ARG, "%s: null d_nodes", fn);
+  if (min_called < 1) return -set_err (TJAMD_ERR_ARG, "%s: min_called %d below 1", fn, min_called);
+  if (mark_capacity < 0) return -set_err (TJAMD_ERR_ARG, "%s: mark_capacity %ld below 0", fn, mark_capacity);
+  if (!d_marks && mark_capacity > 0) return -set_err (TJAMD_ERR_ARG, "%s: null d_marks with a capacity of %ld", fn, mark_capacity);
+  if (n_sites >= (1l << 31) || n_sites * (long) n_samples >= (1l << 31)) return -set_err (TJAMD_ERR_ARG, "%s: %ld sites x %d samples: 2^31 cells or more", fn, n_sites, n_samples);
+  if (d_calls && n_sites * (long) n_nodes >= (1l << 31)) return -set_err (TJAMD_ERR_ARG, "%s: %ld sites x %d nodes: 2^31 calls or more", fn, n_sites, n_nodes);
+  if (tjamd_device_count () <= 0) return -set_err (TJAMD_ERR_NO_DEVICE, "%s: TJAMD_ERR_NO_DEVICE: no HIP device visible (the sites are read by clade on the device; no CPU fallback)", fn);
+  Stage st (c, T_CLADE_SITES);                          // (a call that returns no count leaves no timing behind)
+  if (hipSetDevice (c->device) != hipSuccess) return -set_err (TJAMD_ERR_HIP, "hipSetDevice failed");
+  int rc;
+  if (n_sites == 0 || n_nodes == 0) {                   // no site or no node: no mark, no kernel
+    if (d_node_marks && n_nodes > 0 && hipMemsetAsync (d_node_marks, 0, (size_t) n_nodes * sizeof (int), c->stream) != hipSuccess) return -set_err (TJAMD_ERR_HIP, "%s: memset failed", fn);
+    rc = read_back (c, fn, nullptr, nullptr, 0);
+    if (rc) return -rc;
+    if (h_n_marks) *h_n_marks = 0;
+    return 0;
+  }
+  ScratchCut cut;
+  int *flags; u32 *cnt;
+  cut.take (flags, (size_t) 64 + n_nodes); cut.take (cnt, (size_t) n_sites);
+  rc = cut.commit (c);
+  if (!rc) rc = ensure (c->scan_tmp, scan_tmp_words (n_sites) * 4 + 64, c->stream);
+  if (rc) return -rc;
+  if (hipMemsetAsync (flags, 0, ((size_t) 64 + n_nodes) * sizeof (int), c->stream) != hipSuccess) return -set_err (TJAMD_ERR_HIP, "%s: memset failed", fn);
+  const CladeArgs A = {(const Site *) d_sites, n_sites, d_genotype, n_samples, (const TreeNode *) d_nodes, n_nodes, d_order, min_called, (GroupCall *) d_calls, (GroupSite *) d_site_out,
+                       d_node_marks, (GroupMark *) d_marks, mark_capacity, flags, flags + 64, cnt};
+  const bool small = n_samples <= CLD_SMALL && c->clades_small;
+  // the first form: wavefronts that take a site each in turn, CLD_WAVE_SITES / 4 or more a wavefront where there are that many; the second: two workgroups a CU, each a run of sites
+  const long blocks = small ? std::max (1l, std::min ((n_sites + CLD_WAVE_SITES - 1) / CLD_WAVE_SITES, 8l * c->n_cu)) : std::min (n_sites, 2l * c->n_cu);
+  const long per_block = (n_sites + blocks - 1) / blocks;
+  const unsigned grid = (unsigned) (small ? blocks : (n_sites + per_block - 1) / per_block);
+  st.begin ();
+  if (small) hipLaunchKernelGGL (clade_sites_small_kernel<false>, dim3 (grid), dim3 (256), 0, c->stream, A);
+  else hipLaunchKernelGGL (clade_sites_large_kernel<false>, dim3 (grid), dim3 (CLD_THREADS), 0, c->stream, A, per_block);
+  rc = exclusive_scan (c, cnt, cnt, n_sites, (u32 *) flags + 1, (u32 *) c->scan_tmp.p, c->scan_tmp.cap / 4);
+  if (rc) return -rc;
+  if (small) hipLaunchKernelGGL (clade_sites_small_kernel<true>, dim3 (grid), dim3 (256), 0, c->stream, A);
+  else hipLaunchKernelGGL (clade_sites_large_kernel<true>, dim3 (grid), dim3 (CLD_THREADS), 0, c->stream, A, per_block);
+  st.end ();
+  u32 h[2] = {0, 0};
+  rc = read_back (c, fn, flags, h, 2);
+  if (rc) return -rc;
+  if (h[0] & 1u) return -set_err (TJAMD_ERR_ARG, "%s: d_order is not a permutation of 0 .. n_samples - 1", fn);
+  if (h[0] & 2u) return -set_err (TJAMD_ERR_ARG, "%s: a node has size < 2, first < 0 or first + size above n_samples %d", fn, n_samples);
+  if (h[0] & 4u) return -set_err (TJAMD_ERR_ARG, "%s: a site has n_alleles < 1 or above n_samples %d", fn, n_samples);
+  if (h[0] & 8u) return -set_err (TJAMD_ERR_ARG, "%s: a genotype cell is below -1 or above its site's n_alleles", fn);
+  if (h_n_marks) *h_n_marks = (long) h[1];
+  if ((long) h[1] > mark_capacity) return -set_err (TJAMD_ERR_CAPACITY, "%s: %u marks, caller capacity %ld", fn, h[1], mark_capacity);
+  st.done ();
+  return (long) h[1];
+}
+extern "C" double tjamd_last_clade_sites_ms (tjamd_counter *c) { return c ? c->timer[T_CLADE_SITES].ms (c->device) : -1.0; }
