@@ -116,10 +116,15 @@ int  tjamd_finalise (tjamd_counter *c, int remove_biased, int min_coverage, int 
  * sample's scan, queued on another counter of the same stream in between, runs on) and returns what tjamd_finalise
  * returns.  Between the two calls the counter must not be touched. */
 int  tjamd_finalise_begin (tjamd_counter *c, int remove_biased, int min_coverage);
-/* A second HIP stream for the ordering step (bin partition, sort, index, coverage: five small launches whose time is latency)
- * of a finalise begun with tjamd_finalise_begin: it then runs behind an event, beside whatever the counter's own stream
- * does next -- the next sample's scan on another counter.  NULL: none (everything on the counter's stream, the default;
- * measured on one MI355X: no gain while a scan fills the device). */
+/* The HIP stream for the ordering step (bin partition, sort, index, coverage: six small launches whose time is latency)
+ * of a finalise begun with tjamd_finalise_begin: the step runs there behind an event, beside whatever the counter's own
+ * stream does next -- the next sample's scan on another counter; its kernels are sized to start on a CU that the
+ * scan's workgroups fill (DESIGN.md sections 3.4 and 5).  A stream handle means that stream; NULL means none
+ * (everything on the counter's stream).  A counter on which this was never called uses a side stream that the library
+ * owns: one per device for the whole process, made when first needed and released with the last counter that used it.
+ * TATAJUBA_AMD_ORDER=main in the environment when a counter is created gives that counter none instead (A/B runs,
+ * tests); a later call of this function still decides.  tjamd_finalise and a step that has to be run again with the
+ * count in hand stay on the counter's stream whatever is set here. */
 int  tjamd_counter_set_order_stream (tjamd_counter *c, void *hip_stream);
 int  tjamd_finalise_end (tjamd_counter *c, int *status);
 long tjamd_kept_count (tjamd_counter *c);
@@ -420,8 +425,12 @@ void tjamd_thread_cleanup (void);
 double tjamd_last_scan_ms (tjamd_counter *c);       /* scan kernel(s) of the last tjamd_scan_* call */
 int    tjamd_counter_uses_log (const tjamd_counter *c);  /* 1: k <= 12 and the scan writes a record log that partition_log_kernel distributes (default); 0: the scan kernels partition by themselves (k > 12, or TATAJUBA_AMD_SINK=fused) */
 double tjamd_last_partition_ms (tjamd_counter *c);  /* partition_log_kernel behind the last scan launch (k <= 12); 0 if the scan kernel partitioned by itself */
+/* whole device finalise of the last tjamd_finalise call, or tjamd_finalise_begin / _end pair.  After a pair whose ordering
+ * step went to another stream (tjamd_counter_set_order_stream; the default) the interval begins on the counter's stream
+ * and ends on that one: it includes the time the step spent sharing CUs with the next sample's scan and is no measure
+ * of what the finalise costs the pipeline -- that is the time per sample, bench.py's ms_per_step. */
 double tjamd_last_finalise_ms (tjamd_counter *c);
-double tjamd_last_merge_ms (tjamd_counter *c);      /* kernels of the last tjamd_merge_samples on this counter */   /* whole device finalise of the last tjamd_finalise call */
+double tjamd_last_merge_ms (tjamd_counter *c);      /* kernels of the last tjamd_merge_samples on this counter */
 double tjamd_last_tract_stats_ms (tjamd_counter *c); /* the last tjamd_tract_stats on this counter, first launch to last (host waits included) */
 double tjamd_last_union_tracts_ms (tjamd_counter *c);      /* the last tjamd_union_tracts, first launch to last (host waits included) */
 double tjamd_last_union_tract_stats_ms (tjamd_counter *c); /* the last tjamd_union_tract_stats, first launch to last */

@@ -1582,8 +1582,13 @@ __device__ __forceinline__ void lds_dma32 (const uint8_t *sbase, u32 voff, void 
                 :: "v"(voff), "s"(sbase), "{m0}"(m0v) : "memory");
 }
 
+// (88 scalar registers at most.  A SIMD hands out its 800 in blocks of 16, plus 16 per wavefront: the log variant took 106,
+// six wavefronts of 112 + 16 left 32, and no kernel could start beside it although registers, wavefront slots and LDS were
+// there -- the ordering step of the sample before, queued on the side stream, waited for the scan's end.  At 86 (ten more
+// values kept in lanes of a vector register) six wavefronts take 672 and leave 128: a guest of up to 112.  The variants that
+// partition by themselves are bounded to four wavefronts per SIMD and keep their 106; tests/test_order_budget.py)
 template <int W, bool LOG = false>
-__global__ __launch_bounds__ (FK_BLOCK, FK_BLOCK * (LOG ? FK_LOG_WG_PER_CU : FK_WG_PER_CU) / 256)
+__global__ __launch_bounds__ (FK_BLOCK, FK_BLOCK * (LOG ? FK_LOG_WG_PER_CU : FK_WG_PER_CU) / 256) __attribute__ ((amdgpu_num_sgpr (88)))
 void scan_fast_kernel (const uint8_t *__restrict__ seq, long n_bytes, long n_ftiles, int k, int mprime,
                        Buckets BK, DevCounters *ctr, u32 *__restrict__ slow_list, int par, int all_slow, LogSpace LG)
 {
@@ -3137,54 +3142,92 @@ void bin_count_kernel (const u64 *__restrict__ in, long n, int k, int nbits, u32
   }
 }
 
-// Exclusive prefix of n values by one workgroup of 1024 threads, WGS_CHUNK at a time with a running carry: coalesced
-// load into LDS, every thread sums a contiguous slice, one scan over the slice sums, coalesced store.  Returns the
-// total; vmax = largest value.
+// Exclusive prefix of n values by one workgroup of WGS_THREADS threads, WGS_CHUNK at a time with a running carry: every
+// thread holds WGS_PER contiguous words in registers (16-byte loads, in flight together), sums them, one scan over
+// the threads' sums, and the thread writes its words' prefixes where it read the words.  Returns the total; vmax =
+// largest value.
+// Four wavefronts, a few words of LDS and (see ORDER_KERNEL) at most 32 registers: the ordering step's kernels are
+// sized to start beside three resident workgroups of scan_fast_kernel<1, true>, which leave a CU one wavefront of 32
+// registers per SIMD and 58 KB of LDS.  The kernel's time is a chain of round trips, much the same for four wavefronts
+// as for sixteen.
 #define BS_MAXBINS (1 << BS_MAXBITS)
-#define WGS_CHUNK  16384
+#define WGS_THREADS 256
+#define WGS_WAVES  (WGS_THREADS / 64)
+#define WGS_PER    8                    // (sixteen: 39 registers, or scratch under the cap)
+#define WGS_CHUNK  (WGS_THREADS * WGS_PER)
+// A kernel of the ordering step's planned path: workgroups of four wavefronts at most, 32 registers at most (the
+// attribute counts in pairs on a device whose vector and accumulation registers are one file: 16 states 32).  The
+// compiler keeps to the cap by spilling if it must, so the cap alone proves nothing: tests/test_order_budget.py reads
+// registers, scratch and LDS from the compiler's remarks.
+#define ORDER_REGS   __attribute__ ((amdgpu_num_vgpr (16)))
+#define ORDER_KERNEL __launch_bounds__ (256) ORDER_REGS
 
-#define WGS_PAD(i) ((i) + ((i) >> 5))      // one pad word per 32: a thread's contiguous slice does not collide with its neighbours' banks
-struct WgScanLds { u32 a[WGS_CHUNK + WGS_CHUNK / 32 + 1]; u32 wsum[16]; u32 vmax; };
+struct WgScanLds { u32 wsum[2][WGS_WAVES]; u32 vmax; };   // (the sums of odd and even chunks apart: one barrier per chunk)
 
 __device__ __forceinline__ u32 wg_exclusive_scan (const u32 *__restrict__ in, int n_all, u32 *__restrict__ out, u32 *__restrict__ out2, WgScanLds &L, u32 &vmax)
 {
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  if (tid == 0) L.vmax = 0;
-  u32 carry = 0;
-  for (int base = 0; base < n_all; base += WGS_CHUNK) {
-    const int n = min (WGS_CHUNK, n_all - base);
-    const int per = (n + 1023) / 1024;
-    for (int i = tid; i < n; i += 1024) L.a[WGS_PAD (i)] = in[base + i];
+  // (arrays that are not 16-byte material -- fewer than four bins, in practice: one thread, one word at a time)
+  if ((((size_t) in | (size_t) out | (size_t) out2) & 15) != 0 || (n_all & 3) != 0) {
+    u32 run = 0, mx = 0;
+    if (tid == 0) {
+      for (int i = 0; i < n_all; i++) { const u32 v = in[i]; out[i] = run; if (out2) out2[i] = run; run += v; mx = max (mx, v); }
+      L.wsum[0][0] = run; L.vmax = mx;
+    }
     __syncthreads ();
+    vmax = L.vmax;
+    return L.wsum[0][0];
+  }
+  if (tid == 0) L.vmax = 0;
+  __syncthreads ();
+  u32 carry = 0;
+  int par = 0;
+  for (int base = 0; base < n_all; base += WGS_CHUNK, par ^= 1) {
+    const int i0 = base + tid * WGS_PER;
+    uint4 v[WGS_PER / 4];
+#pragma unroll
+    for (int q = 0; q < WGS_PER / 4; q++) {                // (n_all is a multiple of four: a 16-byte piece is inside or outside)
+      v[q] = make_uint4 (0, 0, 0, 0);
+      if (i0 + 4 * q < n_all) v[q] = *reinterpret_cast<const uint4 *> (in + i0 + 4 * q);
+    }
     u32 sum = 0, mx = 0;
-    for (int j = 0; j < per; j++) { const int b = tid * per + j; if (b < n) { const u32 v = L.a[WGS_PAD (b)]; sum += v; mx = max (mx, v); } }
+#pragma unroll
+    for (int q = 0; q < WGS_PER / 4; q++) { sum += v[q].x + v[q].y + v[q].z + v[q].w; mx = max (max (mx, max (v[q].x, v[q].y)), max (v[q].z, v[q].w)); }
     const u32 incl = wave_inclusive_scan (sum);
-    if (lane == 63) L.wsum[wave] = incl;
+    if (lane == 63) L.wsum[par][wave] = incl;
     for (int o = 32; o > 0; o >>= 1) mx = max (mx, (u32) __shfl_down ((int) mx, o));
     if (lane == 0 && mx) atomicMax (&L.vmax, mx);
     __syncthreads ();
     u32 run = carry + incl - sum, total = 0;
-    for (int w = 0; w < 16; w++) { const u32 x = L.wsum[w]; if (w < wave) run += x; total += x; }
-    for (int j = 0; j < per; j++) { const int b = tid * per + j; if (b < n) { const u32 v = L.a[WGS_PAD (b)]; L.a[WGS_PAD (b)] = run; run += v; } }
-    __syncthreads ();
-    for (int i = tid; i < n; i += 1024) { const u32 v = L.a[WGS_PAD (i)]; out[base + i] = v; if (out2) out2[base + i] = v; }
+    for (int w = 0; w < WGS_WAVES; w++) { const u32 x = L.wsum[par][w]; if (w < wave) run += x; total += x; }
+#pragma unroll
+    for (int q = 0; q < WGS_PER / 4; q++) {
+      uint4 o;
+      o.x = run; run += v[q].x; o.y = run; run += v[q].y; o.z = run; run += v[q].z; o.w = run; run += v[q].w;
+      if (i0 + 4 * q < n_all) {
+        *reinterpret_cast<uint4 *> (out + i0 + 4 * q) = o;
+        if (out2) *reinterpret_cast<uint4 *> (out2 + i0 + 4 * q) = o;
+      }
+    }
     carry += total;
-    __syncthreads ();
   }
+  __syncthreads ();
   vmax = L.vmax;
   return carry;
 }
 
 // bin counts -> binstart[0..nbins] and the scatter cursors (bins[] itself); a bin above rank_max switches the whole
-// sort to the radix path (flag in FinCounts)
-__global__ __launch_bounds__ (1024)
-void bin_scan_kernel (u32 *__restrict__ bins, int nbins, u32 *__restrict__ binstart, u32 rank_max, FinCounts *fin, const FinPlan *__restrict__ plan = nullptr)
+// sort to the radix path (flag in FinCounts).  full (where given): the list of fuller bins that bin_sort_index_kernel
+// writes, emptied here.
+__global__ ORDER_KERNEL
+void bin_scan_kernel (u32 *__restrict__ bins, int nbins, u32 *__restrict__ binstart, u32 rank_max, FinCounts *fin, const FinPlan *__restrict__ plan = nullptr,
+                      u32 *__restrict__ full = nullptr)
 {
   __shared__ WgScanLds L;
   u32 vmax;
   if (plan) { if (!plan->ok) return; nbins = plan->nbins; }
   const u32 total = wg_exclusive_scan (bins, nbins, binstart, bins, L, vmax);
-  if (threadIdx.x == 0) { binstart[nbins] = total; fin->sort_fallback = vmax > rank_max ? 1u : 0u; }
+  if (threadIdx.x == 0) { binstart[nbins] = total; fin->sort_fallback = vmax > rank_max ? 1u : 0u; if (full) full[0] = 0u; }
 }
 
 __global__ __launch_bounds__ (256)
@@ -3425,7 +3468,7 @@ void cov_max_kernel (const u64 *__restrict__ tab, long t, int *result)
 // size are all found among the bin's records -- and the coverage table takes the records in any order.
 //   binctx[bin]        contexts of the bin that reach min_coverage
 //   tstart/tend[st+o]  index range of the o-th such context of the bin (st = first record of the bin)
-#define BSI_WAVES 1
+#define BSF_GRID 1024                   // workgroups of bin_sort_full_kernel (one wavefront each) at most
 
 // the value that lane (lane ^ J) holds, without the LDS pipe: quad permutes for 1 and 2, a row shift either way for 4 and 8,
 // gfx950's row and half swaps for 16 and 32 (a ds_bpermute per word and step kept the LDS pipe busy for half of the sort
@@ -3436,40 +3479,48 @@ __device__ __forceinline__ u32 lane_xor (u32 v, int lane)
   if constexpr (J == 1) return (u32) __builtin_amdgcn_update_dpp (0, (int) v, 0xB1, 0xF, 0xF, false);        // quad_perm [1,0,3,2]
   else if constexpr (J == 2) return (u32) __builtin_amdgcn_update_dpp (0, (int) v, 0x4E, 0xF, 0xF, false);   // quad_perm [2,3,0,1]
   else if constexpr (J == 4 || J == 8) {
-    const u32 up = (u32) __builtin_amdgcn_update_dpp (0, (int) v, 0x100 + J, 0xF, 0xF, false);               // row_shl: lane i gets lane i + J
-    const u32 dn = (u32) __builtin_amdgcn_update_dpp (0, (int) v, 0x110 + J, 0xF, 0xF, false);               // row_shr: lane i gets lane i - J
-    return (lane & J) ? dn : up;
+    // (a bank is four lanes of a row: the banks whose lanes have bit J clear take the shift down from above, the others then
+    // the shift up from below, into the same register -- no second value to choose from, which cost a register per word)
+    constexpr int lo = J == 4 ? 0x5 : 0x3;
+    const int up = __builtin_amdgcn_update_dpp (0, (int) v, 0x100 + J, 0xF, lo, false);                      // row_shl: lane i gets lane i + J
+    return (u32) __builtin_amdgcn_update_dpp (up, (int) v, 0x110 + J, 0xF, 0xF ^ lo, false);                 // row_shr: lane i gets lane i - J
   }
   else if constexpr (J == 16) { const auto r = __builtin_amdgcn_permlane16_swap (v, v, false, false); return (lane & 16) ? r[0] : r[1]; }
   else { const auto r = __builtin_amdgcn_permlane32_swap (v, v, false, false); return (lane & 32) ? r[0] : r[1]; }
 }
 
-__global__ __launch_bounds__ (64 * BSI_WAVES)
-void bin_sort_index_kernel (const u64 *__restrict__ in, u64 *__restrict__ out, const u32 *__restrict__ binstart, int nbins, const FinCounts *fin,
-                            int min_coverage, u64 *__restrict__ cov_tab, int log2t,
-                            u32 *__restrict__ binctx, u32 *__restrict__ tstart, u32 *__restrict__ tend, const FinPlan *__restrict__ plan = nullptr,
-                            int cov_direct = 0)
+// Two kernels share this body, both within the ordering step's register budget (ORDER_KERNEL: one wavefront of 32
+// registers per SIMD is what a CU full of scanning workgroups has left).  FULL = false, bin_sort_index_kernel: every bin
+// in turn; a bin of at most 64 records is sorted across the lanes, a fuller one is only written to the list `full`
+// (full[0]: how many, emptied by bin_scan_kernel; then the bins) -- as scan_fast_kernel lists its slow tiles -- because
+// ranking it keeps much more alive than the sort does.  FULL = true, bin_sort_full_kernel, right behind on the same
+// stream: the listed bins, ranked through LDS.
+template <bool FULL>
+__device__ __forceinline__ void bin_sort_index_bins (const u64 *__restrict__ in, u64 *__restrict__ out, const u32 *__restrict__ binstart, int nbins, const FinCounts *fin,
+                                                     int min_coverage, u64 *__restrict__ cov_tab, int log2t,
+                                                     u32 *__restrict__ binctx, u32 *__restrict__ tstart, u32 *__restrict__ tend, const FinPlan *__restrict__ plan,
+                                                     int cov_direct, u32 *__restrict__ full, u32 *H, u32 *E)
 {
-  // (2 KB of LDS per wavefront: the usual bin lives in registers, a fuller one reads its records where they lie -- with the
-  // records of up to 256 staged in LDS, 8 KB, twenty wavefronts fitted a CU instead of twenty-eight, and a wavefront's
-  // time is a chain of memory round trips that only other wavefronts can fill)
-  __shared__ alignas (16) u32 hd[BSI_WAVES][BS_RANK_MAX];
-  __shared__ u32 sz[BSI_WAVES][BS_RANK_MAX];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int lane = threadIdx.x & 63;
   // (the first bin's bounds are asked for together with the plan: one round trip less in the chain; `nbins` as passed is
   // the layout's size, which the array has whatever the plan says)
-  const int bin0 = (int) blockIdx.x * BSI_WAVES + wave;
+  const int bin0 = (int) blockIdx.x;
   u32 st0 = 0, en0 = 0;
-  if (bin0 < nbins) { st0 = binstart[bin0]; en0 = binstart[bin0 + 1]; }
+  if (!FULL && bin0 < nbins) { st0 = binstart[bin0]; en0 = binstart[bin0 + 1]; }
   if (plan) { if (!plan->ok) return; nbins = plan->nbins; log2t = plan->log2t; cov_direct = (int) plan->cov_direct; }
   if (fin->sort_fallback) return;                       // some bin is too full: the caller takes the radix path
-  u32 *H = hd[wave], *E = sz[wave];
-  for (int bin = bin0; bin < nbins; bin += gridDim.x * BSI_WAVES) {
-    const u32 st = (bin == bin0) ? st0 : binstart[bin], s = ((bin == bin0) ? en0 : binstart[bin + 1]) - st;
+  const u32 n_turns = FULL ? min (full[0], (u32) nbins) : (u32) nbins;
+  for (u32 turn = blockIdx.x; turn < n_turns; turn += gridDim.x) {
+    const int bin = FULL ? (int) full[1 + turn] : (int) turn;
+    const u32 st = (!FULL && bin == bin0) ? st0 : binstart[bin], s = ((!FULL && bin == bin0) ? en0 : binstart[bin + 1]) - st;
     if (s == 0) { if (lane == 0) binctx[bin] = 0; continue; }
     const u64 *R = in + 3 * (u64) st;                   // the bin's records (a fuller bin reads them from here, the same record in every lane)
     u32 nkeep = 0;
-    if (s <= 64u) {
+    if constexpr (!FULL) {
+      if (s <= 64u) {
+        // the usual bin: sorted across the lanes, below
+      }
+      else { if (lane == 0) full[1u + atomicAdd (&full[0], 1u)] = (u32) bin; continue; }
       // The usual bin (a record per lane at most): a bitonic sort of the records across the wavefront's lanes -- 21
       // compare-and-exchange steps of some thirty instructions -- instead of every lane comparing its record with every
       // record of the bin (s / 4 turns of 180); sorted, a record's place is its lane, a context's records are neighbours,
@@ -3482,9 +3533,12 @@ void bin_sort_index_kernel (const u64 *__restrict__ in, u64 *__restrict__ out, c
       // home slots first and adding where the key is already there, one atomic per flank instead of two -- no change, 177
       // against 179 us on the long-read sample: it is the random 8-byte accesses to a 64 MB table that this kernel waits for
       // there, whatever their kind)
+      // (what outlives the sort of the record as it was loaded is its two 31-bit flanks and its count, three registers: the
+      // kernel has 32 in all)
       const int w = meta_count (am);
+      const u32 ka = (u32) a0 & 0x7FFFFFFFu, kb = (u32) a1 & 0x7FFFFFFFu;
       u64 cas_a = 0, cas_b = 0;
-      if (!cov_direct && valid) cov_add2_issue ((u32) (a0 & 0x7FFFFFFFull), (u32) (a1 & 0x7FFFFFFFull), w, cov_tab, log2t, cas_a, cas_b);
+      if (!cov_direct && valid) cov_add2_issue (ka, kb, w, cov_tab, log2t, cas_a, cas_b);
       // order: records before empty lanes, then base, ctx0, ctx1, signed length, all descending (record_before); kh holds
       // what comes before the contexts, kl what comes after them (a lane's own number last: no two lanes compare equal)
       u32 kh = valid ? 2u | ((u32) am & 1u) : 0u;
@@ -3545,14 +3599,14 @@ void bin_sort_index_kernel (const u64 *__restrict__ in, u64 *__restrict__ out, c
       }
       else if (valid) {
         asm volatile ("" : "+v"(cas_a), "+v"(cas_b));      // (or the compiler tests them for zero, and waits, ahead of the sort)
-        cov_add2_finish ((u32) (a0 & 0x7FFFFFFFull), (u32) (a1 & 0x7FFFFFFFull), w, cov_tab, log2t, cas_a, cas_b);
+        cov_add2_finish (ka, kb, w, cov_tab, log2t, cas_a, cas_b);
       }
       if (lane == 0) binctx[bin] = nkeep;
       asm volatile ("s_waitcnt lgkmcnt(0)" ::: "memory");
       __builtin_amdgcn_wave_barrier ();
       continue;
     }
-    for (u32 t0 = 0; t0 < s; t0 += 64) {
+    for (u32 t0 = 0; t0 < s; t0 += 64) {                  // (FULL only: the other kernel has listed the bin and gone on)
       const u32 t = t0 + lane;
       bool keep = false;
       if (t < s) {
@@ -3620,8 +3674,31 @@ void bin_sort_index_kernel (const u64 *__restrict__ in, u64 *__restrict__ out, c
   }
 }
 
+__global__ __launch_bounds__ (64) ORDER_REGS
+void bin_sort_index_kernel (const u64 *__restrict__ in, u64 *__restrict__ out, const u32 *__restrict__ binstart, int nbins, const FinCounts *fin,
+                            int min_coverage, u64 *__restrict__ cov_tab, int log2t,
+                            u32 *__restrict__ binctx, u32 *__restrict__ tstart, u32 *__restrict__ tend, u32 *__restrict__ full,
+                            const FinPlan *__restrict__ plan = nullptr, int cov_direct = 0)
+{
+  bin_sort_index_bins<false> (in, out, binstart, nbins, fin, min_coverage, cov_tab, log2t, binctx, tstart, tend, plan, cov_direct, full, nullptr, nullptr);
+}
+
+__global__ __launch_bounds__ (64) ORDER_REGS
+void bin_sort_full_kernel (const u64 *__restrict__ in, u64 *__restrict__ out, const u32 *__restrict__ binstart, int nbins, const FinCounts *fin,
+                           int min_coverage, u64 *__restrict__ cov_tab, int log2t,
+                           u32 *__restrict__ binctx, u32 *__restrict__ tstart, u32 *__restrict__ tend, u32 *__restrict__ full,
+                           const FinPlan *__restrict__ plan = nullptr, int cov_direct = 0)
+{
+  // (2 KB of LDS: a bin's records are read where they lie, the same record in every lane -- with the records of up to 256
+  // staged in LDS, 8 KB, fewer wavefronts fitted a CU, and a wavefront's time is a chain of memory round trips that only
+  // other wavefronts can fill)
+  __shared__ alignas (16) u32 hd[BS_RANK_MAX];
+  __shared__ u32 sz[BS_RANK_MAX];
+  bin_sort_index_bins<true> (in, out, binstart, nbins, fin, min_coverage, cov_tab, log2t, binctx, tstart, tend, plan, cov_direct, full, hd, sz);
+}
+
 // one workgroup: exclusive prefix of binctx -> binout, number of index ranges, coverage start value
-__global__ __launch_bounds__ (1024)
+__global__ ORDER_KERNEL
 void bin_ctx_scan_kernel (const u32 *__restrict__ binctx, int nbins, u32 *__restrict__ binout, FinCounts *fin, const FinPlan *__restrict__ plan = nullptr)
 {
   __shared__ WgScanLds L;
@@ -3632,7 +3709,7 @@ void bin_ctx_scan_kernel (const u32 *__restrict__ binctx, int nbins, u32 *__rest
 }
 
 // index ranges in order (reference: idx_initial / idx_final, src/hopo_counter.c:388-404) + the coverage maximum
-__global__ __launch_bounds__ (256)
+__global__ ORDER_KERNEL
 void bin_ctx_write_kernel (const u32 *__restrict__ binstart, const u32 *__restrict__ binctx, const u32 *__restrict__ binout, int nbins,
                            const u32 *__restrict__ tstart, const u32 *__restrict__ tend, int *__restrict__ idx_initial, int *__restrict__ idx_final,
                            const u64 *__restrict__ cov_tab, long t, FinCounts *fin, const FinPlan *__restrict__ plan = nullptr)
@@ -3643,9 +3720,27 @@ void bin_ctx_write_kernel (const u32 *__restrict__ binstart, const u32 *__restri
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   for (int bin = blockIdx.x * 4 + wave; bin < nbins; bin += gridDim.x * 4) {
     const u32 cnt = binctx[bin], st = binstart[bin], o0 = binout[bin];
+#pragma unroll 1
     for (u32 o = lane; o < cnt; o += 64) { idx_initial[o0 + o] = (int) tstart[st + o]; idx_final[o0 + o] = (int) tend[st + o]; }
   }
-  cov_max_part (cov_tab, t, &fin->coverage, s_best);
+  // (cov_max_part with 32-bit indices -- a table has 2^31 slots at most, see cov_table_bits -- two slots per load and a fixed
+  // unroll: written over `long` with the launch's sizes the loop cost 38 registers, six more than the ordering step's budget)
+  int best = INT_MIN;
+  const uint4 *tab2 = reinterpret_cast<const uint4 *> (cov_tab);
+  const u32 half = (u32) (t >> 1);                       // (t is a power of two, 1024 at least)
+#pragma unroll 2
+  for (u32 i = blockIdx.x * 256u + threadIdx.x; i < half; i += gridDim.x * 256u) {
+    const uint4 v = tab2[i];
+    if (v.y) best = max (best, (int) v.x);
+    if (v.w) best = max (best, (int) v.z);
+  }
+  for (int o = 32; o > 0; o >>= 1) best = max (best, __shfl_down (best, o));
+  if (lane == 0) s_best[wave] = best;
+  __syncthreads ();
+  if (threadIdx.x == 0) {
+    for (int w = 1; w < 4; w++) best = max (best, s_best[w]);
+    if (best != INT_MIN) atomicMax (&fin->coverage, best);
+  }
 }
 
 // ---- cross-sample merge on the bins --------------------------------------------------------------------------------
@@ -3930,6 +4025,12 @@ struct tjamd_counter
   hipEvent_t ev_done = nullptr;                         // tjamd_finalise_begin: the counts have reached the host
   hipEvent_t ev_agg = nullptr;                          // the aggregation and the clearing of the buckets are done (order_stream waits for it)
   hipStream_t order_stream = nullptr;                   // tjamd_counter_set_order_stream: where a finalise begun with tjamd_finalise_begin runs its ordering step
+  // where that step goes: ORDER_SIDE (default) the library's own side stream of the device, taken when first needed
+  // (side_stream_acquire); ORDER_MAIN (TATAJUBA_AMD_ORDER=main) the counter's stream; ORDER_GIVEN what
+  // tjamd_counter_set_order_stream said, a stream or none
+  enum { ORDER_SIDE, ORDER_MAIN, ORDER_GIVEN } order_mode = ORDER_SIDE;
+  bool side_held = false;                               // this counter counts among the users of its device's side stream
+  unsigned order_path = 0;                              // tjamd_debug_order_path: how the last finalise ran its ordering step
   FinCarry fin;                                         // what finalise_queue leaves for finalise_collect
   hipEvent_t marks[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};   // tjamd_mark / tjamd_wait_mark
   unsigned mark_seq = 0;
@@ -4026,6 +4127,35 @@ static int read_back (tjamd_counter *c, const char *fn, const void *d, void *h, 
   return e == hipSuccess ? TJAMD_OK : set_err (TJAMD_ERR_HIP, "%s: failed: %s", fn, hipGetErrorString (e));
 }
 
+// The library's side stream: one per device for the whole process, where the ordering step of a begun finalise runs
+// beside the next sample's scan.  Made when a counter first needs it, shared by every counter of the device (their
+// steps follow each other on it, as they did on one stream), destroyed with the last counter that used it.  Not one per
+// counter: a process has few hardware queues, and streams that share a queue run one after the other.
+#define TJ_SIDE_DEVICES 64
+static std::mutex g_side_mutex;
+static struct { hipStream_t stream; int users; } g_side[TJ_SIDE_DEVICES];
+
+static hipStream_t side_stream_acquire (tjamd_counter *c)
+{ // null: no such stream (the step then stays on the counter's stream)
+  if (c->device < 0 || c->device >= TJ_SIDE_DEVICES) return nullptr;
+  std::lock_guard<std::mutex> lock (g_side_mutex);
+  auto &s = g_side[c->device];
+  if (!c->side_held) {
+    if (!s.stream && hipStreamCreateWithFlags (&s.stream, hipStreamNonBlocking) != hipSuccess) { s.stream = nullptr; (void) hipGetLastError (); return nullptr; }
+    s.users++; c->side_held = true;
+  }
+  return s.stream;
+}
+
+static void side_stream_release (tjamd_counter *c)
+{
+  if (!c->side_held) return;
+  std::lock_guard<std::mutex> lock (g_side_mutex);
+  auto &s = g_side[c->device];
+  c->side_held = false;
+  if (--s.users == 0 && s.stream) { (void) hipStreamSynchronize (s.stream); (void) hipStreamDestroy (s.stream); s.stream = nullptr; }
+}
+
 extern "C" tjamd_counter *tjamd_counter_create (int device, int kmer_size)
 {
   int n = tjamd_device_count ();
@@ -4048,6 +4178,8 @@ extern "C" tjamd_counter *tjamd_counter_create (int device, int kmer_size)
   const char *sk = getenv ("TATAJUBA_AMD_SINK");          // "fused": scan_fast_kernel<1> partitions its records itself (rounds 1-3); default: record log + partition_log_kernel
   if (sk && !strcmp (sk, "fused")) c->log_mode = 0;
   if (sk && !strcmp (sk, "log")) c->log_mode = 2;
+  const char *om = getenv ("TATAJUBA_AMD_ORDER");         // "main": the ordering step of a begun finalise stays on the counter's stream (no side stream); read here, kept in the counter
+  if (om && !strcmp (om, "main")) c->order_mode = tjamd_counter::ORDER_MAIN;
   const char *fm = getenv ("TATAJUBA_AMD_FAST");          // test hook: 0 = generic scan kernel only, 2 = fast kernel hands every tile over
   if (fm && atoi (fm) >= 0 && atoi (fm) <= 2) c->fast_mode = atoi (fm);
   const char *sg = getenv ("TATAJUBA_AMD_SCAN_GRID");     // test hook: at most n workgroups per scan / log-partition launch (one workgroup then walks many tiles or blocks)
@@ -4087,6 +4219,8 @@ extern "C" void tjamd_counter_destroy (tjamd_counter *c)
   if (!c) return;
   (void) hipSetDevice (c->device);
   if (c->stream) (void) hipStreamSynchronize (c->stream);   // (null: tjamd_counter_create got no further than that)
+  if (c->fin.state == FIN_EVENT) (void) hipEventSynchronize (c->ev_done);   // (begun and never ended: its ordering step may be on another stream)
+  side_stream_release (c);
   DevBuf *all[] = {&c->log, &c->logmeta, &c->pool, &c->table, &c->stage, &c->fix, &c->loc, &c->prefix, &c->rawlist, &c->slow, &c->alt, &c->hist, &c->flags, &c->segid, &c->headpos,
                    &c->keep, &c->outpos, &c->scan_tmp, &c->kept, &c->idx_i, &c->idx_f, &c->cov, &c->bins, &c->binstart, &c->binctx, &c->ovf, &c->grp_jt, &c->grp_hist, &c->fine,
                    &c->ts_cov, &c->ts_aux, &c->ut_tot, &c->ut_lev, &c->ut_fb, &c->ut_slots, &c->lc_work};
@@ -4113,23 +4247,43 @@ extern "C" int tjamd_counter_set_stream (tjamd_counter *c, void *hip_stream)
   if (!c) return set_err (TJAMD_ERR_ARG, "null counter");
   HIPCHK (hipSetDevice (c->device));
   HIPCHK (hipStreamSynchronize (c->stream));
-  c->stream = hip_stream ? (hipStream_t) hip_stream : c->own_stream;
+  // A counter on a caller's stream holds no stream of its own: a process has few hardware queues (four by default),
+  // streams that share one run one after the other, and the side stream of the ordering step must not land on the
+  // queue of the stream it is to run beside -- with two idle own streams on two of the queues it did, in every step of
+  // the bench (profiles/README.md, "Ordering step beside the next scan").
+  if (hip_stream) {
+    if (c->own_stream) { HIPCHK (hipStreamDestroy (c->own_stream)); c->own_stream = nullptr; }
+    c->stream = (hipStream_t) hip_stream;
+  }
+  else {
+    if (!c->own_stream) HIPCHK (hipStreamCreateWithFlags (&c->own_stream, hipStreamNonBlocking));
+    c->stream = c->own_stream;
+  }
   return TJAMD_OK;
 }
 
-// A second stream for the ordering step of a finalise that was begun with tjamd_finalise_begin (null: none).  The step is
-// six small launches whose time is latency, not work (110 us for 234 k records): behind an event on the counter's stream
-// it runs beside whatever that stream does next -- the scan of the next sample on another counter -- and
-// tjamd_finalise_end waits for its last copy as before.  The counter itself must not be touched between the two calls.
+// The stream for the ordering step of a finalise that was begun with tjamd_finalise_begin, named by the caller (null:
+// none, the step stays on the counter's stream).  The step is six small launches whose time is latency, not work (76 us
+// for 235 k records), each sized to start on a CU that three workgroups of scan_fast_kernel<1, true> fill (ORDER_KERNEL):
+// behind an event on the counter's stream it runs beside whatever that stream does next -- the scan of the next sample
+// on another counter -- and tjamd_finalise_end waits for its last copy as before.  The counter itself must not be
+// touched between the two calls.  A counter on which this was never called uses the library's side stream
+// (side_stream_acquire) unless TATAJUBA_AMD_ORDER=main was set when it was made.
 extern "C" int tjamd_counter_set_order_stream (tjamd_counter *c, void *hip_stream)
 {
   if (!c) return set_err (TJAMD_ERR_ARG, "null counter");
   HIPCHK (hipSetDevice (c->device));
   HIPCHK (hipStreamSynchronize (c->stream));
-  if (c->order_stream) HIPCHK (hipStreamSynchronize (c->order_stream));
+  if (c->fin.state == FIN_EVENT) HIPCHK (hipEventSynchronize (c->ev_done));   // (a step begun on the stream that is given up here)
   c->order_stream = (hipStream_t) hip_stream;
+  c->order_mode = tjamd_counter::ORDER_GIVEN;
   return TJAMD_OK;
 }
+
+// diagnostic (tests): how the last finalise ran its ordering step, a sum of 1: planned ahead and queued on another stream than
+// the counter's; 2: with the kept count in hand, on the counter's stream (nothing planned, or more kept than planned
+// for); 4: planned ahead and queued on the counter's stream.  0: no ordering step (or no finalise).
+extern "C" long tjamd_debug_order_path (tjamd_counter *c) { return c ? (long) c->order_path : -1; }
 
 static Buckets make_buckets (const tjamd_counter *c)
 {
@@ -4757,8 +4911,12 @@ static int finalise_binned (tjamd_counter *c, long n1, int min_coverage, long ca
 {
   const bool planned = n1 == 0;
   // (begun, not waited for, and a second stream is there: the step goes to it, behind what the counter's stream holds so far)
-  const bool aside = planned && !wait && c->order_stream != nullptr && c->order_stream != c->stream;
-  const hipStream_t st = aside ? c->order_stream : c->stream;
+  // (the library's side stream unless the caller named a stream, or none; taken only here, where it is first needed)
+  hipStream_t other = nullptr;
+  if (planned && !wait) other = c->order_mode == tjamd_counter::ORDER_GIVEN ? c->order_stream : c->order_mode == tjamd_counter::ORDER_SIDE ? side_stream_acquire (c) : nullptr;
+  const bool aside = other != nullptr && other != c->stream;
+  const hipStream_t st = aside ? other : c->stream;
+  c->order_path |= aside ? 1u : planned ? 4u : 2u;
   const FinPlan *plan = planned ? &c->d_state->plan : nullptr;
   if (planned) n1 = cap;                                // (sizes everything below; the kernels use the plan's numbers)
   const int nbits = bin_bits_for (n1, c->k);
@@ -4774,14 +4932,14 @@ static int finalise_binned (tjamd_counter *c, long n1, int min_coverage, long ca
   int rc = ensure (c->alt, (size_t) n1 * 24, c->stream);
   if (!rc && !c->bins.p) { rc = ensure (c->bins, (size_t) (BS_MAXBINS + 1) * 4, c->stream); c->bins_zeroed = false; }
   if (!rc) rc = ensure (c->binstart, (size_t) (nbins + 1) * 4, c->stream);
-  if (!rc) rc = ensure (c->binctx, (size_t) nbins * 8, c->stream);
+  if (!rc) rc = ensure (c->binctx, ((size_t) nbins * 3 + 1) * 4, c->stream);    // (binctx, binout, then the list of fuller bins and its count)
   if (!rc) rc = ensure (c->headpos, (size_t) n1 * 4, c->stream);
   if (!rc) rc = ensure (c->outpos, (size_t) n1 * 4, c->stream);
   if (!rc) rc = ensure (c->idx_i, (size_t) n1 * 4, c->stream);
   if (!rc) rc = ensure (c->idx_f, (size_t) n1 * 4, c->stream);
   if (!rc) rc = ensure (c->cov, (size_t) t * 8, c->stream);
   if (rc) return rc;
-  u32 *bins = (u32 *) c->bins.p, *binstart = (u32 *) c->binstart.p, *binctx = (u32 *) c->binctx.p, *binout = binctx + nbins;
+  u32 *bins = (u32 *) c->bins.p, *binstart = (u32 *) c->binstart.p, *binctx = (u32 *) c->binctx.p, *binout = binctx + nbins, *full = binout + nbins;
   u32 *tstart = (u32 *) c->headpos.p, *tend = (u32 *) c->outpos.p;
   u64 *ctab = (u64 *) c->cov.p;
   if (!fused && !c->bins_zeroed) HIPCHK (hipMemsetAsync (bins, 0, (size_t) BS_MAXBINS * 4, c->stream));
@@ -4791,13 +4949,17 @@ static int finalise_binned (tjamd_counter *c, long n1, int min_coverage, long ca
   const unsigned g1 = planned ? std::min<unsigned> (grid_for (n1), 2048u) : grid_for (n1);
   if (!fused) hipLaunchKernelGGL (bin_count_kernel, dim3 (g1), dim3 (256), 0, st, (const u64 *) c->kept.p, n1, c->k, nbits, bins,
                                   (uint4 *) c->cov.p, (long) (t / 2), 0, plan);
-  hipLaunchKernelGGL (bin_scan_kernel, dim3 (1), dim3 (1024), 0, st, bins, nbins, binstart, c->bin_rank_max, c->d_fin, plan);
+  hipLaunchKernelGGL (bin_scan_kernel, dim3 (1), dim3 (WGS_THREADS), 0, st, bins, nbins, binstart, c->bin_rank_max, c->d_fin, plan, full);
   hipLaunchKernelGGL (bin_scatter_kernel, dim3 (g1), dim3 (256), 0, st, (const u64 *) c->kept.p, (u64 *) c->alt.p, n1, c->k, nbits, bins, plan,
                       fused ? (uint4 *) c->cov.p : (uint4 *) nullptr);
-  hipLaunchKernelGGL (bin_sort_index_kernel, dim3 ((unsigned) std::min (nbins / BSI_WAVES + 1, 16384)), dim3 (64 * BSI_WAVES), 0, st,
+  hipLaunchKernelGGL (bin_sort_index_kernel, dim3 ((unsigned) std::min (nbins + 1, 16384)), dim3 (64), 0, st,
                       (const u64 *) c->alt.p, (u64 *) c->kept.p, (const u32 *) binstart, nbins, (const FinCounts *) c->d_fin, min_coverage,
-                      ctab, log2t, binctx, tstart, tend, plan, cov_direct);
-  hipLaunchKernelGGL (bin_ctx_scan_kernel, dim3 (1), dim3 (1024), 0, st, (const u32 *) binctx, nbins, binout, c->d_fin, plan);
+                      ctab, log2t, binctx, tstart, tend, full, plan, cov_direct);
+  // (the bins of more than 64 records that the launch above has listed; few or none: a small grid that strides)
+  hipLaunchKernelGGL (bin_sort_full_kernel, dim3 ((unsigned) std::min (nbins, BSF_GRID)), dim3 (64), 0, st,
+                      (const u64 *) c->alt.p, (u64 *) c->kept.p, (const u32 *) binstart, nbins, (const FinCounts *) c->d_fin, min_coverage,
+                      ctab, log2t, binctx, tstart, tend, full, plan, cov_direct);
+  hipLaunchKernelGGL (bin_ctx_scan_kernel, dim3 (1), dim3 (WGS_THREADS), 0, st, (const u32 *) binctx, nbins, binout, c->d_fin, plan);
   hipLaunchKernelGGL (bin_ctx_write_kernel, dim3 (256), dim3 (256), 0, st, (const u32 *) binstart, (const u32 *) binctx, (const u32 *) binout, nbins,
                       (const u32 *) tstart, (const u32 *) tend, (int *) c->idx_i.p, (int *) c->idx_f.p, (const u64 *) ctab, t, c->d_fin, plan);
   HIPCHK (hipGetLastError ());
@@ -4824,7 +4986,7 @@ static int finalise_queue (tjamd_counter *c, int remove_biased, int min_coverage
   // above one), so half of the host's running upper bound of the raw count is a safe capacity: unless that is a lot of
   // memory, the aggregation is launched without first asking the device (one host round trip less) and the exact
   // counts and error flags, copied in stream order before the buckets are cleared, are looked at afterwards.
-  c->n_kept = 0; c->n_idx = 0; c->coverage = 0; c->timer[T_FIN].timed = false;
+  c->n_kept = 0; c->n_idx = 0; c->coverage = 0; c->timer[T_FIN].timed = false; c->order_path = 0;
   f.speculative = (c->raw_bound / 2 + 1) * 24 <= (8ull << 30);
   f.kept_cap = c->raw_bound / 2 + 1;
   int rc = TJAMD_OK;
@@ -6230,13 +6392,13 @@ extern "C" long tjamd_merge_samples (tjamd_counter *c, const void *d_records, co
   Stage st (c, T_MERGE);
   st.begin ();
   hipLaunchKernelGGL (bin_count_kernel, dim3 (grid_for (n)), dim3 (256), 0, c->stream, (const u64 *) d_records, n, c->k, nbits, bins, (uint4 *) nullptr, 0l, 1);
-  hipLaunchKernelGGL (bin_scan_kernel, dim3 (1), dim3 (1024), 0, c->stream, bins, nbins, binstart,
+  hipLaunchKernelGGL (bin_scan_kernel, dim3 (1), dim3 (WGS_THREADS), 0, c->stream, bins, nbins, binstart,
                       c->bin_rank_max < (u32) BS_RANK_MAX ? c->bin_rank_max : (u32) MG_RANK_MAX, c->d_fin);   // (test hook: see TATAJUBA_AMD_BIN_MAX)
   hipLaunchKernelGGL (merge_scatter_kernel, dim3 (grid_for (n)), dim3 (256), 0, c->stream, (const u64 *) d_records, (u64 *) c->alt.p, n, c->k, nbits, bins,
                       (const long *) c->prefix.p, n_samples);
   hipLaunchKernelGGL (bin_merge_kernel, dim3 ((unsigned) std::min (nbins, 16384)), dim3 (64), 0, c->stream, (const u64 *) c->alt.p, (const u32 *) binstart, nbins,
                       (const FinCounts *) c->d_fin, binctx, tpos, ttot);
-  hipLaunchKernelGGL (bin_ctx_scan_kernel, dim3 (1), dim3 (1024), 0, c->stream, (const u32 *) binctx, nbins, binout, c->d_fin);
+  hipLaunchKernelGGL (bin_ctx_scan_kernel, dim3 (1), dim3 (WGS_THREADS), 0, c->stream, (const u32 *) binctx, nbins, binout, c->d_fin);
   hipLaunchKernelGGL (bin_merge_write_kernel, dim3 ((unsigned) std::min (nbins / 4 + 1, 4096)), dim3 (256), 0, c->stream, (const u64 *) c->alt.p, (const u32 *) binstart,
                       (const u32 *) binout, nbins, (const FinCounts *) c->d_fin, (const u32 *) tpos, (const u32 *) ttot, n_samples,
                       (u64 *) d_out_keys, (int *) d_out_counts, capacity);
