@@ -13,6 +13,9 @@
  *                             of samples a <= b: sample_a  sample_b  n_both  n_differ  length_diff
  *   DIR/sample_linkage.tsv    with -C T (which implies -M): tjamd_sample_linkage on that matrix, by n_differ over the pairs with at
  *                             least one site in common; one line per link, in the order single linkage merges: sample_a  sample_b  key
+ *                             with -L complete or -L average (only together with -C T; -L single is the default): the links of
+ *                             tjamd_sample_agglomerate under that linkage instead, in the order (key, round, a, b), and the clusters, the
+ *                             cluster sites, the tree and the clade sites below are built from them
  *   DIR/sample_clusters.tsv   with -C T: tjamd_linkage_clusters at threshold T, one line per sample: sample  cluster
  *   DIR/cluster_sites.tsv     with -G (only together with -C T): tjamd_group_sites on that genotype matrix with the clusters as the groups and a
  *                             min_called of 1: the sites at which every called sample of a cluster carries one genotype that no called
@@ -33,10 +36,11 @@
  * The other options are sample_vcfs.c's.
  *
  *   gcc -O2 -I include examples/merged_vcf.c -L tatajuba_amd -ltatajuba_amd -Wl,-rpath,$PWD/tatajuba_amd -o merged_vcf
- *   ./merged_vcf -r reference.fa [-u] [-D] [-M] [-C T [-G] [-N]] [-e annotation.gff3] [-x 1] [-g G] [-s 3] [-k 10] [-m 3] [-c 5] [-d 1] [-l -1] [-o .] sample1.fastq[.gz] ...   */
+ *   ./merged_vcf -r reference.fa [-u] [-D] [-M] [-C T [-G] [-N] [-L single|complete|average]] [-e annotation.gff3] [-x 1] [-g G] [-s 3] [-k 10] [-m 3] [-c 5] [-d 1] [-l -1] [-o .] sample1.fastq[.gz] ...   */
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
+#include <tatajuba_agglomerate.h>
 #include <tatajuba_clades.h>
 #include <tatajuba_effects.h>
 #include <tatajuba_locate.h>
@@ -107,7 +111,7 @@ main (int argc, char **argv)
   static const char *class_name[5] = {"NONE", "BOUNDARY", "IDENTICAL", "INFRAME", "FRAMESHIFT"};
   long counts[MAX_SAMPLES], total, n_union, n_grouped, n_tracts, n_located, n_gapped = 0, n_var = 0, n_rec, i, cap, ref_bytes, n_contigs = 0, n_names = 0, name_bytes;
   long offsets[MAX_SAMPLES + 1], *contig_len, var_cap, n_sites, n_alleles = 0, s, text_cap = 0;
-  int with_unique = 0, with_depths = 0, with_distances = 0, with_clusters = 0, with_groups = 0, with_clades = 0;
+  int with_unique = 0, with_depths = 0, with_distances = 0, with_clusters = 0, with_groups = 0, with_clades = 0, with_linkage = 0, linkage = 0;
   long long cut = 0;
   long n_links = 0, n_clusters = 0, n_marks = 0;
   tjamd_link *h_links = NULL;
@@ -151,9 +155,16 @@ main (int argc, char **argv)
     else if (!strcmp (argv[a], "-C") && a + 1 < argc) { cut = atoll (argv[++a]); with_clusters = with_distances = 1; }
     else if (!strcmp (argv[a], "-G")) with_groups = 1;
     else if (!strcmp (argv[a], "-N")) with_clades = 1;
+    else if (!strcmp (argv[a], "-L") && a + 1 < argc) {   /* which tree: 0 single linkage (tjamd_sample_linkage), else TJAMD_AGGL_* */
+      a++; with_linkage = 1;
+      if (!strcmp (argv[a], "single")) linkage = 0;
+      else if (!strcmp (argv[a], "complete")) linkage = TJAMD_AGGL_COMPLETE;
+      else if (!strcmp (argv[a], "average")) linkage = TJAMD_AGGL_AVERAGE;
+      else linkage = -1;
+    }
     else if (n < MAX_SAMPLES) files[n++] = argv[a];
   }
-  if (n < 1 || !reference || ((with_groups || with_clades) && !with_clusters)) { fprintf (stderr, "usage: %s -r reference.fa [-u] [-D] [-M] [-C T [-G] [-N]] [-e annotation.gff3] [-x X] [-g G] [-s S] [-k K] [-m M] [-c C] [-d D] [-l L] [-o DIR] sample.fastq[.gz] ...\n", argv[0]); return 2; }
+  if (n < 1 || !reference || ((with_groups || with_clades || with_linkage) && !with_clusters) || linkage < 0) { fprintf (stderr, "usage: %s -r reference.fa [-u] [-D] [-M] [-C T [-G] [-N] [-L single|complete|average]] [-e annotation.gff3] [-x X] [-g G] [-s S] [-k K] [-m M] [-c C] [-d D] [-l L] [-o DIR] sample.fastq[.gz] ...\n", argv[0]); return 2; }
   if (ndev < 1) { fprintf (stderr, "tatajuba_amd error: no HIP device is visible (there is no CPU fallback)\n"); return 1; }
   if (maxd < 0) maxd = 0;                                 /* src/main.c:190-192 */
   if (maxd > k / 2) maxd = k / 2;
@@ -268,7 +279,8 @@ main (int argc, char **argv)
     if (tjamd_device_download (ctr[0], h_dist, d_dist, (size_t) n * (size_t) n * sizeof (tjamd_sample_distance))) return fail ("download");
     if (with_clusters) {                                  /* the tree of the samples from the matrix where it is, and its cut at T */
       void *d_links = tjamd_device_alloc (ctr[0], (size_t) n * sizeof (tjamd_link)), *d_cluster = tjamd_device_alloc (ctr[0], (size_t) n * sizeof (int));
-      n_links = tjamd_sample_linkage (ctr[0], (const tjamd_sample_distance *) d_dist, n, TJAMD_LINK_DIFFER, 1, (tjamd_link *) d_links);
+      n_links = linkage ? tjamd_sample_agglomerate (ctr[0], (const tjamd_sample_distance *) d_dist, n, TJAMD_LINK_DIFFER, 1, linkage, (tjamd_link *) d_links, NULL)
+                        : tjamd_sample_linkage (ctr[0], (const tjamd_sample_distance *) d_dist, n, TJAMD_LINK_DIFFER, 1, (tjamd_link *) d_links);
       if (n_links < 0) return fail ("sample linkage");
       n_clusters = tjamd_linkage_clusters (ctr[0], (const tjamd_link *) d_links, n_links, n, cut, (int *) d_cluster);
       if (n_clusters < 0) return fail ("linkage clusters");

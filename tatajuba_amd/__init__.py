@@ -13,5 +13,6 @@ from .capi import (Counter, Comm, Reference, Annotation, REF_ENTRY_DTYPE, LOCATI
                    SITE_DEPTH_DTYPE, DEPTH_EXPORTS,
                    SAMPLE_DISTANCE_DTYPE, DISTANCE_EXPORTS,
                    LINK_DTYPE, LINK_DIFFER, LINK_LENGTH, LINK_DIFFER_RATE, LINKAGE_EXPORTS,
+                   AGGL_COMPLETE, AGGL_AVERAGE, AGGLOMERATE_EXPORTS,
                    GROUP_CALL_DTYPE, GROUP_SITE_DTYPE, GROUP_MARK_DTYPE, GROUP_EXPORTS,
                    TREE_NODE_DTYPE, CLADE_EXPORTS)

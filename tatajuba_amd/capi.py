@@ -177,6 +177,9 @@ DEPTH_EXPORTS = ["tjamd_site_depths", "tjamd_last_site_depths_ms"]
 DISTANCE_EXPORTS = ["tjamd_sample_distances", "tjamd_last_sample_distances_ms"]
 # ... and include/tatajuba_linkage.h
 LINKAGE_EXPORTS = ["tjamd_sample_linkage", "tjamd_linkage_clusters", "tjamd_last_sample_linkage_ms", "tjamd_last_linkage_clusters_ms"]
+# ... and include/tatajuba_agglomerate.h
+AGGLOMERATE_EXPORTS = ["tjamd_sample_agglomerate", "tjamd_last_sample_agglomerate_ms"]
+AGGL_COMPLETE, AGGL_AVERAGE = 1, 2                                        # TJAMD_AGGL_*: the linkage of tjamd_sample_agglomerate
 # ... and include/tatajuba_groups.h
 GROUP_EXPORTS = ["tjamd_group_sites", "tjamd_last_group_sites_ms"]
 # ... and include/tatajuba_clades.h
@@ -350,6 +353,9 @@ def lib():
     L.tjamd_linkage_clusters.argtypes = [C.c_void_p, C.c_void_p, C.c_long, C.c_int, C.c_longlong, C.c_void_p]
     L.tjamd_last_sample_linkage_ms.restype = C.c_double; L.tjamd_last_sample_linkage_ms.argtypes = [C.c_void_p]
     L.tjamd_last_linkage_clusters_ms.restype = C.c_double; L.tjamd_last_linkage_clusters_ms.argtypes = [C.c_void_p]
+    L.tjamd_sample_agglomerate.restype = C.c_long
+    L.tjamd_sample_agglomerate.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.POINTER(C.c_int)]
+    L.tjamd_last_sample_agglomerate_ms.restype = C.c_double; L.tjamd_last_sample_agglomerate_ms.argtypes = [C.c_void_p]
     L.tjamd_group_sites.restype = C.c_long
     L.tjamd_group_sites.argtypes = [C.c_void_p, C.c_void_p, C.c_long, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_long,
                                     C.POINTER(C.c_long)]
@@ -978,6 +984,17 @@ class Counter:
 
     def last_linkage_clusters_ms(self):
         return lib().tjamd_last_linkage_clusters_ms(self._h)
+
+    def sample_agglomerate(self, d_dist, n_samples, metric, min_both, linkage, d_links):
+        """tjamd_sample_agglomerate on device pointers: the [sample][sample] matrix of tjamd_sample_distances -> the complete
+        (AGGL_COMPLETE) or average (AGGL_AVERAGE) linkage tree of the samples under the metric over the pairs with n_both >=
+        min_both, one LINK_DTYPE record per merge at d_links, ascending in (key, round, a, b).  -> (n_links, n_rounds)"""
+        n_rounds = C.c_int(0)
+        n = self._chkn(lib().tjamd_sample_agglomerate(self._h, d_dist, n_samples, metric, min_both, linkage, d_links, C.byref(n_rounds)))
+        return n, n_rounds.value
+
+    def last_sample_agglomerate_ms(self):
+        return lib().tjamd_last_sample_agglomerate_ms(self._h)
 
     def group_sites(self, d_sites, n_sites, d_genotype, n_samples, d_group, n_groups, min_called, d_calls=None, d_site_out=None, d_group_marks=None,
                     d_marks=None, mark_capacity=0):

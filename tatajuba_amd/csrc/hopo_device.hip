@@ -45,6 +45,7 @@
 #include "../../include/tatajuba_depths.h"
 #include "../../include/tatajuba_distances.h"
 #include "../../include/tatajuba_linkage.h"
+#include "../../include/tatajuba_agglomerate.h"
 #include "../../include/tatajuba_groups.h"
 #include "../../include/tatajuba_clades.h"
 #include "../../include/tatajuba_locate.h"
@@ -3972,7 +3973,7 @@ struct StageTimer
 };
 // the intervals of a counter: the last scan call (its partition kernels between the pieces included: tjamd_last_scan_ms takes
 // them out), finalise, the kernels of tjamd_merge_samples, tjamd_tract_stats, tjamd_union_tracts, tjamd_union_tract_stats
-enum { T_SCAN, T_FIN, T_MERGE, T_TRACT, T_UNION, T_UNION_STATS, T_REF, T_LOCATE, T_LOCATED_TRACTS, T_VARIANTS, T_ANNOTATION, T_TRACT_FEATURES, T_SEED_ORDER, T_LOCATE_GAPPED, T_CODING, T_VARIANT_EFFECTS, T_MERGE_VARIANTS, T_SITE_DEPTHS, T_SAMPLE_DISTANCES, T_SAMPLE_LINKAGE, T_LINKAGE_CLUSTERS, T_GROUP_SITES, T_LINKAGE_TREE, T_CLADE_SITES, TJ_N_TIMERS };   // (T_REF to T_LOCATED_TRACTS: N7, T_VARIANTS: N8, the next two: N9; then two of N10; two of N11; then N12, N13, N14, the two of N15, N16 and the two of N17, end of the file)
+enum { T_SCAN, T_FIN, T_MERGE, T_TRACT, T_UNION, T_UNION_STATS, T_REF, T_LOCATE, T_LOCATED_TRACTS, T_VARIANTS, T_ANNOTATION, T_TRACT_FEATURES, T_SEED_ORDER, T_LOCATE_GAPPED, T_CODING, T_VARIANT_EFFECTS, T_MERGE_VARIANTS, T_SITE_DEPTHS, T_SAMPLE_DISTANCES, T_SAMPLE_LINKAGE, T_LINKAGE_CLUSTERS, T_GROUP_SITES, T_LINKAGE_TREE, T_CLADE_SITES, T_SAMPLE_AGGLOMERATE, TJ_N_TIMERS };   // (T_REF to T_LOCATED_TRACTS: N7, T_VARIANTS: N8, the next two: N9; then two of N10; two of N11; then N12, N13, N14, the two of N15, N16, the two of N17 and N18, end of the file)
 
 // A finalise between its two halves: finalise_queue fills this in, finalise_collect reads it and sets the state back to
 // FIN_IDLE (nothing begun).  FIN_EVENT: begun, ev_done says when the counts have arrived; FIN_ARRIVED: begun, the stream has
@@ -4040,6 +4041,7 @@ struct tjamd_counter
   int scan_grid_cap = 0;                                // TATAJUBA_AMD_SCAN_GRID (tests): n >= 1 caps the workgroups of the scan and log-partition launches; 0: no cap
   int dist_blocks = 0;                                  // TATAJUBA_AMD_DISTANCE_BLOCKS (tests): the workgroups tjamd_sample_distances splits its sites for; 0: four per CU
   int link_small = 1;                                   // TATAJUBA_AMD_LINKAGE_SMALL (tests): 0: tjamd_sample_linkage never takes its single-workgroup path (64 samples and fewer)
+  int aggl_batch = 32;                                  // TATAJUBA_AMD_AGGL_BATCH (tools, tests): the rounds tjamd_sample_agglomerate enqueues between two looks at its flag words; AGGL_BATCH
   int groups_small = 1;                                 // TATAJUBA_AMD_GROUPS_SMALL (tests): 0: tjamd_group_sites never takes its wavefront-per-site form (64 samples and fewer)
   int clades_small = 1;                                 // TATAJUBA_AMD_CLADES_SMALL (tests): 0: tjamd_clade_sites never takes its wavefront-per-site form (64 samples and fewer)
   bool buckets_clean = false;
@@ -4188,6 +4190,8 @@ extern "C" tjamd_counter *tjamd_counter_create (int device, int kmer_size)
   if (db && atoi (db) >= 1) c->dist_blocks = atoi (db);
   const char *ls = getenv ("TATAJUBA_AMD_LINKAGE_SMALL");    // test hook: 0 sends every tjamd_sample_linkage through the key pass, the rounds and the sort kernel
   if (ls && !strcmp (ls, "0")) c->link_small = 0;
+  const char *ab = getenv ("TATAJUBA_AMD_AGGL_BATCH");       // measuring hook: n >= 1 rounds of tjamd_sample_agglomerate per look at the flag words
+  if (ab && atoi (ab) >= 1) c->aggl_batch = atoi (ab);
   const char *gs = getenv ("TATAJUBA_AMD_GROUPS_SMALL");     // test hook: 0 sends every tjamd_group_sites through the workgroup-per-run form with its LDS tables
   if (gs && !strcmp (gs, "0")) c->groups_small = 0;
   const char *cs = getenv ("TATAJUBA_AMD_CLADES_SMALL");     // test hook: 0 sends every tjamd_clade_sites through the workgroup-per-run form with its LDS scans
@@ -10408,3 +10412,326 @@ extern "C" long tjamd_clade_sites (tjamd_counter *c, const tjamd_site *d_sites, 
   return (long) h[1];
 }
 extern "C" double tjamd_last_clade_sites_ms (tjamd_counter *c) { return c ? c->timer[T_CLADE_SITES].ms (c->device) : -1.0; }
+
+// ---- N18: complete and average linkage trees of the samples ------------------------------------------------------------------
+// N14's sample x sample matrix agglomerated under complete or average linkage by rounds of reciprocal nearest neighbours; the
+// rule as built is in include/tatajuba_agglomerate.h.  Not a spanning forest: the cluster x cluster matrix is rewritten as
+// clusters merge, in place, in the u64 key matrix of N15's key pass (the maximum, or the exact sum, of the pairs across two
+// clusters; all ones: no edge, which absorbs).
+//   1. linkage_keys_kernel as N15 runs it, then aggl_init_kernel: every sample a cluster of size 1, and under AVERAGE the bound
+//      of 2^40 on a key.  Raises the error flag; writes nothing of the caller's.
+//   2. rounds of four kernels, launched in batches of AGGL_BATCH without a look at the device in between:
+//      (a) aggl_rowmin_kernel: a wavefront per live row takes the minimum of (D, id) over the live columns; under AVERAGE D is
+//          the cell's sum divided by the two sizes, taken here and never stored.
+//      (b) aggl_pairs_kernel, one workgroup with the nearest neighbours in LDS: the mutual pairs, their links with the round,
+//          the round's pair list, the new sizes (no other kernel of the round reads a size of a cluster that merges: the update
+//          needs the pair list alone); `done` when no pair is left or the tree is whole.
+//      (c) aggl_rows_kernel, a workgroup per pair (X, Y): row X := f (row X, row Y) over all columns; then aggl_cols_kernel, a
+//          wavefront per live row: column P := f (column P, column Q) for every pair (P, Q).  The second reads what the first
+//          wrote, so the cell (X, P) of two pairs of one round holds f of all four cells, and the matrix stays symmetric.
+//      Every kernel of a round returns when `done` or the error flag is up.  Nothing waits for another workgroup.
+//   3. aggl_sort_kernel, behind every batch, returns unless `done` is up: one workgroup sorts the links by (key, round, a, b)
+//      in LDS (two u64 per entry, 64 KB at 4096 places) and stores them.
+// Up to 64 samples aggl_small_kernel does all of it as one workgroup in one launch, the matrix in LDS.  DESIGN.md section 3.5, N18.
+
+struct AgglEdge { u64 key, aux; };                      // a link before the sort: aux = round << 24 | a << 12 | b, a < b < 4096, round < 4096
+#define AGGL_BATCH 32                                   // rounds enqueued between two looks at the flag words (measured)
+#define AGGL_KEY_MAX (1ull << 40)                       // AVERAGE: a key of a pair of samples stays below this, a sum over 2^22 pairs below 2^62
+// flags of a call: [0] error bits (1 a cell's values, 2 a cell and its mirror, 4 a key of 2^40 or more under AVERAGE), [1] done,
+// [2] links appended so far, [3] rounds that merged something, [4] the pairs of the last round
+
+__device__ __forceinline__ u64 aggl_f (u64 x, u64 y, int linkage)
+{
+  if (x == LINK_NONE || y == LINK_NONE) return LINK_NONE;
+  return linkage == TJAMD_AGGL_COMPLETE ? (x > y ? x : y) : x + y;
+}
+// the distance of two clusters from their cell (not LINK_NONE) and their sizes
+__device__ __forceinline__ u64 aggl_d (u64 cell, int sa, int sb, int linkage)
+{ // (sa + sb <= 4096: the product is below 2^23; dividing by it is floor (floor (S / sb) / sa))
+  const u32 pairs = (u32) sa * (u32) sb;
+  return linkage == TJAMD_AGGL_COMPLETE || pairs == 1u ? cell : cell / (u64) pairs;
+}
+
+__global__ __launch_bounds__ (256)
+void aggl_init_kernel (const u64 *__restrict__ keys, int ns, int ld, int linkage, int *__restrict__ size, int *__restrict__ flags)
+{
+  const long n = (long) ns * ld, x0 = (long) blockIdx.x * 256 + threadIdx.x;
+  if (x0 < ld) size[x0] = x0 < ns ? 1 : 0;              // (the padding column is a retired cluster)
+  if (linkage != TJAMD_AGGL_AVERAGE) return;
+  int bad = 0;
+  for (long x = x0; x < n; x += (long) gridDim.x * 256) {
+    const u64 k = keys[x];
+    if (k != LINK_NONE && k >= AGGL_KEY_MAX) bad = 4;
+  }
+  if (bad) atomicOr (flags, bad);
+}
+
+__global__ __launch_bounds__ (256)
+void aggl_rowmin_kernel (const u64 *__restrict__ keys, int ns, int ld, int linkage, const int *__restrict__ size, LinkRowBest *__restrict__ rowbest,
+                         const int *__restrict__ flags)
+{
+  if ((((volatile const int *) flags)[0] | ((volatile const int *) flags)[1]) != 0) return;
+  const int lane = threadIdx.x & 63, a = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (a >= ns) return;                                  // (a whole wavefront)
+  const int sa = size[a];
+  if (sa == 0) return;                                  // a retired row
+  const ulonglong2 *row = (const ulonglong2 *) (keys + (long) a * ld);   // (ld is even and the matrix starts on a 256-byte boundary: 16-byte loads)
+  const int2 *size2 = (const int2 *) size;
+  u64 bk = LINK_NONE;
+  int bb = 0x7fffffff;
+  #pragma unroll 2
+  for (int p = lane; p < ld / 2; p += 64) {             // (a lane's b ascend: the first of equal distances stays; the diagonal holds LINK_NONE)
+    const ulonglong2 k = row[p];
+    const int2 sb = size2[p];
+    if (sb.x != 0 && k.x != LINK_NONE) { const u64 d = aggl_d (k.x, sa, sb.x, linkage); if (d < bk) { bk = d; bb = 2 * p; } }
+    if (sb.y != 0 && k.y != LINK_NONE) { const u64 d = aggl_d (k.y, sa, sb.y, linkage); if (d < bk) { bk = d; bb = 2 * p + 1; } }
+  }
+  for (int o = 32; o; o >>= 1) {
+    const u64 ok = shfl_xor64 (bk, o);
+    const int ob = __shfl_xor (bb, o);
+    if (ok < bk || (ok == bk && ob < bb)) { bk = ok; bb = ob; }
+  }
+  if (lane == 0) rowbest[a] = LinkRowBest {bk, bb, 0};
+}
+
+__global__ __launch_bounds__ (1024)
+void aggl_pairs_kernel (const LinkRowBest *__restrict__ rowbest, int ns, int *__restrict__ size, AgglEdge *__restrict__ edges, u32 *__restrict__ pairs, int *__restrict__ flags)
+{
+  __shared__ int nn[LINK_MAX];                          // a live cluster's nearest neighbour; -1: retired, or no edge
+  __shared__ int n_new;
+  if ((((volatile const int *) flags)[0] | ((volatile const int *) flags)[1]) != 0) return;
+  const int tid = threadIdx.x, base = flags[2], round = flags[3];
+  u64 key[LINK_MAX / 1024];
+  int sv[LINK_MAX / 1024];
+  #pragma unroll
+  for (int j = 0; j < LINK_MAX / 1024; j++) {
+    const int v = tid + 1024 * j;
+    key[j] = LINK_NONE; sv[j] = 0;
+    if (v < ns) {
+      sv[j] = size[v];
+      if (sv[j] != 0) { const LinkRowBest rb = rowbest[v]; key[j] = rb.key; nn[v] = rb.key != LINK_NONE ? rb.b : -1; }
+      else nn[v] = -1;
+    }
+  }
+  if (tid == 0) n_new = 0;
+  __syncthreads ();
+  #pragma unroll
+  for (int j = 0; j < LINK_MAX / 1024; j++) {
+    const int v = tid + 1024 * j;
+    if (v >= ns || key[j] == LINK_NONE) continue;
+    const int w = nn[v];
+    if (w > v && nn[w] == v) {                          // mutual: one link, from its smaller end (fewer than ns links in all)
+      const int at = atomicAdd (&n_new, 1);
+      edges[base + at] = AgglEdge {key[j], (u64) round << 24 | (u64) v << 12 | (u64) w};
+      pairs[at] = (u32) v << 12 | (u32) w;
+      size[v] = sv[j] + size[w]; size[w] = 0;           // (v and w are in this pair alone)
+    }
+  }
+  __syncthreads ();
+  if (tid == 0) {
+    if (n_new == 0) flags[1] = 1;                       // no live cluster has an edge
+    else {
+      flags[2] = base + n_new; flags[3] = round + 1; flags[4] = n_new;
+      if (base + n_new == ns - 1) flags[1] = 1;         // one cluster is left: the matrix is not needed again
+    }
+  }
+}
+
+__global__ __launch_bounds__ (256)
+void aggl_rows_kernel (u64 *__restrict__ keys, int ld, int linkage, const u32 *__restrict__ pairs, const int *__restrict__ flags)
+{
+  if ((((volatile const int *) flags)[0] | ((volatile const int *) flags)[1]) != 0) return;
+  if ((int) blockIdx.x >= flags[4]) return;
+  const u32 pair = pairs[blockIdx.x];
+  ulonglong2 *rx = (ulonglong2 *) (keys + (long) (pair >> 12) * ld);
+  const ulonglong2 *ry = (const ulonglong2 *) (keys + (long) (pair & 4095u) * ld);
+  for (int p = threadIdx.x; p < ld / 2; p += 256) {
+    const ulonglong2 x = rx[p], y = ry[p];
+    rx[p] = ulonglong2 {aggl_f (x.x, y.x, linkage), aggl_f (x.y, y.y, linkage)};
+  }
+}
+
+__global__ __launch_bounds__ (256)
+void aggl_cols_kernel (u64 *__restrict__ keys, int ns, int ld, int linkage, const int *__restrict__ size, const u32 *__restrict__ pairs, const int *__restrict__ flags)
+{
+  if ((((volatile const int *) flags)[0] | ((volatile const int *) flags)[1]) != 0) return;
+  const int lane = threadIdx.x & 63, r = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (r >= ns || size[r] == 0) return;                  // (a whole wavefront) a retired row is not read again
+  u64 *row = keys + (long) r * ld;
+  const int n = flags[4];
+  for (int i = lane; i < n; i += 64) {                  // (the pairs of a round share no cluster: no cell is written twice)
+    const u32 pair = pairs[i];
+    const int P = (int) (pair >> 12), Q = (int) (pair & 4095u);
+    row[P] = aggl_f (row[P], row[Q], linkage);
+  }
+}
+
+__global__ __launch_bounds__ (1024)
+void aggl_sort_kernel (const AgglEdge *__restrict__ edges, int P, Link *__restrict__ out, const int *__restrict__ flags)
+{
+  __shared__ u64 skey[LINK_MAX], saux[LINK_MAX];        // (64 KB: nothing else is in LDS here)
+  if (((volatile const int *) flags)[0] != 0 || ((volatile const int *) flags)[1] == 0) return;
+  const int tid = threadIdx.x, n = flags[2];            // (n <= P, a power of two up to LINK_MAX)
+  for (int i = tid; i < P; i += 1024) {
+    const bool in = i < n;
+    skey[i] = in ? edges[i].key : LINK_NONE; saux[i] = in ? edges[i].aux : LINK_NONE;
+  }
+  __syncthreads ();
+  for (int k = 2; k <= P; k <<= 1)
+    for (int j = k >> 1; j > 0; j >>= 1) {
+      for (int t = tid; t < P / 2; t += 1024) {
+        const int i = ((t & ~(j - 1)) << 1) | (t & (j - 1)), l = i | j;
+        const u64 ki = skey[i], kl = skey[l], xi = saux[i], xl = saux[l];
+        const bool above = ki > kl || (ki == kl && xi > xl);
+        if (above == ((i & k) == 0)) { skey[i] = kl; skey[l] = ki; saux[i] = xl; saux[l] = xi; }
+      }
+      __syncthreads ();
+    }
+  for (int i = tid; i < n; i += 1024) out[i] = Link {(int) (saux[i] >> 12 & 4095u), (int) (saux[i] & 4095u), (long long) skey[i]};
+}
+
+// Up to LINK_SMALL samples: the checks, the rounds and the sort as one workgroup in one launch, the matrix in LDS (32 KB).
+// Waves take the rows in turn for the row minimum; thread v is sample v when the pairs are found; the two phases of the update
+// are two loops with a barrier between them.
+__global__ __launch_bounds__ (256)
+void aggl_small_kernel (const SampleDistance *__restrict__ dist, int ns, int metric, int min_both, int linkage, Link *__restrict__ out, int *__restrict__ flags)
+{
+  __shared__ u64 keys[LINK_SMALL * LINK_SMALL], rowkey[LINK_SMALL], ekey[LINK_SMALL], eaux[LINK_SMALL];
+  __shared__ u32 pairs[LINK_SMALL / 2];
+  __shared__ int size[LINK_SMALL], nn[LINK_SMALL], n_new, bad_any;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, v = tid;
+  if (tid == 0) bad_any = 0;
+  if (tid < LINK_SMALL) { size[tid] = tid < ns ? 1 : 0; ekey[tid] = LINK_NONE; eaux[tid] = LINK_NONE; }
+  __syncthreads ();
+  int bad = 0;
+  for (int x = tid; x < ns * ns; x += 256) {            // every cell beside its mirror, as linkage_small_kernel
+    const int a = x / ns, b = x % ns;
+    const u64 k = linkage_key (dist[x], dist[b * ns + a], a == b, metric, min_both, bad);
+    if (linkage == TJAMD_AGGL_AVERAGE && k != LINK_NONE && k >= AGGL_KEY_MAX) bad |= 4;
+    keys[a * LINK_SMALL + b] = k;
+  }
+  if (bad) atomicOr (&bad_any, bad);
+  __syncthreads ();
+  if (bad_any) { if (tid == 0) flags[0] = bad_any; return; }   // (the whole workgroup; nothing of the caller's is written)
+  int n_links = 0, round = 0;                           // (the same in every thread)
+  for (;; round++) {
+    for (int a = wave; a < ns; a += 4) {                // (a) a wavefront per row, lane b
+      u64 bk = LINK_NONE;
+      int bb = lane;
+      const int sa = size[a], sb = lane < ns ? size[lane] : 0;
+      if (sa != 0 && sb != 0) {
+        const u64 k = keys[a * LINK_SMALL + lane];
+        if (k != LINK_NONE) bk = aggl_d (k, sa, sb, linkage);
+      }
+      for (int o = 32; o; o >>= 1) {
+        const u64 ok = shfl_xor64 (bk, o);
+        const int ob = __shfl_xor (bb, o);
+        if (ok < bk || (ok == bk && ob < bb)) { bk = ok; bb = ob; }
+      }
+      if (lane == 0) { rowkey[a] = bk; nn[a] = bk != LINK_NONE ? bb : -1; }
+    }
+    if (tid == 0) n_new = 0;
+    __syncthreads ();
+    if (v < ns && nn[v] > v && nn[nn[v]] == v) {        // (b) the mutual pairs, from their smaller ends
+      const int at = atomicAdd (&n_new, 1), w = nn[v];
+      pairs[at] = (u32) v << 12 | (u32) w;
+      ekey[n_links + at] = rowkey[v]; eaux[n_links + at] = (u64) round << 24 | (u64) v << 12 | (u64) w;
+    }
+    __syncthreads ();
+    const int n = n_new;
+    if (n == 0) break;                                  // (the whole workgroup) no live cluster has an edge
+    for (int x = tid; x < n * LINK_SMALL; x += 256) {   // (c) rows, then columns
+      const int X = (int) (pairs[x >> 6] >> 12), Y = (int) (pairs[x >> 6] & 4095u), col = x & 63;
+      if (col < ns) keys[X * LINK_SMALL + col] = aggl_f (keys[X * LINK_SMALL + col], keys[Y * LINK_SMALL + col], linkage);
+    }
+    __syncthreads ();
+    for (int x = tid; x < n * LINK_SMALL; x += 256) {
+      const int P = (int) (pairs[x >> 6] >> 12), Q = (int) (pairs[x >> 6] & 4095u), row = x & 63;
+      if (row < ns) keys[row * LINK_SMALL + P] = aggl_f (keys[row * LINK_SMALL + P], keys[row * LINK_SMALL + Q], linkage);
+    }
+    if (tid < n) { const int X = (int) (pairs[tid] >> 12), Y = (int) (pairs[tid] & 4095u); size[X] += size[Y]; size[Y] = 0; }
+    n_links += n;
+    __syncthreads ();
+  }
+  for (int k = 2; k <= LINK_SMALL; k <<= 1)             // the bitonic network over all 64 places, the empty ones last
+    for (int j = k >> 1; j > 0; j >>= 1) {
+      if (tid < LINK_SMALL / 2) {
+        const int i = ((tid & ~(j - 1)) << 1) | (tid & (j - 1)), l = i | j;
+        const u64 ki = ekey[i], kl = ekey[l], xi = eaux[i], xl = eaux[l];
+        const bool above = ki > kl || (ki == kl && xi > xl);
+        if (above == ((i & k) == 0)) { ekey[i] = kl; ekey[l] = ki; eaux[i] = xl; eaux[l] = xi; }
+      }
+      __syncthreads ();
+    }
+  if (tid < n_links) out[tid] = Link {(int) (eaux[tid] >> 12 & 4095u), (int) (eaux[tid] & 4095u), (long long) ekey[tid]};
+  if (tid == 0) { flags[1] = 1; flags[2] = n_links; flags[3] = round; }
+}
+
+extern "C" long tjamd_sample_agglomerate (tjamd_counter *c, const tjamd_sample_distance *d_dist, int n_samples, int metric, int min_both, int linkage, tjamd_link *d_links,
+                                          int *h_n_rounds)
+{
+  static const char *fn = "tjamd_sample_agglomerate";
+  if (!c) return -set_err (TJAMD_ERR_ARG, "%s: null counter", fn);
+  if (!d_dist) return -set_err (TJAMD_ERR_ARG, "%s: null d_dist", fn);
+  if (!d_links && n_samples > 1) return -set_err (TJAMD_ERR_ARG, "%s: null d_links", fn);
+  if (n_samples < 1 || n_samples > LINK_MAX) return -set_err (TJAMD_ERR_ARG, "%s: n_samples %d outside 1..4096", fn, n_samples);
+  if (metric < TJAMD_LINK_DIFFER || metric > TJAMD_LINK_DIFFER_RATE) return -set_err (TJAMD_ERR_ARG, "%s: metric %d outside 0..2", fn, metric);
+  if (min_both < 1) return -set_err (TJAMD_ERR_ARG, "%s: min_both %d below 1", fn, min_both);
+  if (linkage != TJAMD_AGGL_COMPLETE && linkage != TJAMD_AGGL_AVERAGE) return -set_err (TJAMD_ERR_ARG, "%s: linkage %d outside 1..2", fn, linkage);
+  if (tjamd_device_count () <= 0) return -set_err (TJAMD_ERR_NO_DEVICE, "%s: TJAMD_ERR_NO_DEVICE: no HIP device visible (the tree is built on the device; no CPU fallback)", fn);
+  Stage st (c, T_SAMPLE_AGGLOMERATE);                   // (a refused call leaves no timing behind)
+  if (hipSetDevice (c->device) != hipSuccess) return -set_err (TJAMD_ERR_HIP, "hipSetDevice failed");
+  int rc;
+  if (n_samples == 1) {                                 // one sample: no pair, no kernel
+    rc = read_back (c, fn, nullptr, nullptr, 0);
+    if (rc) return -rc;
+    if (h_n_rounds) *h_n_rounds = 0;
+    return 0;
+  }
+  const int ld = (n_samples + 1) & ~1;                  // a row of the matrix: an even number of cells, 16-byte loads
+  int P = 2;
+  while (P < n_samples - 1) P <<= 1;
+  const bool small = n_samples <= LINK_SMALL && c->link_small;   // one workgroup, one launch
+  ScratchCut cut;
+  int *flags, *size, *comp; LinkRowBest *rowbest; AgglEdge *edges; u32 *pairs; u64 *keys;
+  cut.take (flags, 64); cut.take (size, small ? 0 : (size_t) ld + 64); cut.take (comp, small ? 0 : (size_t) ld + 64); cut.take (rowbest, small ? 0 : (size_t) n_samples);
+  cut.take (edges, small ? 0 : (size_t) n_samples); cut.take (pairs, small ? 0 : (size_t) n_samples); cut.take (keys, small ? 0 : (size_t) n_samples * ld);
+  rc = cut.commit (c);
+  if (rc) return -rc;
+  if (hipMemsetAsync (flags, 0, 256, c->stream) != hipSuccess) return -set_err (TJAMD_ERR_HIP, "%s: memset failed", fn);
+  u32 h_flags[4] = {0, 0, 0, 0};
+  st.begin ();
+  if (small) {
+    hipLaunchKernelGGL (aggl_small_kernel, dim3 (1), dim3 (256), 0, c->stream, (const SampleDistance *) d_dist, n_samples, metric, min_both, linkage, (Link *) d_links, flags);
+    st.end ();
+    rc = read_back (c, fn, flags, h_flags, 4);
+    if (rc) return -rc;
+  } else {
+    const unsigned row_blocks = (unsigned) ((n_samples + 3) / 4);
+    hipLaunchKernelGGL (linkage_keys_kernel, dim3 ((unsigned) ((ld + LINK_TILE - 1) / LINK_TILE), (unsigned) ((n_samples + LINK_TILE - 1) / LINK_TILE)), dim3 (256), 0, c->stream,
+                        (const SampleDistance *) d_dist, n_samples, ld, metric, min_both, keys, comp, flags);   // (comp: N15's labels, not read here)
+    hipLaunchKernelGGL (aggl_init_kernel, dim3 ((unsigned) std::min<long> (((long) n_samples * ld + 255) / 256, 4096)), dim3 (256), 0, c->stream, (const u64 *) keys, n_samples, ld,
+                        linkage, size, flags);
+    // a round that is not the last merges at least one pair: n_samples - 1 rounds at most.  A look at the flag words per batch.
+    for (int queued = 0; queued < n_samples - 1 && !h_flags[0] && !h_flags[1]; ) {
+      for (int r = 0; r < c->aggl_batch && queued < n_samples - 1; r++, queued++) {
+        hipLaunchKernelGGL (aggl_rowmin_kernel, dim3 (row_blocks), dim3 (256), 0, c->stream, (const u64 *) keys, n_samples, ld, linkage, (const int *) size, rowbest, (const int *) flags);
+        hipLaunchKernelGGL (aggl_pairs_kernel, dim3 (1), dim3 (1024), 0, c->stream, (const LinkRowBest *) rowbest, n_samples, size, edges, pairs, flags);
+        hipLaunchKernelGGL (aggl_rows_kernel, dim3 ((unsigned) (n_samples / 2)), dim3 (256), 0, c->stream, keys, ld, linkage, (const u32 *) pairs, (const int *) flags);
+        hipLaunchKernelGGL (aggl_cols_kernel, dim3 (row_blocks), dim3 (256), 0, c->stream, keys, n_samples, ld, linkage, (const int *) size, (const u32 *) pairs, (const int *) flags);
+      }
+      hipLaunchKernelGGL (aggl_sort_kernel, dim3 (1), dim3 (1024), 0, c->stream, (const AgglEdge *) edges, P, (Link *) d_links, (const int *) flags);
+      st.end ();                                        // (the last one recorded is the one that is read)
+      rc = read_back (c, fn, flags, h_flags, 4);
+      if (rc) return -rc;
+    }
+  }
+  if (h_flags[0] & 1u) return -set_err (TJAMD_ERR_ARG, "%s: a cell has n_both < 0, n_differ < 0, n_differ > n_both or length_diff < 0", fn);
+  if (h_flags[0] & 2u) return -set_err (TJAMD_ERR_ARG, "%s: a cell (a, b) differs from the cell (b, a)", fn);
+  if (h_flags[0] & 4u) return -set_err (TJAMD_ERR_ARG, "%s: a key of 2^40 or more under TJAMD_AGGL_AVERAGE", fn);
+  if (!h_flags[1]) return -set_err (TJAMD_ERR_STATE, "%s: the rounds did not end", fn);
+  st.done ();
+  if (h_n_rounds) *h_n_rounds = (int) h_flags[3];
+  return (long) h_flags[2];
+}
+extern "C" double tjamd_last_sample_agglomerate_ms (tjamd_counter *c) { return c ? c->timer[T_SAMPLE_AGGLOMERATE].ms (c->device) : -1.0; }
