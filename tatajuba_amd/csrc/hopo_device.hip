@@ -3266,6 +3266,27 @@ __device__ __forceinline__ u32 block_exclusive_scan_256 (u32 v, u32 *s_tmp, u32 
   return wbase + x - v;
 }
 
+// the sum of `mine` over the threads before this one in a workgroup of 1024, and over all of them; one barrier.  wsum: 16 words
+// that nobody reads or writes between the barrier before the call and the barrier after it
+__device__ __forceinline__ int block_exclusive_scan_1024 (int mine, int tid, int *wsum, int &total)
+{
+  const int lane = tid & 63, wave = tid >> 6;
+  int incl = mine;
+  #pragma unroll
+  for (int o = 1; o < 64; o <<= 1) {
+    const int v = __shfl_up (incl, o);
+    if (lane >= o) incl += v;
+  }
+  if (lane == 63) wsum[wave] = incl;
+  __syncthreads ();
+  const int w = lane & 15;                              // every sixteen lanes hold the sixteen sums and fold them among themselves
+  int all = wsum[w], before = w < wave ? all : 0;
+  #pragma unroll
+  for (int o = 1; o < 16; o <<= 1) { all += __shfl_xor (all, o); before += __shfl_xor (before, o); }
+  total = all;
+  return before + incl - mine;
+}
+
 __global__ __launch_bounds__ (256)
 void scan_reduce_kernel (const u32 *__restrict__ in, long n, u32 *__restrict__ bsum)
 {
@@ -4118,6 +4139,15 @@ struct ScratchCut
     return rc;
   }
 };
+
+// The 64 flag words of a call as the last piece of its cut: takes them, commits the cut and clears them on the counter's stream.
+static int commit_with_flags (ScratchCut &cut, tjamd_counter *c, const char *fn, int *&flags)
+{
+  cut.take (flags, 64);
+  const int rc = cut.commit (c);
+  if (rc) return rc;
+  return hipMemsetAsync (flags, 0, 256, c->stream) == hipSuccess ? TJAMD_OK : set_err (TJAMD_ERR_HIP, "%s: memset failed", fn);
+}
 
 // The tail of a call, behind its stage's end (): the error of its launches, the copy of `words` 32-bit words from d to the
 // host (none: the wait alone) on the counter's stream, the wait for the stream.  Decoding the words is the caller's.
@@ -5934,6 +5964,7 @@ __device__ __forceinline__ void check_tiling (const UnionTract *__restrict__ tra
 }
 // a 64-bit word from lane `from` / from lane ^ o of a segment of `width` lanes
 __device__ __forceinline__ u64 shfl64 (u64 x, int from, int width = 64) { const u32 lo = __shfl ((u32) x, from, width), hi = __shfl ((u32) (x >> 32), from, width); return ((u64) hi << 32) | lo; }
+__device__ __forceinline__ u64 readlane64 (u64 x, int from) { return ((u64) (u32) __builtin_amdgcn_readlane ((int) (x >> 32), from) << 32) | (u32) __builtin_amdgcn_readlane ((int) x, from); }
 __device__ __forceinline__ u64 shfl_xor64 (u64 x, int o, int width = 64) { const u32 lo = __shfl_xor ((u32) x, o, width), hi = __shfl_xor ((u32) (x >> 32), o, width); return ((u64) hi << 32) | lo; }
 
 // exact row totals: one segment of S lanes per row, a lane summing samples lane, lane + S, ... (S contiguous words per step)
@@ -9205,6 +9236,40 @@ struct LinkEdge { u64 key; u32 pair, pad; };            // a chosen edge before 
 #define LINK_MAX 4096                                   // samples: the labels of one workgroup's LDS
 // flags of a call: [0] error bits (1 a cell's values, 2 a cell and its mirror; clusters: 1 a link), [1] done (clusters: the number of clusters),
 // [2] links appended so far, [3] rounds that merged something
+static const char CELL_REFUSED[] = "%s: a cell has n_both < 0, n_differ < 0, n_differ > n_both or length_diff < 0";   // error bit 1
+static const char MIRROR_REFUSED[] = "%s: a cell (a, b) differs from the cell (b, a)";                                   // error bit 2
+
+// the early return of every kernel of the rounds: the call's error bits or its `done` word are up
+__device__ __forceinline__ bool link_rounds_over (const int *flags) { return (((volatile const int *) flags)[0] | ((volatile const int *) flags)[1]) != 0; }
+
+// the smallest (key, b) over the lanes of a wavefront, left in every lane: six cross-lane steps
+__device__ __forceinline__ void wave_min_key_b (u64 &bk, int &bb)
+{
+  for (int o = 32; o; o >>= 1) {
+    const u64 ok = shfl_xor64 (bk, o);
+    const int ob = __shfl_xor (bb, o);
+    if (ok < bk || (ok == bk && ob < bb)) { bk = ok; bb = ob; }
+  }
+}
+
+// P places of LDS (a power of two) put into ascending order of (key, tie) by a workgroup of THREADS: the bitonic network, a
+// compare-exchange a thread and step where P / 2 reaches that far.  The caller's barrier stands before the call; one stands
+// behind every step.  Places to be left last hold all ones in both words.
+template <int THREADS, class T>
+__device__ __forceinline__ void lds_bitonic_sort (u64 *key, T *tie, int P)
+{
+  for (int k = 2; k <= P; k <<= 1)
+    for (int j = k >> 1; j > 0; j >>= 1) {
+      for (int t = threadIdx.x; t < P / 2; t += THREADS) {
+        const int i = ((t & ~(j - 1)) << 1) | (t & (j - 1)), l = i | j;
+        const u64 ki = key[i], kl = key[l];
+        const T xi = tie[i], xl = tie[l];
+        const bool above = ki > kl || (ki == kl && xi > xl);
+        if (above == ((i & k) == 0)) { key[i] = kl; key[l] = ki; tie[i] = xl; tie[l] = xi; }
+      }
+      __syncthreads ();
+    }
+}
 
 // the checks of a cell d against the rule and against its mirror m (error bits into `bad`), and its key: LINK_NONE for no edge
 __device__ __forceinline__ u64 linkage_key (const SampleDistance &d, const SampleDistance &m, bool diagonal, int metric, int min_both, int &bad)
@@ -9244,7 +9309,7 @@ void linkage_keys_kernel (const SampleDistance *__restrict__ dist, int ns, int l
 __global__ __launch_bounds__ (256)
 void linkage_rowmin_kernel (const u64 *__restrict__ keys, int ns, int ld, const int *__restrict__ comp, LinkRowBest *__restrict__ rowbest, const int *__restrict__ flags)
 {
-  if ((((volatile const int *) flags)[0] | ((volatile const int *) flags)[1]) != 0) return;
+  if (link_rounds_over (flags)) return;
   const int lane = threadIdx.x & 63, a = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (a >= ns) return;                                  // (a whole wavefront)
   const int ca = comp[a];
@@ -9259,11 +9324,7 @@ void linkage_rowmin_kernel (const u64 *__restrict__ keys, int ns, int ld, const 
     if (cb.x != ca && k.x < bk) { bk = k.x; bb = 2 * p; }
     if (cb.y != ca && k.y < bk) { bk = k.y; bb = 2 * p + 1; }
   }
-  for (int o = 32; o; o >>= 1) {
-    const u64 ok = shfl_xor64 (bk, o);
-    const int ob = __shfl_xor (bb, o);
-    if (ok < bk || (ok == bk && ob < bb)) { bk = ok; bb = ob; }
-  }
+  wave_min_key_b (bk, bb);
   if (lane == 0) rowbest[a] = LinkRowBest {bk, bb, 0};
 }
 
@@ -9274,7 +9335,7 @@ void linkage_merge_kernel (const LinkRowBest *__restrict__ rowbest, int ns, int 
   __shared__ u32 cbpair[LINK_MAX];                      // ... and the smallest pair among the rows that hold it
   __shared__ unsigned short par[LINK_MAX];              // the labels while they are hooked and flattened
   __shared__ int n_new;
-  if ((((volatile const int *) flags)[0] | ((volatile const int *) flags)[1]) != 0) return;
+  if (link_rounds_over (flags)) return;
   const int tid = threadIdx.x, base = flags[2];
   u64 key[LINK_MAX / 1024];
   int other[LINK_MAX / 1024], cv[LINK_MAX / 1024];
@@ -9343,17 +9404,7 @@ void linkage_sort_kernel (const LinkEdge *__restrict__ edges, int P, Link *__res
     skey[i] = in ? edges[i].key : LINK_NONE; spair[i] = in ? edges[i].pair : ~0u;
   }
   __syncthreads ();
-  for (int k = 2; k <= P; k <<= 1)
-    for (int j = k >> 1; j > 0; j >>= 1) {
-      for (int t = tid; t < P / 2; t += 1024) {
-        const int i = ((t & ~(j - 1)) << 1) | (t & (j - 1)), l = i | j;
-        const u64 ki = skey[i], kl = skey[l];
-        const u32 pi = spair[i], pl = spair[l];
-        const bool above = ki > kl || (ki == kl && pi > pl);
-        if (above == ((i & k) == 0)) { skey[i] = kl; skey[l] = ki; spair[i] = pl; spair[l] = pi; }
-      }
-      __syncthreads ();
-    }
+  lds_bitonic_sort<1024> (skey, spair, P);
   for (int i = tid; i < n; i += 1024) out[i] = Link {(int) (spair[i] >> 12), (int) (spair[i] & 4095u), (long long) skey[i]};
 }
 
@@ -9385,11 +9436,7 @@ void linkage_small_kernel (const SampleDistance *__restrict__ dist, int ns, int 
       u64 bk = LINK_NONE;
       int bb = lane;
       if (lane < ns && comp[lane] != comp[a]) bk = keys[a * LINK_SMALL + lane];
-      for (int o = 32; o; o >>= 1) {
-        const u64 ok = shfl_xor64 (bk, o);
-        const int ob = __shfl_xor (bb, o);
-        if (ok < bk || (ok == bk && ob < bb)) { bk = ok; bb = ob; }
-      }
+      wave_min_key_b (bk, bb);
       if (lane == 0) { rowkey[a] = bk; rowb[a] = bb; cbkey[a] = LINK_NONE; cbpair[a] = ~0u; par[a] = comp[a]; }
     }
     if (tid == 0) n_new = 0;
@@ -9420,56 +9467,67 @@ void linkage_small_kernel (const SampleDistance *__restrict__ dist, int ns, int 
     if (tid == 0) n_links += n_new;
     __syncthreads ();
   }
-  for (int k = 2; k <= LINK_SMALL; k <<= 1)             // step 3: the bitonic network over all 64 places, the empty ones last
-    for (int j = k >> 1; j > 0; j >>= 1) {
-      if (tid < LINK_SMALL / 2) {
-        const int i = ((tid & ~(j - 1)) << 1) | (tid & (j - 1)), l = i | j;
-        const u64 ki = ekey[i], kl = ekey[l];
-        const u32 pi = epair[i], pl = epair[l];
-        const bool above = ki > kl || (ki == kl && pi > pl);
-        if (above == ((i & k) == 0)) { ekey[i] = kl; ekey[l] = ki; epair[i] = pl; epair[l] = pi; }
-      }
-      __syncthreads ();
-    }
+  lds_bitonic_sort<256> (ekey, epair, LINK_SMALL);      // step 3: all 64 places, the empty ones last
   if (tid < n_links) out[tid] = Link {(int) (epair[tid] >> 12), (int) (epair[tid] & 4095u), (long long) ekey[tid]};
   if (tid == 0) flags[2] = n_links;
+}
+
+// the argument checks that tjamd_sample_linkage and tjamd_sample_agglomerate share, in their order: 0, or the code of the first
+// that fails with its message set
+static int link_check_args (const char *fn, tjamd_counter *c, const tjamd_sample_distance *d_dist, int n_samples, int metric, int min_both, const tjamd_link *d_links)
+{
+  if (!c) return set_err (TJAMD_ERR_ARG, "%s: null counter", fn);
+  if (!d_dist) return set_err (TJAMD_ERR_ARG, "%s: null d_dist", fn);
+  if (!d_links && n_samples > 1) return set_err (TJAMD_ERR_ARG, "%s: null d_links", fn);
+  if (n_samples < 1 || n_samples > LINK_MAX) return set_err (TJAMD_ERR_ARG, "%s: n_samples %d outside 1..4096", fn, n_samples);
+  if (metric < TJAMD_LINK_DIFFER || metric > TJAMD_LINK_DIFFER_RATE) return set_err (TJAMD_ERR_ARG, "%s: metric %d outside 0..2", fn, metric);
+  if (min_both < 1) return set_err (TJAMD_ERR_ARG, "%s: min_both %d below 1", fn, min_both);
+  return 0;
+}
+
+// The shape of a call on n_samples > 1 samples.  ld: a row of the key matrix, an even number of cells for 16-byte loads; P: the
+// places of the sort, a power of two that holds n_samples - 1 links
+struct LinkShape
+{
+  int ld, P;
+  explicit LinkShape (int n_samples) : ld ((n_samples + 1) & ~1), P (2) { while (P < n_samples - 1) P <<= 1; }
+};
+
+// step 1 of both entries: the key pass, a workgroup per tile
+static void launch_linkage_keys (tjamd_counter *c, const tjamd_sample_distance *d_dist, int n_samples, int ld, int metric, int min_both, u64 *keys, int *comp, int *flags)
+{
+  hipLaunchKernelGGL (linkage_keys_kernel, dim3 ((unsigned) ((ld + LINK_TILE - 1) / LINK_TILE), (unsigned) ((n_samples + LINK_TILE - 1) / LINK_TILE)), dim3 (256), 0, c->stream,
+                      (const SampleDistance *) d_dist, n_samples, ld, metric, min_both, keys, comp, flags);
 }
 
 extern "C" long tjamd_sample_linkage (tjamd_counter *c, const tjamd_sample_distance *d_dist, int n_samples, int metric, int min_both, tjamd_link *d_links)
 {
   static const char *fn = "tjamd_sample_linkage";
-  if (!c) return -set_err (TJAMD_ERR_ARG, "%s: null counter", fn);
-  if (!d_dist) return -set_err (TJAMD_ERR_ARG, "%s: null d_dist", fn);
-  if (!d_links && n_samples > 1) return -set_err (TJAMD_ERR_ARG, "%s: null d_links", fn);
-  if (n_samples < 1 || n_samples > LINK_MAX) return -set_err (TJAMD_ERR_ARG, "%s: n_samples %d outside 1..4096", fn, n_samples);
-  if (metric < TJAMD_LINK_DIFFER || metric > TJAMD_LINK_DIFFER_RATE) return -set_err (TJAMD_ERR_ARG, "%s: metric %d outside 0..2", fn, metric);
-  if (min_both < 1) return -set_err (TJAMD_ERR_ARG, "%s: min_both %d below 1", fn, min_both);
+  int rc = link_check_args (fn, c, d_dist, n_samples, metric, min_both, d_links);
+  if (rc) return -rc;
   if (tjamd_device_count () <= 0) return -set_err (TJAMD_ERR_NO_DEVICE, "%s: TJAMD_ERR_NO_DEVICE: no HIP device visible (the tree is built on the device; no CPU fallback)", fn);
   Stage st (c, T_SAMPLE_LINKAGE);                       // (a refused call leaves no timing behind)
   if (hipSetDevice (c->device) != hipSuccess) return -set_err (TJAMD_ERR_HIP, "hipSetDevice failed");
-  int rc;
   if (n_samples == 1) {                                 // one sample: no pair, no kernel
     rc = read_back (c, fn, nullptr, nullptr, 0);
     return rc ? -rc : 0;
   }
-  const int ld = (n_samples + 1) & ~1;                  // a row of keys: an even number of them, 16-byte loads
-  int n_rounds = 0, P = 2;
+  const LinkShape shape (n_samples);
+  const int ld = shape.ld, P = shape.P;
+  int n_rounds = 0;
   while ((1 << n_rounds) < n_samples) n_rounds++;       // every round at least halves the components that still have an edge
-  while (P < n_samples - 1) P <<= 1;
   const bool small = n_samples <= LINK_SMALL && c->link_small;   // one workgroup, one launch
   ScratchCut cut;
   int *flags, *comp; LinkRowBest *rowbest; LinkEdge *edges; u64 *keys;
-  cut.take (flags, 64); cut.take (comp, small ? 0 : (size_t) ld + 64); cut.take (rowbest, small ? 0 : (size_t) n_samples); cut.take (edges, small ? 0 : (size_t) n_samples);
+  cut.take (comp, small ? 0 : (size_t) ld + 64); cut.take (rowbest, small ? 0 : (size_t) n_samples); cut.take (edges, small ? 0 : (size_t) n_samples);
   cut.take (keys, small ? 0 : (size_t) n_samples * ld);
-  rc = cut.commit (c);
+  rc = commit_with_flags (cut, c, fn, flags);
   if (rc) return -rc;
-  if (hipMemsetAsync (flags, 0, 256, c->stream) != hipSuccess) return -set_err (TJAMD_ERR_HIP, "%s: memset failed", fn);
   st.begin ();
   if (small)
     hipLaunchKernelGGL (linkage_small_kernel, dim3 (1), dim3 (256), 0, c->stream, (const SampleDistance *) d_dist, n_samples, metric, min_both, n_rounds, (Link *) d_links, flags);
   else {
-    hipLaunchKernelGGL (linkage_keys_kernel, dim3 ((unsigned) ((ld + LINK_TILE - 1) / LINK_TILE), (unsigned) ((n_samples + LINK_TILE - 1) / LINK_TILE)), dim3 (256), 0, c->stream,
-                        (const SampleDistance *) d_dist, n_samples, ld, metric, min_both, keys, comp, flags);
+    launch_linkage_keys (c, d_dist, n_samples, ld, metric, min_both, keys, comp, flags);
     for (int r = 0; r < n_rounds; r++) {
       hipLaunchKernelGGL (linkage_rowmin_kernel, dim3 ((unsigned) ((n_samples + 3) / 4)), dim3 (256), 0, c->stream, (const u64 *) keys, n_samples, ld, (const int *) comp,
                           rowbest, (const int *) flags);
@@ -9481,8 +9539,8 @@ extern "C" long tjamd_sample_linkage (tjamd_counter *c, const tjamd_sample_dista
   u32 h_flags[4] = {0, 0, 0, 0};
   rc = read_back (c, fn, flags, h_flags, 4);
   if (rc) return -rc;
-  if (h_flags[0] & 1u) return -set_err (TJAMD_ERR_ARG, "%s: a cell has n_both < 0, n_differ < 0, n_differ > n_both or length_diff < 0", fn);
-  if (h_flags[0] & 2u) return -set_err (TJAMD_ERR_ARG, "%s: a cell (a, b) differs from the cell (b, a)", fn);
+  if (h_flags[0] & 1u) return -set_err (TJAMD_ERR_ARG, CELL_REFUSED, fn);
+  if (h_flags[0] & 2u) return -set_err (TJAMD_ERR_ARG, MIRROR_REFUSED, fn);
   st.done ();
   return (long) h_flags[2];
 }
@@ -9491,7 +9549,7 @@ extern "C" double tjamd_last_sample_linkage_ms (tjamd_counter *c) { return c ? c
 __global__ __launch_bounds__ (1024)
 void linkage_clusters_kernel (const Link *__restrict__ links, long n_links, int ns, long long threshold, int *__restrict__ cluster, int *__restrict__ flags)
 {
-  __shared__ int lab[LINK_MAX], rank[LINK_MAX], sums[2][1024];
+  __shared__ int lab[LINK_MAX], rank[LINK_MAX], wsum[16];
   volatile int *const vlab = lab;                       // (labels move under the reader: every read is a load)
   const int tid = threadIdx.x;
   int bad = 0;
@@ -9529,14 +9587,8 @@ void linkage_clusters_kernel (const Link *__restrict__ links, long n_links, int 
     const int v = (LINK_MAX / 1024) * tid + j;
     if (v < ns && lab[v] == v) mine++;
   }
-  sums[0][tid] = mine;
-  __syncthreads ();
-  int s = 0;
-  for (int o = 1; o < 1024; o <<= 1, s ^= 1) {
-    sums[s ^ 1][tid] = sums[s][tid] + (tid >= o ? sums[s][tid - o] : 0);
-    __syncthreads ();
-  }
-  int at = sums[s][tid] - mine;
+  int n_clusters;
+  int at = block_exclusive_scan_1024 (mine, tid, wsum, n_clusters);
   #pragma unroll
   for (int j = 0; j < LINK_MAX / 1024; j++) {
     const int v = (LINK_MAX / 1024) * tid + j;
@@ -9544,7 +9596,7 @@ void linkage_clusters_kernel (const Link *__restrict__ links, long n_links, int 
   }
   __syncthreads ();
   for (int v = tid; v < ns; v += 1024) cluster[v] = rank[lab[v]];
-  if (tid == 0) flags[1] = sums[s][1023];
+  if (tid == 0) flags[1] = n_clusters;
 }
 
 extern "C" long tjamd_linkage_clusters (tjamd_counter *c, const tjamd_link *d_links, long n_links, int n_samples, long long threshold, int *d_cluster)
@@ -9560,10 +9612,8 @@ extern "C" long tjamd_linkage_clusters (tjamd_counter *c, const tjamd_link *d_li
   if (hipSetDevice (c->device) != hipSuccess) return -set_err (TJAMD_ERR_HIP, "hipSetDevice failed");
   ScratchCut cut;
   int *flags;
-  cut.take (flags, 64);
-  int rc = cut.commit (c);
+  int rc = commit_with_flags (cut, c, fn, flags);
   if (rc) return -rc;
-  if (hipMemsetAsync (flags, 0, 256, c->stream) != hipSuccess) return -set_err (TJAMD_ERR_HIP, "%s: memset failed", fn);
   st.begin ();
   hipLaunchKernelGGL (linkage_clusters_kernel, dim3 (1), dim3 (1024), 0, c->stream, (const Link *) d_links, n_links, n_samples, threshold, d_cluster, flags);
   st.end ();
@@ -9606,48 +9656,144 @@ static_assert (sizeof (GroupCall) == 16 && sizeof (GroupCall) == sizeof (tjamd_g
 static_assert (sizeof (GroupSite) == 16 && sizeof (GroupSite) == sizeof (tjamd_group_site), "group site layout");
 static_assert (sizeof (GroupMark) == 16 && sizeof (GroupMark) == sizeof (tjamd_group_mark), "group mark layout");
 
-#define GRP_MAX 4096                                    // samples, groups and, by the rule's bound, alleles of a site
-#define GRP_SMALL 64                                    // samples up to which a wavefront takes a site
-#define GRP_THREADS 1024
-#define GRP_PER (GRP_MAX / GRP_THREADS)                 // samples, and groups, of a thread of the second form
-#define GRP_FOLD 8                                      // distinct (group, genotype) keys a wavefront folds before its lanes go alone
-#define GRP_NONE 0x7fffffff
-// words of a call: [0] error bits (1 a label, 2 a site's n_alleles, 4 a cell), [1] the number of marks (the scan's total);
-// from word 64 on: the marks of every group
-struct GroupArgs
+// The constants of the site marks, one set for the groups of N16 and the clades of N17 (a key: a group or a node of the tree)
+#define CLD_MAX 4096                                    // samples, keys and, by the rule's bound, alleles of a site
+#define CLD_SMALL 64                                    // samples up to which a wavefront takes a site
+#define CLD_THREADS 1024
+#define CLD_PER (CLD_MAX / CLD_THREADS)                 // samples or leaf positions, and keys, of a thread of the second form
+#define CLD_FOLD 8                                      // distinct keys a wavefront folds into a lane each before its lanes go alone
+#define CLD_WAVE_SITES 64                               // sites a workgroup of the first form is sized for, where there are that many
+#define CLD_NONE 0x7fffffff
+// words of a call: [0] error bits, [1] the number of marks (the scan's total); from word 64 on: the marks of every key.  The
+// error bits of tjamd_group_sites: 1 a label, 2 a site's n_alleles, 4 a cell; of tjamd_clade_sites: 1 the order, 2 a node, 4 a
+// site's n_alleles, 8 a cell
+struct MarkArgs                                         // what the two entries share; GroupArgs and CladeArgs add their own
 {
-  const Site *sites; long n_sites; const int16_t *geno; int ns; const int *group; int n_groups, min_called;
-  GroupCall *calls; GroupSite *site_out; int *group_marks; GroupMark *marks; long cap;
-  int *flags, *gm; u32 *cnt;                            // cnt: a site's marks (written by the first pass), then their offsets (read by the second)
+  int ns, n_keys, min_called; const Site *sites; long n_sites; const int16_t *geno;   // (the three counts first: with the sites first the second pass of both workgroup forms takes 72 registers and more)
+  GroupCall *calls; GroupSite *site_out; int *key_marks; GroupMark *marks; long cap;
+  int *flags, *km; u32 *cnt;                            // km: the marks of every key, in scratch; cnt: a site's marks (written by the first pass), then their offsets (read by the second)
 };
+struct GroupArgs : MarkArgs { const int *group; };
 
-__device__ __forceinline__ u64 readlane64 (u64 x, int from)
+// The start of the second pass: false while the error flag is up, and the pass returns; workgroup 0 copies the marks of every
+// key out of scratch.
+template <int THREADS>
+__device__ __forceinline__ bool marks_emit_begin (const MarkArgs &A)
 {
-  return ((u64) (u32) __builtin_amdgcn_readlane ((int) (x >> 32), from) << 32) | (u32) __builtin_amdgcn_readlane ((int) x, from);
+  if (((volatile const int *) A.flags)[0] != 0) return false;
+  if (A.key_marks && blockIdx.x == 0)
+    for (int j = threadIdx.x; j < A.n_keys; j += THREADS) A.key_marks[j] = A.km[j];
+  return true;
+}
+
+// The rule of a mark for a key with a fixed genotype: enough called members, no called sample outside them carries it, and
+// somebody outside is called.
+__device__ __forceinline__ int mark_rule (int n_called, int min_called, int n_outside, bool outside_called)
+{
+  return n_called >= min_called && n_outside == 0 && outside_called;
+}
+
+// The end of the first pass of a wavefront form: the error bits; lane r of every wavefront holds the marks of one key, the same
+// key in all four wavefronts, and the first n lanes of the workgroup add theirs (key: that of this thread's lane) into scratch.
+__device__ __forceinline__ void marks_count_end_small (const MarkArgs &A, int bad, int (*s_marks)[CLD_SMALL], int my_marks, int n, int key)
+{
+  const int tid = threadIdx.x;
+  if (bad) atomicOr (A.flags, bad);
+  s_marks[tid >> 6][tid & 63] = my_marks;
+  __syncthreads ();
+  if (tid < n) {
+    const int sum = s_marks[0][tid] + s_marks[1][tid] + s_marks[2][tid] + s_marks[3][tid];
+    if (sum) atomicAdd (&A.km[key], sum);
+  }
+}
+
+// The end of the first pass of a workgroup form: the error bits, and the marks of this thread's keys (tid + CLD_THREADS * j).
+__device__ __forceinline__ void marks_count_end (const MarkArgs &A, int bad, const int (&kmarks)[CLD_PER], int tid)
+{
+  if (bad) atomicOr (A.flags, bad);
+  #pragma unroll
+  for (int j = 0; j < CLD_PER; j++)
+    if (kmarks[j]) atomicAdd (&A.km[tid + CLD_THREADS * j], kmarks[j]);
+}
+
+// A wavefront's active lanes folded by their keys before an LDS atomic: up to CLD_FOLD distinct keys elect a lane each, which
+// calls add (the number of its lanes); the lanes that are left call add (1).  Few keys are the usual case and would otherwise
+// meet on one address.
+template <class Add>
+__device__ __forceinline__ void fold_equal_keys (bool active, int key, int lane, Add add)
+{
+  u64 rem = __ballot (active);
+  #pragma unroll 1
+  for (int it = 0; it < CLD_FOLD && rem; it++) {
+    const int j = __ffsll ((long long) rem) - 1;
+    const u64 m = __ballot (active && key == __builtin_amdgcn_readlane (key, j));
+    if (lane == j) add ((int) __popcll (m));
+    rem &= ~m;
+    if ((m >> lane) & 1ull) active = false;
+  }
+  if (active) add (1);
+}
+
+// The tail of a site in the workgroup forms, in four steps.  x_cnt: the carriers of every genotype 0 .. na; markbits: a word
+// per 64 keys, bit set for a mark (the words of keys beyond n_keys stay 0).
+// 1. before the barrier that ends the calls: the genotypes that somebody carries, added to *s_ngeno
+__device__ __forceinline__ void site_count_genotypes (const int *x_cnt, int na, int tid, int *s_ngeno)
+{
+  int nz = 0;
+  for (int x = tid; x <= na; x += CLD_THREADS) nz += x_cnt[x] != 0;
+  for (int o = 32; o; o >>= 1) nz += __shfl_xor (nz, o);
+  if (nz && (tid & 63) == 0) atomicAdd (s_ngeno, nz);
+}
+// 2. behind that barrier: the first wavefront turns the mark words into the site's count and first key; thread 0 writes the
+//    count for the scan, or the site's record (called: the site's called samples; n_genotypes: step 1's sum), and then calls
+//    clear (), which zeroes the form's LDS words of a site
+template <bool EMIT, class Clear>
+__device__ __forceinline__ void site_marks_total (const MarkArgs &A, long i, const u64 *markbits, int tid, int called, const int &n_genotypes, Clear clear)
+{
+  if (tid >= 64) return;
+  const u64 w = markbits[tid];
+  int n_marks = __popcll (w), first = w ? tid * 64 + __ffsll ((long long) w) - 1 : CLD_NONE;
+  for (int o = 32; o; o >>= 1) { n_marks += __shfl_xor (n_marks, o); first = min (first, __shfl_xor (first, o)); }
+  if (tid == 0) {
+    if (!EMIT) A.cnt[i] = (u32) n_marks;
+    else if (A.site_out) A.site_out[i] = GroupSite {called, n_genotypes, n_marks, first == CLD_NONE ? -1 : first};
+    clear ();
+  }
+}
+// 3. the place of key j's mark in the list: the site's offset, the marks in the words below its own, the bits below it there
+__device__ __forceinline__ long site_mark_place (const MarkArgs &A, long i, const u64 *markbits, int j)
+{
+  long pos = (long) A.cnt[i] + __popcll (markbits[j >> 6] & ((1ull << (j & 63)) - 1ull));
+  #pragma unroll 1
+  for (int w = 0; w < (j >> 6); w++) pos += __popcll (markbits[w]);
+  return pos;
+}
+// 4. before the barrier that ends the site: the carriers cleared, as far as this site could touch them
+__device__ __forceinline__ void site_clear_genotypes (int *x_cnt, int na, int tid)
+{
+  for (int x = tid; x <= na; x += CLD_THREADS) x_cnt[x] = 0;
 }
 
 template <bool EMIT>
 __global__ __launch_bounds__ (256)
 void group_sites_small_kernel (const GroupArgs A)
 {
-  __shared__ int s_marks[4][GRP_SMALL];
-  if (EMIT && ((volatile const int *) A.flags)[0] != 0) return;
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, ns = A.ns, n_groups = A.n_groups;
-  if (EMIT && A.group_marks && blockIdx.x == 0)
-    for (int G = tid; G < n_groups; G += 256) A.group_marks[G] = A.gm[G];
+  __shared__ int s_marks[4][CLD_SMALL];
+  if (EMIT && !marks_emit_begin<256> (A)) return;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, ns = A.ns, n_groups = A.n_keys;
   int bad = 0, label = -1;
   if (lane < ns) {
     label = A.group[lane];
     if (label < -1 || label >= n_groups) { bad |= 1; label = -1; }
   }
   const u64 taking = __ballot (label >= 0);
-  int gid = GRP_NONE, ng = 0, my_marks = 0;             // lane r: the r-th smallest group that has a member, and its members
+  int gid = CLD_NONE, ng = 0, my_marks = 0;             // lane r: the r-th smallest group that has a member, and its members
   u64 gmask = 0;
-  for (int cur = -1; ng < GRP_SMALL; ng++) {
-    int next = label > cur ? label : GRP_NONE;
+  for (int cur = -1; ng < CLD_SMALL; ng++) {
+    int next = label > cur ? label : CLD_NONE;
     for (int o = 32; o; o >>= 1) next = min (next, __shfl_xor (next, o));
     next = __builtin_amdgcn_readfirstlane (next);
-    if (next == GRP_NONE) break;
+    if (next == CLD_NONE) break;
     const u64 m = __ballot (label == next);
     if (lane == ng) { gid = next; gmask = m; }
     cur = next;
@@ -9677,7 +9823,7 @@ void group_sites_small_kernel (const GroupArgs A)
         q.fixed = (cm & ~same) ? -2 : x;
         if (q.fixed >= 0) {
           q.n_outside = __popcll (same & others);
-          q.mark = q.n_called >= A.min_called && q.n_outside == 0 && others != 0;
+          q.mark = mark_rule (q.n_called, A.min_called, q.n_outside, others != 0);
         }
       }
       if (q.mark) {
@@ -9714,59 +9860,31 @@ void group_sites_small_kernel (const GroupArgs A)
         if (G < n_groups) A.calls[i * n_groups + G] = q;
       }
   }
-  if (EMIT) return;
-  if (bad) atomicOr (A.flags, bad);
-  s_marks[wave][lane] = my_marks;                       // every wavefront has the same list of groups
-  __syncthreads ();
-  if (tid < ng) {
-    const int n = s_marks[0][tid] + s_marks[1][tid] + s_marks[2][tid] + s_marks[3][tid];
-    if (n) atomicAdd (&A.gm[gid], n);
-  }
-}
-
-// a wavefront's called samples into the two tables of the site: lanes of one (group, genotype) first fold into one lane
-__device__ __forceinline__ void group_tally (bool active, int G, int g, int lane, int *g_cnt, int *g_min, int *g_max, int *x_cnt)
-{
-  const int key = G << 13 | g;                          // (g <= 4096)
-  u64 rem = __ballot (active);
-  #pragma unroll 1
-  for (int it = 0; it < GRP_FOLD && rem; it++) {
-    const int j = __ffsll ((long long) rem) - 1;
-    const u64 m = __ballot (active && key == __builtin_amdgcn_readlane (key, j));
-    if (lane == j) {
-      const int n = __popcll (m);
-      atomicAdd (&g_cnt[G], n); atomicMin (&g_min[G], g); atomicMax (&g_max[G], g); atomicAdd (&x_cnt[g], n);
-    }
-    rem &= ~m;
-    if ((m >> lane) & 1ull) active = false;
-  }
-  if (active) { atomicAdd (&g_cnt[G], 1); atomicMin (&g_min[G], g); atomicMax (&g_max[G], g); atomicAdd (&x_cnt[g], 1); }
+  if (!EMIT) marks_count_end_small (A, bad, s_marks, my_marks, ng, gid);   // every wavefront has the same list of groups
 }
 
 template <bool EMIT>
-__global__ __launch_bounds__ (GRP_THREADS)
+__global__ __launch_bounds__ (CLD_THREADS)
 void group_sites_large_kernel (const GroupArgs A, long per_block)
 {
-  __shared__ int g_cnt[GRP_MAX], g_min[GRP_MAX], g_max[GRP_MAX], x_cnt[GRP_MAX + 1];
-  __shared__ u64 markbits[GRP_MAX / 64];
+  __shared__ int g_cnt[CLD_MAX], g_min[CLD_MAX], g_max[CLD_MAX], x_cnt[CLD_MAX + 1];
+  __shared__ u64 markbits[CLD_MAX / 64];
   __shared__ int s_called, s_ngeno;
-  if (EMIT && ((volatile const int *) A.flags)[0] != 0) return;
-  const int tid = threadIdx.x, lane = tid & 63, ns = A.ns, n_groups = A.n_groups;
-  if (EMIT && A.group_marks && blockIdx.x == 0)
-    for (int G = tid; G < n_groups; G += GRP_THREADS) A.group_marks[G] = A.gm[G];
-  int bad = 0, label[GRP_PER], gmarks[GRP_PER];
+  if (EMIT && !marks_emit_begin<CLD_THREADS> (A)) return;
+  const int tid = threadIdx.x, lane = tid & 63, ns = A.ns, n_groups = A.n_keys;
+  int bad = 0, label[CLD_PER], gmarks[CLD_PER];
   #pragma unroll
-  for (int j = 0; j < GRP_PER; j++) {
-    const int s = tid + GRP_THREADS * j;
+  for (int j = 0; j < CLD_PER; j++) {
+    const int s = tid + CLD_THREADS * j;
     label[j] = -1; gmarks[j] = 0;
     if (s < ns) {
       label[j] = A.group[s];
       if (label[j] < -1 || label[j] >= n_groups) { bad |= 1; label[j] = -1; }
     }
-    g_cnt[s] = 0; g_min[s] = GRP_NONE; g_max[s] = -1; x_cnt[s] = 0;
+    g_cnt[s] = 0; g_min[s] = CLD_NONE; g_max[s] = -1; x_cnt[s] = 0;
   }
-  if (tid < GRP_MAX / 64) markbits[tid] = 0;
-  if (tid == 0) { x_cnt[GRP_MAX] = 0; s_called = 0; s_ngeno = 0; }
+  if (tid < CLD_MAX / 64) markbits[tid] = 0;
+  if (tid == 0) { x_cnt[CLD_MAX] = 0; s_called = 0; s_ngeno = 0; }
   __syncthreads ();
   const long i0 = (long) blockIdx.x * per_block, i1 = min (A.n_sites, i0 + per_block);
   for (long i = i0; i < i1; i++) {
@@ -9777,9 +9895,9 @@ void group_sites_large_kernel (const GroupArgs A, long per_block)
       continue;
     }
     #pragma unroll
-    for (int j = 0; j < GRP_PER; j++) {
-      const int s = tid + GRP_THREADS * j;
-      if (GRP_THREADS * j + (tid & ~63) >= ns) break;   // (a whole wavefront)
+    for (int j = 0; j < CLD_PER; j++) {
+      const int s = tid + CLD_THREADS * j;
+      if (CLD_THREADS * j + (tid & ~63) >= ns) break;   // (a whole wavefront)
       int g = -1;
       if (s < ns) {
         g = A.geno[i * ns + s];
@@ -9788,15 +9906,16 @@ void group_sites_large_kernel (const GroupArgs A, long per_block)
       const bool active = g >= 0 && label[j] >= 0;
       const int n = __popcll (__ballot (active));
       if (n && lane == 0) atomicAdd (&s_called, n);
-      group_tally (active, label[j], g, lane, g_cnt, g_min, g_max, x_cnt);
+      const int G = label[j];                           // the two tables of the site, lanes of one (group, genotype) folded (g <= 4096)
+      fold_equal_keys (active, G << 13 | g, lane, [&] (int n) { atomicAdd (&g_cnt[G], n); atomicMin (&g_min[G], g); atomicMax (&g_max[G], g); atomicAdd (&x_cnt[g], n); });
     }
     __syncthreads ();
     const int all_called = s_called;
     u32 marked = 0;                                     // bit j: this thread's j-th group is marked here
     #pragma unroll
-    for (int j = 0; j < GRP_PER; j++) {                 // a thread per group
-      const int G = tid + GRP_THREADS * j;
-      if (GRP_THREADS * j + (tid & ~63) >= n_groups) continue;   // (a whole wavefront)
+    for (int j = 0; j < CLD_PER; j++) {                 // a thread per group
+      const int G = tid + CLD_THREADS * j;
+      if (CLD_THREADS * j + (tid & ~63) >= n_groups) continue;   // (a whole wavefront)
       int nc = 0, fixed = -1, n_outside = 0, mark = 0;
       if (G < n_groups) {
         nc = g_cnt[G];
@@ -9805,9 +9924,9 @@ void group_sites_large_kernel (const GroupArgs A, long per_block)
           fixed = lo == hi ? lo : -2;
           if (fixed >= 0) {
             n_outside = x_cnt[fixed] - nc;
-            mark = nc >= A.min_called && n_outside == 0 && all_called > nc;
+            mark = mark_rule (nc, A.min_called, n_outside, all_called > nc);
           }
-          if (!(EMIT && mark)) { g_cnt[G] = 0; g_min[G] = GRP_NONE; g_max[G] = -1; }   // (a marked group's entry is its record until the list has it)
+          if (!(EMIT && mark)) { g_cnt[G] = 0; g_min[G] = CLD_NONE; g_max[G] = -1; }   // (a marked group's entry is its record until the list has it)
         }
         if (EMIT && A.calls) A.calls[i * n_groups + G] = GroupCall {nc, fixed, n_outside, mark};
       }
@@ -9816,105 +9935,127 @@ void group_sites_large_kernel (const GroupArgs A, long per_block)
       if (!EMIT) gmarks[j] += mark;
       marked |= (u32) mark << j;
     }
-    if (EMIT && A.site_out) {                           // the genotypes that somebody carries
-      int nz = 0;
-      for (int x = tid; x <= na; x += GRP_THREADS) nz += x_cnt[x] != 0;
-      for (int o = 32; o; o >>= 1) nz += __shfl_xor (nz, o);
-      if (nz && lane == 0) atomicAdd (&s_ngeno, nz);
-    }
+    if (EMIT && A.site_out) site_count_genotypes (x_cnt, na, tid, &s_ngeno);
     __syncthreads ();
-    if (tid < 64) {                                     // the site's marks from the words of its groups (those beyond n_groups stay 0)
-      const u64 w = markbits[tid];
-      int n_marks = __popcll (w), first = w ? tid * 64 + __ffsll ((long long) w) - 1 : GRP_NONE;
-      for (int o = 32; o; o >>= 1) { n_marks += __shfl_xor (n_marks, o); first = min (first, __shfl_xor (first, o)); }
-      if (tid == 0) {
-        if (!EMIT) A.cnt[i] = (u32) n_marks;
-        else if (A.site_out) A.site_out[i] = GroupSite {s_called, s_ngeno, n_marks, first == GRP_NONE ? -1 : first};
-        s_called = 0; s_ngeno = 0;
-      }
-    }
+    site_marks_total<EMIT> (A, i, markbits, tid, all_called, s_ngeno, [&] { s_called = 0; s_ngeno = 0; });
     if (EMIT && marked) {
       #pragma unroll 1
-      for (int j = 0; j < GRP_PER; j++) {
+      for (int j = 0; j < CLD_PER; j++) {
         if (!((marked >> j) & 1u)) continue;
-        const int G = tid + GRP_THREADS * j, nc = g_cnt[G], fixed = g_min[G];
-        g_cnt[G] = 0; g_min[G] = GRP_NONE; g_max[G] = -1;
+        const int G = tid + CLD_THREADS * j, nc = g_cnt[G], fixed = g_min[G];
+        g_cnt[G] = 0; g_min[G] = CLD_NONE; g_max[G] = -1;
         if (!A.marks) continue;
-        long pos = (long) A.cnt[i] + __popcll (markbits[G >> 6] & ((1ull << (G & 63)) - 1ull));   // its rank: the marked groups below it
-        #pragma unroll 1
-        for (int w = 0; w < (G >> 6); w++) pos += __popcll (markbits[w]);
+        const long pos = site_mark_place (A, i, markbits, G);
         if (pos < A.cap) A.marks[pos] = GroupMark {(int) i, G, fixed, nc};
       }
     }
-    for (int x = tid; x <= na; x += GRP_THREADS) x_cnt[x] = 0;   // what this site could touch
+    site_clear_genotypes (x_cnt, na, tid);
     __syncthreads ();
   }
-  if (EMIT) return;
-  if (bad) atomicOr (A.flags, bad);
-  #pragma unroll
-  for (int j = 0; j < GRP_PER; j++)
-    if (gmarks[j]) atomicAdd (&A.gm[tid + GRP_THREADS * j], gmarks[j]);
+  if (!EMIT) marks_count_end (A, bad, gmarks, tid);
+}
+
+// The host side of the two entries.  An entry checks its arguments in this order: mark_check_head (), its own checks of its
+// keys, mark_check_tail (); then mark_sites () runs the three steps.  Each check returns 0, or the code of the first rule that is
+// broken with its message set.
+struct MarkCall                                         // the arguments that both entries have, as the caller gave them
+{
+  const char *fn; tjamd_counter *c; const tjamd_site *d_sites; long n_sites; const int16_t *d_genotype; int n_samples, n_keys, min_called;
+  tjamd_group_call *d_calls; tjamd_group_site *d_site_out; int *d_key_marks; tjamd_group_mark *d_marks; long mark_capacity, *h_n_marks;
+};
+struct MarkRefusal { const char *text; int value; };    // the message of an error bit ("%s" the entry, then "%d" the value where it has one)
+
+// per_sample: the entry's array over the samples (d_group, d_order), and its name
+static int mark_check_head (const MarkCall &m, const void *per_sample, const char *per_sample_name)
+{
+  if (!m.c) return set_err (TJAMD_ERR_ARG, "%s: null counter", m.fn);
+  if (m.n_sites < 0) return set_err (TJAMD_ERR_ARG, "%s: n_sites %ld below 0", m.fn, m.n_sites);
+  if (m.n_sites > 0 && (!m.d_sites || !m.d_genotype)) return set_err (TJAMD_ERR_ARG, "%s: null site or genotype buffer", m.fn);
+  if (!per_sample) return set_err (TJAMD_ERR_ARG, "%s: null %s", m.fn, per_sample_name);
+  if (m.n_samples < 1 || m.n_samples > CLD_MAX) return set_err (TJAMD_ERR_ARG, "%s: n_samples %d outside 1..4096", m.fn, m.n_samples);
+  return 0;
+}
+
+// keys: the entry's noun for its keys; what: what the device does, for the message about a missing one
+static int mark_check_tail (const MarkCall &m, const char *keys, const char *what)
+{
+  if (m.min_called < 1) return set_err (TJAMD_ERR_ARG, "%s: min_called %d below 1", m.fn, m.min_called);
+  if (m.mark_capacity < 0) return set_err (TJAMD_ERR_ARG, "%s: mark_capacity %ld below 0", m.fn, m.mark_capacity);
+  if (!m.d_marks && m.mark_capacity > 0) return set_err (TJAMD_ERR_ARG, "%s: null d_marks with a capacity of %ld", m.fn, m.mark_capacity);
+  if (m.n_sites >= (1l << 31) || m.n_sites * (long) m.n_samples >= (1l << 31)) return set_err (TJAMD_ERR_ARG, "%s: %ld sites x %d samples: 2^31 cells or more", m.fn, m.n_sites, m.n_samples);
+  if (m.d_calls && m.n_sites * (long) m.n_keys >= (1l << 31)) return set_err (TJAMD_ERR_ARG, "%s: %ld sites x %d %s: 2^31 calls or more", m.fn, m.n_sites, m.n_keys, keys);
+  if (tjamd_device_count () <= 0) return set_err (TJAMD_ERR_NO_DEVICE, "%s: TJAMD_ERR_NO_DEVICE: no HIP device visible (%s on the device; no CPU fallback)", m.fn, what);
+  return 0;
+}
+
+// The three steps of a checked call.  timer: the entry's stage; small: its wavefront form; refused: the messages of its error
+// bits, the lowest first, ended by a null text; launch (A, emit, grid, per_block): a pass of its form, the first (emit false)
+// or the second.  Returns what the entry returns.
+template <class Launch>
+static long mark_sites (const MarkCall &m, int timer, bool small, const MarkRefusal *refused, Launch launch)
+{
+  tjamd_counter *c = m.c;
+  const char *fn = m.fn;
+  Stage st (c, timer);                                  // (a call that returns no count leaves no timing behind)
+  if (hipSetDevice (c->device) != hipSuccess) return -set_err (TJAMD_ERR_HIP, "hipSetDevice failed");
+  int rc;
+  if (m.n_sites == 0 || m.n_keys == 0) {                // no site or no key: no mark, no kernel
+    if (m.d_key_marks && m.n_keys > 0 && hipMemsetAsync (m.d_key_marks, 0, (size_t) m.n_keys * sizeof (int), c->stream) != hipSuccess) return -set_err (TJAMD_ERR_HIP, "%s: memset failed", fn);
+    rc = read_back (c, fn, nullptr, nullptr, 0);
+    if (rc) return -rc;
+    if (m.h_n_marks) *m.h_n_marks = 0;
+    return 0;
+  }
+  ScratchCut cut;
+  int *flags; u32 *cnt;
+  cut.take (flags, (size_t) 64 + m.n_keys); cut.take (cnt, (size_t) m.n_sites);
+  rc = cut.commit (c);
+  if (!rc) rc = ensure (c->scan_tmp, scan_tmp_words (m.n_sites) * 4 + 64, c->stream);
+  if (rc) return -rc;
+  if (hipMemsetAsync (flags, 0, ((size_t) 64 + m.n_keys) * sizeof (int), c->stream) != hipSuccess) return -set_err (TJAMD_ERR_HIP, "%s: memset failed", fn);
+  const MarkArgs A = {m.n_samples, m.n_keys, m.min_called, (const Site *) m.d_sites, m.n_sites, m.d_genotype, (GroupCall *) m.d_calls, (GroupSite *) m.d_site_out, m.d_key_marks,
+                      (GroupMark *) m.d_marks, m.mark_capacity, flags, flags + 64, cnt};
+  // the first form: wavefronts that take a site each in turn, CLD_WAVE_SITES / 4 or more a wavefront where there are that many; the second: two workgroups a CU, each a run of sites
+  const long blocks = small ? std::max (1l, std::min ((m.n_sites + CLD_WAVE_SITES - 1) / CLD_WAVE_SITES, 8l * c->n_cu)) : std::min (m.n_sites, 2l * c->n_cu);
+  const long per_block = (m.n_sites + blocks - 1) / blocks;
+  const unsigned grid = (unsigned) (small ? blocks : (m.n_sites + per_block - 1) / per_block);
+  st.begin ();
+  launch (A, false, grid, per_block);
+  rc = exclusive_scan (c, cnt, cnt, m.n_sites, (u32 *) flags + 1, (u32 *) c->scan_tmp.p, c->scan_tmp.cap / 4);
+  if (rc) return -rc;
+  launch (A, true, grid, per_block);
+  st.end ();
+  u32 h[2] = {0, 0};
+  rc = read_back (c, fn, flags, h, 2);
+  if (rc) return -rc;
+  for (int bit = 0; refused[bit].text; bit++)
+    if (h[0] >> bit & 1u) return -set_err (TJAMD_ERR_ARG, refused[bit].text, fn, refused[bit].value);
+  if (m.h_n_marks) *m.h_n_marks = (long) h[1];
+  if ((long) h[1] > m.mark_capacity) return -set_err (TJAMD_ERR_CAPACITY, "%s: %u marks, caller capacity %ld", fn, h[1], m.mark_capacity);
+  st.done ();
+  return (long) h[1];
 }
 
 extern "C" long tjamd_group_sites (tjamd_counter *c, const tjamd_site *d_sites, long n_sites, const int16_t *d_genotype, int n_samples, const int *d_group, int n_groups,
                                    int min_called, tjamd_group_call *d_calls, tjamd_group_site *d_site_out, int *d_group_marks, tjamd_group_mark *d_marks, long mark_capacity,
                                    long *h_n_marks)
 {
-  static const char *fn = "tjamd_group_sites";
-  if (!c) return -set_err (TJAMD_ERR_ARG, "%s: null counter", fn);
-  if (n_sites < 0) return -set_err (TJAMD_ERR_ARG, "%s: n_sites %ld below 0", fn, n_sites);
-  if (n_sites > 0 && (!d_sites || !d_genotype)) return -set_err (TJAMD_ERR_ARG, "%s: null site or genotype buffer", fn);
-  if (!d_group) return -set_err (TJAMD_ERR_ARG, "%s: null d_group", fn);
-  if (n_samples < 1 || n_samples > GRP_MAX) return -set_err (TJAMD_ERR_ARG, "%s: n_samples %d outside 1..4096", fn, n_samples);
-  if (n_groups < 1 || n_groups > GRP_MAX) return -set_err (TJAMD_ERR_ARG, "%s: n_groups %d outside 1..4096", fn, n_groups);
-  if (min_called < 1) return -set_err (TJAMD_ERR_ARG, "%s: min_called %d below 1", fn, min_called);
-  if (mark_capacity < 0) return -set_err (TJAMD_ERR_ARG, "%s: mark_capacity %ld below 0", fn, mark_capacity);
-  if (!d_marks && mark_capacity > 0) return -set_err (TJAMD_ERR_ARG, "%s: null d_marks with a capacity of %ld", fn, mark_capacity);
-  if (n_sites >= (1l << 31) || n_sites * (long) n_samples >= (1l << 31)) return -set_err (TJAMD_ERR_ARG, "%s: %ld sites x %d samples: 2^31 cells or more", fn, n_sites, n_samples);
-  if (d_calls && n_sites * (long) n_groups >= (1l << 31)) return -set_err (TJAMD_ERR_ARG, "%s: %ld sites x %d groups: 2^31 calls or more", fn, n_sites, n_groups);
-  if (tjamd_device_count () <= 0) return -set_err (TJAMD_ERR_NO_DEVICE, "%s: TJAMD_ERR_NO_DEVICE: no HIP device visible (the sites are read by group on the device; no CPU fallback)", fn);
-  Stage st (c, T_GROUP_SITES);                          // (a call that returns no count leaves no timing behind)
-  if (hipSetDevice (c->device) != hipSuccess) return -set_err (TJAMD_ERR_HIP, "hipSetDevice failed");
-  int rc;
-  if (n_sites == 0) {                                   // no site: no mark, no kernel
-    if (d_group_marks && hipMemsetAsync (d_group_marks, 0, (size_t) n_groups * sizeof (int), c->stream) != hipSuccess) return -set_err (TJAMD_ERR_HIP, "%s: memset failed", fn);
-    rc = read_back (c, fn, nullptr, nullptr, 0);
-    if (rc) return -rc;
-    if (h_n_marks) *h_n_marks = 0;
-    return 0;
-  }
-  ScratchCut cut;
-  int *flags; u32 *cnt;
-  cut.take (flags, (size_t) 64 + n_groups); cut.take (cnt, (size_t) n_sites);
-  rc = cut.commit (c);
-  if (!rc) rc = ensure (c->scan_tmp, scan_tmp_words (n_sites) * 4 + 64, c->stream);
+  const MarkCall m = {"tjamd_group_sites", c, d_sites, n_sites, d_genotype, n_samples, n_groups, min_called, d_calls, d_site_out, d_group_marks, d_marks, mark_capacity, h_n_marks};
+  int rc = mark_check_head (m, d_group, "d_group");
   if (rc) return -rc;
-  if (hipMemsetAsync (flags, 0, ((size_t) 64 + n_groups) * sizeof (int), c->stream) != hipSuccess) return -set_err (TJAMD_ERR_HIP, "%s: memset failed", fn);
-  const GroupArgs A = {(const Site *) d_sites, n_sites, d_genotype, n_samples, d_group, n_groups, min_called, (GroupCall *) d_calls, (GroupSite *) d_site_out, d_group_marks,
-                       (GroupMark *) d_marks, mark_capacity, flags, flags + 64, cnt};
-  const bool small = n_samples <= GRP_SMALL && c->groups_small;
-  // the first form: wavefronts that take a site each in turn, sixteen or more a wavefront where there are that many; the second: two workgroups a CU, each a run of sites
-  const long blocks = small ? std::max (1l, std::min ((n_sites + 63) / 64, 8l * c->n_cu)) : std::min (n_sites, 2l * c->n_cu);
-  const long per_block = (n_sites + blocks - 1) / blocks;
-  const unsigned grid = (unsigned) (small ? blocks : (n_sites + per_block - 1) / per_block);
-  st.begin ();
-  if (small) hipLaunchKernelGGL (group_sites_small_kernel<false>, dim3 (grid), dim3 (256), 0, c->stream, A);
-  else hipLaunchKernelGGL (group_sites_large_kernel<false>, dim3 (grid), dim3 (GRP_THREADS), 0, c->stream, A, per_block);
-  rc = exclusive_scan (c, cnt, cnt, n_sites, (u32 *) flags + 1, (u32 *) c->scan_tmp.p, c->scan_tmp.cap / 4);
+  if (n_groups < 1 || n_groups > CLD_MAX) return -set_err (TJAMD_ERR_ARG, "%s: n_groups %d outside 1..4096", m.fn, n_groups);
+  rc = mark_check_tail (m, "groups", "the sites are read by group");
   if (rc) return -rc;
-  if (small) hipLaunchKernelGGL (group_sites_small_kernel<true>, dim3 (grid), dim3 (256), 0, c->stream, A);
-  else hipLaunchKernelGGL (group_sites_large_kernel<true>, dim3 (grid), dim3 (GRP_THREADS), 0, c->stream, A, per_block);
-  st.end ();
-  u32 h[2] = {0, 0};
-  rc = read_back (c, fn, flags, h, 2);
-  if (rc) return -rc;
-  if (h[0] & 1u) return -set_err (TJAMD_ERR_ARG, "%s: a label is below -1 or not below n_groups %d", fn, n_groups);
-  if (h[0] & 2u) return -set_err (TJAMD_ERR_ARG, "%s: a site has n_alleles < 1 or above n_samples %d", fn, n_samples);
-  if (h[0] & 4u) return -set_err (TJAMD_ERR_ARG, "%s: a genotype cell is below -1 or above its site's n_alleles", fn);
-  if (h_n_marks) *h_n_marks = (long) h[1];
-  if ((long) h[1] > mark_capacity) return -set_err (TJAMD_ERR_CAPACITY, "%s: %u marks, caller capacity %ld", fn, h[1], mark_capacity);
-  st.done ();
-  return (long) h[1];
+  const bool small = n_samples <= CLD_SMALL && c->groups_small;
+  const MarkRefusal refused[] = {{"%s: a label is below -1 or not below n_groups %d", n_groups}, {"%s: a site has n_alleles < 1 or above n_samples %d", n_samples},
+                                 {"%s: a genotype cell is below -1 or above its site's n_alleles", 0}, {nullptr, 0}};
+  return mark_sites (m, T_GROUP_SITES, small, refused, [&] (const MarkArgs &M, bool emit, unsigned grid, long per_block) {
+    const GroupArgs A = {M, d_group};
+    if (small && !emit) hipLaunchKernelGGL (group_sites_small_kernel<false>, dim3 (grid), dim3 (256), 0, c->stream, A);
+    else if (small) hipLaunchKernelGGL (group_sites_small_kernel<true>, dim3 (grid), dim3 (256), 0, c->stream, A);
+    else if (!emit) hipLaunchKernelGGL (group_sites_large_kernel<false>, dim3 (grid), dim3 (CLD_THREADS), 0, c->stream, A, per_block);
+    else hipLaunchKernelGGL (group_sites_large_kernel<true>, dim3 (grid), dim3 (CLD_THREADS), 0, c->stream, A, per_block);
+  });
 }
 extern "C" double tjamd_last_group_sites_ms (tjamd_counter *c) { return c ? c->timer[T_GROUP_SITES].ms (c->device) : -1.0; }
 
@@ -9946,19 +10087,12 @@ extern "C" double tjamd_last_group_sites_ms (tjamd_counter *c) { return c ? c->t
 struct TreeNode { int left, right, first, size; };
 static_assert (sizeof (TreeNode) == 16 && sizeof (TreeNode) == sizeof (tjamd_tree_node), "tree node layout");
 
-#define CLD_MAX 4096                                    // samples, nodes and, by the rule's bound, alleles of a site
-#define CLD_SMALL 64                                    // samples up to which a wavefront takes a site
-#define CLD_THREADS 1024
-#define CLD_PER (CLD_MAX / CLD_THREADS)                 // leaf positions, and nodes, of a thread of the second form
-#define CLD_FOLD 8                                      // distinct genotypes a wavefront folds before its lanes go alone
-#define CLD_WAVE_SITES 64                               // sites a wavefront of the first form is sized for, where there are that many
-
 __global__ __launch_bounds__ (1024)
 void linkage_tree_kernel (const Link *__restrict__ links, int n_links, int ns, TreeNode *__restrict__ nodes, int *__restrict__ order, int *__restrict__ flags)
 {
   __shared__ int uf[CLD_MAX], cnode[CLD_MAX];           // a sample's label; per root (its component's smallest member) the node that is the component, or -1 - sample
   __shared__ int nl[CLD_MAX], nr[CLD_MAX], nsz[CLD_MAX], nfi[CLD_MAX];   // the nodes; nfi: a link's packed ends on the way up, a node's first position on the way down
-  __shared__ int sums[2][1024];
+  __shared__ int wsum[16];
   __shared__ int s_cycle;
   const int tid = threadIdx.x;
   int bad = 0;
@@ -9990,14 +10124,8 @@ void linkage_tree_kernel (const Link *__restrict__ links, int n_links, int ns, T
     const int v = CLD_PER * tid + j;
     if (v < ns && uf[v] == v) mine += cnode[v] >= 0 ? nsz[cnode[v]] : 1;
   }
-  sums[0][tid] = mine;
-  __syncthreads ();
-  int s = 0;
-  for (int o = 1; o < 1024; o <<= 1, s ^= 1) {
-    sums[s ^ 1][tid] = sums[s][tid] + (tid >= o ? sums[s][tid - o] : 0);
-    __syncthreads ();
-  }
-  int at = sums[s][tid] - mine;
+  int n_leaves;                                         // (ns: every sample is under one root)
+  int at = block_exclusive_scan_1024 (mine, tid, wsum, n_leaves);
   #pragma unroll
   for (int j = 0; j < CLD_PER; j++) {
     const int v = CLD_PER * tid + j;
@@ -10030,10 +10158,8 @@ extern "C" long tjamd_linkage_tree (tjamd_counter *c, const tjamd_link *d_links,
   if (hipSetDevice (c->device) != hipSuccess) return -set_err (TJAMD_ERR_HIP, "hipSetDevice failed");
   ScratchCut cut;
   int *flags;
-  cut.take (flags, 64);
-  int rc = cut.commit (c);
+  int rc = commit_with_flags (cut, c, fn, flags);
   if (rc) return -rc;
-  if (hipMemsetAsync (flags, 0, 256, c->stream) != hipSuccess) return -set_err (TJAMD_ERR_HIP, "%s: memset failed", fn);
   st.begin ();
   hipLaunchKernelGGL (linkage_tree_kernel, dim3 (1), dim3 (1024), 0, c->stream, (const Link *) d_links, (int) n_links, n_samples, (TreeNode *) d_nodes, d_order, flags);
   st.end ();
@@ -10047,14 +10173,7 @@ extern "C" long tjamd_linkage_tree (tjamd_counter *c, const tjamd_link *d_links,
 }
 extern "C" double tjamd_last_linkage_tree_ms (tjamd_counter *c) { return c ? c->timer[T_LINKAGE_TREE].ms (c->device) : -1.0; }
 
-// words of a call: [0] error bits (1 the order, 2 a node, 4 a site's n_alleles, 8 a cell), [1] the number of marks (the scan's
-// total); from word 64 on: the marks of every node
-struct CladeArgs
-{
-  const Site *sites; long n_sites; const int16_t *geno; int ns; const TreeNode *nodes; int n_nodes; const int *order; int min_called;
-  GroupCall *calls; GroupSite *site_out; int *node_marks; GroupMark *marks; long cap;
-  int *flags, *nm; u32 *cnt;                            // cnt: a site's marks (written by the first pass), then their offsets (read by the second)
-};
+struct CladeArgs : MarkArgs { const TreeNode *nodes; const int *order; };   // (the words of a call: at MarkArgs)
 
 template <bool EMIT>
 __global__ __launch_bounds__ (256)
@@ -10062,10 +10181,8 @@ void clade_sites_small_kernel (const CladeArgs A)
 {
   __shared__ int s_node[CLD_MAX];                       // first | size << 8 of every node (both at most 64); 0: no node, or a refused one
   __shared__ int s_seen[4][CLD_SMALL], s_marks[4][CLD_SMALL];
-  if (EMIT && ((volatile const int *) A.flags)[0] != 0) return;
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, ns = A.ns, n_nodes = A.n_nodes;
-  if (EMIT && A.node_marks && blockIdx.x == 0)
-    for (int j = tid; j < n_nodes; j += 256) A.node_marks[j] = A.nm[j];
+  if (EMIT && !marks_emit_begin<256> (A)) return;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, ns = A.ns, n_nodes = A.n_keys;
   int bad = 0, my_marks = 0;
   for (int j = tid; j < n_nodes; j += 256) {
     const TreeNode nd = A.nodes[j];
@@ -10119,7 +10236,7 @@ void clade_sites_small_kernel (const CladeArgs A)
         q.fixed = (change & mask & ~((2ull << p0) - 1ull)) ? -2 : x;
         if (q.fixed >= 0) {
           q.n_outside = nx - q.n_called;
-          q.mark = q.n_called >= A.min_called && q.n_outside == 0 && all_called > q.n_called;
+          q.mark = mark_rule (q.n_called, A.min_called, q.n_outside, all_called > q.n_called);
         }
       }
       if (EMIT && A.calls && j < n_nodes) A.calls[i * n_nodes + j] = q;
@@ -10132,7 +10249,7 @@ void clade_sites_small_kernel (const CladeArgs A)
             if (A.marks && pos < A.cap) A.marks[pos] = GroupMark {(int) i, j, q.fixed, q.n_called};
           }
           else if (base == 0) my_marks++;
-          else atomicAdd (&A.nm[j], 1);
+          else atomicAdd (&A.km[j], 1);
         }
         n_marks += __popcll (mb);
       }
@@ -10143,50 +10260,7 @@ void clade_sites_small_kernel (const CladeArgs A)
     }
     if (A.site_out && lane == 0) A.site_out[i] = GroupSite {all_called, n_genotypes, n_marks, first};
   }
-  if (EMIT) return;
-  if (bad) atomicOr (A.flags, bad);
-  s_marks[wave][lane] = my_marks;
-  __syncthreads ();
-  if (tid < min (n_nodes, 64)) {
-    const int n = s_marks[0][tid] + s_marks[1][tid] + s_marks[2][tid] + s_marks[3][tid];
-    if (n) atomicAdd (&A.nm[tid], n);
-  }
-}
-
-// a wavefront's called samples into the table of the site's genotypes: lanes of one genotype first fold into one lane
-__device__ __forceinline__ void clade_tally (bool active, int g, int lane, int *x_cnt)
-{
-  u64 rem = __ballot (active);
-  #pragma unroll 1
-  for (int it = 0; it < CLD_FOLD && rem; it++) {
-    const int j = __ffsll ((long long) rem) - 1;
-    const u64 m = __ballot (active && g == __builtin_amdgcn_readlane (g, j));
-    if (lane == j) atomicAdd (&x_cnt[g], (int) __popcll (m));
-    rem &= ~m;
-    if ((m >> lane) & 1ull) active = false;
-  }
-  if (active) atomicAdd (&x_cnt[g], 1);
-}
-
-// the sum of `mine` over the threads before this one in a workgroup of 1024, and over all of them; one barrier.  wsum: 16 words
-// that nobody reads or writes between the barrier before the call and the barrier after it
-__device__ __forceinline__ int clade_scan (int mine, int tid, int *wsum, int &total)
-{
-  const int lane = tid & 63, wave = tid >> 6;
-  int incl = mine;
-  #pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const int v = __shfl_up (incl, o);
-    if (lane >= o) incl += v;
-  }
-  if (lane == 63) wsum[wave] = incl;
-  __syncthreads ();
-  const int w = lane & (CLD_THREADS / 64 - 1);          // every sixteen lanes hold the sixteen sums and fold them among themselves
-  int all = wsum[w], before = w < wave ? all : 0;
-  #pragma unroll
-  for (int o = 1; o < CLD_THREADS / 64; o <<= 1) { all += __shfl_xor (all, o); before += __shfl_xor (before, o); }
-  total = all;
-  return before + incl - mine;
+  if (!EMIT) marks_count_end_small (A, bad, s_marks, my_marks, min (n_nodes, 64), tid);
 }
 
 template <bool EMIT>
@@ -10197,10 +10271,8 @@ void clade_sites_large_kernel (const CladeArgs A, long per_block)
   __shared__ u64 markbits[CLD_MAX / 64];
   __shared__ int wsum[2][CLD_THREADS / 64];
   __shared__ int s_ngeno;
-  if (EMIT && ((volatile const int *) A.flags)[0] != 0) return;
-  const int tid = threadIdx.x, lane = tid & 63, ns = A.ns, n_nodes = A.n_nodes;
-  if (EMIT && A.node_marks && blockIdx.x == 0)
-    for (int j = tid; j < n_nodes; j += CLD_THREADS) A.node_marks[j] = A.nm[j];
+  if (EMIT && !marks_emit_begin<CLD_THREADS> (A)) return;
+  const int tid = threadIdx.x, lane = tid & 63, ns = A.ns, n_nodes = A.n_keys;
   int bad = 0, smp[CLD_PER], node[CLD_PER], nmarks[CLD_PER];   // node: first | size << 16; 0: no node, or a refused one
   #pragma unroll
   for (int k = 0; k < CLD_PER; k++) {
@@ -10251,7 +10323,7 @@ void clade_sites_large_kernel (const CladeArgs A, long per_block)
       mine += g[k] >= 0;
     }
     int all_called;
-    int r = clade_scan (mine, tid, wsum[0], all_called);
+    int r = block_exclusive_scan_1024 (mine, tid, wsum[0], all_called);
     #pragma unroll
     for (int k = 0; k < CLD_PER; k++) {
       const int p = CLD_PER * tid + k;
@@ -10267,7 +10339,7 @@ void clade_sites_large_kernel (const CladeArgs A, long per_block)
       #pragma unroll 1
       for (int k = 0; k < CLD_PER; k++) {
         const int gk = (int) ((packed >> (16 * k)) & 0xffffull) - 1;
-        clade_tally (gk >= 0, gk, lane, x_cnt);
+        fold_equal_keys (gk >= 0, gk, lane, [&] (int n) { atomicAdd (&x_cnt[gk], n); });   // the carriers of the site's genotypes
       }
     }
     __syncthreads ();
@@ -10278,7 +10350,7 @@ void clade_sites_large_kernel (const CladeArgs A, long per_block)
       ch |= (u32) (rr >= 1 && rr < all_called && gc[rr] != gc[rr - 1]) << k;
     }
     int all_changes;
-    int kb = clade_scan (__popc (ch), tid, wsum[1], all_changes);
+    int kb = block_exclusive_scan_1024 (__popc (ch), tid, wsum[1], all_changes);
     #pragma unroll
     for (int k = 0; k < CLD_PER; k++) {
       const int rr = CLD_PER * tid + k;
@@ -10300,7 +10372,7 @@ void clade_sites_large_kernel (const CladeArgs A, long per_block)
           fixed = kr[r1 - 1] != kr[r0] ? -2 : x;
           if (fixed >= 0) {
             n_outside = x_cnt[x] - nc;
-            mark = nc >= A.min_called && n_outside == 0 && all_called > nc;
+            mark = mark_rule (nc, A.min_called, n_outside, all_called > nc);
           }
         }
       }
@@ -10310,106 +10382,51 @@ void clade_sites_large_kernel (const CladeArgs A, long per_block)
       if (!EMIT) { nmarks[0] += mark & (k == 0); nmarks[1] += mark & (k == 1); nmarks[2] += mark & (k == 2); nmarks[3] += mark & (k == 3); }
       marked |= (u32) mark << k;
     }
-    if (EMIT && A.site_out) {                           // the genotypes that somebody carries
+    if (EMIT && A.site_out) {                           // site_count_genotypes (), written out: through the helper this kernel takes 65 registers, one more than eight wavefronts a SIMD have
       int nzx = 0;
       for (int x = tid; x <= na; x += CLD_THREADS) nzx += x_cnt[x] != 0;
       for (int o = 32; o; o >>= 1) nzx += __shfl_xor (nzx, o);
       if (nzx && lane == 0) atomicAdd (&s_ngeno, nzx);
     }
     __syncthreads ();
-    if (tid < 64) {                                     // the site's marks from the words of its nodes (those beyond n_nodes stay 0)
-      const u64 w = markbits[tid];
-      int n_marks = __popcll (w), first = w ? tid * 64 + __ffsll ((long long) w) - 1 : GRP_NONE;
-      for (int o = 32; o; o >>= 1) { n_marks += __shfl_xor (n_marks, o); first = min (first, __shfl_xor (first, o)); }
-      if (tid == 0) {
-        if (!EMIT) A.cnt[i] = (u32) n_marks;
-        else if (A.site_out) A.site_out[i] = GroupSite {all_called, s_ngeno, n_marks, first == GRP_NONE ? -1 : first};
-        s_ngeno = 0;
-      }
-    }
+    site_marks_total<EMIT> (A, i, markbits, tid, all_called, s_ngeno, [&] { s_ngeno = 0; });
     if (EMIT && marked && A.marks) {
       #pragma unroll 1
       for (int k = 0; k < CLD_PER; k++) {
         if (!((marked >> k) & 1u)) continue;
         const int j = tid + CLD_THREADS * k, nd = k == 0 ? node[0] : k == 1 ? node[1] : k == 2 ? node[2] : node[3];
         const int r0 = pc[nd & 0xffff], r1 = pc[(nd & 0xffff) + (nd >> 16)];   // (the site's tables stand until the next barrier)
-        long pos = (long) A.cnt[i] + __popcll (markbits[j >> 6] & ((1ull << (j & 63)) - 1ull));   // its rank: the marked nodes below it
-        #pragma unroll 1
-        for (int w = 0; w < (j >> 6); w++) pos += __popcll (markbits[w]);
+        const long pos = site_mark_place (A, i, markbits, j);
         if (pos < A.cap) A.marks[pos] = GroupMark {(int) i, j, gc[r0], r1 - r0};
       }
     }
-    for (int x = tid; x <= na; x += CLD_THREADS) x_cnt[x] = 0;   // what this site could touch
+    site_clear_genotypes (x_cnt, na, tid);
     __syncthreads ();
   }
-  if (EMIT) return;
-  if (bad) atomicOr (A.flags, bad);
-  #pragma unroll
-  for (int k = 0; k < CLD_PER; k++)
-    if (nmarks[k]) atomicAdd (&A.nm[tid + CLD_THREADS * k], nmarks[k]);
+  if (!EMIT) marks_count_end (A, bad, nmarks, tid);
 }
 
 extern "C" long tjamd_clade_sites (tjamd_counter *c, const tjamd_site *d_sites, long n_sites, const int16_t *d_genotype, int n_samples, const tjamd_tree_node *d_nodes, int n_nodes,
                                    const int *d_order, int min_called, tjamd_group_call *d_calls, tjamd_group_site *d_site_out, int *d_node_marks, tjamd_group_mark *d_marks,
                                    long mark_capacity, long *h_n_marks)
 {
-  static const char *fn = "tjamd_clade_sites";
-  if (!c) return -set_err (TJAMD_ERR_ARG, "%s: null counter", fn);
-  if (n_sites < 0) return -set_err (TJAMD_ERR_ARG, "%s: n_sites %ld below 0", fn, n_sites);
-  if (n_sites > 0 && (!d_sites || !d_genotype)) return -set_err (TJAMD_ERR_ARG, "%s: null site or genotype buffer", fn);
-  if (!d_order) return -set_err (TJAMD_ERR_ARG, "%s: null d_order", fn);
-  if (n_samples < 1 || n_samples > CLD_MAX) return -set_err (TJAMD_ERR_ARG, "%s: n_samples %d outside 1..4096", fn, n_samples);
-  if (n_nodes < 0 || n_nodes > CLD_MAX) return -set_err (TJAMD_ERR_ARG, "%s: n_nodes %d outside 0..4096", fn, n_nodes);
-  if (!d_nodes && n_nodes > 0) return -set_err (TJAMD_ERR_ARG, "%s: null d_nodes", fn);
-  if (min_called < 1) return -set_err (TJAMD_ERR_ARG, "%s: min_called %d below 1", fn, min_called);
-  if (mark_capacity < 0) return -set_err (TJAMD_ERR_ARG, "%s: mark_capacity %ld below 0", fn, mark_capacity);
-  if (!d_marks && mark_capacity > 0) return -set_err (TJAMD_ERR_ARG, "%s: null d_marks with a capacity of %ld", fn, mark_capacity);
-  if (n_sites >= (1l << 31) || n_sites * (long) n_samples >= (1l << 31)) return -set_err (TJAMD_ERR_ARG, "%s: %ld sites x %d samples: 2^31 cells or more", fn, n_sites, n_samples);
-  if (d_calls && n_sites * (long) n_nodes >= (1l << 31)) return -set_err (TJAMD_ERR_ARG, "%s: %ld sites x %d nodes: 2^31 calls or more", fn, n_sites, n_nodes);
-  if (tjamd_device_count () <= 0) return -set_err (TJAMD_ERR_NO_DEVICE, "%s: TJAMD_ERR_NO_DEVICE: no HIP device visible (the sites are read by clade on the device; no CPU fallback)", fn);
-  Stage st (c, T_CLADE_SITES);                          // (a call that returns no count leaves no timing behind)
-  if (hipSetDevice (c->device) != hipSuccess) return -set_err (TJAMD_ERR_HIP, "hipSetDevice failed");
-  int rc;
-  if (n_sites == 0 || n_nodes == 0) {                   // no site or no node: no mark, no kernel
-    if (d_node_marks && n_nodes > 0 && hipMemsetAsync (d_node_marks, 0, (size_t) n_nodes * sizeof (int), c->stream) != hipSuccess) return -set_err (TJAMD_ERR_HIP, "%s: memset failed", fn);
-    rc = read_back (c, fn, nullptr, nullptr, 0);
-    if (rc) return -rc;
-    if (h_n_marks) *h_n_marks = 0;
-    return 0;
-  }
-  ScratchCut cut;
-  int *flags; u32 *cnt;
-  cut.take (flags, (size_t) 64 + n_nodes); cut.take (cnt, (size_t) n_sites);
-  rc = cut.commit (c);
-  if (!rc) rc = ensure (c->scan_tmp, scan_tmp_words (n_sites) * 4 + 64, c->stream);
+  const MarkCall m = {"tjamd_clade_sites", c, d_sites, n_sites, d_genotype, n_samples, n_nodes, min_called, d_calls, d_site_out, d_node_marks, d_marks, mark_capacity, h_n_marks};
+  int rc = mark_check_head (m, d_order, "d_order");
   if (rc) return -rc;
-  if (hipMemsetAsync (flags, 0, ((size_t) 64 + n_nodes) * sizeof (int), c->stream) != hipSuccess) return -set_err (TJAMD_ERR_HIP, "%s: memset failed", fn);
-  const CladeArgs A = {(const Site *) d_sites, n_sites, d_genotype, n_samples, (const TreeNode *) d_nodes, n_nodes, d_order, min_called, (GroupCall *) d_calls, (GroupSite *) d_site_out,
-                       d_node_marks, (GroupMark *) d_marks, mark_capacity, flags, flags + 64, cnt};
+  if (n_nodes < 0 || n_nodes > CLD_MAX) return -set_err (TJAMD_ERR_ARG, "%s: n_nodes %d outside 0..4096", m.fn, n_nodes);
+  if (!d_nodes && n_nodes > 0) return -set_err (TJAMD_ERR_ARG, "%s: null d_nodes", m.fn);
+  rc = mark_check_tail (m, "nodes", "the sites are read by clade");
+  if (rc) return -rc;
   const bool small = n_samples <= CLD_SMALL && c->clades_small;
-  // the first form: wavefronts that take a site each in turn, CLD_WAVE_SITES / 4 or more a wavefront where there are that many; the second: two workgroups a CU, each a run of sites
-  const long blocks = small ? std::max (1l, std::min ((n_sites + CLD_WAVE_SITES - 1) / CLD_WAVE_SITES, 8l * c->n_cu)) : std::min (n_sites, 2l * c->n_cu);
-  const long per_block = (n_sites + blocks - 1) / blocks;
-  const unsigned grid = (unsigned) (small ? blocks : (n_sites + per_block - 1) / per_block);
-  st.begin ();
-  if (small) hipLaunchKernelGGL (clade_sites_small_kernel<false>, dim3 (grid), dim3 (256), 0, c->stream, A);
-  else hipLaunchKernelGGL (clade_sites_large_kernel<false>, dim3 (grid), dim3 (CLD_THREADS), 0, c->stream, A, per_block);
-  rc = exclusive_scan (c, cnt, cnt, n_sites, (u32 *) flags + 1, (u32 *) c->scan_tmp.p, c->scan_tmp.cap / 4);
-  if (rc) return -rc;
-  if (small) hipLaunchKernelGGL (clade_sites_small_kernel<true>, dim3 (grid), dim3 (256), 0, c->stream, A);
-  else hipLaunchKernelGGL (clade_sites_large_kernel<true>, dim3 (grid), dim3 (CLD_THREADS), 0, c->stream, A, per_block);
-  st.end ();
-  u32 h[2] = {0, 0};
-  rc = read_back (c, fn, flags, h, 2);
-  if (rc) return -rc;
-  if (h[0] & 1u) return -set_err (TJAMD_ERR_ARG, "%s: d_order is not a permutation of 0 .. n_samples - 1", fn);
-  if (h[0] & 2u) return -set_err (TJAMD_ERR_ARG, "%s: a node has size < 2, first < 0 or first + size above n_samples %d", fn, n_samples);
-  if (h[0] & 4u) return -set_err (TJAMD_ERR_ARG, "%s: a site has n_alleles < 1 or above n_samples %d", fn, n_samples);
-  if (h[0] & 8u) return -set_err (TJAMD_ERR_ARG, "%s: a genotype cell is below -1 or above its site's n_alleles", fn);
-  if (h_n_marks) *h_n_marks = (long) h[1];
-  if ((long) h[1] > mark_capacity) return -set_err (TJAMD_ERR_CAPACITY, "%s: %u marks, caller capacity %ld", fn, h[1], mark_capacity);
-  st.done ();
-  return (long) h[1];
+  const MarkRefusal refused[] = {{"%s: d_order is not a permutation of 0 .. n_samples - 1", 0}, {"%s: a node has size < 2, first < 0 or first + size above n_samples %d", n_samples},
+                                 {"%s: a site has n_alleles < 1 or above n_samples %d", n_samples}, {"%s: a genotype cell is below -1 or above its site's n_alleles", 0}, {nullptr, 0}};
+  return mark_sites (m, T_CLADE_SITES, small, refused, [&] (const MarkArgs &M, bool emit, unsigned grid, long per_block) {
+    const CladeArgs A = {M, (const TreeNode *) d_nodes, d_order};
+    if (small && !emit) hipLaunchKernelGGL (clade_sites_small_kernel<false>, dim3 (grid), dim3 (256), 0, c->stream, A);
+    else if (small) hipLaunchKernelGGL (clade_sites_small_kernel<true>, dim3 (grid), dim3 (256), 0, c->stream, A);
+    else if (!emit) hipLaunchKernelGGL (clade_sites_large_kernel<false>, dim3 (grid), dim3 (CLD_THREADS), 0, c->stream, A, per_block);
+    else hipLaunchKernelGGL (clade_sites_large_kernel<true>, dim3 (grid), dim3 (CLD_THREADS), 0, c->stream, A, per_block);
+  });
 }
 extern "C" double tjamd_last_clade_sites_ms (tjamd_counter *c) { return c ? c->timer[T_CLADE_SITES].ms (c->device) : -1.0; }
 
@@ -10470,7 +10487,7 @@ __global__ __launch_bounds__ (256)
 void aggl_rowmin_kernel (const u64 *__restrict__ keys, int ns, int ld, int linkage, const int *__restrict__ size, LinkRowBest *__restrict__ rowbest,
                          const int *__restrict__ flags)
 {
-  if ((((volatile const int *) flags)[0] | ((volatile const int *) flags)[1]) != 0) return;
+  if (link_rounds_over (flags)) return;
   const int lane = threadIdx.x & 63, a = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (a >= ns) return;                                  // (a whole wavefront)
   const int sa = size[a];
@@ -10486,11 +10503,7 @@ void aggl_rowmin_kernel (const u64 *__restrict__ keys, int ns, int ld, int linka
     if (sb.x != 0 && k.x != LINK_NONE) { const u64 d = aggl_d (k.x, sa, sb.x, linkage); if (d < bk) { bk = d; bb = 2 * p; } }
     if (sb.y != 0 && k.y != LINK_NONE) { const u64 d = aggl_d (k.y, sa, sb.y, linkage); if (d < bk) { bk = d; bb = 2 * p + 1; } }
   }
-  for (int o = 32; o; o >>= 1) {
-    const u64 ok = shfl_xor64 (bk, o);
-    const int ob = __shfl_xor (bb, o);
-    if (ok < bk || (ok == bk && ob < bb)) { bk = ok; bb = ob; }
-  }
+  wave_min_key_b (bk, bb);
   if (lane == 0) rowbest[a] = LinkRowBest {bk, bb, 0};
 }
 
@@ -10499,7 +10512,7 @@ void aggl_pairs_kernel (const LinkRowBest *__restrict__ rowbest, int ns, int *__
 {
   __shared__ int nn[LINK_MAX];                          // a live cluster's nearest neighbour; -1: retired, or no edge
   __shared__ int n_new;
-  if ((((volatile const int *) flags)[0] | ((volatile const int *) flags)[1]) != 0) return;
+  if (link_rounds_over (flags)) return;
   const int tid = threadIdx.x, base = flags[2], round = flags[3];
   u64 key[LINK_MAX / 1024];
   int sv[LINK_MAX / 1024];
@@ -10540,7 +10553,7 @@ void aggl_pairs_kernel (const LinkRowBest *__restrict__ rowbest, int ns, int *__
 __global__ __launch_bounds__ (256)
 void aggl_rows_kernel (u64 *__restrict__ keys, int ld, int linkage, const u32 *__restrict__ pairs, const int *__restrict__ flags)
 {
-  if ((((volatile const int *) flags)[0] | ((volatile const int *) flags)[1]) != 0) return;
+  if (link_rounds_over (flags)) return;
   if ((int) blockIdx.x >= flags[4]) return;
   const u32 pair = pairs[blockIdx.x];
   ulonglong2 *rx = (ulonglong2 *) (keys + (long) (pair >> 12) * ld);
@@ -10554,7 +10567,7 @@ void aggl_rows_kernel (u64 *__restrict__ keys, int ld, int linkage, const u32 *_
 __global__ __launch_bounds__ (256)
 void aggl_cols_kernel (u64 *__restrict__ keys, int ns, int ld, int linkage, const int *__restrict__ size, const u32 *__restrict__ pairs, const int *__restrict__ flags)
 {
-  if ((((volatile const int *) flags)[0] | ((volatile const int *) flags)[1]) != 0) return;
+  if (link_rounds_over (flags)) return;
   const int lane = threadIdx.x & 63, r = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (r >= ns || size[r] == 0) return;                  // (a whole wavefront) a retired row is not read again
   u64 *row = keys + (long) r * ld;
@@ -10577,16 +10590,7 @@ void aggl_sort_kernel (const AgglEdge *__restrict__ edges, int P, Link *__restri
     skey[i] = in ? edges[i].key : LINK_NONE; saux[i] = in ? edges[i].aux : LINK_NONE;
   }
   __syncthreads ();
-  for (int k = 2; k <= P; k <<= 1)
-    for (int j = k >> 1; j > 0; j >>= 1) {
-      for (int t = tid; t < P / 2; t += 1024) {
-        const int i = ((t & ~(j - 1)) << 1) | (t & (j - 1)), l = i | j;
-        const u64 ki = skey[i], kl = skey[l], xi = saux[i], xl = saux[l];
-        const bool above = ki > kl || (ki == kl && xi > xl);
-        if (above == ((i & k) == 0)) { skey[i] = kl; skey[l] = ki; saux[i] = xl; saux[l] = xi; }
-      }
-      __syncthreads ();
-    }
+  lds_bitonic_sort<1024> (skey, saux, P);
   for (int i = tid; i < n; i += 1024) out[i] = Link {(int) (saux[i] >> 12 & 4095u), (int) (saux[i] & 4095u), (long long) skey[i]};
 }
 
@@ -10623,11 +10627,7 @@ void aggl_small_kernel (const SampleDistance *__restrict__ dist, int ns, int met
         const u64 k = keys[a * LINK_SMALL + lane];
         if (k != LINK_NONE) bk = aggl_d (k, sa, sb, linkage);
       }
-      for (int o = 32; o; o >>= 1) {
-        const u64 ok = shfl_xor64 (bk, o);
-        const int ob = __shfl_xor (bb, o);
-        if (ok < bk || (ok == bk && ob < bb)) { bk = ok; bb = ob; }
-      }
+      wave_min_key_b (bk, bb);
       if (lane == 0) { rowkey[a] = bk; nn[a] = bk != LINK_NONE ? bb : -1; }
     }
     if (tid == 0) n_new = 0;
@@ -10653,16 +10653,7 @@ void aggl_small_kernel (const SampleDistance *__restrict__ dist, int ns, int met
     n_links += n;
     __syncthreads ();
   }
-  for (int k = 2; k <= LINK_SMALL; k <<= 1)             // the bitonic network over all 64 places, the empty ones last
-    for (int j = k >> 1; j > 0; j >>= 1) {
-      if (tid < LINK_SMALL / 2) {
-        const int i = ((tid & ~(j - 1)) << 1) | (tid & (j - 1)), l = i | j;
-        const u64 ki = ekey[i], kl = ekey[l], xi = eaux[i], xl = eaux[l];
-        const bool above = ki > kl || (ki == kl && xi > xl);
-        if (above == ((i & k) == 0)) { ekey[i] = kl; ekey[l] = ki; eaux[i] = xl; eaux[l] = xi; }
-      }
-      __syncthreads ();
-    }
+  lds_bitonic_sort<256> (ekey, eaux, LINK_SMALL);       // all 64 places, the empty ones last
   if (tid < n_links) out[tid] = Link {(int) (eaux[tid] >> 12 & 4095u), (int) (eaux[tid] & 4095u), (long long) ekey[tid]};
   if (tid == 0) { flags[1] = 1; flags[2] = n_links; flags[3] = round; }
 }
@@ -10671,34 +10662,27 @@ extern "C" long tjamd_sample_agglomerate (tjamd_counter *c, const tjamd_sample_d
                                           int *h_n_rounds)
 {
   static const char *fn = "tjamd_sample_agglomerate";
-  if (!c) return -set_err (TJAMD_ERR_ARG, "%s: null counter", fn);
-  if (!d_dist) return -set_err (TJAMD_ERR_ARG, "%s: null d_dist", fn);
-  if (!d_links && n_samples > 1) return -set_err (TJAMD_ERR_ARG, "%s: null d_links", fn);
-  if (n_samples < 1 || n_samples > LINK_MAX) return -set_err (TJAMD_ERR_ARG, "%s: n_samples %d outside 1..4096", fn, n_samples);
-  if (metric < TJAMD_LINK_DIFFER || metric > TJAMD_LINK_DIFFER_RATE) return -set_err (TJAMD_ERR_ARG, "%s: metric %d outside 0..2", fn, metric);
-  if (min_both < 1) return -set_err (TJAMD_ERR_ARG, "%s: min_both %d below 1", fn, min_both);
+  int rc = link_check_args (fn, c, d_dist, n_samples, metric, min_both, d_links);
+  if (rc) return -rc;
   if (linkage != TJAMD_AGGL_COMPLETE && linkage != TJAMD_AGGL_AVERAGE) return -set_err (TJAMD_ERR_ARG, "%s: linkage %d outside 1..2", fn, linkage);
   if (tjamd_device_count () <= 0) return -set_err (TJAMD_ERR_NO_DEVICE, "%s: TJAMD_ERR_NO_DEVICE: no HIP device visible (the tree is built on the device; no CPU fallback)", fn);
   Stage st (c, T_SAMPLE_AGGLOMERATE);                   // (a refused call leaves no timing behind)
   if (hipSetDevice (c->device) != hipSuccess) return -set_err (TJAMD_ERR_HIP, "hipSetDevice failed");
-  int rc;
   if (n_samples == 1) {                                 // one sample: no pair, no kernel
     rc = read_back (c, fn, nullptr, nullptr, 0);
     if (rc) return -rc;
     if (h_n_rounds) *h_n_rounds = 0;
     return 0;
   }
-  const int ld = (n_samples + 1) & ~1;                  // a row of the matrix: an even number of cells, 16-byte loads
-  int P = 2;
-  while (P < n_samples - 1) P <<= 1;
+  const LinkShape shape (n_samples);
+  const int ld = shape.ld, P = shape.P;
   const bool small = n_samples <= LINK_SMALL && c->link_small;   // one workgroup, one launch
   ScratchCut cut;
   int *flags, *size, *comp; LinkRowBest *rowbest; AgglEdge *edges; u32 *pairs; u64 *keys;
-  cut.take (flags, 64); cut.take (size, small ? 0 : (size_t) ld + 64); cut.take (comp, small ? 0 : (size_t) ld + 64); cut.take (rowbest, small ? 0 : (size_t) n_samples);
+  cut.take (size, small ? 0 : (size_t) ld + 64); cut.take (comp, small ? 0 : (size_t) ld + 64); cut.take (rowbest, small ? 0 : (size_t) n_samples);
   cut.take (edges, small ? 0 : (size_t) n_samples); cut.take (pairs, small ? 0 : (size_t) n_samples); cut.take (keys, small ? 0 : (size_t) n_samples * ld);
-  rc = cut.commit (c);
+  rc = commit_with_flags (cut, c, fn, flags);
   if (rc) return -rc;
-  if (hipMemsetAsync (flags, 0, 256, c->stream) != hipSuccess) return -set_err (TJAMD_ERR_HIP, "%s: memset failed", fn);
   u32 h_flags[4] = {0, 0, 0, 0};
   st.begin ();
   if (small) {
@@ -10708,8 +10692,7 @@ extern "C" long tjamd_sample_agglomerate (tjamd_counter *c, const tjamd_sample_d
     if (rc) return -rc;
   } else {
     const unsigned row_blocks = (unsigned) ((n_samples + 3) / 4);
-    hipLaunchKernelGGL (linkage_keys_kernel, dim3 ((unsigned) ((ld + LINK_TILE - 1) / LINK_TILE), (unsigned) ((n_samples + LINK_TILE - 1) / LINK_TILE)), dim3 (256), 0, c->stream,
-                        (const SampleDistance *) d_dist, n_samples, ld, metric, min_both, keys, comp, flags);   // (comp: N15's labels, not read here)
+    launch_linkage_keys (c, d_dist, n_samples, ld, metric, min_both, keys, comp, flags);   // (comp: N15's labels, not read here)
     hipLaunchKernelGGL (aggl_init_kernel, dim3 ((unsigned) std::min<long> (((long) n_samples * ld + 255) / 256, 4096)), dim3 (256), 0, c->stream, (const u64 *) keys, n_samples, ld,
                         linkage, size, flags);
     // a round that is not the last merges at least one pair: n_samples - 1 rounds at most.  A look at the flag words per batch.
@@ -10726,8 +10709,8 @@ extern "C" long tjamd_sample_agglomerate (tjamd_counter *c, const tjamd_sample_d
       if (rc) return -rc;
     }
   }
-  if (h_flags[0] & 1u) return -set_err (TJAMD_ERR_ARG, "%s: a cell has n_both < 0, n_differ < 0, n_differ > n_both or length_diff < 0", fn);
-  if (h_flags[0] & 2u) return -set_err (TJAMD_ERR_ARG, "%s: a cell (a, b) differs from the cell (b, a)", fn);
+  if (h_flags[0] & 1u) return -set_err (TJAMD_ERR_ARG, CELL_REFUSED, fn);
+  if (h_flags[0] & 2u) return -set_err (TJAMD_ERR_ARG, MIRROR_REFUSED, fn);
   if (h_flags[0] & 4u) return -set_err (TJAMD_ERR_ARG, "%s: a key of 2^40 or more under TJAMD_AGGL_AVERAGE", fn);
   if (!h_flags[1]) return -set_err (TJAMD_ERR_STATE, "%s: the rounds did not end", fn);
   st.done ();

@@ -174,7 +174,7 @@ def test_all_three_metrics(either_counter, ns):
                 check(dev_agglomerate(either_counter, d, metric, min_both, linkage), restate_sample_agglomerate(d, metric, min_both, linkage), (name, metric, linkage))
 
 
-@pytest.mark.parametrize("ns", [33, 65, 257])
+@pytest.mark.parametrize("ns", [33, 65, 257, 64, 66])
 def test_equal_keys_take_a_round_per_link(either_counter, ns):
     """everyone's nearest neighbour is cluster 0 and one pair merges a round: n_samples - 1 rounds, more than one batch of them"""
     full = np.ones((ns, ns), np.int64)
@@ -310,6 +310,21 @@ def test_device_refusals(either_counter, ns):
         assert L.tjamd_sample_agglomerate(counter._h, *args, None) == -ERR_ARG
     assert not out.any()
     assert L.tjamd_sample_agglomerate(counter._h, _p(dd), 1, DIFFER, 2, AVERAGE, None, None) == 0   # one sample: no link, d_links may be null
+
+
+@pytest.mark.parametrize("ns", [40, 70])
+def test_two_device_refusals_at_once(either_counter, ns):
+    """a cell with n_differ > n_both and, elsewhere, a cell that differs from its mirror: the message of the lower error bit"""
+    d = fabricate_small(ns, np.random.RandomState(ns))
+    d["n_both"] += 1
+    bad = d.copy()
+    bad["n_differ"][5, ns - 10] = bad["n_differ"][ns - 10, 5] = int(d["n_both"][5, ns - 10]) + 1
+    bad["n_both"][ns - 1, 3] += 1
+    for linkage in LINKAGES:
+        rc, err, buf = dev_agglomerate(either_counter, bad, DIFFER, 2, linkage)
+        assert rc == -ERR_ARG and "a cell has n_both < 0, n_differ < 0, n_differ > n_both or length_diff < 0" in err, (linkage, rc, err)
+        assert buf.untouched()
+    check(dev_agglomerate(either_counter, d, DIFFER, 2, AVERAGE), restate_sample_agglomerate(d, DIFFER, 2, AVERAGE))   # the counter serves the next good call
 
 
 def test_the_limit_of_samples(counter):

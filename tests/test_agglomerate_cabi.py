@@ -272,3 +272,26 @@ def test_sample_agglomerate_checks_its_arguments_without_a_gpu():
             assert got == -ERR_NO_DEVICE and err.startswith("tjamd_sample_agglomerate") and "TJAMD_ERR_NO_DEVICE" in err, (kw, got, err)
     assert out.untouched() and rounds.value == -77  # host memory handed in as the outputs stays as it was
     out.check("d_links")
+
+
+def test_sample_agglomerate_reports_the_first_of_two_broken_rules_without_a_gpu():
+    """two rules broken in one call: the message is that of the rule that is checked first, for every pair of neighbours in the
+    order of the checks"""
+    L = tj.lib()
+    fake = C.c_void_p(0x1000)                     # never dereferenced: each call below fails its argument checks first
+    out = GuardedHost(64 * LINK.itemsize)
+    rounds = C.c_int(-77)
+
+    def call(c=fake, dist=fake, ns=5, metric=DIFFER, min_both=1, linkage=COMPLETE, null_out=False):
+        rc = L.tjamd_sample_agglomerate(c, dist, ns, metric, min_both, linkage, None if null_out else out.c, C.byref(rounds))
+        return rc, L.tjamd_last_error().decode()
+
+    for kw, msg in [({"c": None, "dist": None}, "null counter"), ({"dist": None, "null_out": True}, "null d_dist"), ({"dist": None, "ns": 0}, "null d_dist"),
+                    ({"null_out": True, "ns": 4097}, "null d_links"), ({"null_out": True, "metric": 3}, "null d_links"),
+                    ({"ns": 0, "metric": 3}, "n_samples 0 outside 1..4096"), ({"ns": 4097, "min_both": 0}, "n_samples 4097 outside 1..4096"),
+                    ({"metric": -1, "min_both": 0}, "metric -1 outside 0..2"), ({"metric": 3, "linkage": 3}, "metric 3 outside 0..2"),
+                    ({"min_both": 0, "linkage": 3}, "min_both 0 below 1"), ({"min_both": -7, "linkage": 0}, "min_both -7 below 1")]:
+        got, err = call(**kw)
+        assert got == -ERR_ARG and err.startswith("tjamd_sample_agglomerate") and msg in err, (kw, got, err)
+    assert out.untouched() and rounds.value == -77
+    out.check("d_links")

@@ -30,7 +30,7 @@ from tests.test_distances_cabi import restate_sample_distances
 from tests.test_groups import dev_group_sites, sites_of
 from tests.test_groups_cabi import as_tuples
 from tests.test_linkage import dev_linkage
-from tests.test_linkage_cabi import DIFFER, restate_sample_linkage
+from tests.test_linkage_cabi import DIFFER, planted_root_pairs, restate_sample_linkage
 from tests.test_locate import _dev, _p
 from tests.test_sites import dev_merge, pipeline  # noqa: F401  (pipeline: the module-scoped fixture, built here as there)
 from tests.test_sites_cabi import restate_merge_variants
@@ -262,6 +262,14 @@ def test_the_limit_of_samples(counter):
     print(f"[clades] tjamd_clade_sites, 40 sites x {ns} samples x {ns - 1} nodes: {counter.last_clade_sites_ms():.3f} ms, {len(want['marks'])} marks")
 
 
+@pytest.mark.parametrize("ns", [1023, 1024, 1025, 4096])
+def test_trees_with_planted_roots(counter, ns):
+    """the roots' places in the order come from a scan over their sizes, four consecutive samples a thread: threads with no root,
+    one and four, and a wavefront without any (planted_root_pairs of tests/test_linkage_cabi.py)"""
+    links = links_of(planted_root_pairs(ns))
+    check_tree(dev_tree(counter, links, ns), restate_linkage_tree(links, ns))
+
+
 @pytest.mark.parametrize("ns", [7, 130, 1500])
 def test_tree_refusals(counter, ns):
     rng = np.random.RandomState(ns)
@@ -347,6 +355,26 @@ def test_clade_sites_refusals(either_counter, ns):
         assert L.tjamd_clade_sites(counter._h, *args, _p(out), _p(out), _p(out), _p(out), 1, None) == -ERR_ARG
     assert L.tjamd_clade_sites(counter._h, _p(sd), n_sites, _p(gd), ns, _p(nd), nn, _p(od), 1, None, None, None, None, 1, None) == -ERR_ARG   # a capacity without a list
     assert not out.any()
+
+
+@pytest.mark.parametrize("ns", [6, 70])
+def test_two_clade_sites_refusals_at_once(either_counter, ns):
+    """two error bits raised in one call: the message is that of the lowest bit, and nothing is written"""
+    rng = np.random.RandomState(ns)
+    n_sites = 5
+    tree = restate_linkage_tree(tree_links("forest", ns, rng), ns)
+    nodes, order = tree["nodes"], tree["order"]
+    na, gt = random_matrix(rng, n_sites, ns, tree)
+    na[:] = np.maximum(na, 2)
+    bad_order = order.copy(); bad_order[ns - 1] = order[0]
+    bad_nodes = nodes.copy(); bad_nodes[len(nodes) - 1]["first"], bad_nodes[len(nodes) - 1]["size"] = ns - 1, 2
+    bad_cell = gt.copy(); bad_cell[4, ns - 1] = -2
+    for msg, g, nd, od in (("d_order is not a permutation", gt, bad_nodes, bad_order),
+                           ("a node has size < 2, first < 0 or first + size above n_samples", bad_cell, bad_nodes, order)):
+        rc, err, bufs, count = dev_clade_sites(either_counter, na, g, nd, od, 1)
+        assert rc == -ERR_ARG and msg in err, (msg, rc, err)
+        assert all(b.untouched() for b in bufs.values()) and count == -77, msg
+    check(dev_clade_sites(either_counter, na, gt, nodes, order, 1), restate_clade_sites(na, gt, nodes, order, 1))   # the counter serves the next good call
 
 
 @pytest.mark.parametrize("ns", [6, 130])

@@ -565,3 +565,35 @@ def test_clade_sites_checks_its_arguments_without_a_gpu():
     for name, buf in outs.items():
         assert buf.untouched(), name
         buf.check(name)
+
+
+def test_clade_sites_reports_the_first_of_two_broken_rules_without_a_gpu():
+    """two rules broken in one call: the message is that of the rule that is checked first, for every pair of neighbours in the
+    order of the checks (a pair that cannot be broken together takes the next rule)"""
+    L = tj.lib()
+    fake = C.c_void_p(0x1000)                     # never dereferenced: each call below fails its argument checks first
+    outs = {"calls": GuardedHost(64 * 16), "site_out": GuardedHost(64 * 16), "node_marks": GuardedHost(64 * 4), "marks": GuardedHost(64 * 16)}
+    n_marks = C.c_long(-77)
+
+    def call(c=fake, sites=fake, n_sites=4, gt=fake, ns=7, nodes=fake, nn=5, order=fake, min_called=1, cap=64, null=()):
+        o = {k: (None if k in null else v.c) for k, v in outs.items()}
+        rc = L.tjamd_clade_sites(c, sites, n_sites, gt, ns, nodes, nn, order, min_called, o["calls"], o["site_out"], o["node_marks"], o["marks"], cap, C.byref(n_marks))
+        return rc, L.tjamd_last_error().decode()
+
+    cells = {"n_sites": 1 << 20, "ns": 2048}
+    for kw, msg in [({"c": None, "n_sites": -1}, "null counter"), ({"n_sites": -1, "order": None}, "n_sites -1 below 0"), ({"n_sites": -1, "ns": 0}, "n_sites -1 below 0"),
+                    ({"sites": None, "order": None}, "null site or genotype buffer"), ({"gt": None, "ns": 0}, "null site or genotype buffer"),
+                    ({"order": None, "ns": 0}, "null d_order"), ({"order": None, "nodes": None}, "null d_order"),
+                    ({"ns": 0, "nn": -1}, "n_samples 0 outside 1..4096"), ({"ns": 4097, "nodes": None}, "n_samples 4097 outside 1..4096"),
+                    ({"nn": 4097, "nodes": None}, "n_nodes 4097 outside 0..4096"), ({"nn": 4097, "min_called": 0}, "n_nodes 4097 outside 0..4096"),
+                    ({"nodes": None, "min_called": 0}, "null d_nodes"), ({"nodes": None, "cap": -1}, "null d_nodes"),
+                    ({"min_called": 0, "cap": -1}, "min_called 0 below 1"), ({"min_called": 0, "null": ("marks",), "cap": 1}, "min_called 0 below 1"),
+                    ({"cap": -1, **cells}, "mark_capacity -1 below 0"), ({"cap": -1, "null": ("marks",)}, "mark_capacity -1 below 0"),
+                    ({"null": ("marks",), "cap": 1, **cells}, "null d_marks with a capacity of 1"),
+                    ({"n_sites": 1 << 20, "ns": 2048, "nn": 2048}, "1048576 sites x 2048 samples: 2^31 cells or more")]:
+        got, err = call(**kw)
+        assert got == -ERR_ARG and err.startswith("tjamd_clade_sites") and msg in err, (kw, got, err)
+    assert n_marks.value == -77
+    for name, buf in outs.items():
+        assert buf.untouched(), name
+        buf.check(name)

@@ -354,6 +354,25 @@ def test_device_refusals(either_counter, ns):
     assert not out.any()
 
 
+@pytest.mark.parametrize("ns", [6, 70])
+def test_two_device_refusals_at_once(either_counter, ns):
+    """two error bits raised in one call: the message is that of the lowest bit, and nothing is written"""
+    rng = np.random.RandomState(ns)
+    n_sites, n_groups = 5, 3
+    na, gt, group = random_case(rng, n_sites, ns, n_groups, max_alleles=3)
+    na[:] = np.maximum(na, 2)
+    bad_cell = gt.copy(); bad_cell[4, ns - 1] = -2
+    bad_label = group.copy(); bad_label[1] = n_groups
+    bad_alleles = na.copy(); bad_alleles[2] = 0
+    bad_cell[2] = np.minimum(bad_cell[2], 0)                                      # (the cells of that site stay within any n_alleles)
+    for msg, a, l in (("a label is below -1 or not below n_groups", na, bad_label), ("a site has n_alleles < 1 or above n_samples", bad_alleles, group)):
+        rc, err, bufs, count = dev_group_sites(either_counter, a, bad_cell, l, n_groups, 1)
+        assert rc == -ERR_ARG and msg in err, (msg, rc, err)
+        assert all(b.untouched() for b in bufs.values()) and count == -77, msg
+    gt[2] = np.minimum(gt[2], 0)
+    check(dev_group_sites(either_counter, na, gt, group, n_groups, 1), restate_group_sites_table(na, gt, group, n_groups, 1))   # the counter serves the next good call
+
+
 def test_no_site(either_counter):
     got = dev_group_sites(either_counter, np.zeros(0, np.int64), np.zeros((0, 5), np.int16), [0, 1, 1, -1, 2], 3, 1, capacity=4)
     assert got["rc"] == 0 and got["n_marks"] == 0 and got["group_marks"].tolist() == [0, 0, 0]

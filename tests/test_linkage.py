@@ -24,7 +24,7 @@ from tests.test_distances import dev_distances
 from tests.test_distances_cabi import restate_sample_distances
 from tests.test_linkage_cabi import (ANY_LIST_CLUSTERS, DIFFER, DIFFER_RATE, HAND_CLUSTERS, HAND_LINKS, HAND_LINKS_MIN_BOTH_1, HAND_MIN_BOTH, LENGTH, METRICS, NONE,
                                      _links, any_list, as_tuples, components_of_all_pairs, fabricate_small, fabricate_wide, hand_case, link_keys,
-                                     restate_linkage_clusters, restate_sample_linkage, restate_sample_linkage_prim, symmetric)
+                                     planted_root_pairs, restate_linkage_clusters, restate_sample_linkage, restate_sample_linkage_prim, symmetric)
 from tests.test_locate import _dev, _p
 from tests.test_sites import dev_merge, pipeline  # noqa: F401  (pipeline: the module-scoped fixture, built here as there)
 from tests.test_sites_cabi import restate_merge_variants
@@ -183,7 +183,7 @@ def test_sample_counts(either_counter, ns):
             assert restate_linkage_clusters(links, ns, thr).tolist() == components_of_all_pairs(small, DIFFER, 2, thr).tolist()
 
 
-@pytest.mark.parametrize("ns", [70, 33])
+@pytest.mark.parametrize("ns", [70, 33, 64, 65, 66])
 def test_equal_keys_make_the_star(either_counter, ns):
     counter = either_counter
     full = np.ones((ns, ns), np.int64)
@@ -332,6 +332,34 @@ def test_device_refusals_of_the_linkage(either_counter, ns):
         assert L.tjamd_sample_linkage(counter._h, *args) == -ERR_ARG
     assert not out.any()
     assert L.tjamd_sample_linkage(counter._h, _p(dd), 1, DIFFER, 2, None) == 0   # one sample: no link, d_links may be null
+
+
+@pytest.mark.parametrize("ns", [40, 70])
+def test_two_device_refusals_of_the_linkage_at_once(either_counter, ns):
+    """a cell with n_differ > n_both and, elsewhere, a cell that differs from its mirror: the message of the lower error bit"""
+    d = fabricate_small(ns, np.random.RandomState(ns))
+    d["n_both"] += 1
+    bad = d.copy()
+    bad["n_differ"][5, ns - 10] = bad["n_differ"][ns - 10, 5] = int(d["n_both"][5, ns - 10]) + 1
+    bad["n_both"][ns - 1, 3] += 1
+    rc, err, buf = dev_linkage(either_counter, bad, DIFFER, 2)
+    assert rc == -ERR_ARG and "a cell has n_both < 0, n_differ < 0, n_differ > n_both or length_diff < 0" in err, (rc, err)
+    assert buf.untouched()
+    check_links(dev_linkage(either_counter, d, DIFFER, 2), restate_sample_linkage(d, DIFFER, 2))   # the counter serves the next good call
+
+
+@pytest.mark.parametrize("ns", [1023, 1024, 1025, 4096])
+def test_cuts_with_planted_roots(counter, ns):
+    """the dense ids come from a scan over the roots, four consecutive samples a thread: threads with no root, one and four, and a
+    wavefront without any (planted_root_pairs)"""
+    links = _links([(1 + j % 2, a, b) for j, (a, b) in enumerate(planted_root_pairs(ns))])
+    for thr in (2, 1, 0):
+        want = restate_linkage_clusters(links, ns, thr)
+        check_clusters(dev_clusters(counter, links, ns, thr), want)
+    is_root = np.zeros(ns, bool)
+    is_root[np.unique(restate_linkage_clusters(links, ns, 2), return_index=True)[1]] = True   # a component's first sample
+    per_thread = np.add.reduceat(is_root, np.arange(0, ns, 4))
+    assert {0, 1, 4} <= set(per_thread.tolist()) and not is_root[256:512].any()
 
 
 def test_cuts_of_any_list_and_their_refusals(counter):

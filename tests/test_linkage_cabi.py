@@ -138,6 +138,17 @@ def components_of_all_pairs(dist, metric, min_both, threshold):
     return restate_linkage_clusters(_links([(0, int(x), int(y)) for x, y in zip(a, b)]), ns, 0)
 
 
+def planted_root_pairs(ns):
+    """(a, b) pairs for ns >= 1023 whose roots (the smallest members of the components) sit so that four consecutive samples
+    4t .. 4t + 3 hold no root, one root and four roots, and the 256 samples from 256 on no root at all: 0 takes 511, the 256
+    samples 255 .. 510 are one chain, some t have their four samples joined, everyone else is alone"""
+    assert ns >= 1023
+    pairs = [(0, 511)] + [(s, s + 1) for s in range(255, 510)]
+    for t in sorted({1, 5, 130, 200, 254, ns // 4 - 1}):                    # (the last: the last thread that has four samples)
+        pairs += [(4 * t + j, 4 * t + j + 1) for j in range(3)]
+    return pairs
+
+
 def symmetric(ns, n_both, n_differ, length_diff):
     """a DIST matrix from three [ns, ns] arrays whose upper triangles and diagonals are used"""
     d = np.zeros((ns, ns), DIST)
@@ -339,3 +350,24 @@ def test_linkage_clusters_checks_its_arguments_without_a_gpu():
             assert got == -ERR_NO_DEVICE and err.startswith("tjamd_linkage_clusters") and "TJAMD_ERR_NO_DEVICE" in err, (kw, got, err)
     assert out.untouched()
     out.check("d_cluster")
+
+
+def test_sample_linkage_reports_the_first_of_two_broken_rules_without_a_gpu():
+    """two rules broken in one call: the message is that of the rule that is checked first, for every pair of neighbours in the
+    order of the checks"""
+    L = tj.lib()
+    fake = C.c_void_p(0x1000)                     # never dereferenced: each call below fails its argument checks first
+    out = GuardedHost(64 * LINK.itemsize)
+
+    def call(c=fake, dist=fake, ns=5, metric=DIFFER, min_both=1, null_out=False):
+        rc = L.tjamd_sample_linkage(c, dist, ns, metric, min_both, None if null_out else out.c)
+        return rc, L.tjamd_last_error().decode()
+
+    for kw, msg in [({"c": None, "dist": None}, "null counter"), ({"dist": None, "null_out": True}, "null d_dist"), ({"dist": None, "ns": 0}, "null d_dist"),
+                    ({"null_out": True, "ns": 4097}, "null d_links"), ({"null_out": True, "metric": 3}, "null d_links"),
+                    ({"ns": 0, "metric": 3}, "n_samples 0 outside 1..4096"), ({"ns": 4097, "min_both": 0}, "n_samples 4097 outside 1..4096"),
+                    ({"metric": -1, "min_both": 0}, "metric -1 outside 0..2"), ({"metric": 3, "min_both": -7}, "metric 3 outside 0..2")]:
+        got, err = call(**kw)
+        assert got == -ERR_ARG and err.startswith("tjamd_sample_linkage") and msg in err, (kw, got, err)
+    assert out.untouched()
+    out.check("d_links")
