@@ -29,6 +29,11 @@
  *   DIR/clade_sites.tsv       with -N: the sites at which every called sample of a node's clade carries one genotype that no called sample
  *                             outside it carries, one line per (site, node) in that order: node  contig  POS  REF  the genotype's text
  *                             (REF again for genotype 0)  the clade's called samples
+ *   DIR/clade_support.tsv     with -B R[:seed] (only together with -C T -N): the bootstrap over sites.  tjamd_bootstrap_weights draws R rows of site
+ *                             weights (seed 1 unless given), tjamd_sample_distances_weighted gives the R matrices in one call, every replicate's
+ *                             tree is built as the tree above was (the linkage -L chose, tjamd_linkage_tree), and tjamd_clade_support counts the
+ *                             replicates that hold each clade; one line per node of the tree: node  size  the name of its smallest sample  the
+ *                             key of its link  the sites that support it (the label in sample_tree.nwk)  the replicates that hold it  R
  *   DIR/unique_variants.vcf   with -u: the tutorial's concatenation, one row per distinct allele in N8's own form (the record
  *                             d_unique holds), one column all_samples
  *   DIR/variant_effects.tsv   with -e annotation.gff3: tjamd_variant_effects on d_unique only, one line per allele: variant_effects.c's
@@ -36,12 +41,11 @@
  * The other options are sample_vcfs.c's.
  *
  *   gcc -O2 -I include examples/merged_vcf.c -L tatajuba_amd -ltatajuba_amd -Wl,-rpath,$PWD/tatajuba_amd -o merged_vcf
- *   ./merged_vcf -r reference.fa [-u] [-D] [-M] [-C T [-G] [-N] [-L single|complete|average]] [-e annotation.gff3] [-x 1] [-g G] [-s 3] [-k 10] [-m 3] [-c 5] [-d 1] [-l -1] [-o .] sample1.fastq[.gz] ...   */
+ *   ./merged_vcf -r reference.fa [-u] [-D] [-M] [-C T [-G] [-N [-B R[:seed]]] [-L single|complete|average]] [-e annotation.gff3] [-x 1] [-g G] [-s 3] [-k 10] [-m 3] [-c 5] [-d 1] [-l -1] [-o .] sample1.fastq[.gz] ...   */
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
-#include <tatajuba_agglomerate.h>
-#include <tatajuba_clades.h>
+#include <tatajuba_bootstrap.h>
 #include <tatajuba_effects.h>
 #include <tatajuba_locate.h>
 
@@ -120,6 +124,8 @@ main (int argc, char **argv)
   tjamd_tree_node *h_nodes = NULL;
   int *h_order = NULL, *h_node_marks = NULL;
   long n_clade_marks = 0;
+  int n_boot = 0, *h_support = NULL;                      /* -B: the replicates, and per node of the tree those that hold its clade */
+  unsigned long long boot_seed = 1;
   int n = 0, k = 10, m = 3, cov = 5, maxd = 1, lev = -1, mism = 1, max_edits = -1, max_shift = TJAMD_MAX_SHIFT, coverage[MAX_SAMPLES], a, ndev = tjamd_device_count (), status;
   const void *d_records = NULL;
   void *d_keys, *d_counts, *d_ids, *d_grouped, *d_loc, *d_perm, *d_pkeys, *d_pcounts, *d_tracts, *d_tloc, *d_reflen, *d_summary, *d_var, *d_variants, *d_sites, *d_alleles, *d_genotype, *d_unique,
@@ -155,6 +161,12 @@ main (int argc, char **argv)
     else if (!strcmp (argv[a], "-C") && a + 1 < argc) { cut = atoll (argv[++a]); with_clusters = with_distances = 1; }
     else if (!strcmp (argv[a], "-G")) with_groups = 1;
     else if (!strcmp (argv[a], "-N")) with_clades = 1;
+    else if (!strcmp (argv[a], "-B") && a + 1 < argc) {   /* R or R:seed */
+      const char *colon = strchr (argv[++a], ':');
+      n_boot = atoi (argv[a]);
+      if (colon) boot_seed = strtoull (colon + 1, NULL, 10);
+      if (n_boot < 1 || n_boot > 4096) n_boot = -1;
+    }
     else if (!strcmp (argv[a], "-L") && a + 1 < argc) {   /* which tree: 0 single linkage (tjamd_sample_linkage), else TJAMD_AGGL_* */
       a++; with_linkage = 1;
       if (!strcmp (argv[a], "single")) linkage = 0;
@@ -164,7 +176,7 @@ main (int argc, char **argv)
     }
     else if (n < MAX_SAMPLES) files[n++] = argv[a];
   }
-  if (n < 1 || !reference || ((with_groups || with_clades || with_linkage) && !with_clusters) || linkage < 0) { fprintf (stderr, "usage: %s -r reference.fa [-u] [-D] [-M] [-C T [-G] [-N] [-L single|complete|average]] [-e annotation.gff3] [-x X] [-g G] [-s S] [-k K] [-m M] [-c C] [-d D] [-l L] [-o DIR] sample.fastq[.gz] ...\n", argv[0]); return 2; }
+  if (n < 1 || !reference || ((with_groups || with_clades || with_linkage) && !with_clusters) || linkage < 0 || n_boot < 0 || (n_boot && !with_clades)) { fprintf (stderr, "usage: %s -r reference.fa [-u] [-D] [-M] [-C T [-G] [-N [-B R[:seed]]] [-L single|complete|average]] [-e annotation.gff3] [-x X] [-g G] [-s S] [-k K] [-m M] [-c C] [-d D] [-l L] [-o DIR] sample.fastq[.gz] ...\n", argv[0]); return 2; }
   if (ndev < 1) { fprintf (stderr, "tatajuba_amd error: no HIP device is visible (there is no CPU fallback)\n"); return 1; }
   if (maxd < 0) maxd = 0;                                 /* src/main.c:190-192 */
   if (maxd > k / 2) maxd = k / 2;
@@ -319,6 +331,34 @@ main (int argc, char **argv)
             tjamd_device_download (ctr[0], h_order, d_order, (size_t) n * sizeof (int)) ||
             tjamd_device_download (ctr[0], h_node_marks, d_node_marks, (size_t) n_links * sizeof (int)) ||
             tjamd_device_download (ctr[0], h_clade_marks, d_marks, (size_t) n_clade_marks * sizeof (tjamd_group_mark))) return fail ("download");
+        if (n_boot) {                                     /* how many of R trees over resampled sites hold each clade of this one */
+          const size_t R = (size_t) n_boot;
+          void *d_weights = tjamd_device_alloc (ctr[0], R * (size_t) (n_sites ? n_sites : 1) * sizeof (int)),
+               *d_rep_dist = tjamd_device_alloc (ctr[0], R * (size_t) n * (size_t) n * sizeof (tjamd_sample_distance)),
+               *d_rep_links = tjamd_device_alloc (ctr[0], (size_t) n * sizeof (tjamd_link)),
+               *d_rep_nodes = tjamd_device_alloc (ctr[0], R * (size_t) n * sizeof (tjamd_tree_node)), *d_rep_order = tjamd_device_alloc (ctr[0], R * (size_t) n * sizeof (int)),
+               *d_support = tjamd_device_alloc (ctr[0], (size_t) n * sizeof (int));
+          int *rep_n_nodes = (int *) malloc (R * sizeof (int)), r;
+          h_support = (int *) calloc ((size_t) n, sizeof (int));
+          if (n_sites > 0 && tjamd_bootstrap_weights (ctr[0], n_sites, n_boot, boot_seed, (int *) d_weights) < 0) return fail ("bootstrap weights");
+          if (tjamd_sample_distances_weighted (ctr[0], (const tjamd_site *) d_sites, n_sites, (const tjamd_allele *) d_alleles, n_alleles, (const int16_t *) d_genotype, n,
+                                               (tjamd_sample_distance *) d_rep_dist, (const int *) d_weights, n_boot) < 0) return fail ("weighted sample distances");
+          for (r = 0; r < n_boot; r++) {                  /* a replicate's tree, built as the tree was */
+            const tjamd_sample_distance *d_one = (const tjamd_sample_distance *) d_rep_dist + (size_t) r * (size_t) n * (size_t) n;
+            long nl = linkage ? tjamd_sample_agglomerate (ctr[0], d_one, n, TJAMD_LINK_DIFFER, 1, linkage, (tjamd_link *) d_rep_links, NULL)
+                              : tjamd_sample_linkage (ctr[0], d_one, n, TJAMD_LINK_DIFFER, 1, (tjamd_link *) d_rep_links);
+            if (nl < 0) return fail ("replicate linkage");
+            if (tjamd_linkage_tree (ctr[0], (const tjamd_link *) d_rep_links, nl, n, (tjamd_tree_node *) d_rep_nodes + (size_t) r * (size_t) (n - 1),
+                                    (int *) d_rep_order + (size_t) r * (size_t) n) < 0) return fail ("replicate tree");
+            rep_n_nodes[r] = (int) nl;
+          }
+          if (tjamd_clade_support (ctr[0], (const tjamd_tree_node *) d_nodes, (int) n_links, (const int *) d_order, n, (const tjamd_tree_node *) d_rep_nodes,
+                                   (const int *) d_rep_order, rep_n_nodes, n_boot, (int *) d_support) < 0) return fail ("clade support");
+          if (tjamd_device_download (ctr[0], h_support, d_support, (size_t) n_links * sizeof (int))) return fail ("download");
+          tjamd_device_free (ctr[0], d_weights); tjamd_device_free (ctr[0], d_rep_dist); tjamd_device_free (ctr[0], d_rep_links); tjamd_device_free (ctr[0], d_rep_nodes);
+          tjamd_device_free (ctr[0], d_rep_order); tjamd_device_free (ctr[0], d_support);
+          free (rep_n_nodes);
+        }
         tjamd_device_free (ctr[0], d_nodes); tjamd_device_free (ctr[0], d_order); tjamd_device_free (ctr[0], d_node_marks); tjamd_device_free (ctr[0], d_marks);
       }
       tjamd_device_free (ctr[0], d_links); tjamd_device_free (ctr[0], d_cluster);
@@ -434,6 +474,14 @@ main (int argc, char **argv)
     }
     fclose (fout);
     printf ("%ld marks of %ld nodes in %ld trees\n", n_clade_marks, n_links, n_roots);
+    if (n_boot) {
+      if (!(fout = open_output (outdir, "clade_support.tsv"))) return 1;
+      for (i = 0; i < n_links; i++)
+        fprintf (fout, "%ld\t%d\t%s\t%lld\t%d\t%d\t%d\n", i, h_nodes[i].size, sample_name[h_order[h_nodes[i].first]], h_links[i].key, h_node_marks[i], h_support[i], n_boot);
+      fclose (fout);
+      printf ("%d bootstrap replicates from seed %llu\n", n_boot, boot_seed);
+      free (h_support);
+    }
     free (h_nodes); free (h_order); free (h_node_marks); free (h_clade_marks);
   }
   if (with_clusters) { free (h_links); free (h_cluster); }

@@ -15,4 +15,5 @@ from .capi import (Counter, Comm, Reference, Annotation, REF_ENTRY_DTYPE, LOCATI
                    LINK_DTYPE, LINK_DIFFER, LINK_LENGTH, LINK_DIFFER_RATE, LINKAGE_EXPORTS,
                    AGGL_COMPLETE, AGGL_AVERAGE, AGGLOMERATE_EXPORTS,
                    GROUP_CALL_DTYPE, GROUP_SITE_DTYPE, GROUP_MARK_DTYPE, GROUP_EXPORTS,
-                   TREE_NODE_DTYPE, CLADE_EXPORTS)
+                   TREE_NODE_DTYPE, CLADE_EXPORTS,
+                   BOOTSTRAP_EXPORTS)

@@ -184,6 +184,9 @@ AGGL_COMPLETE, AGGL_AVERAGE = 1, 2                                        # TJAM
 GROUP_EXPORTS = ["tjamd_group_sites", "tjamd_last_group_sites_ms"]
 # ... and include/tatajuba_clades.h
 CLADE_EXPORTS = ["tjamd_linkage_tree", "tjamd_clade_sites", "tjamd_last_linkage_tree_ms", "tjamd_last_clade_sites_ms"]
+# ... and include/tatajuba_bootstrap.h
+BOOTSTRAP_EXPORTS = ["tjamd_bootstrap_weights", "tjamd_sample_distances_weighted", "tjamd_clade_support",
+                     "tjamd_last_bootstrap_weights_ms", "tjamd_last_sample_distances_weighted_ms", "tjamd_last_clade_support_ms"]
 MAX_SHIFT = 3                     # TJAMD_MAX_SHIFT
 
 
@@ -367,6 +370,15 @@ def lib():
                                     C.c_long, C.POINTER(C.c_long)]
     L.tjamd_last_linkage_tree_ms.restype = C.c_double; L.tjamd_last_linkage_tree_ms.argtypes = [C.c_void_p]
     L.tjamd_last_clade_sites_ms.restype = C.c_double; L.tjamd_last_clade_sites_ms.argtypes = [C.c_void_p]
+    L.tjamd_bootstrap_weights.restype = C.c_long
+    L.tjamd_bootstrap_weights.argtypes = [C.c_void_p, C.c_long, C.c_int, C.c_ulonglong, C.c_void_p]
+    L.tjamd_sample_distances_weighted.restype = C.c_long
+    L.tjamd_sample_distances_weighted.argtypes = [C.c_void_p, C.c_void_p, C.c_long, C.c_void_p, C.c_long, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int]
+    L.tjamd_clade_support.restype = C.c_long
+    L.tjamd_clade_support.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(C.c_int), C.c_int, C.c_void_p]
+    L.tjamd_last_bootstrap_weights_ms.restype = C.c_double; L.tjamd_last_bootstrap_weights_ms.argtypes = [C.c_void_p]
+    L.tjamd_last_sample_distances_weighted_ms.restype = C.c_double; L.tjamd_last_sample_distances_weighted_ms.argtypes = [C.c_void_p]
+    L.tjamd_last_clade_support_ms.restype = C.c_double; L.tjamd_last_clade_support_ms.argtypes = [C.c_void_p]
     L.tjamd_group_contexts.restype = C.c_long
     L.tjamd_group_contexts.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_long]
     L.new_genomic_context_list.restype = C.POINTER(GenomicContextListStruct); L.new_genomic_context_list.argtypes = [P]
@@ -1042,6 +1054,33 @@ class Counter:
 
     def last_clade_sites_ms(self):
         return lib().tjamd_last_clade_sites_ms(self._h)
+
+    def bootstrap_weights(self, n_sites, n_replicates, seed, d_weights):
+        """tjamd_bootstrap_weights on a device pointer: n_replicates rows of n_sites int32 weights at d_weights, each the counts of
+        n_sites draws with replacement under the rule of include/tatajuba_bootstrap.h.  -> n_replicates"""
+        return self._chkn(lib().tjamd_bootstrap_weights(self._h, n_sites, n_replicates, seed & 0xFFFFFFFFFFFFFFFF, d_weights))
+
+    def sample_distances_weighted(self, d_sites, n_sites, d_alleles, n_alleles, d_genotype, n_samples, d_out, d_weights, n_replicates):
+        """tjamd_sample_distances_weighted on device pointers: the inputs of sample_distances and int32 weights
+        [replicate][site] -> one [sample][sample] matrix of SAMPLE_DISTANCE_DTYPE per replicate at d_out.  -> n_sites"""
+        return self._chkn(lib().tjamd_sample_distances_weighted(self._h, d_sites, n_sites, d_alleles, n_alleles, d_genotype, n_samples, d_out, d_weights, n_replicates))
+
+    def clade_support(self, d_nodes, n_nodes, d_order, n_samples, d_rep_nodes, d_rep_order, rep_n_nodes, d_support):
+        """tjamd_clade_support on device pointers: the tree (TREE_NODE_DTYPE at d_nodes over the leaf order at d_order) and, per
+        replicate r, rep_n_nodes[r] nodes at d_rep_nodes[r * (n_samples - 1)] over the order at d_rep_order[r * n_samples]
+        (rep_n_nodes: a host sequence, one count per replicate) -> int32 at d_support, per node the replicates that hold its
+        clade.  -> n_nodes"""
+        counts = (C.c_int * len(rep_n_nodes))(*[int(x) for x in rep_n_nodes])
+        return self._chkn(lib().tjamd_clade_support(self._h, d_nodes, n_nodes, d_order, n_samples, d_rep_nodes, d_rep_order, counts, len(rep_n_nodes), d_support))
+
+    def last_bootstrap_weights_ms(self):
+        return lib().tjamd_last_bootstrap_weights_ms(self._h)
+
+    def last_sample_distances_weighted_ms(self):
+        return lib().tjamd_last_sample_distances_weighted_ms(self._h)
+
+    def last_clade_support_ms(self):
+        return lib().tjamd_last_clade_support_ms(self._h)
 
     def uses_log(self):
         lib().tjamd_counter_uses_log.restype = C.c_int

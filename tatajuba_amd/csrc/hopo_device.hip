@@ -48,6 +48,7 @@
 #include "../../include/tatajuba_agglomerate.h"
 #include "../../include/tatajuba_groups.h"
 #include "../../include/tatajuba_clades.h"
+#include "../../include/tatajuba_bootstrap.h"
 #include "../../include/tatajuba_locate.h"
 
 typedef unsigned long long u64;
@@ -3994,7 +3995,7 @@ struct StageTimer
 };
 // the intervals of a counter: the last scan call (its partition kernels between the pieces included: tjamd_last_scan_ms takes
 // them out), finalise, the kernels of tjamd_merge_samples, tjamd_tract_stats, tjamd_union_tracts, tjamd_union_tract_stats
-enum { T_SCAN, T_FIN, T_MERGE, T_TRACT, T_UNION, T_UNION_STATS, T_REF, T_LOCATE, T_LOCATED_TRACTS, T_VARIANTS, T_ANNOTATION, T_TRACT_FEATURES, T_SEED_ORDER, T_LOCATE_GAPPED, T_CODING, T_VARIANT_EFFECTS, T_MERGE_VARIANTS, T_SITE_DEPTHS, T_SAMPLE_DISTANCES, T_SAMPLE_LINKAGE, T_LINKAGE_CLUSTERS, T_GROUP_SITES, T_LINKAGE_TREE, T_CLADE_SITES, T_SAMPLE_AGGLOMERATE, TJ_N_TIMERS };   // (T_REF to T_LOCATED_TRACTS: N7, T_VARIANTS: N8, the next two: N9; then two of N10; two of N11; then N12, N13, N14, the two of N15, N16, the two of N17 and N18, end of the file)
+enum { T_SCAN, T_FIN, T_MERGE, T_TRACT, T_UNION, T_UNION_STATS, T_REF, T_LOCATE, T_LOCATED_TRACTS, T_VARIANTS, T_ANNOTATION, T_TRACT_FEATURES, T_SEED_ORDER, T_LOCATE_GAPPED, T_CODING, T_VARIANT_EFFECTS, T_MERGE_VARIANTS, T_SITE_DEPTHS, T_SAMPLE_DISTANCES, T_SAMPLE_LINKAGE, T_LINKAGE_CLUSTERS, T_GROUP_SITES, T_LINKAGE_TREE, T_CLADE_SITES, T_SAMPLE_AGGLOMERATE, T_BOOTSTRAP_WEIGHTS, T_SAMPLE_DISTANCES_WEIGHTED, T_CLADE_SUPPORT, TJ_N_TIMERS };   // (T_REF to T_LOCATED_TRACTS: N7, T_VARIANTS: N8, the next two: N9; then two of N10; two of N11; then N12, N13, N14, the two of N15, N16, the two of N17, N18 and the three of N19, end of the file)
 
 // A finalise between its two halves: finalise_queue fills this in, finalise_collect reads it and sets the state back to
 // FIN_IDLE (nothing begun).  FIN_EVENT: begun, ev_done says when the counts have arrived; FIN_ARRIVED: begun, the stream has
@@ -4060,7 +4061,7 @@ struct tjamd_counter
   unsigned scan_seq = 0;
   size_t piece_target = TJ_SCAN_PIECE_TARGET;           // TATAJUBA_AMD_SCAN_PIECE (bytes) overrides it: tests
   int scan_grid_cap = 0;                                // TATAJUBA_AMD_SCAN_GRID (tests): n >= 1 caps the workgroups of the scan and log-partition launches; 0: no cap
-  int dist_blocks = 0;                                  // TATAJUBA_AMD_DISTANCE_BLOCKS (tests): the workgroups tjamd_sample_distances splits its sites for; 0: four per CU
+  int dist_blocks = 0;                                  // TATAJUBA_AMD_DISTANCE_BLOCKS (tests): the workgroups tjamd_sample_distances and tjamd_sample_distances_weighted split their sites for; 0: four per CU
   int link_small = 1;                                   // TATAJUBA_AMD_LINKAGE_SMALL (tests): 0: tjamd_sample_linkage never takes its single-workgroup path (64 samples and fewer)
   int aggl_batch = 32;                                  // TATAJUBA_AMD_AGGL_BATCH (tools, tests): the rounds tjamd_sample_agglomerate enqueues between two looks at its flag words; AGGL_BATCH
   int groups_small = 1;                                 // TATAJUBA_AMD_GROUPS_SMALL (tests): 0: tjamd_group_sites never takes its wavefront-per-site form (64 samples and fewer)
@@ -8957,6 +8958,80 @@ __device__ __forceinline__ void sdist_tile_pair (int p, int n_tiles, int &ti, in
   tj = ti + p;
 }
 
+// Staging of one chunk (the CH = SDIST_CELLS / E sites from c0) of the two sample tiles into gA, lA, gB, lB, SDIST_CELLS / 256 cells
+// of either tile a thread: a row of E samples is E consecutive int16 of the matrix and E consecutive lengths of the check pass.
+// Every load is issued before anything waits for one.  A missing cell is staged as -1 in one tile and -2 in the other, so that
+// two equal words are two calls of one allele; its length is 0.  A length beyond an allele's 1023 raises *l_max, the chunk's largest.
+template <int E>
+__device__ __forceinline__ void sdist_stage (const int16_t *__restrict__ gt, const int *__restrict__ lens, int ns, int a0, int b0, long c0, long s_end, int tid,
+                                             int *gA, int *lA, int *gB, int *lB, int *l_max)
+{
+  int g_st[2][SDIST_CELLS / 256], len_st[2][SDIST_CELLS / 256];
+  #pragma unroll
+  for (int j = 0; j < SDIST_CELLS / 256; j++) {
+    const int x = tid + 256 * j;
+    const long site = c0 + x / E;
+    #pragma unroll
+    for (int h = 0; h < 2; h++) {
+      const int sample = (h ? b0 : a0) + x % E;
+      const bool in = site < s_end && sample < ns;
+      g_st[h][j] = in ? (int) gt[site * ns + sample] : -1;
+      len_st[h][j] = in ? lens[site * ns + sample] : 0;
+    }
+  }
+  #pragma unroll
+  for (int j = 0; j < SDIST_CELLS / 256; j++)
+    #pragma unroll
+    for (int h = 0; h < 2; h++) {
+      const int x = tid + 256 * j, g = g_st[h][j], len = len_st[h][j];
+      if (len > 1023) atomicMax (l_max, len);
+      (h ? gB : gA)[x] = g < 0 ? -1 - h : g;
+      (h ? lB : lA)[x] = len;
+    }
+}
+
+// A workgroup's tile of sums, behind its last chunk, to its place: `mine` where the sites are split (the whole tile goes to this
+// workgroup's place in scratch), otherwise the matrix.  With one thread group (Z == 1) a thread stores its 4 x 4 pairs; with
+// several their sums meet in the staging area first (the site loop's last barrier is behind every read of it).
+template <int E>
+__device__ __forceinline__ void sdist_store_tile (const int (&nb)[4][4], const int (&same)[4][4], const u64 (&ld)[4][4], int *lds, SampleDistance *__restrict__ mine,
+                                                  SampleDistance *__restrict__ out, int ns, int a0, int b0, bool mirror, int tid)
+{
+  constexpr int T = E / 4, Z = 256 / (T * T);
+  const int tx = tid % T, ty = (tid / T) % T;
+  if constexpr (Z == 1) {
+    #pragma unroll
+    for (int r = 0; r < 4; r++)
+      #pragma unroll
+      for (int q = 0; q < 4; q++) {
+        const SampleDistance o = {nb[r][q], nb[r][q] - same[r][q], (long long) ld[r][q]};
+        if (mine) mine[(4 * ty + r) * E + 4 * tx + q] = o;
+        else sdist_emit (out, ns, a0 + 4 * ty + r, b0 + 4 * tx + q, mirror, o);
+      }
+  }
+  else {
+    int *const acc_nb = lds, *const acc_nd = lds + E * E;
+    u64 *const acc_ld = (u64 *) (lds + 2 * E * E);
+    for (int x = tid; x < E * E; x += 256) { acc_nb[x] = 0; acc_nd[x] = 0; acc_ld[x] = 0ull; }
+    __syncthreads ();
+    #pragma unroll
+    for (int r = 0; r < 4; r++)
+      #pragma unroll
+      for (int q = 0; q < 4; q++) {
+        const int x = (4 * ty + r) * E + 4 * tx + q;
+        if (nb[r][q]) atomicAdd (acc_nb + x, nb[r][q]);
+        if (nb[r][q] - same[r][q]) atomicAdd (acc_nd + x, nb[r][q] - same[r][q]);
+        if (ld[r][q]) atomicAdd (acc_ld + x, ld[r][q]);
+      }
+    __syncthreads ();
+    for (int x = tid; x < E * E; x += 256) {
+      const SampleDistance o = {acc_nb[x], acc_nd[x], (long long) acc_ld[x]};
+      if (mine) mine[x] = o;
+      else sdist_emit (out, ns, a0 + x / E, b0 + x % E, mirror, o);
+    }
+  }
+}
+
 template <int E>                                        // the tile's edge in samples: 8, 16, 32 or 64
 __global__ __launch_bounds__ (256)
 void sample_distances_kernel (const int16_t *__restrict__ gt, const int *__restrict__ lens, long n_sites, int ns,
@@ -8986,32 +9061,7 @@ void sample_distances_kernel (const int16_t *__restrict__ gt, const int *__restr
   __syncthreads ();
   int parity = 0;
   for (long c0 = s_begin; c0 < s_end; c0 += CH, parity ^= 1) {
-    // Staging, SDIST_CELLS / 256 cells of either tile a thread: a row of E samples is E consecutive int16 of the matrix and E
-    // consecutive lengths of the check pass.  Every load is issued before anything waits for one.  A missing cell is staged as
-    // -1 in one tile and -2 in the other, so that two equal words are two calls of one allele; its length is 0.  A length
-    // beyond an allele's 1023 raises the chunk's largest.
-    int g_st[2][SDIST_CELLS / 256], len_st[2][SDIST_CELLS / 256];
-    #pragma unroll
-    for (int j = 0; j < SDIST_CELLS / 256; j++) {
-      const int x = tid + 256 * j;
-      const long site = c0 + x / E;
-      #pragma unroll
-      for (int h = 0; h < 2; h++) {
-        const int sample = (h ? b0 : a0) + x % E;
-        const bool in = site < s_end && sample < ns;
-        g_st[h][j] = in ? (int) gt[site * ns + sample] : -1;
-        len_st[h][j] = in ? lens[site * ns + sample] : 0;
-      }
-    }
-    #pragma unroll
-    for (int j = 0; j < SDIST_CELLS / 256; j++)
-      #pragma unroll
-      for (int h = 0; h < 2; h++) {
-        const int x = tid + 256 * j, g = g_st[h][j], len = len_st[h][j];
-        if (len > 1023) atomicMax (l_max + parity, len);
-        (h ? gB : gA)[x] = g < 0 ? -1 - h : g;
-        (h ? lB : lA)[x] = len;
-      }
+    sdist_stage<E> (gt, lens, ns, a0, b0, c0, s_end, tid, gA, lA, gB, lB, l_max + parity);
     __syncthreads ();
     if (tid == 0) l_max[parity ^ 1] = 1023;             // (the next chunk's: last read before the barrier that ended the chunk before, raised again behind the one that ends this)
     // A site adds |La - Lb| <= max (La, Lb) <= the chunk's largest length to a pair: the 32-bit sums of floor ((2^32 - 1) / largest)
@@ -9053,50 +9103,21 @@ void sample_distances_kernel (const int16_t *__restrict__ gt, const int *__restr
       for (int q = 0; q < 4; q++) { ld[r][q] += ld32[r][q]; ld32[r][q] = 0u; }
     __syncthreads ();
   }
-  const bool mirror = ti != tj;                         // (a diagonal tile holds both halves itself)
   // where the sites are split, the whole tile goes to this workgroup's place in scratch: [slice][tile pair][E * E]
   SampleDistance *const mine = partial ? partial + ((long) blockIdx.y * gridDim.x + blockIdx.x) * (E * E) : nullptr;
-  if constexpr (Z == 1) {
-    #pragma unroll
-    for (int r = 0; r < 4; r++)
-      #pragma unroll
-      for (int q = 0; q < 4; q++) {
-        const SampleDistance o = {nb[r][q], nb[r][q] - same[r][q], (long long) ld[r][q]};
-        if (mine) mine[(4 * ty + r) * E + 4 * tx + q] = o;
-        else sdist_emit (out, ns, a0 + 4 * ty + r, b0 + 4 * tx + q, mirror, o);
-      }
-  }
-  else {                                                // the thread groups' sums meet in the staging area (the loop's last barrier is behind every read of it)
-    int *const acc_nb = lds, *const acc_nd = lds + E * E;
-    u64 *const acc_ld = (u64 *) (lds + 2 * E * E);
-    for (int x = tid; x < E * E; x += 256) { acc_nb[x] = 0; acc_nd[x] = 0; acc_ld[x] = 0ull; }
-    __syncthreads ();
-    #pragma unroll
-    for (int r = 0; r < 4; r++)
-      #pragma unroll
-      for (int q = 0; q < 4; q++) {
-        const int x = (4 * ty + r) * E + 4 * tx + q;
-        if (nb[r][q]) atomicAdd (acc_nb + x, nb[r][q]);
-        if (nb[r][q] - same[r][q]) atomicAdd (acc_nd + x, nb[r][q] - same[r][q]);
-        if (ld[r][q]) atomicAdd (acc_ld + x, ld[r][q]);
-      }
-    __syncthreads ();
-    for (int x = tid; x < E * E; x += 256) {
-      const SampleDistance o = {acc_nb[x], acc_nd[x], (long long) acc_ld[x]};
-      if (mine) mine[x] = o;
-      else sdist_emit (out, ns, a0 + x / E, b0 + x % E, mirror, o);
-    }
-  }
+  sdist_store_tile<E> (nb, same, ld, lds, mine, out, ns, a0, b0, ti != tj, tid);   // (a diagonal tile holds both halves itself)
 }
 
 // the slices' tiles summed: R lanes per cell of a tile pair (a power of two up to 16), lane l takes slices l, l + R, ...; the
-// lanes' sums meet in shuffles (integer sums: the order does not show)
+// lanes' sums meet in shuffles (integer sums: the order does not show).  blockIdx.y: the matrix (N14 has one; N19 one per
+// replicate, each with its slices in `partial` and its place in `out`)
 __global__ __launch_bounds__ (256)
 void sample_distances_reduce_kernel (const SampleDistance *__restrict__ partial, int n_slices, int n_tiles, int E, int R, int ns, SampleDistance *__restrict__ out,
                                      const int *__restrict__ err)
 {
   if (*(volatile const int *) err != 0) return;
   const long cells = (long) n_tiles * (n_tiles + 1) / 2 * (E * E);
+  partial += blockIdx.y * (n_slices * cells); out += blockIdx.y * ((long) ns * ns);
   const long n_threads = (long) gridDim.x * blockDim.x;   // (a multiple of R: the lanes of a cell stay together)
   const int l = threadIdx.x & (R - 1);
   for (long t = blockIdx.x * (long) blockDim.x + threadIdx.x; t < cells * R; t += n_threads) {   // (cells * R is a multiple of 64: a wavefront leaves the loop as one)
@@ -10718,3 +10739,415 @@ extern "C" long tjamd_sample_agglomerate (tjamd_counter *c, const tjamd_sample_d
   return (long) h_flags[2];
 }
 extern "C" double tjamd_last_sample_agglomerate_ms (tjamd_counter *c) { return c ? c->timer[T_SAMPLE_AGGLOMERATE].ms (c->device) : -1.0; }
+
+// ---- N19: bootstrap support for the clades of the sample tree ----------------------------------------------------------------
+// The rules as built are in include/tatajuba_bootstrap.h.
+// bootstrap_weights_kernel: a thread per draw, blockIdx.y the replicate; the counts meet in integer atomic adds behind a memset.
+// sample_distances_weighted: N14's check pass (it leaves `lens`), a pass over the weights (a workgroup per replicate: none below
+//   0, a sum below 2^31), N14's tiles with the replicates as a new dimension, N14's summing pass with a replicate per blockIdx.y.
+//   A workgroup stages a chunk once (sdist_stage) and walks it for SDISTW_BATCH = 2 replicates, whose weights lie beside the
+//   chunk in LDS; the batches lie in blockIdx.z.  Two because a replicate's sums are 80 registers a thread (16 each of n_both,
+//   same and the 32-bit length sums, 32 of the 64-bit ones): two of them and the walk fit 256 registers, two wavefronts a SIMD.
+//   Where a wavefront's lanes share a site (edges 32 and 64) the weights are read into scalars, and a site whose two weights
+//   are 0 (one in seven of a bootstrap's) is skipped by a uniform branch.  A pair costs four instructions that both replicates
+//   share (the AND of the called bits, a compare and a select for the equal calls, one v_sad_u32 for |La - Lb|) and four per
+//   replicate: c * w (v_mul_u32_u24), its add into n_both, the weight where the calls are equal, and one v_mad_u32_u24 of
+//   |La - Lb| * (c * w) into the 32-bit length sum.  The 24-bit
+//   multiplies hold while the call's largest weight and largest length are below 2^24 and their product within 32 bits, which
+//   the weights' check works out; the 32-bit length sums are flushed when the products since the last flush would pass
+//   2^32 - 1, and at a chunk's end.  A call beyond that is served by a second instance of the kernel (WIDE) with 32-bit
+//   multiplies and a 64-bit product straight into the 64-bit sums.  Both instances are launched; each looks at what the check
+//   left and one of them returns at once, so the host need not look in between.
+// clade_support_kernel: a workgroup per replicate.  The replicate's order becomes pos[sample] in LDS, the base order
+//   q[p] = pos[order[p]], the replicate's nodes a hash set of (first, size) in LDS (8192 places for 4095 nodes at most); a
+//   wavefront per base node takes the minimum and maximum of q over the node's interval, and lane 0 asks the set for (minimum,
+//   size) where the span is size.  The counts meet in scratch; a second kernel copies them out while no flag is up.
+
+#define SDISTW_BATCH 2                                  // replicates a workgroup serves per staged chunk
+
+__device__ __forceinline__ u64 boot_mix (u64 z)
+{
+  z ^= z >> 30; z *= 0xBF58476D1CE4E5B9ull; z ^= z >> 27; z *= 0x94D049BB133111EBull; z ^= z >> 31;
+  return z;
+}
+
+__global__ __launch_bounds__ (256)
+void bootstrap_weights_kernel (long n_sites, u64 seed, int *__restrict__ weights)
+{
+  const u64 base = boot_mix (seed + 0x9E3779B97F4A7C15ull * (u64) (blockIdx.y + 1));
+  int *const mine = weights + blockIdx.y * n_sites;
+  for (long j = blockIdx.x * 256l + threadIdx.x; j < n_sites; j += gridDim.x * 256l) {
+    const u64 h = boot_mix (base + (u64) j);
+    atomicAdd (mine + (long) (((h >> 32) * (u64) n_sites) >> 32), 1);   // ((h >> 32) < 2^32: the site is below n_sites)
+  }
+}
+
+extern "C" long tjamd_bootstrap_weights (tjamd_counter *c, long n_sites, int n_replicates, unsigned long long seed, int *d_weights)
+{
+  static const char *fn = "tjamd_bootstrap_weights";
+  if (!c) return -set_err (TJAMD_ERR_ARG, "%s: null counter", fn);
+  if (!d_weights) return -set_err (TJAMD_ERR_ARG, "%s: null d_weights", fn);
+  if (n_sites < 1 || n_sites >= (1l << 31)) return -set_err (TJAMD_ERR_ARG, "%s: n_sites %ld outside 1..2^31 - 1", fn, n_sites);
+  if (n_replicates < 1 || n_replicates > 4096) return -set_err (TJAMD_ERR_ARG, "%s: n_replicates %d outside 1..4096", fn, n_replicates);
+  if (n_sites * (long) n_replicates >= (1l << 31)) return -set_err (TJAMD_ERR_ARG, "%s: %d replicates x %ld sites: 2^31 weights or more", fn, n_replicates, n_sites);
+  if (tjamd_device_count () <= 0) return -set_err (TJAMD_ERR_NO_DEVICE, "%s: TJAMD_ERR_NO_DEVICE: no HIP device visible (the weights are drawn on the device; no CPU fallback)", fn);
+  Stage st (c, T_BOOTSTRAP_WEIGHTS);
+  if (hipSetDevice (c->device) != hipSuccess) return -set_err (TJAMD_ERR_HIP, "hipSetDevice failed");
+  st.begin ();
+  if (hipMemsetAsync (d_weights, 0, (size_t) (n_sites * n_replicates) * sizeof (int), c->stream) != hipSuccess) return -set_err (TJAMD_ERR_HIP, "%s: memset failed", fn);
+  const long per_rep = std::max (1l, 8l * c->n_cu / n_replicates);
+  hipLaunchKernelGGL (bootstrap_weights_kernel, dim3 ((unsigned) std::min ((n_sites + 255) / 256, per_rep), (unsigned) n_replicates), dim3 (256), 0, c->stream,
+                      n_sites, (u64) seed, d_weights);
+  st.end ();
+  const int rc = read_back (c, fn, nullptr, nullptr, 0);
+  if (rc) return -rc;
+  st.done ();
+  return n_replicates;
+}
+extern "C" double tjamd_last_bootstrap_weights_ms (tjamd_counter *c) { return c ? c->timer[T_BOOTSTRAP_WEIGHTS].ms (c->device) : -1.0; }
+
+// err bits beyond N14's: 256 a weight below 0, 512 a replicate whose weights sum to 2^31 or more.  A workgroup per replicate; each
+// also takes its share of the sites.  err[2] and err[3] become the largest weight and the largest length (1023 at least) of the
+// call: where both are below 2^24 and their product within 32 bits the tiles multiply in 24 bits and sum in 32 between
+// flushes; a call beyond that is served by the WIDE instance of the tile kernel.  Either instance is launched and looks.
+__global__ __launch_bounds__ (256)
+void sample_weights_check_kernel (const int *__restrict__ weights, const Site *__restrict__ sites, long n_sites, int *__restrict__ err)
+{
+  __shared__ u64 part[4];
+  const int *const mine = weights + blockIdx.x * n_sites;
+  u64 sum = 0ull;
+  int bad = 0, w_max = 0, l_max = 1023;
+  for (long i = threadIdx.x; i < n_sites; i += 256) {
+    const int w = mine[i];
+    if (w < 0) bad = 256; else sum += (u64) w;
+    w_max = max (w_max, w);
+  }
+  for (long i = blockIdx.x * 256l + threadIdx.x; i < n_sites; i += gridDim.x * 256l) l_max = max (l_max, sites[i].ref_length);
+  for (int o = 32; o; o >>= 1) { sum += shfl_xor64 (sum, o); w_max = max (w_max, __shfl_xor (w_max, o)); l_max = max (l_max, __shfl_xor (l_max, o)); }
+  if ((threadIdx.x & 63) == 0) { part[threadIdx.x >> 6] = sum; atomicMax (err + 2, w_max); atomicMax (err + 3, l_max); }
+  __syncthreads ();
+  if (threadIdx.x == 0 && part[0] + part[1] + part[2] + part[3] >= (1ull << 31)) bad |= 512;
+  if (bad) atomicOr (err, bad);
+}
+
+// what the weights' check left: does the call need the WIDE instance?
+__device__ __forceinline__ bool sdist_weights_wide (const int *err)
+{
+  const u32 w = (u32) ((volatile const int *) err)[2], l = (u32) ((volatile const int *) err)[3];
+  return w >= (1u << 24) || l >= (1u << 24) || (u64) w * l > 0xffffffffull;
+}
+
+template <int E, bool WIDE>                             // the tile's edge in samples, as in sample_distances_kernel; WIDE: see the weights' check
+__global__ __launch_bounds__ (256, E >= 32 ? 2 : 1)     // (edges 32 and 64, where the work is: two workgroups a CU, two wavefronts a SIMD, 256 registers)
+void sample_distances_weighted_kernel (const int16_t *__restrict__ gt, const int *__restrict__ lens, const int *__restrict__ weights, long n_sites, int ns, int n_rep,
+                                       int n_tiles, long per_slice, SampleDistance *__restrict__ partial, SampleDistance *__restrict__ out, const int *__restrict__ err)
+{
+  constexpr int CH = SDIST_CELLS / E, T = E / 4, Z = 256 / (T * T), NB = SDISTW_BATCH;
+  constexpr bool UNIFORM = T * T >= 64;                 // a wavefront's lanes are one thread group: they share the site, and so its weights
+  __shared__ __attribute__ ((aligned (16))) int lds[4 * SDIST_CELLS];
+  __shared__ int wl[NB][CH];                            // the chunk's weights, a row per replicate of the batch; 0 beyond the sites and the replicates
+  __shared__ int l_max[2];
+  if (*(volatile const int *) err != 0 || sdist_weights_wide (err) != WIDE) return;
+  int *const gA = lds, *const lA = lds + SDIST_CELLS, *const gB = lds + 2 * SDIST_CELLS, *const lB = lds + 3 * SDIST_CELLS;
+  int ti, tj;
+  sdist_tile_pair (blockIdx.x, n_tiles, ti, tj);
+  const int a0 = ti * E, b0 = tj * E, rep0 = blockIdx.z * NB;
+  const long s_begin = blockIdx.y * per_slice, s_end = min (n_sites, s_begin + per_slice);
+  const int tid = threadIdx.x, tx = tid % T, ty = (tid / T) % T, z = tid / (T * T);
+  int nb[NB][4][4], same[NB][4][4];                     // per replicate as in N14, weighted
+  u32 ld32[NB][4][4];
+  u64 ld[NB][4][4];
+  #pragma unroll
+  for (int k = 0; k < NB; k++)
+    #pragma unroll
+    for (int r = 0; r < 4; r++)
+      #pragma unroll
+      for (int q = 0; q < 4; q++) { nb[k][r][q] = 0; same[k][r][q] = 0; ld32[k][r][q] = 0u; ld[k][r][q] = 0ull; }
+  auto flush = [&] {
+    #pragma unroll
+    for (int k = 0; k < NB; k++)
+      #pragma unroll
+      for (int r = 0; r < 4; r++)
+        #pragma unroll
+        for (int q = 0; q < 4; q++) { ld[k][r][q] += ld32[k][r][q]; ld32[k][r][q] = 0u; }
+  };
+  if (tid == 0) l_max[0] = 1023;
+  __syncthreads ();
+  int parity = 0;
+  for (long c0 = s_begin; c0 < s_end; c0 += CH, parity ^= 1) {
+    for (int x = tid; x < NB * CH; x += 256) {
+      const int k = x / CH;
+      const long site = c0 + x % CH;
+      wl[k][x % CH] = site < s_end && rep0 + k < n_rep ? weights[(long) (rep0 + k) * n_sites + site] : 0;
+    }
+    sdist_stage<E> (gt, lens, ns, a0, b0, c0, s_end, tid, gA, lA, gB, lB, l_max + parity);
+    __syncthreads ();
+    if (tid == 0) l_max[parity ^ 1] = 1023;
+    u32 lmax = (u32) l_max[parity];
+    if constexpr (UNIFORM) lmax = (u32) __builtin_amdgcn_readfirstlane ((int) lmax);
+    // A site adds w * |La - Lb| <= w * the chunk's largest length to a pair's 32-bit sum: `room` is what the sums can still take
+    // since the last flush, counted with the larger of the site's weights.
+    u32 room = 0xffffffffu;
+    const int n_here = (int) min ((long) CH, s_end - c0);
+    for (int i = z; i < n_here; i += Z) {
+      u32 w[NB], wmax = 0u;
+      #pragma unroll
+      for (int k = 0; k < NB; k++) {
+        w[k] = (u32) wl[k][i];
+        if constexpr (UNIFORM) w[k] = (u32) __builtin_amdgcn_readfirstlane ((int) w[k]);
+        wmax = max (wmax, w[k]);
+      }
+      if (wmax == 0u) continue;                         // no replicate of the batch drew the site
+      const int4 ga = *(const int4 *) (gA + i * E + 4 * ty), la = *(const int4 *) (lA + i * E + 4 * ty);
+      const int4 gb = *(const int4 *) (gB + i * E + 4 * tx), lb = *(const int4 *) (lB + i * E + 4 * tx);
+      const int gav[4] = {ga.x, ga.y, ga.z, ga.w}, gbv[4] = {gb.x, gb.y, gb.z, gb.w};
+      const u32 lav[4] = {(u32) la.x, (u32) la.y, (u32) la.z, (u32) la.w}, lbv[4] = {(u32) lb.x, (u32) lb.y, (u32) lb.z, (u32) lb.w};
+      u32 ca[4], cb[4];                                 // 1 where the cell is called, once per cell
+      #pragma unroll
+      for (int r = 0; r < 4; r++) { ca[r] = ~(u32) gav[r] >> 31; cb[r] = ~(u32) gbv[r] >> 31; }
+      if constexpr (!WIDE) {                            // (weights and lengths below 2^24, the product of the largest two within 32 bits: the weights' check saw to it)
+        const u32 cost = wmax * lmax;
+        if (cost > room) { flush (); room = 0xffffffffu; }
+        room -= cost;
+        #pragma unroll
+        for (int r = 0; r < 4; r++)
+          #pragma unroll
+          for (int q = 0; q < 4; q++) {                 // (no branch: the sixteen pairs of both replicates stay one straight run of instructions)
+            const u32 c = ca[r] & cb[q], e = gav[r] == gbv[q] ? 1u : 0u, d = __usad (lav[r], lbv[q], 0u);   // (a missing cell equals nothing in the other tile)
+            #pragma unroll
+            for (int k = 0; k < NB; k++) {
+              const u32 cw = __umul24 (c, w[k]);
+              nb[k][r][q] += (int) cw;
+              same[k][r][q] += (int) __umul24 (e, w[k]);
+              ld32[k][r][q] += __umul24 (d, cw);
+            }
+          }
+      }
+      else {                                            // exact in 64 bits, past the 32-bit sums
+        #pragma unroll
+        for (int r = 0; r < 4; r++)
+          #pragma unroll
+          for (int q = 0; q < 4; q++) {
+            const u32 c = ca[r] & cb[q], e = gav[r] == gbv[q] ? 1u : 0u, d = __usad (lav[r], lbv[q], 0u);
+            #pragma unroll
+            for (int k = 0; k < NB; k++) {
+              const u32 cw = c * w[k];
+              nb[k][r][q] += (int) cw;
+              same[k][r][q] += (int) (e * w[k]);
+              ld[k][r][q] += (u64) d * (u64) cw;        // (both below 2^31)
+            }
+          }
+      }
+    }
+    flush ();
+    __syncthreads ();
+  }
+  // where the sites are split: [replicate][slice][tile pair][E * E], a replicate's slices as sample_distances_reduce_kernel reads them
+  #pragma unroll
+  for (int k = 0; k < NB; k++) {
+    const int rep = rep0 + k;
+    if (rep >= n_rep) break;                            // (the whole workgroup)
+    SampleDistance *const mine = partial ? partial + (((long) rep * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x) * (E * E) : nullptr;
+    sdist_store_tile<E> (nb[k], same[k], ld[k], lds, mine, out + (long) rep * ns * ns, ns, a0, b0, ti != tj, tid);
+    if (Z > 1) __syncthreads ();                        // (the next replicate's sums meet where this one's did)
+  }
+}
+
+extern "C" long tjamd_sample_distances_weighted (tjamd_counter *c, const tjamd_site *d_sites, long n_sites, const tjamd_allele *d_alleles, long n_alleles,
+                                                 const int16_t *d_genotype, int n_samples, tjamd_sample_distance *d_out, const int *d_weights, int n_replicates)
+{
+  static const char *fn = "tjamd_sample_distances_weighted";
+  if (!c) return -set_err (TJAMD_ERR_ARG, "%s: null counter", fn);
+  if (!d_out) return -set_err (TJAMD_ERR_ARG, "%s: null d_out", fn);
+  if (n_sites < 0 || n_alleles < 0) return -set_err (TJAMD_ERR_ARG, "%s: n_sites %ld, n_alleles %ld: a count below 0", fn, n_sites, n_alleles);
+  if ((n_sites > 0 && (!d_sites || !d_genotype)) || (n_alleles > 0 && !d_alleles)) return -set_err (TJAMD_ERR_ARG, "%s: null site, allele or genotype buffer", fn);
+  if (n_samples < 1 || n_samples > 4096) return -set_err (TJAMD_ERR_ARG, "%s: n_samples %d outside 1..4096", fn, n_samples);
+  if (n_alleles < n_sites) return -set_err (TJAMD_ERR_ARG, "%s: %ld alleles for %ld sites (a site has at least one)", fn, n_alleles, n_sites);
+  if (n_alleles >= (1l << 31)) return -set_err (TJAMD_ERR_ARG, "%s: %ld alleles: 2^31 or more", fn, n_alleles);
+  if (n_sites * (long) n_samples >= (1l << 31)) return -set_err (TJAMD_ERR_ARG, "%s: %ld sites x %d samples: 2^31 cells or more", fn, n_sites, n_samples);
+  if (n_sites > 0 && !d_weights) return -set_err (TJAMD_ERR_ARG, "%s: null d_weights", fn);
+  if (n_replicates < 1 || n_replicates > 4096) return -set_err (TJAMD_ERR_ARG, "%s: n_replicates %d outside 1..4096", fn, n_replicates);
+  if (n_sites * (long) n_replicates >= (1l << 31)) return -set_err (TJAMD_ERR_ARG, "%s: %d replicates x %ld sites: 2^31 weights or more", fn, n_replicates, n_sites);
+  if (tjamd_device_count () <= 0) return -set_err (TJAMD_ERR_NO_DEVICE, "%s: TJAMD_ERR_NO_DEVICE: no HIP device visible (the distances are summed on the device; no CPU fallback)", fn);
+  Stage st (c, T_SAMPLE_DISTANCES_WEIGHTED);            // (a refused call leaves no timing behind)
+  if (hipSetDevice (c->device) != hipSuccess) return -set_err (TJAMD_ERR_HIP, "hipSetDevice failed");
+  const long n_out = (long) n_samples * n_samples;
+  int rc;
+  if (n_sites == 0) {                                   // no site: every pair of every replicate has nothing in common
+    if (hipMemsetAsync (d_out, 0, (size_t) (n_out * n_replicates) * sizeof (SampleDistance), c->stream) != hipSuccess) return -set_err (TJAMD_ERR_HIP, "%s: memset failed", fn);
+    rc = read_back (c, fn, nullptr, nullptr, 0);
+    return rc ? -rc : 0;
+  }
+  // N14's decomposition with the batches of replicates as a third dimension of the grid: the workgroups aimed at count tile
+  // pairs x batches x slices.  Edge 64 where tile pairs x batches alone give half of them; the sites are split only where tile
+  // pairs x batches leave room.  Scratch, where they are split: a tile per workgroup and replicate, bounded by the workgroups
+  // aimed at (two slices of edge 64 on 1024 workgroups, 128 MB, is the most).
+  const long want = c->dist_blocks ? c->dist_blocks : 4l * c->n_cu;
+  const long n_batches = (n_replicates + SDISTW_BATCH - 1) / SDISTW_BATCH, n_tiles64 = (n_samples + 63) / 64;
+  const int E = n_samples <= 8 ? 8 : n_samples <= 16 ? 16 : n_tiles64 * (n_tiles64 + 1) / 2 * n_batches >= (want + 1) / 2 ? 64 : 32;
+  const int n_tiles = (n_samples + E - 1) / E;
+  const long n_pairs = (long) n_tiles * (n_tiles + 1) / 2, chunk = SDIST_CELLS / E, n_chunks = (n_sites + chunk - 1) / chunk;
+  long n_slices = std::max (1l, std::min (n_chunks, want / (n_pairs * n_batches)));
+  const long per_slice = (n_chunks + n_slices - 1) / n_slices * chunk;
+  n_slices = (n_sites + per_slice - 1) / per_slice;
+  ScratchCut cut;
+  int *err, *lens; SampleDistance *partial;
+  cut.take (err, 64); cut.take (lens, (size_t) (n_sites * n_samples)); cut.take (partial, n_slices > 1 ? (size_t) (n_replicates * n_slices * n_pairs) * E * E : 0);
+  rc = cut.commit (c);
+  if (rc) return -rc;
+  if (n_slices == 1) partial = nullptr;
+  if (hipMemsetAsync (err, 0, 256, c->stream) != hipSuccess) return -set_err (TJAMD_ERR_HIP, "%s: memset failed", fn);
+  SampleDistance *out = (SampleDistance *) d_out;
+  const long check_items = std::max (n_sites * n_samples, n_alleles);
+  st.begin ();
+  hipLaunchKernelGGL (sample_distances_check_kernel, dim3 ((unsigned) std::min ((check_items + 255) / 256, 8l * c->n_cu)), dim3 (256), 0, c->stream,
+                      (const Site *) d_sites, n_sites, (const Allele *) d_alleles, n_alleles, d_genotype, n_samples, lens, err);
+  hipLaunchKernelGGL (sample_weights_check_kernel, dim3 ((unsigned) n_replicates), dim3 (256), 0, c->stream, d_weights, (const Site *) d_sites, n_sites, err);
+  auto launch = [&] (auto narrow, auto wide) {          // (one of the two walks the tiles, the other returns at once: the host does not look in between)
+    for (int wd = 0; wd < 2; wd++)
+      hipLaunchKernelGGL (wd ? wide : narrow, dim3 ((unsigned) n_pairs, (unsigned) n_slices, (unsigned) n_batches), dim3 (256), 0, c->stream, d_genotype, (const int *) lens, d_weights,
+                          n_sites, n_samples, n_replicates, n_tiles, per_slice, partial, out, (const int *) err);
+  };
+  if (E == 8) launch (sample_distances_weighted_kernel<8, false>, sample_distances_weighted_kernel<8, true>);
+  else if (E == 16) launch (sample_distances_weighted_kernel<16, false>, sample_distances_weighted_kernel<16, true>);
+  else if (E == 32) launch (sample_distances_weighted_kernel<32, false>, sample_distances_weighted_kernel<32, true>);
+  else launch (sample_distances_weighted_kernel<64, false>, sample_distances_weighted_kernel<64, true>);
+  if (partial) {
+    int R = 1;                                          // lanes per cell, as in N14
+    while (R < 16 && R < n_slices) R <<= 1;
+    hipLaunchKernelGGL (sample_distances_reduce_kernel, dim3 ((unsigned) std::min ((n_pairs * E * E * R + 255) / 256, 8l * c->n_cu), (unsigned) n_replicates), dim3 (256), 0, c->stream,
+                        (const SampleDistance *) partial, (int) n_slices, n_tiles, E, R, n_samples, out, (const int *) err);
+  }
+  st.end ();
+  u32 h_err = 0;
+  rc = read_back (c, fn, err, &h_err, 1);
+  if (rc) return -rc;
+  if (h_err & 16u) return -set_err (TJAMD_ERR_ARG, "%s: a site has n_alleles < 1", fn);
+  if (h_err & 8u) return -set_err (TJAMD_ERR_ARG, "%s: first_allele and n_alleles of the sites do not chain from 0 to %ld", fn, n_alleles);
+  if (h_err & 32u) return -set_err (TJAMD_ERR_ARG, "%s: an allele's site is not the site that holds it", fn);
+  if (h_err & 64u) return -set_err (TJAMD_ERR_ARG, "%s: an allele's alt_length is outside 0..1023", fn);
+  if (h_err & 128u) return -set_err (TJAMD_ERR_ARG, "%s: a site's ref_length is below 0", fn);
+  if (h_err & 1u) return -set_err (TJAMD_ERR_ARG, "%s: a genotype cell is below -1 or above its site's n_alleles", fn);
+  if (h_err & 256u) return -set_err (TJAMD_ERR_ARG, "%s: a weight is below 0", fn);
+  if (h_err & 512u) return -set_err (TJAMD_ERR_ARG, "%s: the weights of a replicate sum to 2^31 or more", fn);
+  st.done ();
+  return n_sites;
+}
+extern "C" double tjamd_last_sample_distances_weighted_ms (tjamd_counter *c) { return c ? c->timer[T_SAMPLE_DISTANCES_WEIGHTED].ms (c->device) : -1.0; }
+
+#define CSUP_PLACES 8192                                // places of the set of a replicate's nodes: twice the most it can hold
+__device__ __forceinline__ u32 csup_place (u32 key) { return (key * 0x9E3779B1u) >> 19; }   // (the top 13 bits)
+
+// flags[0] bits: 1 an order that is not a permutation, 2 a node outside the samples or of size < 2
+__global__ __launch_bounds__ (1024)
+void clade_support_kernel (const TreeNode *__restrict__ nodes, int n_nodes, const int *__restrict__ order, int ns, const TreeNode *__restrict__ rep_nodes,
+                           const int *__restrict__ rep_order, const int *__restrict__ rep_n_nodes, int *__restrict__ cnt, int *__restrict__ flags)
+{
+  __shared__ u32 seen[CLD_MAX / 32];
+  __shared__ unsigned short pos[CLD_MAX], qp[CLD_MAX];  // a sample's position in the replicate's order; the same, by position in the base order
+  __shared__ u32 places[CSUP_PLACES];                   // first << 13 | size of a replicate's node (size >= 2: never 0), or 0
+  const int tid = threadIdx.x, lane = tid & 63, rep = blockIdx.x;
+  const int *const ro = rep_order + (long) rep * ns;
+  const TreeNode *const rn = rep_nodes + (long) rep * (ns - 1);
+  const int n_rn = rep_n_nodes[rep];                    // (0 .. ns - 1: the entry checked it)
+  int bad = 0;
+  for (int x = tid; x < CLD_MAX / 32; x += 1024) seen[x] = 0u;
+  for (int x = tid; x < CSUP_PLACES; x += 1024) places[x] = 0u;
+  for (int x = tid; x < CLD_MAX; x += 1024) pos[x] = 0;
+  __syncthreads ();
+  for (int p = tid; p < ns; p += 1024) {
+    const int s = ro[p];
+    if (s < 0 || s >= ns) { bad |= 1; continue; }
+    if ((atomicOr (&seen[s >> 5], 1u << (s & 31)) >> (s & 31)) & 1u) bad |= 1;   // ns positions on ns samples: one sample left out is one sample twice
+    pos[s] = (unsigned short) p;
+  }
+  for (int k = tid; k < n_rn; k += 1024) {
+    const TreeNode nd = rn[k];
+    if (!(nd.size >= 2 && nd.size <= ns && nd.first >= 0 && nd.first <= ns - nd.size)) { bad |= 2; continue; }
+    const u32 key = (u32) nd.first << 13 | (u32) nd.size;
+    for (u32 at = csup_place (key); ; at = (at + 1) & (CSUP_PLACES - 1)) {   // (fewer nodes than half the places: a free one comes)
+      const u32 old = atomicCAS (&places[at], 0u, key);
+      if (old == 0u || old == key) break;               // (an equal node is in the set once)
+    }
+  }
+  __syncthreads ();
+  for (int x = tid; x < CLD_MAX / 32; x += 1024) seen[x] = 0u;
+  __syncthreads ();
+  for (int p = tid; p < ns; p += 1024) {
+    const int s = order[p];
+    if (s < 0 || s >= ns) { bad |= 1; qp[p] = 0; continue; }
+    if ((atomicOr (&seen[s >> 5], 1u << (s & 31)) >> (s & 31)) & 1u) bad |= 1;
+    qp[p] = pos[s];
+  }
+  __syncthreads ();
+  for (int j = tid >> 6; j < n_nodes; j += 16) {        // a wavefront per node of the base
+    const TreeNode nd = nodes[j];
+    if (!(nd.size >= 2 && nd.size <= ns && nd.first >= 0 && nd.first <= ns - nd.size)) { bad |= 2; continue; }
+    int lo = CLD_MAX, hi = -1;
+    for (int p = nd.first + lane; p < nd.first + nd.size; p += 64) { const int v = qp[p]; lo = min (lo, v); hi = max (hi, v); }
+    for (int o = 32; o; o >>= 1) { lo = min (lo, __shfl_xor (lo, o)); hi = max (hi, __shfl_xor (hi, o)); }
+    if (lane == 0 && hi - lo + 1 == nd.size) {          // the members lie side by side in the replicate's order: is that interval a node there?
+      const u32 key = (u32) lo << 13 | (u32) nd.size;
+      for (u32 at = csup_place (key); ; at = (at + 1) & (CSUP_PLACES - 1)) {
+        const u32 v = places[at];
+        if (v == key) { atomicAdd (cnt + j, 1); break; }
+        if (v == 0u) break;
+      }
+    }
+  }
+  if (bad) atomicOr (flags, bad);
+}
+
+__global__ __launch_bounds__ (256)
+void clade_support_store_kernel (const int *__restrict__ cnt, int n_nodes, int *__restrict__ support, const int *__restrict__ flags)
+{
+  if (*(volatile const int *) flags != 0) return;
+  const int j = blockIdx.x * 256 + threadIdx.x;
+  if (j < n_nodes) support[j] = cnt[j];
+}
+
+extern "C" long tjamd_clade_support (tjamd_counter *c, const tjamd_tree_node *d_nodes, int n_nodes, const int *d_order, int n_samples, const tjamd_tree_node *d_rep_nodes,
+                                     const int *d_rep_order, const int *h_rep_n_nodes, int n_replicates, int *d_support)
+{
+  static const char *fn = "tjamd_clade_support";
+  if (!c) return -set_err (TJAMD_ERR_ARG, "%s: null counter", fn);
+  if (n_samples < 1 || n_samples > CLD_MAX) return -set_err (TJAMD_ERR_ARG, "%s: n_samples %d outside 1..4096", fn, n_samples);
+  if (n_nodes < 0 || n_nodes > CLD_MAX) return -set_err (TJAMD_ERR_ARG, "%s: n_nodes %d outside 0..4096", fn, n_nodes);
+  if (n_replicates < 1 || n_replicates > 4096) return -set_err (TJAMD_ERR_ARG, "%s: n_replicates %d outside 1..4096", fn, n_replicates);
+  if (!d_order || !d_rep_order) return -set_err (TJAMD_ERR_ARG, "%s: null d_order or d_rep_order", fn);
+  if (!h_rep_n_nodes) return -set_err (TJAMD_ERR_ARG, "%s: null h_rep_n_nodes", fn);
+  if (n_nodes > 0 && (!d_nodes || !d_support)) return -set_err (TJAMD_ERR_ARG, "%s: null d_nodes or d_support", fn);
+  for (int r = 0; r < n_replicates; r++) {
+    if (h_rep_n_nodes[r] < 0 || h_rep_n_nodes[r] > n_samples - 1)
+      return -set_err (TJAMD_ERR_ARG, "%s: replicate %d has %d nodes, outside 0..n_samples - 1 = %d", fn, r, h_rep_n_nodes[r], n_samples - 1);
+    if (h_rep_n_nodes[r] > 0 && !d_rep_nodes) return -set_err (TJAMD_ERR_ARG, "%s: null d_rep_nodes", fn);
+  }
+  if (tjamd_device_count () <= 0) return -set_err (TJAMD_ERR_NO_DEVICE, "%s: TJAMD_ERR_NO_DEVICE: no HIP device visible (the clades are compared on the device; no CPU fallback)", fn);
+  Stage st (c, T_CLADE_SUPPORT);                        // (a refused call leaves no timing behind)
+  if (hipSetDevice (c->device) != hipSuccess) return -set_err (TJAMD_ERR_HIP, "hipSetDevice failed");
+  int rc;
+  if (n_nodes == 0) {                                   // no clade to ask about: no kernel
+    rc = read_back (c, fn, nullptr, nullptr, 0);
+    return rc ? -rc : 0;
+  }
+  ScratchCut cut;
+  int *flags, *cnt, *rep_n;
+  cut.take (cnt, (size_t) n_nodes); cut.take (rep_n, (size_t) n_replicates);
+  rc = commit_with_flags (cut, c, fn, flags);
+  if (rc) return -rc;
+  if (hipMemsetAsync (cnt, 0, (size_t) n_nodes * sizeof (int), c->stream) != hipSuccess) return -set_err (TJAMD_ERR_HIP, "%s: memset failed", fn);
+  if (hipMemcpyAsync (rep_n, h_rep_n_nodes, (size_t) n_replicates * sizeof (int), hipMemcpyHostToDevice, c->stream) != hipSuccess) return -set_err (TJAMD_ERR_HIP, "%s: copy failed", fn);
+  st.begin ();
+  hipLaunchKernelGGL (clade_support_kernel, dim3 ((unsigned) n_replicates), dim3 (1024), 0, c->stream, (const TreeNode *) d_nodes, n_nodes, d_order, n_samples,
+                      (const TreeNode *) d_rep_nodes, d_rep_order, (const int *) rep_n, cnt, flags);
+  hipLaunchKernelGGL (clade_support_store_kernel, dim3 ((unsigned) ((n_nodes + 255) / 256)), dim3 (256), 0, c->stream, (const int *) cnt, n_nodes, d_support, (const int *) flags);
+  st.end ();
+  u32 h_flags[1] = {0};
+  rc = read_back (c, fn, flags, h_flags, 1);
+  if (rc) return -rc;
+  if (h_flags[0] & 1u) return -set_err (TJAMD_ERR_ARG, "%s: d_order or a replicate's order is not a permutation of 0 .. n_samples - 1", fn);
+  if (h_flags[0] & 2u) return -set_err (TJAMD_ERR_ARG, "%s: a node has size < 2, first < 0 or first + size above n_samples %d", fn, n_samples);
+  st.done ();
+  return n_nodes;
+}
+extern "C" double tjamd_last_clade_support_ms (tjamd_counter *c) { return c ? c->timer[T_CLADE_SUPPORT].ms (c->device) : -1.0; }
