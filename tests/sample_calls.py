@@ -1,0 +1,192 @@
+"""One caller per entry of the sample-comparison layer (N14-N19: distances, bootstrap weights, weighted distances, linkage,
+clusters, group sites, tree, clade sites, agglomerate, clade support), in the style of tests/bounds_calls.py: every output in a
+guarded buffer of exactly the size the header asks for, every const input frozen, guards and inputs checked before the caller
+returns; and the bytes that each of these entries cuts from the counter's scratch block, restated from hopo_device.hip.
+tests/test_sample_reuse.py calls through these.  An entry of this layer that cuts scratch gets a caller and a line here.
+
+The inputs are device tensors (tests/bounds_calls.py: dev), made once per problem by the caller's caller.  A Result carries the
+return value, the message of a refused call, the guarded outputs, and .ms, the entry's timer read after the call."""
+import ctypes as C
+
+import tatajuba_amd as tj
+from tests.bounds_calls import Result, _buffers, _checked, _p
+from tests.guarded import frozen
+
+DIST, LINK, NODE = tj.SAMPLE_DISTANCE_DTYPE, tj.LINK_DTYPE, tj.TREE_NODE_DTYPE
+CALL, GSITE, MARK = tj.GROUP_CALL_DTYPE, tj.GROUP_SITE_DTYPE, tj.GROUP_MARK_DTYPE
+UNSET = -77                              # what a scalar output holds before the call
+
+
+def call_sample_distances(c, sd, n_sites, ad, n_alleles, gd, ns):
+    """sd, ad, gd: device bytes of tjamd_site[n_sites], tjamd_allele[n_alleles] and int16 [n_sites, ns]"""
+    outs = _buffers({"d_out": ns * ns * DIST.itemsize}, ())
+    with frozen(sd, ad, gd):
+        rc = tj.lib().tjamd_sample_distances(c._h, _p(sd), n_sites, _p(ad), n_alleles, _p(gd), ns, _p(outs["d_out"]))
+        _checked(outs)
+    return Result(rc, outs, ms=c.last_sample_distances_ms())
+
+
+def call_bootstrap_weights(c, n_sites, n_rep, seed):
+    outs = _buffers({"d_weights": n_rep * n_sites * 4}, ())
+    rc = tj.lib().tjamd_bootstrap_weights(c._h, n_sites, n_rep, seed, _p(outs["d_weights"]))
+    _checked(outs)
+    return Result(rc, outs, ms=c.last_bootstrap_weights_ms())
+
+
+def call_sample_distances_weighted(c, sd, n_sites, ad, n_alleles, gd, ns, wd, n_rep):
+    """wd: device bytes of int32 [n_rep, n_sites]"""
+    outs = _buffers({"d_out": n_rep * ns * ns * DIST.itemsize}, ())
+    with frozen(sd, ad, gd, wd):
+        rc = tj.lib().tjamd_sample_distances_weighted(c._h, _p(sd), n_sites, _p(ad), n_alleles, _p(gd), ns, _p(outs["d_out"]), _p(wd), n_rep)
+        _checked(outs)
+    return Result(rc, outs, ms=c.last_sample_distances_weighted_ms())
+
+
+def call_sample_linkage(c, dd, ns, metric, min_both):
+    """dd: device bytes of tjamd_sample_distance [ns, ns]"""
+    outs = _buffers({"d_links": (ns - 1) * LINK.itemsize}, ())
+    with frozen(dd):
+        rc = tj.lib().tjamd_sample_linkage(c._h, _p(dd), ns, metric, min_both, _p(outs["d_links"]))
+        _checked(outs)
+    return Result(rc, outs, ms=c.last_sample_linkage_ms())
+
+
+def call_sample_agglomerate(c, dd, ns, metric, min_both, linkage):
+    outs = _buffers({"d_links": (ns - 1) * LINK.itemsize}, ())
+    rounds = C.c_int(UNSET)
+    with frozen(dd):
+        rc = tj.lib().tjamd_sample_agglomerate(c._h, _p(dd), ns, metric, min_both, linkage, _p(outs["d_links"]), C.byref(rounds))
+        _checked(outs)
+    return Result(rc, outs, ms=c.last_sample_agglomerate_ms(), n_rounds=rounds.value)
+
+
+def call_linkage_clusters(c, ld, n_links, ns, threshold):
+    """ld: device bytes of tjamd_link[n_links]"""
+    outs = _buffers({"d_cluster": ns * 4}, ())
+    with frozen(ld):
+        rc = tj.lib().tjamd_linkage_clusters(c._h, _p(ld), n_links, ns, threshold, _p(outs["d_cluster"]))
+        _checked(outs)
+    return Result(rc, outs, ms=c.last_linkage_clusters_ms())
+
+
+def call_linkage_tree(c, ld, n_links, ns):
+    outs = _buffers({"d_nodes": n_links * NODE.itemsize, "d_order": ns * 4}, ())
+    with frozen(ld):
+        rc = tj.lib().tjamd_linkage_tree(c._h, _p(ld), n_links, ns, _p(outs["d_nodes"]), _p(outs["d_order"]))
+        _checked(outs)
+    return Result(rc, outs, ms=c.last_linkage_tree_ms())
+
+
+def call_group_sites(c, sd, n_sites, gd, ns, labels, n_groups, min_called, cap):
+    """labels: device int32 [ns]; cap: the capacity of d_marks.  Every optional output is asked for"""
+    outs = _buffers({"d_calls": n_sites * n_groups * CALL.itemsize, "d_site_out": n_sites * GSITE.itemsize, "d_group_marks": n_groups * 4, "d_marks": cap * MARK.itemsize}, ())
+    n_marks = C.c_long(UNSET)
+    with frozen(sd, gd, labels):
+        rc = tj.lib().tjamd_group_sites(c._h, _p(sd), n_sites, _p(gd), ns, _p(labels), n_groups, min_called, _p(outs["d_calls"]), _p(outs["d_site_out"]),
+                                        _p(outs["d_group_marks"]), _p(outs["d_marks"]), cap, C.byref(n_marks))
+        _checked(outs)
+    return Result(rc, outs, ms=c.last_group_sites_ms(), n_marks=n_marks.value)
+
+
+def call_clade_sites(c, sd, n_sites, gd, ns, nd, n_nodes, od, min_called, cap):
+    """nd, od: device bytes of tjamd_tree_node[n_nodes] and int32 [ns]"""
+    outs = _buffers({"d_calls": n_sites * n_nodes * CALL.itemsize, "d_site_out": n_sites * GSITE.itemsize, "d_node_marks": n_nodes * 4, "d_marks": cap * MARK.itemsize}, ())
+    n_marks = C.c_long(UNSET)
+    with frozen(sd, gd, nd, od):
+        rc = tj.lib().tjamd_clade_sites(c._h, _p(sd), n_sites, _p(gd), ns, _p(nd), n_nodes, _p(od), min_called, _p(outs["d_calls"]), _p(outs["d_site_out"]),
+                                        _p(outs["d_node_marks"]), _p(outs["d_marks"]), cap, C.byref(n_marks))
+        _checked(outs)
+    return Result(rc, outs, ms=c.last_clade_sites_ms(), n_marks=n_marks.value)
+
+
+def call_clade_support(c, nd, n_nodes, od, ns, rnd, rod, counts):
+    """rnd, rod: device bytes of tjamd_tree_node [n_rep, ns - 1] and int32 [n_rep, ns]; counts: the nodes of every replicate"""
+    outs = _buffers({"d_support": n_nodes * 4}, ())
+    h_counts = (C.c_int * len(counts))(*counts)
+    with frozen(nd, od, rnd, rod):
+        rc = tj.lib().tjamd_clade_support(c._h, _p(nd), n_nodes, _p(od), ns, _p(rnd), _p(rod), h_counts, len(counts), _p(outs["d_support"]))
+        _checked(outs)
+    assert list(h_counts) == list(counts)
+    return Result(rc, outs, ms=c.last_clade_support_ms())
+
+
+# ---- the scratch that each entry cuts ---------------------------------------------------------------------------------------
+# ScratchCut of hopo_device.hip: the pieces of a call in the order they lie in the block, each on a 256-byte boundary, the first
+# at offset 0.  n_cu: the device's compute units (256 on an MI355X): a distance call aims at 4 n_cu workgroups, or at dist_blocks
+# where the counter was made under TATAJUBA_AMD_DISTANCE_BLOCKS, as every counter of tests/test_sample_reuse.py is.
+# LINK_SMALL = CLD_SMALL = 64.
+
+SDIST_CELLS, SDISTW_BATCH, SMALL = 2048, 2, 64
+
+
+def _r(nbytes):
+    return (nbytes + 255) & ~255
+
+
+def _tiles(ns, n_sites, n_cu, n_rep, dist_blocks=0):
+    """the decomposition of both distance entries -> (tile edge, tile pairs, slices)"""
+    want = dist_blocks or 4 * n_cu
+    n_batches = (n_rep + SDISTW_BATCH - 1) // SDISTW_BATCH if n_rep else 1
+    t64 = (ns + 63) // 64
+    E = 8 if ns <= 8 else 16 if ns <= 16 else 64 if t64 * (t64 + 1) // 2 * n_batches >= (want + 1) // 2 else 32
+    n_tiles = (ns + E - 1) // E
+    n_pairs, chunk = n_tiles * (n_tiles + 1) // 2, SDIST_CELLS // E
+    n_chunks = (n_sites + chunk - 1) // chunk
+    n_slices = max(1, min(n_chunks, want // (n_pairs * n_batches)))
+    per_slice = (n_chunks + n_slices - 1) // n_slices * chunk
+    return E, n_pairs, (n_sites + per_slice - 1) // per_slice
+
+
+def cut_distances(ns, n_sites, n_cu=256, n_rep=0, dist_blocks=0):
+    """-> [(piece, offset, bytes)]: err, lens, partial.  n_rep 0: tjamd_sample_distances; otherwise the weighted entry"""
+    E, n_pairs, n_slices = _tiles(ns, n_sites, n_cu, n_rep, dist_blocks)
+    partial = (max(n_rep, 1) * n_slices * n_pairs * E * E * DIST.itemsize) if n_slices > 1 else 0
+    return _layout([("err", 256), ("lens", 4 * n_sites * ns), ("partial", partial)])
+
+
+def cut_linkage(ns, small_form=True):
+    """comp, rowbest, edges, keys, flags: nothing but the flags in the one-workgroup form"""
+    ld = (ns + 1) & ~1
+    if ns <= SMALL and small_form:
+        return _layout([("flags", 256)])
+    return _layout([("comp", 4 * (ld + 64)), ("rowbest", 16 * ns), ("edges", 16 * ns), ("keys", 8 * ns * ld), ("flags", 256)])
+
+
+def cut_agglomerate(ns, small_form=True):
+    ld = (ns + 1) & ~1
+    if ns <= SMALL and small_form:
+        return _layout([("flags", 256)])
+    return _layout([("size", 4 * (ld + 64)), ("comp", 4 * (ld + 64)), ("rowbest", 16 * ns), ("edges", 16 * ns), ("pairs", 4 * ns), ("keys", 8 * ns * ld), ("flags", 256)])
+
+
+def cut_flags_alone():
+    """tjamd_linkage_clusters and tjamd_linkage_tree"""
+    return _layout([("flags", 256)])
+
+
+def cut_marks(n_keys, n_sites):
+    """tjamd_group_sites (n_keys: groups) and tjamd_clade_sites (nodes), in either form: the flags and every key's marks first"""
+    return _layout([("flags", 4 * (64 + n_keys)), ("cnt", 4 * n_sites)])
+
+
+def cut_support(n_nodes, n_rep):
+    return _layout([("cnt", 4 * n_nodes), ("rep_n", 4 * n_rep), ("flags", 256)])
+
+
+def _layout(pieces):
+    out, at = [], 0
+    for name, nbytes in pieces:
+        out.append((name, at, nbytes))
+        at += _r(nbytes)
+    return out
+
+
+def cut_bytes(layout):
+    """the bytes of the block that a cut takes"""
+    return sum(_r(nbytes) for _, _, nbytes in layout)
+
+
+def piece(layout, name):
+    """-> (first byte, one past the last byte written) of a piece"""
+    (at, nbytes), = [(a, n) for p, a, n in layout if p == name]
+    return at, at + nbytes

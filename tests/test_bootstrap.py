@@ -467,27 +467,59 @@ FAMILY = ([list(range(0, 6)), list(range(6, 12))] + [list(range(0, 4)), list(ran
           + [[2 * i, 2 * i + 1] for i in range(6)] + [[i] for i in range(12)])   # halves, thirds, pairs, single samples
 
 
-def planted_corpus():
-    """12 samples, 120 sites of one allele each, carried by one clade of the family; 15 % of the cells are missing"""
-    rng = np.random.RandomState(19)
-    sites, alleles, g = fabricate(PLANTED_SITES, PLANTED_NS, rng, n_alleles=[1] * PLANTED_SITES, p_missing=0.0, p_ref=1.0)
-    for i in range(PLANTED_SITES):
-        g[i, FAMILY[rng.randint(len(FAMILY))]] = 1
+def nested_family(ns):
+    """the halves of 0 .. ns - 1, their halves, and so on down to pairs: the clades of a balanced tree"""
+    family = []
+
+    def split(lo, hi):
+        if hi - lo < ns:
+            family.append(list(range(lo, hi)))
+        if hi - lo > 2:
+            split(lo, (lo + hi) // 2)
+            split((lo + hi) // 2, hi)
+
+    split(0, ns)
+    return [f for f in family if len(f) >= 2]
+
+
+def planted_corpus(ns=PLANTED_NS, n_sites=PLANTED_SITES, family=FAMILY, seed=19):
+    """ns samples (12), n_sites sites (120) of one allele each, carried by one clade of the family; 15 % of the cells are missing"""
+    rng = np.random.RandomState(seed)
+    sites, alleles, g = fabricate(n_sites, ns, rng, n_alleles=[1] * n_sites, p_missing=0.0, p_ref=1.0)
+    for i in range(n_sites):
+        g[i, family[rng.randint(len(family))]] = 1
     g[rng.random_sample(g.shape) < 0.15] = -1
     return sites, alleles, g
 
 
-def planted_chain():
-    """the chain of restatements on the planted corpus"""
-    ns, n_sites, R = PLANTED_NS, PLANTED_SITES, PLANTED_REPLICATES
-    sites, alleles, g = planted_corpus()
+def _single_linkage(dist):
+    return restate_sample_linkage(dist, DIFFER, 1)
+
+
+def planted_distances(ns=PLANTED_NS, n_sites=PLANTED_SITES, R=PLANTED_REPLICATES, seed=PLANTED_SEED, family=FAMILY, corpus_seed=19):
+    """the restated chain on a planted corpus up to the replicates' matrices"""
+    sites, alleles, g = planted_corpus(ns, n_sites, family, corpus_seed)
     x = {"sites": sites, "alleles": alleles, "g": g, "dist": restate_sample_distances(sites, alleles, g)}
-    x["base"] = restate_linkage_tree(restate_sample_linkage(x["dist"], DIFFER, 1), ns)
-    x["w"] = restate_bootstrap_weights(n_sites, R, PLANTED_SEED)
+    x["w"] = restate_bootstrap_weights(n_sites, R, seed)
     x["rep_dist"] = restate_sample_distances_weighted(sites, alleles, g, x["w"])
-    x["rep_links"] = [restate_sample_linkage(x["rep_dist"][r], DIFFER, 1) for r in range(R)]
-    x["rep_trees"] = [restate_linkage_tree(l, ns) for l in x["rep_links"]]
-    x["support"] = restate_clade_support(x["base"]["nodes"], x["base"]["order"], [(t["nodes"], t["order"]) for t in x["rep_trees"]])
+    return x
+
+
+def planted_trees(x, build=_single_linkage, support=restate_clade_support):
+    """the restated chain from the matrices on: the links that `build` makes of a matrix, their trees, and the support of the
+    base's clades -> {"base_links", "base", "rep_links", "rep_trees", "support"}"""
+    ns = x["dist"].shape[0]
+    t = {"base_links": build(x["dist"]), "rep_links": [build(d) for d in x["rep_dist"]]}
+    t["base"] = restate_linkage_tree(t["base_links"], ns)
+    t["rep_trees"] = [restate_linkage_tree(l, ns) for l in t["rep_links"]]
+    t["support"] = support(t["base"]["nodes"], t["base"]["order"], [(r["nodes"], r["order"]) for r in t["rep_trees"]])
+    return t
+
+
+def planted_chain(**corpus):
+    """the chain of restatements on the planted corpus, single linkage"""
+    x = planted_distances(**corpus)
+    x.update(planted_trees(x))
     return x
 
 

@@ -288,6 +288,72 @@ def test_the_support_on_fabricated_intervals():
     assert len(seen) >= 4 and max(seen) >= 3                                  # counts differ from node to node
 
 
+def _checked_intervals(nodes, order, ns):
+    """the refusals of _checked_tree, in its order -> (order int64 [ns], first int64 [n], size int64 [n])"""
+    order = np.asarray(order, np.int64).reshape(-1)
+    if len(order) != ns or (order < 0).any() or (order >= ns).any() or (np.bincount(order, minlength=ns) != 1).any():
+        raise ValueError("order")
+    first, size = np.asarray(nodes["first"], np.int64), np.asarray(nodes["size"], np.int64)
+    if ((size < 2) | (first < 0) | (first + size > ns)).any():
+        raise ValueError("node")
+    return order, first, size
+
+
+def restate_clade_support_by_positions(nodes, order, replicates):
+    """restate_clade_support without a set per node, in numpy, for trees of thousands of samples (a caterpillar of 4096 has 8
+    million members).  Per replicate pos = argsort(rep_order) is every sample's place in the replicate's order; a node of the base
+    is held iff the places of its members pos[order[first: first + size]] are side by side (max - min + 1 == size) and (min, size)
+    is among the replicate's (first, size) pairs.  The same refusals in the same order"""
+    ns = len(order)
+    order, first, size = _checked_intervals(nodes, order, ns)
+    checked = [_checked_intervals(rn, ro, ns) for rn, ro in replicates]
+    out = np.zeros(len(first), np.int32)
+    if not len(first):
+        return out
+    cuts = np.stack([first, first + size], 1).reshape(-1)                     # reduceat: the slices [first, first + size) are its even results
+    for ro, rfirst, rsize in checked:
+        q = np.append(np.argsort(ro, kind="stable")[order], 0)                # (one more element, in odd results alone: a slice may end at ns)
+        lo, hi = np.minimum.reduceat(q, cuts)[::2], np.maximum.reduceat(q, cuts)[::2]
+        out += ((hi - lo + 1 == size) & np.isin(lo * (ns + 1) + size, rfirst * (ns + 1) + rsize)).astype(np.int32)
+    return out
+
+
+@pytest.mark.parametrize("ns", [2, 3, 9, 64, 65, 130, 257])
+def test_the_support_by_positions_is_the_support_by_sets(ns):
+    for seed in range(3):
+        nodes, order, reps = fabricate_support(ns, 5, np.random.RandomState(1000 * ns + seed))
+        want = restate_clade_support(nodes, order, reps)
+        assert restate_clade_support_by_positions(nodes, order, reps).tolist() == want.tolist(), (ns, seed)
+        assert restate_clade_support_by_positions(nodes, order, reps).dtype == want.dtype
+        assert restate_clade_support_by_positions(nodes[:0], order, reps).tolist() == []
+        whole = nodes_of([(0, ns)])                                           # a slice that ends at ns
+        assert restate_clade_support_by_positions(whole, order, reps + [(whole, order)]).tolist() == restate_clade_support(whole, order, reps + [(whole, order)]).tolist()
+
+
+def test_the_support_by_positions_on_the_hand_case_and_its_refusals():
+    nodes, order, reps = hand_support_case()
+    assert restate_clade_support_by_positions(nodes, order, reps).tolist() == HAND_SUPPORT
+    assert restate_clade_support_by_positions(nodes, order, [(nodes, order)] * 3).tolist() == [3] * 5
+    for bad_order in ([0, 5, 3, 4, 1, 2, 2], [0, 5, 3, 4, 1, 2, 7], [0, 5, 3, 4, 1, 2, -1], [0, 5, 3, 4, 1, 2]):
+        for restate in (restate_clade_support, restate_clade_support_by_positions):
+            with pytest.raises(ValueError, match="order"):
+                restate(nodes, bad_order, reps)
+            if len(bad_order) == 7:
+                with pytest.raises(ValueError, match="order"):
+                    restate(nodes, order, reps[:1] + [(reps[1][0], bad_order)])
+    for bad_node in ((0, 1), (-1, 3), (6, 2), (0, 8), (1 << 30, 1 << 30)):
+        for restate in (restate_clade_support, restate_clade_support_by_positions):
+            with pytest.raises(ValueError, match="node"):
+                restate(nodes_of([bad_node]), order, reps)
+            with pytest.raises(ValueError, match="node"):
+                restate(nodes, order, [(nodes_of([bad_node]), order)])
+    for restate in (restate_clade_support, restate_clade_support_by_positions):   # a bad order is named before a bad node, the base before a replicate
+        with pytest.raises(ValueError, match="order"):
+            restate(nodes_of([(0, 1)]), [0, 5, 3, 4, 1, 2, 2], reps)
+        with pytest.raises(ValueError, match="node"):
+            restate(nodes_of([(0, 1)]), order, [(reps[0][0], [0] * 7)])
+
+
 def clade_support_text(names, links, tree, node_marks, support, n_replicates):
     """clade_support.tsv of examples/merged_vcf.c -B: node, size, the name of its smallest member, key, supporting sites, support, R"""
     return "".join("%d\t%d\t%s\t%d\t%d\t%d\t%d\n" % (j, nd["size"], names[int(tree["order"][int(nd["first"])])], links["key"][j], node_marks[j], support[j], n_replicates)
