@@ -30,8 +30,8 @@
  *                             outside it carries, one line per (site, node) in that order: node  contig  POS  REF  the genotype's text
  *                             (REF again for genotype 0)  the clade's called samples
  *   DIR/clade_support.tsv     with -B R[:seed] (only together with -C T -N): the bootstrap over sites.  tjamd_bootstrap_weights draws R rows of site
- *                             weights (seed 1 unless given), tjamd_sample_distances_weighted gives the R matrices in one call, every replicate's
- *                             tree is built as the tree above was (the linkage -L chose, tjamd_linkage_tree), and tjamd_clade_support counts the
+ *                             weights (seed 1 unless given), tjamd_sample_distances_weighted gives the R matrices in one call, tjamd_replicate_trees
+ *                             builds every replicate's tree as the tree above was (the linkage -L chose) in one call, and tjamd_clade_support counts the
  *                             replicates that hold each clade; one line per node of the tree: node  size  the name of its smallest sample  the
  *                             key of its link  the sites that support it (the label in sample_tree.nwk)  the replicates that hold it  R
  *   DIR/unique_variants.vcf   with -u: the tutorial's concatenation, one row per distinct allele in N8's own form (the record
@@ -45,7 +45,7 @@
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
-#include <tatajuba_bootstrap.h>
+#include <tatajuba_replicate_trees.h>
 #include <tatajuba_effects.h>
 #include <tatajuba_locate.h>
 
@@ -335,27 +335,20 @@ main (int argc, char **argv)
           const size_t R = (size_t) n_boot;
           void *d_weights = tjamd_device_alloc (ctr[0], R * (size_t) (n_sites ? n_sites : 1) * sizeof (int)),
                *d_rep_dist = tjamd_device_alloc (ctr[0], R * (size_t) n * (size_t) n * sizeof (tjamd_sample_distance)),
-               *d_rep_links = tjamd_device_alloc (ctr[0], (size_t) n * sizeof (tjamd_link)),
                *d_rep_nodes = tjamd_device_alloc (ctr[0], R * (size_t) n * sizeof (tjamd_tree_node)), *d_rep_order = tjamd_device_alloc (ctr[0], R * (size_t) n * sizeof (int)),
                *d_support = tjamd_device_alloc (ctr[0], (size_t) n * sizeof (int));
-          int *rep_n_nodes = (int *) malloc (R * sizeof (int)), r;
+          int *rep_n_nodes = (int *) malloc (R * sizeof (int));
           h_support = (int *) calloc ((size_t) n, sizeof (int));
           if (n_sites > 0 && tjamd_bootstrap_weights (ctr[0], n_sites, n_boot, boot_seed, (int *) d_weights) < 0) return fail ("bootstrap weights");
           if (tjamd_sample_distances_weighted (ctr[0], (const tjamd_site *) d_sites, n_sites, (const tjamd_allele *) d_alleles, n_alleles, (const int16_t *) d_genotype, n,
                                                (tjamd_sample_distance *) d_rep_dist, (const int *) d_weights, n_boot) < 0) return fail ("weighted sample distances");
-          for (r = 0; r < n_boot; r++) {                  /* a replicate's tree, built as the tree was */
-            const tjamd_sample_distance *d_one = (const tjamd_sample_distance *) d_rep_dist + (size_t) r * (size_t) n * (size_t) n;
-            long nl = linkage ? tjamd_sample_agglomerate (ctr[0], d_one, n, TJAMD_LINK_DIFFER, 1, linkage, (tjamd_link *) d_rep_links, NULL)
-                              : tjamd_sample_linkage (ctr[0], d_one, n, TJAMD_LINK_DIFFER, 1, (tjamd_link *) d_rep_links);
-            if (nl < 0) return fail ("replicate linkage");
-            if (tjamd_linkage_tree (ctr[0], (const tjamd_link *) d_rep_links, nl, n, (tjamd_tree_node *) d_rep_nodes + (size_t) r * (size_t) (n - 1),
-                                    (int *) d_rep_order + (size_t) r * (size_t) n) < 0) return fail ("replicate tree");
-            rep_n_nodes[r] = (int) nl;
-          }
+          /* every replicate's tree, built as the tree was (linkage: 0 is TJAMD_TREE_SINGLE, else TJAMD_AGGL_*); the links are not kept */
+          if (tjamd_replicate_trees (ctr[0], (const tjamd_sample_distance *) d_rep_dist, n, n_boot, TJAMD_LINK_DIFFER, 1, linkage, NULL, (tjamd_tree_node *) d_rep_nodes,
+                                     (int *) d_rep_order, rep_n_nodes, NULL) < 0) return fail ("replicate trees");
           if (tjamd_clade_support (ctr[0], (const tjamd_tree_node *) d_nodes, (int) n_links, (const int *) d_order, n, (const tjamd_tree_node *) d_rep_nodes,
                                    (const int *) d_rep_order, rep_n_nodes, n_boot, (int *) d_support) < 0) return fail ("clade support");
           if (tjamd_device_download (ctr[0], h_support, d_support, (size_t) n_links * sizeof (int))) return fail ("download");
-          tjamd_device_free (ctr[0], d_weights); tjamd_device_free (ctr[0], d_rep_dist); tjamd_device_free (ctr[0], d_rep_links); tjamd_device_free (ctr[0], d_rep_nodes);
+          tjamd_device_free (ctr[0], d_weights); tjamd_device_free (ctr[0], d_rep_dist); tjamd_device_free (ctr[0], d_rep_nodes);
           tjamd_device_free (ctr[0], d_rep_order); tjamd_device_free (ctr[0], d_support);
           free (rep_n_nodes);
         }

@@ -187,6 +187,9 @@ CLADE_EXPORTS = ["tjamd_linkage_tree", "tjamd_clade_sites", "tjamd_last_linkage_
 # ... and include/tatajuba_bootstrap.h
 BOOTSTRAP_EXPORTS = ["tjamd_bootstrap_weights", "tjamd_sample_distances_weighted", "tjamd_clade_support",
                      "tjamd_last_bootstrap_weights_ms", "tjamd_last_sample_distances_weighted_ms", "tjamd_last_clade_support_ms"]
+# ... and include/tatajuba_replicate_trees.h
+REPLICATE_TREE_EXPORTS = ["tjamd_replicate_trees", "tjamd_last_replicate_trees_ms"]
+TREE_SINGLE = 0                                                            # TJAMD_TREE_SINGLE: the third linkage of tjamd_replicate_trees, beside AGGL_*
 MAX_SHIFT = 3                     # TJAMD_MAX_SHIFT
 
 
@@ -379,6 +382,9 @@ def lib():
     L.tjamd_last_bootstrap_weights_ms.restype = C.c_double; L.tjamd_last_bootstrap_weights_ms.argtypes = [C.c_void_p]
     L.tjamd_last_sample_distances_weighted_ms.restype = C.c_double; L.tjamd_last_sample_distances_weighted_ms.argtypes = [C.c_void_p]
     L.tjamd_last_clade_support_ms.restype = C.c_double; L.tjamd_last_clade_support_ms.argtypes = [C.c_void_p]
+    L.tjamd_replicate_trees.restype = C.c_long
+    L.tjamd_replicate_trees.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int)]
+    L.tjamd_last_replicate_trees_ms.restype = C.c_double; L.tjamd_last_replicate_trees_ms.argtypes = [C.c_void_p]
     L.tjamd_group_contexts.restype = C.c_long
     L.tjamd_group_contexts.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_long]
     L.new_genomic_context_list.restype = C.POINTER(GenomicContextListStruct); L.new_genomic_context_list.argtypes = [P]
@@ -1081,6 +1087,19 @@ class Counter:
 
     def last_clade_support_ms(self):
         return lib().tjamd_last_clade_support_ms(self._h)
+
+    def replicate_trees(self, d_dist, n_samples, n_replicates, metric, min_both, linkage, d_rep_links, d_rep_nodes, d_rep_order):
+        """tjamd_replicate_trees on device pointers: the [replicate][sample][sample] matrices of sample_distances_weighted -> per
+        replicate the links of sample_linkage (TREE_SINGLE) or sample_agglomerate (AGGL_COMPLETE, AGGL_AVERAGE) at
+        d_rep_links[r * (n_samples - 1)] (None: not handed out), and the nodes and the leaf order of linkage_tree on them at
+        d_rep_nodes[r * (n_samples - 1)] and d_rep_order[r * n_samples]: what clade_support takes.
+        -> (rep_n_nodes, rep_n_rounds), a list of one count per replicate each"""
+        counts, rounds = (C.c_int * n_replicates)(), (C.c_int * n_replicates)()
+        self._chkn(lib().tjamd_replicate_trees(self._h, d_dist, n_samples, n_replicates, metric, min_both, linkage, d_rep_links, d_rep_nodes, d_rep_order, counts, rounds))
+        return list(counts), list(rounds)
+
+    def last_replicate_trees_ms(self):
+        return lib().tjamd_last_replicate_trees_ms(self._h)
 
     def uses_log(self):
         lib().tjamd_counter_uses_log.restype = C.c_int

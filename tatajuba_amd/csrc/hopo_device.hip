@@ -49,6 +49,7 @@
 #include "../../include/tatajuba_groups.h"
 #include "../../include/tatajuba_clades.h"
 #include "../../include/tatajuba_bootstrap.h"
+#include "../../include/tatajuba_replicate_trees.h"
 #include "../../include/tatajuba_locate.h"
 
 typedef unsigned long long u64;
@@ -3995,7 +3996,7 @@ struct StageTimer
 };
 // the intervals of a counter: the last scan call (its partition kernels between the pieces included: tjamd_last_scan_ms takes
 // them out), finalise, the kernels of tjamd_merge_samples, tjamd_tract_stats, tjamd_union_tracts, tjamd_union_tract_stats
-enum { T_SCAN, T_FIN, T_MERGE, T_TRACT, T_UNION, T_UNION_STATS, T_REF, T_LOCATE, T_LOCATED_TRACTS, T_VARIANTS, T_ANNOTATION, T_TRACT_FEATURES, T_SEED_ORDER, T_LOCATE_GAPPED, T_CODING, T_VARIANT_EFFECTS, T_MERGE_VARIANTS, T_SITE_DEPTHS, T_SAMPLE_DISTANCES, T_SAMPLE_LINKAGE, T_LINKAGE_CLUSTERS, T_GROUP_SITES, T_LINKAGE_TREE, T_CLADE_SITES, T_SAMPLE_AGGLOMERATE, T_BOOTSTRAP_WEIGHTS, T_SAMPLE_DISTANCES_WEIGHTED, T_CLADE_SUPPORT, TJ_N_TIMERS };   // (T_REF to T_LOCATED_TRACTS: N7, T_VARIANTS: N8, the next two: N9; then two of N10; two of N11; then N12, N13, N14, the two of N15, N16, the two of N17, N18 and the three of N19, end of the file)
+enum { T_SCAN, T_FIN, T_MERGE, T_TRACT, T_UNION, T_UNION_STATS, T_REF, T_LOCATE, T_LOCATED_TRACTS, T_VARIANTS, T_ANNOTATION, T_TRACT_FEATURES, T_SEED_ORDER, T_LOCATE_GAPPED, T_CODING, T_VARIANT_EFFECTS, T_MERGE_VARIANTS, T_SITE_DEPTHS, T_SAMPLE_DISTANCES, T_SAMPLE_LINKAGE, T_LINKAGE_CLUSTERS, T_GROUP_SITES, T_LINKAGE_TREE, T_CLADE_SITES, T_SAMPLE_AGGLOMERATE, T_BOOTSTRAP_WEIGHTS, T_SAMPLE_DISTANCES_WEIGHTED, T_CLADE_SUPPORT, T_REPLICATE_TREES, TJ_N_TIMERS };   // (T_REF to T_LOCATED_TRACTS: N7, T_VARIANTS: N8, the next two: N9; then two of N10; two of N11; then N12, N13, N14, the two of N15, N16, the two of N17, N18, the three of N19 and N20, end of the file)
 
 // A finalise between its two halves: finalise_queue fills this in, finalise_collect reads it and sets the state back to
 // FIN_IDLE (nothing begun).  FIN_EVENT: begun, ev_done says when the counts have arrived; FIN_ARRIVED: begun, the stream has
@@ -4064,6 +4065,7 @@ struct tjamd_counter
   int dist_blocks = 0;                                  // TATAJUBA_AMD_DISTANCE_BLOCKS (tests): the workgroups tjamd_sample_distances and tjamd_sample_distances_weighted split their sites for; 0: four per CU
   int link_small = 1;                                   // TATAJUBA_AMD_LINKAGE_SMALL (tests): 0: tjamd_sample_linkage never takes its single-workgroup path (64 samples and fewer)
   int aggl_batch = 32;                                  // TATAJUBA_AMD_AGGL_BATCH (tools, tests): the rounds tjamd_sample_agglomerate enqueues between two looks at its flag words; AGGL_BATCH
+  int trees_group = 0;                                  // TATAJUBA_AMD_TREES_GROUP (tests, tools): n >= 1: the replicates tjamd_replicate_trees takes through at a time; 0: what 1 GiB of scratch holds
   int groups_small = 1;                                 // TATAJUBA_AMD_GROUPS_SMALL (tests): 0: tjamd_group_sites never takes its wavefront-per-site form (64 samples and fewer)
   int clades_small = 1;                                 // TATAJUBA_AMD_CLADES_SMALL (tests): 0: tjamd_clade_sites never takes its wavefront-per-site form (64 samples and fewer)
   bool buckets_clean = false;
@@ -4223,6 +4225,8 @@ extern "C" tjamd_counter *tjamd_counter_create (int device, int kmer_size)
   if (ls && !strcmp (ls, "0")) c->link_small = 0;
   const char *ab = getenv ("TATAJUBA_AMD_AGGL_BATCH");       // measuring hook: n >= 1 rounds of tjamd_sample_agglomerate per look at the flag words
   if (ab && atoi (ab) >= 1) c->aggl_batch = atoi (ab);
+  const char *tg = getenv ("TATAJUBA_AMD_TREES_GROUP");      // test hook: n >= 1 replicates of tjamd_replicate_trees per group
+  if (tg && atoi (tg) >= 1) c->trees_group = atoi (tg);
   const char *gs = getenv ("TATAJUBA_AMD_GROUPS_SMALL");     // test hook: 0 sends every tjamd_group_sites through the workgroup-per-run form with its LDS tables
   if (gs && !strcmp (gs, "0")) c->groups_small = 0;
   const char *cs = getenv ("TATAJUBA_AMD_CLADES_SMALL");     // test hook: 0 sends every tjamd_clade_sites through the workgroup-per-run form with its LDS scans
@@ -9302,13 +9306,14 @@ __device__ __forceinline__ u64 linkage_key (const SampleDistance &d, const Sampl
   return metric == TJAMD_LINK_DIFFER ? (u64) d.n_differ : metric == TJAMD_LINK_LENGTH ? (u64) d.length_diff : ((u64) d.n_differ << 32) / (u64) d.n_both;
 }
 
-__global__ __launch_bounds__ (256)
-void linkage_keys_kernel (const SampleDistance *__restrict__ dist, int ns, int ld, int metric, int min_both, u64 *__restrict__ keys, int *__restrict__ comp,
-                          int *__restrict__ flags)
+// The tile (blockIdx.y, blockIdx.x) of one matrix: the kernels of N15 and N20 (a replicate per blockIdx.z) hand it their
+// matrix.  -> the error bits of the tile's cells.  STORE: the keys go to scratch; without it the tile is checked and nothing is
+// written.  key_max: a key at or above it raises bit 4 (N18's bound under AVERAGE; LINK_NONE: no bound)
+template <bool STORE>
+__device__ __forceinline__ int linkage_keys_tile (const SampleDistance *__restrict__ dist, int ns, int ld, int metric, int min_both, u64 key_max, u64 *__restrict__ keys)
 {
   __shared__ __attribute__ ((aligned (16))) SampleDistance mirror[LINK_TILE * (LINK_TILE + 1)];   // (rows of 33: a column is read without bank conflicts)
   const int tid = threadIdx.x, a0 = blockIdx.y * LINK_TILE, b0 = blockIdx.x * LINK_TILE;
-  if (blockIdx.y == 0 && tid < LINK_TILE && b0 + tid < ld) comp[b0 + tid] = b0 + tid;   // every sample its own component (ld <= the array's length)
   #pragma unroll
   for (int j = 0; j < LINK_TILE * LINK_TILE / 256; j++) {   // the tile (b, a), in its rows
     const int x = tid + 256 * j, q = x / LINK_TILE, r = x % LINK_TILE, b = b0 + q, a = a0 + r;
@@ -9322,13 +9327,23 @@ void linkage_keys_kernel (const SampleDistance *__restrict__ dist, int ns, int l
     if (a >= ns || b >= ld) continue;
     u64 key = LINK_NONE;
     if (b < ns) key = linkage_key (dist[(long) a * ns + b], mirror[q * (LINK_TILE + 1) + r], a == b, metric, min_both, bad);
-    keys[(long) a * ld + b] = key;                      // (scratch)
+    if (key != LINK_NONE && key >= key_max) bad |= 4;
+    if (STORE) keys[(long) a * ld + b] = key;           // (scratch)
   }
-  if (bad) atomicOr (flags, bad);
+  return bad;
 }
 
 __global__ __launch_bounds__ (256)
-void linkage_rowmin_kernel (const u64 *__restrict__ keys, int ns, int ld, const int *__restrict__ comp, LinkRowBest *__restrict__ rowbest, const int *__restrict__ flags)
+void linkage_keys_kernel (const SampleDistance *__restrict__ dist, int ns, int ld, int metric, int min_both, u64 *__restrict__ keys, int *__restrict__ comp,
+                          int *__restrict__ flags)
+{
+  const int tid = threadIdx.x, b0 = blockIdx.x * LINK_TILE;
+  if (blockIdx.y == 0 && tid < LINK_TILE && b0 + tid < ld) comp[b0 + tid] = b0 + tid;   // every sample its own component (ld <= the array's length)
+  const int bad = linkage_keys_tile<true> (dist, ns, ld, metric, min_both, LINK_NONE, keys);
+  if (bad) atomicOr (flags, bad);
+}
+
+__device__ __forceinline__ void linkage_rowmin_body (const u64 *__restrict__ keys, int ns, int ld, const int *__restrict__ comp, LinkRowBest *__restrict__ rowbest, const int *__restrict__ flags)
 {
   if (link_rounds_over (flags)) return;
   const int lane = threadIdx.x & 63, a = blockIdx.x * 4 + (threadIdx.x >> 6);
@@ -9348,9 +9363,11 @@ void linkage_rowmin_kernel (const u64 *__restrict__ keys, int ns, int ld, const 
   wave_min_key_b (bk, bb);
   if (lane == 0) rowbest[a] = LinkRowBest {bk, bb, 0};
 }
+__global__ __launch_bounds__ (256)
+void linkage_rowmin_kernel (const u64 *__restrict__ keys, int ns, int ld, const int *__restrict__ comp, LinkRowBest *__restrict__ rowbest, const int *__restrict__ flags)
+{ linkage_rowmin_body (keys, ns, ld, comp, rowbest, flags); }
 
-__global__ __launch_bounds__ (1024)
-void linkage_merge_kernel (const LinkRowBest *__restrict__ rowbest, int ns, int n_jump, int *__restrict__ comp, LinkEdge *__restrict__ edges, int *__restrict__ flags)
+__device__ __forceinline__ void linkage_merge_body (const LinkRowBest *__restrict__ rowbest, int ns, int n_jump, int *__restrict__ comp, LinkEdge *__restrict__ edges, int *__restrict__ flags)
 {
   __shared__ u64 cbkey[LINK_MAX];                       // per root: its component's smallest key ...
   __shared__ u32 cbpair[LINK_MAX];                      // ... and the smallest pair among the rows that hold it
@@ -9412,9 +9429,11 @@ void linkage_merge_kernel (const LinkRowBest *__restrict__ rowbest, int ns, int 
   }
   if (tid == 0) { flags[2] = base + n_new; flags[3] += 1; }
 }
-
 __global__ __launch_bounds__ (1024)
-void linkage_sort_kernel (const LinkEdge *__restrict__ edges, int P, Link *__restrict__ out, const int *__restrict__ flags)
+void linkage_merge_kernel (const LinkRowBest *__restrict__ rowbest, int ns, int n_jump, int *__restrict__ comp, LinkEdge *__restrict__ edges, int *__restrict__ flags)
+{ linkage_merge_body (rowbest, ns, n_jump, comp, edges, flags); }
+
+__device__ __forceinline__ void linkage_sort_body (const LinkEdge *__restrict__ edges, int P, Link *__restrict__ out, const int *__restrict__ flags)
 {
   __shared__ u64 skey[LINK_MAX];
   __shared__ u32 spair[LINK_MAX];
@@ -9428,14 +9447,18 @@ void linkage_sort_kernel (const LinkEdge *__restrict__ edges, int P, Link *__res
   lds_bitonic_sort<1024> (skey, spair, P);
   for (int i = tid; i < n; i += 1024) out[i] = Link {(int) (spair[i] >> 12), (int) (spair[i] & 4095u), (long long) skey[i]};
 }
+__global__ __launch_bounds__ (1024)
+void linkage_sort_kernel (const LinkEdge *__restrict__ edges, int P, Link *__restrict__ out, const int *__restrict__ flags)
+{ linkage_sort_body (edges, P, out, flags); }
 
 // Up to LINK_SMALL samples the key matrix fits in LDS (32 KB) and one workgroup does steps 1 to 3 in one launch: the same
 // checks, rounds and sort, a lane per sample.  Waves take the rows in turn for the row minimum; thread v is sample v in the
 // merge.  Barriers of one workgroup, nothing else, order the steps.
 #define LINK_SMALL 64
 
-__global__ __launch_bounds__ (256)
-void linkage_small_kernel (const SampleDistance *__restrict__ dist, int ns, int metric, int min_both, int n_rounds, Link *__restrict__ out, int *__restrict__ flags)
+// The body of the workgroup, for N15's kernel and N20's (a workgroup per replicate, the tree behind the links): -> the number
+// of links, thread i < that number holding link i in `mine`; or -1 with the error bits in `bad_bits`, in every thread alike
+__device__ __forceinline__ int linkage_small_body (const SampleDistance *__restrict__ dist, int ns, int metric, int min_both, int n_rounds, Link &mine, int &bad_bits)
 {
   __shared__ u64 keys[LINK_SMALL * LINK_SMALL], rowkey[LINK_SMALL], cbkey[LINK_SMALL], ekey[LINK_SMALL];
   __shared__ u32 cbpair[LINK_SMALL], epair[LINK_SMALL];
@@ -9451,7 +9474,8 @@ void linkage_small_kernel (const SampleDistance *__restrict__ dist, int ns, int 
   }
   if (bad) atomicOr (&bad_any, bad);
   __syncthreads ();
-  if (bad_any) { if (tid == 0) flags[0] = bad_any; return; }   // (the whole workgroup; nothing of the caller's is written)
+  bad_bits = bad_any;
+  if (bad_any) return -1;                               // (the whole workgroup)
   for (int r = 0; r < n_rounds; r++) {                  // step 2
     for (int a = wave; a < ns; a += 4) {                // (a) a wavefront per row, lane b
       u64 bk = LINK_NONE;
@@ -9489,7 +9513,19 @@ void linkage_small_kernel (const SampleDistance *__restrict__ dist, int ns, int 
     __syncthreads ();
   }
   lds_bitonic_sort<256> (ekey, epair, LINK_SMALL);      // step 3: all 64 places, the empty ones last
-  if (tid < n_links) out[tid] = Link {(int) (epair[tid] >> 12), (int) (epair[tid] & 4095u), (long long) ekey[tid]};
+  if (tid < n_links) mine = Link {(int) (epair[tid] >> 12), (int) (epair[tid] & 4095u), (long long) ekey[tid]};
+  return n_links;
+}
+
+__global__ __launch_bounds__ (256)
+void linkage_small_kernel (const SampleDistance *__restrict__ dist, int ns, int metric, int min_both, int n_rounds, Link *__restrict__ out, int *__restrict__ flags)
+{
+  const int tid = threadIdx.x;
+  Link mine;
+  int bad;
+  const int n_links = linkage_small_body (dist, ns, metric, min_both, n_rounds, mine, bad);
+  if (n_links < 0) { if (tid == 0) flags[0] = bad; return; }   // (the whole workgroup; nothing of the caller's is written)
+  if (tid < n_links) out[tid] = mine;
   if (tid == 0) flags[2] = n_links;
 }
 
@@ -10108,8 +10144,7 @@ extern "C" double tjamd_last_group_sites_ms (tjamd_counter *c) { return c ? c->t
 struct TreeNode { int left, right, first, size; };
 static_assert (sizeof (TreeNode) == 16 && sizeof (TreeNode) == sizeof (tjamd_tree_node), "tree node layout");
 
-__global__ __launch_bounds__ (1024)
-void linkage_tree_kernel (const Link *__restrict__ links, int n_links, int ns, TreeNode *__restrict__ nodes, int *__restrict__ order, int *__restrict__ flags)
+__device__ __forceinline__ void linkage_tree_body (const Link *__restrict__ links, int n_links, int ns, TreeNode *__restrict__ nodes, int *__restrict__ order, int *__restrict__ flags)
 {
   __shared__ int uf[CLD_MAX], cnode[CLD_MAX];           // a sample's label; per root (its component's smallest member) the node that is the component, or -1 - sample
   __shared__ int nl[CLD_MAX], nr[CLD_MAX], nsz[CLD_MAX], nfi[CLD_MAX];   // the nodes; nfi: a link's packed ends on the way up, a node's first position on the way down
@@ -10165,6 +10200,9 @@ void linkage_tree_kernel (const Link *__restrict__ links, int n_links, int ns, T
   __syncthreads ();
   for (int j = tid; j < n_links; j += 1024) nodes[j] = TreeNode {nl[j], nr[j], nfi[j], nsz[j]};
 }
+__global__ __launch_bounds__ (1024)
+void linkage_tree_kernel (const Link *__restrict__ links, int n_links, int ns, TreeNode *__restrict__ nodes, int *__restrict__ order, int *__restrict__ flags)
+{ linkage_tree_body (links, n_links, ns, nodes, order, flags); }
 
 extern "C" long tjamd_linkage_tree (tjamd_counter *c, const tjamd_link *d_links, long n_links, int n_samples, tjamd_tree_node *d_nodes, int *d_order)
 {
@@ -10504,8 +10542,7 @@ void aggl_init_kernel (const u64 *__restrict__ keys, int ns, int ld, int linkage
   if (bad) atomicOr (flags, bad);
 }
 
-__global__ __launch_bounds__ (256)
-void aggl_rowmin_kernel (const u64 *__restrict__ keys, int ns, int ld, int linkage, const int *__restrict__ size, LinkRowBest *__restrict__ rowbest,
+__device__ __forceinline__ void aggl_rowmin_body (const u64 *__restrict__ keys, int ns, int ld, int linkage, const int *__restrict__ size, LinkRowBest *__restrict__ rowbest,
                          const int *__restrict__ flags)
 {
   if (link_rounds_over (flags)) return;
@@ -10527,9 +10564,12 @@ void aggl_rowmin_kernel (const u64 *__restrict__ keys, int ns, int ld, int linka
   wave_min_key_b (bk, bb);
   if (lane == 0) rowbest[a] = LinkRowBest {bk, bb, 0};
 }
+__global__ __launch_bounds__ (256)
+void aggl_rowmin_kernel (const u64 *__restrict__ keys, int ns, int ld, int linkage, const int *__restrict__ size, LinkRowBest *__restrict__ rowbest,
+                         const int *__restrict__ flags)
+{ aggl_rowmin_body (keys, ns, ld, linkage, size, rowbest, flags); }
 
-__global__ __launch_bounds__ (1024)
-void aggl_pairs_kernel (const LinkRowBest *__restrict__ rowbest, int ns, int *__restrict__ size, AgglEdge *__restrict__ edges, u32 *__restrict__ pairs, int *__restrict__ flags)
+__device__ __forceinline__ void aggl_pairs_body (const LinkRowBest *__restrict__ rowbest, int ns, int *__restrict__ size, AgglEdge *__restrict__ edges, u32 *__restrict__ pairs, int *__restrict__ flags)
 {
   __shared__ int nn[LINK_MAX];                          // a live cluster's nearest neighbour; -1: retired, or no edge
   __shared__ int n_new;
@@ -10570,9 +10610,11 @@ void aggl_pairs_kernel (const LinkRowBest *__restrict__ rowbest, int ns, int *__
     }
   }
 }
+__global__ __launch_bounds__ (1024)
+void aggl_pairs_kernel (const LinkRowBest *__restrict__ rowbest, int ns, int *__restrict__ size, AgglEdge *__restrict__ edges, u32 *__restrict__ pairs, int *__restrict__ flags)
+{ aggl_pairs_body (rowbest, ns, size, edges, pairs, flags); }
 
-__global__ __launch_bounds__ (256)
-void aggl_rows_kernel (u64 *__restrict__ keys, int ld, int linkage, const u32 *__restrict__ pairs, const int *__restrict__ flags)
+__device__ __forceinline__ void aggl_rows_body (u64 *__restrict__ keys, int ld, int linkage, const u32 *__restrict__ pairs, const int *__restrict__ flags)
 {
   if (link_rounds_over (flags)) return;
   if ((int) blockIdx.x >= flags[4]) return;
@@ -10584,9 +10626,11 @@ void aggl_rows_kernel (u64 *__restrict__ keys, int ld, int linkage, const u32 *_
     rx[p] = ulonglong2 {aggl_f (x.x, y.x, linkage), aggl_f (x.y, y.y, linkage)};
   }
 }
-
 __global__ __launch_bounds__ (256)
-void aggl_cols_kernel (u64 *__restrict__ keys, int ns, int ld, int linkage, const int *__restrict__ size, const u32 *__restrict__ pairs, const int *__restrict__ flags)
+void aggl_rows_kernel (u64 *__restrict__ keys, int ld, int linkage, const u32 *__restrict__ pairs, const int *__restrict__ flags)
+{ aggl_rows_body (keys, ld, linkage, pairs, flags); }
+
+__device__ __forceinline__ void aggl_cols_body (u64 *__restrict__ keys, int ns, int ld, int linkage, const int *__restrict__ size, const u32 *__restrict__ pairs, const int *__restrict__ flags)
 {
   if (link_rounds_over (flags)) return;
   const int lane = threadIdx.x & 63, r = blockIdx.x * 4 + (threadIdx.x >> 6);
@@ -10599,9 +10643,11 @@ void aggl_cols_kernel (u64 *__restrict__ keys, int ns, int ld, int linkage, cons
     row[P] = aggl_f (row[P], row[Q], linkage);
   }
 }
+__global__ __launch_bounds__ (256)
+void aggl_cols_kernel (u64 *__restrict__ keys, int ns, int ld, int linkage, const int *__restrict__ size, const u32 *__restrict__ pairs, const int *__restrict__ flags)
+{ aggl_cols_body (keys, ns, ld, linkage, size, pairs, flags); }
 
-__global__ __launch_bounds__ (1024)
-void aggl_sort_kernel (const AgglEdge *__restrict__ edges, int P, Link *__restrict__ out, const int *__restrict__ flags)
+__device__ __forceinline__ void aggl_sort_body (const AgglEdge *__restrict__ edges, int P, Link *__restrict__ out, const int *__restrict__ flags)
 {
   __shared__ u64 skey[LINK_MAX], saux[LINK_MAX];        // (64 KB: nothing else is in LDS here)
   if (((volatile const int *) flags)[0] != 0 || ((volatile const int *) flags)[1] == 0) return;
@@ -10614,12 +10660,15 @@ void aggl_sort_kernel (const AgglEdge *__restrict__ edges, int P, Link *__restri
   lds_bitonic_sort<1024> (skey, saux, P);
   for (int i = tid; i < n; i += 1024) out[i] = Link {(int) (saux[i] >> 12 & 4095u), (int) (saux[i] & 4095u), (long long) skey[i]};
 }
+__global__ __launch_bounds__ (1024)
+void aggl_sort_kernel (const AgglEdge *__restrict__ edges, int P, Link *__restrict__ out, const int *__restrict__ flags)
+{ aggl_sort_body (edges, P, out, flags); }
 
 // Up to LINK_SMALL samples: the checks, the rounds and the sort as one workgroup in one launch, the matrix in LDS (32 KB).
 // Waves take the rows in turn for the row minimum; thread v is sample v when the pairs are found; the two phases of the update
 // are two loops with a barrier between them.
-__global__ __launch_bounds__ (256)
-void aggl_small_kernel (const SampleDistance *__restrict__ dist, int ns, int metric, int min_both, int linkage, Link *__restrict__ out, int *__restrict__ flags)
+// The body, as linkage_small_body: -> the number of links, or -1; `rounds`: the rounds that merged something
+__device__ __forceinline__ int aggl_small_body (const SampleDistance *__restrict__ dist, int ns, int metric, int min_both, int linkage, Link &mine, int &rounds, int &bad_bits)
 {
   __shared__ u64 keys[LINK_SMALL * LINK_SMALL], rowkey[LINK_SMALL], ekey[LINK_SMALL], eaux[LINK_SMALL];
   __shared__ u32 pairs[LINK_SMALL / 2];
@@ -10637,7 +10686,8 @@ void aggl_small_kernel (const SampleDistance *__restrict__ dist, int ns, int met
   }
   if (bad) atomicOr (&bad_any, bad);
   __syncthreads ();
-  if (bad_any) { if (tid == 0) flags[0] = bad_any; return; }   // (the whole workgroup; nothing of the caller's is written)
+  bad_bits = bad_any;
+  if (bad_any) return -1;                               // (the whole workgroup)
   int n_links = 0, round = 0;                           // (the same in every thread)
   for (;; round++) {
     for (int a = wave; a < ns; a += 4) {                // (a) a wavefront per row, lane b
@@ -10675,8 +10725,21 @@ void aggl_small_kernel (const SampleDistance *__restrict__ dist, int ns, int met
     __syncthreads ();
   }
   lds_bitonic_sort<256> (ekey, eaux, LINK_SMALL);       // all 64 places, the empty ones last
-  if (tid < n_links) out[tid] = Link {(int) (eaux[tid] >> 12 & 4095u), (int) (eaux[tid] & 4095u), (long long) ekey[tid]};
-  if (tid == 0) { flags[1] = 1; flags[2] = n_links; flags[3] = round; }
+  if (tid < n_links) mine = Link {(int) (eaux[tid] >> 12 & 4095u), (int) (eaux[tid] & 4095u), (long long) ekey[tid]};
+  rounds = round;
+  return n_links;
+}
+
+__global__ __launch_bounds__ (256)
+void aggl_small_kernel (const SampleDistance *__restrict__ dist, int ns, int metric, int min_both, int linkage, Link *__restrict__ out, int *__restrict__ flags)
+{
+  const int tid = threadIdx.x;
+  Link mine;
+  int rounds, bad;
+  const int n_links = aggl_small_body (dist, ns, metric, min_both, linkage, mine, rounds, bad);
+  if (n_links < 0) { if (tid == 0) flags[0] = bad; return; }   // (the whole workgroup; nothing of the caller's is written)
+  if (tid < n_links) out[tid] = mine;
+  if (tid == 0) { flags[1] = 1; flags[2] = n_links; flags[3] = rounds; }
 }
 
 extern "C" long tjamd_sample_agglomerate (tjamd_counter *c, const tjamd_sample_distance *d_dist, int n_samples, int metric, int min_both, int linkage, tjamd_link *d_links,
@@ -11151,3 +11214,323 @@ extern "C" long tjamd_clade_support (tjamd_counter *c, const tjamd_tree_node *d_
   return n_nodes;
 }
 extern "C" double tjamd_last_clade_support_ms (tjamd_counter *c) { return c ? c->timer[T_CLADE_SUPPORT].ms (c->device) : -1.0; }
+
+// ---- N20: the trees of all bootstrap replicates in one call -------------------------------------------------------------------
+// The rule as built is in include/tatajuba_replicate_trees.h: per replicate the bytes of N15's or N18's builder and of N17's
+// tree.  The bodies of their kernels run here with the replicate taken from the grid (blockIdx.y; blockIdx.z in the key pass),
+// every array of a call strided by the replicate; nothing of those bodies is restated.
+//   0. rep_check_kernel, all replicates of the call at once: N15's tiles without the stores, and N18's bound under AVERAGE.
+//      A replicate's error bits go to its flag words, their OR to the call's error word.  It is complete before any other
+//      kernel of the call starts, every other kernel returns at once while the call's word is up, and so a refused call
+//      writes nothing of the caller's, whatever the group of the bad replicate (why not staging).
+//   Up to 64 samples, rep_trees_small_kernel: a workgroup per replicate; linkage_small_body or aggl_small_body leave the sorted
+//      links in registers, a link a thread; they go to LDS, and tree_small builds N17's nodes and the leaf order there.
+//   Beyond, per group of replicates: rep_keys_kernel, the rounds (N15: ceil (log2 n_samples) times rowmin and merge, no look at
+//      the device; N18: batches of aggl_batch rounds of four kernels and the sort, one look per batch for the whole group, until
+//      every replicate of the group is done: a replicate that is done returns at once from every kernel), then rep_tree_kernel,
+//      a workgroup per replicate with linkage_tree_body on the replicate's links in scratch.
+// flag words of a replicate (8): [0] its error bits, [1] to [4] as N15 / N18 use them, [5] the tree's error word (0: the links
+// are the builder's own), [6] its links are sorted (N18's sort runs behind every batch), [7] the call's error word as the sort
+// kernel saw it (the host's one copy per batch brings it along).
+
+#define REP_FLAGS 8
+
+struct RepCut                                           // the scratch of a group: piece + replicate * stride
+{
+  u64 *keys; int *comp, *size; LinkRowBest *rowbest; LinkEdge *edges; u32 *pairs; Link *links; int *rflags; const int *flags;
+  int ns, ld, ldc;                                      // ldc: the stride of comp and size (ld + 64 words at least, a multiple of 64)
+  __device__ __forceinline__ u64 *keys_of (int g) const { return keys + (long) g * ns * ld; }
+  __device__ __forceinline__ int *comp_of (int g) const { return comp + (long) g * ldc; }
+  __device__ __forceinline__ int *size_of (int g) const { return size + (long) g * ldc; }
+  __device__ __forceinline__ LinkRowBest *rowbest_of (int g) const { return rowbest + (long) g * ns; }
+  __device__ __forceinline__ LinkEdge *edges_of (int g) const { return edges + (long) g * ns; }
+  __device__ __forceinline__ AgglEdge *aggl_edges_of (int g) const { return (AgglEdge *) edges + (long) g * ns; }
+  __device__ __forceinline__ u32 *pairs_of (int g) const { return pairs + (long) g * ns; }
+  __device__ __forceinline__ Link *links_of (int g) const { return links + (long) g * (ns - 1); }
+  __device__ __forceinline__ int *flags_of (int g) const { return rflags + (long) g * REP_FLAGS; }
+  __device__ __forceinline__ bool refused () const { return *(volatile const int *) flags != 0; }
+};
+static_assert (sizeof (LinkEdge) == sizeof (AgglEdge), "one stride for the edges of both builders");
+
+__global__ __launch_bounds__ (256)
+void rep_check_kernel (const SampleDistance *__restrict__ dist, int ns, int ld, int metric, int min_both, u64 key_max, int *__restrict__ rflags, int *__restrict__ flags)
+{
+  const int r = blockIdx.z;
+  const int bad = linkage_keys_tile<false> (dist + (long) r * ns * ns, ns, ld, metric, min_both, key_max, nullptr);
+  if (bad) { atomicOr (&rflags[(long) r * REP_FLAGS], bad); atomicOr (flags, bad); }
+}
+
+// N17's tree of at most 63 links on at most 64 samples, as linkage_tree_body builds it, by a workgroup of 256: the links in
+// LDS, lane 0 walks them up and the nodes down, wavefront 0 lays the roots out (sample v in lane v).  The links are the
+// builder's own: no check, and the walk is bounded by n_links < ns all the same.
+__device__ __forceinline__ void tree_small (const Link *sl, int n_links, int ns, TreeNode *__restrict__ nodes, int *__restrict__ order)
+{
+  __shared__ int uf[LINK_SMALL], cnode[LINK_SMALL], nl[LINK_SMALL], nr[LINK_SMALL], nsz[LINK_SMALL], nfi[LINK_SMALL], ord[LINK_SMALL];
+  const int tid = threadIdx.x;
+  if (tid < ns) { uf[tid] = tid; cnode[tid] = -1 - tid; }
+  __syncthreads ();
+  if (tid == 0)
+    for (int j = 0; j < n_links; j++) {
+      int ra = sl[j].a, rb = sl[j].b;
+      while (uf[ra] != ra) { const int up = uf[uf[ra]]; uf[ra] = up; ra = up; }
+      while (uf[rb] != rb) { const int up = uf[uf[rb]]; uf[rb] = up; rb = up; }
+      const int lo = min (ra, rb), hi = max (ra, rb), cl = cnode[lo], cr = cnode[hi];
+      nl[j] = cl; nr[j] = cr; nsz[j] = (cl >= 0 ? nsz[cl] : 1) + (cr >= 0 ? nsz[cr] : 1);
+      uf[hi] = lo; cnode[lo] = j;
+    }
+  __syncthreads ();
+  if (tid < 64) {                                       // the roots in the order of their smallest member
+    const bool root = tid < ns && uf[tid] == tid;
+    const int cn = root ? cnode[tid] : -1, mine = !root ? 0 : cn >= 0 ? nsz[cn] : 1;
+    int incl = mine;
+    #pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+      const int v = __shfl_up (incl, o);
+      if (tid >= o) incl += v;
+    }
+    if (root) { if (cn >= 0) nfi[cn] = incl - mine; else ord[incl - mine] = tid; }
+  }
+  __syncthreads ();
+  if (tid == 0)
+    for (int j = n_links - 1; j >= 0; j--) {            // a parent comes before its children
+      const int f = nfi[j], l = nl[j], r = nr[j], fr = f + (l >= 0 ? nsz[l] : 1);
+      if (l >= 0) nfi[l] = f; else ord[f] = -1 - l;
+      if (r >= 0) nfi[r] = fr; else ord[fr] = -1 - r;
+    }
+  __syncthreads ();
+  if (tid < n_links) nodes[tid] = TreeNode {nl[tid], nr[tid], nfi[tid], nsz[tid]};
+  if (tid < ns) order[tid] = ord[tid];
+}
+
+template <bool AGGL>
+__global__ __launch_bounds__ (256)
+void rep_trees_small_kernel (const SampleDistance *__restrict__ dist, int ns, int metric, int min_both, int linkage, int n_rounds, Link *__restrict__ links_out,
+                             TreeNode *__restrict__ nodes, int *__restrict__ order, int *__restrict__ rflags, const int *__restrict__ flags)
+{
+  __shared__ Link sl[LINK_SMALL];
+  if (*(volatile const int *) flags != 0) return;       // (the whole workgroup) a replicate of the call is refused
+  const int tid = threadIdx.x, r = blockIdx.x;
+  const SampleDistance *d = dist + (long) r * ns * ns;
+  Link mine = Link {0, 0, 0};
+  int rounds = 0, bad = 0, n;
+  if (AGGL) n = aggl_small_body (d, ns, metric, min_both, linkage, mine, rounds, bad);
+  else n = linkage_small_body (d, ns, metric, min_both, n_rounds, mine, bad);
+  if (n < 0) return;                                    // (the check pass has read every cell: not taken)
+  if (tid < n) {
+    sl[tid] = mine;
+    if (links_out) links_out[(long) r * (ns - 1) + tid] = mine;
+  }
+  if (tid == 0) { rflags[(long) r * REP_FLAGS + 1] = 1; rflags[(long) r * REP_FLAGS + 2] = n; rflags[(long) r * REP_FLAGS + 3] = rounds; }
+  __syncthreads ();
+  tree_small (sl, n, ns, nodes + (long) r * (ns - 1), order + (long) r * ns);
+}
+
+__global__ __launch_bounds__ (256)
+void rep_keys_kernel (RepCut A, const SampleDistance *__restrict__ dist, int metric, int min_both)
+{
+  if (A.refused ()) return;
+  const int g = blockIdx.z, tid = threadIdx.x, b0 = blockIdx.x * LINK_TILE;
+  if (blockIdx.y == 0 && tid < LINK_TILE && b0 + tid < A.ld) {   // every sample its own component, and a cluster of size 1 (the padding column: a retired cluster)
+    A.comp_of (g)[b0 + tid] = b0 + tid;
+    A.size_of (g)[b0 + tid] = b0 + tid < A.ns ? 1 : 0;
+  }
+  (void) linkage_keys_tile<true> (dist + (long) g * A.ns * A.ns, A.ns, A.ld, metric, min_both, LINK_NONE, A.keys_of (g));
+}
+
+__global__ __launch_bounds__ (256)
+void rep_linkage_rowmin_kernel (RepCut A)
+{
+  const int g = blockIdx.y;
+  if (A.refused ()) return;
+  linkage_rowmin_body (A.keys_of (g), A.ns, A.ld, A.comp_of (g), A.rowbest_of (g), A.flags_of (g));
+}
+
+__global__ __launch_bounds__ (1024)
+void rep_linkage_merge_kernel (RepCut A, int n_jump)
+{
+  const int g = blockIdx.y;
+  if (A.refused ()) return;
+  linkage_merge_body (A.rowbest_of (g), A.ns, n_jump, A.comp_of (g), A.edges_of (g), A.flags_of (g));
+}
+
+__global__ __launch_bounds__ (1024)
+void rep_linkage_sort_kernel (RepCut A, int P)
+{
+  const int g = blockIdx.y;
+  if (A.refused ()) return;
+  linkage_sort_body (A.edges_of (g), P, A.links_of (g), A.flags_of (g));
+}
+
+__global__ __launch_bounds__ (256)
+void rep_aggl_rowmin_kernel (RepCut A, int linkage)
+{
+  const int g = blockIdx.y;
+  if (A.refused ()) return;
+  aggl_rowmin_body (A.keys_of (g), A.ns, A.ld, linkage, A.size_of (g), A.rowbest_of (g), A.flags_of (g));
+}
+
+__global__ __launch_bounds__ (1024)
+void rep_aggl_pairs_kernel (RepCut A)
+{
+  const int g = blockIdx.y;
+  if (A.refused ()) return;
+  aggl_pairs_body (A.rowbest_of (g), A.ns, A.size_of (g), A.aggl_edges_of (g), A.pairs_of (g), A.flags_of (g));
+}
+
+__global__ __launch_bounds__ (256)
+void rep_aggl_rows_kernel (RepCut A, int linkage)
+{
+  const int g = blockIdx.y;
+  if (A.refused ()) return;
+  aggl_rows_body (A.keys_of (g), A.ld, linkage, A.pairs_of (g), A.flags_of (g));
+}
+
+__global__ __launch_bounds__ (256)
+void rep_aggl_cols_kernel (RepCut A, int linkage)
+{
+  const int g = blockIdx.y;
+  if (A.refused ()) return;
+  aggl_cols_body (A.keys_of (g), A.ns, A.ld, linkage, A.size_of (g), A.pairs_of (g), A.flags_of (g));
+}
+
+__global__ __launch_bounds__ (1024)
+void rep_aggl_sort_kernel (RepCut A, int P)
+{
+  const int g = blockIdx.y;
+  int *const f = A.flags_of (g);
+  const int refused = *(volatile const int *) A.flags;
+  if (refused) { if (threadIdx.x == 0) f[7] = refused; return; }   // (what the host reads per batch)
+  if (f[6]) return;                                     // sorted behind an earlier batch
+  const bool done = ((volatile const int *) f)[1] != 0; // (the whole workgroup reads one word that no kernel of this launch writes)
+  aggl_sort_body (A.aggl_edges_of (g), P, A.links_of (g), f);
+  if (done && threadIdx.x == 0) f[6] = 1;
+}
+
+__global__ __launch_bounds__ (1024)
+void rep_tree_kernel (RepCut A, Link *__restrict__ links_out, TreeNode *__restrict__ nodes, int *__restrict__ order)
+{
+  const int g = blockIdx.x;
+  if (A.refused ()) return;
+  int *const f = A.flags_of (g);
+  const int n_links = f[2], ns = A.ns;                  // (0 .. ns - 1: the builders append fewer than ns links)
+  const Link *links = A.links_of (g);
+  if (links_out)
+    for (int j = threadIdx.x; j < n_links; j += 1024) links_out[(long) g * (ns - 1) + j] = links[j];
+  linkage_tree_body (links, n_links, ns, nodes + (long) g * (ns - 1), order + (long) g * ns, f + 5);
+}
+
+extern "C" long tjamd_replicate_trees (tjamd_counter *c, const tjamd_sample_distance *d_dist, int n_samples, int n_replicates, int metric, int min_both, int linkage,
+                                       tjamd_link *d_rep_links, tjamd_tree_node *d_rep_nodes, int *d_rep_order, int *h_rep_n_nodes, int *h_rep_n_rounds)
+{
+  static const char *fn = "tjamd_replicate_trees";
+  if (!c) return -set_err (TJAMD_ERR_ARG, "%s: null counter", fn);
+  if (!d_dist) return -set_err (TJAMD_ERR_ARG, "%s: null d_dist", fn);
+  if (!d_rep_order) return -set_err (TJAMD_ERR_ARG, "%s: null d_rep_order", fn);
+  if (!h_rep_n_nodes) return -set_err (TJAMD_ERR_ARG, "%s: null h_rep_n_nodes", fn);
+  if (!d_rep_nodes && n_samples > 1) return -set_err (TJAMD_ERR_ARG, "%s: null d_rep_nodes", fn);
+  if (n_samples < 1 || n_samples > LINK_MAX) return -set_err (TJAMD_ERR_ARG, "%s: n_samples %d outside 1..4096", fn, n_samples);
+  if (n_replicates < 1 || n_replicates > 4096) return -set_err (TJAMD_ERR_ARG, "%s: n_replicates %d outside 1..4096", fn, n_replicates);
+  if (metric < TJAMD_LINK_DIFFER || metric > TJAMD_LINK_DIFFER_RATE) return -set_err (TJAMD_ERR_ARG, "%s: metric %d outside 0..2", fn, metric);
+  if (min_both < 1) return -set_err (TJAMD_ERR_ARG, "%s: min_both %d below 1", fn, min_both);
+  if (linkage != TJAMD_TREE_SINGLE && linkage != TJAMD_AGGL_COMPLETE && linkage != TJAMD_AGGL_AVERAGE) return -set_err (TJAMD_ERR_ARG, "%s: linkage %d outside 0..2", fn, linkage);
+  if (tjamd_device_count () <= 0) return -set_err (TJAMD_ERR_NO_DEVICE, "%s: TJAMD_ERR_NO_DEVICE: no HIP device visible (the trees are built on the device; no CPU fallback)", fn);
+  Stage st (c, T_REPLICATE_TREES);                      // (a refused call leaves no timing behind)
+  if (hipSetDevice (c->device) != hipSuccess) return -set_err (TJAMD_ERR_HIP, "hipSetDevice failed");
+  const int ns = n_samples, R = n_replicates;
+  int rc;
+  if (ns == 1) {                                        // one sample: no pair, no kernel; every order is the sample 0
+    if (hipMemsetAsync (d_rep_order, 0, (size_t) R * sizeof (int), c->stream) != hipSuccess) return -set_err (TJAMD_ERR_HIP, "%s: memset failed", fn);
+    rc = read_back (c, fn, nullptr, nullptr, 0);
+    if (rc) return -rc;
+    for (int r = 0; r < R; r++) { h_rep_n_nodes[r] = 0; if (h_rep_n_rounds) h_rep_n_rounds[r] = 0; }
+    return R;
+  }
+  const LinkShape shape (ns);
+  const int ld = shape.ld, P = shape.P, ldc = (ld + 64 + 63) & ~63;
+  int n_rounds = 0;
+  while ((1 << n_rounds) < ns) n_rounds++;              // N15: every round at least halves the components that still have an edge
+  const bool aggl = linkage != TJAMD_TREE_SINGLE, small = ns <= LINK_SMALL && c->link_small;
+  // the replicates of a group: what REP_SCRATCH_CAP holds of one replicate's pieces (each rounded up as the cut rounds the group's)
+  const size_t per = small ? 0 : (size_t) ns * ld * 8 + 2 * (size_t) ldc * 4 + 2 * (size_t) ns * 16 + (size_t) ns * 4 + (size_t) (ns - 1) * 16;
+  const size_t REP_SCRATCH_CAP = (size_t) 1 << 30;
+  const int G = c->trees_group ? std::min (R, c->trees_group) : small ? R : (int) std::max<size_t> (1, std::min<size_t> ((size_t) R, REP_SCRATCH_CAP / per));
+  const size_t Gs = small ? 0 : (size_t) G;
+  ScratchCut cut;
+  RepCut A;
+  int *flags;
+  cut.take (A.comp, Gs * ldc); cut.take (A.size, Gs * ldc); cut.take (A.rowbest, Gs * ns); cut.take (A.edges, Gs * ns); cut.take (A.pairs, Gs * ns);
+  cut.take (A.links, Gs * (ns - 1)); cut.take (A.keys, Gs * ns * ld); cut.take (A.rflags, (size_t) R * REP_FLAGS);
+  rc = commit_with_flags (cut, c, fn, flags);
+  if (rc) return -rc;
+  int *const rflags = A.rflags;                         // (of replicate 0; A.rflags moves with the group)
+  A.flags = flags; A.ns = ns; A.ld = ld; A.ldc = ldc;
+  if (hipMemsetAsync (rflags, 0, (size_t) R * REP_FLAGS * sizeof (int), c->stream) != hipSuccess) return -set_err (TJAMD_ERR_HIP, "%s: memset failed", fn);
+  std::vector<int> h_rf ((size_t) R * REP_FLAGS, 0);
+  const SampleDistance *dist = (const SampleDistance *) d_dist;
+  const unsigned tiles_x = (unsigned) ((ld + LINK_TILE - 1) / LINK_TILE), tiles_y = (unsigned) ((ns + LINK_TILE - 1) / LINK_TILE), row_blocks = (unsigned) ((ns + 3) / 4);
+  st.begin ();
+  hipLaunchKernelGGL (rep_check_kernel, dim3 (tiles_x, tiles_y, (unsigned) R), dim3 (256), 0, c->stream, dist, ns, ld, metric, min_both,
+                      linkage == TJAMD_AGGL_AVERAGE ? AGGL_KEY_MAX : LINK_NONE, rflags, flags);
+  bool refused = false;
+  for (int r0 = 0; r0 < R && !refused; r0 += G) {
+    const unsigned g = (unsigned) std::min (G, R - r0);
+    const SampleDistance *gdist = dist + (size_t) r0 * ns * ns;
+    Link *glinks = d_rep_links ? (Link *) d_rep_links + (size_t) r0 * (ns - 1) : nullptr;
+    TreeNode *gnodes = (TreeNode *) d_rep_nodes + (size_t) r0 * (ns - 1);
+    int *gorder = d_rep_order + (size_t) r0 * ns;
+    A.rflags = rflags + (size_t) r0 * REP_FLAGS;
+    if (small) {
+      if (aggl) hipLaunchKernelGGL (rep_trees_small_kernel<true>, dim3 (g), dim3 (256), 0, c->stream, gdist, ns, metric, min_both, linkage, n_rounds, glinks, gnodes, gorder, A.rflags, (const int *) flags);
+      else hipLaunchKernelGGL (rep_trees_small_kernel<false>, dim3 (g), dim3 (256), 0, c->stream, gdist, ns, metric, min_both, linkage, n_rounds, glinks, gnodes, gorder, A.rflags, (const int *) flags);
+      continue;
+    }
+    hipLaunchKernelGGL (rep_keys_kernel, dim3 (tiles_x, tiles_y, g), dim3 (256), 0, c->stream, A, gdist, metric, min_both);
+    if (!aggl) {
+      for (int r = 0; r < n_rounds; r++) {
+        hipLaunchKernelGGL (rep_linkage_rowmin_kernel, dim3 (row_blocks, g), dim3 (256), 0, c->stream, A);
+        hipLaunchKernelGGL (rep_linkage_merge_kernel, dim3 (1, g), dim3 (1024), 0, c->stream, A, n_rounds);
+      }
+      hipLaunchKernelGGL (rep_linkage_sort_kernel, dim3 (1, g), dim3 (1024), 0, c->stream, A, P);
+    } else {
+      // N18's batches: a look at the group's flag words per batch; the rounds enqueued are those of the group's slowest replicate
+      bool over = false;
+      for (int queued = 0; queued < ns - 1 && !over && !refused; ) {
+        for (int r = 0; r < c->aggl_batch && queued < ns - 1; r++, queued++) {
+          hipLaunchKernelGGL (rep_aggl_rowmin_kernel, dim3 (row_blocks, g), dim3 (256), 0, c->stream, A, linkage);
+          hipLaunchKernelGGL (rep_aggl_pairs_kernel, dim3 (1, g), dim3 (1024), 0, c->stream, A);
+          hipLaunchKernelGGL (rep_aggl_rows_kernel, dim3 ((unsigned) (ns / 2), g), dim3 (256), 0, c->stream, A, linkage);
+          hipLaunchKernelGGL (rep_aggl_cols_kernel, dim3 (row_blocks, g), dim3 (256), 0, c->stream, A, linkage);
+        }
+        hipLaunchKernelGGL (rep_aggl_sort_kernel, dim3 (1, g), dim3 (1024), 0, c->stream, A, P);
+        st.end ();
+        int *h = h_rf.data () + (size_t) r0 * REP_FLAGS;
+        rc = read_back (c, fn, A.rflags, h, (size_t) g * REP_FLAGS);
+        if (rc) return -rc;
+        over = true;
+        for (unsigned k = 0; k < g; k++) { if (h[k * REP_FLAGS + 7]) refused = true; if (!h[k * REP_FLAGS + 1]) over = false; }
+      }
+      if (refused) break;
+      if (!over) return -set_err (TJAMD_ERR_STATE, "%s: the rounds did not end", fn);
+    }
+    hipLaunchKernelGGL (rep_tree_kernel, dim3 (g), dim3 (1024), 0, c->stream, A, glinks, gnodes, gorder);
+  }
+  st.end ();
+  rc = read_back (c, fn, rflags, h_rf.data (), (size_t) R * REP_FLAGS);
+  if (rc) return -rc;
+  for (int r = 0; r < R; r++) {                         // the smallest refused replicate, its first broken rule in N15's / N18's order
+    const int bad = h_rf[(size_t) r * REP_FLAGS];
+    if (!bad) continue;
+    char text[256];
+    snprintf (text, sizeof text, bad & 1 ? CELL_REFUSED : bad & 2 ? MIRROR_REFUSED : "%s: a key of 2^40 or more under TJAMD_AGGL_AVERAGE", fn);
+    return -set_err (TJAMD_ERR_ARG, "%s (replicate %d)", text, r);
+  }
+  for (int r = 0; r < R; r++)
+    if (h_rf[(size_t) r * REP_FLAGS + 5]) return -set_err (TJAMD_ERR_STATE, "%s: the links of replicate %d are no forest", fn, r);
+  st.done ();
+  for (int r = 0; r < R; r++) {
+    h_rep_n_nodes[r] = h_rf[(size_t) r * REP_FLAGS + 2];
+    if (h_rep_n_rounds) h_rep_n_rounds[r] = aggl ? h_rf[(size_t) r * REP_FLAGS + 3] : 0;
+  }
+  return R;
+}
+extern "C" double tjamd_last_replicate_trees_ms (tjamd_counter *c) { return c ? c->timer[T_REPLICATE_TREES].ms (c->device) : -1.0; }
