@@ -34,6 +34,12 @@
  *                             builds every replicate's tree as the tree above was (the linkage -L chose) in one call, and tjamd_clade_support counts the
  *                             replicates that hold each clade; one line per node of the tree: node  size  the name of its smallest sample  the
  *                             key of its link  the sites that support it (the label in sample_tree.nwk)  the replicates that hold it  R
+ *   DIR/consensus_tree.nwk    with -K [percent] (only together with -C T -N -B R): tjamd_consensus_tree on the R replicate trees, the clades that
+ *                             more than half of the replicates hold (with a percentage above 50: at least ceil (percent * R / 100) of them), in Newick
+ *                             with several children per node where the replicates disagree; the label of an inner node is the number of
+ *                             replicates that hold its clade, and there are no branch lengths; a root per line
+ *   DIR/consensus_clades.tsv  with -K: one line per node of the consensus tree: node  parent (-1: a root)  size  the replicates that hold it  R
+ *                             its samples, separated by commas, in the order of the tree's leaves
  *   DIR/unique_variants.vcf   with -u: the tutorial's concatenation, one row per distinct allele in N8's own form (the record
  *                             d_unique holds), one column all_samples
  *   DIR/variant_effects.tsv   with -e annotation.gff3: tjamd_variant_effects on d_unique only, one line per allele: variant_effects.c's
@@ -41,11 +47,11 @@
  * The other options are sample_vcfs.c's.
  *
  *   gcc -O2 -I include examples/merged_vcf.c -L tatajuba_amd -ltatajuba_amd -Wl,-rpath,$PWD/tatajuba_amd -o merged_vcf
- *   ./merged_vcf -r reference.fa [-u] [-D] [-M] [-C T [-G] [-N [-B R[:seed]]] [-L single|complete|average]] [-e annotation.gff3] [-x 1] [-g G] [-s 3] [-k 10] [-m 3] [-c 5] [-d 1] [-l -1] [-o .] sample1.fastq[.gz] ...   */
+ *   ./merged_vcf -r reference.fa [-u] [-D] [-M] [-C T [-G] [-N [-B R[:seed] [-K [percent]]]] [-L single|complete|average]] [-e annotation.gff3] [-x 1] [-g G] [-s 3] [-k 10] [-m 3] [-c 5] [-d 1] [-l -1] [-o .] sample1.fastq[.gz] ...   */
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
-#include <tatajuba_replicate_trees.h>
+#include <tatajuba_consensus.h>
 #include <tatajuba_effects.h>
 #include <tatajuba_locate.h>
 
@@ -107,6 +113,25 @@ print_clade (FILE *fout, int child, long long parent_key, const tjamd_tree_node 
   fprintf (fout, ")%d:%lld", node_marks[child], parent_key - links[child].key);
 }
 
+/* node j of the consensus tree in Newick, or with j == -1 its roots, one per line: a node's children are the nodes under it
+ * and the samples of its interval that lie in none of them, in the order of the leaves; the label is the node's count */
+static void
+print_consensus (FILE *fout, int j, const tjamd_consensus_node *nodes, int n_nodes, const int *order, int n, char **sample_name)
+{
+  int p = j < 0 ? 0 : nodes[j].first, i;
+  const int end = j < 0 ? n : p + nodes[j].size;
+  if (j >= 0) fputc ('(', fout);
+  while (p < end) {
+    int child = -1;
+    for (i = 0; i < n_nodes; i++) if (nodes[i].parent == j && nodes[i].first == p) child = i;
+    if (j >= 0 && p > nodes[j].first) fputc (',', fout);
+    if (child >= 0) { print_consensus (fout, child, nodes, n_nodes, order, n, sample_name); p += nodes[child].size; }
+    else fprintf (fout, "%s", sample_name[order[p++]]);
+    if (j < 0) fprintf (fout, ";\n");
+  }
+  if (j >= 0) fprintf (fout, ")%d", nodes[j].count);
+}
+
 int
 main (int argc, char **argv)
 {
@@ -126,6 +151,10 @@ main (int argc, char **argv)
   long n_clade_marks = 0;
   int n_boot = 0, *h_support = NULL;                      /* -B: the replicates, and per node of the tree those that hold its clade */
   unsigned long long boot_seed = 1;
+  int with_consensus = 0, cons_min = 0, *h_cons_order = NULL; /* -K: the consensus of the replicates; the replicates a kept clade needs */
+  double cons_percent = 0;                                /* 0: more than half */
+  long n_cons = 0;
+  tjamd_consensus_node *h_cons = NULL;
   int n = 0, k = 10, m = 3, cov = 5, maxd = 1, lev = -1, mism = 1, max_edits = -1, max_shift = TJAMD_MAX_SHIFT, coverage[MAX_SAMPLES], a, ndev = tjamd_device_count (), status;
   const void *d_records = NULL;
   void *d_keys, *d_counts, *d_ids, *d_grouped, *d_loc, *d_perm, *d_pkeys, *d_pcounts, *d_tracts, *d_tloc, *d_reflen, *d_summary, *d_var, *d_variants, *d_sites, *d_alleles, *d_genotype, *d_unique,
@@ -167,6 +196,14 @@ main (int argc, char **argv)
       if (colon) boot_seed = strtoull (colon + 1, NULL, 10);
       if (n_boot < 1 || n_boot > 4096) n_boot = -1;
     }
+    else if (!strcmp (argv[a], "-K")) {                   /* alone, or with a percentage above 50 */
+      char *end = NULL;
+      with_consensus = 1;
+      if (a + 1 < argc && argv[a + 1][0] >= '0' && argv[a + 1][0] <= '9' && (cons_percent = strtod (argv[a + 1], &end), end && !*end)) {
+        a++;
+        if (!(cons_percent > 50 && cons_percent <= 100)) with_consensus = -1;
+      } else cons_percent = 0;
+    }
     else if (!strcmp (argv[a], "-L") && a + 1 < argc) {   /* which tree: 0 single linkage (tjamd_sample_linkage), else TJAMD_AGGL_* */
       a++; with_linkage = 1;
       if (!strcmp (argv[a], "single")) linkage = 0;
@@ -176,7 +213,7 @@ main (int argc, char **argv)
     }
     else if (n < MAX_SAMPLES) files[n++] = argv[a];
   }
-  if (n < 1 || !reference || ((with_groups || with_clades || with_linkage) && !with_clusters) || linkage < 0 || n_boot < 0 || (n_boot && !with_clades)) { fprintf (stderr, "usage: %s -r reference.fa [-u] [-D] [-M] [-C T [-G] [-N [-B R[:seed]]] [-L single|complete|average]] [-e annotation.gff3] [-x X] [-g G] [-s S] [-k K] [-m M] [-c C] [-d D] [-l L] [-o DIR] sample.fastq[.gz] ...\n", argv[0]); return 2; }
+  if (n < 1 || !reference || ((with_groups || with_clades || with_linkage) && !with_clusters) || linkage < 0 || n_boot < 0 || (n_boot && !with_clades) || with_consensus < 0 || (with_consensus && !n_boot)) { fprintf (stderr, "usage: %s -r reference.fa [-u] [-D] [-M] [-C T [-G] [-N [-B R[:seed] [-K [percent]]]] [-L single|complete|average]] [-e annotation.gff3] [-x X] [-g G] [-s S] [-k K] [-m M] [-c C] [-d D] [-l L] [-o DIR] sample.fastq[.gz] ...\n", argv[0]); return 2; }
   if (ndev < 1) { fprintf (stderr, "tatajuba_amd error: no HIP device is visible (there is no CPU fallback)\n"); return 1; }
   if (maxd < 0) maxd = 0;                                 /* src/main.c:190-192 */
   if (maxd > k / 2) maxd = k / 2;
@@ -348,6 +385,19 @@ main (int argc, char **argv)
           if (tjamd_clade_support (ctr[0], (const tjamd_tree_node *) d_nodes, (int) n_links, (const int *) d_order, n, (const tjamd_tree_node *) d_rep_nodes,
                                    (const int *) d_rep_order, rep_n_nodes, n_boot, (int *) d_support) < 0) return fail ("clade support");
           if (tjamd_device_download (ctr[0], h_support, d_support, (size_t) n_links * sizeof (int))) return fail ("download");
+          if (with_consensus) {                           /* what the replicates agree on among themselves, whatever the tree above holds */
+            void *d_cons = tjamd_device_alloc (ctr[0], (size_t) n * sizeof (tjamd_consensus_node)), *d_cons_order = tjamd_device_alloc (ctr[0], (size_t) n * sizeof (int));
+            cons_min = n_boot / 2 + 1;
+            if (cons_percent > 0) { cons_min = (int) (cons_percent * n_boot / 100.0); if (cons_min * 100.0 < cons_percent * n_boot) cons_min++; }
+            h_cons = (tjamd_consensus_node *) malloc ((size_t) n * sizeof (tjamd_consensus_node));
+            h_cons_order = (int *) malloc ((size_t) n * sizeof (int));
+            n_cons = tjamd_consensus_tree (ctr[0], (const tjamd_tree_node *) d_rep_nodes, (const int *) d_rep_order, rep_n_nodes, n, n_boot, cons_min,
+                                           (tjamd_consensus_node *) d_cons, (int *) d_cons_order, NULL, NULL);
+            if (n_cons < 0) return fail ("consensus tree");
+            if (tjamd_device_download (ctr[0], h_cons, d_cons, (size_t) n_cons * sizeof (tjamd_consensus_node)) ||
+                tjamd_device_download (ctr[0], h_cons_order, d_cons_order, (size_t) n * sizeof (int))) return fail ("download");
+            tjamd_device_free (ctr[0], d_cons); tjamd_device_free (ctr[0], d_cons_order);
+          }
           tjamd_device_free (ctr[0], d_weights); tjamd_device_free (ctr[0], d_rep_dist); tjamd_device_free (ctr[0], d_rep_nodes);
           tjamd_device_free (ctr[0], d_rep_order); tjamd_device_free (ctr[0], d_support);
           free (rep_n_nodes);
@@ -474,6 +524,20 @@ main (int argc, char **argv)
       fclose (fout);
       printf ("%d bootstrap replicates from seed %llu\n", n_boot, boot_seed);
       free (h_support);
+      if (with_consensus) {
+        if (!(fout = open_output (outdir, "consensus_tree.nwk"))) return 1;
+        print_consensus (fout, -1, h_cons, (int) n_cons, h_cons_order, n, sample_name);
+        fclose (fout);
+        if (!(fout = open_output (outdir, "consensus_clades.tsv"))) return 1;
+        for (i = 0; i < n_cons; i++) {
+          fprintf (fout, "%ld\t%d\t%d\t%d\t%d\t", i, h_cons[i].parent, h_cons[i].size, h_cons[i].count, n_boot);
+          for (a = 0; a < h_cons[i].size; a++) fprintf (fout, "%s%s", a ? "," : "", sample_name[h_cons_order[h_cons[i].first + a]]);
+          fputc ('\n', fout);
+        }
+        fclose (fout);
+        printf ("%ld clades in at least %d of %d replicates\n", n_cons, cons_min, n_boot);
+        free (h_cons); free (h_cons_order);
+      }
     }
     free (h_nodes); free (h_order); free (h_node_marks); free (h_clade_marks);
   }

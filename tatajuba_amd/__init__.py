@@ -17,4 +17,5 @@ from .capi import (Counter, Comm, Reference, Annotation, REF_ENTRY_DTYPE, LOCATI
                    GROUP_CALL_DTYPE, GROUP_SITE_DTYPE, GROUP_MARK_DTYPE, GROUP_EXPORTS,
                    TREE_NODE_DTYPE, CLADE_EXPORTS,
                    BOOTSTRAP_EXPORTS,
-                   TREE_SINGLE, REPLICATE_TREE_EXPORTS)
+                   TREE_SINGLE, REPLICATE_TREE_EXPORTS,
+                   CONSENSUS_NODE_DTYPE, CONSENSUS_EXPORTS)

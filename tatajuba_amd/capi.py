@@ -80,6 +80,8 @@ GROUP_MARK_DTYPE = np.dtype([("site", "<i4"), ("group", "<i4"), ("genotype", "<i
 assert GROUP_CALL_DTYPE.itemsize == 16 and GROUP_SITE_DTYPE.itemsize == 16 and GROUP_MARK_DTYPE.itemsize == 16
 TREE_NODE_DTYPE = np.dtype([("left", "<i4"), ("right", "<i4"), ("first", "<i4"), ("size", "<i4")])    # tjamd_tree_node (include/tatajuba_clades.h)
 assert TREE_NODE_DTYPE.itemsize == 16
+CONSENSUS_NODE_DTYPE = np.dtype([("parent", "<i4"), ("count", "<i4"), ("first", "<i4"), ("size", "<i4")])   # tjamd_consensus_node (include/tatajuba_consensus.h)
+assert CONSENSUS_NODE_DTYPE.itemsize == 16
 
 
 class TatajubaAmdError(RuntimeError):
@@ -190,6 +192,8 @@ BOOTSTRAP_EXPORTS = ["tjamd_bootstrap_weights", "tjamd_sample_distances_weighted
 # ... and include/tatajuba_replicate_trees.h
 REPLICATE_TREE_EXPORTS = ["tjamd_replicate_trees", "tjamd_last_replicate_trees_ms"]
 TREE_SINGLE = 0                                                            # TJAMD_TREE_SINGLE: the third linkage of tjamd_replicate_trees, beside AGGL_*
+# ... and include/tatajuba_consensus.h
+CONSENSUS_EXPORTS = ["tjamd_consensus_tree", "tjamd_last_consensus_tree_ms"]
 MAX_SHIFT = 3                     # TJAMD_MAX_SHIFT
 
 
@@ -385,6 +389,9 @@ def lib():
     L.tjamd_replicate_trees.restype = C.c_long
     L.tjamd_replicate_trees.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int)]
     L.tjamd_last_replicate_trees_ms.restype = C.c_double; L.tjamd_last_replicate_trees_ms.argtypes = [C.c_void_p]
+    L.tjamd_consensus_tree.restype = C.c_long
+    L.tjamd_consensus_tree.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int), C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_long)]
+    L.tjamd_last_consensus_tree_ms.restype = C.c_double; L.tjamd_last_consensus_tree_ms.argtypes = [C.c_void_p]
     L.tjamd_group_contexts.restype = C.c_long
     L.tjamd_group_contexts.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_long]
     L.new_genomic_context_list.restype = C.POINTER(GenomicContextListStruct); L.new_genomic_context_list.argtypes = [P]
@@ -1100,6 +1107,19 @@ class Counter:
 
     def last_replicate_trees_ms(self):
         return lib().tjamd_last_replicate_trees_ms(self._h)
+
+    def consensus_tree(self, d_rep_nodes, d_rep_order, rep_n_nodes, n_samples, min_count, d_nodes, d_order, d_rep_count=None):
+        """tjamd_consensus_tree on device pointers: the replicates as clade_support takes them (rep_n_nodes: a host sequence, one
+        count per replicate) -> the majority-rule consensus tree, CONSENSUS_NODE_DTYPE at d_nodes over the leaf order at
+        d_order, the classes held by at least min_count replicates; and, where d_rep_count is given, per node of every
+        replicate the count of its class at d_rep_count[r * (n_samples - 1) + k].  -> (n_nodes, n_classes)"""
+        counts = (C.c_int * len(rep_n_nodes))(*[int(x) for x in rep_n_nodes])
+        n_classes = C.c_long(-1)
+        n = self._chkn(lib().tjamd_consensus_tree(self._h, d_rep_nodes, d_rep_order, counts, n_samples, len(rep_n_nodes), min_count, d_nodes, d_order, d_rep_count, C.byref(n_classes)))
+        return n, n_classes.value
+
+    def last_consensus_tree_ms(self):
+        return lib().tjamd_last_consensus_tree_ms(self._h)
 
     def uses_log(self):
         lib().tjamd_counter_uses_log.restype = C.c_int

@@ -50,6 +50,7 @@
 #include "../../include/tatajuba_clades.h"
 #include "../../include/tatajuba_bootstrap.h"
 #include "../../include/tatajuba_replicate_trees.h"
+#include "../../include/tatajuba_consensus.h"
 #include "../../include/tatajuba_locate.h"
 
 typedef unsigned long long u64;
@@ -3996,7 +3997,7 @@ struct StageTimer
 };
 // the intervals of a counter: the last scan call (its partition kernels between the pieces included: tjamd_last_scan_ms takes
 // them out), finalise, the kernels of tjamd_merge_samples, tjamd_tract_stats, tjamd_union_tracts, tjamd_union_tract_stats
-enum { T_SCAN, T_FIN, T_MERGE, T_TRACT, T_UNION, T_UNION_STATS, T_REF, T_LOCATE, T_LOCATED_TRACTS, T_VARIANTS, T_ANNOTATION, T_TRACT_FEATURES, T_SEED_ORDER, T_LOCATE_GAPPED, T_CODING, T_VARIANT_EFFECTS, T_MERGE_VARIANTS, T_SITE_DEPTHS, T_SAMPLE_DISTANCES, T_SAMPLE_LINKAGE, T_LINKAGE_CLUSTERS, T_GROUP_SITES, T_LINKAGE_TREE, T_CLADE_SITES, T_SAMPLE_AGGLOMERATE, T_BOOTSTRAP_WEIGHTS, T_SAMPLE_DISTANCES_WEIGHTED, T_CLADE_SUPPORT, T_REPLICATE_TREES, TJ_N_TIMERS };   // (T_REF to T_LOCATED_TRACTS: N7, T_VARIANTS: N8, the next two: N9; then two of N10; two of N11; then N12, N13, N14, the two of N15, N16, the two of N17, N18, the three of N19 and N20, end of the file)
+enum { T_SCAN, T_FIN, T_MERGE, T_TRACT, T_UNION, T_UNION_STATS, T_REF, T_LOCATE, T_LOCATED_TRACTS, T_VARIANTS, T_ANNOTATION, T_TRACT_FEATURES, T_SEED_ORDER, T_LOCATE_GAPPED, T_CODING, T_VARIANT_EFFECTS, T_MERGE_VARIANTS, T_SITE_DEPTHS, T_SAMPLE_DISTANCES, T_SAMPLE_LINKAGE, T_LINKAGE_CLUSTERS, T_GROUP_SITES, T_LINKAGE_TREE, T_CLADE_SITES, T_SAMPLE_AGGLOMERATE, T_BOOTSTRAP_WEIGHTS, T_SAMPLE_DISTANCES_WEIGHTED, T_CLADE_SUPPORT, T_REPLICATE_TREES, T_CONSENSUS_TREE, TJ_N_TIMERS };   // (T_REF to T_LOCATED_TRACTS: N7, T_VARIANTS: N8, the next two: N9; then two of N10; two of N11; then N12, N13, N14, the two of N15, N16, the two of N17, N18, the three of N19, N20 and N21, end of the file)
 
 // A finalise between its two halves: finalise_queue fills this in, finalise_collect reads it and sets the state back to
 // FIN_IDLE (nothing begun).  FIN_EVENT: begun, ev_done says when the counts have arrived; FIN_ARRIVED: begun, the stream has
@@ -4066,6 +4067,7 @@ struct tjamd_counter
   int link_small = 1;                                   // TATAJUBA_AMD_LINKAGE_SMALL (tests): 0: tjamd_sample_linkage never takes its single-workgroup path (64 samples and fewer)
   int aggl_batch = 32;                                  // TATAJUBA_AMD_AGGL_BATCH (tools, tests): the rounds tjamd_sample_agglomerate enqueues between two looks at its flag words; AGGL_BATCH
   int trees_group = 0;                                  // TATAJUBA_AMD_TREES_GROUP (tests, tools): n >= 1: the replicates tjamd_replicate_trees takes through at a time; 0: what 1 GiB of scratch holds
+  int consensus_key_bits = 51;                          // TATAJUBA_AMD_CONSENSUS_KEY_BITS (tests): b in 0 .. 51: the bits of the hash sum that tjamd_consensus_tree keeps in a clade's key; CONS_KEY_BITS
   int groups_small = 1;                                 // TATAJUBA_AMD_GROUPS_SMALL (tests): 0: tjamd_group_sites never takes its wavefront-per-site form (64 samples and fewer)
   int clades_small = 1;                                 // TATAJUBA_AMD_CLADES_SMALL (tests): 0: tjamd_clade_sites never takes its wavefront-per-site form (64 samples and fewer)
   bool buckets_clean = false;
@@ -4227,6 +4229,8 @@ extern "C" tjamd_counter *tjamd_counter_create (int device, int kmer_size)
   if (ab && atoi (ab) >= 1) c->aggl_batch = atoi (ab);
   const char *tg = getenv ("TATAJUBA_AMD_TREES_GROUP");      // test hook: n >= 1 replicates of tjamd_replicate_trees per group
   if (tg && atoi (tg) >= 1) c->trees_group = atoi (tg);
+  const char *kb = getenv ("TATAJUBA_AMD_CONSENSUS_KEY_BITS");   // test hook: fewer bits put different clades into one run of tjamd_consensus_tree, which then tells them apart by comparison
+  if (kb && *kb && atoi (kb) >= 0) c->consensus_key_bits = std::min (atoi (kb), 51);
   const char *gs = getenv ("TATAJUBA_AMD_GROUPS_SMALL");     // test hook: 0 sends every tjamd_group_sites through the workgroup-per-run form with its LDS tables
   if (gs && !strcmp (gs, "0")) c->groups_small = 0;
   const char *cs = getenv ("TATAJUBA_AMD_CLADES_SMALL");     // test hook: 0 sends every tjamd_clade_sites through the workgroup-per-run form with its LDS scans
@@ -11534,3 +11538,397 @@ extern "C" long tjamd_replicate_trees (tjamd_counter *c, const tjamd_sample_dist
   return R;
 }
 extern "C" double tjamd_last_replicate_trees_ms (tjamd_counter *c) { return c ? c->timer[T_REPLICATE_TREES].ms (c->device) : -1.0; }
+
+// ---- N21: the majority-rule consensus tree of the bootstrap replicates ----------------------------------------------------------
+// The rule as built is in include/tatajuba_consensus.h.  A clade is a record: its index g = rep_off[r] + k among all nodes of
+// the call, and a key (size << 51 | the low bits of a hash sum over its members).  Equal sets have equal keys; equal keys are
+// told apart by comparing sets, so nothing rests on the hash.
+//   1. cons_records_kernel, a workgroup per replicate: the permutation, the nodes and the crossing check (far[p]: the furthest
+//      end of the nodes that start at p; a node crosses another exactly when a node that starts inside it ends behind it), the
+//      positions of the samples to scratch, the prefix sums of the hashes in LDS, a record per node.  Error bits go to the
+//      replicate's word and to the call's; every later kernel returns at once while the call's word is up.
+//   2. kv_sort on all 64 bits; cons_heads_kernel and a scan number the runs of equal keys.
+//   3. rounds: cons_lead_kernel takes the first unsettled record of every run as its leader (an integer minimum), and
+//      cons_compare_kernel, a wavefront per unsettled record, settles the leader itself and every record whose set is the
+//      leader's.  The host reads one word per round and goes on while a record is unsettled.
+//   4. cons_count_kernel: a record counts for its class unless an earlier record of its run has its class and its replicate
+//      (those lie next to each other: the sort is stable and the records were emitted replicate by replicate).
+//   5. cons_kept_kernel hands the counts out and lists the leaders of the kept classes; cons_info_kernel, a wavefront per kept
+//      class, finds its smallest member; cons_order_kernel ranks them by (size, smallest member); cons_parent_kernel, a
+//      wavefront per kept class, finds the first larger class that holds its smallest member (laminar: that class holds all of
+//      it) and marks its members' smallest class; cons_layout_kernel lays nodes and samples out.
+// flag words of the call: [0] error bits (1 order, 2 node, 4 crossing), [1] a record is unsettled after this round, [2] kept
+// classes, [3] classes, [4] more kept classes than n_samples - 1 (cannot be: a laminar family).
+
+#define CONS_KEY_BITS 51
+#define CONS_SALT 0x5851F42D4C957F2Dull
+#define CONS_NONE 0xFFFFu
+
+struct ConsNode { int parent, count, first, size; };
+struct ConsKept { int size, minm, count, rep, first, pad; };   // rep, first: where the class's leader lies
+static_assert (sizeof (ConsNode) == sizeof (tjamd_consensus_node) && sizeof (ConsNode) == sizeof (TreeNode), "a consensus node is read as a tree node");
+static_assert (offsetof (ConsNode, first) == offsetof (TreeNode, first) && offsetof (ConsNode, size) == offsetof (TreeNode, size), "first and size where tjamd_tree_node has them");
+
+struct ConsIn                                           // the replicates of a call, as every kernel of it reads them
+{
+  const TreeNode *rep_nodes; const int *rep_order, *rep_n, *rep_off; const unsigned short *pos; int ns, R;
+  __device__ __forceinline__ int rep_of (int g) const   // the replicate of record g: the last one that starts at or before it
+  {
+    int lo = 0, hi = R;
+    while (hi - lo > 1) { const int mid = (lo + hi) >> 1; if (rep_off[mid] <= g) lo = mid; else hi = mid; }
+    return lo;
+  }
+  __device__ __forceinline__ TreeNode node_of (int g, int r) const { return rep_nodes[(long) r * (ns - 1) + (g - rep_off[r])]; }
+  __device__ __forceinline__ const int *members_of (int r, int first) const { return rep_order + (long) r * ns + first; }
+};
+
+__global__ __launch_bounds__ (1024)
+void cons_records_kernel (ConsIn A, u64 key_mask, unsigned short *__restrict__ pos_out, u64 *__restrict__ key, u32 *__restrict__ val, int *__restrict__ rbad, int *__restrict__ flags)
+{
+  __shared__ u32 seen[CLD_MAX / 32];
+  __shared__ int far[CLD_MAX];                          // the furthest end of the nodes that start at a position, or 0
+  __shared__ u64 pre[CLD_MAX + 1];                      // pre[p]: the wrapping sum of the hashes of the samples before position p
+  __shared__ u64 wsum[16];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, r = blockIdx.x, ns = A.ns;
+  const int *const ro = A.rep_order + (long) r * ns;
+  const TreeNode *const rn = A.rep_nodes + (long) r * (ns - 1);
+  const int n_rn = A.rep_n[r], off = A.rep_off[r];      // (0 .. ns - 1: the entry checked it)
+  int bad = 0;
+  for (int x = tid; x < CLD_MAX / 32; x += 1024) seen[x] = 0u;
+  for (int x = tid; x < CLD_MAX; x += 1024) far[x] = 0;
+  __syncthreads ();
+  u64 run[4], total = 0;                                // four positions a thread
+  #pragma unroll
+  for (int q = 0; q < 4; q++) {
+    const int p = tid * 4 + q;
+    u64 h = 0;
+    if (p < ns) {
+      const int s = ro[p];
+      if (s < 0 || s >= ns) bad |= 1;
+      else {
+        if ((atomicOr (&seen[s >> 5], 1u << (s & 31)) >> (s & 31)) & 1u) bad |= 1;   // ns positions on ns samples: one sample left out is one sample twice
+        pos_out[(long) r * ns + s] = (unsigned short) p;
+        h = boot_mix (CONS_SALT + (u64) s);
+      }
+    }
+    total += h; run[q] = total;
+  }
+  u64 incl = total;
+  #pragma unroll
+  for (int o = 1; o < 64; o <<= 1) {
+    const u64 v = __shfl_up (incl, o);
+    if (lane >= o) incl += v;
+  }
+  if (lane == 63) wsum[wave] = incl;
+  __syncthreads ();
+  u64 base = incl - total;
+  for (int w = 0; w < wave; w++) base += wsum[w];
+  if (tid == 0) pre[0] = 0;
+  #pragma unroll
+  for (int q = 0; q < 4; q++) if (tid * 4 + q < ns) pre[tid * 4 + q + 1] = base + run[q];
+  for (int k = tid; k < n_rn; k += 1024) {
+    const TreeNode nd = rn[k];
+    if (!(nd.size >= 2 && nd.size <= ns && nd.first >= 0 && nd.first <= ns - nd.size)) bad |= 2;
+    else atomicMax (&far[nd.first], nd.first + nd.size);
+  }
+  __syncthreads ();
+  for (int k = wave; k < n_rn; k += 16) {               // a wavefront per node
+    const TreeNode nd = rn[k];
+    const bool ok = nd.size >= 2 && nd.size <= ns && nd.first >= 0 && nd.first <= ns - nd.size;
+    u64 kk = 0;
+    if (ok) {
+      const int end = nd.first + nd.size;
+      int m = 0;
+      for (int p = nd.first + 1 + lane; p < end; p += 64) m = max (m, far[p]);
+      for (int o = 32; o; o >>= 1) m = max (m, __shfl_xor (m, o));
+      if (m > end) bad |= 4;                            // a node that starts inside this one ends behind it
+      kk = (u64) nd.size << CONS_KEY_BITS | ((pre[end] - pre[nd.first]) & key_mask);
+    }
+    if (lane == 0) { key[off + k] = kk; val[off + k] = (u32) (off + k); }
+  }
+  if (bad) { atomicOr (&rbad[r], bad); atomicOr (flags, bad); }
+}
+
+__global__ __launch_bounds__ (256)
+void cons_heads_kernel (const u64 *__restrict__ key, long n, u32 *__restrict__ head, int *__restrict__ cls, int *__restrict__ cnt)
+{
+  for (long i = blockIdx.x * (long) blockDim.x + threadIdx.x; i < n; i += (long) gridDim.x * blockDim.x) {
+    head[i] = (i == 0 || key[i] != key[i - 1]) ? 1u : 0u;
+    cls[i] = -1; cnt[i] = 0;
+  }
+}
+
+// (the run of sorted record i: the heads before it and its own, less one)
+__device__ __forceinline__ u32 cons_run (const u32 *__restrict__ head, const u32 *__restrict__ hex, long i) { return hex[i] + head[i] - 1u; }
+
+__global__ __launch_bounds__ (256)
+void cons_lead_kernel (long n, const u32 *__restrict__ head, const u32 *__restrict__ hex, const int *__restrict__ cls, u32 *__restrict__ lead, const int *__restrict__ flags)
+{
+  if (*(volatile const int *) flags != 0) return;
+  for (long i = blockIdx.x * (long) blockDim.x + threadIdx.x; i < n; i += (long) gridDim.x * blockDim.x)
+    if (cls[i] < 0) atomicMin (&lead[cons_run (head, hex, i)], (u32) i);
+}
+
+__global__ __launch_bounds__ (256)
+void cons_compare_kernel (ConsIn A, long n, const u32 *__restrict__ val, const u32 *__restrict__ head, const u32 *__restrict__ hex, const u32 *__restrict__ lead,
+                          int *__restrict__ cls, int *__restrict__ flags)
+{
+  if (*(volatile const int *) flags != 0) return;
+  const int lane = threadIdx.x & 63;
+  for (long i = (blockIdx.x * (long) blockDim.x + threadIdx.x) >> 6; i < n; i += ((long) gridDim.x * blockDim.x) >> 6) {   // a wavefront per record
+    if (cls[i] >= 0) continue;
+    const long L = lead[cons_run (head, hex, i)];
+    if (L == i) { if (lane == 0) cls[i] = (int) i; continue; }
+    if (L < 0 || L >= n) continue;                      // (not taken: an unsettled record put an index of its run there)
+    const int g = (int) val[i], gl = (int) val[L], r = A.rep_of (g), rl = A.rep_of (gl);
+    const TreeNode nd = A.node_of (g, r), ld = A.node_of (gl, rl);
+    bool equal = nd.size == ld.size;                    // (the key holds the size: taken)
+    if (equal) {
+      const int *const mem = A.members_of (rl, ld.first);
+      const unsigned short *const pos = A.pos + (long) r * A.ns;
+      int lo = CLD_MAX, hi = -1;
+      for (int t = lane; t < ld.size; t += 64) { const int v = pos[mem[t]]; lo = min (lo, v); hi = max (hi, v); }
+      for (int o = 32; o; o >>= 1) { lo = min (lo, __shfl_xor (lo, o)); hi = max (hi, __shfl_xor (hi, o)); }
+      equal = hi - lo + 1 == nd.size && lo == nd.first; // the leader's members lie side by side in this replicate's order, and there this node lies
+    }
+    if (lane == 0) { if (equal) cls[i] = (int) L; else atomicOr (flags + 1, 1); }
+  }
+}
+
+__global__ __launch_bounds__ (256)
+void cons_count_kernel (ConsIn A, long n, const u32 *__restrict__ val, const u32 *__restrict__ head, const u32 *__restrict__ hex, const int *__restrict__ cls,
+                        int *__restrict__ cnt, int *__restrict__ flags)
+{
+  if (*(volatile const int *) flags != 0) return;
+  for (long i = blockIdx.x * (long) blockDim.x + threadIdx.x; i < n; i += (long) gridDim.x * blockDim.x) {
+    const int L = cls[i];
+    if (L < 0 || L >= n) continue;                      // (not taken: the rounds settle every record)
+    const int r = A.rep_of ((int) val[i]);
+    const u32 run = cons_run (head, hex, i);
+    bool again = false;                                 // an earlier record of this replicate in this class: the replicate is counted there
+    for (long j = i - 1; j >= 0 && !again && cons_run (head, hex, j) == run && A.rep_of ((int) val[j]) == r; j--) again = cls[j] == L;
+    if (!again) atomicAdd (&cnt[L], 1);
+    if (L == i) atomicAdd (flags + 3, 1);
+  }
+}
+
+__global__ __launch_bounds__ (256)
+void cons_kept_kernel (ConsIn A, long n, const u32 *__restrict__ val, const int *__restrict__ cls, const int *__restrict__ cnt, int min_count,
+                       int *__restrict__ rep_count, int *__restrict__ kept, int *__restrict__ flags)
+{
+  if (*(volatile const int *) flags != 0) return;
+  for (long i = blockIdx.x * (long) blockDim.x + threadIdx.x; i < n; i += (long) gridDim.x * blockDim.x) {
+    const int L = cls[i];
+    if (L < 0 || L >= n) continue;
+    const int count = cnt[L];
+    if (rep_count) {
+      const int g = (int) val[i], r = A.rep_of (g);
+      rep_count[(long) r * (A.ns - 1) + (g - A.rep_off[r])] = count;
+    }
+    if (L == i && count >= min_count) {
+      const int slot = atomicAdd (flags + 2, 1);        // (any order: cons_order_kernel ranks them by a total order)
+      if (slot < A.ns - 1) kept[slot] = (int) i;
+    }
+  }
+}
+
+__global__ __launch_bounds__ (256)
+void cons_info_kernel (ConsIn A, const u32 *__restrict__ val, const int *__restrict__ cnt, const int *__restrict__ kept, ConsKept *__restrict__ info, const int *__restrict__ flags)
+{
+  if (*(volatile const int *) flags != 0) return;
+  const int lane = threadIdx.x & 63, slot = (blockIdx.x * 256 + threadIdx.x) >> 6, nk = min (((volatile const int *) flags)[2], A.ns - 1);
+  if (slot >= nk) return;
+  const int i = kept[slot], g = (int) val[i], r = A.rep_of (g);
+  const TreeNode nd = A.node_of (g, r);
+  const int *const mem = A.members_of (r, nd.first);
+  int m = CLD_MAX;
+  for (int t = lane; t < nd.size; t += 64) m = min (m, mem[t]);
+  for (int o = 32; o; o >>= 1) m = min (m, __shfl_xor (m, o));
+  if (lane == 0) info[slot] = ConsKept {nd.size, m, cnt[i], r, nd.first, 0};
+}
+
+__global__ __launch_bounds__ (1024)
+void cons_order_kernel (const ConsKept *__restrict__ info, ConsKept *__restrict__ sorted, int *__restrict__ leafpar, int ns, const int *__restrict__ flags)
+{
+  __shared__ u32 keys[CLD_MAX];
+  if (*(volatile const int *) flags != 0) return;
+  const int tid = threadIdx.x, nk = min (((volatile const int *) flags)[2], ns - 1);
+  for (int s = tid; s < ns; s += 1024) leafpar[s] = CLD_MAX;
+  for (int x = tid; x < nk; x += 1024) keys[x] = (u32) info[x].size << 12 | (u32) info[x].minm;
+  __syncthreads ();
+  for (int x = tid; x < nk; x += 1024) {
+    const u32 mine = keys[x];
+    int rank = 0;
+    for (int j = 0; j < nk; j++) rank += (keys[j] < mine || (keys[j] == mine && j < x)) ? 1 : 0;
+    sorted[rank] = info[x];
+  }
+}
+
+__global__ __launch_bounds__ (256)
+void cons_parent_kernel (ConsIn A, const ConsKept *__restrict__ sorted, int *__restrict__ kpar, int *__restrict__ leafpar, const int *__restrict__ flags)
+{
+  if (*(volatile const int *) flags != 0) return;
+  const int lane = threadIdx.x & 63, j = (blockIdx.x * 256 + threadIdx.x) >> 6, nk = min (((volatile const int *) flags)[2], A.ns - 1);
+  if (j >= nk) return;
+  const ConsKept me = sorted[j];
+  const int *const mem = A.members_of (me.rep, me.first);
+  for (int t = lane; t < me.size; t += 64) atomicMin (&leafpar[mem[t]], j);   // the smallest kept class that holds the sample
+  int par = -1;
+  for (int b = j + 1; b < nk && par < 0; b += 64) {     // classes of the same size are disjoint from this one: the first larger one that holds its smallest member
+    bool hit = false;
+    if (b + lane < nk) {
+      const ConsKept c = sorted[b + lane];
+      if (c.size > me.size) { const int p = A.pos[(long) c.rep * A.ns + me.minm]; hit = p >= c.first && p < c.first + c.size; }
+    }
+    const u64 hits = __ballot (hit);
+    if (hits) par = b + __ffsll ((long long) hits) - 1;
+  }
+  if (lane == 0) kpar[j] = par;
+}
+
+__global__ __launch_bounds__ (1024)
+void cons_layout_kernel (const ConsKept *__restrict__ sorted, const int *__restrict__ kpar, const int *__restrict__ leafpar, int ns, ConsNode *__restrict__ nodes,
+                         int *__restrict__ order, int *__restrict__ flags)
+{
+  // all of them by node or by sample; CONS_NONE: no parent
+  __shared__ unsigned short par[CLD_MAX], siz[CLD_MAX], cur[CLD_MAX], fst[CLD_MAX], top[CLD_MAX], lpar[CLD_MAX], loff[CLD_MAX];
+  if (*(volatile const int *) flags != 0) return;
+  const int tid = threadIdx.x, n_kept = ((volatile const int *) flags)[2];
+  if (n_kept > ns - 1) { if (tid == 0) flags[4] = 1; return; }
+  const int nk = n_kept;
+  for (int x = tid; x < nk; x += 1024) { par[x] = kpar[x] < 0 ? CONS_NONE : (unsigned short) kpar[x]; siz[x] = (unsigned short) sorted[x].size; cur[x] = 0; fst[x] = 0; }
+  for (int t = tid; t < ns; t += 1024) { top[t] = CONS_NONE; lpar[t] = leafpar[t] >= nk ? CONS_NONE : (unsigned short) leafpar[t]; loff[t] = 0; }
+  __syncthreads ();
+  // The nodes whose smallest member is t are nested; the largest of them, top[t], is the one whose parent starts elsewhere.
+  // Every other one is its parent's first child, and so is the sample t in the smallest of them: cur[] of a node starts
+  // behind its first child.
+  for (int x = tid; x < nk; x += 1024) {
+    const int P = kpar[x];
+    if (P < 0 || sorted[P].minm != sorted[x].minm) top[sorted[x].minm] = (unsigned short) x;
+    else cur[P] = siz[x];
+  }
+  __syncthreads ();
+  for (int t = tid; t < ns; t += 1024) if (top[t] != CONS_NONE && lpar[t] != CONS_NONE) cur[lpar[t]] = 1;   // (lpar[t] is a node: top[t] holds t)
+  __syncthreads ();
+  if (tid == 0) {
+    int roots = 0;                                      // the samples in ascending order: what starts at t takes the next place in its parent
+    for (int t = 0; t < ns; t++) {
+      const int x = top[t];
+      if (x != CONS_NONE) {
+        const int P = par[x];
+        if (P == CONS_NONE) { fst[x] = (unsigned short) roots; roots += siz[x]; } else { fst[x] = cur[P]; cur[P] = (unsigned short) (cur[P] + siz[x]); }
+      } else {
+        const int P = lpar[t];
+        if (P == CONS_NONE) { loff[t] = (unsigned short) roots; roots += 1; } else { loff[t] = cur[P]; cur[P] = (unsigned short) (cur[P] + 1); }
+      }
+    }
+    for (int x = nk - 1; x >= 0; x--)                   // a parent comes behind its children: from the back, its first is final
+      if (par[x] != CONS_NONE) fst[x] = (unsigned short) (fst[x] + fst[par[x]]);
+  }
+  __syncthreads ();
+  for (int x = tid; x < nk; x += 1024) nodes[x] = ConsNode {kpar[x], sorted[x].count, (int) fst[x], (int) siz[x]};
+  for (int t = tid; t < ns; t += 1024) {
+    const int at = (lpar[t] == CONS_NONE ? 0 : (int) fst[lpar[t]]) + (int) loff[t];
+    if (at < ns) order[at] = t;
+  }
+}
+
+extern "C" long tjamd_consensus_tree (tjamd_counter *c, const tjamd_tree_node *d_rep_nodes, const int *d_rep_order, const int *h_rep_n_nodes, int n_samples, int n_replicates,
+                                      int min_count, tjamd_consensus_node *d_nodes, int *d_order, int *d_rep_count, long *h_n_classes)
+{
+  static const char *fn = "tjamd_consensus_tree";
+  if (!c) return -set_err (TJAMD_ERR_ARG, "%s: null counter", fn);
+  if (!d_rep_order) return -set_err (TJAMD_ERR_ARG, "%s: null d_rep_order", fn);
+  if (!h_rep_n_nodes) return -set_err (TJAMD_ERR_ARG, "%s: null h_rep_n_nodes", fn);
+  if (!d_order) return -set_err (TJAMD_ERR_ARG, "%s: null d_order", fn);
+  if (n_samples < 1 || n_samples > CLD_MAX) return -set_err (TJAMD_ERR_ARG, "%s: n_samples %d outside 1..4096", fn, n_samples);
+  if (n_replicates < 1 || n_replicates > 4096) return -set_err (TJAMD_ERR_ARG, "%s: n_replicates %d outside 1..4096", fn, n_replicates);
+  if (!d_nodes && n_samples > 1) return -set_err (TJAMD_ERR_ARG, "%s: null d_nodes", fn);
+  long n = 0;                                           // the clades of the call
+  for (int r = 0; r < n_replicates; r++) {
+    if (h_rep_n_nodes[r] < 0 || h_rep_n_nodes[r] > n_samples - 1)
+      return -set_err (TJAMD_ERR_ARG, "%s: replicate %d has %d nodes, outside 0..n_samples - 1 = %d", fn, r, h_rep_n_nodes[r], n_samples - 1);
+    if (h_rep_n_nodes[r] > 0 && !d_rep_nodes) return -set_err (TJAMD_ERR_ARG, "%s: null d_rep_nodes", fn);
+    n += h_rep_n_nodes[r];
+  }
+  if (min_count > n_replicates || 2l * min_count <= n_replicates)
+    return -set_err (TJAMD_ERR_ARG, "%s: min_count %d outside %d..%d (more than half of the %d replicates)", fn, min_count, n_replicates / 2 + 1, n_replicates, n_replicates);
+  if (tjamd_device_count () <= 0) return -set_err (TJAMD_ERR_NO_DEVICE, "%s: TJAMD_ERR_NO_DEVICE: no HIP device visible (the clades are classed on the device; no CPU fallback)", fn);
+  Stage st (c, T_CONSENSUS_TREE);                       // (a refused call leaves no timing behind)
+  if (hipSetDevice (c->device) != hipSuccess) return -set_err (TJAMD_ERR_HIP, "hipSetDevice failed");
+  const int ns = n_samples, R = n_replicates;
+  int rc;
+  if (ns == 1) {                                        // one sample: no clade, no kernel
+    if (hipMemsetAsync (d_order, 0, sizeof (int), c->stream) != hipSuccess) return -set_err (TJAMD_ERR_HIP, "%s: memset failed", fn);
+    rc = read_back (c, fn, nullptr, nullptr, 0);
+    if (rc) return -rc;
+    if (h_n_classes) *h_n_classes = 0;
+    return 0;
+  }
+  std::vector<int> h_rep ((size_t) 2 * R + 1);          // the counts, and where each replicate's records start
+  for (int r = 0, at = 0; r < R; r++) { h_rep[r] = h_rep_n_nodes[r]; h_rep[R + r] = at; at += h_rep_n_nodes[r]; }
+  h_rep[2 * R] = (int) n;
+  const size_t n1 = (size_t) std::max (n, 1l);
+  ScratchCut cut;
+  u64 *key[2]; u32 *val[2], *head, *hex, *lead; int *cls, *cnt, *reps, *rbad, *kept, *kpar, *flags; unsigned short *pos; ConsKept *info;
+  cut.take (key[0], n1); cut.take (key[1], n1); cut.take (val[0], n1); cut.take (val[1], n1); cut.take (head, n1); cut.take (hex, n1); cut.take (lead, n1);
+  cut.take (cls, n1); cut.take (cnt, n1); cut.take (pos, (size_t) R * ns); cut.take (reps, (size_t) 2 * R + 1); cut.take (rbad, (size_t) R);
+  cut.take (kept, (size_t) ns); cut.take (kpar, (size_t) 2 * ns); cut.take (info, (size_t) 2 * ns);
+  rc = commit_with_flags (cut, c, fn, flags);
+  if (!rc) rc = reserve_sort (c, (long) n1, (long) n1);
+  if (rc) return -rc;
+  ConsKept *const sorted = info + ns; int *const leafpar = kpar + ns;
+  if (hipMemsetAsync (rbad, 0, (size_t) R * sizeof (int), c->stream) != hipSuccess) return -set_err (TJAMD_ERR_HIP, "%s: memset failed", fn);
+  if (hipMemcpyAsync (reps, h_rep.data (), h_rep.size () * sizeof (int), hipMemcpyHostToDevice, c->stream) != hipSuccess) return -set_err (TJAMD_ERR_HIP, "%s: copy failed", fn);
+  ConsIn A;
+  A.rep_nodes = (const TreeNode *) d_rep_nodes; A.rep_order = d_rep_order; A.rep_n = reps; A.rep_off = reps + R; A.pos = pos; A.ns = ns; A.R = R;
+  const u64 key_mask = (1ull << c->consensus_key_bits) - 1ull;
+  const unsigned wave_grid = (unsigned) std::max<long> (1, std::min<long> ((n + 3) / 4, 16l * c->n_cu)), kept_grid = (unsigned) ((ns - 1 + 3) / 4);
+  u32 h_flags[5] = {0, 0, 0, 0, 0};
+  st.begin ();
+  hipLaunchKernelGGL (cons_records_kernel, dim3 ((unsigned) R), dim3 (1024), 0, c->stream, A, key_mask, pos, key[0], val[0], rbad, flags);
+  if (n > 0) {
+    rc = kv_sort (c, key, val, n, 64);
+    if (rc) return -rc;
+    hipLaunchKernelGGL (cons_heads_kernel, dim3 (grid_for (n)), dim3 (256), 0, c->stream, (const u64 *) key[0], n, head, cls, cnt);
+    rc = exclusive_scan (c, head, hex, n, nullptr, (u32 *) c->scan_tmp.p, c->scan_tmp.cap / 4);
+    if (rc) return -rc;
+    for (long round = 0; ; round++) {                   // a round settles the leader of every run that has an unsettled record: n rounds at the very most
+      if (round > n) return -set_err (TJAMD_ERR_STATE, "%s: the rounds did not end", fn);
+      if (hipMemsetAsync (flags + 1, 0, sizeof (int), c->stream) != hipSuccess || hipMemsetAsync (lead, 0xFF, (size_t) n * sizeof (u32), c->stream) != hipSuccess)
+        return -set_err (TJAMD_ERR_HIP, "%s: memset failed", fn);
+      hipLaunchKernelGGL (cons_lead_kernel, dim3 (grid_for (n)), dim3 (256), 0, c->stream, n, (const u32 *) head, (const u32 *) hex, (const int *) cls, lead, (const int *) flags);
+      hipLaunchKernelGGL (cons_compare_kernel, dim3 (wave_grid), dim3 (256), 0, c->stream, A, n, (const u32 *) val[0], (const u32 *) head, (const u32 *) hex, (const u32 *) lead, cls, flags);
+      st.end ();
+      rc = read_back (c, fn, flags, h_flags, 2);
+      if (rc) return -rc;
+      if (h_flags[0] || !h_flags[1]) break;
+    }
+    hipLaunchKernelGGL (cons_count_kernel, dim3 (grid_for (n)), dim3 (256), 0, c->stream, A, n, (const u32 *) val[0], (const u32 *) head, (const u32 *) hex, (const int *) cls, cnt, flags);
+    hipLaunchKernelGGL (cons_kept_kernel, dim3 (grid_for (n)), dim3 (256), 0, c->stream, A, n, (const u32 *) val[0], (const int *) cls, (const int *) cnt, min_count, d_rep_count, kept, flags);
+    hipLaunchKernelGGL (cons_info_kernel, dim3 (kept_grid), dim3 (256), 0, c->stream, A, (const u32 *) val[0], (const int *) cnt, (const int *) kept, info, (const int *) flags);
+  }
+  hipLaunchKernelGGL (cons_order_kernel, dim3 (1), dim3 (1024), 0, c->stream, (const ConsKept *) info, sorted, leafpar, ns, (const int *) flags);
+  if (n > 0) hipLaunchKernelGGL (cons_parent_kernel, dim3 (kept_grid), dim3 (256), 0, c->stream, A, (const ConsKept *) sorted, kpar, leafpar, (const int *) flags);
+  hipLaunchKernelGGL (cons_layout_kernel, dim3 (1), dim3 (1024), 0, c->stream, (const ConsKept *) sorted, (const int *) kpar, (const int *) leafpar, ns, (ConsNode *) d_nodes, d_order, flags);
+  st.end ();
+  rc = read_back (c, fn, flags, h_flags, 5);
+  if (rc) return -rc;
+  if (h_flags[0]) {                                     // the smallest refused replicate, its first broken rule in the header's order
+    std::vector<int> h_bad ((size_t) R, 0);
+    rc = read_back (c, fn, rbad, h_bad.data (), (size_t) R);
+    if (rc) return -rc;
+    for (int r = 0; r < R; r++) {
+      const int bad = h_bad[r];
+      if (bad & 1) return -set_err (TJAMD_ERR_ARG, "%s: the order of replicate %d is not a permutation of 0 .. n_samples - 1", fn, r);
+      if (bad & 2) return -set_err (TJAMD_ERR_ARG, "%s: a node of replicate %d has size < 2, first < 0 or first + size above n_samples %d", fn, r, ns);
+      if (bad & 4) return -set_err (TJAMD_ERR_ARG, "%s: two nodes of replicate %d cross (they overlap and neither contains the other)", fn, r);
+    }
+    return -set_err (TJAMD_ERR_STATE, "%s: an error word without a replicate", fn);
+  }
+  if (h_flags[4]) return -set_err (TJAMD_ERR_STATE, "%s: %u kept classes on %d samples", fn, h_flags[2], ns);
+  st.done ();
+  if (h_n_classes) *h_n_classes = (long) h_flags[3];
+  return (long) h_flags[2];
+}
+extern "C" double tjamd_last_consensus_tree_ms (tjamd_counter *c) { return c ? c->timer[T_CONSENSUS_TREE].ms (c->device) : -1.0; }
