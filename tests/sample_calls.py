@@ -1,5 +1,5 @@
-"""One caller per entry of the sample-comparison layer (N14-N19: distances, bootstrap weights, weighted distances, linkage,
-clusters, group sites, tree, clade sites, agglomerate, clade support), in the style of tests/bounds_calls.py: every output in a
+"""One caller per entry of the sample-comparison layer (N14-N21: distances, bootstrap weights, weighted distances, linkage,
+clusters, group sites, tree, clade sites, agglomerate, clade support, replicate trees, consensus tree), in the style of tests/bounds_calls.py: every output in a
 guarded buffer of exactly the size the header asks for, every const input frozen, guards and inputs checked before the caller
 returns; and the bytes that each of these entries cuts from the counter's scratch block, restated from hopo_device.hip.
 tests/test_sample_reuse.py calls through these.  An entry of this layer that cuts scratch gets a caller and a line here.
@@ -14,6 +14,7 @@ from tests.guarded import frozen
 
 DIST, LINK, NODE = tj.SAMPLE_DISTANCE_DTYPE, tj.LINK_DTYPE, tj.TREE_NODE_DTYPE
 CALL, GSITE, MARK = tj.GROUP_CALL_DTYPE, tj.GROUP_SITE_DTYPE, tj.GROUP_MARK_DTYPE
+CNODE = tj.CONSENSUS_NODE_DTYPE
 UNSET = -77                              # what a scalar output holds before the call
 
 
@@ -110,13 +111,39 @@ def call_clade_support(c, nd, n_nodes, od, ns, rnd, rod, counts):
     return Result(rc, outs, ms=c.last_clade_support_ms())
 
 
+def call_replicate_trees(c, dd, ns, n_rep, metric, min_both, linkage):
+    """dd: device bytes of tjamd_sample_distance [n_rep, ns, ns]"""
+    outs = _buffers({"d_rep_links": n_rep * (ns - 1) * LINK.itemsize, "d_rep_nodes": n_rep * (ns - 1) * NODE.itemsize, "d_rep_order": n_rep * ns * 4}, ())
+    n_nodes, n_rounds = (C.c_int * n_rep)(*[UNSET] * n_rep), (C.c_int * n_rep)(*[UNSET] * n_rep)
+    with frozen(dd):
+        rc = tj.lib().tjamd_replicate_trees(c._h, _p(dd), ns, n_rep, metric, min_both, linkage, _p(outs["d_rep_links"]), _p(outs["d_rep_nodes"]), _p(outs["d_rep_order"]),
+                                            n_nodes, n_rounds)
+        _checked(outs)
+    return Result(rc, outs, ms=c.last_replicate_trees_ms(), n_nodes=tuple(n_nodes), n_rounds=tuple(n_rounds))
+
+
+def call_consensus_tree(c, rnd, rod, counts, ns, min_count):
+    """rnd, rod: device bytes of tjamd_tree_node [n_rep, ns - 1] and int32 [n_rep, ns]; counts: the nodes of every replicate"""
+    n_rep = len(counts)
+    outs = _buffers({"d_nodes": (ns - 1) * CNODE.itemsize, "d_order": ns * 4, "d_rep_count": n_rep * (ns - 1) * 4}, ())
+    h_counts, n_classes = (C.c_int * n_rep)(*counts), C.c_long(UNSET)
+    with frozen(rnd, rod):
+        rc = tj.lib().tjamd_consensus_tree(c._h, _p(rnd), _p(rod), h_counts, ns, n_rep, min_count, _p(outs["d_nodes"]), _p(outs["d_order"]), _p(outs["d_rep_count"]),
+                                           C.byref(n_classes))
+        _checked(outs)
+    assert list(h_counts) == list(counts)
+    return Result(rc, outs, ms=c.last_consensus_tree_ms(), n_classes=n_classes.value)
+
+
 # ---- the scratch that each entry cuts ---------------------------------------------------------------------------------------
 # ScratchCut of hopo_device.hip: the pieces of a call in the order they lie in the block, each on a 256-byte boundary, the first
 # at offset 0.  n_cu: the device's compute units (256 on an MI355X): a distance call aims at 4 n_cu workgroups, or at dist_blocks
 # where the counter was made under TATAJUBA_AMD_DISTANCE_BLOCKS, as every counter of tests/test_sample_reuse.py is.
-# LINK_SMALL = CLD_SMALL = 64.
+# LINK_SMALL = CLD_SMALL = 64.  REP_FLAGS: the flag words tjamd_replicate_trees keeps per replicate of the call; REP_SCRATCH_CAP:
+# the bytes its groups of replicates are sized for; PIECES: what one ScratchCut holds, the flag words included.
 
 SDIST_CELLS, SDISTW_BATCH, SMALL = 2048, 2, 64
+REP_FLAGS, REP_SCRATCH_CAP, PIECES = 8, 1 << 30, 16
 
 
 def _r(nbytes):
@@ -173,7 +200,36 @@ def cut_support(n_nodes, n_rep):
     return _layout([("cnt", 4 * n_nodes), ("rep_n", 4 * n_rep), ("flags", 256)])
 
 
+def rep_group(ns, n_rep, group=0, small_form=True):
+    """-> (the bytes `per` of one replicate's pieces, the replicates G of a group); group: TATAJUBA_AMD_TREES_GROUP, 0 without it"""
+    ld = (ns + 1) & ~1
+    ldc = (ld + 64 + 63) & ~63
+    if ns <= SMALL and small_form:
+        return 0, min(n_rep, group) if group else n_rep
+    per = ns * ld * 8 + 2 * ldc * 4 + 2 * ns * 16 + ns * 4 + (ns - 1) * 16
+    return per, min(n_rep, group) if group else max(1, min(n_rep, REP_SCRATCH_CAP // per))
+
+
+def cut_replicate_trees(ns, n_rep, group=0, small_form=True):
+    """comp, size, rowbest, edges, pairs, links, keys of a group of replicates (comp and size ldc ints a replicate: ld + 64 rounded
+    up to 64), the REP_FLAGS words of every replicate of the call, flags: nothing but the last two in the one-workgroup form"""
+    ld = (ns + 1) & ~1
+    ldc = (ld + 64 + 63) & ~63
+    G = 0 if ns <= SMALL and small_form else rep_group(ns, n_rep, group, small_form)[1]
+    return _layout([("comp", 4 * G * ldc), ("size", 4 * G * ldc), ("rowbest", 16 * G * ns), ("edges", 16 * G * ns), ("pairs", 4 * G * ns), ("links", 16 * G * (ns - 1)),
+                    ("keys", 8 * G * ns * ld), ("rflags", 4 * n_rep * REP_FLAGS), ("flags", 256)])
+
+
+def cut_consensus(n_clades, ns, n_rep):
+    """the records (two buffers of keys and of values, head, hex, lead, cls, cnt: at least one record), the samples' positions,
+    the counts and offsets of the replicates, their error words, the kept classes, flags: 16 pieces, as many as a cut holds"""
+    n1 = max(n_clades, 1)
+    return _layout([("key0", 8 * n1), ("key1", 8 * n1), ("val0", 4 * n1), ("val1", 4 * n1), ("head", 4 * n1), ("hex", 4 * n1), ("lead", 4 * n1), ("cls", 4 * n1), ("cnt", 4 * n1),
+                    ("pos", 2 * n_rep * ns), ("reps", 4 * (2 * n_rep + 1)), ("rbad", 4 * n_rep), ("kept", 4 * ns), ("kpar", 4 * 2 * ns), ("info", 24 * 2 * ns), ("flags", 256)])
+
+
 def _layout(pieces):
+    assert len(pieces) <= PIECES
     out, at = [], 0
     for name, nbytes in pieces:
         out.append((name, at, nbytes))

@@ -73,10 +73,10 @@ def dev_consensus(counter, reps, ns, min_count, null=()):
         assert 0 <= rc <= ns - 1 and (counter.last_consensus_tree_ms() > 0 if ns > 1 else counter.last_consensus_tree_ms() == -1.0)
         raw = {k: b.payload.cpu().numpy() for k, b in bufs.items()}
         assert (raw["nodes"][rc * 16:] == payload_pattern(bufs["nodes"].nbytes)[rc * 16:]).all()   # entries from the return value on are not written
-        rep_count = []
+        rep_count, pattern = [], payload_pattern(bufs["rep_count"].nbytes)
         for r in range(R):
             lo, hi = (r * (ns - 1) + (0 if "rep_count" in null else counts[r])) * 4, (r + 1) * (ns - 1) * 4
-            assert (raw["rep_count"][lo:hi] == payload_pattern(bufs["rep_count"].nbytes)[lo:hi]).all(), r
+            assert (raw["rep_count"][lo:hi] == pattern[lo:hi]).all(), r
             rep_count.append(raw["rep_count"][r * (ns - 1) * 4: (r * (ns - 1) + counts[r]) * 4].copy().view(np.int32))
         runs.append({"nodes": raw["nodes"][: rc * 16].copy().view(CNODE), "order": raw["order"].copy().view(np.int32), "rep_count": rep_count,
                      "n_classes": None if "classes" in null else n_classes.value})

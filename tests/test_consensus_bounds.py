@@ -6,10 +6,11 @@ records and the four kept classes a block of wavefronts takes (256 to 258 sample
 records and the workgroups of 1024 that order and lay out the kept classes (1024 to 1026), and the limit of 4096 samples with
 four positions a thread (4095 and 4096).
 
-The replicates are one tree under different leaf orders, so the answer is known without the restatement, whose frozensets are
-too slow for 4096 samples: the consensus is that tree, every count is the number of replicates, a node's interval starts with
-its smallest member, and its parent is the tree's.  A caterpillar, the most members a call can hold, runs once at each limit.
-Up to 258 samples the restatement is compared as well, on replicates that disagree."""
+The replicates are one tree under different leaf orders, so the answer is known without the restatement, whose frozensets
+take seconds at 4096 samples (6.5 s for five replicates: affordable once, not at fifteen sizes; tests/test_consensus_limits.py
+runs it there, on replicates that disagree): the consensus is that tree, every count is the number of replicates, a node's
+interval starts with its smallest member, and its parent is the tree's.  A caterpillar, the most members a call can hold, runs
+once at each limit.  Up to 258 samples the restatement is compared as well, on replicates that disagree."""
 import numpy as np
 import pytest
 

@@ -39,11 +39,10 @@ def _torch():
 def dev_rep_trees(counter, dist, metric, min_both, linkage, null_links=False):
     """two calls of tjamd_replicate_trees on dist [R, ns, ns] -> per replicate {"links", "n_rounds", "nodes", "order"} as numpy;
     or, when the call is refused, (negative code, message, the guarded buffers).  Entries past a replicate's n_nodes must
-    hold what the buffer held before the call."""
+    hold what the buffer held before the call.  dist may be (device bytes of the matrices, R, ns), for an input laid out on the device."""
     torch = _torch()
     L = tj.lib()
-    R, ns = dist.shape[:2]
-    dd = _dev(dist)
+    dd, R, ns = dist if isinstance(dist, tuple) else (_dev(dist),) + dist.shape[:2]
     runs = []
     for _ in range(2):
         bufs = {"links": GuardedDevice(R * (ns - 1) * LINK.itemsize), "nodes": GuardedDevice(R * (ns - 1) * NODE.itemsize), "order": GuardedDevice(R * ns * 4)}
@@ -62,13 +61,14 @@ def dev_rep_trees(counter, dist, metric, min_both, linkage, null_links=False):
             return rc, err, bufs
         assert rc == R and (ns == 1 or counter.last_replicate_trees_ms() > 0)
         raw = {k: b.payload.cpu().numpy() for k, b in bufs.items()}
+        pattern = {k: payload_pattern(bufs[k].nbytes) for k in ("links", "nodes")}
         out = []
         for r in range(R):
             n = counts[r]
             assert 0 <= n <= ns - 1 and 0 <= rounds[r] <= n, (r, n, rounds[r])
             for k in ("links", "nodes"):                                                # entries from n_nodes on are not written
                 lo, hi = (r * (ns - 1) + (0 if null_links and k == "links" else n)) * 16, (r + 1) * (ns - 1) * 16
-                assert (raw[k][lo:hi] == payload_pattern(bufs[k].nbytes)[lo:hi]).all(), (k, r, n)
+                assert (raw[k][lo:hi] == pattern[k][lo:hi]).all(), (k, r, n)
             at = r * (ns - 1) * 16
             out.append({"links": raw["links"][at: at + n * 16].copy().view(LINK), "nodes": raw["nodes"][at: at + n * 16].copy().view(NODE),
                         "order": raw["order"][r * ns * 4: (r + 1) * ns * 4].copy().view(np.int32), "n_rounds": rounds[r]})

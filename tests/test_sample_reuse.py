@@ -1,6 +1,8 @@
-"""Scratch carried between the calls of the sample-comparison layer (N14-N19).  Every one of its entries cuts its scratch from one
+"""Scratch carried between the calls of the sample-comparison layer (N14-N21).  Every one of its entries cuts its scratch from one
 block of the counter, from offset 0, and the layouts differ: the two distance entries put their error words first, the entries of
-the trees put their flag words last, where an earlier, larger call had its data.  A kernel that read a word this call had not
+the trees put their flag words last, where an earlier, larger call had its data; tjamd_replicate_trees (N20) cuts eight pieces
+per group of replicates and keeps eight flag words per replicate in front of the call's, and tjamd_consensus_tree (N21) cuts
+sixteen pieces, as many as a cut holds.  A kernel that read a word this call had not
 written (a count that is added to, an error word, the round counters, the padding column of the key matrix) would pass every test
 that takes a fresh counter.  tests/test_counter_reuse.py does this for the layers up to N12; here, on one counter per test:
 
@@ -16,7 +18,9 @@ input is frozen (tests/sample_calls.py).
 The problems.  large: 1025 samples (rows of 1026 keys: a padding column; a second trip of the 1024-thread kernels), 600 sites (tiles
 of edge 32 over sliced sites: `partial` in use), 5 replicates (two full batches and one more).  small: 67 samples, 90 sites, 3
 replicates (rows of 68; just past the 64 samples of the one-workgroup forms).  tiny: 9 samples, 40 sites (the one-workgroup forms:
-no scratch but the flags; tiles of edge 16).
+no scratch but the flags; tiles of edge 16).  The replicates of tjamd_replicate_trees are the weighted matrices of the problem, under
+all three linkages; those of tjamd_consensus_tree are one fabricated tree under 1 + samples / 64 transpositions a replicate
+(tests/test_consensus_cabi.py), since the bootstrap trees of random sites share no clade: test_the_consensus_inputs_are_worth_a_consensus.
 
 The poisons, both through the public API, their return codes alone checked:
   P1  tjamd_sample_distances on 16384 sites x 130 samples, every ref_length 2^31 - 1 and every genotype 0: `lens` is 0x7fffffff in
@@ -28,6 +32,7 @@ compute units of an MI355X, the large problem's 561 tile pairs leave no room for
 unweighted call has 5 slices and its weighted call 2, `partial` is in use, and no cut depends on the device.  SMALL_CUTS lists
 what every call on a small problem then cuts; test_the_poisons_cover_the_small_cuts holds the list to the formulas of
 tests/sample_calls.py and the largest cut to half of what either poison covers."""
+import functools
 import os
 
 import numpy as np
@@ -39,12 +44,15 @@ from tests.bounds_calls import dev
 from tests.test_agglomerate_cabi import AVERAGE, COMPLETE, restate_sample_agglomerate
 from tests.test_bootstrap_cabi import restate_bootstrap_weights, restate_clade_support, restate_sample_distances_weighted
 from tests.test_clades_cabi import restate_clade_sites, restate_linkage_tree
+from tests.test_consensus_cabi import fabricate_replicates, majority, pack, restate_consensus
 from tests.test_distances_cabi import fabricate, restate_sample_distances
 from tests.test_groups_cabi import restate_group_sites
 from tests.test_linkage_cabi import DIFFER, LENGTH, restate_linkage_clusters, restate_sample_linkage
+from tests.test_replicate_trees_cabi import LINKAGES, SINGLE, restate_replicate_trees
 
 ERR_ARG = 3
 DIST, LINK, NODE = sc.DIST, sc.LINK, sc.NODE
+UNSET = sc.UNSET
 SHAPES = {"large": (1025, 600, 5), "small": (67, 90, 3), "tiny": (9, 40, 3)}       # samples, sites, replicates
 SMALLS = ("small", "tiny")
 POISON_SITES, POISON_SAMPLES = 16384, 130
@@ -74,6 +82,15 @@ SMALL_CUTS = {
     ("tjamd_clade_sites", "tiny"): 768,
     ("tjamd_clade_support", "small"): 1024,                # cnt 264 -> 512, rep_n 256, flags
     ("tjamd_clade_support", "tiny"): 768,
+    # three replicates: comp and size 3 x 192 ints each, rowbest and edges 3 x 67 x 16 -> 3 328 each, pairs 804 -> 1 024, links
+    # 3 x 66 x 16 -> 3 328, keys 3 x 67 x 68 x 8 = 109 344 -> 109 568, the replicates' flags 3 x 8 ints -> 256, flags
+    ("tjamd_replicate_trees", "small"): 125696,
+    ("tjamd_replicate_trees", "tiny"): 512,                # the replicates' flags and the call's
+    ("tjamd_replicate_trees", "tiny", "rounds"): 7680,     # comp and size 3 x 128 ints each, rowbest, edges 512, pairs, links 512, keys 2 160 -> 2 304, 256, 256
+    # 198 records: two of keys 1 584 -> 1 792, seven of ints 792 -> 1 024, pos 402 -> 512, reps, rbad 256, kept 268 -> 512, kpar 536
+    # -> 768, info 134 x 24 = 3 216 -> 3 328, flags
+    ("tjamd_consensus_tree", "small"): 16640,
+    ("tjamd_consensus_tree", "tiny"): 4352,                # 24 records: nine pieces of 256, pos, reps, rbad, kept, kpar 256 each, info 432 -> 512, flags
 }
 
 
@@ -89,8 +106,11 @@ def small_cut_formulas():
         out["tjamd_linkage_clusters", name] = out["tjamd_linkage_tree", name] = sc.cut_flags_alone()
         out["tjamd_group_sites", name] = out["tjamd_clade_sites", name] = sc.cut_marks(ns, n_sites)
         out["tjamd_clade_support", name] = sc.cut_support(ns - 1, n_rep)
+        out["tjamd_replicate_trees", name] = sc.cut_replicate_trees(ns, n_rep)
+        out["tjamd_consensus_tree", name] = sc.cut_consensus(sum(consensus_input(name)[2]), ns, n_rep)
     out["tjamd_sample_linkage", "tiny", "rounds"] = sc.cut_linkage(9, small_form=False)
     out["tjamd_sample_agglomerate", "tiny", "rounds"] = sc.cut_agglomerate(9, small_form=False)
+    out["tjamd_replicate_trees", "tiny", "rounds"] = sc.cut_replicate_trees(9, SHAPES["tiny"][2], small_form=False)
     return out
 
 
@@ -110,9 +130,19 @@ def test_the_poisons_cover_the_small_cuts():
     assert first == 4608 + 2 * 16640 == 37888 and last == first + ns * (ns + 1) * 8
     assert first <= 64 << 10 and last > largest and 2 * largest <= last - first
     # the flag words of the entries of the trees fall inside an earlier, larger call's data
-    for entry in ("tjamd_sample_linkage", "tjamd_sample_agglomerate", "tjamd_clade_support"):
+    for entry in ("tjamd_sample_linkage", "tjamd_sample_agglomerate", "tjamd_clade_support", "tjamd_replicate_trees", "tjamd_consensus_tree"):
         at = sc.piece(cuts[entry, "small"], "flags")[0]
         assert 256 <= at < largest, entry
+    # ... and so do the flag words that tjamd_replicate_trees keeps per replicate, and the words that tjamd_consensus_tree clears or
+    # fills per call: the replicates' error words, their counts and offsets
+    for entry, name in (("tjamd_replicate_trees", "rflags"), ("tjamd_consensus_tree", "rbad"), ("tjamd_consensus_tree", "reps")):
+        at = sc.piece(cuts[entry, "small"], name)[0]
+        assert 256 <= at < largest, (entry, name)
+    assert sc.piece(cuts["tjamd_replicate_trees", "tiny", "rounds"], "rflags")[0] == 7168 and [n for n, _, _ in cuts["tjamd_consensus_tree", "small"]][-1] == "flags"
+    assert len(cuts["tjamd_consensus_tree", "small"]) == sc.PIECES == 16 and len(cuts["tjamd_replicate_trees", "small"]) == 9
+    # the groups of tjamd_replicate_trees: all replicates of these problems in one
+    for name, (ns_, _, n_rep) in SHAPES.items():
+        assert sc.rep_group(ns_, n_rep)[1] == n_rep, name
     # the shapes: a padding column, a second trip, sliced sites at edge 32; past the one-workgroup forms; inside them, edge 16
     assert ns % 2 == 1 and ns > 1024 and sc._tiles(ns, 600, 256, 0, BLOCKS) == (32, 561, 5) and sc._tiles(ns, 600, 256, 5, BLOCKS) == (32, 561, 2)
     assert sc._tiles(ns, 600, 256, 0)[2] == 1 == sc._tiles(ns, 600, 256, 5)[2]     # (without the switch: one slice, no `partial`)
@@ -121,11 +151,35 @@ def test_the_poisons_cover_the_small_cuts():
     with open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tatajuba_amd", "csrc", "hopo_device.hip")) as src:
         text = src.read()
     for define in ("#define SDIST_CELLS %d " % sc.SDIST_CELLS, "#define SDISTW_BATCH %d " % sc.SDISTW_BATCH, "#define LINK_SMALL %d\n" % sc.SMALL,
-                   "#define CLD_SMALL %d " % sc.SMALL, "used += (count * sizeof (T) + 255) & ~(size_t) 255;"):
+                   "#define CLD_SMALL %d " % sc.SMALL, "used += (count * sizeof (T) + 255) & ~(size_t) 255;",
+                   "#define REP_FLAGS %d\n" % sc.REP_FLAGS, "const size_t REP_SCRATCH_CAP = (size_t) 1 << 30;", "ldc = (ld + 64 + 63) & ~63;", "} piece[%d];" % sc.PIECES,
+                   "const size_t per = small ? 0 : (size_t) ns * ld * 8 + 2 * (size_t) ldc * 4 + 2 * (size_t) ns * 16 + (size_t) ns * 4 + (size_t) (ns - 1) * 16;",
+                   "std::min<size_t> ((size_t) R, REP_SCRATCH_CAP / per)", "const size_t n1 = (size_t) std::max (n, 1l);",
+                   # the pieces in the order of the cut.take lines
+                   "cut.take (A.comp, Gs * ldc); cut.take (A.size, Gs * ldc); cut.take (A.rowbest, Gs * ns); cut.take (A.edges, Gs * ns); cut.take (A.pairs, Gs * ns);\n"
+                   "  cut.take (A.links, Gs * (ns - 1)); cut.take (A.keys, Gs * ns * ld); cut.take (A.rflags, (size_t) R * REP_FLAGS);\n",
+                   "cut.take (key[0], n1); cut.take (key[1], n1); cut.take (val[0], n1); cut.take (val[1], n1); cut.take (head, n1); cut.take (hex, n1); cut.take (lead, n1);\n"
+                   "  cut.take (cls, n1); cut.take (cnt, n1); cut.take (pos, (size_t) R * ns); cut.take (reps, (size_t) 2 * R + 1); cut.take (rbad, (size_t) R);\n"
+                   "  cut.take (kept, (size_t) ns); cut.take (kpar, (size_t) 2 * ns); cut.take (info, (size_t) 2 * ns);\n",
+                   "struct ConsKept { int size, minm, count, rep, first, pad; };", "const unsigned short *pos;"):
         assert define in text, define
 
 
 # ---- the problems -----------------------------------------------------------------------------------------------------------
+
+@functools.lru_cache(maxsize=None)
+def consensus_input(name):
+    """the replicates tjamd_consensus_tree is called on -> (rep_nodes, rep_orders, counts) as tests/test_consensus_cabi.py packs them"""
+    ns, _, n_rep = SHAPES[name]
+    return pack(fabricate_replicates(ns, n_rep, 1 + ns // 64, 100 + ns), ns)
+
+
+@pytest.mark.parametrize("name", list(SHAPES))
+def test_the_consensus_inputs_are_worth_a_consensus(name):
+    ns, _, n_rep = SHAPES[name]
+    want = restate_consensus(*consensus_input(name), ns, majority(n_rep))
+    assert len(want["nodes"]) >= ns // 2 and want["n_classes"] > len(want["nodes"]), (len(want["nodes"]), want["n_classes"])
+
 
 def new_counter(**switches):
     """a counter made under TATAJUBA_AMD_DISTANCE_BLOCKS=4096 and the switches given (read when the counter is made)"""
@@ -143,7 +197,7 @@ def new_counter(**switches):
 
 
 class Problem:
-    """a full set of inputs for all ten entries; what one entry needs from another is made once, on a counter of its own"""
+    """a full set of inputs for all twelve entries; what one entry needs from another is made once, on a counter of its own"""
 
     def __init__(self, name):
         self.name = name
@@ -209,6 +263,9 @@ class Problem:
             self.counts.append(rl.rc)
             self.reps.append((rn, ro))
         self.rep_nodes, self.rnd, self.rod = rep_nodes, dev(rep_nodes), dev(rep_order)
+        self.rep_dd = dev(self.rep_dist)
+        self.cons_nodes, self.cons_orders, self.cons_counts = consensus_input(self.name)
+        self.cnd, self.cod, self.min_count = dev(self.cons_nodes), dev(self.cons_orders), majority(n_rep)
 
 
 def signature(r, *more):
@@ -222,6 +279,11 @@ def run_agglomerate(c, p):
     return tuple(signature(r, r.n_rounds) for r in both)
 
 
+def run_replicate_trees(c, p):
+    out = [sc.call_replicate_trees(c, p.rep_dd, p.ns, p.n_rep, DIFFER, 1, linkage) for linkage in LINKAGES]
+    return tuple(signature(r, r.n_nodes, r.n_rounds) for r in out)
+
+
 ENTRIES = {
     "tjamd_sample_distances": lambda c, p: signature(sc.call_sample_distances(c, p.sd, p.n_sites, p.ad, p.n_alleles, p.gd, p.ns)),
     "tjamd_bootstrap_weights": lambda c, p: signature(sc.call_bootstrap_weights(c, p.n_sites, p.n_rep, p.seed)),
@@ -233,8 +295,10 @@ ENTRIES = {
     "tjamd_clade_sites": lambda c, p: (lambda r: signature(r, r.n_marks))(sc.call_clade_sites(c, p.sd, p.n_sites, p.gmd, p.ns, p.nd, p.n_links, p.od, 1, p.clade_cap)),
     "tjamd_sample_agglomerate": run_agglomerate,
     "tjamd_clade_support": lambda c, p: signature(sc.call_clade_support(c, p.nd, p.n_links, p.od, p.ns, p.rnd, p.rod, p.counts)),
+    "tjamd_replicate_trees": run_replicate_trees,
+    "tjamd_consensus_tree": lambda c, p: (lambda r: signature(r, r.n_classes))(sc.call_consensus_tree(c, p.cnd, p.cod, p.cons_counts, p.ns, p.min_count)),
 }
-WITH_A_SMALL_FORM = ("tjamd_sample_linkage", "tjamd_sample_agglomerate", "tjamd_group_sites", "tjamd_clade_sites")
+WITH_A_SMALL_FORM = ("tjamd_sample_linkage", "tjamd_sample_agglomerate", "tjamd_group_sites", "tjamd_clade_sites", "tjamd_replicate_trees")
 assert {k[0] for k in SMALL_CUTS} == set(ENTRIES)
 
 
@@ -278,6 +342,23 @@ def check_against_the_restatements(p, fresh):
     rc, _, o = out("tjamd_clade_support")
     want = restate_clade_support(tree["nodes"], tree["order"], reps)
     assert rc == ns - 1 and o["d_support"] == want.tobytes() and 0 < want.max() and want.min() < want.max()
+    for i, linkage in enumerate(LINKAGES):
+        rc, (n_nodes, n_rounds), o = out("tjamd_replicate_trees", i)
+        want = restate_replicate_trees(p.rep_dist, DIFFER, 1, linkage)
+        assert rc == p.n_rep and n_nodes == tuple(len(t["nodes"]) for t in want) and n_rounds == tuple(t["n_rounds"] for t in want), linkage
+        assert linkage == SINGLE or max(n_rounds) > 1
+        for r, t in enumerate(want):                                          # (entries past a replicate's count: left as they were)
+            at, n = r * (ns - 1) * 16, len(t["nodes"]) * 16
+            assert o["d_rep_links"][at: at + n] == t["links"].tobytes() and o["d_rep_nodes"][at: at + n] == t["nodes"].tobytes(), (linkage, r)
+            assert o["d_rep_order"][r * ns * 4: (r + 1) * ns * 4] == t["order"].tobytes(), (linkage, r)
+            if linkage == SINGLE:                                             # what the preparation counter made replicate by replicate
+                assert (t["nodes"].tobytes(), t["order"].tobytes()) == (p.reps[r][0].tobytes(), p.reps[r][1].tobytes())
+    rc, (n_classes,), o = out("tjamd_consensus_tree")
+    want = restate_consensus(p.cons_nodes, p.cons_orders, p.cons_counts, ns, p.min_count)
+    assert rc == len(want["nodes"]) >= ns // 2 and n_classes == want["n_classes"] > rc
+    assert o["d_nodes"][: rc * 16] == want["nodes"].tobytes() and o["d_order"] == want["order"].tobytes()
+    for r, counts in enumerate(want["rep_count"]):
+        assert o["d_rep_count"][r * (ns - 1) * 4: (r * (ns - 1) + len(counts)) * 4] == counts.tobytes(), r
 
 
 class World:
@@ -428,6 +509,55 @@ def support(**bad):
     return make
 
 
+def replicate_trees(metric, linkage, changes):
+    """changes: p, the last replicate's matrix -> [(field, cell, value)]"""
+    def make(p):
+        d = p.rep_dist.copy()
+        for field, at, value in changes(p, d[p.n_rep - 1]):
+            d[field][p.n_rep - 1][at] = value
+        dd = dev(d)
+
+        def call(c):
+            r = sc.call_replicate_trees(c, dd, p.ns, p.n_rep, metric, 1, linkage)
+            assert r.rc >= 0 or (set(r.n_nodes) == set(r.n_rounds) == {UNSET} and r.err.endswith("(replicate %d)" % (p.n_rep - 1))), r.err
+            return r
+        return call
+    return make
+
+
+def consensus(order=None, nodes=None):
+    """order: p, the last replicate's order -> place, value; nodes: p, its nodes -> [(node, first, size)]"""
+    def make(p):
+        last = p.n_rep - 1
+        cn, co = p.cons_nodes.copy(), p.cons_orders.copy()
+        if order:
+            at, value = order(p, co[last * p.ns: (last + 1) * p.ns])
+            co[last * p.ns + at] = value
+        for k, first, size in (nodes(p, cn[last * (p.ns - 1): last * (p.ns - 1) + p.cons_counts[last]]) if nodes else ()):
+            cn[last * (p.ns - 1) + k]["first"], cn[last * (p.ns - 1) + k]["size"] = first, size
+        cnd, cod = dev(cn), dev(co)
+
+        def call(c):
+            r = sc.call_consensus_tree(c, cnd, cod, p.cons_counts, p.ns, p.min_count)
+            assert r.rc >= 0 or (r.n_classes == UNSET and "replicate %d" % last in r.err), r.err
+            return r
+        return call
+    return make
+
+
+def _a_key_of_2_40(p, d):
+    """a pair that is an edge whatever the weights gave it, with a length_diff of 2^40"""
+    both = max(int(d["n_both"][2, 5]), 1)
+    return [(f, at, v) for f, v in (("length_diff", 1 << 40), ("n_both", both)) for at in ((2, 5), (5, 2))]
+
+
+def _crossing(p, nodes):
+    """two nodes of two samples each become (1, n_samples - 2) and (2, n_samples - 2): they overlap and neither holds the other"""
+    two = [k for k in range(len(nodes)) if nodes[k]["size"] == 2][:2]
+    assert len(two) == 2
+    return [(two[0], 1, p.ns - 2), (two[1], 2, p.ns - 2)]
+
+
 def _over(p, d):
     """a cell and its mirror with n_differ above n_both"""
     a, b = 5, p.ns - 10
@@ -481,10 +611,17 @@ REFUSALS.update({
     "clades: a genotype cell": (GENOTYPE, marks(False, g=_last_cell)),
     "support 1: an order": ("is not a permutation of 0 .. n_samples - 1", support(order=_twice)),
     "support 2: a node": (NODE_TEXT, support(rep_nodes=lambda p: ((p.n_rep - 1) * (p.ns - 1) + 1, (0, 0, p.ns - 1, 2)))),
+    "trees 1: a cell": (CELL, replicate_trees(DIFFER, COMPLETE, _over)),
+    "trees 2: a mirror": (MIRROR, replicate_trees(DIFFER, SINGLE, lambda p, d: [("n_both", (p.ns - 1, 3), int(d["n_both"][p.ns - 1, 3]) + 1)])),
+    "trees 4: a key of 2^40": ("a key of 2^40 or more under TJAMD_AGGL_AVERAGE", replicate_trees(LENGTH, AVERAGE, _a_key_of_2_40)),
+    "consensus 1: an order": ("is not a permutation of 0 .. n_samples - 1", consensus(order=lambda p, o: (4, int(o[0])))),
+    "consensus 2: a node": ("has size < 2, first < 0 or first + size above n_samples", consensus(nodes=lambda p, n: [(len(n) // 2, p.ns - 1, 2)])),
+    "consensus 4: crossing nodes": ("cross (they overlap and neither contains the other)", consensus(nodes=_crossing)),
 })
 # distances and weighted: bits 1, 8, 16, 32, 64, 128, and 256 and 512; linkage 1, 2; agglomerate 1, 2, 4; a bad link; a bad end and
-# a cycle; the three texts of the groups and the four of the clades; support 1, 2
-assert len(REFUSALS) == 6 + 8 + 2 + 3 + 1 + 2 + 3 + 4 + 2
+# a cycle; the three texts of the groups and the four of the clades; support 1, 2; the trees of the replicates 1, 2, 4; the consensus
+# 1, 2, 4.  The last two entries' refusals lie in the last replicate, which their callers hold the message to.
+assert len(REFUSALS) == 6 + 8 + 2 + 3 + 1 + 2 + 3 + 4 + 2 + 3 + 3
 
 
 @pytest.mark.gpu
