@@ -95,12 +95,12 @@ long tjamd_coding_download (const tjamd_coding *cod, tjamd_cds *out, long capaci
  *       included, zero beyond the protein's end; both 0 when identical.
  *   pad = 0.
  * Returns n and writes exactly n records (n = 0: returns 0, writes nothing).  Refused with TJAMD_ERR_ARG from an error flag
- * raised on the device (nothing is read outside any array either way, and what d_out then holds is unspecified): a contig
+ * raised on the device by a first pass that writes nothing (nothing is read outside any array, and d_out is left as it was): a contig
  * outside the stream's contigs; pos < 1, or q beyond the contig; n_flank outside 0 .. 32; ref_length or alt_length below 1;
  * with d_tract_feat given, a tract outside [0, n_tracts) or a feature index outside [-1, n_features).  Refused on the host
  * with TJAMD_ERR_ARG: n < 0, null buffers, a null counter or table, a coding table of another device; TJAMD_ERR_CAPACITY for
  * 2^31 records or more; without a device, TJAMD_ERR_NO_DEVICE.  Changes none of its inputs nor the counter's finalised
- * state.  One launch; waits once, at the end.
+ * state.  Two launches (the check, the walk); waits once, at the end.
  * Not built: equal (tract, alt_length) records of several samples are walked once each; deduplicating them first is the step
  * after. */
 enum { TJAMD_EFFECT_NONE = 0, TJAMD_EFFECT_BOUNDARY = 1, TJAMD_EFFECT_IDENTICAL = 2, TJAMD_EFFECT_INFRAME = 3, TJAMD_EFFECT_FRAMESHIFT = 4 };

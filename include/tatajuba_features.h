@@ -80,8 +80,9 @@ long tjamd_annotation_download (const tjamd_annotation *a, uint64_t *h_points, i
  *     With d_keys or d_counts NULL max_length is 0 and n_union, n_samples and d_tracts are not read.
  * Returns n_tracts and writes exactly n_tracts records (n_tracts = 0: returns 0, writes nothing).  Refused with
  * TJAMD_ERR_ARG: when a union is given, tracts that do not tile it (from an error flag raised on the device) and n_samples
- * outside 1 ... 4096; an annotation of another device; null buffers.  Without a device, TJAMD_ERR_NO_DEVICE.  Changes none
- * of its inputs nor the counter's finalised state.  One launch; waits once, at the end. */
+ * outside 1 ... 4096; an annotation of another device; null buffers.  Without a device, TJAMD_ERR_NO_DEVICE.  A refused call
+ * writes nothing to d_out (the tiling is checked by a launch of its own, in front of the lookup).  Changes none of its inputs
+ * nor the counter's finalised state.  One launch without a union, two with one; waits once, at the end. */
 typedef struct { int feature, max_length; } tjamd_tract_feature;                                   /* 8 bytes */
 long tjamd_tract_features (tjamd_counter *c, const tjamd_annotation *a, const void *d_keys, const void *d_counts, long n_union,
                            int n_samples, const tjamd_union_tract *d_tracts, long n_tracts, const tjamd_location *d_tract_loc,

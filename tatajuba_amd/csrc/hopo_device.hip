@@ -7921,14 +7921,20 @@ extern "C" double tjamd_last_annotation_ms (tjamd_counter *c) { return c ? c->ti
 // segment's first lane looks the location up in the table (one binary search) and reads the tract's rows; with a union, a
 // lane per sample (looping beyond 64) takes the length of the sample's modal row and the segment reduces the maximum with
 // shuffles.  Without a union (keys == NULL, S = 1) a thread per tract does the lookup alone.  err |= 1: the tracts do not
-// tile the union (check_tiling; tract_rows reads nothing outside the arrays either way).
+// tile the union (tiling_check_kernel, a launch of its own in front: the lookup returns while the flag is up, so a refused call
+// writes nothing; tract_rows reads nothing outside the arrays either way).
+__global__ void tiling_check_kernel (const UnionTract *__restrict__ tracts, long n_tracts, long n_union, int *__restrict__ err)
+{
+  check_tiling (tracts, n_tracts, n_union, err);
+}
+
 __global__ __launch_bounds__ (256)
 void tract_features_kernel (const u64 *__restrict__ keys, const int *__restrict__ counts, long n_union, int ns, int S,
                             const UnionTract *__restrict__ tracts, long n_tracts, const Location *__restrict__ tloc,
                             const u64 *__restrict__ points, const u32 *__restrict__ prio, long np, TractFeature *__restrict__ out, int *__restrict__ err)
 {
   const long gthread = blockIdx.x * (long) blockDim.x + threadIdx.x, n_threads = (long) gridDim.x * blockDim.x;
-  if (keys) check_tiling (tracts, n_tracts, n_union, err);
+  if (*(volatile int *) err != 0) return;                // (the check is complete: every thread reads the same word)
   const int lane = threadIdx.x & (S - 1);
   const long segs_per_grid = n_threads / S;
   for (long t = gthread / S; t < n_tracts; t += segs_per_grid) {   // (uniform across a segment)
@@ -7988,6 +7994,7 @@ extern "C" long tjamd_tract_features (tjamd_counter *c, const tjamd_annotation *
   if (hipMemsetAsync (err, 0, 4, c->stream) != hipSuccess) return -set_err (TJAMD_ERR_HIP, "%s: memset failed", fn);
   st.begin ();
   const int S = have_union ? tract_segment (n_samples) : 1;
+  if (have_union) hipLaunchKernelGGL (tiling_check_kernel, dim3 (grid_for (n_tracts)), dim3 (256), 0, c->stream, (const UnionTract *) d_tracts, n_tracts, n_union, err);
   hipLaunchKernelGGL (tract_features_kernel, dim3 (tract_grid (n_tracts, S)), dim3 (256), 0, c->stream, have_union ? (const u64 *) d_keys : (const u64 *) nullptr,
                       (const int *) d_counts, n_union, n_samples, S, (const UnionTract *) d_tracts, n_tracts, (const Location *) d_tract_loc,
                       (const u64 *) a->points, (const u32 *) a->prio, a->n_points, (TractFeature *) d_out, err);
@@ -8245,11 +8252,43 @@ __device__ __forceinline__ u32 alt_symbol (const Walk &w, const char *tab, long 
 }
 
 // err bits: 1 contig, 2 pos or q, 4 n_flank, 8 a length, 16 tract, 32 feature index (tjamd_variant_effects names them)
+// effect_record_bad: the bits of one record, with the record's feature, the start of its contig and the contig's length
+__device__ __forceinline__ int effect_record_bad (const Variant &v, const u32 *__restrict__ cstart, long n_contigs, const TractFeature *__restrict__ tf, long n_tracts,
+                                                  long n_features, int &f, long &c0, long &clen)
+{
+  int bad = 0;
+  f = -1; c0 = 0; clen = 0;
+  if (v.contig < 0 || (long) v.contig >= n_contigs) bad |= 1;
+  else { c0 = cstart[v.contig]; clen = (long) cstart[v.contig + 1] - 1 - c0; }
+  if (v.n_flank < 0 || v.n_flank > 32) bad |= 4;
+  if (v.ref_length < 1 || v.alt_length < 1) bad |= 8;
+  const long q = (long) v.pos - 1 + max ((long) v.ref_length - (long) v.alt_length, 0l) + (long) v.n_flank;
+  if (!bad && (v.pos < 1 || q >= clen)) bad |= 2;
+  if (tf) {
+    if (v.tract < 0 || (long) v.tract >= n_tracts) bad |= 16;
+    else { f = tf[v.tract].feature; if (f < -1 || (long) f >= n_features) { bad |= 32; f = -1; } }
+  }
+  return bad;
+}
+
+// every record's check, a launch of its own in front of the walk: variant_effects_kernel returns while the flag is up, so a
+// refused call writes nothing
+__global__ void variant_effects_check_kernel (const u32 *__restrict__ cstart, long n_contigs, long n_features, const Variant *__restrict__ var, long n,
+                                              const TractFeature *__restrict__ tf, long n_tracts, int *__restrict__ err)
+{
+  for (long i = blockIdx.x * (long) blockDim.x + threadIdx.x; i < n; i += (long) gridDim.x * blockDim.x) {
+    int f; long c0, clen;
+    const int bad = effect_record_bad (var[i], cstart, n_contigs, tf, n_tracts, n_features, f, c0, clen);
+    if (bad) atomicOr (err, bad);
+  }
+}
+
 __global__ __launch_bounds__ (256)
 void variant_effects_kernel (const uint8_t *__restrict__ codes, const u32 *__restrict__ cstart, long n_contigs, const CodRow *__restrict__ rows, long n_features,
                              const Variant *__restrict__ var, long n, const TractFeature *__restrict__ tf, long n_tracts, Effect *__restrict__ out, int *__restrict__ err)
 {
   __shared__ char tab[64];                              // the lanes index the amino acids apart: LDS, not a constant array
+  if (*(volatile int *) err != 0) return;                // (the check is complete: every thread reads the same word)
   if (threadIdx.x < 64) tab[threadIdx.x] = aa_table_byte (threadIdx.x);
   __syncthreads ();
   const int lane = threadIdx.x & 63;
@@ -8263,22 +8302,13 @@ void variant_effects_kernel (const uint8_t *__restrict__ codes, const u32 *__res
     int delta = 0;
     if (i < n) {
       const Variant v = var[i];
-      int bad = 0, f = -1;
-      long clen = 0, c0 = 0;
-      if (v.contig < 0 || (long) v.contig >= n_contigs) bad |= 1;
-      else { c0 = cstart[v.contig]; clen = (long) cstart[v.contig + 1] - 1 - c0; }
-      if (v.n_flank < 0 || v.n_flank > 32) bad |= 4;
-      if (v.ref_length < 1 || v.alt_length < 1) bad |= 8;
+      int f;
+      long clen, c0;
+      const int bad = effect_record_bad (v, cstart, n_contigs, tf, n_tracts, n_features, f, c0, clen);
       const long Lr = v.ref_length, La = v.alt_length, nfl = v.n_flank;
       const long n_ref = max (Lr - La, 0l) + 1 + nfl, n_alt = max (La - Lr, 0l) + 1 + nfl;
       const long p = (long) v.pos - 1, q = p + n_ref - 1;
-      if (!bad && (v.pos < 1 || q >= clen)) bad |= 2;
-      if (tf) {
-        if (v.tract < 0 || (long) v.tract >= n_tracts) bad |= 16;
-        else { f = tf[v.tract].feature; if (f < -1 || (long) f >= n_features) { bad |= 32; f = -1; } }
-      }
-      if (bad) atomicOr (err, bad);                     // (the call is refused; the record is left alone)
-      else {
+      if (!bad) {                                       // (a bad record has raised the flag in the check: this launch has returned)
         r.feature = f;
         CodRow row = {Cds {-1, -1, -1, -1}, 0, 0, 0, 0};
         if (f >= 0) row = rows[f];
@@ -8373,6 +8403,8 @@ extern "C" long tjamd_variant_effects (tjamd_counter *c, const tjamd_coding *cod
   int *err = (int *) c->lc_work.p;
   if (hipMemsetAsync (err, 0, 4, c->stream) != hipSuccess) return -set_err (TJAMD_ERR_HIP, "%s: memset failed", fn);
   st.begin ();
+  hipLaunchKernelGGL (variant_effects_check_kernel, dim3 (grid_for (n)), dim3 (256), 0, c->stream, (const u32 *) cod->cstart, cod->n_contigs, cod->n_features,
+                      (const Variant *) d_variants, n, (const TractFeature *) d_tract_feat, n_tracts, err);
   hipLaunchKernelGGL (variant_effects_kernel, dim3 ((unsigned) std::min<long> ((n + 255) / 256, 65536)), dim3 (256), 0, c->stream, (const uint8_t *) cod->codes,
                       (const u32 *) cod->cstart, cod->n_contigs, (const CodRow *) cod->rows, cod->n_features, (const Variant *) d_variants, n,
                       (const TractFeature *) d_tract_feat, n_tracts, (Effect *) d_out, err);

@@ -1,7 +1,8 @@
 """The case table of the bounds tests (every exported entry that takes an output pointer, and what it writes through it)
 and one caller per device entry that puts every output into a guarded buffer of exactly the size the header asks for,
 holds the const inputs frozen, makes the call, and checks guards and inputs before it returns.
-tests/test_buffer_bounds.py, tests/test_sample_widths.py and tests/test_counter_reuse.py all call through these."""
+tests/test_buffer_bounds.py, tests/test_sample_widths.py, tests/test_variant_bounds.py and tests/test_counter_reuse.py all call
+through these.  The sample-comparison layer (N14-N21) has its callers and its part of the table in tests/sample_calls.py."""
 import ctypes as C
 import functools
 import random
@@ -14,6 +15,7 @@ from tests.guarded import GuardedDevice, GuardedHost, frozen
 ERR_ARG, ERR_CAP = 3, 4
 TS, TR, SU, LOC = tj.TRACT_SUMMARY_DTYPE, tj.UNION_TRACT_DTYPE, tj.UNION_TRACT_SUMMARY_DTYPE, tj.LOCATION_DTYPE
 VAR, TF, EF, ST, AL = tj.VARIANT_DTYPE, tj.TRACT_FEATURE_DTYPE, tj.EFFECT_DTYPE, tj.SITE_DTYPE, tj.ALLELE_DTYPE
+SDP = tj.SITE_DEPTH_DTYPE
 N_STATS = 5                              # TJAMD_N_TRACT_STATS
 
 # row counts, tract counts and query counts of the device entries: one on each side of, and at, every constant by which the
@@ -32,6 +34,13 @@ DEVICE = {
     "tjamd_union_tract_sample_stats": ("d_values", "d_modal_len", "d_n_context", "d_n_len"),
     "tjamd_locate": ("d_loc",),
     "tjamd_located_tracts": ("d_perm", "d_out_keys", "d_out_counts", "d_out_tracts", "d_tract_loc", "d_ref_length"),
+    # the variant layer, N8-N13, each declared in a header of its own (tests/test_locate_gapped_bounds.py, tests/test_variant_bounds.py)
+    "tjamd_locate_gapped": ("d_loc", "d_how"),
+    "tjamd_tract_variants": ("d_out", "h_offsets"),
+    "tjamd_tract_features": ("d_out",),
+    "tjamd_variant_effects": ("d_out",),
+    "tjamd_merge_variants": ("d_sites", "d_alleles", "d_genotype", "d_allele_of", "d_unique"),
+    "tjamd_site_depths": ("d_genotype", "d_depth", "d_allele_depth", "d_summary"),
 }
 # HOST: host memory, written by an entry that needs a GPU (tests/test_buffer_bounds.py)
 HOST = {
@@ -45,6 +54,8 @@ HOST = {
     "tjamd_scan_windows": ("out", "window_of"),
     "tjamd_device_download": ("host",),
     "tjamd_gather_histograms": ("counts",),
+    "tjamd_annotation_download": ("h_points", "h_winner"),
+    "tjamd_coding_download": ("out",),
 }
 # CPU: host memory, written without a GPU (tests/test_host_bounds.py)
 CPU = {
@@ -52,8 +63,13 @@ CPU = {
     "tjamd_read_file_stream_mt": ("out",),
     "tjamd_synth_stream": ("out",),
     "tjamd_peer_access_report": ("out",),
+    "tjamd_read_file_names": ("out",),
+    "tjamd_gff3_read": ("out", "strings"),
+    "tjamd_translate": ("out",),
+    "tjamd_gff3_read_phase": ("out",),
+    "tjamd_site_ref_alt": ("out",),
 }
-# entries of include/tatajuba_amd.h with a pointer parameter that is not const and that the tables above leave out, and why
+# entries of the headers under include/ with a pointer parameter that is not const and that the tables above leave out, and why
 ALLOW = {
     "tjamd_counter_set_stream": "hip_stream is a handle that is stored, nothing is written through it",
     "tjamd_counter_set_order_stream": "hip_stream is a handle that is stored, nothing is written through it",
@@ -86,6 +102,11 @@ def _p(x):
     if isinstance(x, (GuardedDevice, GuardedHost)):
         return x.c
     return C.c_void_p(x.data_ptr()) if x.numel() else None
+
+
+def _p0(g, cap):
+    """an output with a capacity: NULL at a capacity of 0, as a caller with nothing to receive passes it"""
+    return _p(g) if cap else None
 
 
 class Union:
@@ -259,14 +280,16 @@ def call_locate_gapped(c, ref, kd, n, max_edits, max_shift):
     return Result(rc, outs)
 
 
-def call_tract_variants(c, ref, u, tracts, nt, tract_loc, cap, lst=None):
-    """tracts, tract_loc: device bytes of tjamd_union_tract[nt] and tjamd_location[nt]; lst: device int32 tensor, or None (every tract)"""
+def call_tract_variants(c, ref, u, tracts, nt, tract_loc, cap, lst=None, n_list=None):
+    """tracts, tract_loc: device bytes of tjamd_union_tract[nt] and tjamd_location[nt]; lst: device int32 tensor, or None (every tract);
+    n_list: the entries of lst to take (all of them).  Capacity 0 passes a NULL d_out.  .ms: the entry's timer after the call"""
     outs = _buffers({"d_out": cap * VAR.itemsize, "h_offsets": (u.ns + 1) * 8}, (), host=("h_offsets",))
+    n_list = (0 if lst is None else int(lst.numel())) if n_list is None else n_list
     with frozen(u.kd, u.md, tracts, tract_loc, lst):
-        rc = tj.lib().tjamd_tract_variants(c._h, ref._h, _p(u.kd), _p(u.md), u.n, u.ns, _p(tracts), nt, _p(tract_loc), _p(lst), 0 if lst is None else int(lst.numel()),
-                                           _p(outs["d_out"]), cap, _p(outs["h_offsets"]))
+        rc = tj.lib().tjamd_tract_variants(c._h, ref._h, _p(u.kd), _p(u.md), u.n, u.ns, _p(tracts), nt, _p(tract_loc), None if lst is None else C.c_void_p(lst.data_ptr()), n_list,
+                                           _p0(outs["d_out"], cap), cap, _p(outs["h_offsets"]))
         _checked(outs)
-    return Result(rc, outs)
+    return Result(rc, outs, ms=c.last_tract_variants_ms())
 
 
 def call_tract_features(c, ann, u, tracts, nt, tract_loc):
@@ -274,7 +297,7 @@ def call_tract_features(c, ann, u, tracts, nt, tract_loc):
     with frozen(u.kd, u.md, tracts, tract_loc):
         rc = tj.lib().tjamd_tract_features(c._h, ann._h, _p(u.kd), _p(u.md), u.n, u.ns, _p(tracts), nt, _p(tract_loc), _p(outs["d_out"]))
         _checked(outs)
-    return Result(rc, outs)
+    return Result(rc, outs, ms=c.last_tract_features_ms())
 
 
 def call_variant_effects(c, cod, variants, n, tract_feat=None, nt=0):
@@ -283,19 +306,47 @@ def call_variant_effects(c, cod, variants, n, tract_feat=None, nt=0):
     with frozen(variants, tract_feat):
         rc = tj.lib().tjamd_variant_effects(c._h, cod._h, _p(variants), n, _p(tract_feat), nt, _p(outs["d_out"]))
         _checked(outs)
+    return Result(rc, outs, ms=c.last_variant_effects_ms())
+
+
+def call_merge_variants(c, k, variants, n, ns, nt, site_cap, allele_cap, null=()):
+    """variants: device bytes of tjamd_variant[>= n]; null: the optional outputs (d_genotype, d_allele_of, d_unique) passed as NULL;
+    d_sites and d_alleles are NULL at a capacity of 0.  d_genotype is sized by the site capacity, as the header sizes it"""
+    assert set(null) <= {"d_genotype", "d_allele_of", "d_unique"}
+    outs = _buffers({"d_sites": site_cap * ST.itemsize, "d_alleles": allele_cap * AL.itemsize, "d_genotype": site_cap * ns * 2, "d_allele_of": n * 4,
+                     "d_unique": allele_cap * VAR.itemsize}, null)
+    na = C.c_long(-1)
+    with frozen(variants):
+        rc = tj.lib().tjamd_merge_variants(c._h, k, _p(variants), n, ns, nt, _p0(outs["d_sites"], site_cap), site_cap, _p0(outs["d_alleles"], allele_cap), allele_cap,
+                                           _p(outs["d_genotype"]), _p(outs["d_allele_of"]), _p(outs["d_unique"]), C.byref(na))
+        _checked(outs)
+    return Result(rc, outs, n_alleles=na.value, ms=c.last_merge_variants_ms())
+
+
+def call_site_depths(c, ref, u, tracts, nt, tract_loc, sites, n_sites, alleles, n_alleles, null=()):
+    """sites, alleles: device bytes of tjamd_site[n_sites] and tjamd_allele[n_alleles] (None with a count of 0); null: the outputs passed
+    as NULL.  AD is guarded at exactly (n_sites + n_alleles) * n_samples ints: a site's last class row ends on the payload's last byte"""
+    outs = _buffers({"d_genotype": n_sites * u.ns * 2, "d_depth": n_sites * u.ns * 4, "d_allele_depth": (n_sites + n_alleles) * u.ns * 4,
+                     "d_summary": n_sites * SDP.itemsize}, null)
+    with frozen(u.kd, u.md, tracts, tract_loc, sites, alleles):
+        rc = tj.lib().tjamd_site_depths(c._h, ref._h, _p(u.kd), _p(u.md), u.n, u.ns, _p(tracts), nt, _p(tract_loc), _p(sites), n_sites, _p(alleles), n_alleles,
+                                        *[_p(outs[name]) for name in DEVICE["tjamd_site_depths"]])
+        _checked(outs)
+    return Result(rc, outs, ms=c.last_site_depths_ms())
+
+
+def call_annotation_download(ann, cap):
+    outs = _buffers({"h_points": cap * 8, "h_winner": cap * 4}, (), host=("h_points", "h_winner"))
+    rc = tj.lib().tjamd_annotation_download(ann._h, _p(outs["h_points"]), _p(outs["h_winner"]), cap)
+    _checked(outs)
     return Result(rc, outs)
 
 
-def call_merge_variants(c, k, variants, n, ns, nt, site_cap, allele_cap):
-    """variants: device bytes of tjamd_variant[n]; every optional output is asked for"""
-    outs = _buffers({"d_sites": site_cap * ST.itemsize, "d_alleles": allele_cap * AL.itemsize, "d_genotype": site_cap * ns * 2, "d_allele_of": n * 4,
-                     "d_unique": allele_cap * VAR.itemsize}, ())
-    na = C.c_long(-1)
-    with frozen(variants):
-        rc = tj.lib().tjamd_merge_variants(c._h, k, _p(variants), n, ns, nt, _p(outs["d_sites"]), site_cap, _p(outs["d_alleles"]), allele_cap,
-                                           _p(outs["d_genotype"]), _p(outs["d_allele_of"]), _p(outs["d_unique"]), C.byref(na))
-        _checked(outs)
-    return Result(rc, outs, n_alleles=na.value)
+def call_coding_download(cod, cap):
+    outs = _buffers({"out": cap * tj.CDS_DTYPE.itemsize}, (), host=("out",))
+    rc = tj.lib().tjamd_coding_download(cod._h, _p(outs["out"]), cap)
+    _checked(outs)
+    return Result(rc, outs)
 
 
 # ---- the outputs in the shape the suite's checks take (tests/test_tract_stats.py, test_union_tracts.py, test_locate.py) ----

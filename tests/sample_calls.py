@@ -9,6 +9,8 @@ return value, the message of a refused call, the guarded outputs, and .ms, the e
 import ctypes as C
 
 import tatajuba_amd as tj
+import numpy as np
+
 from tests.bounds_calls import Result, _buffers, _checked, _p
 from tests.guarded import frozen
 
@@ -16,6 +18,24 @@ DIST, LINK, NODE = tj.SAMPLE_DISTANCE_DTYPE, tj.LINK_DTYPE, tj.TREE_NODE_DTYPE
 CALL, GSITE, MARK = tj.GROUP_CALL_DTYPE, tj.GROUP_SITE_DTYPE, tj.GROUP_MARK_DTYPE
 CNODE = tj.CONSENSUS_NODE_DTYPE
 UNSET = -77                              # what a scalar output holds before the call
+
+# entry -> the outputs it writes through caller pointers, each of which its caller below puts into a guarded buffer: this layer's
+# part of the case table of tests/bounds_calls.py, read by tests/test_host_bounds.py.  An array on the host (h_rep_n_nodes) is an
+# output like any other; a pointer to one scalar (h_n_rounds, h_n_marks, h_n_classes) has no row
+OUTPUTS = {
+    "tjamd_sample_distances": ("d_out",),
+    "tjamd_bootstrap_weights": ("d_weights",),
+    "tjamd_sample_distances_weighted": ("d_out",),
+    "tjamd_sample_linkage": ("d_links",),
+    "tjamd_sample_agglomerate": ("d_links",),
+    "tjamd_linkage_clusters": ("d_cluster",),
+    "tjamd_linkage_tree": ("d_nodes", "d_order"),
+    "tjamd_group_sites": ("d_calls", "d_site_out", "d_group_marks", "d_marks"),
+    "tjamd_clade_sites": ("d_calls", "d_site_out", "d_node_marks", "d_marks"),
+    "tjamd_clade_support": ("d_support",),
+    "tjamd_replicate_trees": ("d_rep_links", "d_rep_nodes", "d_rep_order", "h_rep_n_nodes", "h_rep_n_rounds"),
+    "tjamd_consensus_tree": ("d_nodes", "d_order", "d_rep_count"),
+}
 
 
 def call_sample_distances(c, sd, n_sites, ad, n_alleles, gd, ns):
@@ -112,14 +132,16 @@ def call_clade_support(c, nd, n_nodes, od, ns, rnd, rod, counts):
 
 
 def call_replicate_trees(c, dd, ns, n_rep, metric, min_both, linkage):
-    """dd: device bytes of tjamd_sample_distance [n_rep, ns, ns]"""
-    outs = _buffers({"d_rep_links": n_rep * (ns - 1) * LINK.itemsize, "d_rep_nodes": n_rep * (ns - 1) * NODE.itemsize, "d_rep_order": n_rep * ns * 4}, ())
-    n_nodes, n_rounds = (C.c_int * n_rep)(*[UNSET] * n_rep), (C.c_int * n_rep)(*[UNSET] * n_rep)
+    """dd: device bytes of tjamd_sample_distance [n_rep, ns, ns].  The two host arrays are guarded like the device outputs: a call
+    that leaves them alone leaves them untouched(); .n_nodes and .n_rounds are what they hold after the call"""
+    outs = _buffers({"d_rep_links": n_rep * (ns - 1) * LINK.itemsize, "d_rep_nodes": n_rep * (ns - 1) * NODE.itemsize, "d_rep_order": n_rep * ns * 4,
+                     "h_rep_n_nodes": n_rep * 4, "h_rep_n_rounds": n_rep * 4}, (), host=("h_rep_n_nodes", "h_rep_n_rounds"))
     with frozen(dd):
         rc = tj.lib().tjamd_replicate_trees(c._h, _p(dd), ns, n_rep, metric, min_both, linkage, _p(outs["d_rep_links"]), _p(outs["d_rep_nodes"]), _p(outs["d_rep_order"]),
-                                            n_nodes, n_rounds)
+                                            C.cast(outs["h_rep_n_nodes"].c, C.POINTER(C.c_int)), C.cast(outs["h_rep_n_rounds"].c, C.POINTER(C.c_int)))
         _checked(outs)
-    return Result(rc, outs, ms=c.last_replicate_trees_ms(), n_nodes=tuple(n_nodes), n_rounds=tuple(n_rounds))
+    return Result(rc, outs, ms=c.last_replicate_trees_ms(), n_nodes=tuple(outs["h_rep_n_nodes"].view(np.int32).tolist()),
+                  n_rounds=tuple(outs["h_rep_n_rounds"].view(np.int32).tolist()))
 
 
 def call_consensus_tree(c, rnd, rod, counts, ns, min_count):

@@ -34,9 +34,13 @@ cut_ids = lambda cuts: [f"{kind}-{v}" for kind, v in cuts]
 
 
 def test_the_table_names_every_case_below():
-    assert set(bc.DEVICE) == {"tjamd_merge_samples", "tjamd_tract_ids", "tjamd_tract_stats", "tjamd_tract_sample_stats", "tjamd_union_tracts",
-                              "tjamd_union_tract_stats", "tjamd_union_tract_sample_stats", "tjamd_locate", "tjamd_located_tracts"}
-    assert set(bc.HOST) == set(HOST_CASES)
+    elsewhere = {"tjamd_locate_gapped": "tests/test_locate_gapped_bounds.py"}    # the variant layer, N8-N13, has files of its own
+    elsewhere.update({name: "tests/test_variant_bounds.py" for name in ("tjamd_tract_variants", "tjamd_tract_features", "tjamd_variant_effects", "tjamd_merge_variants",
+                                                                        "tjamd_site_depths", "tjamd_annotation_download", "tjamd_coding_download")})
+    assert all(os.path.exists(os.path.join(os.path.dirname(__file__), os.path.basename(f))) for f in elsewhere.values())
+    assert set(bc.DEVICE) - set(elsewhere) == {"tjamd_merge_samples", "tjamd_tract_ids", "tjamd_tract_stats", "tjamd_tract_sample_stats", "tjamd_union_tracts",
+                                               "tjamd_union_tract_stats", "tjamd_union_tract_sample_stats", "tjamd_locate", "tjamd_located_tracts"}
+    assert set(bc.HOST) - set(elsewhere) == set(HOST_CASES) and set(elsewhere) <= set(bc.DEVICE) | set(bc.HOST)
 
 
 # ---- the unions: prefixes of one union of random families, cut to a number of rows, of context-keyed tracts, of grouped tracts

@@ -5,7 +5,7 @@ left -- would pass every test that takes a fresh counter.  Here one counter goes
 a large problem (4097 rows by 70 samples), then on a small one of another shape (65 rows by 3 samples), then on the small
 one directly after each kind of refused call on the large one, with a sample scanned, the counter reset and another
 scanned, and a reference built, used, closed and built again smaller; the annotation layer (variants, features, the seed
-order and the gapped lookup, coding effects, merged sites) goes through the same sequence on tracts placed on the genome.
+order and the gapped lookup, coding effects, merged sites, site depths) goes through the same sequence on tracts placed on the genome.
 Every result is bit for bit that of the same call on a fresh counter; every output sits in a guarded buffer
 (tests/bounds_calls.py)."""
 import random
@@ -83,6 +83,10 @@ class Problem:
             mv = bc.call_merge_variants(prep, K, self.variants, self.n_variants, self.u.ns, self.nt, self.nt, self.n_variants)
             assert lg.rc > 0 and ve.rc == self.n_variants and mv.rc > 0 and mv.n_alleles >= mv.rc
             self.n_sites, self.n_alleles = mv.rc, mv.n_alleles
+            self.sites_host, self.sites = mv["d_sites"].view(tj.SITE_DTYPE, mv.rc), mv["d_sites"].payload.clone()      # what tjamd_site_depths reads
+            self.alleles = mv["d_alleles"].payload[: mv.n_alleles * tj.ALLELE_DTYPE.itemsize].clone()
+            sd = bc.call_site_depths(prep, ref, self.u, self.tracts, self.nt, self.tract_loc, self.sites, self.n_sites, self.alleles, self.n_alleles)
+            assert sd.rc == self.n_sites, sd.err
         finally:
             for h in (cod, ann, ref):
                 if h is not None:
@@ -154,6 +158,7 @@ ENTRIES = {
     "tjamd_reference_add_seeds, tjamd_locate_gapped": lambda c, p: with_reference(c, p, lambda ref: bc.call_locate_gapped(c, ref, p.queries, p.n_queries, MM, MM), seeds=True),
     "tjamd_coding_create, tjamd_variant_effects": run_effects,
     "tjamd_merge_variants": lambda c, p: (lambda r: signature(r, r.n_alleles))(bc.call_merge_variants(c, K, p.variants, p.n_variants, p.u.ns, p.nt, p.n_sites, p.n_alleles)),
+    "tjamd_site_depths": lambda c, p: with_reference(c, p, lambda ref: bc.call_site_depths(c, ref, p.u, p.tracts, p.nt, p.tract_loc, p.sites, p.n_sites, p.alleles, p.n_alleles)),
 }
 
 
@@ -201,6 +206,11 @@ def refuse_on_the_genome(c, p):
         bc.call_tract_features(c, ann, p.u, bc.dev(bad), len(bad), p.tract_loc).refused(ERR_ARG, "do not tile the union")
         listed = bc.dev(np.array([0, p.nt], np.int32), np.int32)
         bc.call_tract_variants(c, ref, p.u, p.tracts, p.nt, p.tract_loc, p.n_variants, lst=listed).refused(ERR_ARG, "a listed tract id is outside")
+        miscounted = p.sites_host.copy()                                      # tjamd_site_depths cuts scratch (SdShared): one of its device refusals
+        miscounted["n_called"][len(miscounted) // 2] += 1
+        r = bc.call_site_depths(c, ref, p.u, p.tracts, p.nt, p.tract_loc, bc.dev(miscounted), p.n_sites, p.alleles, p.n_alleles)
+        r.refused(ERR_ARG, "n_called is not the number of samples with an allele")
+        assert all(g.untouched() for g in r.outs.values()) and r.ms == -1.0
     finally:
         ann.close()
         ref.close()

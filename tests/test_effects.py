@@ -86,6 +86,7 @@ def dev_effects(counter, cod, variants, tf=None, n=None, n_tracts=None):
         out.check("d_out")
         if rc < 0:
             assert counter.last_variant_effects_ms() == -1.0 and err.startswith("tjamd_variant_effects")
+            assert out.untouched()                                  # (the records are checked by a launch of its own, in front of the walk)
             return rc, err
         assert rc == n and (n == 0 or counter.last_variant_effects_ms() > 0)
         runs.append(out.view(EF, n))

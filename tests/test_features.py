@@ -85,7 +85,7 @@ def dev_tract_features(counter, ann, u=None, loc=None, nt=None, with_union=True,
             torch.cuda.synchronize()
         out.check("d_out")
         if rc < 0:
-            assert out.untouched() or n == 0 or "tile" in err       # (a broken tiling is found on the device, after the records were written)
+            assert out.untouched()                                  # (a broken tiling is found on the device by a launch of its own, in front of the records)
             assert counter.last_tract_features_ms() == -1.0 and err.startswith("tjamd_tract_features")
             return rc, err
         assert rc == n and (n == 0 or counter.last_tract_features_ms() > 0)

@@ -519,7 +519,7 @@ def replicate_trees(metric, linkage, changes):
 
         def call(c):
             r = sc.call_replicate_trees(c, dd, p.ns, p.n_rep, metric, 1, linkage)
-            assert r.rc >= 0 or (set(r.n_nodes) == set(r.n_rounds) == {UNSET} and r.err.endswith("(replicate %d)" % (p.n_rep - 1))), r.err
+            assert r.rc >= 0 or (r["h_rep_n_nodes"].untouched() and r["h_rep_n_rounds"].untouched() and r.err.endswith("(replicate %d)" % (p.n_rep - 1))), r.err
             return r
         return call
     return make
