@@ -3254,12 +3254,18 @@ void bin_scatter_kernel (const u64 *__restrict__ in, u64 *__restrict__ out, long
 
 #define SC_ITEMS 4096
 
+// the sum of x over this lane and the lanes before it in the wavefront by six __shfl_up steps, for any type that adds (wave_inclusive_scan: the DPP form for u32)
+template <class T> __device__ __forceinline__ T wave_inclusive_sum (T x, int lane)
+{
+  #pragma unroll
+  for (int o = 1; o < 64; o <<= 1) { const T v = __shfl_up (x, o); if (lane >= o) x += v; }
+  return x;
+}
+
 __device__ __forceinline__ u32 block_exclusive_scan_256 (u32 v, u32 *s_tmp, u32 &total)
 { // exclusive scan of one value per thread over 256 threads
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  u32 x = v;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) { u32 y = __shfl_up (x, o); if (lane >= o) x += y; }
+  const u32 x = wave_inclusive_sum (v, lane);
   if (lane == 63) s_tmp[wave] = x;
   __syncthreads ();
   u32 wbase = 0;
@@ -3274,7 +3280,7 @@ __device__ __forceinline__ u32 block_exclusive_scan_256 (u32 v, u32 *s_tmp, u32 
 __device__ __forceinline__ int block_exclusive_scan_1024 (int mine, int tid, int *wsum, int &total)
 {
   const int lane = tid & 63, wave = tid >> 6;
-  int incl = mine;
+  int incl = mine;                                      // (wave_inclusive_sum written out: through the helper the three kernels that scan here compile an instruction shorter, not to the same code)
   #pragma unroll
   for (int o = 1; o < 64; o <<= 1) {
     const int v = __shfl_up (incl, o);
@@ -4113,11 +4119,17 @@ static int finalise_status (tjamd_counter *c, int *status, int s) { c->status = 
 // One call's use of a timer of its counter.  Construction clears `timed` (where the entry does that relative to its checks is
 // the entry's choice; a null counter, or one that stands for a counter where there is no device, is left alone), begin ()
 // and end () record on the counter's stream, done () marks the interval as good.  A call that leaves by any other way has
-// no timing: "a failed call leaves no timing behind" holds without the author's care.
+// no timing: "a failed call leaves no timing behind" holds without the author's care.  enter () is the head of a device call whose
+// argument checks are done: the refusal without a device (`what`: the clause that says what the device does), then the counter's device.
 struct Stage
 {
   tjamd_counter *c; StageTimer *t;
   Stage (tjamd_counter *c_, int slot) : c (c_), t (c_ && tjamd_device_count () > 0 ? &c_->timer[slot] : nullptr) { if (t) t->timed = false; }
+  int enter (const char *fn, const char *what)
+  { // 0, or the code of the step that fails with its message set
+    if (tjamd_device_count () <= 0) return set_err (TJAMD_ERR_NO_DEVICE, "%s: TJAMD_ERR_NO_DEVICE: no HIP device visible (%s on the device; no CPU fallback)", fn, what);
+    return hipSetDevice (c->device) == hipSuccess ? TJAMD_OK : set_err (TJAMD_ERR_HIP, "hipSetDevice failed");
+  }
   void begin () { (void) t->begin (c->stream); }
   void end () { (void) t->end (c->stream); }
   void done () { t->timed = true; }
@@ -9181,82 +9193,118 @@ void sample_distances_reduce_kernel (const SampleDistance *__restrict__ partial,
   }
 }
 
+// The host path that N14's entry and N19's weighted one share: where a helper takes a count of matrices or of batches, N14 passes 1.
+// The argument checks behind an entry's own `null counter`, in their order: 0, or the code of the first that fails with its message set.
+static int sdist_check_args (const char *fn, const tjamd_site *d_sites, long n_sites, const tjamd_allele *d_alleles, long n_alleles, const int16_t *d_genotype,
+                             int n_samples, const tjamd_sample_distance *d_out)
+{
+  if (!d_out) return set_err (TJAMD_ERR_ARG, "%s: null d_out", fn);
+  if (n_sites < 0 || n_alleles < 0) return set_err (TJAMD_ERR_ARG, "%s: n_sites %ld, n_alleles %ld: a count below 0", fn, n_sites, n_alleles);
+  if ((n_sites > 0 && (!d_sites || !d_genotype)) || (n_alleles > 0 && !d_alleles)) return set_err (TJAMD_ERR_ARG, "%s: null site, allele or genotype buffer", fn);
+  if (n_samples < 1 || n_samples > 4096) return set_err (TJAMD_ERR_ARG, "%s: n_samples %d outside 1..4096", fn, n_samples);
+  if (n_alleles < n_sites) return set_err (TJAMD_ERR_ARG, "%s: %ld alleles for %ld sites (a site has at least one)", fn, n_alleles, n_sites);
+  if (n_alleles >= (1l << 31)) return set_err (TJAMD_ERR_ARG, "%s: %ld alleles: 2^31 or more", fn, n_alleles);
+  if (n_sites * (long) n_samples >= (1l << 31)) return set_err (TJAMD_ERR_ARG, "%s: %ld sites x %d samples: 2^31 cells or more", fn, n_sites, n_samples);
+  return 0;
+}
+
+// The decomposition: tiles of E x E pairs on or above the diagonal, E = 64 where that (times the batches) alone gives half the
+// workgroups aimed at (four per CU), otherwise 32, and 16 or 8 where the samples are no more; the sites in slices of whole chunks,
+// as many as bring the workgroups to that number (few samples: many slices, their tiles summed from scratch; many samples: one,
+// stored at once).  The scratch is one tile per workgroup: it is bounded by the workgroups aimed at, not by S^2 x slices (16 MB at
+// most: 1024 tiles of edge 32); and the lengths of the check pass, an int per genotype cell: twice the matrix, 2 GB at 125 000
+// sites x 4096 samples, under 8 GB at the 2^31 cells accepted.  They are ints because ref_length is one (runs of the test genomes
+// pass 1500, the tests go to 2^31 - 1); an int16 copy for inputs whose lengths all fit would halve that and take a third off what a
+// tile stages, behind a reduction over the sites ahead of the launch and four more instances of the tile kernel: not built.
+struct SdistShape
+{
+  int E, n_tiles; long n_pairs, n_slices, per_slice;
+  SdistShape (const tjamd_counter *c, long n_sites, int n_samples, long n_batches)
+  {
+    const long want = c->dist_blocks ? c->dist_blocks : 4l * c->n_cu, n_tiles64 = (n_samples + 63) / 64;
+    E = n_samples <= 8 ? 8 : n_samples <= 16 ? 16 : n_tiles64 * (n_tiles64 + 1) / 2 * n_batches >= (want + 1) / 2 ? 64 : 32;
+    n_tiles = (n_samples + E - 1) / E; n_pairs = (long) n_tiles * (n_tiles + 1) / 2;
+    const long chunk = SDIST_CELLS / E, n_chunks = (n_sites + chunk - 1) / chunk;
+    n_slices = std::max (1l, std::min (n_chunks, want / (n_pairs * n_batches)));
+    per_slice = (n_chunks + n_slices - 1) / n_slices * chunk; n_slices = (n_sites + per_slice - 1) / per_slice;
+  }
+};
+struct SdistScratch { int *err, *lens; SampleDistance *partial; };   // the error word; the lengths; the slices' tiles, or null where the sites are not split
+
+template <class F> static void for_edge (int E, F &&f)
+{ // E as a compile-time constant: f is called with std::integral_constant<int, E>, as with_width does for the record width
+  if (E == 8) f (std::integral_constant<int, 8> ());
+  else if (E == 16) f (std::integral_constant<int, 16> ());
+  else if (E == 32) f (std::integral_constant<int, 32> ());
+  else f (std::integral_constant<int, 64> ());
+}
+
+static long sdist_empty (tjamd_counter *c, const char *fn, tjamd_sample_distance *d_out, int n_samples, long n_matrices)
+{ // no site: every pair of every matrix has nothing in common
+  if (hipMemsetAsync (d_out, 0, (size_t) ((long) n_samples * n_samples * n_matrices) * sizeof (SampleDistance), c->stream) != hipSuccess) return -set_err (TJAMD_ERR_HIP, "%s: memset failed", fn);
+  const int rc = read_back (c, fn, nullptr, nullptr, 0);
+  return rc ? -rc : 0;
+}
+
+// the head of a call with sites: its scratch (a tile per workgroup and matrix where the sites are split), the stage's begin, the check pass
+static int sdist_head (Stage &st, const char *fn, const SdistShape &s, const tjamd_site *d_sites, long n_sites, const tjamd_allele *d_alleles, long n_alleles,
+                       const int16_t *d_genotype, int n_samples, long n_matrices, SdistScratch &x)
+{
+  tjamd_counter *const c = st.c; ScratchCut cut;
+  cut.take (x.err, 64); cut.take (x.lens, (size_t) (n_sites * n_samples)); cut.take (x.partial, s.n_slices > 1 ? (size_t) (n_matrices * s.n_slices * s.n_pairs) * s.E * s.E : 0);
+  if (const int rc = cut.commit (c)) return rc;
+  if (s.n_slices == 1) x.partial = nullptr;
+  if (hipMemsetAsync (x.err, 0, 256, c->stream) != hipSuccess) return set_err (TJAMD_ERR_HIP, "%s: memset failed", fn);
+  const long check_items = std::max (n_sites * n_samples, n_alleles);
+  st.begin ();
+  hipLaunchKernelGGL (sample_distances_check_kernel, dim3 ((unsigned) std::min ((check_items + 255) / 256, 8l * c->n_cu)), dim3 (256), 0, c->stream,
+                      (const Site *) d_sites, n_sites, (const Allele *) d_alleles, n_alleles, d_genotype, n_samples, x.lens, x.err);
+  return 0;
+}
+
+// the error bits of sample_distances_check_kernel, in the order they are reported: 0 if none is up
+static int sdist_refusal (const char *fn, u32 h_err, long n_alleles)
+{
+  if (h_err & 16u) return set_err (TJAMD_ERR_ARG, "%s: a site has n_alleles < 1", fn);
+  if (h_err & 8u) return set_err (TJAMD_ERR_ARG, "%s: first_allele and n_alleles of the sites do not chain from 0 to %ld", fn, n_alleles);
+  if (h_err & 32u) return set_err (TJAMD_ERR_ARG, "%s: an allele's site is not the site that holds it", fn);
+  if (h_err & 64u) return set_err (TJAMD_ERR_ARG, "%s: an allele's alt_length is outside 0..1023", fn);
+  if (h_err & 128u) return set_err (TJAMD_ERR_ARG, "%s: a site's ref_length is below 0", fn);
+  if (h_err & 1u) return set_err (TJAMD_ERR_ARG, "%s: a genotype cell is below -1 or above its site's n_alleles", fn);
+  return 0;
+}
+
+// the tail, behind the tile kernels: the slices' tiles of every matrix summed into `out`, the stage's end, the error word (h_err: all its bits) and its shared bits decoded
+static int sdist_tail (Stage &st, const char *fn, const SdistShape &s, const SdistScratch &x, int n_samples, long n_matrices, SampleDistance *out, long n_alleles, u32 &h_err)
+{
+  int R = 1;                                            // lanes per cell: as many as there are slices, 16 at most
+  while (R < 16 && R < s.n_slices) R <<= 1;
+  if (x.partial)
+    hipLaunchKernelGGL (sample_distances_reduce_kernel, dim3 ((unsigned) std::min ((s.n_pairs * s.E * s.E * R + 255) / 256, 8l * st.c->n_cu), (unsigned) n_matrices), dim3 (256), 0,
+                        st.c->stream, (const SampleDistance *) x.partial, (int) s.n_slices, s.n_tiles, s.E, R, n_samples, out, (const int *) x.err);
+  st.end ();
+  const int rc = read_back (st.c, fn, x.err, &h_err, 1);
+  return rc ? rc : sdist_refusal (fn, h_err, n_alleles);
+}
+
 extern "C" long tjamd_sample_distances (tjamd_counter *c, const tjamd_site *d_sites, long n_sites, const tjamd_allele *d_alleles, long n_alleles,
                                         const int16_t *d_genotype, int n_samples, tjamd_sample_distance *d_out)
 {
   static const char *fn = "tjamd_sample_distances";
   if (!c) return -set_err (TJAMD_ERR_ARG, "%s: null counter", fn);
-  if (!d_out) return -set_err (TJAMD_ERR_ARG, "%s: null d_out", fn);
-  if (n_sites < 0 || n_alleles < 0) return -set_err (TJAMD_ERR_ARG, "%s: n_sites %ld, n_alleles %ld: a count below 0", fn, n_sites, n_alleles);
-  if ((n_sites > 0 && (!d_sites || !d_genotype)) || (n_alleles > 0 && !d_alleles)) return -set_err (TJAMD_ERR_ARG, "%s: null site, allele or genotype buffer", fn);
-  if (n_samples < 1 || n_samples > 4096) return -set_err (TJAMD_ERR_ARG, "%s: n_samples %d outside 1..4096", fn, n_samples);
-  if (n_alleles < n_sites) return -set_err (TJAMD_ERR_ARG, "%s: %ld alleles for %ld sites (a site has at least one)", fn, n_alleles, n_sites);
-  if (n_alleles >= (1l << 31)) return -set_err (TJAMD_ERR_ARG, "%s: %ld alleles: 2^31 or more", fn, n_alleles);
-  if (n_sites * (long) n_samples >= (1l << 31)) return -set_err (TJAMD_ERR_ARG, "%s: %ld sites x %d samples: 2^31 cells or more", fn, n_sites, n_samples);
-  if (tjamd_device_count () <= 0) return -set_err (TJAMD_ERR_NO_DEVICE, "%s: TJAMD_ERR_NO_DEVICE: no HIP device visible (the distances are summed on the device; no CPU fallback)", fn);
+  if (const int bad = sdist_check_args (fn, d_sites, n_sites, d_alleles, n_alleles, d_genotype, n_samples, d_out)) return -bad;
   Stage st (c, T_SAMPLE_DISTANCES);                     // (a refused call leaves no timing behind)
-  if (hipSetDevice (c->device) != hipSuccess) return -set_err (TJAMD_ERR_HIP, "hipSetDevice failed");
-  const long n_out = (long) n_samples * n_samples;
-  int rc;
-  if (n_sites == 0) {                                   // no site: every pair has nothing in common
-    if (hipMemsetAsync (d_out, 0, (size_t) n_out * sizeof (SampleDistance), c->stream) != hipSuccess) return -set_err (TJAMD_ERR_HIP, "%s: memset failed", fn);
-    rc = read_back (c, fn, nullptr, nullptr, 0);
-    return rc ? -rc : 0;
-  }
-  // the decomposition: tiles of E x E pairs on or above the diagonal, E = 64 where that alone gives half the workgroups aimed at
-  // (four per CU), otherwise 32, and 16 or 8 where the samples are no more; the sites in slices of whole chunks, as many as bring
-  // the workgroups to that number (few samples: many slices, their tiles summed from scratch; many samples: one, stored at once).
-  // The scratch is one tile per workgroup: it is bounded by the workgroups aimed at, not by S^2 x slices (16 MB at most: 1024
-  // tiles of edge 32); and the lengths of the check pass, an int per genotype cell: twice the matrix, 2 GB at 125 000 sites x
-  // 4096 samples, under 8 GB at the 2^31 cells accepted.  They are ints because ref_length is one (runs of the test genomes pass
-  // 1500, the tests go to 2^31 - 1); an int16 copy for inputs whose lengths all fit would halve that and take a third off what a
-  // tile stages, behind a reduction over the sites ahead of the launch and four more instances of the tile kernel: not built.
-  const long want = c->dist_blocks ? c->dist_blocks : 4l * c->n_cu;
-  const long n_tiles64 = (n_samples + 63) / 64;
-  const int E = n_samples <= 8 ? 8 : n_samples <= 16 ? 16 : n_tiles64 * (n_tiles64 + 1) / 2 >= (want + 1) / 2 ? 64 : 32;
-  const int n_tiles = (n_samples + E - 1) / E;
-  const long n_pairs = (long) n_tiles * (n_tiles + 1) / 2, chunk = SDIST_CELLS / E, n_chunks = (n_sites + chunk - 1) / chunk;
-  long n_slices = std::max (1l, std::min (n_chunks, want / n_pairs));
-  const long per_slice = (n_chunks + n_slices - 1) / n_slices * chunk;
-  n_slices = (n_sites + per_slice - 1) / per_slice;
-  ScratchCut cut;
-  int *err, *lens; SampleDistance *partial;
-  cut.take (err, 64); cut.take (lens, (size_t) (n_sites * n_samples)); cut.take (partial, n_slices > 1 ? (size_t) (n_slices * n_pairs) * E * E : 0);
-  rc = cut.commit (c);
-  if (rc) return -rc;
-  if (n_slices == 1) partial = nullptr;
-  if (hipMemsetAsync (err, 0, 256, c->stream) != hipSuccess) return -set_err (TJAMD_ERR_HIP, "%s: memset failed", fn);
-  const Site *sites = (const Site *) d_sites;
-  const Allele *alleles = (const Allele *) d_alleles;
-  SampleDistance *out = (SampleDistance *) d_out;
-  const long check_items = std::max (n_sites * n_samples, n_alleles);
-  st.begin ();
-  hipLaunchKernelGGL (sample_distances_check_kernel, dim3 ((unsigned) std::min ((check_items + 255) / 256, 8l * c->n_cu)), dim3 (256), 0, c->stream,
-                      sites, n_sites, alleles, n_alleles, d_genotype, n_samples, lens, err);
-  auto launch = [&] (auto kernel) {
-    hipLaunchKernelGGL (kernel, dim3 ((unsigned) n_pairs, (unsigned) n_slices), dim3 (256), 0, c->stream, d_genotype, (const int *) lens, n_sites, n_samples,
-                        n_tiles, per_slice, partial, out, (const int *) err);
-  };
-  if (E == 8) launch (sample_distances_kernel<8>);
-  else if (E == 16) launch (sample_distances_kernel<16>);
-  else if (E == 32) launch (sample_distances_kernel<32>);
-  else launch (sample_distances_kernel<64>);
-  if (partial) {
-    int R = 1;                                          // lanes per cell: as many as there are slices, 16 at most
-    while (R < 16 && R < n_slices) R <<= 1;
-    hipLaunchKernelGGL (sample_distances_reduce_kernel, dim3 ((unsigned) std::min ((n_pairs * E * E * R + 255) / 256, 8l * c->n_cu)), dim3 (256), 0, c->stream,
-                        (const SampleDistance *) partial, (int) n_slices, n_tiles, E, R, n_samples, out, (const int *) err);
-  }
-  st.end ();
+  if (const int bad = st.enter (fn, "the distances are summed")) return -bad;
+  if (n_sites == 0) return sdist_empty (c, fn, d_out, n_samples, 1);
+  const SdistShape s (c, n_sites, n_samples, 1);
+  SdistScratch x; SampleDistance *const out = (SampleDistance *) d_out;
+  if (const int bad = sdist_head (st, fn, s, d_sites, n_sites, d_alleles, n_alleles, d_genotype, n_samples, 1, x)) return -bad;
+  for_edge (s.E, [&] (auto e) {
+    hipLaunchKernelGGL (sample_distances_kernel<decltype (e)::value>, dim3 ((unsigned) s.n_pairs, (unsigned) s.n_slices), dim3 (256), 0, c->stream, d_genotype,
+                        (const int *) x.lens, n_sites, n_samples, s.n_tiles, s.per_slice, x.partial, out, (const int *) x.err);
+  });
   u32 h_err = 0;
-  rc = read_back (c, fn, err, &h_err, 1);
-  if (rc) return -rc;
-  if (h_err & 16u) return -set_err (TJAMD_ERR_ARG, "%s: a site has n_alleles < 1", fn);
-  if (h_err & 8u) return -set_err (TJAMD_ERR_ARG, "%s: first_allele and n_alleles of the sites do not chain from 0 to %ld", fn, n_alleles);
-  if (h_err & 32u) return -set_err (TJAMD_ERR_ARG, "%s: an allele's site is not the site that holds it", fn);
-  if (h_err & 64u) return -set_err (TJAMD_ERR_ARG, "%s: an allele's alt_length is outside 0..1023", fn);
-  if (h_err & 128u) return -set_err (TJAMD_ERR_ARG, "%s: a site's ref_length is below 0", fn);
-  if (h_err & 1u) return -set_err (TJAMD_ERR_ARG, "%s: a genotype cell is below -1 or above its site's n_alleles", fn);
+  if (const int bad = sdist_tail (st, fn, s, x, n_samples, 1, out, n_alleles, h_err)) return -bad;
   st.done ();
   return n_sites;
 }
@@ -9598,9 +9646,8 @@ extern "C" long tjamd_sample_linkage (tjamd_counter *c, const tjamd_sample_dista
   static const char *fn = "tjamd_sample_linkage";
   int rc = link_check_args (fn, c, d_dist, n_samples, metric, min_both, d_links);
   if (rc) return -rc;
-  if (tjamd_device_count () <= 0) return -set_err (TJAMD_ERR_NO_DEVICE, "%s: TJAMD_ERR_NO_DEVICE: no HIP device visible (the tree is built on the device; no CPU fallback)", fn);
   Stage st (c, T_SAMPLE_LINKAGE);                       // (a refused call leaves no timing behind)
-  if (hipSetDevice (c->device) != hipSuccess) return -set_err (TJAMD_ERR_HIP, "hipSetDevice failed");
+  if (const int bad = st.enter (fn, "the tree is built")) return -bad;
   if (n_samples == 1) {                                 // one sample: no pair, no kernel
     rc = read_back (c, fn, nullptr, nullptr, 0);
     return rc ? -rc : 0;
@@ -9700,9 +9747,8 @@ extern "C" long tjamd_linkage_clusters (tjamd_counter *c, const tjamd_link *d_li
   if (n_links < 0 || n_links > (1l << 24)) return -set_err (TJAMD_ERR_ARG, "%s: n_links %ld outside 0..2^24", fn, n_links);
   if (!d_links && n_links > 0) return -set_err (TJAMD_ERR_ARG, "%s: null d_links", fn);
   if (n_samples < 1 || n_samples > LINK_MAX) return -set_err (TJAMD_ERR_ARG, "%s: n_samples %d outside 1..4096", fn, n_samples);
-  if (tjamd_device_count () <= 0) return -set_err (TJAMD_ERR_NO_DEVICE, "%s: TJAMD_ERR_NO_DEVICE: no HIP device visible (the tree is cut on the device; no CPU fallback)", fn);
   Stage st (c, T_LINKAGE_CLUSTERS);                     // (a refused call leaves no timing behind)
-  if (hipSetDevice (c->device) != hipSuccess) return -set_err (TJAMD_ERR_HIP, "hipSetDevice failed");
+  if (const int bad = st.enter (fn, "the tree is cut")) return -bad;
   ScratchCut cut;
   int *flags;
   int rc = commit_with_flags (cut, c, fn, flags);
@@ -10179,6 +10225,8 @@ extern "C" double tjamd_last_group_sites_ms (tjamd_counter *c) { return c ? c->t
 
 struct TreeNode { int left, right, first, size; };
 static_assert (sizeof (TreeNode) == 16 && sizeof (TreeNode) == sizeof (tjamd_tree_node), "tree node layout");
+// a caller's node lies inside the ns samples: an interval [first, first + size) of the leaf order with two members or more
+__device__ __forceinline__ bool tree_node_ok (const TreeNode &nd, int ns) { return nd.size >= 2 && nd.size <= ns && nd.first >= 0 && nd.first <= ns - nd.size; }
 
 __device__ __forceinline__ void linkage_tree_body (const Link *__restrict__ links, int n_links, int ns, TreeNode *__restrict__ nodes, int *__restrict__ order, int *__restrict__ flags)
 {
@@ -10248,9 +10296,8 @@ extern "C" long tjamd_linkage_tree (tjamd_counter *c, const tjamd_link *d_links,
   if (n_samples < 1 || n_samples > CLD_MAX) return -set_err (TJAMD_ERR_ARG, "%s: n_samples %d outside 1..4096", fn, n_samples);
   if (n_links < 0 || n_links > n_samples - 1) return -set_err (TJAMD_ERR_ARG, "%s: n_links %ld outside 0..n_samples - 1 = %d", fn, n_links, n_samples - 1);
   if (n_links > 0 && (!d_links || !d_nodes)) return -set_err (TJAMD_ERR_ARG, "%s: null link or node buffer", fn);
-  if (tjamd_device_count () <= 0) return -set_err (TJAMD_ERR_NO_DEVICE, "%s: TJAMD_ERR_NO_DEVICE: no HIP device visible (the tree is built on the device; no CPU fallback)", fn);
   Stage st (c, T_LINKAGE_TREE);                         // (a refused call leaves no timing behind)
-  if (hipSetDevice (c->device) != hipSuccess) return -set_err (TJAMD_ERR_HIP, "hipSetDevice failed");
+  if (const int bad = st.enter (fn, "the tree is built")) return -bad;
   ScratchCut cut;
   int *flags;
   int rc = commit_with_flags (cut, c, fn, flags);
@@ -10281,7 +10328,7 @@ void clade_sites_small_kernel (const CladeArgs A)
   int bad = 0, my_marks = 0;
   for (int j = tid; j < n_nodes; j += 256) {
     const TreeNode nd = A.nodes[j];
-    const bool ok = nd.size >= 2 && nd.size <= ns && nd.first >= 0 && nd.first <= ns - nd.size;
+    const bool ok = tree_node_ok (nd, ns);
     if (!ok) bad |= 2;
     s_node[j] = ok ? (nd.first | nd.size << 8) : 0;
   }
@@ -10379,7 +10426,7 @@ void clade_sites_large_kernel (const CladeArgs A, long per_block)
     }
     if (j < n_nodes) {
       const TreeNode nd = A.nodes[j];
-      if (nd.size >= 2 && nd.size <= ns && nd.first >= 0 && nd.first <= ns - nd.size) node[k] = nd.first | nd.size << 16;
+      if (tree_node_ok (nd, ns)) node[k] = nd.first | nd.size << 16;
       else bad |= 2;
     }
     x_cnt[j] = 0;
@@ -10785,9 +10832,8 @@ extern "C" long tjamd_sample_agglomerate (tjamd_counter *c, const tjamd_sample_d
   int rc = link_check_args (fn, c, d_dist, n_samples, metric, min_both, d_links);
   if (rc) return -rc;
   if (linkage != TJAMD_AGGL_COMPLETE && linkage != TJAMD_AGGL_AVERAGE) return -set_err (TJAMD_ERR_ARG, "%s: linkage %d outside 1..2", fn, linkage);
-  if (tjamd_device_count () <= 0) return -set_err (TJAMD_ERR_NO_DEVICE, "%s: TJAMD_ERR_NO_DEVICE: no HIP device visible (the tree is built on the device; no CPU fallback)", fn);
   Stage st (c, T_SAMPLE_AGGLOMERATE);                   // (a refused call leaves no timing behind)
-  if (hipSetDevice (c->device) != hipSuccess) return -set_err (TJAMD_ERR_HIP, "hipSetDevice failed");
+  if (const int bad = st.enter (fn, "the tree is built")) return -bad;
   if (n_samples == 1) {                                 // one sample: no pair, no kernel
     rc = read_back (c, fn, nullptr, nullptr, 0);
     if (rc) return -rc;
@@ -10864,6 +10910,24 @@ extern "C" double tjamd_last_sample_agglomerate_ms (tjamd_counter *c) { return c
 
 #define SDISTW_BATCH 2                                  // replicates a workgroup serves per staged chunk
 
+// The replicates' arguments of N19 to N21, each where its entry's order of refusals has it: 0, or the code with its message set.
+static int replicates_arg (const char *fn, int n) { return n < 1 || n > 4096 ? set_err (TJAMD_ERR_ARG, "%s: n_replicates %d outside 1..4096", fn, n) : 0; }
+static int weights_count_arg (const char *fn, int n_replicates, long n_sites)
+{
+  return n_sites * (long) n_replicates >= (1l << 31) ? set_err (TJAMD_ERR_ARG, "%s: %d replicates x %ld sites: 2^31 weights or more", fn, n_replicates, n_sites) : 0;
+}
+// every replicate's count of nodes within 0..n_samples - 1, and the nodes' buffer where one has any; the counts are added to *total (may be null)
+static int rep_nodes_args (const char *fn, const int *h_rep_n_nodes, int n_replicates, int n_samples, const tjamd_tree_node *d_rep_nodes, long *total)
+{
+  for (int r = 0; r < n_replicates; r++) {
+    if (h_rep_n_nodes[r] < 0 || h_rep_n_nodes[r] > n_samples - 1)
+      return set_err (TJAMD_ERR_ARG, "%s: replicate %d has %d nodes, outside 0..n_samples - 1 = %d", fn, r, h_rep_n_nodes[r], n_samples - 1);
+    if (h_rep_n_nodes[r] > 0 && !d_rep_nodes) return set_err (TJAMD_ERR_ARG, "%s: null d_rep_nodes", fn);
+    if (total) *total += h_rep_n_nodes[r];             // (a refused call does not read it)
+  }
+  return 0;
+}
+
 __device__ __forceinline__ u64 boot_mix (u64 z)
 {
   z ^= z >> 30; z *= 0xBF58476D1CE4E5B9ull; z ^= z >> 27; z *= 0x94D049BB133111EBull; z ^= z >> 31;
@@ -10887,11 +10951,10 @@ extern "C" long tjamd_bootstrap_weights (tjamd_counter *c, long n_sites, int n_r
   if (!c) return -set_err (TJAMD_ERR_ARG, "%s: null counter", fn);
   if (!d_weights) return -set_err (TJAMD_ERR_ARG, "%s: null d_weights", fn);
   if (n_sites < 1 || n_sites >= (1l << 31)) return -set_err (TJAMD_ERR_ARG, "%s: n_sites %ld outside 1..2^31 - 1", fn, n_sites);
-  if (n_replicates < 1 || n_replicates > 4096) return -set_err (TJAMD_ERR_ARG, "%s: n_replicates %d outside 1..4096", fn, n_replicates);
-  if (n_sites * (long) n_replicates >= (1l << 31)) return -set_err (TJAMD_ERR_ARG, "%s: %d replicates x %ld sites: 2^31 weights or more", fn, n_replicates, n_sites);
-  if (tjamd_device_count () <= 0) return -set_err (TJAMD_ERR_NO_DEVICE, "%s: TJAMD_ERR_NO_DEVICE: no HIP device visible (the weights are drawn on the device; no CPU fallback)", fn);
+  if (const int bad = replicates_arg (fn, n_replicates)) return -bad;
+  if (const int bad = weights_count_arg (fn, n_replicates, n_sites)) return -bad;
   Stage st (c, T_BOOTSTRAP_WEIGHTS);
-  if (hipSetDevice (c->device) != hipSuccess) return -set_err (TJAMD_ERR_HIP, "hipSetDevice failed");
+  if (const int bad = st.enter (fn, "the weights are drawn")) return -bad;
   st.begin ();
   if (hipMemsetAsync (d_weights, 0, (size_t) (n_sites * n_replicates) * sizeof (int), c->stream) != hipSuccess) return -set_err (TJAMD_ERR_HIP, "%s: memset failed", fn);
   const long per_rep = std::max (1l, 8l * c->n_cu / n_replicates);
@@ -11057,76 +11120,29 @@ extern "C" long tjamd_sample_distances_weighted (tjamd_counter *c, const tjamd_s
 {
   static const char *fn = "tjamd_sample_distances_weighted";
   if (!c) return -set_err (TJAMD_ERR_ARG, "%s: null counter", fn);
-  if (!d_out) return -set_err (TJAMD_ERR_ARG, "%s: null d_out", fn);
-  if (n_sites < 0 || n_alleles < 0) return -set_err (TJAMD_ERR_ARG, "%s: n_sites %ld, n_alleles %ld: a count below 0", fn, n_sites, n_alleles);
-  if ((n_sites > 0 && (!d_sites || !d_genotype)) || (n_alleles > 0 && !d_alleles)) return -set_err (TJAMD_ERR_ARG, "%s: null site, allele or genotype buffer", fn);
-  if (n_samples < 1 || n_samples > 4096) return -set_err (TJAMD_ERR_ARG, "%s: n_samples %d outside 1..4096", fn, n_samples);
-  if (n_alleles < n_sites) return -set_err (TJAMD_ERR_ARG, "%s: %ld alleles for %ld sites (a site has at least one)", fn, n_alleles, n_sites);
-  if (n_alleles >= (1l << 31)) return -set_err (TJAMD_ERR_ARG, "%s: %ld alleles: 2^31 or more", fn, n_alleles);
-  if (n_sites * (long) n_samples >= (1l << 31)) return -set_err (TJAMD_ERR_ARG, "%s: %ld sites x %d samples: 2^31 cells or more", fn, n_sites, n_samples);
+  if (const int bad = sdist_check_args (fn, d_sites, n_sites, d_alleles, n_alleles, d_genotype, n_samples, d_out)) return -bad;
   if (n_sites > 0 && !d_weights) return -set_err (TJAMD_ERR_ARG, "%s: null d_weights", fn);
-  if (n_replicates < 1 || n_replicates > 4096) return -set_err (TJAMD_ERR_ARG, "%s: n_replicates %d outside 1..4096", fn, n_replicates);
-  if (n_sites * (long) n_replicates >= (1l << 31)) return -set_err (TJAMD_ERR_ARG, "%s: %d replicates x %ld sites: 2^31 weights or more", fn, n_replicates, n_sites);
-  if (tjamd_device_count () <= 0) return -set_err (TJAMD_ERR_NO_DEVICE, "%s: TJAMD_ERR_NO_DEVICE: no HIP device visible (the distances are summed on the device; no CPU fallback)", fn);
+  if (const int bad = replicates_arg (fn, n_replicates)) return -bad;
+  if (const int bad = weights_count_arg (fn, n_replicates, n_sites)) return -bad;
   Stage st (c, T_SAMPLE_DISTANCES_WEIGHTED);            // (a refused call leaves no timing behind)
-  if (hipSetDevice (c->device) != hipSuccess) return -set_err (TJAMD_ERR_HIP, "hipSetDevice failed");
-  const long n_out = (long) n_samples * n_samples;
-  int rc;
-  if (n_sites == 0) {                                   // no site: every pair of every replicate has nothing in common
-    if (hipMemsetAsync (d_out, 0, (size_t) (n_out * n_replicates) * sizeof (SampleDistance), c->stream) != hipSuccess) return -set_err (TJAMD_ERR_HIP, "%s: memset failed", fn);
-    rc = read_back (c, fn, nullptr, nullptr, 0);
-    return rc ? -rc : 0;
-  }
-  // N14's decomposition with the batches of replicates as a third dimension of the grid: the workgroups aimed at count tile
-  // pairs x batches x slices.  Edge 64 where tile pairs x batches alone give half of them; the sites are split only where tile
-  // pairs x batches leave room.  Scratch, where they are split: a tile per workgroup and replicate, bounded by the workgroups
-  // aimed at (two slices of edge 64 on 1024 workgroups, 128 MB, is the most).
-  const long want = c->dist_blocks ? c->dist_blocks : 4l * c->n_cu;
-  const long n_batches = (n_replicates + SDISTW_BATCH - 1) / SDISTW_BATCH, n_tiles64 = (n_samples + 63) / 64;
-  const int E = n_samples <= 8 ? 8 : n_samples <= 16 ? 16 : n_tiles64 * (n_tiles64 + 1) / 2 * n_batches >= (want + 1) / 2 ? 64 : 32;
-  const int n_tiles = (n_samples + E - 1) / E;
-  const long n_pairs = (long) n_tiles * (n_tiles + 1) / 2, chunk = SDIST_CELLS / E, n_chunks = (n_sites + chunk - 1) / chunk;
-  long n_slices = std::max (1l, std::min (n_chunks, want / (n_pairs * n_batches)));
-  const long per_slice = (n_chunks + n_slices - 1) / n_slices * chunk;
-  n_slices = (n_sites + per_slice - 1) / per_slice;
-  ScratchCut cut;
-  int *err, *lens; SampleDistance *partial;
-  cut.take (err, 64); cut.take (lens, (size_t) (n_sites * n_samples)); cut.take (partial, n_slices > 1 ? (size_t) (n_replicates * n_slices * n_pairs) * E * E : 0);
-  rc = cut.commit (c);
-  if (rc) return -rc;
-  if (n_slices == 1) partial = nullptr;
-  if (hipMemsetAsync (err, 0, 256, c->stream) != hipSuccess) return -set_err (TJAMD_ERR_HIP, "%s: memset failed", fn);
-  SampleDistance *out = (SampleDistance *) d_out;
-  const long check_items = std::max (n_sites * n_samples, n_alleles);
-  st.begin ();
-  hipLaunchKernelGGL (sample_distances_check_kernel, dim3 ((unsigned) std::min ((check_items + 255) / 256, 8l * c->n_cu)), dim3 (256), 0, c->stream,
-                      (const Site *) d_sites, n_sites, (const Allele *) d_alleles, n_alleles, d_genotype, n_samples, lens, err);
-  hipLaunchKernelGGL (sample_weights_check_kernel, dim3 ((unsigned) n_replicates), dim3 (256), 0, c->stream, d_weights, (const Site *) d_sites, n_sites, err);
-  auto launch = [&] (auto narrow, auto wide) {          // (one of the two walks the tiles, the other returns at once: the host does not look in between)
+  if (const int bad = st.enter (fn, "the distances are summed")) return -bad;
+  if (n_sites == 0) return sdist_empty (c, fn, d_out, n_samples, n_replicates);
+  // N14's decomposition with the batches of replicates as a third dimension of the grid: the workgroups aimed at count tile pairs
+  // x batches x slices, and the sites are split only where tile pairs x batches leave room.  Scratch, where they are split: a tile per
+  // workgroup and replicate, bounded by the workgroups aimed at (two slices of edge 64 on 1024 workgroups, 128 MB, is the most).
+  const long n_batches = (n_replicates + SDISTW_BATCH - 1) / SDISTW_BATCH;
+  const SdistShape s (c, n_sites, n_samples, n_batches);
+  SdistScratch x; SampleDistance *const out = (SampleDistance *) d_out;
+  if (const int bad = sdist_head (st, fn, s, d_sites, n_sites, d_alleles, n_alleles, d_genotype, n_samples, n_replicates, x)) return -bad;
+  hipLaunchKernelGGL (sample_weights_check_kernel, dim3 ((unsigned) n_replicates), dim3 (256), 0, c->stream, d_weights, (const Site *) d_sites, n_sites, x.err);
+  for_edge (s.E, [&] (auto e) {                         // (one of the two walks the tiles, the other returns at once: the host does not look in between)
+    constexpr int E = decltype (e)::value;
     for (int wd = 0; wd < 2; wd++)
-      hipLaunchKernelGGL (wd ? wide : narrow, dim3 ((unsigned) n_pairs, (unsigned) n_slices, (unsigned) n_batches), dim3 (256), 0, c->stream, d_genotype, (const int *) lens, d_weights,
-                          n_sites, n_samples, n_replicates, n_tiles, per_slice, partial, out, (const int *) err);
-  };
-  if (E == 8) launch (sample_distances_weighted_kernel<8, false>, sample_distances_weighted_kernel<8, true>);
-  else if (E == 16) launch (sample_distances_weighted_kernel<16, false>, sample_distances_weighted_kernel<16, true>);
-  else if (E == 32) launch (sample_distances_weighted_kernel<32, false>, sample_distances_weighted_kernel<32, true>);
-  else launch (sample_distances_weighted_kernel<64, false>, sample_distances_weighted_kernel<64, true>);
-  if (partial) {
-    int R = 1;                                          // lanes per cell, as in N14
-    while (R < 16 && R < n_slices) R <<= 1;
-    hipLaunchKernelGGL (sample_distances_reduce_kernel, dim3 ((unsigned) std::min ((n_pairs * E * E * R + 255) / 256, 8l * c->n_cu), (unsigned) n_replicates), dim3 (256), 0, c->stream,
-                        (const SampleDistance *) partial, (int) n_slices, n_tiles, E, R, n_samples, out, (const int *) err);
-  }
-  st.end ();
+      hipLaunchKernelGGL ((wd == 0 ? sample_distances_weighted_kernel<E, false> : sample_distances_weighted_kernel<E, true>), dim3 ((unsigned) s.n_pairs, (unsigned) s.n_slices, (unsigned) n_batches),
+                          dim3 (256), 0, c->stream, d_genotype, (const int *) x.lens, d_weights, n_sites, n_samples, n_replicates, s.n_tiles, s.per_slice, x.partial, out, (const int *) x.err);
+  });
   u32 h_err = 0;
-  rc = read_back (c, fn, err, &h_err, 1);
-  if (rc) return -rc;
-  if (h_err & 16u) return -set_err (TJAMD_ERR_ARG, "%s: a site has n_alleles < 1", fn);
-  if (h_err & 8u) return -set_err (TJAMD_ERR_ARG, "%s: first_allele and n_alleles of the sites do not chain from 0 to %ld", fn, n_alleles);
-  if (h_err & 32u) return -set_err (TJAMD_ERR_ARG, "%s: an allele's site is not the site that holds it", fn);
-  if (h_err & 64u) return -set_err (TJAMD_ERR_ARG, "%s: an allele's alt_length is outside 0..1023", fn);
-  if (h_err & 128u) return -set_err (TJAMD_ERR_ARG, "%s: a site's ref_length is below 0", fn);
-  if (h_err & 1u) return -set_err (TJAMD_ERR_ARG, "%s: a genotype cell is below -1 or above its site's n_alleles", fn);
+  if (const int bad = sdist_tail (st, fn, s, x, n_samples, n_replicates, out, n_alleles, h_err)) return -bad;
   if (h_err & 256u) return -set_err (TJAMD_ERR_ARG, "%s: a weight is below 0", fn);
   if (h_err & 512u) return -set_err (TJAMD_ERR_ARG, "%s: the weights of a replicate sum to 2^31 or more", fn);
   st.done ();
@@ -11136,6 +11152,10 @@ extern "C" double tjamd_last_sample_distances_weighted_ms (tjamd_counter *c) { r
 
 #define CSUP_PLACES 8192                                // places of the set of a replicate's nodes: twice the most it can hold
 __device__ __forceinline__ u32 csup_place (u32 key) { return (key * 0x9E3779B1u) >> 19; }   // (the top 13 bits)
+
+// a permutation check's step over a cleared bitmap in LDS: raises the bit of s (in range: the caller saw to it) and says whether it
+// was up.  ns positions on ns samples: one sample left out is one sample twice
+__device__ __forceinline__ bool seen_twice (u32 *seen, int s) { return (atomicOr (&seen[s >> 5], 1u << (s & 31)) >> (s & 31)) & 1u; }
 
 // flags[0] bits: 1 an order that is not a permutation, 2 a node outside the samples or of size < 2
 __global__ __launch_bounds__ (1024)
@@ -11157,12 +11177,12 @@ void clade_support_kernel (const TreeNode *__restrict__ nodes, int n_nodes, cons
   for (int p = tid; p < ns; p += 1024) {
     const int s = ro[p];
     if (s < 0 || s >= ns) { bad |= 1; continue; }
-    if ((atomicOr (&seen[s >> 5], 1u << (s & 31)) >> (s & 31)) & 1u) bad |= 1;   // ns positions on ns samples: one sample left out is one sample twice
+    if (seen_twice (seen, s)) bad |= 1;
     pos[s] = (unsigned short) p;
   }
   for (int k = tid; k < n_rn; k += 1024) {
     const TreeNode nd = rn[k];
-    if (!(nd.size >= 2 && nd.size <= ns && nd.first >= 0 && nd.first <= ns - nd.size)) { bad |= 2; continue; }
+    if (!tree_node_ok (nd, ns)) { bad |= 2; continue; }
     const u32 key = (u32) nd.first << 13 | (u32) nd.size;
     for (u32 at = csup_place (key); ; at = (at + 1) & (CSUP_PLACES - 1)) {   // (fewer nodes than half the places: a free one comes)
       const u32 old = atomicCAS (&places[at], 0u, key);
@@ -11175,13 +11195,13 @@ void clade_support_kernel (const TreeNode *__restrict__ nodes, int n_nodes, cons
   for (int p = tid; p < ns; p += 1024) {
     const int s = order[p];
     if (s < 0 || s >= ns) { bad |= 1; qp[p] = 0; continue; }
-    if ((atomicOr (&seen[s >> 5], 1u << (s & 31)) >> (s & 31)) & 1u) bad |= 1;
+    if (seen_twice (seen, s)) bad |= 1;
     qp[p] = pos[s];
   }
   __syncthreads ();
   for (int j = tid >> 6; j < n_nodes; j += 16) {        // a wavefront per node of the base
     const TreeNode nd = nodes[j];
-    if (!(nd.size >= 2 && nd.size <= ns && nd.first >= 0 && nd.first <= ns - nd.size)) { bad |= 2; continue; }
+    if (!tree_node_ok (nd, ns)) { bad |= 2; continue; }
     int lo = CLD_MAX, hi = -1;
     for (int p = nd.first + lane; p < nd.first + nd.size; p += 64) { const int v = qp[p]; lo = min (lo, v); hi = max (hi, v); }
     for (int o = 32; o; o >>= 1) { lo = min (lo, __shfl_xor (lo, o)); hi = max (hi, __shfl_xor (hi, o)); }
@@ -11212,18 +11232,13 @@ extern "C" long tjamd_clade_support (tjamd_counter *c, const tjamd_tree_node *d_
   if (!c) return -set_err (TJAMD_ERR_ARG, "%s: null counter", fn);
   if (n_samples < 1 || n_samples > CLD_MAX) return -set_err (TJAMD_ERR_ARG, "%s: n_samples %d outside 1..4096", fn, n_samples);
   if (n_nodes < 0 || n_nodes > CLD_MAX) return -set_err (TJAMD_ERR_ARG, "%s: n_nodes %d outside 0..4096", fn, n_nodes);
-  if (n_replicates < 1 || n_replicates > 4096) return -set_err (TJAMD_ERR_ARG, "%s: n_replicates %d outside 1..4096", fn, n_replicates);
+  if (const int bad = replicates_arg (fn, n_replicates)) return -bad;
   if (!d_order || !d_rep_order) return -set_err (TJAMD_ERR_ARG, "%s: null d_order or d_rep_order", fn);
   if (!h_rep_n_nodes) return -set_err (TJAMD_ERR_ARG, "%s: null h_rep_n_nodes", fn);
   if (n_nodes > 0 && (!d_nodes || !d_support)) return -set_err (TJAMD_ERR_ARG, "%s: null d_nodes or d_support", fn);
-  for (int r = 0; r < n_replicates; r++) {
-    if (h_rep_n_nodes[r] < 0 || h_rep_n_nodes[r] > n_samples - 1)
-      return -set_err (TJAMD_ERR_ARG, "%s: replicate %d has %d nodes, outside 0..n_samples - 1 = %d", fn, r, h_rep_n_nodes[r], n_samples - 1);
-    if (h_rep_n_nodes[r] > 0 && !d_rep_nodes) return -set_err (TJAMD_ERR_ARG, "%s: null d_rep_nodes", fn);
-  }
-  if (tjamd_device_count () <= 0) return -set_err (TJAMD_ERR_NO_DEVICE, "%s: TJAMD_ERR_NO_DEVICE: no HIP device visible (the clades are compared on the device; no CPU fallback)", fn);
+  if (const int bad = rep_nodes_args (fn, h_rep_n_nodes, n_replicates, n_samples, d_rep_nodes, nullptr)) return -bad;
   Stage st (c, T_CLADE_SUPPORT);                        // (a refused call leaves no timing behind)
-  if (hipSetDevice (c->device) != hipSuccess) return -set_err (TJAMD_ERR_HIP, "hipSetDevice failed");
+  if (const int bad = st.enter (fn, "the clades are compared")) return -bad;
   int rc;
   if (n_nodes == 0) {                                   // no clade to ask about: no kernel
     rc = read_back (c, fn, nullptr, nullptr, 0);
@@ -11318,12 +11333,7 @@ __device__ __forceinline__ void tree_small (const Link *sl, int n_links, int ns,
   if (tid < 64) {                                       // the roots in the order of their smallest member
     const bool root = tid < ns && uf[tid] == tid;
     const int cn = root ? cnode[tid] : -1, mine = !root ? 0 : cn >= 0 ? nsz[cn] : 1;
-    int incl = mine;
-    #pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-      const int v = __shfl_up (incl, o);
-      if (tid >= o) incl += v;
-    }
+    const int incl = wave_inclusive_sum (mine, tid);
     if (root) { if (cn >= 0) nfi[cn] = incl - mine; else ord[incl - mine] = tid; }
   }
   __syncthreads ();
@@ -11465,13 +11475,12 @@ extern "C" long tjamd_replicate_trees (tjamd_counter *c, const tjamd_sample_dist
   if (!h_rep_n_nodes) return -set_err (TJAMD_ERR_ARG, "%s: null h_rep_n_nodes", fn);
   if (!d_rep_nodes && n_samples > 1) return -set_err (TJAMD_ERR_ARG, "%s: null d_rep_nodes", fn);
   if (n_samples < 1 || n_samples > LINK_MAX) return -set_err (TJAMD_ERR_ARG, "%s: n_samples %d outside 1..4096", fn, n_samples);
-  if (n_replicates < 1 || n_replicates > 4096) return -set_err (TJAMD_ERR_ARG, "%s: n_replicates %d outside 1..4096", fn, n_replicates);
+  if (const int bad = replicates_arg (fn, n_replicates)) return -bad;
   if (metric < TJAMD_LINK_DIFFER || metric > TJAMD_LINK_DIFFER_RATE) return -set_err (TJAMD_ERR_ARG, "%s: metric %d outside 0..2", fn, metric);
   if (min_both < 1) return -set_err (TJAMD_ERR_ARG, "%s: min_both %d below 1", fn, min_both);
   if (linkage != TJAMD_TREE_SINGLE && linkage != TJAMD_AGGL_COMPLETE && linkage != TJAMD_AGGL_AVERAGE) return -set_err (TJAMD_ERR_ARG, "%s: linkage %d outside 0..2", fn, linkage);
-  if (tjamd_device_count () <= 0) return -set_err (TJAMD_ERR_NO_DEVICE, "%s: TJAMD_ERR_NO_DEVICE: no HIP device visible (the trees are built on the device; no CPU fallback)", fn);
   Stage st (c, T_REPLICATE_TREES);                      // (a refused call leaves no timing behind)
-  if (hipSetDevice (c->device) != hipSuccess) return -set_err (TJAMD_ERR_HIP, "hipSetDevice failed");
+  if (const int bad = st.enter (fn, "the trees are built")) return -bad;
   const int ns = n_samples, R = n_replicates;
   int rc;
   if (ns == 1) {                                        // one sample: no pair, no kernel; every order is the sample 0
@@ -11638,19 +11647,14 @@ void cons_records_kernel (ConsIn A, u64 key_mask, unsigned short *__restrict__ p
       const int s = ro[p];
       if (s < 0 || s >= ns) bad |= 1;
       else {
-        if ((atomicOr (&seen[s >> 5], 1u << (s & 31)) >> (s & 31)) & 1u) bad |= 1;   // ns positions on ns samples: one sample left out is one sample twice
+        if (seen_twice (seen, s)) bad |= 1;
         pos_out[(long) r * ns + s] = (unsigned short) p;
         h = boot_mix (CONS_SALT + (u64) s);
       }
     }
     total += h; run[q] = total;
   }
-  u64 incl = total;
-  #pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const u64 v = __shfl_up (incl, o);
-    if (lane >= o) incl += v;
-  }
+  const u64 incl = wave_inclusive_sum (total, lane);
   if (lane == 63) wsum[wave] = incl;
   __syncthreads ();
   u64 base = incl - total;
@@ -11660,13 +11664,13 @@ void cons_records_kernel (ConsIn A, u64 key_mask, unsigned short *__restrict__ p
   for (int q = 0; q < 4; q++) if (tid * 4 + q < ns) pre[tid * 4 + q + 1] = base + run[q];
   for (int k = tid; k < n_rn; k += 1024) {
     const TreeNode nd = rn[k];
-    if (!(nd.size >= 2 && nd.size <= ns && nd.first >= 0 && nd.first <= ns - nd.size)) bad |= 2;
+    if (!tree_node_ok (nd, ns)) bad |= 2;
     else atomicMax (&far[nd.first], nd.first + nd.size);
   }
   __syncthreads ();
   for (int k = wave; k < n_rn; k += 16) {               // a wavefront per node
     const TreeNode nd = rn[k];
-    const bool ok = nd.size >= 2 && nd.size <= ns && nd.first >= 0 && nd.first <= ns - nd.size;
+    const bool ok = tree_node_ok (nd, ns);
     u64 kk = 0;
     if (ok) {
       const int end = nd.first + nd.size;
@@ -11874,20 +11878,14 @@ extern "C" long tjamd_consensus_tree (tjamd_counter *c, const tjamd_tree_node *d
   if (!h_rep_n_nodes) return -set_err (TJAMD_ERR_ARG, "%s: null h_rep_n_nodes", fn);
   if (!d_order) return -set_err (TJAMD_ERR_ARG, "%s: null d_order", fn);
   if (n_samples < 1 || n_samples > CLD_MAX) return -set_err (TJAMD_ERR_ARG, "%s: n_samples %d outside 1..4096", fn, n_samples);
-  if (n_replicates < 1 || n_replicates > 4096) return -set_err (TJAMD_ERR_ARG, "%s: n_replicates %d outside 1..4096", fn, n_replicates);
+  if (const int bad = replicates_arg (fn, n_replicates)) return -bad;
   if (!d_nodes && n_samples > 1) return -set_err (TJAMD_ERR_ARG, "%s: null d_nodes", fn);
   long n = 0;                                           // the clades of the call
-  for (int r = 0; r < n_replicates; r++) {
-    if (h_rep_n_nodes[r] < 0 || h_rep_n_nodes[r] > n_samples - 1)
-      return -set_err (TJAMD_ERR_ARG, "%s: replicate %d has %d nodes, outside 0..n_samples - 1 = %d", fn, r, h_rep_n_nodes[r], n_samples - 1);
-    if (h_rep_n_nodes[r] > 0 && !d_rep_nodes) return -set_err (TJAMD_ERR_ARG, "%s: null d_rep_nodes", fn);
-    n += h_rep_n_nodes[r];
-  }
+  if (const int bad = rep_nodes_args (fn, h_rep_n_nodes, n_replicates, n_samples, d_rep_nodes, &n)) return -bad;
   if (min_count > n_replicates || 2l * min_count <= n_replicates)
     return -set_err (TJAMD_ERR_ARG, "%s: min_count %d outside %d..%d (more than half of the %d replicates)", fn, min_count, n_replicates / 2 + 1, n_replicates, n_replicates);
-  if (tjamd_device_count () <= 0) return -set_err (TJAMD_ERR_NO_DEVICE, "%s: TJAMD_ERR_NO_DEVICE: no HIP device visible (the clades are classed on the device; no CPU fallback)", fn);
   Stage st (c, T_CONSENSUS_TREE);                       // (a refused call leaves no timing behind)
-  if (hipSetDevice (c->device) != hipSuccess) return -set_err (TJAMD_ERR_HIP, "hipSetDevice failed");
+  if (const int bad = st.enter (fn, "the clades are classed")) return -bad;
   const int ns = n_samples, R = n_replicates;
   int rc;
   if (ns == 1) {                                        // one sample: no clade, no kernel

@@ -36,7 +36,9 @@ ERR_ARG = 3
 DIST, NODE, LINK = tj.SAMPLE_DISTANCE_DTYPE, tj.TREE_NODE_DTYPE, tj.LINK_DTYPE
 
 with open(os.path.join(ROOT, "tatajuba_amd", "csrc", "hopo_device.hip")) as _src:
-    BATCH = int(re.search(r"^#define SDISTW_BATCH (\d+)\s", _src.read(), re.M).group(1))
+    _text = _src.read()
+    BATCH = int(re.search(r"^#define SDISTW_BATCH (\d+)\s", _text, re.M).group(1))
+    SDIST_CELLS = int(re.search(r"^#define SDIST_CELLS (\d+)\s", _text, re.M).group(1))
 assert BATCH == 2                                        # the replicate counts below stand on both sides of it
 REPLICATE_COUNTS = (1, BATCH, BATCH + 1, 2 * BATCH + 1)
 
@@ -205,13 +207,57 @@ def test_hand_case(counter):
     check_weighted(got, restate_sample_distances_weighted(sites, alleles, genotype, [HAND_WEIGHTS, [1, 1, 1], [0, 0, 0]]))
 
 
-@pytest.mark.parametrize("ns,n_sites", [(3, 256), (17, 63), (65, 100), (130, 150)])
-def test_one_replicate_of_ones_is_the_unweighted_matrix(counter, one_block_counter, ns, n_sites):
+# one site, and one site more than a chunk (SDIST_CELLS / edge sites), at the edges 8, 16 and 32: the two entries share the
+# decomposition, the cut of the scratch and the summing launch, by one slice and by two
+EDGE_SHAPES = [(ns, n) for ns, edge in ((2, 8), (9, 16), (17, 32)) for n in (1, SDIST_CELLS // edge + 1)]
+assert EDGE_SHAPES == [(2, 1), (2, 257), (9, 1), (9, 129), (17, 1), (17, 65)]
+
+
+@pytest.mark.parametrize("ns,n_sites", [(3, 256), (17, 63), (65, 100), (130, 150)] + EDGE_SHAPES)
+def test_one_replicate_of_ones_is_the_unweighted_matrix(counter, one_block_counter, twelve_block_counter, ns, n_sites):
+    """the natural decomposition (a second chunk is a second slice), one workgroup aimed at (never split), and twelve (split
+    wherever there are two chunks, 130 samples included)"""
     sites, alleles, g = corpus(ns, n_sites)[:3]
-    for c in (counter, one_block_counter):
+    want = restate_sample_distances(sites, alleles, g)
+    for c in (counter, one_block_counter, twelve_block_counter):
         plain = dev_distances(c, sites, alleles, g, ns)
+        check_distances(plain, want)
         got = dev_weighted(c, sites, alleles, g, ns, np.ones((1, n_sites), np.int32))
         assert isinstance(got, np.ndarray) and got[0].tobytes() == plain.tobytes()
+
+
+def test_both_entries_report_the_shared_refusals_alike(counter):
+    """each error bit of the check pass that the two entries share (16, 8, 32, 64, 128, 1), raised once on 3 sites x 2 samples
+    through both: one code, one text behind the entry's name, nothing written"""
+    ns, n_sites = 2, 3
+    sites, alleles, g = fabricate(n_sites, ns, np.random.RandomState(5), n_alleles=[2] * n_sites, p_missing=0.0)
+    ones = np.ones((1, n_sites), np.int32)
+    plain = dev_distances(counter, sites, alleles, g, ns)
+    check_distances(plain, restate_sample_distances(sites, alleles, g))
+    assert dev_weighted(counter, sites, alleles, g, ns, ones)[0].tobytes() == plain.tobytes()
+    cases = [("a site has n_alleles < 1", "sites", "n_alleles", 1, 0),
+             ("first_allele and n_alleles of the sites do not chain from 0 to 6", "sites", "first_allele", 1, 3),
+             ("an allele's site is not the site that holds it", "alleles", "site", 4, 1),
+             ("an allele's alt_length is outside 0..1023", "alleles", "alt_length", 5, 1024),
+             ("a site's ref_length is below 0", "sites", "ref_length", 2, -1),
+             ("a genotype cell is below -1 or above its site's n_alleles", "genotype", None, (1, 1), -2)]
+    for msg, which, field, idx, value in cases:
+        s, a, gg = sites.copy(), alleles.copy(), g.copy()
+        if which == "genotype":
+            gg[idx] = value
+        else:
+            (s if which == "sites" else a)[field][idx] = value
+        with pytest.raises(ValueError):
+            restate_sample_distances(s, a, gg)
+        texts = []
+        for name, got in (("tjamd_sample_distances", dev_distances(counter, s, a, gg, ns)),
+                          ("tjamd_sample_distances_weighted", dev_weighted(counter, s, a, gg, ns, ones))):
+            rc, err, buf = got
+            assert rc == -ERR_ARG and err.startswith(name + ": "), (msg, name, rc, err)
+            assert buf.untouched(), (msg, name)                               # nothing was written
+            texts.append(err[len(name):])
+        assert texts[0] == texts[1] == ": " + msg, (msg, texts)
+    assert dev_weighted(counter, sites, alleles, g, ns, ones)[0].tobytes() == plain.tobytes()     # the counter serves the next good call
 
 
 @pytest.mark.parametrize("ns,n_sites", [(8, 257), (33, 63), (130, 150)])

@@ -484,3 +484,50 @@ def test_clade_support_checks_its_arguments_without_a_gpu():
             assert got == -ERR_NO_DEVICE and err.startswith("tjamd_clade_support") and "TJAMD_ERR_NO_DEVICE" in err, (kw, got, err)
     assert out.untouched()
     out.check("d_support")
+
+
+def test_both_distance_entries_share_their_refusals_without_a_gpu():
+    """every refusal that tjamd_sample_distances and tjamd_sample_distances_weighted share ahead of the device, by the same bad
+    arguments through both (the weighted entry otherwise valid, one replicate): one code, one text behind the entry's name; the
+    weighted entry's own three refusals come only where the shared ones pass"""
+    L = tj.lib()
+    fake = C.c_void_p(0x1000)                      # never dereferenced: each call below fails its argument checks first
+    out = GuardedHost(64 * DIST.itemsize)
+    names = ("tjamd_sample_distances", "tjamd_sample_distances_weighted")
+
+    def call(weighted, sites=fake, n_sites=3, alleles=fake, n_alleles=4, gt=fake, ns=2, null_out=False, w=fake, n_rep=1):
+        args = (fake, sites, n_sites, alleles, n_alleles, gt, ns, None if null_out else out.c)
+        rc = L.tjamd_sample_distances_weighted(*args, w, n_rep) if weighted else L.tjamd_sample_distances(*args)
+        err = L.tjamd_last_error().decode()
+        assert err.startswith(names[weighted] + ": "), err
+        return rc, err[len(names[weighted]):]
+
+    shared = [({"null_out": True}, "null d_out"),
+              ({"n_sites": -1}, "n_sites -1, n_alleles 4: a count below 0"), ({"n_alleles": -1}, "n_sites 3, n_alleles -1: a count below 0"),
+              ({"sites": None}, "null site, allele or genotype buffer"), ({"alleles": None}, "null site, allele or genotype buffer"),
+              ({"gt": None}, "null site, allele or genotype buffer"),
+              ({"ns": 0}, "n_samples 0 outside 1..4096"), ({"ns": 4097}, "n_samples 4097 outside 1..4096"),
+              ({"n_alleles": 2}, "2 alleles for 3 sites (a site has at least one)"),
+              ({"n_alleles": 1 << 31}, "2147483648 alleles: 2^31 or more"),
+              ({"n_sites": 1 << 19, "n_alleles": 1 << 19, "ns": 4096}, "524288 sites x 4096 samples: 2^31 cells or more")]
+    own = [({"w": None}, "null d_weights"), ({"n_rep": 0}, "n_replicates 0 outside 1..4096"), ({"n_rep": 4097}, "n_replicates 4097 outside 1..4096"),
+           ({"n_sites": 1 << 19, "n_alleles": 1 << 19, "n_rep": 4096}, "4096 replicates x 524288 sites: 2^31 weights or more")]
+    for kw, msg in shared:
+        plain, weighted = call(False, **kw), call(True, **kw)
+        assert plain == weighted and plain == (-ERR_ARG, ": " + msg), (kw, plain, weighted)
+        n_both = 0
+        for more, _ in own:                        # a shared refusal is named before any of the weighted entry's own
+            if set(more) & set(kw):                # (the two bad arguments are different ones)
+                continue
+            both = dict(more, **kw)
+            assert call(True, **both) == weighted, (both, weighted)
+            n_both += 1
+        assert n_both >= 3, kw
+    for kw, msg in own:                            # ... which come where the shared checks pass
+        got = call(True, **kw)
+        assert got == (-ERR_ARG, ": " + msg), (kw, got)
+        if tj.device_count() == 0:                 # the same arguments pass every check of the plain entry: it asks for the device
+            rc, err = call(False, **{k: v for k, v in kw.items() if k not in ("w", "n_rep")})
+            assert rc == -ERR_NO_DEVICE and "TJAMD_ERR_NO_DEVICE" in err, (kw, rc, err)
+    assert out.untouched()
+    out.check("d_out")
