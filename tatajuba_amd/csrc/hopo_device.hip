@@ -4134,6 +4134,8 @@ struct Stage
   void end () { (void) t->end (c->stream); }
   void done () { t->timed = true; }
 };
+// the getter of a slot's last interval: milliseconds, -1.0 for a null counter or where the last call left no timing
+#define TJ_LAST_MS(name, slot) extern "C" double name (tjamd_counter *c) { return c ? c->timer[slot].ms (c->device) : -1.0; }
 
 // The scratch of one call, cut from c->lc_work: each piece is listed once, in the order it lies in the block, on a 256-byte
 // boundary.  take () only notes the caller's pointer and the piece's offset; commit () grows the block once (which may
@@ -4157,14 +4159,17 @@ struct ScratchCut
   }
 };
 
-// The 64 flag words of a call as the last piece of its cut: takes them, commits the cut and clears them on the counter's stream.
-static int commit_with_flags (ScratchCut &cut, tjamd_counter *c, const char *fn, int *&flags)
+// The 64 flag words of a call (ints, or the type of the call's count) as the last piece of its cut: takes them, commits the cut and
+// clears them on the counter's stream.  flags_alone: the same for a call with no other scratch, the words at the head of c->lc_work.
+template <class T> static int commit_with_flags (ScratchCut &cut, tjamd_counter *c, const char *fn, T *&flags)
 {
+  static_assert (sizeof (T) == 4, "a flag word");
   cut.take (flags, 64);
   const int rc = cut.commit (c);
   if (rc) return rc;
   return hipMemsetAsync (flags, 0, 256, c->stream) == hipSuccess ? TJAMD_OK : set_err (TJAMD_ERR_HIP, "%s: memset failed", fn);
 }
+template <class T> static int flags_alone (tjamd_counter *c, const char *fn, T *&flags) { ScratchCut cut; return commit_with_flags (cut, c, fn, flags); }
 
 // The tail of a call, behind its stage's end (): the error of its launches, the copy of `words` 32-bit words from d to the
 // host (none: the wait alone) on the counter's stream, the wait for the stream.  Decoding the words is the caller's.
@@ -4865,6 +4870,8 @@ static int exclusive_scan (tjamd_counter *c, const u32 *in, u32 *out, long n, u3
   HIPCHK (hipGetLastError ());
   return TJAMD_OK;
 }
+// the same in the counter's own scan scratch, which the caller has sized with scan_tmp_words
+static int exclusive_scan (tjamd_counter *c, const u32 *in, u32 *out, long n, u32 *total_out) { return exclusive_scan (c, in, out, n, total_out, (u32 *) c->scan_tmp.p, c->scan_tmp.cap / 4); }
 
 static size_t scan_tmp_words (long n)
 {
@@ -4884,7 +4891,7 @@ static int radix_sort_records (tjamd_counter *c, u64 *&a, u64 *&b, long n)
   for (int p = 0; p < passes; p++) {
     hipLaunchKernelGGL (radix_count_kernel, dim3 (nblk), dim3 (256), 0, c->stream, (const u64 *) a, n, p, c->k, (u32 *) c->hist.p, nblk);
     HIPCHK (hipGetLastError ());
-    rc = exclusive_scan (c, (const u32 *) c->hist.p, (u32 *) c->hist.p, nh, nullptr, (u32 *) c->scan_tmp.p, c->scan_tmp.cap / 4);
+    rc = exclusive_scan (c, (const u32 *) c->hist.p, (u32 *) c->hist.p, nh, nullptr);
     if (rc) return rc;
     hipLaunchKernelGGL (radix_scatter_kernel, dim3 (nblk), dim3 (256), 0, c->stream, (const u64 *) a, b, n, p, c->k, (const u32 *) c->hist.p, nblk);
     HIPCHK (hipGetLastError ());
@@ -4920,7 +4927,7 @@ static int finalise_radix (tjamd_counter *c, long n1, int min_coverage)
   u32 *keep = (u32 *) c->keep.p, *outpos = (u32 *) c->outpos.p;
   hipLaunchKernelGGL (seg_heads_kernel, dim3 (grid_for (n1)), dim3 (256), 0, c->stream, kept, n1, flags, 1);
   HIPCHK (hipGetLastError ());
-  rc = exclusive_scan (c, flags, segid, n1, &c->d_fin->n_ctx, (u32 *) c->scan_tmp.p, c->scan_tmp.cap / 4);
+  rc = exclusive_scan (c, flags, segid, n1, &c->d_fin->n_ctx);
   if (rc) return rc;
   hipLaunchKernelGGL (seg_headpos_kernel, dim3 (grid_for (n1)), dim3 (256), 0, c->stream, (const u32 *) flags, (const u32 *) segid, n1, headpos);
   HIPCHK (hipGetLastError ());
@@ -4930,7 +4937,7 @@ static int finalise_radix (tjamd_counter *c, long n1, int min_coverage)
   HIPCHK (hipMemcpyAsync (c->h_fin, c->d_fin, sizeof (FinCounts), hipMemcpyDeviceToHost, c->stream));
   HIPCHK (hipStreamSynchronize (c->stream));
   const long n_ctx = c->h_fin->n_ctx;
-  rc = exclusive_scan (c, keep, outpos, n_ctx, &c->d_fin->n_idx, (u32 *) c->scan_tmp.p, c->scan_tmp.cap / 4);
+  rc = exclusive_scan (c, keep, outpos, n_ctx, &c->d_fin->n_idx);
   if (!rc) rc = ensure (c->idx_i, (size_t) n_ctx * 4, c->stream);
   if (!rc) rc = ensure (c->idx_f, (size_t) n_ctx * 4, c->stream);
   if (rc) return rc;
@@ -5205,7 +5212,7 @@ extern "C" double tjamd_last_scan_ms (tjamd_counter *c)
 }
 
 // the kernels of the last tjamd_merge_samples on this counter (bin path), HIP events on its stream
-extern "C" double tjamd_last_merge_ms (tjamd_counter *c) { return c ? c->timer[T_MERGE].ms (c->device) : -1.0; }
+TJ_LAST_MS (tjamd_last_merge_ms, T_MERGE)
 
 // 1: one-word records go through the record log and partition_log_kernel (k <= 12, the default); 0: every scan kernel
 // partitions its records itself
@@ -5221,7 +5228,7 @@ extern "C" double tjamd_last_partition_ms (tjamd_counter *c)
   return (double) ms;
 }
 
-extern "C" double tjamd_last_finalise_ms (tjamd_counter *c) { return c ? c->timer[T_FIN].ms (c->device) : -1.0; }
+TJ_LAST_MS (tjamd_last_finalise_ms, T_FIN)
 
 extern "C" long tjamd_last_scan_launches (tjamd_counter *c) { return c ? c->last_scan_launches : -1; }
 extern "C" long tjamd_plan_mismatches (tjamd_counter *c) { return c ? c->plan_mismatches : -1; }
@@ -5499,7 +5506,7 @@ static int queue_group_heads (tjamd_counter *c, const char *who, const u64 *keys
                                 head, (const u32 *) c->keep.p, (int *) c->grp_jt.p, count_of, lev_of);
     if (n_cand) *n_cand = (long) nc;
   }
-  return exclusive_scan (c, (const u32 *) head, (u32 *) c->outpos.p, n, total, (u32 *) c->scan_tmp.p, c->scan_tmp.cap / 4);
+  return exclusive_scan (c, (const u32 *) head, (u32 *) c->outpos.p, n, total);
 }
 
 extern "C" long tjamd_group_contexts (tjamd_counter *c, int max_distance_per_flank, int *group_of, tjamd_group *groups, long capacity)
@@ -5625,7 +5632,7 @@ static int ensure_tract_id_scratch (tjamd_counter *c, long n)
 static int queue_tract_ids (tjamd_counter *c, const void *d_keys, long n, int *ids, u32 *total)
 {
   hipLaunchKernelGGL (tract_head_kernel, dim3 (grid_for (n)), dim3 (256), 0, c->stream, (const u64 *) d_keys, n, (u32 *) c->flags.p);
-  int rc = exclusive_scan (c, (const u32 *) c->flags.p, (u32 *) c->outpos.p, n, total, (u32 *) c->scan_tmp.p, c->scan_tmp.cap / 4);
+  int rc = exclusive_scan (c, (const u32 *) c->flags.p, (u32 *) c->outpos.p, n, total);
   if (rc) return rc;
   hipLaunchKernelGGL (tract_id_kernel, dim3 (grid_for (n)), dim3 (256), 0, c->stream, (const u32 *) c->outpos.p, (const u32 *) c->flags.p, n, ids);
   if (hipGetLastError () != hipSuccess) return set_err (TJAMD_ERR_HIP, "tract id launch failed");
@@ -5770,13 +5777,21 @@ __device__ __forceinline__ void write_listed_sample (long i, int s, int ns, cons
   if (n_context) n_context[i * ns + s] = nc;
 }
 
+// The segment mapping of the kernels that give an item (a tract, a list entry, a row) S lanes, S a power of two that divides the
+// workgroup: declares the thread's lane in its segment, its segment's first item and the stride to the next (the grid's segments).
+// A macro: inside a function the compiler reads blockDim the long way, and every kernel that called one came out longer.
+#define SEGMENT_MAP(S, lane, first, stride) \
+  const int lane = threadIdx.x & ((S) - 1); \
+  const long stride = (long) gridDim.x * (blockDim.x / (S)); \
+  const long first = (blockIdx.x * (long) blockDim.x + threadIdx.x) / (S);
+
 __global__ __launch_bounds__ (256)
 void tract_stats_kernel (const u64 *__restrict__ keys, const int *__restrict__ counts, long n_union, int ns, int S, const int *__restrict__ cov,
                          const int *__restrict__ ref_len, TractSummary *__restrict__ sum, long n_bound, int *__restrict__ err, u32 *__restrict__ varflag)
 { // n_bound: the tracts the caller has room for; the tracts there are (err[1] + 1) and whether the ids were good (err[0] == 0)
   // come from tract_starts_kernel.  Every flag below n_bound is written (0 outside the tracts), so the scan behind is sound.
   // err[2]: set here if a tract's rows lie outside the union.
-  const int lane = threadIdx.x & (S - 1);
+  const int lane = threadIdx.x & (S - 1);                // (SEGMENT_MAP written out: the load of n_tracts stands before the division)
   const long segs_per_grid = (long) gridDim.x * (blockDim.x / S);
   const long n_tracts = err[0] ? 0 : min ((long) err[1] + 1, n_bound);
   for (long t = (blockIdx.x * (long) blockDim.x + threadIdx.x) / S; t < n_bound; t += segs_per_grid) {   // (uniform across a segment)
@@ -5815,9 +5830,8 @@ void tract_sample_stats_kernel (const u64 *__restrict__ keys, const int *__restr
                                 const TractSummary *__restrict__ sum, long n_tracts, const int *__restrict__ list, long n_list,
                                 double *__restrict__ values, int *__restrict__ modal_len, int *__restrict__ n_context, int *__restrict__ err)
 {
-  const int lane = threadIdx.x & (S - 1);
-  const long segs_per_grid = (long) gridDim.x * (blockDim.x / S);
-  for (long i = (blockIdx.x * (long) blockDim.x + threadIdx.x) / S; i < n_list; i += segs_per_grid) {
+  SEGMENT_MAP (S, lane, first_item, segs_per_grid)
+  for (long i = first_item; i < n_list; i += segs_per_grid) {
     long first, end;
     listed_tract_rows (sum, n_tracts, n_union, list[i], lane, err, first, end);
     for (int s = lane; s < ns; s += S) {
@@ -5906,7 +5920,7 @@ extern "C" long tjamd_tract_stats (tjamd_counter *c, const void *d_keys, const v
   hipLaunchKernelGGL (tract_stats_kernel, dim3 (tract_grid (n_bound, S)), dim3 (256), 0, c->stream, (const u64 *) d_keys, (const int *) d_counts, n_union,
                       n_samples, S, (const int *) c->ts_cov.p, d_ref_length, (TractSummary *) d_summary, n_bound, err, (u32 *) c->flags.p);
   if (hipGetLastError () != hipSuccess) return -set_err (TJAMD_ERR_HIP, "tract stats launch failed");
-  rc = exclusive_scan (c, (const u32 *) c->flags.p, (u32 *) c->outpos.p, n_bound, total, (u32 *) c->scan_tmp.p, c->scan_tmp.cap / 4);
+  rc = exclusive_scan (c, (const u32 *) c->flags.p, (u32 *) c->outpos.p, n_bound, total);
   if (rc) return -rc;
   if (d_var) hipLaunchKernelGGL (tract_var_scatter_kernel, dim3 (grid_for (n_bound)), dim3 (256), 0, c->stream, (const u32 *) c->flags.p, (const u32 *) c->outpos.p,
                                  n_bound, d_var);
@@ -5947,7 +5961,7 @@ extern "C" long tjamd_tract_sample_stats (tjamd_counter *c, const void *d_keys, 
   return n_list;
 }
 
-extern "C" double tjamd_last_tract_stats_ms (tjamd_counter *c) { return c ? c->timer[T_TRACT].ms (c->device) : -1.0; }
+TJ_LAST_MS (tjamd_last_tract_stats_ms, T_TRACT)
 
 // ---------------------------------------------------------------------------------------------------------------
 // N6: tracts across samples by grouping (reference: new_genomic_context_list's grouping, src/context_histogram.c:245-270,
@@ -5992,9 +6006,8 @@ __device__ __forceinline__ u64 shfl_xor64 (u64 x, int o, int width = 64) { const
 __global__ __launch_bounds__ (256)
 void union_totals_kernel (const int *__restrict__ counts, long n, int ns, int S, long long *__restrict__ total)
 {
-  const int lane = threadIdx.x & (S - 1);
-  const long segs_per_grid = (long) gridDim.x * (blockDim.x / S);
-  for (long r = (blockIdx.x * (long) blockDim.x + threadIdx.x) / S; r < n; r += segs_per_grid) {   // (uniform across a segment)
+  SEGMENT_MAP (S, lane, first_item, segs_per_grid)
+  for (long r = first_item; r < n; r += segs_per_grid) {   // (uniform across a segment)
     long long t = 0;
     for (int s = lane; s < ns; s += S) t += counts[r * ns + s];
     for (int o = 1; o < S; o <<= 1) t += __shfl_xor (t, o, S);
@@ -6166,9 +6179,8 @@ void union_tract_stats_kernel (const u64 *__restrict__ keys, const int *__restri
                                long long *__restrict__ g_cnt, int *__restrict__ g_len, int *__restrict__ err)
 {
   UT_LANE_SLOTS (FULL, g_cnt, g_len)
-  const int lane = threadIdx.x & (S - 1);
-  const long segs_per_grid = (long) gridDim.x * (blockDim.x / S);
-  for (long t = gthread / S; t < n_tracts; t += segs_per_grid) {   // (uniform across a segment)
+  SEGMENT_MAP (S, lane, first_item, segs_per_grid)
+  for (long t = first_item; t < n_tracts; t += segs_per_grid) {   // (uniform across a segment)
     if (FULL && !fallback[t]) continue;
     const UnionTract u = tracts[t];
     const long first = u.first, end = first + (long) u.n_rows;
@@ -6212,9 +6224,8 @@ void union_tract_sample_stats_kernel (const u64 *__restrict__ keys, const int *_
                                       u32 *__restrict__ fallback, long long *__restrict__ g_cnt, int *__restrict__ g_len, int *__restrict__ err)
 {
   UT_LANE_SLOTS (FULL, g_cnt, g_len)
-  const int lane = threadIdx.x & (S - 1);
-  const long segs_per_grid = (long) gridDim.x * (blockDim.x / S);
-  for (long i = gthread / S; i < n_list; i += segs_per_grid) {
+  SEGMENT_MAP (S, lane, first_item, segs_per_grid)
+  for (long i = first_item; i < n_list; i += segs_per_grid) {
     if (FULL && !fallback[i]) continue;
     long first, end;
     listed_tract_rows (sum, n_tracts, n_union, list[i], lane, err, first, end);
@@ -6284,8 +6295,8 @@ extern "C" long tjamd_union_tract_stats (tjamd_counter *c, const void *d_keys, c
   launch (union_tract_stats_kernel<false>, tract_grid (nt, S));
   launch (union_tract_stats_kernel<true>, (unsigned) UT_FULL_BLOCKS);
   if (hipGetLastError () != hipSuccess) return -set_err (TJAMD_ERR_HIP, "%s: launch failed", fn);
-  rc = exclusive_scan (c, vf, (u32 *) c->outpos.p, nt, total, (u32 *) c->scan_tmp.p, c->scan_tmp.cap / 4);
-  if (!rc) rc = exclusive_scan (c, sf, (u32 *) c->headpos.p, nt, total + 1, (u32 *) c->scan_tmp.p, c->scan_tmp.cap / 4);
+  rc = exclusive_scan (c, vf, (u32 *) c->outpos.p, nt, total);
+  if (!rc) rc = exclusive_scan (c, sf, (u32 *) c->headpos.p, nt, total + 1);
   if (rc) return -rc;
   if (d_var) hipLaunchKernelGGL (tract_var_scatter_kernel, dim3 (grid_for (nt)), dim3 (256), 0, c->stream, (const u32 *) vf, (const u32 *) c->outpos.p, nt, d_var);
   if (d_sel) hipLaunchKernelGGL (tract_var_scatter_kernel, dim3 (grid_for (nt)), dim3 (256), 0, c->stream, (const u32 *) sf, (const u32 *) c->headpos.p, nt, d_sel);
@@ -6334,11 +6345,11 @@ extern "C" long tjamd_union_tract_sample_stats (tjamd_counter *c, const void *d_
 }
 
 // first launch to last of the last tjamd_union_tracts, the host's wait for the retry candidates included
-extern "C" double tjamd_last_union_tracts_ms (tjamd_counter *c) { return c ? c->timer[T_UNION].ms (c->device) : -1.0; }
+TJ_LAST_MS (tjamd_last_union_tracts_ms, T_UNION)
 
 extern "C" long tjamd_last_union_tract_candidates (tjamd_counter *c) { return c ? c->union_cand : -1; }
 
-extern "C" double tjamd_last_union_tract_stats_ms (tjamd_counter *c) { return c ? c->timer[T_UNION_STATS].ms (c->device) : -1.0; }
+TJ_LAST_MS (tjamd_last_union_tract_stats_ms, T_UNION_STATS)
 
 // Peer access between two devices of this process, asked for once per ordered pair: with it hipMemcpyPeerAsync moves the
 // bytes over xGMI directly, without it the runtime stages them through host memory.  Returns 1 direct, 0 staged;
@@ -6485,7 +6496,7 @@ static long merge_samples_radix (tjamd_counter *c, const void *d_records, long n
   if (a != (u64 *) c->rawlist.p) std::swap (c->rawlist, c->alt);
   u32 *flags = (u32 *) c->flags.p, *segid = (u32 *) c->segid.p;
   hipLaunchKernelGGL (seg_heads_kernel, dim3 (grid_for (n)), dim3 (256), 0, c->stream, (const u64 *) a, n, flags, 0);
-  rc = exclusive_scan (c, flags, segid, n, &c->d_fin->n_seg, (u32 *) c->scan_tmp.p, c->scan_tmp.cap / 4);
+  rc = exclusive_scan (c, flags, segid, n, &c->d_fin->n_seg);
   if (rc) return -rc;
   if (hipMemcpyAsync (c->h_fin, c->d_fin, sizeof (FinCounts), hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
       hipStreamSynchronize (c->stream) != hipSuccess) return -set_err (TJAMD_ERR_HIP, "merge failed: %s", hipGetErrorString (hipGetLastError ()));
@@ -6788,6 +6799,7 @@ struct RefEntry { u64 ctx0, ctx1; long long flat; int contig, pos, length, base,
 static_assert (sizeof (RefEntry) == 48 && sizeof (RefEntry) == sizeof (tjamd_ref_entry), "reference entry layout");
 struct Location { long long flat; int contig, pos, ref_length, mismatches, neg_strand, n_hits; };
 static_assert (sizeof (Location) == 32 && sizeof (Location) == sizeof (tjamd_location), "location layout");
+#define LC_NOWHERE Location {-1, -1, -1, 0, 0, 0, 0}     // a row or a tract that has no location: flat, contig and pos -1, the rest 0
 
 // The two orders of the index are arrays of three-word records (primary flank, secondary flank, word) sorted by
 // radix_sort_records: descending by (base, primary, secondary), entries of one key in ascending entry number -- which is
@@ -6807,11 +6819,38 @@ struct tjamd_reference
   bool has_seeds = false;
 };
 
+// a handle (`what`: its noun; N7's reference, N9's annotation, N11's coding table) lives on the counter's device
+static int on_counter_device (const char *fn, const char *what, int device, const tjamd_counter *c)
+{
+  return device == c->device ? TJAMD_OK : set_err (TJAMD_ERR_ARG, "%s: the %s lives on device %d, the counter on device %d", fn, what, device, c->device);
+}
 static int reference_of_counter (const char *fn, const tjamd_reference *ref, const tjamd_counter *c)
 { // the reference belongs to the counter: the same k, the same device (neither is null)
   if (ref->k != c->k) return set_err (TJAMD_ERR_ARG, "%s: the reference was built with k = %d, the counter has k = %d", fn, ref->k, c->k);
-  if (ref->device != c->device) return set_err (TJAMD_ERR_ARG, "%s: the reference lives on device %d, the counter on device %d", fn, ref->device, c->device);
-  return TJAMD_OK;
+  return on_counter_device (fn, "reference", ref->device, c);
+}
+
+// A genome stream from the host (N7's index, N11's coding table).  stream_refused: what can be said of it without a device, 0 or
+// the code with the message set.  upload_stream: its bytes into c->stage, grown here (which may wait for the counter's stream).
+static int stream_refused (const char *fn, const void *h_stream, size_t n_bytes)
+{
+  if (n_bytes && !h_stream) return set_err (TJAMD_ERR_ARG, "%s: null stream", fn);
+  return n_bytes < (size_t) 1 << 31 ? TJAMD_OK : set_err (TJAMD_ERR_CAPACITY, "%s: a stream of %zu bytes (positions are 32-bit)", fn, n_bytes);
+}
+static int upload_stream (tjamd_counter *c, const char *fn, const void *h_stream, size_t n_bytes)
+{
+  const int rc = ensure (c->stage, (n_bytes + 255) & ~(size_t) 255, c->stream);
+  if (rc || !n_bytes) return rc;
+  return hipMemcpyAsync (c->stage.p, h_stream, n_bytes, hipMemcpyHostToDevice, c->stream) == hipSuccess ? TJAMD_OK : set_err (TJAMD_ERR_HIP, "%s: copy to device failed", fn);
+}
+
+// Feature i of a host array against the number of contigs it may name (N9's table, N11's): 0, or the code with the message set.
+// (Per feature: N9's own rule, cls, keeps its place between one feature and the next.)
+static int feature_refused (const char *fn, long i, const tjamd_feature &x, long n_contigs)
+{
+  if (x.contig < 0 || (long) x.contig >= n_contigs) return set_err (TJAMD_ERR_ARG, "%s: feature %ld: contig %d outside [0, %ld)", fn, i, x.contig, n_contigs);
+  if (x.start < 1) return set_err (TJAMD_ERR_ARG, "%s: feature %ld: start %d < 1", fn, i, x.start);
+  return x.end >= x.start ? TJAMD_OK : set_err (TJAMD_ERR_ARG, "%s: feature %ld: end %d < start %d", fn, i, x.end, x.start);
 }
 
 // byte classes of the index: 0-3 the base of an ACGTU byte (either case), 4 the contig delimiter, 5 anything else
@@ -6908,8 +6947,7 @@ extern "C" tjamd_reference *tjamd_reference_create (tjamd_counter *c, const void
   static const char *fn = "tjamd_reference_create";
   if (tjamd_device_count () <= 0) { set_err (TJAMD_ERR_NO_DEVICE, "%s: TJAMD_ERR_NO_DEVICE: no HIP device visible (the index is built on the device; no CPU fallback)", fn); return NULL; }
   if (!c) { set_err (TJAMD_ERR_ARG, "%s: null counter", fn); return NULL; }
-  if (n_bytes && !h_stream) { set_err (TJAMD_ERR_ARG, "%s: null stream", fn); return NULL; }
-  if (n_bytes >= (size_t) 1 << 31) { set_err (TJAMD_ERR_CAPACITY, "%s: a stream of %zu bytes (positions are 32-bit)", fn, n_bytes); return NULL; }
+  if (stream_refused (fn, h_stream, n_bytes)) return NULL;
   HIPCHK_NULL (hipSetDevice (c->device));
   Stage st (c, T_REF);
   std::unique_ptr<tjamd_reference, void (*) (tjamd_reference *)> ref (new tjamd_reference (), tjamd_reference_destroy);
@@ -6919,22 +6957,20 @@ extern "C" tjamd_reference *tjamd_reference_create (tjamd_counter *c, const void
   ScratchCut cut;
   u32 *flag, *excl, *segpos, *nlflag, *nlex, *nlpos, *tot;
   cut.take (flag, n); cut.take (excl, n); cut.take (segpos, n + 1); cut.take (nlflag, n); cut.take (nlex, n); cut.take (nlpos, n + 1); cut.take (tot, 64);
-  if (cut.commit (c) || ensure (c->stage, ((size_t) n + 255) & ~(size_t) 255, c->stream) || ensure (c->scan_tmp, scan_tmp_words (n) * 4 + 64, c->stream)) return NULL;
+  if (cut.commit (c) || upload_stream (c, fn, h_stream, n_bytes) || ensure (c->scan_tmp, scan_tmp_words (n) * 4 + 64, c->stream)) return NULL;
   for (int i = 0; i < 4; i++)
     if (hipMalloc (&ref->owned[i], (size_t) n * (i ? 24 : sizeof (RefEntry))) != hipSuccess) { set_err (TJAMD_ERR_HIP, "%s: hipMalloc failed for %ld bytes of genome", fn, n); return NULL; }
-  const uint8_t *seq = (const uint8_t *) c->stage.p;
-  u32 *tmp = (u32 *) c->scan_tmp.p; const size_t tw = c->scan_tmp.cap / 4;
   u32 *n_seg = tot, *n_ent = tot + 1, *n_nl = tot + 2;
   const dim3 g (grid_for (n)), b (256);
-  if (hipMemcpyAsync (c->stage.p, h_stream, n_bytes, hipMemcpyHostToDevice, c->stream) != hipSuccess) { set_err (TJAMD_ERR_HIP, "%s: copy to device failed", fn); return NULL; }
+  const uint8_t *seq = (const uint8_t *) c->stage.p;
   st.begin ();
   hipLaunchKernelGGL (ref_seg_flag_kernel, g, b, 0, c->stream, seq, n, flag);
-  int rc = exclusive_scan (c, flag, excl, n, n_seg, tmp, tw);
+  int rc = exclusive_scan (c, flag, excl, n, n_seg);
   hipLaunchKernelGGL (ref_seg_pos_kernel, g, b, 0, c->stream, (const u32 *) flag, (const u32 *) excl, n, segpos);
   u32 *vflag = flag, *vex = excl;                       // (both free again once the segment positions are written)
   hipLaunchKernelGGL (ref_seg_class_kernel, g, b, 0, c->stream, seq, n, c->k, (const u32 *) segpos, (const u32 *) n_seg, vflag, nlflag);
-  if (!rc) rc = exclusive_scan (c, vflag, vex, n, n_ent, tmp, tw);
-  if (!rc) rc = exclusive_scan (c, nlflag, nlex, n, n_nl, tmp, tw);
+  if (!rc) rc = exclusive_scan (c, vflag, vex, n, n_ent);
+  if (!rc) rc = exclusive_scan (c, nlflag, nlex, n, n_nl);
   hipLaunchKernelGGL (ref_nlpos_kernel, g, b, 0, c->stream, (const u32 *) segpos, (const u32 *) n_seg, (const u32 *) nlflag, (const u32 *) nlex, n, nlpos);
   u64 *r0 = (u64 *) ref->owned[1], *r1 = (u64 *) ref->owned[2], *r2 = (u64 *) ref->owned[3];
   hipLaunchKernelGGL (ref_entry_kernel, g, b, 0, c->stream, seq, n, c->k, (const u32 *) segpos, (const u32 *) n_seg, (const u32 *) vflag, (const u32 *) vex,
@@ -6981,7 +7017,7 @@ extern "C" long tjamd_reference_download (const tjamd_reference *ref, tjamd_ref_
     return -set_err (TJAMD_ERR_HIP, "tjamd_reference_download: copy failed");
   return ref->n_entries;
 }
-extern "C" double tjamd_last_reference_ms (tjamd_counter *c) { return c ? c->timer[T_REF].ms (c->device) : -1.0; }
+TJ_LAST_MS (tjamd_last_reference_ms, T_REF)
 
 // ---- the lookup --------------------------------------------------------------------------------------------------
 // Thread mapping: a lane per query finds its two buckets (the entries with its base and its exact flank) by binary search
@@ -6991,6 +7027,24 @@ extern "C" double tjamd_last_reference_ms (tjamd_counter *c) { return c ? c->tim
 // the time of a wavefront is the sum of its long buckets over 64, not the longest one times 64.
 
 #define LC_LANE_WALK 16
+
+// The host path of both lookups behind their argument checks and the counter's device: the interval of `slot`, nothing to do for
+// no row, the count word cleared, the lookup's launch (which gets the word), the count read back and returned
+template <class Launch> static long lookup_rows (tjamd_counter *c, const char *fn, int slot, long n, Launch &&launch)
+{
+  Stage st (c, slot);
+  if (n == 0) return 0;
+  u32 *n_located, found = 0;
+  int rc = flags_alone (c, fn, n_located);
+  if (rc) return -rc;
+  st.begin ();
+  launch (n_located);
+  st.end ();
+  rc = read_back (c, fn, n_located, &found, 1);
+  if (rc) return -rc;
+  st.done ();
+  return (long) found;
+}
 
 // first record of ord[0, n) (descending by base, primary) that does not sort before / that sorts behind (base, primary)
 __device__ __forceinline__ long ord_bound (const u64 *__restrict__ ord, long n, u32 qb, u64 qp, bool behind)
@@ -7004,6 +7058,30 @@ __device__ __forceinline__ long ord_bound (const u64 *__restrict__ ord, long n, 
     if (before) lo = mid + 1; else hi = mid;
   }
   return lo;
+}
+
+// The range walk of both lookups, the mapping above, called by all 64 lanes: a lane's own range [lo, hi) and its NQ query words q;
+// try_record (i, q, best, hits) is the lookup's step for record i.  Of a long range the bounds and q are broadcast from its owner,
+// (best, hits) is reduced with shuffles and folded into the owner's.
+template <int NQ, class Try>
+__device__ __forceinline__ void lc_walk_range (int lane, long lo, long hi, const u64 (&q)[NQ], u64 &best, u32 &hits, Try try_record)
+{
+  const bool mine = hi - lo <= LC_LANE_WALK;
+  if (mine) for (long i = lo; i < hi; i++) try_record (i, q, best, hits);
+  u64 big = __ballot (!mine);
+  while (big) {                                         // the wavefront walks its long ranges together, one after the other
+    const int src = __ffsll ((long long) big) - 1;
+    big &= big - 1;
+    const long blo = __shfl (lo, src), bhi = __shfl (hi, src);
+    u64 bq[NQ];
+#pragma unroll
+    for (int w = 0; w < NQ; w++) bq[w] = __shfl (q[w], src);
+    u64 wb = ~0ull; u32 wh = 0;
+    for (long i = blo + lane; i < bhi; i += 64) try_record (i, bq, wb, wh);
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) { const u64 ob = __shfl_xor (wb, o); wb = ob < wb ? ob : wb; wh += __shfl_xor (wh, o); }
+    if (lane == src) { best = wb < best ? wb : best; hits += wh; }
+  }
 }
 
 // one record against a query's inexact flank: best = (mismatches << 32 | entry number), the smallest wins
@@ -7032,25 +7110,12 @@ void locate_kernel (const u64 *__restrict__ keys, long n, const u64 *__restrict_
 #pragma unroll
     for (int side = 0; side < 2; side++) {
       const u64 *__restrict__ ord = side ? ord1 : ord0;
-      const u64 qp = qc[side], qs = qc[1 - side];
+      const u64 qp = qc[side], qs[1] = {qc[1 - side]};
       long lo = 0, hi = 0;
       if (active) { lo = ord_bound (ord, n_ent, qb, qp, false); hi = ord_bound (ord, n_ent, qb, qp, true); }
-      const bool mine = hi - lo <= LC_LANE_WALK;
-      if (mine) for (long i = lo; i < hi; i++) locate_try (ord, i, qs, maxm, side == 1, best, hits);
-      u64 big = __ballot (!mine);
-      while (big) {                                     // the wavefront walks its long buckets together, one after the other
-        const int src = __ffsll ((long long) big) - 1;
-        big &= big - 1;
-        const long blo = __shfl (lo, src), bhi = __shfl (hi, src);
-        const u64 bqs = __shfl (qs, src);
-        u64 wb = ~0ull; u32 wh = 0;
-        for (long i = blo + lane; i < bhi; i += 64) locate_try (ord, i, bqs, maxm, side == 1, wb, wh);
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) { const u64 ob = __shfl_xor (wb, o); wb = ob < wb ? ob : wb; wh += __shfl_xor (wh, o); }
-        if (lane == src) { best = wb < best ? wb : best; hits += wh; }
-      }
+      lc_walk_range (lane, lo, hi, qs, best, hits, [&] (long i, const u64 (&q)[1], u64 &b, u32 &h) { locate_try (ord, i, q[0], maxm, side == 1, b, h); });
     }
-    Location o = {-1, -1, -1, 0, 0, 0, 0};
+    Location o = LC_NOWHERE;
     if (hits) {
       const RefEntry e = entries[best & 0xFFFFFFFFull];
       o = Location {e.flat, e.contig, e.pos, e.length, (int) (best >> 32), e.neg_strand, (int) hits};
@@ -7071,23 +7136,12 @@ extern "C" long tjamd_locate (tjamd_counter *c, const tjamd_reference *ref, cons
   if (n >= (1l << 31)) return -set_err (TJAMD_ERR_CAPACITY, "%s: %ld rows", fn, n);
   if (n > 0 && (!d_keys || !d_loc)) return -set_err (TJAMD_ERR_ARG, "%s: null key or location buffer", fn);
   if (hipSetDevice (c->device) != hipSuccess) return -set_err (TJAMD_ERR_HIP, "hipSetDevice failed");
-  Stage st (c, T_LOCATE);
-  if (n == 0) return 0;
-  int rc = ensure (c->lc_work, 256, c->stream);
-  if (rc) return -rc;
-  u32 *n_located = (u32 *) c->lc_work.p;
-  if (hipMemsetAsync (n_located, 0, 4, c->stream) != hipSuccess) return -set_err (TJAMD_ERR_HIP, "%s: memset failed", fn);
-  st.begin ();
-  hipLaunchKernelGGL (locate_kernel, dim3 (grid_for (n)), dim3 (256), 0, c->stream, (const u64 *) d_keys, n, (const u64 *) ref->ord[0], (const u64 *) ref->ord[1],
-                      ref->n_entries, (const RefEntry *) ref->entries, max_mismatches, (Location *) d_loc, n_located);
-  st.end ();
-  u32 found = 0;
-  rc = read_back (c, fn, n_located, &found, 1);
-  if (rc) return -rc;
-  st.done ();
-  return (long) found;
+  return lookup_rows (c, fn, T_LOCATE, n, [&] (u32 *n_located) {
+    hipLaunchKernelGGL (locate_kernel, dim3 (grid_for (n)), dim3 (256), 0, c->stream, (const u64 *) d_keys, n, (const u64 *) ref->ord[0], (const u64 *) ref->ord[1],
+                        ref->n_entries, (const RefEntry *) ref->entries, max_mismatches, (Location *) d_loc, n_located);
+  });
 }
-extern "C" double tjamd_last_locate_ms (tjamd_counter *c) { return c ? c->timer[T_LOCATE].ms (c->device) : -1.0; }
+TJ_LAST_MS (tjamd_last_locate_ms, T_LOCATE)
 
 // ---- N10: the second pass of the lookup: flanks that differ from the genome by indels, or in both flanks -----------------
 // The reference maps context + tract with BWA, by edit distance over the whole string (src/hopo_counter.c:495-572), and allows
@@ -7210,7 +7264,7 @@ extern "C" long tjamd_reference_add_seeds (tjamd_counter *c, tjamd_reference *re
   st.done ();
   return n;
 }
-extern "C" double tjamd_last_seed_order_ms (tjamd_counter *c) { return c ? c->timer[T_SEED_ORDER].ms (c->device) : -1.0; }
+TJ_LAST_MS (tjamd_last_seed_order_ms, T_SEED_ORDER)
 
 // ---- the gapped lookup ---------------------------------------------------------------------------------------------
 // Thread mapping: that of locate_kernel, for its reason (at k >= 12 nearly every range is short and the 64 lanes stay in
@@ -7249,7 +7303,7 @@ void locate_gapped_kernel (const u64 *__restrict__ keys, long n, const u64 *__re
     const bool todo = active && loc[q].flat < 0;                        // (a located row skips the searches, not the hand-offs)
     u64 qc0 = 0, qc1 = 0; u32 qb = 0;
     if (todo) { qc0 = keys[3 * q]; qc1 = keys[3 * q + 1]; qb = (u32) keys[3 * q + 2] & 3u; }
-    const u64 qi0 = rev_k (qc0, k), qi1 = qc1;                          // inner-first
+    const u64 qi[2] = {rev_k (qc0, k), qc1};                            // inner-first
     u64 best = ~0ull; u32 hits = 0;
 #pragma unroll
     for (int side = 0; side < 2; side++) {
@@ -7257,20 +7311,7 @@ void locate_gapped_kernel (const u64 *__restrict__ keys, long n, const u64 *__re
       const u64 top = (side ? rev_k (qc1, k) : qc0) | rest, bottom = top & ~rest;     // every primary flank with the row's inner h bases
       long lo = 0, hi = 0;
       if (todo) { lo = ord_bound (ord, n_ent, qb, top, false); hi = ord_bound (ord, n_ent, qb, bottom, true); }
-      const bool mine = hi - lo <= LC_LANE_WALK;
-      if (mine) for (long i = lo; i < hi; i++) gapped_try<B> (ord, i, side, k, qi0, qi1, seed_mask, max_edits, best, hits);
-      u64 big = __ballot (!mine);
-      while (big) {                                     // the wavefront walks its long ranges together, one after the other
-        const int src = __ffsll ((long long) big) - 1;
-        big &= big - 1;
-        const long blo = __shfl (lo, src), bhi = __shfl (hi, src);
-        const u64 b0 = __shfl (qi0, src), b1 = __shfl (qi1, src);
-        u64 wb = ~0ull; u32 wh = 0;
-        for (long i = blo + lane; i < bhi; i += 64) gapped_try<B> (ord, i, side, k, b0, b1, seed_mask, max_edits, wb, wh);
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) { const u64 ob = __shfl_xor (wb, o); wb = ob < wb ? ob : wb; wh += __shfl_xor (wh, o); }
-        if (lane == src) { best = wb < best ? wb : best; hits += wh; }
-      }
+      lc_walk_range (lane, lo, hi, qi, best, hits, [&] (long i, const u64 (&q)[2], u64 &b, u32 &h) { gapped_try<B> (ord, i, side, k, q[0], q[1], seed_mask, max_edits, b, h); });
     }
     if (todo && hits) {
       const RefEntry e = entries[best & 0xFFFFFFFFull];
@@ -7297,25 +7338,14 @@ extern "C" long tjamd_locate_gapped (tjamd_counter *c, const tjamd_reference *re
   if (!ref->has_seeds) return -set_err (TJAMD_ERR_ARG, "%s: the reference has no seed order (tjamd_reference_add_seeds comes first)", fn);
   if (max_edits > c->k) return -set_err (TJAMD_ERR_ARG, "%s: max_edits %d outside 0..%d", fn, max_edits, c->k);
   if (hipSetDevice (c->device) != hipSuccess) return -set_err (TJAMD_ERR_HIP, "hipSetDevice failed");
-  Stage st (c, T_LOCATE_GAPPED);
-  if (n == 0) return 0;
-  int rc = ensure (c->lc_work, 256, c->stream);
-  if (rc) return -rc;
-  u32 *n_located = (u32 *) c->lc_work.p;
-  if (hipMemsetAsync (n_located, 0, 4, c->stream) != hipSuccess) return -set_err (TJAMD_ERR_HIP, "%s: memset failed", fn);
-  st.begin ();
+  return lookup_rows (c, fn, T_LOCATE_GAPPED, n, [&] (u32 *n_located) {
 #define LG_LAUNCH(B) hipLaunchKernelGGL (locate_gapped_kernel<B>, dim3 (grid_for (n)), dim3 (256), 0, c->stream, (const u64 *) d_keys, n, (const u64 *) ref->ord[0], \
-                                         (const u64 *) ref->seed, ref->n_entries, (const RefEntry *) ref->entries, c->k, max_edits, (Location *) d_loc, d_how, n_located)
-  switch (max_shift) { case 0: LG_LAUNCH (0); break; case 1: LG_LAUNCH (1); break; case 2: LG_LAUNCH (2); break; default: LG_LAUNCH (3); break; }
+                                           (const u64 *) ref->seed, ref->n_entries, (const RefEntry *) ref->entries, c->k, max_edits, (Location *) d_loc, d_how, n_located)
+    switch (max_shift) { case 0: LG_LAUNCH (0); break; case 1: LG_LAUNCH (1); break; case 2: LG_LAUNCH (2); break; default: LG_LAUNCH (3); break; }
 #undef LG_LAUNCH
-  st.end ();
-  u32 found = 0;
-  rc = read_back (c, fn, n_located, &found, 1);
-  if (rc) return -rc;
-  st.done ();
-  return (long) found;
+  });
 }
-extern "C" double tjamd_last_locate_gapped_ms (tjamd_counter *c) { return c ? c->timer[T_LOCATE_GAPPED].ms (c->device) : -1.0; }
+TJ_LAST_MS (tjamd_last_locate_gapped_ms, T_LOCATE_GAPPED)
 
 // ---- tracts by location ------------------------------------------------------------------------------------------
 
@@ -7434,7 +7464,7 @@ static int kv_sort (tjamd_counter *c, u64 *(&key)[2], u32 *(&val)[2], long n, in
   const int nblk = (int) ((n + RS_ITEMS - 1) / RS_ITEMS);
   for (int p = 0; p < (bits + 7) / 8; p++) {
     hipLaunchKernelGGL (kv_count_kernel, dim3 (nblk), dim3 (256), 0, c->stream, (const u64 *) key[0], n, p, (u32 *) c->hist.p, nblk);
-    const int rc = exclusive_scan (c, (const u32 *) c->hist.p, (u32 *) c->hist.p, 256l * nblk, nullptr, (u32 *) c->scan_tmp.p, c->scan_tmp.cap / 4);
+    const int rc = exclusive_scan (c, (const u32 *) c->hist.p, (u32 *) c->hist.p, 256l * nblk, nullptr);
     if (rc) return rc;
     hipLaunchKernelGGL (kv_scatter_kernel, dim3 (nblk), dim3 (256), 0, c->stream, (const u64 *) key[0], (const u32 *) val[0], key[1], val[1], n, p,
                         (const u32 *) c->hist.p, nblk);
@@ -7502,7 +7532,7 @@ __global__ void lt_merge_kernel (long nt, long n, const u32 *__restrict__ head, 
       }
     }
     out[g] = o;
-    const Location l = loc_row >= 0 ? loc[loc_row] : Location {-1, -1, -1, 0, 0, 0, 0};
+    const Location l = loc_row >= 0 ? loc[loc_row] : LC_NOWHERE;
     if (out_loc) out_loc[g] = l;
     if (ref_length) ref_length[g] = l.ref_length;
   }
@@ -7532,7 +7562,6 @@ extern "C" long tjamd_located_tracts (tjamd_counter *c, const void *d_keys, cons
   if (!rc) rc = ensure (c->ut_tot, (size_t) n * 8, c->stream);
   if (!rc) rc = reserve_sort (c, n, n);                 // (sized before the number of tracts is known: at most one per row)
   if (rc) return -rc;
-  u32 *tmp = (u32 *) c->scan_tmp.p; const size_t tw = c->scan_tmp.cap / 4;
   long long *total = (long long *) c->ut_tot.p;
   u32 *n_out = tot; int *err = (int *) tot + 1;
   if (hipMemsetAsync (tot, 0, 256, c->stream) != hipSuccess) return -set_err (TJAMD_ERR_HIP, "%s: memset failed", fn);
@@ -7543,7 +7572,7 @@ extern "C" long tjamd_located_tracts (tjamd_counter *c, const void *d_keys, cons
   long nt = n_tracts;
   if (!tracts) {                                        // the context-keyed tracts: their number is needed on the host (one wait more)
     hipLaunchKernelGGL (tract_head_kernel, dim3 (grid_for (n)), dim3 (256), 0, c->stream, (const u64 *) d_keys, n, head);
-    rc = exclusive_scan (c, head, hex, n, tot + 2, tmp, tw);
+    rc = exclusive_scan (c, head, hex, n, tot + 2);
     if (rc) return -rc;
     hipLaunchKernelGGL (lt_context_tract_kernel, dim3 (grid_for (n)), dim3 (256), 0, c->stream, n, (const long long *) total, (const u32 *) head, (const u32 *) hex, own);
     u32 nh = 0;
@@ -7556,8 +7585,8 @@ extern "C" long tjamd_located_tracts (tjamd_counter *c, const void *d_keys, cons
   rc = kv_sort (c, key, val, nt, 8 * LT_KEY_PASSES);
   if (rc) return -rc;
   hipLaunchKernelGGL (lt_head_kernel, dim3 (grid_for (nt)), dim3 (256), 0, c->stream, (const u64 *) key[0], (const u32 *) val[0], nt, tracts, head, rows);
-  rc = exclusive_scan (c, head, hex, nt, n_out, tmp, tw);
-  if (!rc) rc = exclusive_scan (c, rows, rowstart, nt, nullptr, tmp, tw);
+  rc = exclusive_scan (c, head, hex, nt, n_out);
+  if (!rc) rc = exclusive_scan (c, rows, rowstart, nt, nullptr);
   if (rc) return -rc;
   hipLaunchKernelGGL (lt_perm_kernel, dim3 (grid_for (n)), dim3 (256), 0, c->stream, n, nt, (const u32 *) rowstart, (const u32 *) val[0], tracts,
                       (const u64 *) d_keys, d_perm, (u64 *) d_out_keys);
@@ -7577,7 +7606,7 @@ extern "C" long tjamd_located_tracts (tjamd_counter *c, const void *d_keys, cons
   st.done ();
   return (long) h[0];
 }
-extern "C" double tjamd_last_located_tracts_ms (tjamd_counter *c) { return c ? c->timer[T_LOCATED_TRACTS].ms (c->device) : -1.0; }
+TJ_LAST_MS (tjamd_last_located_tracts_ms, T_LOCATED_TRACTS)
 
 // ---- N8: per-sample tract variants against the reference ---------------------------------------------------------------
 // The VCF step of the reference (update_vcf_file_from_context_histogram, find_ref_alt_ht_variants_from_strings,
@@ -7656,7 +7685,7 @@ void tract_variants_kernel (const u64 *__restrict__ keys, const int *__restrict_
   const long gthread = blockIdx.x * (long) blockDim.x + threadIdx.x, n_threads = (long) gridDim.x * blockDim.x;
   if (!WRITE) check_tiling (tracts, n_tracts, n_union, err);
   const int lane = threadIdx.x & (S - 1);
-  const long segs_per_grid = n_threads / S;
+  const long segs_per_grid = n_threads / S;              // (its own spelling, not SEGMENT_MAP's: a 64-bit division, and this kernel's code as it was)
   for (long i = gthread / S; i < n_list; i += segs_per_grid) {   // (uniform across a segment)
     const long t = list ? (long) list[i] : i;
     long first = 0, end = 0, ent = -1;
@@ -7739,7 +7768,7 @@ extern "C" long tjamd_tract_variants (tjamd_counter *c, const tjamd_reference *r
   };
   launch (tract_variants_kernel<false>);
   if (hipGetLastError () != hipSuccess) return -set_err (TJAMD_ERR_HIP, "%s: launch failed", fn);
-  rc = exclusive_scan (c, flag, excl, n_flags, total, (u32 *) c->scan_tmp.p, c->scan_tmp.cap / 4);
+  rc = exclusive_scan (c, flag, excl, n_flags, total);
   if (rc) return -rc;
   hipLaunchKernelGGL (variant_offsets_kernel, dim3 (grid_for (n_samples)), dim3 (256), 0, c->stream, (const u32 *) excl, n_list, n_samples, offs);
   launch (tract_variants_kernel<true>);                 // (guarded by capacity: the count is only read for the check below)
@@ -7756,7 +7785,7 @@ extern "C" long tjamd_tract_variants (tjamd_counter *c, const tjamd_reference *r
   st.done ();
   return n_rec;
 }
-extern "C" double tjamd_last_tract_variants_ms (tjamd_counter *c) { return c ? c->timer[T_VARIANTS].ms (c->device) : -1.0; }
+TJ_LAST_MS (tjamd_last_tract_variants_ms, T_VARIANTS)
 
 // ---- N9: the GFF3 feature a located tract lies in, and the longest modal length ------------------------------------------
 // genomic_context_find_features (src/context_histogram.c:331-351) asks, per located histogram, for the features that hold
@@ -7866,8 +7895,7 @@ extern "C" tjamd_annotation *tjamd_annotation_create (tjamd_counter *c, const tj
     if (n_features < 0 || (n_features > 0 && !h_features)) return set_err (TJAMD_ERR_ARG, "%s: %ld features with %s buffer", fn, n_features, h_features ? "a" : "a null");
     if (n_features > AN_MAX_FEATURES) return set_err (TJAMD_ERR_ARG, "%s: %ld features, more than 2^30", fn, n_features);
     if (tjamd_device_count () <= 0) return set_err (TJAMD_ERR_NO_DEVICE, "%s: TJAMD_ERR_NO_DEVICE: no HIP device visible (the table is built on the device; no CPU fallback)", fn);
-    if (ref->device != c->device) return set_err (TJAMD_ERR_ARG, "%s: the reference lives on device %d, the counter on device %d", fn, ref->device, c->device);
-    return TJAMD_OK;
+    return on_counter_device (fn, "reference", ref->device, c);
   };
   const int bad = refused ();
   Stage st (c, T_ANNOTATION);                           // (a refused call leaves no timing behind)
@@ -7876,9 +7904,7 @@ extern "C" tjamd_annotation *tjamd_annotation_create (tjamd_counter *c, const tj
   long nr = 0;                                          // features that are not regions
   for (long i = 0; i < n; i++) {
     const tjamd_feature &x = h_features[i];
-    if (x.contig < 0 || (long) x.contig >= ref->n_contigs) { set_err (TJAMD_ERR_ARG, "%s: feature %ld: contig %d outside [0, %ld)", fn, i, x.contig, ref->n_contigs); return NULL; }
-    if (x.start < 1) { set_err (TJAMD_ERR_ARG, "%s: feature %ld: start %d < 1", fn, i, x.start); return NULL; }
-    if (x.end < x.start) { set_err (TJAMD_ERR_ARG, "%s: feature %ld: end %d < start %d", fn, i, x.end, x.start); return NULL; }
+    if (feature_refused (fn, i, x, ref->n_contigs)) return NULL;
     if (x.cls < 0 || x.cls > 2) { set_err (TJAMD_ERR_ARG, "%s: feature %ld: cls %d outside 0..2", fn, i, x.cls); return NULL; }
     nr += x.cls != TJAMD_FEATURE_REGION;
   }
@@ -7897,7 +7923,7 @@ extern "C" tjamd_annotation *tjamd_annotation_create (tjamd_counter *c, const tj
   st.begin ();
   hipLaunchKernelGGL (an_flag_kernel, dim3 (grid_for (n)), dim3 (256), 0, c->stream, (const Feature *) feat, n, flag);
   if (np) {
-    int rc = exclusive_scan (c, flag, excl, n, nullptr, (u32 *) c->scan_tmp.p, c->scan_tmp.cap / 4);
+    int rc = exclusive_scan (c, flag, excl, n, nullptr);
     hipLaunchKernelGGL (an_points_kernel, dim3 (grid_for (n)), dim3 (256), 0, c->stream, (const Feature *) feat, n, (const u32 *) excl, key[0], val[0]);
     int bits = 32;                                      // of a point: the position, and what the contig numbers need
     while (bits < 64 && ((u64) (ref->n_contigs - 1) >> (bits - 32))) bits++;
@@ -7927,7 +7953,7 @@ extern "C" long tjamd_annotation_download (const tjamd_annotation *a, uint64_t *
   for (long e = 0; e < np; e++) h_winner[e] = priority_winner (prio[(size_t) e]);
   return np;
 }
-extern "C" double tjamd_last_annotation_ms (tjamd_counter *c) { return c ? c->timer[T_ANNOTATION].ms (c->device) : -1.0; }
+TJ_LAST_MS (tjamd_last_annotation_ms, T_ANNOTATION)
 
 // One record per tract.  Segment mapping of union_tract_stats_kernel and tract_variants_kernel: S lanes per tract; the
 // segment's first lane looks the location up in the table (one binary search) and reads the tract's rows; with a union, a
@@ -7948,7 +7974,7 @@ void tract_features_kernel (const u64 *__restrict__ keys, const int *__restrict_
   const long gthread = blockIdx.x * (long) blockDim.x + threadIdx.x, n_threads = (long) gridDim.x * blockDim.x;
   if (*(volatile int *) err != 0) return;                // (the check is complete: every thread reads the same word)
   const int lane = threadIdx.x & (S - 1);
-  const long segs_per_grid = n_threads / S;
+  const long segs_per_grid = n_threads / S;              // (its own spelling, not SEGMENT_MAP's: a 64-bit division, and this kernel's code as it was)
   for (long t = gthread / S; t < n_tracts; t += segs_per_grid) {   // (uniform across a segment)
     int feature = -1, longest = 0;
     long first = 0, end = 0;
@@ -7992,18 +8018,16 @@ extern "C" long tjamd_tract_features (tjamd_counter *c, const tjamd_annotation *
     if (n_tracts > 0 && (!d_tract_loc || !d_out)) return set_err (TJAMD_ERR_ARG, "%s: null tract location or output buffer", fn);
     if (!c || !a) return set_err (TJAMD_ERR_ARG, "%s: null counter or annotation", fn);
     if (tjamd_device_count () <= 0) return set_err (TJAMD_ERR_NO_DEVICE, "%s: TJAMD_ERR_NO_DEVICE: no HIP device visible (the tracts are looked up on the device; no CPU fallback)", fn);
-    if (a->device != c->device) return set_err (TJAMD_ERR_ARG, "%s: the annotation lives on device %d, the counter on device %d", fn, a->device, c->device);
-    return TJAMD_OK;
+    return on_counter_device (fn, "annotation", a->device, c);
   };
   int rc = refused ();
   Stage st (c, T_TRACT_FEATURES);                       // (a refused call leaves no timing behind)
   if (rc) return -rc;
   if (hipSetDevice (c->device) != hipSuccess) return -set_err (TJAMD_ERR_HIP, "hipSetDevice failed");
   if (n_tracts == 0) return 0;
-  rc = ensure (c->lc_work, 256, c->stream);
+  int *err;
+  rc = flags_alone (c, fn, err);
   if (rc) return -rc;
-  int *err = (int *) c->lc_work.p;
-  if (hipMemsetAsync (err, 0, 4, c->stream) != hipSuccess) return -set_err (TJAMD_ERR_HIP, "%s: memset failed", fn);
   st.begin ();
   const int S = have_union ? tract_segment (n_samples) : 1;
   if (have_union) hipLaunchKernelGGL (tiling_check_kernel, dim3 (grid_for (n_tracts)), dim3 (256), 0, c->stream, (const UnionTract *) d_tracts, n_tracts, n_union, err);
@@ -8018,7 +8042,7 @@ extern "C" long tjamd_tract_features (tjamd_counter *c, const tjamd_annotation *
   st.done ();
   return n_tracts;
 }
-extern "C" double tjamd_last_tract_features_ms (tjamd_counter *c) { return c ? c->timer[T_TRACT_FEATURES].ms (c->device) : -1.0; }
+TJ_LAST_MS (tjamd_last_tract_features_ms, T_TRACT_FEATURES)
 
 // ---- N11: the coding effect of a variant record ---------------------------------------------------------------------------
 // The rule is in include/tatajuba_effects.h.  The table (tjamd_coding) keeps the genome as one code per byte, the contig
@@ -8167,8 +8191,7 @@ extern "C" tjamd_coding *tjamd_coding_create (tjamd_counter *c, const void *h_st
   long n_contigs = 0;
   auto refused = [&] () -> int {                        // the checks that read no handle: the caller's host buffers, then the device
     if (!c) return set_err (TJAMD_ERR_ARG, "%s: null counter", fn);
-    if (n_bytes && !h_stream) return set_err (TJAMD_ERR_ARG, "%s: null stream", fn);
-    if (n_bytes >= (size_t) 1 << 31) return set_err (TJAMD_ERR_CAPACITY, "%s: a stream of %zu bytes (positions are 32-bit)", fn, n_bytes);
+    if (const int rc = stream_refused (fn, h_stream, n_bytes)) return rc;
     if (n_features < 0 || (n_features > 0 && !h_features)) return set_err (TJAMD_ERR_ARG, "%s: %ld features with %s buffer", fn, n_features, h_features ? "a" : "a null");
     if (n_features > CD_MAX_FEATURES) return set_err (TJAMD_ERR_ARG, "%s: %ld features, more than 2^30", fn, n_features);
     const char *s = (const char *) h_stream;
@@ -8176,12 +8199,7 @@ extern "C" tjamd_coding *tjamd_coding_create (tjamd_counter *c, const void *h_st
       const char *nl = (const char *) memchr (s + at, '\n', n_bytes - at);
       at = nl ? (size_t) (nl - s) + 1 : n_bytes;
     }
-    for (long i = 0; i < n_features; i++) {
-      const tjamd_feature &x = h_features[i];
-      if (x.contig < 0 || (long) x.contig >= n_contigs) return set_err (TJAMD_ERR_ARG, "%s: feature %ld: contig %d outside [0, %ld)", fn, i, x.contig, n_contigs);
-      if (x.start < 1) return set_err (TJAMD_ERR_ARG, "%s: feature %ld: start %d < 1", fn, i, x.start);
-      if (x.end < x.start) return set_err (TJAMD_ERR_ARG, "%s: feature %ld: end %d < start %d", fn, i, x.end, x.start);
-    }
+    for (long i = 0; i < n_features; i++) if (const int rc = feature_refused (fn, i, h_features[i], n_contigs)) return rc;
     if (tjamd_device_count () <= 0) return set_err (TJAMD_ERR_NO_DEVICE, "%s: TJAMD_ERR_NO_DEVICE: no HIP device visible (the table is built on the device; no CPU fallback)", fn);
     return TJAMD_OK;
   };
@@ -8195,17 +8213,16 @@ extern "C" tjamd_coding *tjamd_coding_create (tjamd_counter *c, const void *h_st
   ScratchCut cut;
   u32 *nlflag, *nlex; Feature *feat; signed char *phase;
   cut.take (nlflag, n + 1); cut.take (nlex, n + 1); cut.take (feat, nf + 1); cut.take (phase, nf + 1);
-  if (cut.commit (c) || ensure (c->stage, ((size_t) n + 255) & ~(size_t) 255, c->stream) || ensure (c->scan_tmp, scan_tmp_words (n) * 4 + 64, c->stream)) return NULL;
+  if (cut.commit (c) || upload_stream (c, fn, h_stream, n_bytes) || ensure (c->scan_tmp, scan_tmp_words (n) * 4 + 64, c->stream)) return NULL;
   if (hipMalloc (&cod->codes, (size_t) std::max<long> (n, 1)) != hipSuccess || hipMalloc (&cod->cstart, (size_t) (n_contigs + 2) * 4) != hipSuccess ||
       hipMalloc (&cod->rows, (size_t) std::max<long> (nf, 1) * sizeof (CodRow)) != hipSuccess) { set_err (TJAMD_ERR_HIP, "%s: hipMalloc failed for %ld bytes of genome and %ld features", fn, n, nf); return NULL; }
-  if ((n && hipMemcpyAsync (c->stage.p, h_stream, n_bytes, hipMemcpyHostToDevice, c->stream) != hipSuccess) ||
-      (nf && hipMemcpyAsync (feat, h_features, (size_t) nf * sizeof (Feature), hipMemcpyHostToDevice, c->stream) != hipSuccess) ||
+  if ((nf && hipMemcpyAsync (feat, h_features, (size_t) nf * sizeof (Feature), hipMemcpyHostToDevice, c->stream) != hipSuccess) ||
       (nf && h_phase && hipMemcpyAsync (phase, h_phase, (size_t) nf, hipMemcpyHostToDevice, c->stream) != hipSuccess)) { set_err (TJAMD_ERR_HIP, "%s: copy to device failed", fn); return NULL; }
   st.begin ();
   if (n) {
     const uint8_t *seq = (const uint8_t *) c->stage.p;
     hipLaunchKernelGGL (cd_code_kernel, dim3 (grid_for (n)), dim3 (256), 0, c->stream, seq, n, cod->codes, nlflag);
-    if (exclusive_scan (c, nlflag, nlex, n, nullptr, (u32 *) c->scan_tmp.p, c->scan_tmp.cap / 4)) return NULL;
+    if (exclusive_scan (c, nlflag, nlex, n, nullptr)) return NULL;
     hipLaunchKernelGGL (cd_cstart_kernel, dim3 (grid_for (n)), dim3 (256), 0, c->stream, seq, n, (const u32 *) nlflag, (const u32 *) nlex, cod->cstart);
   }
   if (nf)                                               // (features need contigs, contigs need bytes: n > 0 here)
@@ -8230,7 +8247,7 @@ extern "C" long tjamd_coding_download (const tjamd_coding *cod, tjamd_cds *out, 
       hipMemcpy2D (out, sizeof (Cds), cod->rows, sizeof (CodRow), sizeof (Cds), (size_t) nf, hipMemcpyDeviceToHost) != hipSuccess) return -set_err (TJAMD_ERR_HIP, "%s: copy failed", fn);
   return nf;
 }
-extern "C" double tjamd_last_coding_ms (tjamd_counter *c) { return c ? c->timer[T_CODING].ms (c->device) : -1.0; }
+TJ_LAST_MS (tjamd_last_coding_ms, T_CODING)
 
 // what the wavefront needs of an owner's record: the span, where the edit sits in it and what ALT is made of
 struct Walk
@@ -8402,18 +8419,16 @@ extern "C" long tjamd_variant_effects (tjamd_counter *c, const tjamd_coding *cod
     if (d_tract_feat && n_tracts < 0) return set_err (TJAMD_ERR_ARG, "%s: n_tracts %ld < 0", fn, n_tracts);
     if (!c || !cod) return set_err (TJAMD_ERR_ARG, "%s: null counter or coding table", fn);
     if (tjamd_device_count () <= 0) return set_err (TJAMD_ERR_NO_DEVICE, "%s: TJAMD_ERR_NO_DEVICE: no HIP device visible (the records are classified on the device; no CPU fallback)", fn);
-    if (cod->device != c->device) return set_err (TJAMD_ERR_ARG, "%s: the coding table lives on device %d, the counter on device %d", fn, cod->device, c->device);
-    return TJAMD_OK;
+    return on_counter_device (fn, "coding table", cod->device, c);
   };
   int rc = refused ();
   Stage st (c, T_VARIANT_EFFECTS);                      // (a refused call leaves no timing behind)
   if (rc) return -rc;
   if (hipSetDevice (c->device) != hipSuccess) return -set_err (TJAMD_ERR_HIP, "hipSetDevice failed");
   if (n == 0) return 0;
-  rc = ensure (c->lc_work, 256, c->stream);
+  int *err;
+  rc = flags_alone (c, fn, err);
   if (rc) return -rc;
-  int *err = (int *) c->lc_work.p;
-  if (hipMemsetAsync (err, 0, 4, c->stream) != hipSuccess) return -set_err (TJAMD_ERR_HIP, "%s: memset failed", fn);
   st.begin ();
   hipLaunchKernelGGL (variant_effects_check_kernel, dim3 (grid_for (n)), dim3 (256), 0, c->stream, (const u32 *) cod->cstart, cod->n_contigs, cod->n_features,
                       (const Variant *) d_variants, n, (const TractFeature *) d_tract_feat, n_tracts, err);
@@ -8433,7 +8448,7 @@ extern "C" long tjamd_variant_effects (tjamd_counter *c, const tjamd_coding *cod
   st.done ();
   return n;
 }
-extern "C" double tjamd_last_variant_effects_ms (tjamd_counter *c) { return c ? c->timer[T_VARIANT_EFFECTS].ms (c->device) : -1.0; }
+TJ_LAST_MS (tjamd_last_variant_effects_ms, T_VARIANT_EFFECTS)
 
 // ---- N12: the per-sample variant records merged into multi-sample sites ------------------------------------------------
 // The reference leaves this to its user (docs/tutorial.md, "Downstream analyses": sort | uniq over the per-sample VCF files,
@@ -8674,7 +8689,6 @@ extern "C" long tjamd_merge_variants (tjamd_counter *c, int kmer_size, const tja
   rc = cut.commit (c);
   if (!rc) rc = reserve_sort (c, n, n);
   if (rc) return -rc;
-  u32 *tmp = (u32 *) c->scan_tmp.p; const size_t tw = c->scan_tmp.cap / 4;
   int *err = (int *) tot + 2;                           // tot: the alleles, the sites, the error flag
   if (hipMemsetAsync (tot, 0, 256, c->stream) != hipSuccess) return -set_err (TJAMD_ERR_HIP, "%s: memset failed", fn);
   st.begin ();
@@ -8693,8 +8707,8 @@ extern "C" long tjamd_merge_variants (tjamd_counter *c, int kmer_size, const tja
   }
   if (rc) return -rc;
   hipLaunchKernelGGL (mv_head_kernel, dim3 (grid), dim3 (256), 0, c->stream, rec, (const u32 *) val[0], n, ahead, shead, smp, err);
-  rc = exclusive_scan (c, ahead, aex, n, tot, tmp, tw);
-  if (!rc) rc = exclusive_scan (c, shead, sex, n, tot + 1, tmp, tw);
+  rc = exclusive_scan (c, ahead, aex, n, tot);
+  if (!rc) rc = exclusive_scan (c, shead, sex, n, tot + 1);
   if (rc) return -rc;
   hipLaunchKernelGGL (mv_start_kernel, dim3 (grid), dim3 (256), 0, c->stream, n, (const u32 *) ahead, (const u32 *) aex, (const u32 *) shead, (const u32 *) sex, astart, sstart);
   hipLaunchKernelGGL (mv_site_kernel, dim3 (grid), dim3 (256), 0, c->stream, rec, (const u32 *) val[0], (const u32 *) smp, (const u32 *) sstart, (const u32 *) tot, n_samples, agg, err);
@@ -8721,7 +8735,7 @@ extern "C" long tjamd_merge_variants (tjamd_counter *c, int kmer_size, const tja
   st.done ();
   return (long) h[1];
 }
-extern "C" double tjamd_last_merge_variants_ms (tjamd_counter *c) { return c ? c->timer[T_MERGE_VARIANTS].ms (c->device) : -1.0; }
+TJ_LAST_MS (tjamd_last_merge_variants_ms, T_MERGE_VARIANTS)
 
 // ---- N13: per-site read depths and reference genotypes of the merged sites ------------------------------------------------
 // What tjamd_merge_variants cannot know from N8's records: whether a sample without a record equals the reference or has no
@@ -8744,6 +8758,22 @@ struct SdShared { int first, end, k_eff, a0, na, Lr, neg, ok; u64 fr; };   // wh
 // err bits: 1 tiling, 2 site.tract, 4 the site against its tract's location and entry, 8 the allele chain, 16 n_alleles < 1,
 // 32 allele.site, 64 allele.n_flank, 128 a modal row that no allele holds, 256 n_called (tjamd_site_depths names them)
 
+// The allele chain of the merged sites, the rule of N13's first pass and of N14's check: bit 16 where site i (first_allele a0,
+// n_alleles na) has no allele, bit 8 where it does not begin where site i - 1 ends (the first: at 0) or, the last one, does not end
+// at n_alleles.  site_bit_refused: the text of either bit and of bit 32 (an allele outside its site; each entry finds that in its
+// own way), one bit per call, so that each entry keeps its own order of decoding.
+__device__ __forceinline__ int site_chain_bad (const Site *__restrict__ sites, long n_sites, long n_alleles, long i, int a0, int na)
+{
+  const long a_want = i ? (long) sites[i - 1].first_allele + (long) sites[i - 1].n_alleles : 0l;
+  return (na < 1 ? 16 : 0) | ((long) a0 != a_want || (i == n_sites - 1 && (long) a0 + (long) na != n_alleles) ? 8 : 0);
+}
+static int site_bit_refused (const char *fn, u32 bit, long n_alleles)
+{
+  if (bit == 16u) return set_err (TJAMD_ERR_ARG, "%s: a site has n_alleles < 1", fn);
+  if (bit == 8u) return set_err (TJAMD_ERR_ARG, "%s: first_allele and n_alleles of the sites do not chain from 0 to %ld", fn, n_alleles);
+  return set_err (TJAMD_ERR_ARG, "%s: an allele's site is not the site that holds it", fn);
+}
+
 __device__ __forceinline__ int sd_saturated (long long x) { return x > 0x7fffffffll ? 0x7fffffff : (int) x; }
 
 template <bool WRITE>
@@ -8759,7 +8789,7 @@ void site_depths_kernel (const u64 *__restrict__ keys, const int *__restrict__ c
   else check_tiling (tracts, n_tracts, n_union, err);
   const int lane = threadIdx.x & (S - 1);
   const int log_S = __ffs (S) - 1;                       // (S is a power of two)
-  const long segs_per_grid = n_threads >> log_S;
+  const long segs_per_grid = n_threads >> log_S;         // (its own spelling, not SEGMENT_MAP's: shifts, and this kernel's code as it was)
   for (long i = gthread >> log_S; i < n_sites; i += segs_per_grid) {   // (uniform across a segment)
     int first = 0, end = 0, ent = -1, a0 = 0;           // (rows, entries and alleles are fewer than 2^31: the entry checks it)
     int k_eff = 0, na = 0, n_called = 0, Lr = 0, neg = 0;
@@ -8771,12 +8801,9 @@ void site_depths_kernel (const u64 *__restrict__ keys, const int *__restrict__ c
     else if (lane == 0) {
       const Site site = sites[i];
       const long t = site.tract;
-      int bad = 0;
       n_called = site.n_called;
-      const long a_want = i ? (long) sites[i - 1].first_allele + (long) sites[i - 1].n_alleles : 0l;
       a0 = site.first_allele; na = site.n_alleles;
-      if (na < 1) bad |= 16;
-      if ((long) a0 != a_want || (i == n_sites - 1 && (long) a0 + (long) na != n_alleles)) bad |= 8;
+      int bad = site_chain_bad (sites, n_sites, n_alleles, i, a0, na);
       if (a0 < 0 || na < 1 || (long) a0 + (long) na > n_alleles) { if (na >= 1) bad |= 8; a0 = 0; na = 0; }   // (nothing is read outside the alleles)
       long t_first = 0, t_end = 0;
       if (t < 0 || t >= n_tracts) bad |= 2;
@@ -8922,17 +8949,17 @@ extern "C" long tjamd_site_depths (tjamd_counter *c, const tjamd_reference *ref,
   if (rc) return -rc;
   if (h_err & 1u) return -set_err (TJAMD_ERR_ARG, TILING_REFUSED, fn);
   if (h_err & 2u) return -set_err (TJAMD_ERR_ARG, "%s: a site's tract is outside [0, %ld)", fn, n_tracts);
-  if (h_err & 16u) return -set_err (TJAMD_ERR_ARG, "%s: a site has n_alleles < 1", fn);
-  if (h_err & 8u) return -set_err (TJAMD_ERR_ARG, "%s: first_allele and n_alleles of the sites do not chain from 0 to %ld", fn, n_alleles);
+  if (h_err & 16u) return -site_bit_refused (fn, 16u, n_alleles);
+  if (h_err & 8u) return -site_bit_refused (fn, 8u, n_alleles);
   if (h_err & 4u) return -set_err (TJAMD_ERR_ARG, "%s: a site has no index entry, or its flat, contig or ref_length is not its tract's", fn);
-  if (h_err & 32u) return -set_err (TJAMD_ERR_ARG, "%s: an allele's site is not the site that holds it", fn);
+  if (h_err & 32u) return -site_bit_refused (fn, 32u, n_alleles);
   if (h_err & 64u) return -set_err (TJAMD_ERR_ARG, "%s: an allele's n_flank is outside 0..%d", fn, c->k);
   if (h_err & 128u) return -set_err (TJAMD_ERR_ARG, "%s: a sample's modal row is a variant that the site's alleles do not hold (sites of another union or list)", fn);
   if (h_err & 256u) return -set_err (TJAMD_ERR_ARG, "%s: a site's n_called is not the number of samples with an allele (sites merged from another list or a subset)", fn);
   st.done ();
   return n_sites;
 }
-extern "C" double tjamd_last_site_depths_ms (tjamd_counter *c) { return c ? c->timer[T_SITE_DEPTHS].ms (c->device) : -1.0; }
+TJ_LAST_MS (tjamd_last_site_depths_ms, T_SITE_DEPTHS)
 
 // ---- N14: pairwise sample distances over the merged sites -------------------------------------------------------------------
 // The site x sample genotype matrix of N12 / N13 reduced to a sample x sample matrix of (n_both, n_differ, length_diff); the rule
@@ -8967,10 +8994,7 @@ void sample_distances_check_kernel (const Site *__restrict__ sites, long n_sites
   const long gthread = blockIdx.x * (long) blockDim.x + threadIdx.x, n_threads = (long) gridDim.x * blockDim.x;
   int bad = 0;
   for (long i = gthread; i < n_sites; i += n_threads) {
-    const int a0 = sites[i].first_allele, na = sites[i].n_alleles;
-    const long a_want = i ? (long) sites[i - 1].first_allele + (long) sites[i - 1].n_alleles : 0l;
-    if (na < 1) bad |= 16;
-    if ((long) a0 != a_want || (i == n_sites - 1 && (long) a0 + (long) na != n_alleles)) bad |= 8;
+    bad |= site_chain_bad (sites, n_sites, n_alleles, i, sites[i].first_allele, sites[i].n_alleles);
     if (sites[i].ref_length < 0) bad |= 128;
   }
   for (long a = gthread; a < n_alleles; a += n_threads) {   // (where the chain holds, an allele lies in one site's range: its own)
@@ -9265,9 +9289,7 @@ static int sdist_head (Stage &st, const char *fn, const SdistShape &s, const tja
 // the error bits of sample_distances_check_kernel, in the order they are reported: 0 if none is up
 static int sdist_refusal (const char *fn, u32 h_err, long n_alleles)
 {
-  if (h_err & 16u) return set_err (TJAMD_ERR_ARG, "%s: a site has n_alleles < 1", fn);
-  if (h_err & 8u) return set_err (TJAMD_ERR_ARG, "%s: first_allele and n_alleles of the sites do not chain from 0 to %ld", fn, n_alleles);
-  if (h_err & 32u) return set_err (TJAMD_ERR_ARG, "%s: an allele's site is not the site that holds it", fn);
+  for (const u32 bit : {16u, 8u, 32u}) if (h_err & bit) return site_bit_refused (fn, bit, n_alleles);
   if (h_err & 64u) return set_err (TJAMD_ERR_ARG, "%s: an allele's alt_length is outside 0..1023", fn);
   if (h_err & 128u) return set_err (TJAMD_ERR_ARG, "%s: a site's ref_length is below 0", fn);
   if (h_err & 1u) return set_err (TJAMD_ERR_ARG, "%s: a genotype cell is below -1 or above its site's n_alleles", fn);
@@ -9308,7 +9330,7 @@ extern "C" long tjamd_sample_distances (tjamd_counter *c, const tjamd_site *d_si
   st.done ();
   return n_sites;
 }
-extern "C" double tjamd_last_sample_distances_ms (tjamd_counter *c) { return c ? c->timer[T_SAMPLE_DISTANCES].ms (c->device) : -1.0; }
+TJ_LAST_MS (tjamd_last_sample_distances_ms, T_SAMPLE_DISTANCES)
 
 // ---- N15: the single-linkage tree of the samples and its clusters at a threshold ---------------------------------------------
 // N14's sample x sample matrix reduced to the minimum spanning forest of its pairs under the total order (key, a, b), and a list
@@ -9684,7 +9706,7 @@ extern "C" long tjamd_sample_linkage (tjamd_counter *c, const tjamd_sample_dista
   st.done ();
   return (long) h_flags[2];
 }
-extern "C" double tjamd_last_sample_linkage_ms (tjamd_counter *c) { return c ? c->timer[T_SAMPLE_LINKAGE].ms (c->device) : -1.0; }
+TJ_LAST_MS (tjamd_last_sample_linkage_ms, T_SAMPLE_LINKAGE)
 
 __global__ __launch_bounds__ (1024)
 void linkage_clusters_kernel (const Link *__restrict__ links, long n_links, int ns, long long threshold, int *__restrict__ cluster, int *__restrict__ flags)
@@ -9763,7 +9785,7 @@ extern "C" long tjamd_linkage_clusters (tjamd_counter *c, const tjamd_link *d_li
   st.done ();
   return (long) h_flags[1];
 }
-extern "C" double tjamd_last_linkage_clusters_ms (tjamd_counter *c) { return c ? c->timer[T_LINKAGE_CLUSTERS].ms (c->device) : -1.0; }
+TJ_LAST_MS (tjamd_last_linkage_clusters_ms, T_LINKAGE_CLUSTERS)
 
 // ---- N16: the sites that set a group of samples apart from the rest --------------------------------------------------------
 // The site x sample genotype matrix reduced per site under the key (group, genotype); the rule as built is in
@@ -10160,7 +10182,7 @@ static long mark_sites (const MarkCall &m, int timer, bool small, const MarkRefu
   const unsigned grid = (unsigned) (small ? blocks : (m.n_sites + per_block - 1) / per_block);
   st.begin ();
   launch (A, false, grid, per_block);
-  rc = exclusive_scan (c, cnt, cnt, m.n_sites, (u32 *) flags + 1, (u32 *) c->scan_tmp.p, c->scan_tmp.cap / 4);
+  rc = exclusive_scan (c, cnt, cnt, m.n_sites, (u32 *) flags + 1);
   if (rc) return -rc;
   launch (A, true, grid, per_block);
   st.end ();
@@ -10196,7 +10218,7 @@ extern "C" long tjamd_group_sites (tjamd_counter *c, const tjamd_site *d_sites, 
     else hipLaunchKernelGGL (group_sites_large_kernel<true>, dim3 (grid), dim3 (CLD_THREADS), 0, c->stream, A, per_block);
   });
 }
-extern "C" double tjamd_last_group_sites_ms (tjamd_counter *c) { return c ? c->timer[T_GROUP_SITES].ms (c->device) : -1.0; }
+TJ_LAST_MS (tjamd_last_group_sites_ms, T_GROUP_SITES)
 
 // ---- N17: the tree of the links as nodes, and the sites that support each of its clades ------------------------------------
 // The rules as built are in include/tatajuba_clades.h.
@@ -10313,7 +10335,7 @@ extern "C" long tjamd_linkage_tree (tjamd_counter *c, const tjamd_link *d_links,
   st.done ();
   return n_links;
 }
-extern "C" double tjamd_last_linkage_tree_ms (tjamd_counter *c) { return c ? c->timer[T_LINKAGE_TREE].ms (c->device) : -1.0; }
+TJ_LAST_MS (tjamd_last_linkage_tree_ms, T_LINKAGE_TREE)
 
 struct CladeArgs : MarkArgs { const TreeNode *nodes; const int *order; };   // (the words of a call: at MarkArgs)
 
@@ -10570,7 +10592,7 @@ extern "C" long tjamd_clade_sites (tjamd_counter *c, const tjamd_site *d_sites, 
     else hipLaunchKernelGGL (clade_sites_large_kernel<true>, dim3 (grid), dim3 (CLD_THREADS), 0, c->stream, A, per_block);
   });
 }
-extern "C" double tjamd_last_clade_sites_ms (tjamd_counter *c) { return c ? c->timer[T_CLADE_SITES].ms (c->device) : -1.0; }
+TJ_LAST_MS (tjamd_last_clade_sites_ms, T_CLADE_SITES)
 
 // ---- N18: complete and average linkage trees of the samples ------------------------------------------------------------------
 // N14's sample x sample matrix agglomerated under complete or average linkage by rounds of reciprocal nearest neighbours; the
@@ -10883,7 +10905,7 @@ extern "C" long tjamd_sample_agglomerate (tjamd_counter *c, const tjamd_sample_d
   if (h_n_rounds) *h_n_rounds = (int) h_flags[3];
   return (long) h_flags[2];
 }
-extern "C" double tjamd_last_sample_agglomerate_ms (tjamd_counter *c) { return c ? c->timer[T_SAMPLE_AGGLOMERATE].ms (c->device) : -1.0; }
+TJ_LAST_MS (tjamd_last_sample_agglomerate_ms, T_SAMPLE_AGGLOMERATE)
 
 // ---- N19: bootstrap support for the clades of the sample tree ----------------------------------------------------------------
 // The rules as built are in include/tatajuba_bootstrap.h.
@@ -10966,7 +10988,7 @@ extern "C" long tjamd_bootstrap_weights (tjamd_counter *c, long n_sites, int n_r
   st.done ();
   return n_replicates;
 }
-extern "C" double tjamd_last_bootstrap_weights_ms (tjamd_counter *c) { return c ? c->timer[T_BOOTSTRAP_WEIGHTS].ms (c->device) : -1.0; }
+TJ_LAST_MS (tjamd_last_bootstrap_weights_ms, T_BOOTSTRAP_WEIGHTS)
 
 // err bits beyond N14's: 256 a weight below 0, 512 a replicate whose weights sum to 2^31 or more.  A workgroup per replicate; each
 // also takes its share of the sites.  err[2] and err[3] become the largest weight and the largest length (1023 at least) of the
@@ -11148,7 +11170,7 @@ extern "C" long tjamd_sample_distances_weighted (tjamd_counter *c, const tjamd_s
   st.done ();
   return n_sites;
 }
-extern "C" double tjamd_last_sample_distances_weighted_ms (tjamd_counter *c) { return c ? c->timer[T_SAMPLE_DISTANCES_WEIGHTED].ms (c->device) : -1.0; }
+TJ_LAST_MS (tjamd_last_sample_distances_weighted_ms, T_SAMPLE_DISTANCES_WEIGHTED)
 
 #define CSUP_PLACES 8192                                // places of the set of a replicate's nodes: twice the most it can hold
 __device__ __forceinline__ u32 csup_place (u32 key) { return (key * 0x9E3779B1u) >> 19; }   // (the top 13 bits)
@@ -11264,7 +11286,7 @@ extern "C" long tjamd_clade_support (tjamd_counter *c, const tjamd_tree_node *d_
   st.done ();
   return n_nodes;
 }
-extern "C" double tjamd_last_clade_support_ms (tjamd_counter *c) { return c ? c->timer[T_CLADE_SUPPORT].ms (c->device) : -1.0; }
+TJ_LAST_MS (tjamd_last_clade_support_ms, T_CLADE_SUPPORT)
 
 // ---- N20: the trees of all bootstrap replicates in one call -------------------------------------------------------------------
 // The rule as built is in include/tatajuba_replicate_trees.h: per replicate the bytes of N15's or N18's builder and of N17's
@@ -11578,7 +11600,7 @@ extern "C" long tjamd_replicate_trees (tjamd_counter *c, const tjamd_sample_dist
   }
   return R;
 }
-extern "C" double tjamd_last_replicate_trees_ms (tjamd_counter *c) { return c ? c->timer[T_REPLICATE_TREES].ms (c->device) : -1.0; }
+TJ_LAST_MS (tjamd_last_replicate_trees_ms, T_REPLICATE_TREES)
 
 // ---- N21: the majority-rule consensus tree of the bootstrap replicates ----------------------------------------------------------
 // The rule as built is in include/tatajuba_consensus.h.  A clade is a record: its index g = rep_off[r] + k among all nodes of
@@ -11921,7 +11943,7 @@ extern "C" long tjamd_consensus_tree (tjamd_counter *c, const tjamd_tree_node *d
     rc = kv_sort (c, key, val, n, 64);
     if (rc) return -rc;
     hipLaunchKernelGGL (cons_heads_kernel, dim3 (grid_for (n)), dim3 (256), 0, c->stream, (const u64 *) key[0], n, head, cls, cnt);
-    rc = exclusive_scan (c, head, hex, n, nullptr, (u32 *) c->scan_tmp.p, c->scan_tmp.cap / 4);
+    rc = exclusive_scan (c, head, hex, n, nullptr);
     if (rc) return -rc;
     for (long round = 0; ; round++) {                   // a round settles the leader of every run that has an unsettled record: n rounds at the very most
       if (round > n) return -set_err (TJAMD_ERR_STATE, "%s: the rounds did not end", fn);
@@ -11961,4 +11983,4 @@ extern "C" long tjamd_consensus_tree (tjamd_counter *c, const tjamd_tree_node *d
   if (h_n_classes) *h_n_classes = (long) h_flags[3];
   return (long) h_flags[2];
 }
-extern "C" double tjamd_last_consensus_tree_ms (tjamd_counter *c) { return c ? c->timer[T_CONSENSUS_TREE].ms (c->device) : -1.0; }
+TJ_LAST_MS (tjamd_last_consensus_tree_ms, T_CONSENSUS_TREE)

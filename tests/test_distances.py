@@ -12,12 +12,14 @@ import pytest
 
 import tatajuba_amd as tj
 from tests.guarded import GuardedDevice, frozen
-from tests.test_depths import depth_vcf_text, dev_depths
+from tests.test_depths import OUTPUTS, depth_vcf_text, dev_depths, whole_chain
 from tests.test_depths_cabi import restate_site_depths
 from tests.test_distances_cabi import HAND_EXPECTED, fabricate, hand_case, restate_sample_distances
 from tests.test_locate import _dev, _p
+from tests.test_locate_cabi import restate_reference_index
 from tests.test_sites import dev_merge, pipeline  # noqa: F401  (pipeline: the module-scoped fixture, built here as there)
 from tests.test_sites_cabi import merged_vcf_text, restate_merge_variants
+from tests.test_variants_cabi import A_ROWS, HAND_GENOME, K, T_ROWS, canonical_row
 
 pytestmark = pytest.mark.gpu
 
@@ -256,6 +258,45 @@ def test_device_refusals(counter):
     assert counter.sample_distances(_p(sd), len(sites), _p(ad), len(alleles), _p(gd), ns, _p(out)) == len(sites)
     assert counter.last_sample_distances_ms() > 0
     assert out.cpu().numpy().tobytes() == restate_sample_distances(sites, alleles, g).tobytes()
+
+
+def test_site_depths_and_sample_distances_refuse_a_broken_allele_chain_alike():
+    """one chain rule, two consumers.  Two tracts of the hand genome of tests/test_variants_cabi.py (AAA at 4, TTTTT at 11), each
+    with its reference row and one longer row, two samples of which the second has the longer rows: N8, N12 and N13 on the device
+    give two sites, two alleles and their genotypes.  That output with sites[1].first_allele off by one, and with
+    sites[0].n_alleles = 0, goes through tjamd_site_depths and tjamd_sample_distances: the same clause behind either name, and no
+    byte of any output (guarded buffers) is written"""
+    ns = 2
+    entries, _ = restate_reference_index(HAND_GENOME, K)
+    by_flat = {int(e["flat"]): e for e in entries}
+    keys, tracts, locs = [], [], []
+    for flat, rows in ((4, A_ROWS[:2]), (11, T_ROWS[:2])):
+        e = by_flat[flat]
+        tracts.append((len(keys), 2, 1, len(keys), 0, 0, 9))
+        keys += [canonical_row(*r) for r in rows]
+        locs.append((int(e["flat"]), int(e["contig"]), int(e["pos"]), int(e["length"]), 0, int(e["neg_strand"]), 1))
+    mat = np.array([[4, 0], [0, 5]] * 2, np.int32)                           # sample 0: the reference rows; sample 1: the longer ones
+    c = tj.Counter(K)
+    ref = tj.Reference(c, HAND_GENOME)
+    u, m, depths, _ = whole_chain(c, ref, np.array(keys, np.uint64), mat, np.array(tracts, tj.UNION_TRACT_DTYPE), np.array(locs, tj.LOCATION_DTYPE), entries, K)
+    sites, alleles, g = m["sites"], m["alleles"], depths["genotype"]
+    assert len(sites) == 2 and len(alleles) == 2 and g.tolist() == [[0, 1], [0, 1]] and sites["first_allele"].tolist() == [0, 1]
+    want = restate_sample_distances(sites, alleles, g)
+    check_distances(dev_distances(c, sites, alleles, g, ns), want)
+    for msg, field, idx, value in (("first_allele and n_alleles of the sites do not chain from 0 to 2", "first_allele", 1, 2),
+                                   ("a site has n_alleles < 1", "n_alleles", 0, 0)):
+        bad = sites.copy()
+        bad[field][idx] = value
+        said = []
+        for name, (rc, err, buf) in (("tjamd_site_depths", dev_depths(c, ref, u, bad, alleles)), ("tjamd_sample_distances", dev_distances(c, bad, alleles, g, ns))):
+            assert rc == -ERR_ARG and err.startswith(name + ": "), (msg, name, rc, err)
+            assert all(b.untouched() for b in (buf.values() if isinstance(buf, dict) else [buf])), (msg, name)
+            said.append(err[len(name):])
+        assert said[0] == said[1] == ": " + msg, (msg, said)
+    assert dev_depths(c, ref, u, sites, alleles)["genotype"].tobytes() == g.tobytes()      # the counter serves the next good calls
+    check_distances(dev_distances(c, sites, alleles, g, ns), want)
+    ref.close()
+    c.close()
 
 
 # ---- the pipeline ----------------------------------------------------------------------------------------------------------

@@ -16,10 +16,10 @@ import tatajuba_amd as tj
 from oracle import orc
 from tests.guarded import GuardedDevice, GuardedHost, frozen
 from tests.test_effects_cabi import (ALT_STOP, BAD_FEATURES, BOUNDARY, CDS, CODON_AA, DNA, EF, EFFECTS_HEADER, FRAMESHIFT, FT, IDENTICAL, INFRAME, NONE, OTHER,
-                                     REF_STOP, REGION, TF, VAR, CD, effects_tsv_line, restate_cds, restate_effects, revcomp, unpack8, variant_of)
+                                     REF_STOP, REGION, TF, VAR, CD, effects_tsv_line, one_feature, restate_cds, restate_effects, revcomp, unpack8, variant_of)
 from tests.test_features import dev_tract_features, gff3_of
 from tests.test_locate import _dev, _p, dev_locate, dev_located_tracts
-from tests.test_locate_cabi import restate_locate, restate_located_tracts, restate_reference_index
+from tests.test_locate_cabi import contigs_of, restate_locate, restate_located_tracts, restate_reference_index
 from tests.test_features_cabi import restate_tract_features
 from tests.test_union_tracts import _oracle_sample, device_union, make_genome, reads_of, sample_of
 from tests.test_union_tracts_cabi import oracle_union_grouping, restate_union_tract_stats
@@ -383,6 +383,33 @@ def test_device_refusals(counter, world):
         assert rc == -ERR_ARG and "the coding table lives on device 0, the counter on device 1" in L.tjamd_last_error().decode()
         other.close()
     same_records(dev_effects(counter, cod, good, tf), want, EF)
+
+
+def test_annotation_and_coding_table_refuse_a_feature_alike():
+    """one rule for a feature's contig, start and end, two tables: every row of BAD_FEATURES that a genome of two contigs can
+    express (the contig rows of the two-contig streams, the start and end rows) is refused by tjamd_annotation_create and by
+    tjamd_coding_create with the same clause behind the entry's own name, and neither leaves a handle or an interval"""
+    L = tj.lib()
+    g = b"ACGT\nAC\n"
+    rows = {msg: f for s, f, msg in BAD_FEATURES if "contig" not in msg or len(contigs_of(s)) == 2}
+    assert len(rows) == 4 and sorted(m.split(":")[1].split()[0] for m in rows) == ["contig", "contig", "end", "start"]
+    counter = tj.Counter(5)
+    ref = tj.Reference(counter, g)
+    assert ref.n_contigs == 2
+    for table in (lambda f: tj.Annotation(counter, ref, f), lambda f: tj.Coding(counter, g, f)):      # both tables take a good feature,
+        table(one_feature(contig=1, start=1, end=2)).close()                                           # so an interval stands to be cleared
+    assert counter.last_annotation_ms() > 0 and counter.last_coding_ms() > 0
+    for msg, f in rows.items():
+        said = []
+        for name, call, ms in (("tjamd_annotation_create", lambda: L.tjamd_annotation_create(counter._h, ref._h, f.ctypes.data, 1), counter.last_annotation_ms),
+                               ("tjamd_coding_create", lambda: L.tjamd_coding_create(counter._h, g, len(g), f.ctypes.data, 1, None), counter.last_coding_ms)):
+            h = call()
+            err = L.tjamd_last_error().decode()
+            assert not h and ms() == -1.0 and err.startswith(name + ": "), (name, msg, err)
+            said.append(err[len(name):])
+        assert said[0] == said[1] == ": " + msg, (msg, said)
+    ref.close()
+    counter.close()
 
 
 # ---- the pipeline ------------------------------------------------------------------------------------------------------

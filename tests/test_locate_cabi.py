@@ -199,6 +199,36 @@ def test_reference_create_without_a_device_names_the_error():
         assert "null counter" in err, err
 
 
+def test_index_and_coding_table_refuse_a_stream_alike():
+    """the two entries that take a genome stream from the host say one thing of it: a null stream with bytes, and a stream of
+    2^31 bytes (through a pointer that is never read).  Each says it where its own order puts it: tjamd_reference_create refuses
+    a missing device before it looks at anything else, tjamd_coding_create a null counter; so without a device the clause is
+    heard from the coding table alone, and with one (a real counter then) from both, word for word behind the entry's name."""
+    L = tj.lib()
+    fake = C.c_void_p(0x1000)
+    have_device = tj.device_count() > 0
+    counter = tj.Counter(5) if have_device else None
+    h = counter._h if have_device else fake      # (without a device no counter can exist, and neither entry reads the pointer)
+
+    def said(name, handle):
+        err = L.tjamd_last_error().decode()
+        assert not handle and err.startswith(name + ": "), (name, err)
+        return err[len(name) + 2:]
+
+    for stream, n_bytes, code_clause in ((None, 5, "null stream"), (fake, 1 << 31, "a stream of 2147483648 bytes (positions are 32-bit)")):
+        assert said("tjamd_coding_create", L.tjamd_coding_create(h, stream, n_bytes, None, 0, None)) == code_clause
+        assert said("tjamd_coding_create", L.tjamd_coding_create(None, stream, n_bytes, None, 0, None)) == "null counter"
+        of_index = said("tjamd_reference_create", L.tjamd_reference_create(h, stream, n_bytes))
+        of_index_without_counter = said("tjamd_reference_create", L.tjamd_reference_create(None, stream, n_bytes))
+        if have_device:
+            assert of_index == code_clause and of_index_without_counter == "null counter"
+            assert counter.last_reference_ms() == -1.0 and counter.last_coding_ms() == -1.0
+        else:
+            assert of_index.startswith("TJAMD_ERR_NO_DEVICE") and of_index_without_counter == of_index
+    if have_device:
+        counter.close()
+
+
 def test_locate_entries_check_their_arguments_without_a_gpu():
     L = tj.lib()
     fake = C.c_void_p(0x1000)                     # never dereferenced: each call below fails its argument checks first

@@ -239,6 +239,53 @@ def test_locate_gapped_with_ranges_on_both_sides_of_the_lane_walk(k, total):
     c.close()
 
 
+def test_both_lookups_at_the_edge_of_the_lane_walk():
+    """k = 2, the smallest the counter takes.  A contig of 2 + length + 2 bases holds one entry (its other runs lack a flank inside
+    the contig), so every bucket is built by hand from repeated A tracts that share one flank and differ in the other (and in
+    length): 16 and 17 tracts behind the left flanks CG and GT, 16 and 17 in front of the right flanks TC and CT.  The flanks'
+    inner bases keep the four groups apart as well, so the buckets of tjamd_locate (the whole flank) and the seed ranges of
+    tjamd_locate_gapped (h = 1: the inner base) both have exactly LC_LANE_WALK and LC_LANE_WALK + 1 entries, in either order of
+    the index.  One wavefront holds a row of each, rows that own a range of both lengths, and rows of base C, whose ranges are
+    empty.  The random cases of the tests above pass both lengths only by chance."""
+    k, W = 2, LC_LANE_WALK
+    rights, lefts = ("GA", "GC", "GG", "GT"), ("AC", "CC", "GC", "TC")       # (inner bases G and C: no other group has them)
+    contigs = [("CG", 3 + i % 5, rights[i % 4]) for i in range(W)] + [("GT", 3 + i % 6, rights[i % 4]) for i in range(W + 1)]
+    contigs += [(lefts[i % 4], 3 + i % 7, "TC") for i in range(W)] + [(lefts[i % 4], 3 + i % 4, "CT") for i in range(W + 1)]
+    g = "".join(f"{l}{'A' * n}{r}\n" for l, n, r in contigs).encode()
+    entries, n_contigs = restate_reference_index(g, k)
+    assert len(entries) == n_contigs == 4 * W + 2 and (entries["base"] == 0).all()
+    A, C_ = 0, 1
+    rows = [("CG", "GA", A), ("AA", "AA", C_), ("GT", "GG", A), ("AC", "TC", A), ("GC", "CT", A), ("CG", "CT", A), ("GT", "TC", A),
+            ("CG", "TT", A), ("GT", "AT", A), ("TT", "TC", A), ("CA", "CT", A), ("TG", "GG", C_), ("CG", "GT", A), ("GT", "GA", A), ("CG", "AC", A), ("TA", "TC", A)]
+    keys = np.array([canonical([CODE[ord(x)] for x in l], [CODE[ord(x)] for x in r], b)[:2] + (b | (5 << 2),) for l, r, b in rows], dtype=np.uint64)
+    assert len(keys) < 64
+    size = [dict(zip(*(x.tolist() for x in np.unique(entries[side], return_counts=True)))) for side in ("ctx0", "ctx1")]
+    b0 = np.array([size[0].get(int(a), 0) if int(m) & 3 == A else 0 for a, _, m in keys])
+    b1 = np.array([size[1].get(int(b), 0) if int(m) & 3 == A else 0 for _, b, m in keys])
+    r0, r1 = seed_ranges(entries, keys, k)
+    for own, other in ((b0, b1), (b1, b0), (r0, r1), (r1, r0)):              # each length on each side, alone in its row and beside the other
+        assert (own == W).any() and (own == W + 1).any() and ((own == W) & (other == W + 1)).any()
+        assert ((own == W) & (other < W)).any() and ((own == W + 1) & (other < W)).any()
+    assert (b0[[1, 11]] == 0).all() and (b1[[1, 11]] == 0).all() and (r0[[1, 11]] == 0).all() and (r1[[1, 11]] == 0).all()
+    c = tj.Counter(k)
+    ref = tj.Reference(c, g)
+    assert ref.add_seeds(c) == len(entries)
+    same_entries(ref.download(), entries)
+    for mm in (0, 1, 2):
+        want = restate_locate(entries, keys, mm)
+        n, got = dev_locate(c, ref, keys, mm)
+        assert got.tobytes() == want.tobytes() and n == int((want["flat"] >= 0).sum()) > 0, (mm, np.flatnonzero(got != want)[:5])
+    assert want["n_hits"].max() > W + 1 and (want["flat"][[1, 11]] < 0).all()
+    nowhere = np.zeros(len(keys), LOC)
+    nowhere[:] = NOWHERE
+    for max_edits, max_shift in ((0, 0), (1, 0), (2, 0), (1, 1), (2, 1)):
+        want, how = check_gapped(c, ref, entries, keys, nowhere, k, max_edits, max_shift)
+        assert (how[[1, 11]] == -1).all() and (how == 1).any()
+    assert want["n_hits"].max() > W + 1
+    ref.close()
+    c.close()
+
+
 # ---- every row located on entry, or none -------------------------------------------------------------------------------------
 
 def test_all_rows_located_already_and_none_located():

@@ -337,9 +337,12 @@ def test_new_entries_are_declared_exported_and_prototyped():
 def test_merge_variants_checks_its_arguments_without_a_gpu():
     L = tj.lib()
     fake = C.c_void_p(0x1000)                     # never dereferenced: each call below fails its argument checks first
+    # (but for the counter where a device is visible: a refused call clears that counter's interval, so it is a real one there)
+    counter = tj.Counter(15) if tj.device_count() > 0 else None
+    handle = C.c_void_p(counter._h) if counter else fake
     na = GuardedHost(8)
 
-    def call(c=fake, k=15, rec=fake, n=10, ns=2, nt=5, sites=fake, scap=10, alleles=fake, acap=10, gt=fake, aof=fake, uniq=fake, n_alleles=na.c):
+    def call(c=handle, k=15, rec=fake, n=10, ns=2, nt=5, sites=fake, scap=10, alleles=fake, acap=10, gt=fake, aof=fake, uniq=fake, n_alleles=na.c):
         rc = L.tjamd_merge_variants(c, k, rec, n, ns, nt, sites, scap, alleles, acap, gt, aof, uniq, n_alleles)
         return rc, L.tjamd_last_error().decode()
 
@@ -358,3 +361,6 @@ def test_merge_variants_checks_its_arguments_without_a_gpu():
             got, err = call(**kw)
             assert got == -ERR_NO_DEVICE and err.startswith("tjamd_merge_variants") and "TJAMD_ERR_NO_DEVICE" in err, (got, err)
         assert na.untouched()
+    else:
+        assert counter.last_merge_variants_ms() == -1.0
+        counter.close()
