@@ -59,6 +59,51 @@ int  tjamd_scan_host (tjamd_counter *c, const void *h_stream, size_t n_bytes, in
 long tjamd_scan_host_located (tjamd_counter *c, const void *h_stream, size_t n_bytes, int min_tract_size,
                               tjamd_located_record *out, long capacity);
 
+/* Plain FASTQ text parsed on the device (the three memchr and one memcpy per record of the host reader, as a line count and a
+ * compaction in HBM): text in, the stream of reads out, scanned at once or kept.  A session is tjamd_fastq_begin, any number
+ * of pushes, tjamd_fastq_end; the text is the concatenation of all pushes of the session, in order.
+ *
+ * The rule.  A regular record starting at offset p is four lines L0..L3, each ended by '\n', of which all of these hold:
+ *   L0[0] == '@';   len (L1) >= 1 and L1[0] is none of '>' '+' '@';   L2[0] == '+';   len (L3) == len (L1);
+ *   none of the record's bytes is '\r'.
+ * Line parity decides what is a header, the byte alone does not: a quality line may start with '@'.  On the push marked
+ * `final`, the end of the text ends a non-empty L3 that has no '\n'.  The consumed prefix is the longest run of regular
+ * records from offset 0; its stream is L1 + '\n' for each record, in order: what tjamd_read_file_stream makes of the same
+ * bytes.  Everything from the first irregular record on is left to the caller (tjamd_fastq_end says where it starts):
+ * FASTA and multi-line records, CRLF, a blank line, a quality line of another length, after `final` a record cut short,
+ * and the reference's stop at a bad quality string, which stays where it is, in the host reader.
+ *
+ * Pushes may cut the text anywhere, mid-line, mid-record, one byte at a time: the incomplete tail of a push is carried on
+ * the device (never through the host) in front of the next push's text.  The carry is at most TJAMD_FASTQ_CARRY_MAX bytes
+ * (TATAJUBA_AMD_FASTQ_CARRY in the environment when the counter is created shortens it: tests): a record that a push
+ * boundary cuts must end within that many bytes of its start, or the session stops with code 2 at its start.  After a
+ * stop the later pushes of the session do nothing.  A push does not wait for the device (growing a buffer, and a
+ * staging buffer of tjamd_fastq_push_host still in flight, may); tjamd_fastq_end is the one wait of a session.  d_text
+ * must stay as it is until then (or until a mark taken behind the push has been waited for); h_text is free again when
+ * tjamd_fastq_push_host returns unless it is pinned memory (tjamd_host_alloc), which is copied from where it lies and is
+ * free after such a mark.  No byte at or beyond d_text + n_bytes, rounded up to 16, is read.
+ *
+ * tjamd_fastq_begin: min_tract_size >= 0 scans every push's stream into the counter's raw records exactly as
+ * tjamd_scan_device would with that value -- which, like tjamd_scan_device, takes 1 ... 32 and refuses 0: the all-monomers
+ * scan exists for located records only (tjamd_scan_host_located) --, small pushes gathered into one scan launch, so the
+ * records are all there when tjamd_fastq_end has returned; -1 parses only and keeps the session's whole stream
+ * for tjamd_fastq_stream.  Refused with TJAMD_ERR_ARG: a push without begin, begin inside a session, a push after `final`;
+ * and, before a device is looked for: a null counter, null text with n_bytes > 0, n_bytes above 1 GiB, a d_text that is
+ * not 16-byte aligned, min_tract_size < -1.  Without a device: TJAMD_ERR_NO_DEVICE.  n_bytes == 0 is valid (how a caller
+ * says `final` late).  A session ended without a final push reports an incomplete record as stop 1.
+ * Not built: gzip or BGZF on the device, FASTA or multi-line records on the device, paired files in one session, read names. */
+enum { TJAMD_FASTQ_CARRY_MAX = 1 << 20 };
+int  tjamd_fastq_begin (tjamd_counter *c, int min_tract_size);
+int  tjamd_fastq_push_device (tjamd_counter *c, const void *d_text, size_t n_bytes, int final);   /* 16-byte aligned */
+int  tjamd_fastq_push_host   (tjamd_counter *c, const void *h_text, size_t n_bytes, int final);   /* staged copy, then the same */
+long tjamd_fastq_end (tjamd_counter *c);          /* waits; bytes of text consumed since begin, or a negative TJAMD_ERR_* */
+long tjamd_fastq_reads (const tjamd_counter *c);  /* records consumed by the last ended session */
+int  tjamd_fastq_stop (const tjamd_counter *c);   /* 0: all text consumed; 1: irregular record at the consumed offset;
+                                                     2: a record did not end within the carry */
+const void *tjamd_fastq_stream (const tjamd_counter *c);   /* device pointer, 16-byte aligned; parse-only sessions, else NULL */
+long tjamd_fastq_stream_bytes (const tjamd_counter *c);
+int  tjamd_fastq_tile_bytes (void);               /* text bytes one workgroup takes per step: what the edge tests aim at */
+
 /* Many short strings in one launch: what the reference does with one counter and one update_hopo_counter_from_seq call per
  * reference window (src/genome_set.c:525-577), batched.  seqs[i] / lens[i]: the windows; min_tract_size as in
  * update_hopo_counter_from_seq (0: the all-monomers scan).  out: hopo_element[capacity] in window order, then read order,
@@ -439,6 +484,7 @@ double tjamd_last_reference_ms (tjamd_counter *c);         /* kernels of the las
 double tjamd_last_locate_ms (tjamd_counter *c);            /* the lookup kernel of the last tjamd_locate */
 double tjamd_last_located_tracts_ms (tjamd_counter *c);    /* the last tjamd_located_tracts, first launch to last (host waits included) */
 double tjamd_last_tract_variants_ms (tjamd_counter *c);    /* the last tjamd_tract_variants, first launch to last */
+double tjamd_last_fastq_ms (tjamd_counter *c);    /* parse kernels of the last ended session; -1.0 for NULL / after a refusal */
 long   tjamd_last_scan_launches (tjamd_counter *c);
 /* finalises of this counter whose device-side sizing of the ordering step had read a stale kept count (checked against the
  * count at the next kernel boundary and repaired; expected to stay 0) */

@@ -145,7 +145,10 @@ EXPORTS = [
     "dna_in_2_bits", "bit_2_dna",
     "tjamd_device_count", "tjamd_source_hash", "tjamd_last_error", "tjamd_version", "tjamd_counter_create", "tjamd_counter_destroy",
     "tjamd_counter_reset", "tjamd_counter_set_stream", "tjamd_counter_set_order_stream", "tjamd_counter_device", "tjamd_scan_device", "tjamd_scan_host",
-    "tjamd_scan_host_located", "tjamd_read_file_stream_mt", "tjamd_host_alloc", "tjamd_host_free", "tjamd_device_alloc", "tjamd_device_free", "tjamd_device_download", "tjamd_sync", "tjamd_mark", "tjamd_wait_mark", "tjamd_reserve", "tjamd_raw_count",
+    "tjamd_scan_host_located",
+    "tjamd_fastq_begin", "tjamd_fastq_push_device", "tjamd_fastq_push_host", "tjamd_fastq_end", "tjamd_fastq_reads", "tjamd_fastq_stop", "tjamd_fastq_stream",
+    "tjamd_fastq_stream_bytes", "tjamd_fastq_tile_bytes", "tjamd_last_fastq_ms",
+    "tjamd_read_file_stream_mt", "tjamd_host_alloc", "tjamd_host_free", "tjamd_device_alloc", "tjamd_device_free", "tjamd_device_download", "tjamd_sync", "tjamd_mark", "tjamd_wait_mark", "tjamd_reserve", "tjamd_raw_count",
     "tjamd_download_raw", "tjamd_undefined_runs", "tjamd_upload_raw", "tjamd_finalise", "tjamd_finalise_begin", "tjamd_finalise_end", "tjamd_kept_count",
     "tjamd_n_idx", "tjamd_coverage", "tjamd_download_kept", "tjamd_download_idx", "tjamd_kept_device_ptr",
     "tjamd_merge_samples", "tjamd_gather_histograms", "tjamd_peer_access_report", "tjamd_comm_unique_id", "tjamd_comm_create", "tjamd_comm_destroy",
@@ -429,6 +432,16 @@ def lib():
                                      C.c_void_p, C.c_long, C.c_int]
     L.tjamd_read_file_stream.restype = C.c_long
     L.tjamd_read_file_stream.argtypes = [C.c_char_p, C.c_void_p, C.c_long, C.POINTER(C.c_long)]
+    L.tjamd_fastq_begin.restype = C.c_int; L.tjamd_fastq_begin.argtypes = [C.c_void_p, C.c_int]
+    L.tjamd_fastq_push_device.restype = C.c_int; L.tjamd_fastq_push_device.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]
+    L.tjamd_fastq_push_host.restype = C.c_int; L.tjamd_fastq_push_host.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]
+    L.tjamd_fastq_end.restype = C.c_long; L.tjamd_fastq_end.argtypes = [C.c_void_p]
+    L.tjamd_fastq_reads.restype = C.c_long; L.tjamd_fastq_reads.argtypes = [C.c_void_p]
+    L.tjamd_fastq_stop.restype = C.c_int; L.tjamd_fastq_stop.argtypes = [C.c_void_p]
+    L.tjamd_fastq_stream.restype = C.c_void_p; L.tjamd_fastq_stream.argtypes = [C.c_void_p]
+    L.tjamd_fastq_stream_bytes.restype = C.c_long; L.tjamd_fastq_stream_bytes.argtypes = [C.c_void_p]
+    L.tjamd_fastq_tile_bytes.restype = C.c_int; L.tjamd_fastq_tile_bytes.argtypes = []
+    L.tjamd_last_fastq_ms.restype = C.c_double; L.tjamd_last_fastq_ms.argtypes = [C.c_void_p]
     _LIB = L
     return L
 
@@ -798,6 +811,48 @@ class Counter:
         out = np.zeros(cap, dtype=LOCATED_DTYPE)
         n = self._chkn(lib().tjamd_scan_host_located(self._h, a.ctypes.data, a.size, m, out.ctypes.data, cap))
         return out[:n]
+
+    # FASTQ text parsed on the device (tjamd_fastq_*, include/tatajuba_amd.h): a session is begin, pushes, end
+    def fastq_begin(self, m=-1):
+        """m >= 1: every push's stream is scanned as scan_device would; -1: parse only, the stream is kept"""
+        self._chk(lib().tjamd_fastq_begin(self._h, m))
+
+    def fastq_push_host(self, buf, final=False):
+        a = np.ascontiguousarray(np.frombuffer(buf, dtype=np.uint8) if not isinstance(buf, np.ndarray) else buf)
+        self._chk(lib().tjamd_fastq_push_host(self._h, a.ctypes.data if a.size else None, a.size, int(final)))
+
+    def fastq_push_device(self, dptr, n_bytes, final=False):
+        """dptr: 16-byte aligned device memory that stays as it is until fastq_end"""
+        self._chk(lib().tjamd_fastq_push_device(self._h, C.c_void_p(dptr) if n_bytes else None, n_bytes, int(final)))
+
+    def fastq_end(self):
+        """waits; (bytes of text consumed, records, stop code, bytes of stream)"""
+        consumed = self._chkn(lib().tjamd_fastq_end(self._h))
+        return consumed, lib().tjamd_fastq_reads(self._h), lib().tjamd_fastq_stop(self._h), lib().tjamd_fastq_stream_bytes(self._h)
+
+    def fastq_stream(self):
+        """the stream of the last parse-only session, downloaded (bytes)"""
+        n, p = lib().tjamd_fastq_stream_bytes(self._h), lib().tjamd_fastq_stream(self._h)
+        out = np.zeros(max(n, 0), np.uint8)
+        if n > 0:
+            if not p:
+                raise TatajubaAmdError("the last session kept no stream (it scanned)")
+            self._chk(lib().tjamd_device_download(self._h, out.ctypes.data, C.c_void_p(p), n))
+        return out.tobytes()
+
+    def fastq_parse(self, text, cuts=()):
+        """One parse-only session over text, pushed from host memory in the pieces that the ascending offsets `cuts` make
+        of it, the last one final -> (consumed, reads, stop, stream bytes)."""
+        text = bytes(text)
+        edges = [0] + [int(x) for x in cuts] + [len(text)]
+        self.fastq_begin(-1)
+        for i in range(len(edges) - 1):
+            self.fastq_push_host(text[edges[i]: edges[i + 1]], final=(i == len(edges) - 2))
+        consumed, reads, stop, _ = self.fastq_end()
+        return consumed, reads, stop, self.fastq_stream()
+
+    def last_fastq_ms(self):
+        return lib().tjamd_last_fastq_ms(self._h)
 
     def raw_count(self):
         return self._chkn(lib().tjamd_raw_count(self._h))

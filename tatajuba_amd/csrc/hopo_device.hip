@@ -4076,6 +4076,8 @@ struct tjamd_counter
   int consensus_key_bits = 51;                          // TATAJUBA_AMD_CONSENSUS_KEY_BITS (tests): b in 0 .. 51: the bits of the hash sum that tjamd_consensus_tree keeps in a clade's key; CONS_KEY_BITS
   int groups_small = 1;                                 // TATAJUBA_AMD_GROUPS_SMALL (tests): 0: tjamd_group_sites never takes its wavefront-per-site form (64 samples and fewer)
   int clades_small = 1;                                 // TATAJUBA_AMD_CLADES_SMALL (tests): 0: tjamd_clade_sites never takes its wavefront-per-site form (64 samples and fewer)
+  int fastq_carry_max = TJAMD_FASTQ_CARRY_MAX;         // TATAJUBA_AMD_FASTQ_CARRY (tests): n >= 16 bytes: the longest record a push boundary of a tjamd_fastq_* session may cut
+  struct FastqSession *fq = nullptr;                    // tjamd_fastq_*: made by the first tjamd_fastq_begin (end of the file)
   bool buckets_clean = false;
   long plan_mismatches = 0;   // finalises whose in-kernel reading of the kept count differed from the kernel boundary's (expected: 0)
   bool ctr_clean = false;     // the scan counters are zero but for n_undefined (clear_buckets_kernel did it, no scan since)
@@ -4252,6 +4254,8 @@ extern "C" tjamd_counter *tjamd_counter_create (int device, int kmer_size)
   if (gs && !strcmp (gs, "0")) c->groups_small = 0;
   const char *cs = getenv ("TATAJUBA_AMD_CLADES_SMALL");     // test hook: 0 sends every tjamd_clade_sites through the workgroup-per-run form with its LDS scans
   if (cs && !strcmp (cs, "0")) c->clades_small = 0;
+  const char *fc = getenv ("TATAJUBA_AMD_FASTQ_CARRY");     // test hook: a shorter carry for the tjamd_fastq_* sessions of this counter
+  if (fc && atoi (fc) >= 16 && atoi (fc) <= TJAMD_FASTQ_CARRY_MAX) c->fastq_carry_max = atoi (fc);
   const char *sl = getenv ("TATAJUBA_AMD_BUCKET_SLACK");
   if (sl && atof (sl) >= 1.0) c->slack = atof (sl);
   HIPCHK_NULL (hipStreamCreateWithFlags (&c->own_stream, hipStreamNonBlocking));
@@ -4274,6 +4278,8 @@ extern "C" tjamd_counter *tjamd_counter_create (int device, int kmer_size)
   return made.release ();
 }
 
+static void fastq_release (tjamd_counter *c);         // (the buffers, events and pinned memory of its tjamd_fastq_* sessions)
+
 extern "C" void tjamd_counter_destroy (tjamd_counter *c)
 {
   if (!c) return;
@@ -4281,6 +4287,7 @@ extern "C" void tjamd_counter_destroy (tjamd_counter *c)
   if (c->stream) (void) hipStreamSynchronize (c->stream);   // (null: tjamd_counter_create got no further than that)
   if (c->fin.state == FIN_EVENT) (void) hipEventSynchronize (c->ev_done);   // (begun and never ended: its ordering step may be on another stream)
   side_stream_release (c);
+  fastq_release (c);
   DevBuf *all[] = {&c->log, &c->logmeta, &c->pool, &c->table, &c->stage, &c->fix, &c->loc, &c->prefix, &c->rawlist, &c->slow, &c->alt, &c->hist, &c->flags, &c->segid, &c->headpos,
                    &c->keep, &c->outpos, &c->scan_tmp, &c->kept, &c->idx_i, &c->idx_f, &c->cov, &c->bins, &c->binstart, &c->binctx, &c->ovf, &c->grp_jt, &c->grp_hist, &c->fine,
                    &c->ts_cov, &c->ts_aux, &c->ut_tot, &c->ut_lev, &c->ut_fb, &c->ut_slots, &c->lc_work};
@@ -11984,3 +11991,473 @@ extern "C" long tjamd_consensus_tree (tjamd_counter *c, const tjamd_tree_node *d
   return (long) h_flags[2];
 }
 TJ_LAST_MS (tjamd_last_consensus_tree_ms, T_CONSENSUS_TREE)
+
+// ---------------------------------------------------------------------------------------------------------------
+// Plain FASTQ text parsed on the device (tjamd_fastq_*; the rule: include/tatajuba_amd.h).
+//
+// A push sees a logical text: the carry region of `cap` bytes (a multiple of FQ_TILE; the carried tail lies at its end, from
+// FqState::start on) and behind it the pushed bytes where they lie, so a 16-byte chunk and a tile are in one of the two.  The
+// host knows bounds only (the carry is at most what the push before could see, or what a look-back that has arrived says;
+// the stream at most half the text), sizes every grid and buffer from them, and waits for nothing before tjamd_fastq_end;
+// what a kernel needs of the device's own numbers it takes from FqState, which the kernel before it wrote.  Per push: fq_count_kernel (line ends per tile, the first '\r'),
+// a scan of the tile counts, fq_lines_kernel (the line ends as 32-bit offsets), fq_check_kernel (one lane per record of four
+// lines: the rule, len (L1) + 1), a scan of those lengths, fq_finish_kernel (one lane: the consumed prefix, the stop, the
+// session's sums), fq_copy_kernel (the stream, by output position: 16 bytes a lane whatever the read lengths are) and
+// fq_carry_kernel (the tail, into the other of two carry buffers).  No workgroup waits for another: kernel boundaries order it all.
+
+#define FQ_TILE   4096                  // text bytes of one workgroup: 256 lanes x 16 bytes (a wavefront spans 1024)
+#define FQ_BLOCK  256
+#define FQ_MAX_PUSH (1ull << 30)
+#define FQ_STAGE_BYTES (8u << 20)       // tjamd_fastq_push_host from pageable memory: two pinned buffers of this size
+#define FQ_SCAN_BATCH (16u << 20)       // a session that scans hands its stream on when this many bytes may have gathered (every push of 32 MiB of text and more)
+#define FQ_TIMED_PUSHES 1024            // pushes of a session with an event pair of their own; a longer session has no time
+#define FQ_LOOKS  8
+#define FQ_NONE   0xFFFFFFFFu
+
+struct FqState
+{ // (device; tjamd_fastq_end copies it to the host)
+  u32 start;                            // logical offset of the first byte not yet consumed (cap: no carry)
+  u32 stop;
+  u32 n_lines;                          // line ends of this push from start on
+  u32 first_bad, first_cr, big0;        // this push: the first irregular record, the first '\r', record 0 began in the carry and outgrew it
+  u32 n_good, push_stream;              // records this push consumed, their stream bytes
+  u32 new_pos, tail_len;                // where the unconsumed tail starts, and its length
+  u64 consumed, reads, stream_total;    // of the session
+  u64 stream_fill, stream_base;         // bytes in the stream buffer; where this push's bytes begin in it
+};
+
+struct FqSrc { const uint8_t *carry, *text; u32 cap, lo, end; int final; };   // tiles start at lo; end = cap + the push's bytes
+
+__device__ __forceinline__ u32 fq_byte (const FqSrc &S, u32 p) { return p < S.cap ? S.carry[p] : S.text[p - S.cap]; }
+
+// bit i: byte p0 + i of the logical text, in [start, end), is a line end -- a '\n', or the end of a final text whose last
+// byte is none (the bit of position `end`); cr: the same for '\r'
+__device__ __forceinline__ u32 fq_chunk_masks (const FqSrc &S, u32 p0, u32 start, u32 &cr)
+{
+  u32 nl = 0;
+  cr = 0;
+  if (p0 < S.end && p0 + 16 > start) {
+    const uint4 v = *(const uint4 *) (p0 < S.cap ? S.carry + p0 : S.text + (p0 - S.cap));
+    const u32 w[4] = {v.x, v.y, v.z, v.w};
+    #pragma unroll
+    for (int j = 0; j < 4; j++) {
+      #pragma unroll
+      for (int b = 0; b < 4; b++) {
+        const u32 ch = (w[j] >> (8 * b)) & 0xFFu;
+        nl |= (u32) (ch == (u32) '\n') << (4 * j + b);
+        cr |= (u32) (ch == (u32) '\r') << (4 * j + b);
+      }
+    }
+    u32 keep = 0xFFFFu;
+    if (start > p0) keep &= 0xFFFFu << (start - p0);
+    if (S.end - p0 < 16) keep &= (1u << (S.end - p0)) - 1u;
+    nl &= keep; cr &= keep;
+  }
+  if (S.final && S.end > start && (S.end & ~15u) == p0 && fq_byte (S, S.end - 1) != (u32) '\n') nl |= 1u << (S.end - p0);
+  return nl;
+}
+
+__global__ void fq_begin_kernel (FqState *st, u32 cap)
+{
+  FqState z = {};
+  z.start = cap; z.first_bad = z.first_cr = FQ_NONE;
+  *st = z;
+}
+
+__global__ __launch_bounds__ (FQ_BLOCK)
+void fq_count_kernel (FqSrc S, FqState *st, u32 *__restrict__ tile_count)
+{
+  __shared__ u32 s_tmp[4];
+  if (st->stop) return;
+  const u32 p0 = S.lo + blockIdx.x * FQ_TILE + threadIdx.x * 16u;
+  u32 cr;
+  const u32 nl = fq_chunk_masks (S, p0, st->start, cr);
+  u32 total;
+  block_exclusive_scan_256 (__popc (nl), s_tmp, total);
+  if (threadIdx.x == 0) tile_count[blockIdx.x] = total;
+  if (cr) { const u32 at = p0 + (u32) __ffs (cr) - 1u; if (at < st->first_cr) atomicMin (&st->first_cr, at); }
+}
+
+__global__ __launch_bounds__ (FQ_BLOCK)
+void fq_lines_kernel (FqSrc S, const FqState *st, const u32 *__restrict__ tile_base, u32 *__restrict__ lineend, u32 lcap)
+{
+  __shared__ u32 s_tmp[4];
+  if (st->stop) return;
+  const u32 p0 = S.lo + blockIdx.x * FQ_TILE + threadIdx.x * 16u;
+  u32 cr, nl = fq_chunk_masks (S, p0, st->start, cr);
+  u32 total;
+  u32 rank = tile_base[blockIdx.x] + block_exclusive_scan_256 (__popc (nl), s_tmp, total);
+  while (nl) {
+    if (rank < lcap) lineend[rank] = p0 + (u32) __ffs (nl) - 1u;
+    rank++; nl &= nl - 1u;
+  }
+}
+
+// one lane per record r of the first lcap line ends (lcap / 4 = rb records at most; more lines than lcap: a record among
+// these is irregular, since rb regular records are longer than the text): the rule, and len[r] = len (L1) + 1, 0 from the
+// last whole record on, up to and including r = rb
+__global__ void fq_check_kernel (FqSrc S, FqState *st, const u32 *__restrict__ lineend, u32 lcap, u32 rb, u32 carry_max, u32 *__restrict__ len)
+{
+  const u32 r = blockIdx.x * blockDim.x + threadIdx.x;
+  if (r > rb || st->stop) return;
+  const u32 n_rec = min (st->n_lines, lcap) >> 2;
+  u32 l = 0;
+  if (r < n_rec) {
+    const u32 s0 = r ? lineend[4 * r - 1] + 1u : st->start;
+    const u32 e0 = lineend[4 * r], e1 = lineend[4 * r + 1], e2 = lineend[4 * r + 2], e3 = lineend[4 * r + 3];
+    const u32 l1 = e1 - e0 - 1u, l3 = e3 - e2 - 1u, cr = st->first_cr;
+    bool ok = fq_byte (S, s0) == (u32) '@' && l1 >= 1u && l3 == l1 && !(cr >= s0 && cr <= e3);   // (an empty line's first byte is its '\n', never the text's end)
+    if (ok) { const u32 ch = fq_byte (S, e0 + 1u); ok = ch != (u32) '>' && ch != (u32) '+' && ch != (u32) '@' && fq_byte (S, e1 + 1u) == (u32) '+'; }
+    if (!ok && r < st->first_bad) atomicMin (&st->first_bad, r);
+    if (r == 0 && s0 < S.cap && min (e3 + 1u, S.end) - s0 > carry_max) st->big0 = 1u;   // cut by a push boundary and longer than the carry
+    l = l1 + 1u;
+  }
+  len[r] = l;
+}
+
+__global__ void fq_finish_kernel (FqSrc S, FqState *st, const u32 *__restrict__ lineend, const u32 *__restrict__ off, u32 lcap, u32 carry_max, int flush)
+{ // flush: the stream buffer is handed to the scan behind this push, the next push's bytes begin at its start
+  if (threadIdx.x || blockIdx.x) return;
+  st->stream_base = st->stream_fill;
+  if (st->stop) { st->n_good = 0; st->push_stream = 0; if (flush) st->stream_fill = 0; return; }
+  const u32 n_rec = min (st->n_lines, lcap) >> 2, bad = st->big0 ? 0u : st->first_bad;
+  const u32 n_good = min (bad, n_rec);
+  const u32 new_pos = n_good ? min (lineend[4 * n_good - 1] + 1u, S.end) : st->start;
+  const u32 tail = S.end - new_pos, grown = off[n_good];
+  u32 stop = 0;
+  if (st->big0) stop = 2;
+  else if (bad < n_rec) stop = 1;
+  else if (!S.final && tail > carry_max) stop = 2;
+  st->consumed += new_pos - st->start; st->reads += n_good; st->stream_total += grown;
+  st->stream_fill = flush ? 0ull : st->stream_fill + grown;
+  st->n_good = n_good; st->push_stream = grown; st->new_pos = new_pos; st->tail_len = tail; st->stop = stop;
+  st->start = (stop || S.final) ? S.cap : S.cap - tail;
+  st->first_bad = st->first_cr = FQ_NONE; st->big0 = 0;
+}
+
+// the largest r in [lo, hi] with off[r] <= o (off[lo] <= o)
+__device__ __forceinline__ u32 fq_record_of (const u32 *__restrict__ off, u32 lo, u32 hi, u32 o)
+{
+  while (lo < hi) { const u32 mid = (lo + hi + 1u) >> 1; if (off[mid] <= o) lo = mid; else hi = mid - 1u; }
+  return lo;
+}
+
+// The stream by output position: a lane makes the 16 bytes at one 16-byte line of the stream buffer, from whichever records
+// they come, and stores them at once (byte by byte on the push's first and last line).  pad_to != 0 (scan sessions): every
+// byte from the data's end to pad_to is a '\n', so that the scan can take the host's bound for the length.
+__global__ __launch_bounds__ (256)
+void fq_copy_kernel (FqSrc S, const FqState *st, const u32 *__restrict__ lineend, const u32 *__restrict__ len, const u32 *__restrict__ off,
+                     uint8_t *__restrict__ stream, u64 pad_to)
+{
+  __shared__ u32 s_r[2];
+  const u64 base = st->stream_base, data_hi = base + st->push_stream, w_hi = pad_to ? pad_to : data_hi;
+  const u32 n_good = st->n_good;
+  const u64 a_blk = (base & ~15ull) + (u64) blockIdx.x * 4096ull;
+  if (a_blk >= w_hi) return;
+  const bool has_data = n_good && a_blk < data_hi;
+  if (has_data && threadIdx.x < 2) {
+    const u64 a = threadIdx.x ? min (a_blk + 4096ull, data_hi) - 1ull : max (a_blk, base);
+    s_r[threadIdx.x] = fq_record_of (off, 0u, n_good - 1u, (u32) (a - base));
+  }
+  __syncthreads ();
+  const u64 a0 = a_blk + 16ull * threadIdx.x;
+  if (a0 >= w_hi || a0 + 16ull <= base) return;
+  u32 r = 0, j = 0, l = 0, p = 0;
+  const u64 a_first = max (a0, base);
+  if (has_data && a_first < data_hi) {
+    const u32 o = (u32) (a_first - base);
+    r = fq_record_of (off, s_r[0], s_r[1], o);
+    j = o - off[r]; l = len[r]; p = lineend[4 * r] + 1u + j;
+  }
+  u32 w[4] = {0u, 0u, 0u, 0u};
+  #pragma unroll
+  for (int i = 0; i < 16; i++) {
+    const u64 a = a0 + (u64) i;
+    u32 ch = (u32) '\n';
+    if (a >= base && a < data_hi) {
+      if (j + 1u < l) ch = fq_byte (S, p);
+      j++; p++;
+      if (j == l) { r++; j = 0; if (r < n_good) { l = len[r]; p = lineend[4 * r] + 1u; } }
+    }
+    w[i >> 2] |= ch << (8 * (i & 3));
+  }
+  if (a0 >= base && a0 + 16ull <= w_hi) *(uint4 *) (stream + a0) = make_uint4 (w[0], w[1], w[2], w[3]);
+  else {
+    #pragma unroll
+    for (int i = 0; i < 16; i++) { const u64 a = a0 + (u64) i; if (a >= base && a < w_hi) stream[a] = (uint8_t) (w[i >> 2] >> (8 * (i & 3))); }
+  }
+}
+
+__global__ void fq_carry_kernel (FqSrc S, const FqState *st, uint8_t *__restrict__ next_carry)
+{ // the tail [new_pos, new_pos + tail_len) to the end of the other carry buffer
+  if (st->stop || S.final) return;
+  const u32 tail = st->tail_len, from = st->new_pos, to = S.cap - tail;
+  const u32 i0 = (blockIdx.x * blockDim.x + threadIdx.x) * 16u;
+  for (u32 i = i0; i < min (i0 + 16u, tail); i++) next_carry[to + i] = (uint8_t) fq_byte (S, from + i);
+}
+
+struct FastqSession
+{
+  bool open = false, final_seen = false, ended = false;
+  int m = -1;                                           // -1: parse only
+  u32 cap = 0;                                          // the carry region: the counter's carry limit rounded up to tiles
+  // What the host knows.  The carry is at most carry_bound: what the push before could see, and less once a look-back has
+  // arrived (below).  The stream in the buffer comes from text_since bytes at most -- the carry bound when the buffer was
+  // last handed to the scan, plus every byte pushed since -- so it is at most half of them: a bound of the session, which
+  // the number of pushes does not enter.
+  size_t carry_bound = 0, text_since = 0, stream_bound = 0, pushed = 0;
+  // look-backs: behind every push the state block is copied to one of FQ_LOOKS pinned slots, and a later push takes from the
+  // slots whose copy has arrived (asked without waiting) the tail that push left: the carry is at most that plus what was
+  // pushed since.  Without them the bound could only rise, to the carry's limit, and stay there whatever the pushes hold.
+  FqState *look = nullptr; hipEvent_t look_ev[FQ_LOOKS] = {}; bool look_used[FQ_LOOKS] = {}; size_t look_pushed[FQ_LOOKS] = {};
+  bool seen_stop = false;
+  int cur = 0;                                          // which carry buffer the next push reads
+  DevBuf carry[2], state, text, stream;
+  void *pin[2] = {nullptr, nullptr}; hipEvent_t pin_ev[2] = {nullptr, nullptr}; bool pin_used[2] = {false, false}; int pin_next = 0;
+  std::vector<hipEvent_t> ev;                           // pairs around the parse kernels of the pushes
+  long n_push = 0;
+  long consumed = -1, reads = 0, stream_bytes = 0; int stop = 0; bool kept = false; double ms = -1.0;
+};
+
+static void fastq_release (tjamd_counter *c)
+{
+  FastqSession *q = c->fq;
+  if (!q) return;
+  DevBuf *all[] = {&q->carry[0], &q->carry[1], &q->state, &q->text, &q->stream};
+  for (DevBuf *b : all) release (*b);
+  for (int i = 0; i < 2; i++) { if (q->pin[i]) (void) hipHostFree (q->pin[i]); if (q->pin_ev[i]) (void) hipEventDestroy (q->pin_ev[i]); }
+  for (hipEvent_t e : q->ev) (void) hipEventDestroy (e);
+  for (hipEvent_t e : q->look_ev) if (e) (void) hipEventDestroy (e);
+  if (q->look) (void) hipHostFree (q->look);
+  delete q;
+  c->fq = nullptr;
+}
+
+extern "C" int tjamd_fastq_tile_bytes (void) { return FQ_TILE; }
+// diagnostic (tests, tools): the sessions this process has ended -- how a run of the drop-in shows which way its file went
+static long g_fastq_sessions = 0;
+extern "C" long tjamd_debug_fastq_sessions (void) { return __atomic_load_n (&g_fastq_sessions, __ATOMIC_RELAXED); }
+
+// The counter of this thread's last call that was refused before the counter was read (it may be no counter at all: the
+// pointer is compared, never followed): tjamd_last_fastq_ms gives -1.0 for it until a call on it gets through.
+static thread_local const tjamd_counter *g_fastq_refused = nullptr;
+
+static int fastq_host_refusal (const char *fn, tjamd_counter *c, const void *text, size_t n_bytes, bool device_text, int min_tract_size)
+{
+  if (!c) return set_err (TJAMD_ERR_ARG, "%s: TJAMD_ERR_ARG: null counter", fn);
+  if (!text && n_bytes) return set_err (TJAMD_ERR_ARG, "%s: TJAMD_ERR_ARG: null text with n_bytes %zu", fn, n_bytes);
+  if (n_bytes > FQ_MAX_PUSH) return set_err (TJAMD_ERR_ARG, "%s: TJAMD_ERR_ARG: n_bytes %zu above 1 GiB (push the text in pieces)", fn, n_bytes);
+  if (device_text && ((uintptr_t) text & 15u)) return set_err (TJAMD_ERR_ARG, "%s: TJAMD_ERR_ARG: d_text must be 16-byte aligned", fn);
+  if (min_tract_size < -1) return set_err (TJAMD_ERR_ARG, "%s: TJAMD_ERR_ARG: min_tract_size %d below -1", fn, min_tract_size);
+  if (tjamd_device_count () <= 0) return set_err (TJAMD_ERR_NO_DEVICE, "%s: TJAMD_ERR_NO_DEVICE: no HIP device visible (the text is parsed on the device; no CPU fallback)", fn);
+  return TJAMD_OK;
+}
+
+// the refusals of a call that need no device, then the one without a device, then the counter's device
+static int fastq_enter (const char *fn, tjamd_counter *c, const void *text, size_t n_bytes, bool device_text, int min_tract_size)
+{
+  const int rc = fastq_host_refusal (fn, c, text, n_bytes, device_text, min_tract_size);
+  if (rc) { g_fastq_refused = c; return rc; }
+  if (g_fastq_refused == c) g_fastq_refused = nullptr;
+  if (c->fq) c->fq->ms = -1.0;                          // (a refused call leaves no timing behind: tjamd_fastq_end sets it again)
+  return hipSetDevice (c->device) == hipSuccess ? TJAMD_OK : set_err (TJAMD_ERR_HIP, "hipSetDevice failed");
+}
+
+// the look-backs that have arrived: a smaller carry bound, and whether the session is known to have stopped
+static void fastq_look_back (FastqSession *q, u32 carry_max)
+{
+  for (int i = 0; i < FQ_LOOKS; i++) {
+    if (!q->look_used[i] || hipEventQuery (q->look_ev[i]) != hipSuccess) continue;
+    const FqState &h = q->look[i];
+    if (h.stop) q->seen_stop = true;
+    const size_t tail = (h.stop ? 0 : (size_t) h.tail_len) + (q->pushed - q->look_pushed[i]);
+    q->carry_bound = std::min (q->carry_bound, std::min ((size_t) carry_max, tail));
+    q->look_used[i] = false;
+  }
+  (void) hipGetLastError ();                            // (a copy that has not arrived is an error to hipEventQuery, not to the call)
+}
+
+// (hopo_host.c, not exported: a session that is known to have stopped takes no more text in)
+extern "C" int tj_fastq_seen_stop (tjamd_counter *c)
+{
+  if (!c || !c->fq || !c->fq->open || hipSetDevice (c->device) != hipSuccess) return 0;
+  fastq_look_back (c->fq, (u32) c->fastq_carry_max);
+  return c->fq->seen_stop ? 1 : 0;
+}
+
+// diagnostic (tests): what a counter's sessions hold on to -- 0: bytes of the stream buffer, 1: bytes of the scratch block
+// the pushes cut up, 2: the bound of the raw records that sizes their storage
+extern "C" long tjamd_debug_fastq_footprint (const tjamd_counter *c, int what)
+{
+  if (!c) return -1;
+  return what == 0 ? (c->fq ? (long) c->fq->stream.cap : 0) : what == 1 ? (long) c->lc_work.cap : what == 2 ? (long) c->raw_bound : -1;
+}
+
+extern "C" int tjamd_fastq_begin (tjamd_counter *c, int min_tract_size)
+{
+  static const char *fn = "tjamd_fastq_begin";
+  int rc = fastq_enter (fn, c, nullptr, 0, false, min_tract_size);
+  if (rc) return rc;
+  if (c->fq && c->fq->open) return set_err (TJAMD_ERR_ARG, "%s: TJAMD_ERR_ARG: a session is open on this counter (tjamd_fastq_end closes it)", fn);
+  if (min_tract_size >= 0 && (rc = check_scan_args (c, min_tract_size))) return rc;
+  if (!c->fq) c->fq = new FastqSession ();
+  FastqSession *q = c->fq;
+  q->cap = (u32) (((size_t) c->fastq_carry_max + FQ_TILE - 1) / FQ_TILE * FQ_TILE);
+  for (int i = 0; i < 2 && !rc; i++) rc = ensure (q->carry[i], q->cap, c->stream);
+  if (!rc) rc = ensure (q->state, sizeof (FqState), c->stream);
+  if (rc) return rc;
+  if (!q->look) {
+    HIPCHK (hipHostMalloc ((void **) &q->look, FQ_LOOKS * sizeof (FqState), hipHostMallocDefault));
+    for (hipEvent_t &e : q->look_ev) HIPCHK (hipEventCreateWithFlags (&e, hipEventDisableTiming));
+  }
+  hipLaunchKernelGGL (fq_begin_kernel, dim3 (1), dim3 (1), 0, c->stream, (FqState *) q->state.p, q->cap);
+  HIPCHK (hipGetLastError ());
+  q->open = true; q->final_seen = false; q->ended = false; q->m = min_tract_size;
+  q->carry_bound = 0; q->text_since = 0; q->stream_bound = 0; q->pushed = 0; q->cur = 0; q->n_push = 0; q->seen_stop = false;
+  for (bool &u : q->look_used) u = false;               // (the last session's end waited for its copies)
+  return TJAMD_OK;
+}
+
+// One push of an open session.  A session that scans gathers its stream in the buffer as one that parses only does, and
+// hands it to the scan when FQ_SCAN_BATCH bytes may have gathered, on the final push and (`hand_on`) at the session's end:
+// every scan launch adds a worst case of its own to the bounds that size the counter's record storage, which thousands of
+// small pushes would run out of memory on.
+static int fastq_push (tjamd_counter *c, const void *d_text, size_t n_bytes, int final, bool hand_on)
+{
+  FastqSession *q = c->fq;
+  int rc;
+  const u32 cap = q->cap, carry_max = (u32) c->fastq_carry_max;
+  fastq_look_back (q, carry_max);
+  const size_t avail = q->carry_bound + n_bytes;        // text this push can see, at most
+  if (avail == 0 && !hand_on) return TJAMD_OK;
+  FqSrc S;
+  S.carry = (const uint8_t *) q->carry[q->cur].p; S.text = (const uint8_t *) d_text; S.cap = cap;
+  S.lo = cap - (u32) ((q->carry_bound + FQ_TILE - 1) / FQ_TILE * FQ_TILE); S.end = cap + (u32) n_bytes; S.final = final ? 1 : 0;
+  const long n_tiles = (long) ((S.end - S.lo) / FQ_TILE) + 1;
+  const u32 rb = (u32) (avail / 8 + 1), lcap = 4u * rb;  // a regular record is eight bytes or more
+  const size_t grown = avail / 2 + 16;                  // ... and gives at most half of them to the stream: this push's share
+  const bool keep = q->m < 0;
+  const size_t had = q->stream_bound, bound = (q->text_since + n_bytes) / 2 + 16, need = (bound + 15) & ~(size_t) 15;   // the buffer's, behind this push
+  const bool flush = !keep && (hand_on || final || bound >= FQ_SCAN_BATCH);
+  rc = ensure (q->stream, need + 256, c->stream, std::min (had, q->stream.cap));
+  if (rc) return rc;
+  ScratchCut cut;
+  u32 *tile_count, *tile_base, *lineend, *len, *off, *tmp;
+  const size_t tmp_words = scan_tmp_words (std::max<long> (n_tiles, (long) rb + 1));
+  cut.take (tile_count, (size_t) n_tiles); cut.take (tile_base, (size_t) n_tiles); cut.take (lineend, (size_t) lcap);
+  cut.take (len, (size_t) rb + 1); cut.take (off, (size_t) rb + 1); cut.take (tmp, tmp_words);
+  rc = cut.commit (c);
+  if (rc) return rc;
+  FqState *st = (FqState *) q->state.p;
+  const bool timed = q->n_push < FQ_TIMED_PUSHES;
+  if (timed) {
+    while (q->ev.size () < (size_t) (2 * q->n_push + 2)) { hipEvent_t e; HIPCHK (hipEventCreate (&e)); q->ev.push_back (e); }
+    HIPCHK (hipEventRecord (q->ev[2 * q->n_push], c->stream));
+  }
+  hipLaunchKernelGGL (fq_count_kernel, dim3 ((unsigned) n_tiles), dim3 (FQ_BLOCK), 0, c->stream, S, st, tile_count);
+  rc = exclusive_scan (c, tile_count, tile_base, n_tiles, &st->n_lines, tmp, tmp_words);
+  if (rc) return rc;
+  hipLaunchKernelGGL (fq_lines_kernel, dim3 ((unsigned) n_tiles), dim3 (FQ_BLOCK), 0, c->stream, S, (const FqState *) st, (const u32 *) tile_base, lineend, lcap);
+  hipLaunchKernelGGL (fq_check_kernel, dim3 (rb / 256 + 1), dim3 (256), 0, c->stream, S, st, (const u32 *) lineend, lcap, rb, carry_max, len);
+  rc = exclusive_scan (c, len, off, (long) rb + 1, nullptr, tmp, tmp_words);
+  if (rc) return rc;
+  hipLaunchKernelGGL (fq_finish_kernel, dim3 (1), dim3 (64), 0, c->stream, S, st, (const u32 *) lineend, (const u32 *) off, lcap, carry_max, flush ? 1 : 0);
+  // (the copy's first line may begin up to 15 bytes in front of the push's first byte: one block more than the bytes need;
+  // a push that pads the buffer for the scan does not know where its bytes begin, and takes blocks for all of it)
+  hipLaunchKernelGGL (fq_copy_kernel, dim3 ((unsigned) (((flush ? need : grown) + 15) / 4096 + 2)), dim3 (256), 0, c->stream, S, (const FqState *) st, (const u32 *) lineend, (const u32 *) len,
+                      (const u32 *) off, (uint8_t *) q->stream.p, flush ? (u64) need : 0ull);
+  if (!final) {
+    const size_t carry_next = std::min ((size_t) carry_max, avail);
+    hipLaunchKernelGGL (fq_carry_kernel, dim3 ((unsigned) std::max<size_t> (1, (carry_next + 4095) / 4096)), dim3 (256), 0, c->stream, S, (const FqState *) st, (uint8_t *) q->carry[q->cur ^ 1].p);   // (nothing in sight: one workgroup that finds no tail)
+    q->carry_bound = carry_next; q->cur ^= 1;
+  }
+  else q->carry_bound = 0;
+  HIPCHK (hipGetLastError ());
+  if (timed) HIPCHK (hipEventRecord (q->ev[2 * q->n_push + 1], c->stream));
+  q->pushed += n_bytes;
+  const int slot = (int) (q->n_push % FQ_LOOKS);         // (a slot whose copy is still on its way is left alone: this push leaves no look-back)
+  if (!q->look_used[slot]) {
+    HIPCHK (hipMemcpyAsync (&q->look[slot], st, sizeof (FqState), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK (hipEventRecord (q->look_ev[slot], c->stream));
+    q->look_used[slot] = true; q->look_pushed[slot] = q->pushed;
+  }
+  q->n_push++;
+  q->text_since = flush ? q->carry_bound : q->text_since + n_bytes;
+  q->stream_bound = flush ? 0 : bound;
+  if (flush && (rc = tjamd_scan_device (c, q->stream.p, need, q->m))) return rc;
+  return TJAMD_OK;
+}
+
+extern "C" int tjamd_fastq_push_device (tjamd_counter *c, const void *d_text, size_t n_bytes, int final)
+{
+  static const char *fn = "tjamd_fastq_push_device";
+  int rc = fastq_enter (fn, c, d_text, n_bytes, true, 0);
+  if (rc) return rc;
+  FastqSession *q = c->fq;
+  if (!q || !q->open) return set_err (TJAMD_ERR_ARG, "%s: TJAMD_ERR_ARG: no session is open on this counter (tjamd_fastq_begin opens one)", fn);
+  if (q->final_seen) return set_err (TJAMD_ERR_ARG, "%s: TJAMD_ERR_ARG: a push behind the final one", fn);
+  rc = fastq_push (c, d_text, n_bytes, final, false);
+  if (!rc && final) q->final_seen = true;
+  return rc;
+}
+
+extern "C" int tjamd_fastq_push_host (tjamd_counter *c, const void *h_text, size_t n_bytes, int final)
+{
+  static const char *fn = "tjamd_fastq_push_host";
+  int rc = fastq_enter (fn, c, h_text, n_bytes, false, 0);
+  if (rc) return rc;
+  FastqSession *q = c->fq;
+  if (!q || !q->open) return set_err (TJAMD_ERR_ARG, "%s: TJAMD_ERR_ARG: no session is open on this counter (tjamd_fastq_begin opens one)", fn);
+  if (q->final_seen) return set_err (TJAMD_ERR_ARG, "%s: TJAMD_ERR_ARG: a push behind the final one", fn);
+  if (n_bytes) {
+    rc = ensure (q->text, ((n_bytes + 15) & ~(size_t) 15) + 256, c->stream);
+    if (rc) return rc;
+    hipPointerAttribute_t at;
+    const bool pinned = hipPointerGetAttributes (&at, h_text) == hipSuccess && at.type == hipMemoryTypeHost;
+    (void) hipGetLastError ();                          // (pageable memory is an error to that call, not to this one)
+    if (pinned) HIPCHK (hipMemcpyAsync (q->text.p, h_text, n_bytes, hipMemcpyHostToDevice, c->stream));
+    else {
+      for (size_t at_byte = 0; at_byte < n_bytes; at_byte += FQ_STAGE_BYTES) {
+        const int b = q->pin_next;
+        const size_t part = std::min ((size_t) FQ_STAGE_BYTES, n_bytes - at_byte);
+        if (!q->pin[b]) { HIPCHK (hipHostMalloc (&q->pin[b], FQ_STAGE_BYTES, hipHostMallocDefault)); HIPCHK (hipEventCreateWithFlags (&q->pin_ev[b], hipEventDisableTiming)); }
+        if (q->pin_used[b]) HIPCHK (hipEventSynchronize (q->pin_ev[b]));   // (the one wait of a push: this buffer's copy of two parts ago)
+        memcpy (q->pin[b], (const char *) h_text + at_byte, part);
+        HIPCHK (hipMemcpyAsync ((char *) q->text.p + at_byte, q->pin[b], part, hipMemcpyHostToDevice, c->stream));
+        HIPCHK (hipEventRecord (q->pin_ev[b], c->stream));
+        q->pin_used[b] = true; q->pin_next = b ^ 1;
+      }
+    }
+  }
+  return tjamd_fastq_push_device (c, n_bytes ? q->text.p : nullptr, n_bytes, final);
+}
+
+extern "C" long tjamd_fastq_end (tjamd_counter *c)
+{
+  static const char *fn = "tjamd_fastq_end";
+  int rc = fastq_enter (fn, c, nullptr, 0, false, 0);
+  if (rc) return -rc;
+  FastqSession *q = c->fq;
+  if (!q || !q->open) return -set_err (TJAMD_ERR_ARG, "%s: TJAMD_ERR_ARG: no session is open on this counter", fn);
+  if (q->m >= 0 && q->stream_bound > 0 && (rc = fastq_push (c, nullptr, 0, 0, true))) return -rc;   // (the stream that has not gone to the scan yet)
+  q->open = false;
+  FqState h;
+  static_assert (sizeof (FqState) % 4 == 0, "read back in words");
+  rc = read_back (c, fn, q->state.p, &h, sizeof (FqState) / 4);
+  if (rc) return -rc;
+  q->consumed = (long) h.consumed; q->reads = (long) h.reads; q->stream_bytes = (long) h.stream_total;
+  q->stop = h.stop ? (int) h.stop : (h.tail_len ? 1 : 0);
+  q->kept = q->m < 0; q->ended = true;
+  (void) __atomic_add_fetch (&g_fastq_sessions, 1, __ATOMIC_RELAXED);
+  double ms = 0.0;
+  for (long i = 0; i < q->n_push && i < FQ_TIMED_PUSHES; i++) { float f = 0.f; if (hipEventElapsedTime (&f, q->ev[2 * i], q->ev[2 * i + 1]) != hipSuccess) { ms = -1.0; break; } ms += (double) f; }
+  q->ms = q->n_push > FQ_TIMED_PUSHES ? -1.0 : ms;
+  (void) hipGetLastError ();
+  return q->consumed;
+}
+
+extern "C" long tjamd_fastq_reads (const tjamd_counter *c) { return c && c->fq && c->fq->ended ? c->fq->reads : -1; }
+extern "C" int tjamd_fastq_stop (const tjamd_counter *c) { return c && c->fq && c->fq->ended ? c->fq->stop : -1; }
+extern "C" const void *tjamd_fastq_stream (const tjamd_counter *c) { return c && c->fq && c->fq->ended && c->fq->kept ? c->fq->stream.p : nullptr; }
+extern "C" long tjamd_fastq_stream_bytes (const tjamd_counter *c) { return c && c->fq && c->fq->ended ? c->fq->stream_bytes : -1; }
+extern "C" double tjamd_last_fastq_ms (tjamd_counter *c) { return c && c != g_fastq_refused && c->fq && c->fq->ended ? c->fq->ms : -1.0; }

@@ -15,6 +15,8 @@
 #include <sched.h>
 #include <sys/stat.h>
 #include <unistd.h>
+#include <fcntl.h>
+#include <sys/mman.h>
 #include "fastq_reader.h"
 #include "feeder.h"
 #include "tj_inflate.h"
@@ -25,6 +27,7 @@
 #include <stdarg.h>
 #include <limits.h>
 
+int tj_fastq_seen_stop (tjamd_counter *c);          /* hopo_device.hip: 1 once a look-back of the open session says it has stopped */
 void tj_set_last_error (const char *msg);            /* hopo_device.hip: what tjamd_last_error () returns */
 
 /* ---- tables (reference: src/hopo_counter.c:10-11,205-216; constant here, so no lazy-initialisation race) -------- */
@@ -248,17 +251,157 @@ tj_feeder_threads (const tatajuba_options_t *opt)
 
 /* ---- file -> device (reference: src/hopo_counter.c:135-157) -------------------------------------------------------- */
 
-hopo_counter
-new_or_append_hopo_counter_from_file (hopo_counter hc, const char *filename, tatajuba_options_t opt)
+/* the records of an open reader, from where it stands to its end, through two pinned batch buffers into the scan; returns
+ * the counter's raw records (the stream has been waited for) */
+static long
+tj_scan_records (tjr_reader *rd, tjamd_counter *dev, int min_tract_size)
 {
-  hopo_counter h = hc;
-  tjamd_counter *dev;
-  tjr_reader *rd;
   unsigned char *buf[2] = {NULL, NULL};
   size_t fill = 0;
   int cur = 0, in_flight = 0;
   long len, n;
   const char *seq;
+  buf[0] = (unsigned char *) tj_pinned_get (TJ_BATCH_BYTES);
+  buf[1] = (unsigned char *) tj_pinned_get (TJ_BATCH_BYTES);
+  if (!buf[0] || !buf[1]) tj_fatal ("%s", tjamd_last_error ());
+
+  while ((len = tjr_next (rd, &seq)) >= 0) {           /* -2 (bad quality string) ends the file silently, as in the reference */
+    if ((size_t) len + 1 > TJ_BATCH_BYTES) {            /* one read larger than a batch: send it on its own */
+      unsigned char *big = (unsigned char *) malloc ((size_t) len + 1);
+      memcpy (big, seq, (size_t) len); big[len] = '\n';
+      if (fill) { if (tjamd_scan_host (dev, buf[cur], fill, min_tract_size)) tj_fatal ("%s", tjamd_last_error ()); fill = 0; }
+      if (tjamd_scan_host (dev, big, (size_t) len + 1, min_tract_size) || tjamd_sync (dev)) tj_fatal ("%s", tjamd_last_error ());
+      free (big);
+      in_flight = 0;
+      continue;
+    }
+    if (fill + (size_t) len + 1 > TJ_BATCH_BYTES) {     /* batch full: queue copy + scan, parse on into the other buffer */
+      if (in_flight && tjamd_raw_count (dev) < 0) tj_fatal ("%s", tjamd_last_error ()); /* the other buffer's copy must be done (+ exact counts: see tj_sink_sync) */
+      if (tjamd_scan_host (dev, buf[cur], fill, min_tract_size)) tj_fatal ("%s", tjamd_last_error ());
+      in_flight = 1; cur ^= 1; fill = 0;
+    }
+    memcpy (buf[cur] + fill, seq, (size_t) len);
+    buf[cur][fill + (size_t) len] = '\n';
+    fill += (size_t) len + 1;
+  }
+  if (fill && tjamd_scan_host (dev, buf[cur], fill, min_tract_size)) tj_fatal ("%s", tjamd_last_error ());
+  n = tjamd_raw_count (dev);                            /* synchronises the stream */
+  if (n < 0) tj_fatal ("%s", tjamd_last_error ());
+  tj_pinned_put (buf[0]); tj_pinned_put (buf[1]);
+  return n;
+}
+
+/* TATAJUBA_AMD_FASTQ_PARSE=device: a plain file's bytes go to the device as they lie and are parsed there (tjamd_fastq_*).
+ * The file is mapped; its pieces (TATAJUBA_AMD_FASTQ_PIECE bytes, 64 MiB by default) are copied by the feeder threads, a
+ * slice each, into one of TJ_FQ_BUFS pinned buffers and pushed from there, so that up to TJ_FQ_BUFS pieces are on their
+ * way while the next one is copied; nobody on the host looks at a byte.  Once the session is known to have stopped (asked
+ * without waiting, when a buffer comes free) no further piece is copied or sent.  What the device leaves (FASTA, wrapped or CRLF
+ * records, a damaged one: from the first irregular record on) the ordinary reader takes from that offset of the mapping, on
+ * the same counter.  Returns the counter's raw records, or -1 if the file cannot be opened or mapped (the ordinary path
+ * then reports it). */
+#define TJ_FQ_BUFS 3
+#define TJ_FQ_PIECE (64l << 20)
+
+typedef struct
+{
+  pthread_barrier_t go, done;
+  const unsigned char *src;
+  unsigned char *dst;
+  size_t len;
+  int n_threads, quit;
+} tj_fq_copy;
+typedef struct { tj_fq_copy *job; int index; } tj_fq_worker;
+
+static void
+tj_fq_copy_slice (const tj_fq_copy *job, int index)
+{
+  const size_t per = (job->len + (size_t) job->n_threads - 1) / (size_t) job->n_threads, from = per * (size_t) index;
+  if (from < job->len) memcpy (job->dst + from, job->src + from, job->len - from < per ? job->len - from : per);
+}
+
+static void *
+tj_fq_copy_thread (void *arg)
+{
+  tj_fq_worker *w = (tj_fq_worker *) arg;
+  for (;;) {
+    pthread_barrier_wait (&w->job->go);
+    if (w->job->quit) return NULL;
+    tj_fq_copy_slice (w->job, w->index);
+    pthread_barrier_wait (&w->job->done);
+  }
+}
+
+static long
+tj_fastq_from_device_parse (hopo_counter h, const char *filename, tatajuba_options_t opt, int threads)
+{
+  tjamd_counter *dev;
+  struct stat st;
+  const char *e = getenv ("TATAJUBA_AMD_FASTQ_PIECE");
+  size_t piece = (e && atol (e) >= 16) ? (size_t) atol (e) : (size_t) TJ_FQ_PIECE, size, at;
+  unsigned char *map, *buf[TJ_FQ_BUFS];
+  long mark[TJ_FQ_BUFS], consumed, n;
+  pthread_t tid[TJF_MAX_THREADS];
+  tj_fq_worker worker[TJF_MAX_THREADS];
+  tj_fq_copy job;
+  int fd = open (filename, O_RDONLY), i, b = 0;
+  if (fd < 0) return -1;
+  if (fstat (fd, &st) != 0 || st.st_size <= 0) { close (fd); return -1; }
+  size = (size_t) st.st_size;
+  map = (unsigned char *) mmap (NULL, size, PROT_READ, MAP_PRIVATE, fd, 0);
+  close (fd);
+  if (map == MAP_FAILED) return -1;
+  if (piece > (1ul << 30)) piece = 1ul << 30;
+  if (piece > size) piece = (size + 15) & ~(size_t) 15;
+  dev = tj_device_counter (h);
+  for (i = 0; i < TJ_FQ_BUFS; i++) { buf[i] = (unsigned char *) tj_pinned_get (piece); mark[i] = -1; if (!buf[i]) tj_fatal ("out of pinned host memory for the pieces of '%s'", filename); }
+  if (threads < 1) threads = 1;
+  if (threads > TJF_MAX_THREADS) threads = TJF_MAX_THREADS;
+  job.n_threads = threads; job.quit = 0;
+  pthread_barrier_init (&job.go, NULL, (unsigned) threads); pthread_barrier_init (&job.done, NULL, (unsigned) threads);
+  for (i = 1; i < threads; i++) {
+    worker[i].job = &job; worker[i].index = i;
+    if (pthread_create (&tid[i], NULL, tj_fq_copy_thread, &worker[i])) tj_fatal ("cannot start a feeder thread");
+  }
+  (void) tjamd_reserve (dev, size / 2, opt.min_tract_size);
+  if (tjamd_fastq_begin (dev, opt.min_tract_size)) tj_fatal ("%s", tjamd_last_error ());
+  for (at = 0; at < size; at += piece, b = (b + 1) % TJ_FQ_BUFS) {
+    const size_t len = size - at < piece ? size - at : piece;
+    if (mark[b] >= 0 && tjamd_wait_mark (dev, (int) mark[b])) tj_fatal ("%s", tjamd_last_error ());   /* this buffer's piece of three pieces ago has left it */
+    if (mark[b] >= 0 && tj_fastq_seen_stop (dev)) break;   /* the device has met a record it leaves to the host: no more text for it */
+    job.src = map + at; job.dst = buf[b]; job.len = len;
+    pthread_barrier_wait (&job.go);
+    tj_fq_copy_slice (&job, 0);
+    pthread_barrier_wait (&job.done);
+    if (tjamd_fastq_push_host (dev, buf[b], len, at + len == size)) tj_fatal ("%s", tjamd_last_error ());
+    mark[b] = tjamd_mark (dev);
+    if (mark[b] < 0) tj_fatal ("%s", tjamd_last_error ());
+  }
+  job.quit = 1;
+  pthread_barrier_wait (&job.go);
+  for (i = 1; i < threads; i++) pthread_join (tid[i], NULL);
+  pthread_barrier_destroy (&job.go); pthread_barrier_destroy (&job.done);
+  consumed = tjamd_fastq_end (dev);
+  if (consumed < 0) tj_fatal ("%s", tjamd_last_error ());
+  for (i = 0; i < TJ_FQ_BUFS; i++) tj_pinned_put (buf[i]);
+  if ((size_t) consumed < size) {                       /* the rest is the ordinary reader's, from the first record the device left */
+    tjr_reader *rd = tjr_open_mem (map, size, (size_t) consumed);
+    n = tj_scan_records (rd, dev, opt.min_tract_size);
+    tjr_close (rd);
+  }
+  else {
+    n = tjamd_raw_count (dev);
+    if (n < 0) tj_fatal ("%s", tjamd_last_error ());
+  }
+  munmap (map, size);
+  return n;
+}
+
+hopo_counter
+new_or_append_hopo_counter_from_file (hopo_counter hc, const char *filename, tatajuba_options_t opt)
+{
+  hopo_counter h = hc;
+  tjr_reader *rd;
+  long n;
 
   if (!h) {
     h = new_hopo_counter (opt.kmer_size);
@@ -267,6 +410,15 @@ new_or_append_hopo_counter_from_file (hopo_counter hc, const char *filename, tat
     h->opt = opt;
   }
   if (h->idx_initial) tj_fatal ("This counter has been compared to another; cannot add more reads to it"); /* reference :152 */
+  {                                                     /* opt-in: a plain file parsed on the device (unset or "host": everything below, as ever) */
+    const char *where = getenv ("TATAJUBA_AMD_FASTQ_PARSE");
+    if (where && !strcmp (where, "device") && tjf_is_plain_file (filename) == 1 &&
+        (n = tj_fastq_from_device_parse (h, filename, opt, tj_feeder_threads (&opt))) >= 0) {
+      tj_priv (h)->n_device = n;
+      h->n_elem = tj_n_elem (tj_priv (h)->n_host, n, h->name);
+      return h;
+    }
+  }
   {                                                     /* big file: several readers / inflaters (feeder.c), same output */
     struct stat st;
     int threads;
@@ -299,35 +451,8 @@ new_or_append_hopo_counter_from_file (hopo_counter hc, const char *filename, tat
   }
   rd = tjr_open (filename);
   if (!rd) tj_fatal ("cannot open '%s' (the reference leaves gzopen unchecked, src/hopo_counter.c:142; this build stops)", filename);
-  dev = tj_device_counter (h);
-  buf[0] = (unsigned char *) tj_pinned_get (TJ_BATCH_BYTES);
-  buf[1] = (unsigned char *) tj_pinned_get (TJ_BATCH_BYTES);
-  if (!buf[0] || !buf[1]) tj_fatal ("%s", tjamd_last_error ());
-
-  while ((len = tjr_next (rd, &seq)) >= 0) {           /* -2 (bad quality string) ends the file silently, as in the reference */
-    if ((size_t) len + 1 > TJ_BATCH_BYTES) {            /* one read larger than a batch: send it on its own */
-      unsigned char *big = (unsigned char *) malloc ((size_t) len + 1);
-      memcpy (big, seq, (size_t) len); big[len] = '\n';
-      if (fill) { if (tjamd_scan_host (dev, buf[cur], fill, opt.min_tract_size)) tj_fatal ("%s", tjamd_last_error ()); fill = 0; }
-      if (tjamd_scan_host (dev, big, (size_t) len + 1, opt.min_tract_size) || tjamd_sync (dev)) tj_fatal ("%s", tjamd_last_error ());
-      free (big);
-      in_flight = 0;
-      continue;
-    }
-    if (fill + (size_t) len + 1 > TJ_BATCH_BYTES) {     /* batch full: queue copy + scan, parse on into the other buffer */
-      if (in_flight && tjamd_raw_count (dev) < 0) tj_fatal ("%s", tjamd_last_error ()); /* the other buffer's copy must be done (+ exact counts: see tj_sink_sync) */
-      if (tjamd_scan_host (dev, buf[cur], fill, opt.min_tract_size)) tj_fatal ("%s", tjamd_last_error ());
-      in_flight = 1; cur ^= 1; fill = 0;
-    }
-    memcpy (buf[cur] + fill, seq, (size_t) len);
-    buf[cur][fill + (size_t) len] = '\n';
-    fill += (size_t) len + 1;
-  }
-  if (fill && tjamd_scan_host (dev, buf[cur], fill, opt.min_tract_size)) tj_fatal ("%s", tjamd_last_error ());
+  n = tj_scan_records (rd, tj_device_counter (h), opt.min_tract_size);
   tjr_close (rd);
-  n = tjamd_raw_count (dev);                            /* synchronises the stream */
-  if (n < 0) tj_fatal ("%s", tjamd_last_error ());
-  tj_pinned_put (buf[0]); tj_pinned_put (buf[1]);
   tj_priv (h)->n_device = n;
   h->n_elem = tj_n_elem (tj_priv (h)->n_host, n, h->name);
   return h;
